@@ -19,6 +19,11 @@ scaling -- the SAME corpus and the same query batches.  No rank ever holds the c
 sums, rows shipped to the owners of their lists with one all-to-all), the inverted lists end up sharded by cluster
 (LPT by list length); per batch every rank runs the replicated coarse quantiser and scans only its lists, partial
 top-k are exchanged with ONE RCCL all-gather and merged on every rank.
+
+A plain run does only what the headline needs: set-up (corpus + build_index), warm-up, the timed steps, the line.  Every other
+leg -- recall and self-retrieval checks, the roofline pass with one batch in flight, the coarse contraction, CPU baselines, other
+sizes and configurations, one rank's nominal share of cfg4 / cfg5 -- runs with `--full` (the --no-* options drop some of them).
+`--dump-outputs DIR` writes the last timed step's results (ids, distances, counts) as DIR/<name>.npy.
 """
 from __future__ import annotations
 
@@ -35,6 +40,7 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak (MI355X_MICROARCH.md); 6290 GB/s is the measured copy ceiling
+SUB_INDEX_BYTES = 16e9  # host memory the all-cores CPU leg may fill with prepared sub-indexes before it stops adding queries
 
 
 def log(*a):
@@ -42,6 +48,18 @@ def log(*a):
 
 
 from benchlib.line import LINE_LIMIT, compact_line, emit  # noqa: E402,F401  (the ONE stdout line: contract keys + numbers; everything else to a side file / stderr)
+from benchlib.dump import dump_outputs  # noqa: E402
+
+
+def host_cpus() -> int:
+    """CPUs this process may use: its affinity mask, capped by OMP_NUM_THREADS where the environment sets a budget.  (A pool sized by
+    the machine's CPU count on a shared host only queues behind itself, and the all-cores CPU leg holds one sub-index per thread's query.)"""
+    n = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
+    try:
+        n = min(n, int(os.environ.get("OMP_NUM_THREADS", n)))
+    except ValueError:
+        pass
+    return max(1, n)
 
 
 def main():
@@ -69,7 +87,14 @@ def main():
                     "another; every step's work is inside the timed region (1 = strictly one batch after the other)")
     ap.add_argument("--ahead", action="store_true", help="compute the next batch's coarse quantiser on a side stream under the current "
                     "list scan (vers_ivf_coarse_ahead_dev; same-box A/B at cfg3: +0.8 %% -- the scan already fills the chip)")
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also run every other leg: recall and self-retrieval checks, "
+                    "the roofline pass with one batch in flight, the coarse contraction, CPU baselines, other sizes and configurations "
+                    "(without it the --no-* options have nothing to drop)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's ids, distances and counts as "
+                    "DIR/<name>.npy (float64 / float32 / float64)")
     args = ap.parse_args()
+    if not args.full:   # a plain run: set-up, warm-up, the timed steps and the line -- nothing else
+        args.no_cpu = args.no_recall = args.no_extra = args.no_nominal = True
     if args.f32_rows:
         os.environ["VERS_SHADOW"] = "0"   # (read once by the library when it loads; the ranks inherit it)
 
@@ -287,8 +312,13 @@ def main():
     elapsed = time.perf_counter() - t0
     for x in streams:
         index.poll(x.cuda_stream)  # NaN / insufficient latch -> raises
-    last_o = outs[(args.warmup + args.steps - 1) % S]   # the results of the last timed batch (recall, CPU comparison)
+    last_o = outs[(args.warmup + args.steps - 1) % S]   # the results of the last timed batch (recall, CPU comparison, --dump-outputs)
     ids, dst, cnt = last_o["ids"], last_o["dst"], last_o["cnt"]
+    ids_i64 = ids.cpu().numpy(); dst_h = dst.cpu().numpy(); cnt_h = cnt.cpu().numpy()
+    ids_h = ids_i64.astype(np.uint64)
+    if rank == 0 and args.dump_outputs:
+        written = dump_outputs(args.dump_outputs, {"ids": ids_i64, "distances": dst_h, "counts": cnt_h})
+        log(f"[bench] last timed step's outputs -> {args.dump_outputs}: {', '.join(written)}")
     ls = index.last_scan()
     scan_ms = index.scan_times(reset=True)
     if dist is not None:
@@ -297,7 +327,7 @@ def main():
         elapsed = float(t.item())
     qps = args.steps * B / elapsed
     scan_ms_one = None
-    if multi and S > 1:
+    if multi and S > 1 and args.full:
         # every rank: the same steps one batch after the other -- the dominant kernel's duration without the queueing behind other
         # batches' scans that an event pair measures when several are in flight (see the one-GPU leg below)
         for i in range(args.warmup):
@@ -360,16 +390,26 @@ def main():
                 "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic,
                 "traffic_source": traffic_source, "algorithmic_bytes_per_launch": int(algo_bytes), "streamed_bytes_per_launch": int(streamed),
                 "row_operand": "fp16 shadow of the rows, 2 B/element (results are the exact f32 bits)" if shadow else "f32 rows",
-                "launch_ms": round(scan_mean_ms, 4), "launches_timed": int(len(scan_ms)), "work_items": int(ls["items"])}
+                "launch_ms": round(scan_mean_ms, 4), "launches_timed": int(len(scan_ms)), "work_items": int(ls["items"]),
+                "measured_on": f"event pairs around the launches of the timed region, {S} batch(es) in flight"}
     if shadow:
         roofline["f32_rows_equivalent"] = {"bytes_per_launch": int(f32_bytes), "GBs": round(f32_bytes / (scan_mean_ms * 1e-3) / 1e9, 1),
                                            "frac_of_peak": round(f32_bytes / (scan_mean_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
                                            "note": "SURVEY 8d's f32 bytes of the same union of lists over this launch time: above 1 because the kernel reads the half-size shadow instead"}
+    if S > 1 and not args.full:
+        # With several batches in flight an event pair around a launch also measures its wait behind another batch's scan; the kernel's
+        # own time comes from the one-batch-in-flight pass of --full.  A plain run gives the timed region's figure under its own name only.
+        roofline["timed_region"] = {"launch_ms": roofline["launch_ms"], "achieved": roofline["achieved"], "frac": roofline["frac"], "launches_timed": roofline["launches_timed"],
+                                    "note": f"event pairs around the launches of the timed region, {S} batches in flight: includes the time a launch waits for the CUs "
+                                            f"another batch's scan still holds"}
+        roofline.update({"launch_ms": None, "achieved": None, "frac": None, "launches_timed": None,
+                         "measured_on": "not measured: the kernel's own launch time needs the one-batch-in-flight pass of --full"})
+        if shadow:
+            roofline["f32_rows_equivalent"].update({"GBs": None, "frac_of_peak": None})
 
     # ---- recall@10 against the exact scan (utils::search_exhaustive over the same values) --------------
     last = args.warmup + args.steps - 1
     recall = None
-    ids_h = ids.cpu().numpy().astype(np.uint64); dst_h = dst.cpu().numpy(); cnt_h = cnt.cpu().numpy()
     if not args.no_recall:
         nq_r = min(B, 1024)
         eids = torch.zeros(nq_r, top_k, dtype=torch.int64, device=dev)
@@ -398,7 +438,7 @@ def main():
     # a stored row queried bit-identically comes back first at distance exactly 0.0 (assign and search use the same
     # symmetric ordered distance and the same first-minimum rule: ivfflat.rs:36-43 vs :159-160)
     self_ok = None
-    if not multi:
+    if not multi and args.full:
         own = [c for c in range(0, nlist, max(1, nlist // 8)) if lens[c] > 0][:8]
         rows_ids = [index.get_list(c) for c in own]
         sq = np.stack([r[0][len(r[1]) // 2] for r in rows_ids]); sid = np.array([r[1][len(r[1]) // 2] for r in rows_ids])
@@ -483,7 +523,7 @@ def main():
         if ke:
             extra["kmeans_assign_k65536"] = ke
             log(f"[bench] k-means at k=65536 (N={nk}): build {tk:.2f} s, contraction {ke['algorithmic_tflops']} algorithmic TFLOP/s, {ke['points_redone_exactly_pct']} % re-done exactly")
-    if rank == 0:
+    if rank == 0 and args.full:
         # the batched coarse quantiser's contraction, queries x centroids [B x d].[d x nlist]: the production kernel (three bf16
         # MFMA products of hi/lo-split operands) as timed in the last step, and the f32 MFMA kernel on the same batch (same
         # results: both are pre-filters behind the exact re-score + certificate) -- north_star's "MFMA utilisation on the
@@ -542,7 +582,7 @@ def main():
         roofline.update({"launch_ms": round(m1, 4), "achieved": round(algo_bytes / (m1 * 1e-3) / 1e9, 1), "frac": round(algo_bytes / (m1 * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
                          "launches_timed": int(len(scan_ms_one[0])), "measured_on": f"the same {args.steps} steps, one batch in flight, right after the timed region (rank 0's launches)"})
         roofline["one_batch_in_flight"] = {"whole_step_ms": round(scan_ms_one[1] / args.steps * 1e3, 4), "whole_step_queries_per_sec": round(args.steps * B / scan_ms_one[1], 1)}
-    if rank == 0 and not multi and S > 1:
+    if rank == 0 and not multi and S > 1 and args.full:
         # With several batches in flight an event pair around a list-scan launch also measures how long the launch QUEUED behind
         # another batch's scan (two scans cannot share the chip: each block takes a whole CU) -- not the kernel.  The roofline of the
         # dominant kernel is therefore taken from the same steps run one batch after the other (--streams 1) right after the
@@ -977,7 +1017,7 @@ def main():
                "gpu_matches_cpu_bitwise": mismatches == 0, "mismatching_queries": mismatches}
         log(f"[bench] cpu baseline {cpu['value']} q/s on 1 core over {n_cpu} queries; GPU==CPU bitwise: {mismatches == 0}")
         # all host cores, one query per thread (the C call releases the GIL)
-        cores = os.cpu_count() or 1
+        cores = host_cpus()
         model = ""
         try:
             model = next(l.split(":", 1)[1].strip() for l in open("/proc/cpuinfo") if l.startswith("model name"))
@@ -989,7 +1029,12 @@ def main():
         if n_par > 0:
             pick = [(n_cpu + i) % B for i in range(n_par)]  # further queries of the batch (wrapping around on small batches)
             qs = [np.ascontiguousarray(qh[i]) for i in pick]
-            subs = [sub_index(q) for q in qs]                                   # (not timed)
+            subs, held = [], 0                                                  # (not timed; each holds its query's probed rows: ~240 MB at cfg3)
+            for q in qs:
+                if subs and held > SUB_INDEX_BYTES:
+                    break
+                subs.append(sub_index(q)); held += subs[-1][0].nbytes
+            n_par = len(subs); pick, qs = pick[:n_par], qs[:n_par]
             t0 = time.perf_counter()
             with ThreadPoolExecutor(max_workers=cores) as ex:
                 res = list(ex.map(lambda a: run_one(*a), zip(qs, subs)))

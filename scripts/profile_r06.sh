@@ -35,12 +35,12 @@ OUT_JSON=$OUT/shard_all_ranks.json
 ( cd "$ROOT" && python3 scripts/rank_nominal.py cfg4 NLIST=4096 OUT=$OUT/cfg4_rank_nlist4096.json > "$OUT/cfg4_rank_nlist4096.log" 2>&1 )
 ( cd "$ROOT" && python3 scripts/rank_nominal.py cfg5 OUT=$OUT/cfg5_rank.json > "$OUT/cfg5_rank.log" 2>&1 )
 run cfg3/trace "" "$ROOT/bench.py" $B3                                  # (clean: ONLY the timed configuration's launches -- ADVICE r04)
-run cfg3x/trace "" "$ROOT/bench.py" --streams 1 --steps 20 --warmup 5 --no-cpu --no-recall --no-nominal   # (the extras' kernels: f32 coarse contraction, f32-row scan, ... in their own pass)
+run cfg3x/trace "" "$ROOT/bench.py" --full --streams 1 --steps 20 --warmup 5 --no-cpu --no-recall --no-nominal   # (the extras' kernels: f32 coarse contraction, f32-row scan, ... in their own pass)
 run cfg3/pmc_fetch "FETCH_SIZE" "$ROOT/bench.py" $B3
 run cfg3/pmc_write "WRITE_SIZE" "$ROOT/bench.py" $B3
-run cfg3/pmc_mfma "SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU_MFMA_MOPS_F32 SQ_WAVES SQ_WAVE_CYCLES GRBM_GUI_ACTIVE" "$ROOT/bench.py" --streams 1 --steps 20 --warmup 5 --no-cpu --no-recall --no-nominal
+run cfg3/pmc_mfma "SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU_MFMA_MOPS_F32 SQ_WAVES SQ_WAVE_CYCLES GRBM_GUI_ACTIVE" "$ROOT/bench.py" --full --streams 1 --steps 20 --warmup 5 --no-cpu --no-recall --no-nominal
 run cfg3/pmc_sq "SQ_WAVES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_ACTIVE_INST_VALU SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_LDS" "$ROOT/bench.py" $B3
-run cfg3_s3/trace "" "$ROOT/bench.py" --steps 20 --warmup 5 --no-cpu --no-recall --no-extra
+run cfg3_s3/trace "" "$ROOT/bench.py" --full --steps 20 --warmup 5 --no-cpu --no-recall --no-extra   # (--full: the one-batch pass after the timed region)
 run b1/trace "" "$ROOT/bench.py" $B1
 run b1/pmc_fetch "FETCH_SIZE" "$ROOT/bench.py" $B1
 run flat/trace "" "$ROOT/scripts/bench_flat.py"

@@ -74,7 +74,7 @@ f3, n3 = mean_of(pmc("cfg3/pmc_fetch"), PK, "FETCH_SIZE", 5, 25)   # (the 20 tim
 w3, _ = mean_of(pmc("cfg3/pmc_write"), PK, "WRITE_SIZE", 5, 25)
 pk = [v for k, v in a3.items() if PK in k]
 if pk and f3:
-    d = pk[0][5:25]   # the 20 TIMED launches (5 warm-up before them; behind them the run's self-retrieval check -- a batch of 8 -- and its result read-backs)
+    d = pk[0][5:25]   # the 20 TIMED launches (5 warm-up before them; nothing behind them: profile_r06.sh runs a plain bench here)
     print(f"{PK}...>: mean {sum(d)/len(d):.1f} us over the {len(d)} timed dispatches (min {min(d):.1f}); FETCH_SIZE mean {f3:.0f} KB over {n3} "
           f"dispatches -> HBM read bytes per launch = FETCH_SIZE * 1024 * 2 = {f3*1024*2:.4g}; WRITE_SIZE mean {w3 or 0:.0f} KB")
     facts["cfg3"] = {"kernel": short([k for k in a3 if PK in k][0]).split("(")[0].replace("void ", "") + (" (fp16 shadow rows)" if "true" in PK else " (f32 rows)"), "config": {"rows": 10000000, "d": 768, "nlist": 4096, "nprobe": 32, "batch": 1024},

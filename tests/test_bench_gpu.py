@@ -36,7 +36,7 @@ def run_bench(*extra, env=None, full=False):
 
 
 def test_bench_single_gpu_line():
-    line, out, _ = run_bench("--cpu-seconds", "2", full=True)
+    line, out, _ = run_bench("--full", "--cpu-seconds", "2", full=True)
     assert line["n_gpus"] == 1 and line["unit"] == "queries/sec" and line["value"] > 0 and line["value"] == out["value"]
     rf = line["roofline"]
     assert rf["bound"] == "hbm" and 0 < rf["frac"] < 1.5 and rf["peak"] == 8000.0 and rf["unit"] == "GB/s" and rf["achieved"] > 0
@@ -68,9 +68,39 @@ def test_bench_single_gpu_line():
     assert ex["coarse_gemm"]["us"] > 0 and ex["coarse_gemm_f32"]["us"] > 0 and ex["single_query"]["end_to_end_us"] > 0
 
 
+def test_bench_plain_run_is_lean_and_dumps_its_last_timed_step(tmp_path):
+    """Without --full: set-up, warm-up, the timed steps and the line -- no check or leg of its own.  --dump-outputs writes what the
+    last timed step returned: the CPU restatement's answer for that batch (step warmup + steps - 1 = 2 of the run's 3 query batches)."""
+    import numpy as np
+    from oracle import c_oracle as co
+    from tests import datagen as dg
+    dump = tmp_path / "dump"
+    line, out, _ = run_bench("--dump-outputs", str(dump), full=True)
+    assert line["steps"] == 2 and line["warmup"] == 1 and line["ms_per_step"] > 0 and line["value"] > 0
+    assert line["recall_at_10"] is None and line["self_retrieval_ok"] is None and line["cpu_baseline"] is None
+    assert set(line["extra"]) <= {"memory", "build_index_s", "kmeans_assign"}, sorted(line["extra"])   # (figures of the set-up itself)
+    assert "one_batch_in_flight" not in out["roofline"] and "coarse_gemm" not in out["extra"]
+    # 3 batches in flight: the kernel's own launch time needs --full's one-batch pass; the queue-inclusive figure is named as such
+    assert line["roofline"]["frac"] is None and line["roofline"]["launch_ms"] is None and line["roofline"]["timed_region_launch_ms"] > 0
+    assert sorted(os.listdir(dump)) == ["counts.npy", "distances.npy", "ids.npy"]
+    ids, dst, cnt = (np.load(dump / f) for f in ("ids.npy", "distances.npy", "counts.npy"))
+    assert ids.dtype == np.float64 and dst.dtype == np.float32 and cnt.dtype == np.float64
+    assert ids.shape == dst.shape == (64, 10) and cnt.shape == (64,)
+    n, d, nlist, nprobe, B, k = 20000, 64, 16, 4, 64, 10          # SMALL; bench.py's seeds, 16 modes per list, 4 k-means iterations
+    sigma, modes = dg.default_sigma(d), 16 * nlist
+    X = dg.dist_c(0x5EED0001, n, d, modes, sigma, seed_c=0x5EEDC0DE)
+    init = (dg.mix64(np.uint64(0xB01D) + np.arange(nlist, dtype=np.uint64)) % np.uint64(n)).astype(np.uint64)
+    ob = co.build_index(X, nlist, 1, 4, init)
+    Q = dg.dist_c(0x5EED0002, B, d, modes, sigma, seed_c=0x5EEDC0DE, start=2 * B)
+    for qi in range(B):
+        oi, od = co.search_nprobe(X, ob["centroids"], ob["ids"], Q[qi], k, nprobe)
+        assert cnt[qi] == len(oi) and np.array_equal(ids[qi, :len(oi)], oi.astype(np.float64)), qi
+        assert np.array_equal(dst[qi, :len(od)].view(np.uint32), od.view(np.uint32)), qi
+
+
 def test_bench_gpus_2_spawns_ranks_and_builds_row_sharded():
-    one, _ = run_bench("--no-cpu", "--no-extra")
-    two, err = run_bench("--gpus", "2", "--no-cpu", "--no-extra", env={"VERS_BENCH_BACKEND": "gloo"})
+    one, _ = run_bench("--full", "--no-cpu", "--no-extra")
+    two, err = run_bench("--gpus", "2", "--full", "--no-cpu", "--no-extra", env={"VERS_BENCH_BACKEND": "gloo"})
     assert two["n_gpus"] == 2
     assert "row-sharded build over 2 ranks: 10000 rows generated per rank" in err
     assert two["recall_at_10"] == one["recall_at_10"]
@@ -83,8 +113,8 @@ def test_bench_multi_rank_path_through_rccl_with_one_rank():
     build entry, libvers_rccl.so's communicator made from an id broadcast through torch.distributed, vers_ivf_search_sharded_dev
     with ncclAllGather queued on the batch's stream, three batches in flight -- with the ONE rank a test box has (RCCL refuses
     two ranks on one GPU).  Same recall as the plain single-GPU run."""
-    one, _ = run_bench("--no-cpu", "--no-extra")
-    rc, err = run_bench("--no-cpu", "--no-extra", env={"VERS_BENCH_FORCE_SHARDED": "1"})
+    one, _ = run_bench("--full", "--no-cpu", "--no-extra")
+    rc, err = run_bench("--full", "--no-cpu", "--no-extra", env={"VERS_BENCH_FORCE_SHARDED": "1"})
     assert rc["n_gpus"] == 1 and rc["recall_at_10"] == one["recall_at_10"] and rc["value"] > 0
     assert rc["config"]["exchange"] == "rccl_allgather_inside_search_sharded_dev", rc["config"]["exchange"]
     assert "libvers_rccl.so" in err
@@ -95,7 +125,7 @@ def test_bench_gpus_8_over_gloo_on_one_gpu():
     """world 8 -- the size the driver's scaling run ends at -- through every rank-count-dependent piece of the run (LPT over 8
     owners, the row-sharded build's chain of 7 hops, partials of 8 ranks merged per batch) with the eight ranks sharing the test
     box's GPU over gloo; same recall as one rank."""
-    one, _ = run_bench("--no-cpu", "--no-extra")
-    eight, err = run_bench("--gpus", "8", "--no-cpu", "--no-extra", env={"VERS_BENCH_BACKEND": "gloo"})
+    one, _ = run_bench("--full", "--no-cpu", "--no-extra")
+    eight, err = run_bench("--gpus", "8", "--full", "--no-cpu", "--no-extra", env={"VERS_BENCH_BACKEND": "gloo"})
     assert eight["n_gpus"] == 8 and eight["recall_at_10"] == one["recall_at_10"]
     assert "lists sharded over 8 ranks (LPT)" in err and eight["config"]["exchange"] == "gloo_gather_inside_search_sharded_dev"

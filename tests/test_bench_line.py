@@ -63,3 +63,18 @@ def test_a_leg_that_failed_or_was_skipped_does_not_break_the_line():
     line = compact_line(full)
     assert line["cpu_baseline"] is None and line["extra"] == {"cfg4_rank": {"failed": True}}
     assert len(json.dumps(line)) < LINE_LIMIT
+
+
+def test_a_plain_run_without_the_kernel_roofline_makes_a_line():
+    """bench.py without --full and several batches in flight: the kernel's own launch time is not measured (it needs the one-batch
+    pass), the timed region's event-pair figure is under roofline.timed_region; no leg, no CPU baseline, no recall."""
+    full = full_result()
+    rf = full["roofline"]
+    rf["timed_region"] = {"launch_ms": 4.5, "achieved": 3150.0, "frac": 0.39, "launches_timed": 20, "note": "queueing included"}
+    rf.update(launch_ms=None, achieved=None, frac=None, launches_timed=None, measured_on="not measured")
+    rf["f32_rows_equivalent"].update(GBs=None, frac_of_peak=None)
+    full.update(extra={}, cpu_baseline=None, cpu_baseline_all_cores=None, cpu_baseline_kmeans=None, recall_at_10=None, self_retrieval_ok=None)
+    full.pop("value_f32_rows", None)
+    line = compact_line(full)
+    assert line["roofline"]["frac"] is None and line["roofline"]["timed_region_launch_ms"] == 4.5 and line["extra"] == {}
+    assert line["value"] == full["value"] and line["ms_per_step"] == full["ms_per_step"] and len(json.dumps(line)) < LINE_LIMIT
