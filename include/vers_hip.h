@@ -123,6 +123,11 @@ int32_t vers_build_stats(double* out8, int32_t reset);
  * + the rows-to-owners exchange), [8] what derives from the stored rows (centroid operands, |x|^2, fp16 shadow, row-major
  * copy), [9] the rest (init draws, convergence tests, read-back).  reset != 0 zeroes them (and vers_build_stats'). */
 int32_t vers_build_phases(double* out10, int32_t reset);
+/* The add_batch calls of this process by PHASE (host wall clock in ms, the stream synchronised at each phase's end).  out[9]:
+ * [0] calls, [1] rows added, [2] re-layouts, [3] staging of the rows (host pack + copy, or the device copy), [4] assignment,
+ * [5] grouping by list, [6] re-layout, [7] placement + length tables, [8] derived arrays (|x|^2, shadow, row-major copy).
+ * reset != 0 zeroes them. */
+int32_t vers_add_batch_phases(double* out9, int32_t reset);
 /* IVFFlatIndex::update_centroids (ivfflat.rs:47-71): per cluster the f32 sum
  * of its members in ascending row order divided by the count; empty cluster
  * -> zero vector.  out_centroids is packed [k * d]. */
@@ -212,6 +217,25 @@ int32_t vers_ivf_upload_end(vers_ivf_t* h);
  * vec_id = assignments.len() (the reference ignores the caller's vec_id, :209) and is appended
  * to that list.  Returns both so the host can mirror values/assignments/ids. */
 int32_t vers_ivf_add(vers_ivf_t* h, const float* row, uint64_t* out_cluster, uint64_t* out_vec_id);
+/* Index::add for n vectors in one call: exactly what n calls of vers_ivf_add with rows[0], rows[1], ... in that order
+ * would leave behind (same clusters, vec ids, list order, stored bits, search results), in one pass over the batch.
+ *   vec ids   : *out_first_vec_id .. *out_first_vec_id + *out_added - 1 (= assignments.len() at the call, ascending);
+ *               each list receives its new rows after its existing ones, in ascending vec id (ivfflat.rs:200-213).
+ *   clusters  : out_clusters[i] = first-minimum centroid of row i in the index's metric (the build's assign pass).
+ *   errors    : the first row with a NaN distance (k >= 2) ends the call with VERS_ERR_NAN; the rows before it are added
+ *               (*out_added = its index), as the loop of single adds would have left them.  k == 1 accepts a NaN row.
+ *               No centroids: VERS_ERR_EMPTY.  n_total + n beyond the u32 vec id space: VERS_ERR_INVALID, nothing added.
+ *               n == 0: no-op.
+ *   rows      : host, row_stride_bytes >= 4 d (a multiple of 4; Vec<Vector<N>>'s 256-byte pitch as it is); streamed through a
+ *               bounded staging buffer (option "add_batch_rows" rows per chunk, default 131072) -- no device copy of the batch.
+ *   _dev      : rows_dev [n][ld_floats], ld_floats >= d a multiple of 4; columns d .. ld_floats-1 may hold anything (never read
+ *               into the index); out_clusters_dev is a device array.
+ * Synchronous; holds the handle exclusively and waits for searches in flight.  Sharded handles (vers_ivf_set_shard): every rank
+ * calls with the same rows and gets the same clusters and vec ids; only a list's owner stores its rows, every rank counts them. */
+int32_t vers_ivf_add_batch(vers_ivf_t* h, const float* rows, uint64_t n, uint64_t row_stride_bytes,
+                           uint64_t* out_clusters /* [n], nullable */, uint64_t* out_first_vec_id, uint64_t* out_added);
+int32_t vers_ivf_add_batch_dev(vers_ivf_t* h, const float* rows_dev, uint64_t n, uint64_t ld_floats,
+                               uint64_t* out_clusters_dev /* [n], nullable */, uint64_t* out_first_vec_id, uint64_t* out_added);
 /* Index::search_approximate (ivfflat.rs:153-198) for b queries.
  *   nprobe == 0 : the reference's semantics -- nearest list, spill into the next-nearest while
  *                 fewer than top_k results; results CONCATENATED per list (not globally sorted);

@@ -56,6 +56,8 @@ SIGNATURES = {
     "vers_ivf_upload_chunk_dev": (C.c_int32, [_vp, _vp, C.c_uint64, _vp, C.c_uint64, C.c_uint64]),
     "vers_ivf_upload_end": (C.c_int32, [_vp]),
     "vers_ivf_add": (C.c_int32, [_vp, _vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "vers_ivf_add_batch": (C.c_int32, [_vp, _vp, C.c_uint64, C.c_uint64, _vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "vers_ivf_add_batch_dev": (C.c_int32, [_vp, _vp, C.c_uint64, C.c_uint64, _vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "vers_ivf_search": (C.c_int32, [_vp, _vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, _vp, _vp, _vp]),
     "vers_ivf_search_dev": (C.c_int32, [_vp, _vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, _vp, _vp, _vp, _vp]),
     "vers_ivf_poll": (C.c_int32, [_vp, _vp]),
@@ -94,6 +96,7 @@ SIGNATURES = {
     "vers_assign_stats": (C.c_int32, [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_int32]),
     "vers_build_stats": (C.c_int32, [C.POINTER(C.c_double), C.c_int32]),
     "vers_build_phases": (C.c_int32, [C.POINTER(C.c_double), C.c_int32]),
+    "vers_add_batch_phases": (C.c_int32, [C.POINTER(C.c_double), C.c_int32]),
     "vers_kmeans_update": (C.c_int32, [C.c_int32, _vp, C.c_uint64, C.c_uint64, _vp, C.c_uint64, C.c_uint32, _vp]),
     "vers_kmeans_cost": (C.c_int32, [C.c_int32, _vp, C.c_uint64, C.c_uint64, _vp, C.c_uint64, C.c_uint64, _vp, C.c_uint32,
                                      C.POINTER(C.c_float)]),
@@ -296,6 +299,14 @@ def build_phases(reset=False) -> dict:
     return dict(zip(keys, (round(float(x), 2) for x in v)))
 
 
+
+
+def add_batch_phases(reset=False) -> dict:
+    """The add_batch calls of this process by phase, host wall clock in ms (vers_add_batch_phases)."""
+    v = (C.c_double * 9)()
+    check(lib().vers_add_batch_phases(v, 1 if reset else 0))
+    keys = ("calls", "rows", "relayouts", "stage_ms", "assign_ms", "group_ms", "relayout_ms", "place_ms", "derive_ms")
+    return dict(zip(keys, (float(x) for x in v)))
 
 
 def set_option(name: str, value: int):

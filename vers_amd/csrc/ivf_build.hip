@@ -216,6 +216,123 @@ __global__ void advance_fill_kernel(const uint32_t* counts, uint32_t k, const ui
   }
 }
 
+
+// ---- vers_ivf_add_batch: placement of a staged chunk and the derived arrays of the tiles it touched -------------------------------
+// One job per destination tile of 64 storage rows: rows [lo, hi) of tile `tile` receive the chunk's rows sorted[src], sorted[src + 1], ...
+// (the cluster-sorted order of the chunk: one list's new rows are consecutive there, in ascending vec id).  The other rows of the tile --
+// the list's existing rows in front, slack behind -- keep their bits.
+struct AddTileJob {
+  uint32_t tile, lo, hi, src;
+};
+
+// One BLOCK per job, as gather_tiles_kernel: the new rows are read as they lie (whole rows of the staged chunk, zero-padded to ldx),
+// the rest of a partly new tile is read back in its own 1 KiB pieces, and every float4 column of the tile is written as one whole
+// 1 KiB piece from LDS.  row_ids[new row] = vid0 + its index in the chunk.
+__global__ __launch_bounds__(256) void add_tiles_kernel(const float* X, uint32_t ldx, uint32_t d, uint32_t ld, const AddTileJob* jobs,
+                                                        const uint32_t* sorted, uint32_t vid0, float* rows, uint32_t* row_ids) {
+  extern __shared__ __attribute__((aligned(16))) f32x4 tl[];  // [64][kGatherCols4 + 1]
+  __shared__ uint32_t s_src[kWave];
+  const AddTileJob jb = jobs[blockIdx.x];
+  if (threadIdx.x < 64) {
+    uint32_t src = 0xFFFFFFFFu;
+    if (threadIdx.x >= jb.lo && threadIdx.x < jb.hi) {
+      src = sorted[jb.src + (threadIdx.x - jb.lo)];
+      row_ids[(uint64_t)jb.tile * 64 + threadIdx.x] = vid0 + src;
+    }
+    s_src[threadIdx.x] = src;
+  }
+  __syncthreads();
+  const bool partial = jb.lo > 0 || jb.hi < 64;
+  const uint32_t ld4 = ld / 4, ldx4 = ldx / 4;
+  f32x4* tile = reinterpret_cast<f32x4*>(rows + (uint64_t)jb.tile * 64ull * ld);
+  constexpr uint32_t kPitch = kGatherCols4 + 1;
+  for (uint32_t c0 = 0; c0 < ld4; c0 += kGatherCols4) {
+    const uint32_t nc = ld4 - c0 < kGatherCols4 ? ld4 - c0 : kGatherCols4;
+    for (uint32_t i = threadIdx.x; i < 64u * kGatherCols4; i += 256u) {  // the new rows: a row's float4s by consecutive threads
+      const uint32_t r = i / kGatherCols4, j = i % kGatherCols4, c4 = c0 + j;
+      const uint32_t id = s_src[r];
+      if (j >= nc || id == 0xFFFFFFFFu) continue;
+      f32x4 v = {0.0f, 0.0f, 0.0f, 0.0f};
+      if (c4 < ldx4 && c4 * 4 < d) v = reinterpret_cast<const f32x4*>(X + (uint64_t)id * ldx)[c4];  // (the stage's padding is zero)
+      tl[r * kPitch + j] = v;
+    }
+    if (partial)
+      for (uint32_t i = threadIdx.x; i < 64u * nc; i += 256u) {  // the rows that stay: read back piece by piece
+        const uint32_t j = i / 64u, r = i % 64u;
+        if (s_src[r] == 0xFFFFFFFFu) tl[r * kPitch + j] = tile[(uint64_t)(c0 + j) * 64 + r];
+      }
+    __syncthreads();
+    for (uint32_t i = threadIdx.x; i < 64u * nc; i += 256u) {  // a piece's 64 rows by consecutive threads: 1 KiB contiguous
+      const uint32_t j = i / 64u, r = i % 64u;
+      tile[(uint64_t)(c0 + j) * 64 + r] = tl[r * kPitch + j];
+    }
+    __syncthreads();
+  }
+}
+
+// the chunk's rows per list onto both length tables (every list: a sharded rank counts the rows it does not store, as vers_ivf_add)
+__global__ void add_counts_kernel(const uint32_t* counts, uint32_t k, const uint32_t* list_slot, uint32_t* list_len, uint32_t* slot_len) {
+  const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= k || counts[c] == 0) return;
+  list_len[c] += counts[c];
+  slot_len[list_slot[c]] += counts[c];
+}
+
+// assignments of the kept rows are cluster indices (< k) before anything is indexed by them; an out-of-range one is reported and
+// replaced by 0 so that the grouping stays in bounds (the chunk is then refused before its placement)
+__global__ void add_check_assign_kernel(uint32_t* a, uint32_t n, uint32_t k, uint32_t* bad) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n && a[i] >= k) { a[i] = 0u; *bad = 1u; }
+}
+
+// rows [0, ld) of the chunk's source pitch -> the zero-padded stage [n][ldx] (the caller's columns d .. ld_src-1 may hold anything)
+__global__ void add_stage_rows_kernel(const float* src, uint64_t ld_src, uint32_t d, uint32_t ldx, uint64_t n, float* dst) {
+  const uint32_t ldx4 = ldx / 4;
+  const uint64_t total = n * ldx4;
+  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (uint64_t)gridDim.x * blockDim.x) {
+    const uint64_t r = i / ldx4;
+    const uint32_t c4 = (uint32_t)(i % ldx4);
+    f32x4 v = reinterpret_cast<const f32x4*>(src + r * ld_src)[c4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u)
+      if (c4 * 4 + u >= d) v[u] = 0.0f;
+    reinterpret_cast<f32x4*>(dst + r * ldx)[c4] = v;
+  }
+}
+
+// Tile-list forms of refresh_norms' kernels: row i of the list is storage row tiles[i / 64] * 64 + i % 64 (same per-row bodies, prescan.hip.h)
+__global__ void rows_to_f16_tiles_kernel(const float* rows, uint32_t ld, const uint32_t* tiles, uint64_t n_rows, uint16_t* rows_h) {
+  const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const uint32_t g8 = ld / 8;
+  const uint64_t i = t / g8;
+  if (i >= n_rows) return;
+  row_to_f16(rows, ld, (uint64_t)tiles[i >> 6] * 64 + (i & 63), (uint32_t)(t % g8), rows_h);
+}
+__global__ void shadow_residual_tiles_kernel(const float* rows, uint32_t ld, const uint32_t* row_ids, const uint32_t* tiles, uint64_t n_rows,
+                                             uint32_t* rmax2_bits) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n_rows) return;
+  const uint64_t r = (uint64_t)tiles[i >> 6] * 64 + (i & 63);
+  if (row_ids[r] == 0xFFFFFFFFu) return;
+  row_shadow_residual(rows, ld, r, rmax2_bits);
+}
+__global__ void row_norms_tiles_kernel(const float* rows, uint32_t ld, const uint32_t* row_ids, const uint32_t* tiles, uint64_t n_rows, float* xnorm,
+                                       uint32_t* xmax2_bits) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n_rows) return;
+  row_norm_blocked(rows, ld, row_ids, (uint64_t)tiles[i >> 6] * 64 + (i & 63), xnorm, xmax2_bits);
+}
+// the row-major copy (vers_ivf::rows_rm, all ld columns as refresh_norms writes it) of the listed tiles
+__global__ void from_blocked_tiles_kernel(const float* in, uint32_t ld, const uint32_t* tiles, uint64_t n_rows, float* out) {
+  const uint64_t total = n_rows * ld;
+  for (uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (uint64_t)gridDim.x * blockDim.x) {
+    const uint64_t i = t / ld;
+    const uint32_t j = (uint32_t)(t % ld);
+    const uint64_t r = (uint64_t)tiles[i >> 6] * 64 + (i & 63);
+    out[r * ld + j] = in[(r >> 6) * 64ull * ld + ((uint64_t)(j >> 2) * 64 + (r & 63)) * 4 + (j & 3)];
+  }
+}
+
 }  // namespace vers
 
 namespace vers {
@@ -989,12 +1106,14 @@ int32_t build_common(vers_ivf* h, const float* X, uint32_t ldx, uint64_t n, cons
   return VERS_OK;
 }
 
-int32_t relayout(vers_ivf* h) {
+// Every owned list moves to a new storage plan with room for lens[c] rows plus head-room (the rows it holds now, h_len[c], are copied):
+// relayout() plans for the current lengths, add_batch for the lengths after the chunk -- one re-layout per chunk however many lists overflow.
+static int32_t relayout_for(vers_ivf* h, const uint32_t* lens) {
   const uint32_t k = h->k;
   std::vector<uint32_t> noff(k), ncap(k);
   uint64_t off = 0;
   for (uint32_t c = 0; c < k; ++c) {
-    const uint32_t len = h->h_len[c];
+    const uint32_t len = lens[c];
     ncap[c] = h->h_owner[c] == h->rank ? round_up(len + std::max<uint32_t>(64u, len / 8u), 64u) : 0u;
     noff[c] = (uint32_t)off;
     off += ncap[c];
@@ -1015,6 +1134,7 @@ int32_t relayout(vers_ivf* h) {
   VERS_HIP_TRY(hipDeviceSynchronize());
   std::swap(h->rows.p, nrows.p); std::swap(h->rows.cap, nrows.cap);
   std::swap(h->row_ids.p, nids.p); std::swap(h->row_ids.cap, nids.cap);
+  nrows.release(); nids.release();  // (the old storage goes before refresh_norms re-allocates the shadow and the row-major copy)
   h->h_off = noff; h->h_cap = ncap; h->cap_rows = off;
   VERS_HIP_TRY(hipMemcpy(h->list_off.p, h->h_off.data(), (size_t)k * 4, hipMemcpyHostToDevice));
   {
@@ -1026,6 +1146,8 @@ int32_t relayout(vers_ivf* h) {
   VERS_HIP_TRY(hipDeviceSynchronize());
   return VERS_OK;
 }
+
+int32_t relayout(vers_ivf* h) { return relayout_for(h, h->h_len.data()); }
 
 
 // ---- streamed upload: begin / chunk / end (see vers_hip.h) -----------------------------------------------------------------
@@ -1245,6 +1367,265 @@ int32_t upload_end_locked(vers_ivf* h) {
   return finish_index(h, k, n_total, nullptr);
 }
 
+
+// ---- add_batch: Index::add for many rows (see vers_hip.h) -----------------------------------------------------------------------
+// Where the time of the add_batch calls of this process went (vers_add_batch_phases): host wall clock per phase, the stream
+// synchronised at each phase's end.
+constexpr int kAddBatchPhases = 9;
+static std::mutex g_ab_mu;
+static double g_ab[kAddBatchPhases] = {};  // calls, rows, re-layouts, stage, assign, group, relayout, place, derive (ms)
+struct AbClock {
+  int slot;
+  std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+  explicit AbClock(int s) : slot(s) {}
+  int32_t done() {  // the phase's work is finished when its clock stops
+    VERS_HIP_TRY(hipStreamSynchronize(nullptr));
+    std::lock_guard<std::mutex> lk(g_ab_mu);
+    g_ab[slot] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return VERS_OK;
+  }
+};
+static void ab_count(int slot, double v) {
+  std::lock_guard<std::mutex> lk(g_ab_mu);
+  g_ab[slot] += v;
+}
+
+// |x|^2 (+ maximum), fp16 shadow (+ residual maximum) and row-major copy of the listed tiles: refresh_norms for a tile list, one launch per array
+static int32_t refresh_tiles(vers_ivf* h, const uint32_t* tiles, uint32_t nt, hipStream_t st) {
+  if (nt == 0) return VERS_OK;
+  const uint64_t n_rows = (uint64_t)nt * 64;
+  if (shadow_mode() != 0) {
+    if (h->shadow_valid) {
+      const uint64_t work = n_rows * (h->ld / 8);
+      hipLaunchKernelGGL(rows_to_f16_tiles_kernel, dim3((unsigned)((work + 255) / 256)), dim3(256), 0, st, h->rows.as<float>(), h->ld, tiles, n_rows,
+                         h->rows_bf.as<uint16_t>());
+      hipLaunchKernelGGL(shadow_residual_tiles_kernel, dim3((unsigned)((n_rows + 255) / 256)), dim3(256), 0, st, h->rows.as<float>(), h->ld,
+                         (const uint32_t*)h->row_ids.as<uint32_t>(), tiles, n_rows, h->pre_misc.as<uint32_t>() + 2);
+      VERS_HIP_TRY(hipGetLastError());
+    }
+  } else {
+    h->shadow_valid = false;  // rows changed without their shadow following (as refresh_norms)
+  }
+  if (h->rows_rm.p) {
+    const uint64_t blocks = std::min<uint64_t>(65536, (n_rows * h->ld + 255) / 256);
+    hipLaunchKernelGGL(from_blocked_tiles_kernel, dim3((unsigned)blocks), dim3(256), 0, st, h->rows.as<float>(), h->ld, tiles, n_rows, h->rows_rm.as<float>());
+    VERS_HIP_TRY(hipGetLastError());
+  }
+  hipLaunchKernelGGL(row_norms_tiles_kernel, dim3((unsigned)((n_rows + 255) / 256)), dim3(256), 0, st, h->rows.as<float>(), h->ld,
+                     (const uint32_t*)h->row_ids.as<uint32_t>(), tiles, n_rows, h->xnorm.as<float>(), h->pre_misc.as<uint32_t>());
+  VERS_HIP_TRY(hipGetLastError());
+  return VERS_OK;
+}
+
+// One staged chunk X [m][ldx] (zero-padded) of rows with vec ids n_total, n_total + 1, ...: assignment, grouping, at most one re-layout,
+// placement, tables, derived arrays.  A NaN distance at row i (k >= 2) keeps rows 0 .. i-1 only (*out_nan).  *out_m = rows added;
+// out_a32_host (nullable) receives their clusters.
+static int32_t add_batch_chunk(vers_ivf* h, const float* X, uint32_t m, uint32_t* out_m, bool* out_nan, uint32_t* out_a32_host) {
+  const uint32_t k = h->k;
+  const hipStream_t st = nullptr;
+  auto& ab = h->ab;
+  uint32_t* a32 = ab.a32.as<uint32_t>();
+  *out_m = 0;
+  *out_nan = false;
+  // 1. first-minimum centroid of every row (ivfflat.rs:201-207) -- the build's assign pass on the handle's centroids
+  {
+    AbClock clk(4);
+    if (k == 1) {  // one centroid: every row goes there, a NaN one included (nothing is compared)
+      VERS_HIP_TRY(hipMemsetAsync(a32, 0, (size_t)m * sizeof(uint32_t), st));
+    } else {
+      if (int32_t rc = h->km.status.reserve(16)) return rc;
+      VERS_HIP_TRY(hipMemsetAsync(h->km.status.p, 0, 16, st));
+      if (int32_t rc = (km_use_mfma(m, k, h->d) ? km_assign_mfma : km_assign)(X, h->ldx, m, h->centroids.as<float>(), h->ldx, k, h->d, a32, nullptr,
+                                                                              h->km, h->n_cu, st, h->metric))
+        return rc;
+      uint32_t stw = 0;
+      VERS_HIP_TRY(hipMemcpy(&stw, h->km.status.p, 4, hipMemcpyDeviceToHost));
+      if (stw & 1u) {
+        // The pass reports a NaN distance by one status word, not per row: the first row that has one is found by bisection with the
+        // exact scan over the rows not yet cleared ([0, lo) holds none, [lo, hi) holds one) -- about one more pass over the chunk, on the
+        // error path only.  The rows before it keep the assignments of the pass above.
+        DevBuf tmp;
+        if (int32_t rc = tmp.reserve((size_t)m * sizeof(uint32_t))) return rc;
+        uint32_t lo = 0, hi = m;
+        while (hi - lo > 1) {
+          const uint32_t mid = lo + (hi - lo) / 2;
+          VERS_HIP_TRY(hipMemsetAsync(h->km.status.p, 0, 16, st));
+          if (int32_t rc = km_assign(X + (uint64_t)lo * h->ldx, h->ldx, mid - lo, h->centroids.as<float>(), h->ldx, k, h->d, tmp.as<uint32_t>(), nullptr,
+                                     h->km, h->n_cu, st, h->metric))
+            return rc;
+          VERS_HIP_TRY(hipMemcpy(&stw, h->km.status.p, 4, hipMemcpyDeviceToHost));
+          if (stw & 1u) hi = mid;
+          else lo = mid;
+        }
+        VERS_HIP_TRY(hipMemsetAsync(h->km.status.p, 0, 16, st));
+        m = lo;
+        *out_nan = true;
+      }
+    }
+    if (int32_t rc = clk.done()) return rc;
+  }
+  if (m == 0) return VERS_OK;
+  // 2. stable grouping by list, rows per list
+  uint32_t* counts = h->km.counts.as<uint32_t>();
+  uint32_t* starts = counts + k;
+  std::vector<uint32_t> cnt(k);
+  {
+    AbClock clk(5);
+    if (int32_t rc = ab.jobs.reserve(16)) return rc;  // (its first word: the range check's flag until the jobs are written)
+    VERS_HIP_TRY(hipMemsetAsync(ab.jobs.p, 0, 4, st));
+    hipLaunchKernelGGL(add_check_assign_kernel, dim3((m + 255) / 256), dim3(256), 0, st, a32, m, k, ab.jobs.as<uint32_t>());
+    VERS_HIP_TRY(hipGetLastError());
+    if (int32_t rc = km_group(a32, m, k, ab.sorted.as<uint32_t>(), counts, starts, h->km, st)) return rc;
+    uint32_t bad = 0;
+    VERS_HIP_TRY(hipMemcpy(cnt.data(), counts, (size_t)k * 4, hipMemcpyDeviceToHost));
+    VERS_HIP_TRY(hipMemcpy(&bad, ab.jobs.p, 4, hipMemcpyDeviceToHost));
+    if (bad) return fail(VERS_ERR_HIP, "vers_ivf_add_batch: the assign pass returned a cluster index out of range");
+    if (int32_t rc = clk.done()) return rc;
+  }
+  // 3. new lengths; one re-layout for the whole chunk when an owned list outgrows its capacity
+  std::vector<uint32_t> nl(k), first(k);
+  bool grow = false;
+  {
+    uint32_t run = 0;
+    for (uint32_t c = 0; c < k; ++c) {
+      first[c] = run;
+      run += cnt[c];
+      nl[c] = h->h_len[c] + cnt[c];  // (no overflow: n_total + n <= 0xFFFFFFFE was checked)
+      if (h->h_owner[c] == h->rank && nl[c] > h->h_cap[c]) grow = true;
+    }
+  }
+  if (grow) {
+    AbClock clk(6);
+    if (int32_t rc = relayout_for(h, nl.data())) return rc;
+    ab_count(2, 1.0);
+    if (int32_t rc = clk.done()) return rc;
+  }
+  // 4. placement: one job per touched tile of an owned list; row p of list c's new rows -> storage row list_off[c] + old_len[c] + p
+  std::vector<AddTileJob> jobs;
+  for (uint32_t c = 0; c < k; ++c) {
+    if (!cnt[c] || h->h_owner[c] != h->rank) continue;
+    const uint64_t b = (uint64_t)h->h_off[c] + h->h_len[c], e = b + cnt[c];
+    for (uint64_t t = b / 64; t * 64 < e; ++t) {
+      const uint64_t r0 = std::max<uint64_t>(b, t * 64), r1 = std::min<uint64_t>(e, t * 64 + 64);
+      jobs.push_back(AddTileJob{(uint32_t)t, (uint32_t)(r0 - t * 64), (uint32_t)(r1 - t * 64), first[c] + (uint32_t)(r0 - b)});
+    }
+  }
+  const uint32_t nt = (uint32_t)jobs.size();
+  const size_t jobs_b = (size_t)nt * sizeof(AddTileJob);
+  {
+    AbClock clk(7);
+    if (nt) {
+      std::vector<uint32_t> tiles(nt);
+      for (uint32_t i = 0; i < nt; ++i) tiles[i] = jobs[i].tile;
+      if (int32_t rc = ab.jobs.reserve(jobs_b + (size_t)nt * 4)) return rc;
+      VERS_HIP_TRY(hipMemcpy(ab.jobs.p, jobs.data(), jobs_b, hipMemcpyHostToDevice));
+      VERS_HIP_TRY(hipMemcpy(ab.jobs.as<char>() + jobs_b, tiles.data(), (size_t)nt * 4, hipMemcpyHostToDevice));
+      const size_t lds = 64 * (size_t)(kGatherCols4 + 1) * sizeof(f32x4);
+      if (int32_t rc = scan_prepare_launch(add_tiles_kernel, lds)) return rc;
+      hipLaunchKernelGGL(add_tiles_kernel, dim3(nt), dim3(256), lds, st, X, h->ldx, h->d, h->ld, (const AddTileJob*)ab.jobs.p,
+                         (const uint32_t*)ab.sorted.as<uint32_t>(), (uint32_t)h->n_total, h->rows.as<float>(), h->row_ids.as<uint32_t>());
+      VERS_HIP_TRY(hipGetLastError());
+    }
+    hipLaunchKernelGGL(add_counts_kernel, dim3((k + 255) / 256), dim3(256), 0, st, (const uint32_t*)counts, k, (const uint32_t*)h->list_slot.as<uint32_t>(),
+                       h->list_len.as<uint32_t>(), h->slot_len.as<uint32_t>());
+    VERS_HIP_TRY(hipGetLastError());
+    if (int32_t rc = clk.done()) return rc;
+  }
+  // 5. derived arrays of the touched tiles; the index is consistent once the stream is idle (the caller returns after that)
+  {
+    AbClock clk(8);
+    if (int32_t rc = refresh_tiles(h, (const uint32_t*)(ab.jobs.as<char>() + jobs_b), nt, st)) return rc;
+    if (int32_t rc = clk.done()) return rc;
+  }
+  if (out_a32_host) VERS_HIP_TRY(hipMemcpy(out_a32_host, a32, (size_t)m * 4, hipMemcpyDeviceToHost));
+  for (uint32_t c = 0; c < k; ++c) h->max_len = std::max(h->max_len, nl[c]);
+  h->h_len = nl;
+  h->n_total += m;
+  *out_m = m;
+  return VERS_OK;
+}
+
+// The batch in chunks of option "add_batch_rows" rows (default: the matrix-core assign pass's batch), each staged zero-padded with pitch ldx:
+// rows_host != nullptr copies through the pinned buffer (rows at row_stride_bytes), otherwise from rows_dev (pitch ld_floats) on the device.
+// Clusters go to out_host (u64, host) or out_dev (u64, device), either may be null.
+int32_t add_batch_locked(vers_ivf* h, const float* rows_host, uint64_t row_stride_bytes, const float* rows_dev, uint64_t ld_floats, uint64_t n,
+                         uint64_t* out_host, uint64_t* out_dev, uint64_t* out_first_vec_id, uint64_t* out_added) {
+  VERS_HIP_TRY(hipDeviceSynchronize());  // searches still in flight on any stream read the rows and tables this call changes
+  if (out_first_vec_id) *out_first_vec_id = h->n_total;
+  if (out_added) *out_added = 0;
+  if (h->k == 0) return fail(VERS_ERR_EMPTY, "add_batch on an index without centroids (reference: unwrap on None, ivfflat.rs:207)");
+  if (n == 0) return VERS_OK;
+  if (h->n_total + n > 0xFFFFFFFEull) return fail(VERS_ERR_INVALID, "vers_ivf_add_batch: vec_id space exhausted");
+  const uint32_t ldx = h->ldx, d = h->d;
+  const uint64_t chunk = std::min<uint64_t>(n, (uint64_t)std::max<int64_t>(1, opt_get("add_batch_rows", 131072)));
+  auto& ab = h->ab;
+  if (int32_t rc = ab.stage.reserve(chunk * ldx * sizeof(float))) return rc;
+  if (int32_t rc = ab.a32.reserve(chunk * sizeof(uint32_t))) return rc;
+  if (int32_t rc = ab.sorted.reserve(chunk * sizeof(uint32_t))) return rc;
+  if (int32_t rc = h->km.counts.reserve((2 * (size_t)h->k + 2) * sizeof(uint32_t))) return rc;
+  if (int32_t rc = h->pre_misc.reserve(64)) return rc;
+  if (rows_host && ab.pin_cap < chunk * ldx * sizeof(float)) {
+    ab.free_pin();
+    VERS_HIP_TRY(hipHostMalloc(&ab.pin, chunk * ldx * sizeof(float), hipHostMallocDefault));
+    ab.pin_cap = chunk * ldx * sizeof(float);
+  }
+  std::vector<uint32_t> a_host(out_host ? chunk : 0);
+  uint64_t added = 0;
+  ab_count(0, 1.0);
+  for (uint64_t s0 = 0; s0 < n; s0 += chunk) {
+    const uint32_t m = (uint32_t)std::min<uint64_t>(chunk, n - s0);
+    {
+      AbClock clk(3);
+      if (rows_host) {
+        float* pin = (float*)ab.pin;
+        auto pack = [&](uint64_t i0, uint64_t i1) {
+          for (uint64_t i = i0; i < i1; ++i) {
+            float* dst = pin + i * ldx;
+            std::memcpy(dst, (const char*)rows_host + (s0 + i) * row_stride_bytes, (size_t)d * 4);
+            for (uint32_t j = d; j < ldx; ++j) dst[j] = 0.0f;
+          }
+        };
+        const unsigned hw = std::max(1u, std::thread::hardware_concurrency());
+        const unsigned nth = (size_t)m * ldx * 4 >= (size_t(8) << 20) ? std::min(8u, hw) : 1u;
+        if (nth > 1) {
+          std::vector<std::thread> th;
+          const uint64_t per = (m + nth - 1) / nth;
+          for (unsigned t = 1; t < nth; ++t) th.emplace_back(pack, std::min<uint64_t>(m, t * per), std::min<uint64_t>(m, (t + 1) * per));
+          pack(0, std::min<uint64_t>(m, per));
+          for (auto& t : th) t.join();
+        } else {
+          pack(0, m);
+        }
+        VERS_HIP_TRY(hipMemcpyAsync(ab.stage.p, pin, (size_t)m * ldx * 4, hipMemcpyHostToDevice, nullptr));
+      } else {
+        const uint64_t blocks = std::min<uint64_t>((uint64_t)h->n_cu * 8, ((uint64_t)m * (ldx / 4) + 255) / 256);
+        hipLaunchKernelGGL(add_stage_rows_kernel, dim3((unsigned)blocks), dim3(256), 0, nullptr, rows_dev + s0 * ld_floats, ld_floats, d, ldx, (uint64_t)m,
+                           ab.stage.as<float>());
+        VERS_HIP_TRY(hipGetLastError());
+      }
+      if (int32_t rc = clk.done()) return rc;
+    }
+    uint32_t got = 0;
+    bool nan = false;
+    const int32_t rc = add_batch_chunk(h, ab.stage.as<float>(), m, &got, &nan, out_host ? a_host.data() : nullptr);
+    if (got) {
+      if (out_host)
+        for (uint32_t i = 0; i < got; ++i) out_host[s0 + i] = a_host[i];
+      if (out_dev) {
+        hipLaunchKernelGGL(u32_to_u64_kernel, dim3((got + 255) / 256), dim3(256), 0, nullptr, (const uint32_t*)ab.a32.as<uint32_t>(), (uint64_t)got,
+                           out_dev + s0);
+        VERS_HIP_TRY(hipGetLastError());
+        VERS_HIP_TRY(hipStreamSynchronize(nullptr));
+      }
+      added += got;
+      if (out_added) *out_added = added;
+      ab_count(1, (double)got);
+    }
+    if (rc) return rc;
+    if (nan) return fail(VERS_ERR_NAN, "NaN distance in add_batch at row " + std::to_string(s0 + got) + " (reference panics)");
+  }
+  return VERS_OK;
+}
 }  // namespace ivf
 }  // namespace vers
 
@@ -1443,6 +1824,33 @@ int32_t vers_ivf_add(vers_ivf_t* h, const float* row, uint64_t* out_cluster, uin
   h->n_total += 1;
   if (out_cluster) *out_cluster = c;
   if (out_vec_id) *out_vec_id = vid;
+  return VERS_OK;
+}
+
+int32_t vers_ivf_add_batch(vers_ivf_t* h, const float* rows, uint64_t n, uint64_t row_stride_bytes, uint64_t* out_clusters, uint64_t* out_first_vec_id,
+                           uint64_t* out_added) {
+  if (!h || (n && !rows) || row_stride_bytes < (uint64_t)(h ? h->d : 0) * 4 || row_stride_bytes % 4)
+    return fail(VERS_ERR_INVALID, "vers_ivf_add_batch: bad arguments (row_stride_bytes must be >= 4 d and a multiple of 4)");
+  std::unique_lock<std::shared_mutex> lk(h->index);
+  DeviceGuard g(h->device);
+  return add_batch_locked(h, rows, row_stride_bytes, nullptr, 0, n, out_clusters, nullptr, out_first_vec_id, out_added);
+}
+
+int32_t vers_ivf_add_batch_dev(vers_ivf_t* h, const float* rows_dev, uint64_t n, uint64_t ld_floats, uint64_t* out_clusters_dev, uint64_t* out_first_vec_id,
+                               uint64_t* out_added) {
+  if (!h || (n && !rows_dev) || ld_floats < (uint64_t)(h ? h->d : 0) || ld_floats % 4 || ld_floats > 0x3FFFFFFFull)
+    return fail(VERS_ERR_INVALID, "vers_ivf_add_batch_dev: bad arguments (ld_floats must be >= d and a multiple of 4)");
+  std::unique_lock<std::shared_mutex> lk(h->index);
+  DeviceGuard g(h->device);
+  return add_batch_locked(h, nullptr, 0, rows_dev, ld_floats, n, nullptr, out_clusters_dev, out_first_vec_id, out_added);
+}
+
+int32_t vers_add_batch_phases(double* out, int32_t reset) {
+  std::lock_guard<std::mutex> lk(g_ab_mu);
+  if (out)
+    for (int i = 0; i < kAddBatchPhases; ++i) out[i] = g_ab[i];
+  if (reset)
+    for (double& v : g_ab) v = 0.0;
   return VERS_OK;
 }
 

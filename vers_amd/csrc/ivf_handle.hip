@@ -159,6 +159,7 @@ int32_t vers_ivf_destroy(vers_ivf_t* h) {
   if (h->fail_watch) (void)hipHostFree(h->fail_watch);
   if (h->st_pin) (void)hipHostFree(h->st_pin);
   h->up.close();
+  h->ab.free_pin();
   delete h;
   return VERS_OK;
 }

@@ -166,6 +166,17 @@ struct vers_ivf {
       if (pin) { (void)hipHostFree(pin); pin = nullptr; pin_cap = 0; }
     }
   } up;
+  // vers_ivf_add_batch / _add_batch_dev (ivf_build.hip): scratch of one staged chunk, kept between calls (the callers hold the handle
+  // exclusively).  stage [chunk][ldx] zero-padded rows | a32 / sorted [chunk] | jobs: the touched tiles' placement jobs + tile indices.
+  struct AddBatchState {
+    DevBuf stage, a32, sorted, jobs, c64;
+    void* pin = nullptr;  // pinned staging of the host-pointer call: one chunk of rows at pitch ldx
+    size_t pin_cap = 0;
+    void free_pin() {
+      if (pin) (void)hipHostFree(pin);
+      pin = nullptr; pin_cap = 0;
+    }
+  } ab;
   // matrix-core list scan (prescan.hip.h): |x|^2 per storage row, [0] max |x|^2 bits, [1] certificate failures (running)
   DevBuf xnorm, pre_misc;
   // fp16 shadow of the rows for the matrix-core pre-selection (+50 % corpus memory; VERS_SHADOW=0 or a failed

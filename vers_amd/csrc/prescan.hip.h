@@ -77,13 +77,8 @@ struct PreParams {
 // list holds; fp16: as many as with f32 rows).  Elements beyond +-65504 become inf (the row's vals are then non-finite
 // and its queries are re-done exactly); tiny ones lose relative precision in fp16's subnormal range -- both are covered
 // by shadow_residual_kernel's MEASURED bound rather than a formula.
-// Thread = (row, group of 8 columns).
-static __global__ void rows_to_f16_kernel(const float* rows, uint32_t ld, uint64_t r_begin, uint64_t r_end, uint16_t* rows_h) {
-  const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const uint32_t g8 = ld / 8;
-  const uint64_t r = r_begin + t / g8;
-  const uint32_t j = (uint32_t)(t % g8);
-  if (r >= r_end) return;
+// Thread = (row, group of 8 columns).  (The three per-row bodies below are shared with the tile-list forms of add_batch, ivf_build.hip.)
+static __device__ __forceinline__ void row_to_f16(const float* rows, uint32_t ld, uint64_t r, uint32_t j, uint16_t* rows_h) {
   const float* src = rows + (r >> 6) * 64ull * ld;
   f16x8_t out;
 #pragma unroll
@@ -96,16 +91,21 @@ static __global__ void rows_to_f16_kernel(const float* rows, uint32_t ld, uint64
   uint16_t* dst = rows_h + (r >> 6) * 64ull * ld + ((uint64_t)((j >> 1) * 2 + (rr >> 5)) * 64 + (j & 1) * 32 + (rr & 31)) * 8;
   *reinterpret_cast<f16x8_t*>(dst) = out;
 }
+static __global__ void rows_to_f16_kernel(const float* rows, uint32_t ld, uint64_t r_begin, uint64_t r_end, uint16_t* rows_h) {
+  const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const uint32_t g8 = ld / 8;
+  const uint64_t r = r_begin + t / g8;
+  const uint32_t j = (uint32_t)(t % g8);
+  if (r >= r_end) return;
+  row_to_f16(rows, ld, r, j, rows_h);
+}
 
 // max over the stored rows of |x - fp16(x)|^2 (thread per row, like blocked_row_norms_kernel): the exact finish bounds
 // the shadow's error of a val by 2 |<x - x~, q>| <= 2 R |q| with this R.  x - fp16(x) is exact in f32 (the two are within
 // a factor of two of each other, or the difference is below fp16's subnormal spacing and x itself is tiny); the sum of
 // squares is inflated for its own roundings where it is used.  A finite element that overflows fp16 gives R = inf: no
 // certificate holds and the shadow switches itself off (vers_ivf::rows_bf).
-static __global__ void shadow_residual_kernel(const float* rows, uint32_t ld, const uint32_t* row_ids, uint64_t r_begin, uint64_t r_end,
-                                              uint32_t* rmax2_bits) {
-  const uint64_t r = r_begin + (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (r >= r_end || row_ids[r] == 0xFFFFFFFFu) return;
+static __device__ __forceinline__ void row_shadow_residual(const float* rows, uint32_t ld, uint64_t r, uint32_t* rmax2_bits) {
   const f32x4* p = reinterpret_cast<const f32x4*>(rows + (r >> 6) * 64ull * ld) + (r & 63);
   float acc = 0.0f;
   for (uint32_t j = 0; j < ld / 4; ++j) {
@@ -118,13 +118,17 @@ static __global__ void shadow_residual_kernel(const float* rows, uint32_t ld, co
   }
   if (acc == acc) atomicMax(rmax2_bits, __float_as_uint(acc));  // acc >= 0: bit order == value order (NaN rows: flagged by their vals)
 }
+static __global__ void shadow_residual_kernel(const float* rows, uint32_t ld, const uint32_t* row_ids, uint64_t r_begin, uint64_t r_end,
+                                              uint32_t* rmax2_bits) {
+  const uint64_t r = r_begin + (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= r_end || row_ids[r] == 0xFFFFFFFFu) return;
+  row_shadow_residual(rows, ld, r, rmax2_bits);
+}
 
 // |x|^2 of every storage row of the blocked matrix (thread per row: consecutive rows are consecutive float4s) and
 // the maximum over the rows that hold a vector.
-static __global__ void blocked_row_norms_kernel(const float* rows, uint32_t ld, const uint32_t* row_ids, uint64_t r_begin, uint64_t r_end,
-                                                float* xnorm, uint32_t* xmax2_bits) {
-  const uint64_t r = r_begin + (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (r >= r_end) return;
+static __device__ __forceinline__ void row_norm_blocked(const float* rows, uint32_t ld, const uint32_t* row_ids, uint64_t r, float* xnorm,
+                                                        uint32_t* xmax2_bits) {
   const f32x4* p = reinterpret_cast<const f32x4*>(rows + (r >> 6) * 64ull * ld) + (r & 63);
   float acc = 0.0f;
   for (uint32_t j = 0; j < ld / 4; ++j) {
@@ -140,6 +144,12 @@ static __global__ void blocked_row_norms_kernel(const float* rows, uint32_t ld, 
   const bool holds_vector = row_ids[r] != 0xFFFFFFFFu;
   xnorm[r] = holds_vector ? acc : 0.0f;
   if (holds_vector && acc == acc) atomicMax(xmax2_bits, __float_as_uint(acc));  // acc >= 0: bit order == value order
+}
+static __global__ void blocked_row_norms_kernel(const float* rows, uint32_t ld, const uint32_t* row_ids, uint64_t r_begin, uint64_t r_end,
+                                                float* xnorm, uint32_t* xmax2_bits) {
+  const uint64_t r = r_begin + (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= r_end) return;
+  row_norm_blocked(rows, ld, row_ids, r, xnorm, xmax2_bits);
 }
 
 // ---- the scan kernel: a quad of row segments x one query block per block of eight waves ----------------

@@ -99,6 +99,21 @@ class IVFFlatIndex {
     ids[(size_t)c].push_back((size_t)id);
   }
 
+  // add for many vectors in one call (vers_ivf_add_batch): the same fields as embeddings.size() calls of add.  On an error (a NaN
+  // distance at row i) the rows before it are added, mirrored here, and the error is thrown.
+  void add_batch(const std::vector<Vector<N>>& embeddings) {
+    std::vector<uint64_t> cl(embeddings.size() ? embeddings.size() : 1);
+    uint64_t first = 0, added = 0;
+    const int32_t rc = vers_ivf_add_batch(handle(), embeddings.empty() ? nullptr : embeddings[0].v, embeddings.size(), sizeof(Vector<N>),
+                                          cl.data(), &first, &added);
+    for (uint64_t i = 0; i < added; ++i) {
+      values.push_back(embeddings[i]);
+      assignments.push_back((size_t)cl[i]);
+      ids[(size_t)cl[i]].push_back((size_t)(first + i));
+    }
+    check(rc);
+  }
+
   // Index::search_approximate (ivfflat.rs:153-198)
   std::vector<std::pair<size_t, float>> search_approximate(const Vector<N>& query, size_t top_k) const {
     std::vector<uint64_t> oi(top_k ? top_k : 1);

@@ -92,6 +92,35 @@ class IVFFlatIndex:
         self.ids[c.value].append(int(vid.value))
         return int(c.value), int(vid.value)
 
+    def add_batch(self, embeddings):
+        """`add` for every row of `embeddings` [n][d] in one call (vers_ivf_add_batch): same clusters, vec ids, lists and
+        fields as n calls of add.  Returns (clusters, vec_ids) as u64 arrays.  On an error (a NaN distance at row i) the
+        rows before it are added and mirrored, then the error is raised."""
+        e = np.ascontiguousarray(embeddings, dtype=np.float32).reshape(-1, self.d)
+        n = e.shape[0]
+        cl = np.zeros(max(n, 1), dtype=np.uint64)
+        first = C.c_uint64(0); added = C.c_uint64(0)
+        rc = lib().vers_ivf_add_batch(self._h, _ptr(e), n, 4 * self.d, _ptr(cl), C.byref(first), C.byref(added))
+        m = int(added.value)
+        cl = cl[:m]
+        vids = np.arange(first.value, first.value + m, dtype=np.uint64)
+        if m:
+            assert first.value == len(self.assignments)
+            self.values = np.concatenate([self.values, e[:m]], axis=0)
+            self.assignments = np.concatenate([self.assignments, cl])
+            for c, v in zip(cl.tolist(), vids.tolist()):
+                self.ids[c].append(v)
+        check(rc)
+        return cl, vids
+
+    def add_batch_dev(self, rows_ptr: int, n: int, ld: int, clusters_ptr: int = 0):
+        """vers_ivf_add_batch_dev on rows already in HBM ([n][ld] f32); clusters (u64) to clusters_ptr when given.  The host
+        fields are NOT mirrored (the rows stay on the device).  Returns (first_vec_id, added)."""
+        first = C.c_uint64(0); added = C.c_uint64(0)
+        check(lib().vers_ivf_add_batch_dev(self._h, _vp(rows_ptr), n, ld, _vp(clusters_ptr) if clusters_ptr else None, C.byref(first),
+                                           C.byref(added)))
+        return int(first.value), int(added.value)
+
     # -- Index::search_approximate (ivfflat.rs:153-198) ---------------------------------------------
     def search_approximate(self, query, top_k: int):
         ids, dist, cnt = self.search_batch(np.asarray(query, dtype=np.float32).reshape(1, self.d), top_k, nprobe=0)
