@@ -23,7 +23,9 @@ int32_t vers_ivf_test_last_vals(vers_ivf_t* h, uint32_t q, uint64_t* out_vec_ids
 /* TEST HOOK: one wave of the matrix-core instruction a pre-filter uses, accumulated over K exactly as the kernels do, on
  * caller-chosen operands (tests/test_mfma_model_gpu.py measures the accumulation error the certificates' bounds assume).
  * kind 0 v_mfma_f32_32x32x16_f16, 1 v_mfma_f32_32x32x16_bf16 (A, B: 16-bit patterns), 2 v_mfma_f32_32x32x2_f32,
- * 3 v_mfma_f32_16x16x1_4b_f32 (f32).  A [rows][K], B [K][cols] row-major; rows x cols = 32 x 32 (kind 3: 64 x 16); host pointers. */
+ * 3 v_mfma_f32_16x16x1_4b_f32 (f32), 4 bf16x3: the three v_mfma_f32_32x32x16_bf16 products of dist_gemm_x3_kernel, <lo, hi> + <hi, lo> +
+ * <hi, hi> into one accumulator (A [2][32][K], B [2][K][32]: the hi plane, then the lo plane).  A [rows][K], B [K][cols] row-major;
+ * rows x cols = 32 x 32 (kind 3: 64 x 16); host pointers. */
 int32_t vers_test_mfma(int32_t device, uint32_t kind, const void* A, const void* B, uint32_t K, float* out_C);
 /* MEASUREMENT HOOK: fills *out with an exchange that is a STAND-IN WITH RCCL's FOOTPRINT for one-GPU emulations of a W-GPU
  * search (scripts/emulate_shard.py): all_gather_async launches ONE kernel of `workgroups` blocks x `threads` (256 | 512) threads

@@ -52,6 +52,22 @@ def test_product_boundary_carries_no_test_hooks():
         assert hasattr(tlib, n) and not hasattr(lib, n), n
 
 
+def test_certificate_audit_hooks_live_in_the_test_library():
+    """include/vers_hip_audit.h: the coarse / assign certificate audit hooks -- declared there only, bound by testhooks.AUDIT_SIGNATURES,
+    exported by libvers_hip_test.so and not by the product library."""
+    from vers_amd import testhooks
+    names = header_functions("vers_hip_audit.h")
+    assert names == ["vers_ivf_test_last_coarse", "vers_test_assign_filter"]
+    assert sorted(testhooks.AUDIT_SIGNATURES) == names
+    assert not set(names) & set(header_functions()) and not set(names) & set(header_functions("vers_hip_test.h"))
+    so = vbuild.build()
+    tso = vbuild.build_test_hooks()
+    lib = ctypes.CDLL(so, mode=ctypes.RTLD_GLOBAL)
+    tlib = ctypes.CDLL(tso)
+    for n in names:
+        assert hasattr(tlib, n) and not hasattr(lib, n), n
+
+
 def test_status_codes_match_header():
     txt = open(os.path.join(ROOT, "include", "vers_hip.h")).read()
     for name, val in [("VERS_OK", capi.OK), ("VERS_ERR_INVALID", capi.ERR_INVALID), ("VERS_ERR_NAN", capi.ERR_NAN),

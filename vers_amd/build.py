@@ -62,12 +62,12 @@ TEST_LIB = os.path.join(LIBDIR, "libvers_hip_test.so")
 
 
 def build_test_hooks(force: bool = False, verbose: bool = False) -> str:
-    """libvers_hip_test.so (include/vers_hip_test.h): the TEST / emulation hooks, a second library linked AGAINST libvers_hip.so --
+    """libvers_hip_test.so (include/vers_hip_test.h, include/vers_hip_audit.h): the TEST / emulation hooks, a second library linked AGAINST libvers_hip.so --
     the product library exports nothing named *test* (tests/test_abi.py)."""
     hipcc = _hipcc()
     srcs = sorted(os.path.join(TEST_SRC_DIR, f) for f in os.listdir(TEST_SRC_DIR) if f.endswith(".hip"))
     deps = srcs + [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hpp", ".hip.h", ".h"))]
-    deps += [os.path.join(os.path.dirname(_HERE), "include", h) for h in ("vers_hip.h", "vers_hip_test.h")] + [LIB]
+    deps += [os.path.join(os.path.dirname(_HERE), "include", h) for h in ("vers_hip.h", "vers_hip_test.h", "vers_hip_audit.h")] + [LIB]
     if force or _stale(TEST_LIB, deps):
         cmd = [hipcc] + CXXFLAGS + ["-shared"] + srcs + ["-o", TEST_LIB, f"-L{LIBDIR}", "-lvers_hip", "-Wl,-rpath,$ORIGIN"]
         if verbose:

@@ -245,15 +245,22 @@ static __global__ __launch_bounds__(256) void dist_gemm_kernel(const float* __re
 }
 
 // ---- the same contraction as THREE bf16 MFMA products of hi/lo-split operands -----------------------------------------
-// x = hi + lo + r with hi = bf16(x), lo = bf16(x - hi) (both round-to-nearest; x - hi is exact), |r| <= 2^-18 |x|.
+// x = hi + lo + r with hi = bf16(x), lo = bf16(x - hi) (both round-to-nearest; x - hi is exact).  bf16 keeps 8 significant
+// bits: for x in [2^e, 2^(e+1)), |x - hi| <= 2^(e-8), so |lo| <= 2^(e-8) <= 2^-8 |x|, and x - hi lies below 2^(e-8) (or is
+// that power of two, which bf16 holds), where half an ulp of bf16 is at most 2^(e-17): |r| <= 2^-17 |x|.
 //     <a, b> ~ <a_hi, b_hi> + <a_hi, b_lo> + <a_lo, b_hi>          (v_mfma_f32_32x32x16_bf16, f32 accumulation)
-// drops <a_lo, b_lo> and the residuals: |error| <= 3 * 2^-18 |a||b| on top of the f32 accumulation error that the f32
-// kernel has too -- 1.1e-5 |a||b| against a certificate bound E of 2.3e-4 (|a|^2 + |b|^2) at d = 768.  The consumers add
-// kX3Slack * (|q|^2 + max|c|^2) to their E (coarse_select_rescore_kernel, assign_rescore_kernel), so the product is a
-// PRE-FILTER exactly like the f32 one: results stay the reference's bits.  The matrix cores run bf16 at 16x the f32
-// rate, three products = 5.3x fewer MFMA cycles; the kernel is then bound by its operand traffic (global -> split in
-// registers -> LDS -> fragments), not by the MFMAs.
-constexpr float kX3Slack = 1.6e-5f;  // >= 2 * 3 * 2^-18 (G = norm - 2 dot doubles the dot's error), rounded up
+// drops, per element, a_lo b_lo + a r_b + r_a b - r_a r_b:  <= (2^-16 + 2 * 2^-17 + 2^-34) |a_k||b_k| = (2^-15 + 2^-34) |a_k||b_k|,
+// attained to within 2 % by x = 1 + 2^-8 - 2^-17 - 2^-23 in both operands (hi = 1, lo = 2^-8 - 2^-16, r = 2^-17 - 2^-23).  Summed
+// and by Cauchy-Schwarz <= (2^-15 + 2^-34) |a||b|; G = norm - 2 dot doubles it and 2 |a||b| <= |a|^2 + |b|^2, so the split
+// costs G at most (2^-15 + 2^-34) (|a|^2 + |b|^2) = 3.0518e-5 (|a|^2 + |b|^2) -- on top of the f32 accumulation error that the f32 kernel
+// has too (three instructions per 16 columns, each spending well under one rounding: tests/test_mfma_model_gpu.py), against a
+// certificate bound E of 2.6e-4 (|a|^2 + |b|^2) at d = 768.  The consumers add kX3Slack * (|q|^2 + max|c|^2) to their E
+// (coarse_select_rescore_kernel, coarse_select_wide_kernel, assign_rescore_kernel), so the product is a PRE-FILTER exactly like
+// the f32 one: results stay the reference's bits.  (Rounds 1-6 charged 1.6e-5, from a residual bound of 2^-18 |x| that bf16's
+// 8-bit significand does not give: on split-aligned operands the share was exceeded 1.87x -- tests/test_certificate_coarse_assign_gpu.py.)
+// The matrix cores run bf16 at 16x the f32 rate, three products = 5.3x fewer MFMA cycles; the kernel is then bound by its
+// operand traffic (global -> split in registers -> LDS -> fragments), not by the MFMAs.
+constexpr float kX3Slack = 3.06e-5f;  // >= 2^-15 + 2^-34 (the split's share of G above), rounded up
 // ONE product (dist_gemm_x3w_kernel<2, 1>, the first filter of the assign cascade) on FP16 operands x~ = fp16(x), c~ = fp16(c): the products
 // are exact in the f32 accumulator, so <x, c> - <x~, c~> = <x - x~, c> + <x~, c - c~>, bounded with the MEASURED residuals r_x = |x - x~|
 // (per point, summed by assign_rescore_kernel next to |x|^2) and R_c = max |c - c~| (to_f16_resid_kernel): |.| <= r_x |c| + (|x| + r_x) R_c;
@@ -552,8 +559,10 @@ __device__ __forceinline__ void wide_epilogue(f32x16 (&acc)[2][4], void* T, cons
 // interleaved, both operands pre-split by LDS-DMA / through registers: DESIGN.md Appendix A and the history of this file; the
 // instantiation keeps the kernel's name in the committed profiles.)
 // TERMS = 1 (round 6): ONLY the <hi, hi> product -- a third of the MFMAs, half the LDS traffic and split work -- as the FIRST filter of
-// a cascade: its values err by up to 2^-8 (|x|^2 + |c|^2) (kX1Slack), the certificate of assign_rescore_kernel is that much wider, and
-// the points it cannot settle go to the tile-limited exact re-scan (assign_tile_rescan_kernel) instead of a second contraction.  On
+// a cascade.  Both operands are FP16 (x~ = fp16(x), c~ = fp16(c)), whose products are exact in the f32 accumulator; assign_rescore_kernel
+// charges the difference to <x, c> with the MEASURED residuals (rc2_bits: max |c - c~|, and |x - x~| per point; the comment at kX3Slack),
+// not with a slack constant, and the points it cannot settle go to the tile-limited exact re-scan (assign_tile_rescan_kernel) instead of
+// a second contraction.  On
 // clustered data almost every point's nearest centroid beats the runner-up by far more than that (km_assign_mfma decides per pass
 // from its first batch).
 template <int SCHED, int TERMS = 3>  // TERMS = 1: Ch holds FP16 bit patterns, the points are converted to fp16
@@ -1026,7 +1035,8 @@ constexpr int kSelRowsW = 32;   // candidate rows a wave stages: 64 candidates d
 static __global__ __launch_bounds__(kWave * kSelWaves) void coarse_select_rescore_kernel(
     const float* G, uint32_t N_pad, uint32_t k, const float* C_rm, uint32_t ldc, const float* qp, uint32_t ldq, uint32_t d_pad,
     float cmax2, uint32_t P, uint32_t PS, uint64_t* probe, uint32_t* status, uint32_t* fallback_count, int metric,
-    unsigned long long* stamps, PlanQ pq, uint32_t n_queries) {
+    unsigned long long* stamps, PlanQ pq, uint32_t n_queries, float* qe_out = nullptr) {
+  // qe_out != nullptr: (|q|^2, E) of every query as this kernel used them, [b][2] (audited: vers_ivf_test_last_coarse)
   const uint32_t q = blockIdx.x;
   if (q >= n_queries) return;  // (whole blocks)
   const int lane = threadIdx.x & 63;
@@ -1198,6 +1208,7 @@ static __global__ __launch_bounds__(kWave * kSelWaves) void coarse_select_rescor
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) qn += __shfl_xor(qn, off, kWave);
   const float E = ((5.0f * (float)d_pad + 16.0f) * 5.9604645e-08f + kX3Slack) * (qn + cmax2 + (metric ? 1.0f : 0.0f));  // (+ the bf16x3 product's share)
+  if (qe_out && wid == 0 && lane == 0) { qe_out[2 * (uint64_t)q] = qn; qe_out[2 * (uint64_t)q + 1] = E; }
   const uint32_t Pq = P < k ? P : k;
   const float gP = __uint_as_float(order_bits_to_f32_bits((uint32_t)(readlane64(sel, (int)Pq - 1) >> 32)));
   const float gl = __uint_as_float(order_bits_to_f32_bits((uint32_t)(sel >> 32)));
@@ -1301,7 +1312,8 @@ static __global__ __launch_bounds__(kWave * kSelWaves) void coarse_select_rescor
 constexpr int kSelWideWaves = 4;
 static __global__ __launch_bounds__(kWave * kSelWideWaves) void coarse_select_wide_kernel(
     const float* G, uint32_t N_pad, uint32_t k, const float* C_rm, uint32_t ldc, const float* qp, uint32_t ldq, uint32_t d_pad,
-    float cmax2, uint32_t P, uint32_t PS, uint64_t* probe, uint32_t* status, uint32_t* fallback_count, int metric, PlanQ pq, uint32_t n_queries) {
+    float cmax2, uint32_t P, uint32_t PS, uint64_t* probe, uint32_t* status, uint32_t* fallback_count, int metric, PlanQ pq, uint32_t n_queries,
+    float* qe_out = nullptr) {
   __shared__ uint64_t sh[kSelWideWaves][kWideR][kWave];
   __shared__ uint64_t s_key[kWideKeys];
   __shared__ uint32_t s_ci[kWideKeys];
@@ -1364,6 +1376,7 @@ static __global__ __launch_bounds__(kWave * kSelWideWaves) void coarse_select_wi
   float qn = 0.0f;
   for (int w = 0; w < kSelWideWaves; ++w) qn += s_qn[w];  // (written before the fold's barriers)
   const float E = ((5.0f * (float)d_pad + 16.0f) * 5.9604645e-08f + kX3Slack) * (qn + cmax2 + (metric ? 1.0f : 0.0f));
+  if (qe_out && threadIdx.x == 0) { qe_out[2 * (uint64_t)q] = qn; qe_out[2 * (uint64_t)q + 1] = E; }
   if (wid == 0) {
     // which candidates are worth their row (coarse_select_rescore_kernel (2)): G <= g_P + 2 E; sorted by G, they are a prefix
     const float gP = __uint_as_float(order_bits_to_f32_bits((uint32_t)(wide_get(sel, Pq - 1u) >> 32)));
@@ -1490,8 +1503,10 @@ constexpr int kRsPitch = 36;  // floats per staged row: lane-per-row ds_read_b12
 static __global__ __launch_bounds__(kWave) void assign_rescore_kernel(const float* X, uint32_t ldx, const float* C_rm, uint32_t ldc, uint32_t d, uint32_t d_pad,
                                              const float* cmax2_dev, const uint32_t* best, const float* g2, uint32_t nb, uint32_t k,
                                              uint32_t i_base, uint32_t* assign, float* mind, uint32_t* fb_list, uint32_t* fb_count,
-                                             uint32_t* status, int metric, float* fb_thr = nullptr, const uint32_t* rc2_bits = nullptr) {
+                                             uint32_t* status, int metric, float* fb_thr = nullptr, const uint32_t* rc2_bits = nullptr,
+                                             float* e_out = nullptr) {
   // rc2_bits != nullptr: the values came from the SINGLE fp16 product (the cascade's first filter): the bound uses the measured residuals
+  // e_out != nullptr: every point's E as charged here (audited: vers_test_assign_filter)
   __shared__ __attribute__((aligned(16))) float sx[kWave * kRsPitch];
   __shared__ __attribute__((aligned(16))) float sc[kWave * kRsPitch];
   const int lane = threadIdx.x;  // (a block is one wave: no barrier anywhere, the LDS image is the wave's own and its accesses are in order)
@@ -1567,6 +1582,7 @@ static __global__ __launch_bounds__(kWave) void assign_rescore_kernel(const floa
     const float rx = 1.01f * __builtin_sqrtf(rx2), Rc = 1.01f * __builtin_sqrtf(__uint_as_float(*rc2_bits));
     E += 2.02f * (rx * __builtin_sqrtf(*cmax2_dev) + (__builtin_sqrtf(xn) + rx) * Rc);
   }
+  if (e_out) e_out[i] = E;
   const float lower = tau + (metric ? 1.0f : xn) - E;  // NaN if anything overflowed
   const bool finite = tau < __builtin_inff() && E < __builtin_inff();
   const bool certified = k == 1 || (finite && acc < lower);

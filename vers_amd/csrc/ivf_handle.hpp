@@ -87,6 +87,10 @@ struct SearchWs {
   uint32_t* st_word() const { return st_slot == 0 && st_dev ? st_dev : status.as<uint32_t>() + st_slot; }
   // geometry of the most recent matrix-core list scan on this workspace (TEST HOOK vers_ivf_test_last_vals)
   struct LastPre { bool valid = false; uint32_t b = 0, P = 0, S_max = 0, kp = 0, top_k = 0; const float* qp = nullptr; int shadow = 0; } last_pre;
+  // the most recent batched coarse quantiser on the matrix cores (coarse_mfma): its G rows stay in gbuf, the (|q|^2, E) the selection
+  // kernel used in coarse_qe [b][2] (vers_ivf_test_last_coarse)
+  struct LastCoarse { bool valid = false; uint32_t b = 0, P = 0; int x3 = 0; float cmax2 = 0.0f; } last_coarse;
+  DevBuf coarse_qe;
   GroupTotals last_tot{};
   const GroupTotals* tot_dev = nullptr;  // device totals of the last planned search
   bool tot_valid = false;

@@ -512,6 +512,7 @@ int32_t coarse_mfma(vers_ivf* h, const float* qp, uint32_t b, uint32_t P, uint64
   const uint32_t M_pad = round_up(b, kGemmBM);
   const uint32_t PS = std::min<uint32_t>(kMaxTopK, P + 16);
   if (int32_t rc = W->gbuf.reserve((size_t)M_pad * h->k_pad * sizeof(float))) return rc;
+  if (int32_t rc = W->coarse_qe.reserve((size_t)b * 2 * sizeof(float))) return rc;
   // (event records only when the call is timed at all -- vers_set_option("scan_events") -- and never on the look-ahead stream)
   const bool timed = W->ev_on && (st != W->ahead_stream || W->ahead_stream == nullptr);
   if (timed) VERS_HIP_TRY(hipEventRecord(W->evc[0], st));
@@ -528,15 +529,17 @@ int32_t coarse_mfma(vers_ivf* h, const float* qp, uint32_t b, uint32_t P, uint64
     if (int32_t rc = scan_prepare_launch(coarse_select_wide_kernel, lds)) return rc;
     hipLaunchKernelGGL(coarse_select_wide_kernel, dim3(b), dim3(kWave * kSelWideWaves), lds, st, W->gbuf.as<float>(), h->k_pad, h->k,
                        h->centroids_g.as<float>(), h->ldq, qp, h->ldq, h->ldq, coarse_mode() == 2 ? __builtin_inff() : h->cmax2, P, P + 32u,
-                       probe_out, W->st_word(), h->coarse_stat.as<uint32_t>(), h->metric, plan ? *plan : PlanQ{}, b);
+                       probe_out, W->st_word(), h->coarse_stat.as<uint32_t>(), h->metric, plan ? *plan : PlanQ{}, b, W->coarse_qe.as<float>());
   } else
   hipLaunchKernelGGL(coarse_select_rescore_kernel, dim3(b), dim3(kWave * kSelWaves), 0, st, W->gbuf.as<float>(), h->k_pad, h->k,
                      h->centroids_g.as<float>(), h->ldq, qp, h->ldq, h->ldq, coarse_mode() == 2 ? __builtin_inff() : h->cmax2, P, PS,
                      probe_out, W->st_word(), h->coarse_stat.as<uint32_t>(), h->metric,
                      (scan_debug_flags() & 16u) && W->stamps.p ? W->stamps.as<unsigned long long>() : (unsigned long long*)nullptr,
-                     plan ? *plan : PlanQ{}, b);
+                     plan ? *plan : PlanQ{}, b, W->coarse_qe.as<float>());
   VERS_HIP_TRY(hipGetLastError());
   if (timed) { VERS_HIP_TRY(hipEventRecord(W->evc[2], st)); W->evc_valid = true; }
+  W->last_coarse.valid = true; W->last_coarse.b = b; W->last_coarse.P = P; W->last_coarse.x3 = (gemm_x3_mask() & 2) != 0 ? 1 : 0;
+  W->last_coarse.cmax2 = coarse_mode() == 2 ? __builtin_inff() : h->cmax2;
   h->mfma_batches += 1;
   return VERS_OK;
 }

@@ -247,8 +247,10 @@ int32_t km_assign_mfma(const float* X, uint32_t ldx, uint64_t n, const float* C,
   // their runner-up centroid by far more than the window; rows spread evenly over the sphere do not): in auto mode a pass starts with
   // a small probing batch and keeps the cascade while at most 1/8 of a batch's points stay open; the verdict is remembered in the
   // scratch for the following passes over the same (n, k).
-  const int terms_opt = (int)opt_get("assign_terms", 0);
-  const bool wide_shape = (gemm_x3_mask() & 1) != 0 && round_up(k, kGemmBM) % kGemmWide == 0;
+  const int forced = ws.force_filter;
+  const bool x3 = forced < 0 ? (gemm_x3_mask() & 1) != 0 : forced != 0;
+  const int terms_opt = forced < 0 ? (int)opt_get("assign_terms", 0) : (forced >= 2 ? 1 : 3);
+  const bool wide_shape = x3 && round_up(k, kGemmBM) % kGemmWide == 0;
   if (ws.cascade_n != n || ws.cascade_k != k) { ws.cascade_n = n; ws.cascade_k = k; ws.cascade = -1; }
   bool hi_only = wide_shape && terms_opt != 3 && (terms_opt == 1 || ws.cascade != 0);
   const bool probing = hi_only && terms_opt == 0 && ws.cascade < 0;
@@ -271,7 +273,7 @@ int32_t km_assign_mfma(const float* X, uint32_t ldx, uint64_t n, const float* C,
   hipLaunchKernelGGL(max_norm_kernel, dim3(1), dim3(256), 0, st, ws.cnorm.as<float>(), k, cmax2_dev);
   VERS_HIP_TRY(hipGetLastError());
   const __bf16 *cg_h = nullptr, *cg_l = nullptr;
-  if (gemm_x3_mask() & 1) {  // every block of the pass re-reads the centroids: split them into bf16 hi / lo once, not per tile
+  if (x3) {  // every block of the pass re-reads the centroids: split them into bf16 hi / lo once, not per tile
     const size_t ne = (size_t)k_pad * ldq;
     if (int32_t rc = ws.cg_s.reserve(2 * ne * sizeof(uint16_t))) return rc;
     VERS_HIP_TRY(launch_split_bf16(ws.cg.as<float>(), ne, ws.cg_s.as<__bf16>(), ws.cg_s.as<__bf16>() + ne, st));
@@ -317,7 +319,7 @@ int32_t km_assign_mfma(const float* X, uint32_t ldx, uint64_t n, const float* C,
     // both operands fp16 in memory, staged by LDS-DMA (dist_gemm_h_kernel) from 4096 centroids on: the batch's conversion pass (0.11 ms per
     // 131072 x 768 points) is a tenth of the contraction at k = 4096 -- 1.03 ms with it against 1.04 for the register-staged kernel that
     // converts while it stages -- and nothing at k = 65536 (12.6 vs 16.2 ms).  Option "assign_glds": 1 always, 0 never.
-    const int glds_opt = (int)opt_get("assign_glds", -1);
+    const int glds_opt = forced < 0 ? (int)opt_get("assign_glds", -1) : (forced == 3 ? 1 : 0);
     const bool h_fits = (uint64_t)k_pad * ldq * 2u < (1ull << 32) && (uint64_t)mb * ldq * 2u < (1ull << 32);  // (its source offsets are 32 bits wide)
     const bool use_h = hi_only && wide && gemm_h_ok(ldq) && h_fits && (glds_opt > 0 || (glds_opt < 0 && k_pad >= 4096));
     if (use_h) {
@@ -340,7 +342,7 @@ int32_t km_assign_mfma(const float* X, uint32_t ldx, uint64_t n, const float* C,
       } else if (wide)
         VERS_HIP_TRY(launch_gemm_wide(k_pad, nb_pad, st, xb, hi_only ? cg_f16 : cg_h, cg_l, ws.cnorm.as<float>(), ldq, (uint32_t)mb, metric, k, part_v1, part_c1, part_v2, hi_only));
       else
-        VERS_HIP_TRY(launch_gemm<true>((gemm_x3_mask() & 1) != 0, k_pad / kGemmBM, nb_pad / kGemmBN, st, ws.cg.as<float>(), xb, ws.cnorm.as<float>(), ldq,
+        VERS_HIP_TRY(launch_gemm<true>(x3, k_pad / kGemmBM, nb_pad / kGemmBN, st, ws.cg.as<float>(), xb, ws.cnorm.as<float>(), ldq,
                                        (uint32_t)mb, (float*)nullptr, metric, k, part_v1, part_c1, part_v2, cg_h, cg_l));
     }
     build_stats_add(&BuildStats::gemm_launches, 1.0);
@@ -350,7 +352,11 @@ int32_t km_assign_mfma(const float* X, uint32_t ldx, uint64_t n, const float* C,
                        (const uint32_t*)fbq_count);
     hipLaunchKernelGGL(assign_rescore_kernel, dim3((nb + 63) / 64), dim3(64), 0, st, X + i0 * ldx, ldx, C, ldc, d, ldq, cmax2_dev, best, g2,
                        nb, k, (uint32_t)i0, out_assign + i0, out_mind ? out_mind + i0 : nullptr, tile_rescan ? fbq_list : fb_list,
-                       tile_rescan ? fbq_count : fb_count, ws.status.as<uint32_t>(), metric, fbq_thr, hi_only && wide ? (const uint32_t*)rc2_bits : (const uint32_t*)nullptr);
+                       tile_rescan ? fbq_count : fb_count, ws.status.as<uint32_t>(), metric, fbq_thr, hi_only && wide ? (const uint32_t*)rc2_bits : (const uint32_t*)nullptr,
+                       ws.probe ? ws.probe->e_dev + i0 : (float*)nullptr);
+    if (ws.probe) {
+      ws.probe->batches += 1; ws.probe->wide = wide; ws.probe->hi_only = hi_only && wide; ws.probe->used_h = use_h; ws.probe->tile_rescan = tile_rescan;
+    }
     if (tile_rescan) {
       if (xb_padded == nullptr) {  // the re-scan reads this batch's rows zero padded to ldq columns (its scalar operand): staged when the caller's are not
         if (int32_t rc = ws.xp.reserve((size_t)mb * ldq * sizeof(float))) return rc;
@@ -373,9 +379,33 @@ int32_t km_assign_mfma(const float* X, uint32_t ldx, uint64_t n, const float* C,
       open_before = open_now;
     }
   }
+  if (ws.probe && ws.probe->batches == 1) {  // (one batch: its triples and candidates are still in place)
+    AssignProbe& pr = *ws.probe;
+    const uint32_t nb = (uint32_t)n;
+    VERS_HIP_TRY(hipStreamSynchronize(st));
+    pr.n_tiles = n_tiles;
+    pr.best.resize(nb); pr.g2.resize(nb);
+    VERS_HIP_TRY(hipMemcpy(pr.best.data(), best, nb * 4u, hipMemcpyDeviceToHost));
+    VERS_HIP_TRY(hipMemcpy(pr.g2.data(), g2, nb * 4u, hipMemcpyDeviceToHost));
+    pr.part_v1.resize((size_t)n_tiles * nb); pr.part_c1.resize((size_t)n_tiles * nb); pr.part_v2.resize((size_t)n_tiles * nb);
+    VERS_HIP_TRY(hipMemcpy2D(pr.part_v1.data(), nb * 4u, part_v1, mb * 4u, nb * 4u, n_tiles, hipMemcpyDeviceToHost));
+    VERS_HIP_TRY(hipMemcpy2D(pr.part_c1.data(), nb * 4u, part_c1, mb * 4u, nb * 4u, n_tiles, hipMemcpyDeviceToHost));
+    VERS_HIP_TRY(hipMemcpy2D(pr.part_v2.data(), nb * 4u, part_v2, mb * 4u, nb * 4u, n_tiles, hipMemcpyDeviceToHost));
+  }
+  if (ws.probe) {  // the queue holds point indices of the whole pass
+    AssignProbe& pr = *ws.probe;
+    VERS_HIP_TRY(hipStreamSynchronize(st));
+    uint32_t nq = 0;
+    VERS_HIP_TRY(hipMemcpy(&nq, tile_rescan ? fbq_count : fb_count, 4, hipMemcpyDeviceToHost));
+    pr.queue.resize(nq);
+    if (nq) VERS_HIP_TRY(hipMemcpy(pr.queue.data(), tile_rescan ? fbq_list : fb_list, nq * 4u, hipMemcpyDeviceToHost));
+    pr.thr.assign(tile_rescan ? nq : 0u, 0.0f);
+    if (tile_rescan && nq) VERS_HIP_TRY(hipMemcpy(pr.thr.data(), fbq_thr, nq * 4u, hipMemcpyDeviceToHost));
+  }
   uint32_t nf = 0;
   VERS_HIP_TRY(hipMemcpyAsync(&nf, fb_count, 4, hipMemcpyDeviceToHost, st));
   VERS_HIP_TRY(hipStreamSynchronize(st));
+  if (ws.probe) ws.probe->n_full = nf;
   g_mfma_points += n;
   g_mfma_fallbacks += nf;
   if (nf) {  // uncertified points: the exact scan decides (order of fb_list is irrelevant: results are scattered by index)

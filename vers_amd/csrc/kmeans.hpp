@@ -1,6 +1,8 @@
 // kmeans.hpp -- device-level k-means steps shared by kmeans.hip (C ABI primitives) and
 // ivf_build.hip (build_index).  All pointers are device pointers; nothing synchronises unless noted.
 #pragma once
+#include <vector>
+
 #include "common.hpp"
 
 namespace vers {
@@ -24,7 +26,19 @@ struct DevBuf {
 void dev_mem_stats(uint64_t* now, uint64_t* peak, bool reset_peak);  // bytes held through DevBuf, process-wide
 void dev_mem_account(int64_t delta);  // for the one allocation made outside DevBuf::reserve
 
+// TEST HOOK (vers_test_assign_filter): what one batch of km_assign_mfma left behind before its exact paths ran.
+struct AssignProbe {
+  float* e_dev = nullptr;   // [n] device (the caller's): every point's E as assign_rescore_kernel charged it
+  uint32_t batches = 0, n_tiles = 0, wide = 0, hi_only = 0, used_h = 0, tile_rescan = 0, n_full = 0;
+  std::vector<uint32_t> best, part_c1, queue;  // candidate per point; [tile][point]; the points the certificate left open, in queue order
+  std::vector<float> g2, part_v1, part_v2, thr;  // second-smallest value per point; [tile][point]; fb_thr per queue entry (tile re-scan only)
+};
+
 struct KMeansScratch {
+  // TEST HOOK: the filter km_assign_mfma runs (-1: the options decide; 0 f32 MFMA, 1 bf16x3, 2 / 3 one fp16 product by the register-staged /
+  // LDS-DMA kernel), and where it reports one batch's values (vers_test_assign_filter)
+  int force_filter = -1;
+  AssignProbe* probe = nullptr;
   // the assign cascade's verdict for passes over (cascade_n, cascade_k): -1 not probed yet, 1 the <hi, hi> first filter pays, 0 it does not (km_assign_mfma)
   int cascade = -1;
   uint64_t cascade_n = 0;

@@ -1,4 +1,4 @@
-"""ctypes binding of libvers_hip_test.so (include/vers_hip_test.h): the TEST and one-GPU-emulation hooks.  They are NOT in the
+"""ctypes binding of libvers_hip_test.so (include/vers_hip_test.h, include/vers_hip_audit.h): the TEST and one-GPU-emulation hooks.  They are NOT in the
 product library (libvers_hip.so exports nothing named *test*): this second library links against it and takes its handles.
 Used by tests/ and by the emulation / nominal-rank scripts only."""
 from __future__ import annotations
@@ -22,6 +22,12 @@ SIGNATURES = {
     "vers_test_wave_net": (C.c_int32, [C.c_int32, _vp, _vp]),
     "vers_test_wide_net": (C.c_int32, [C.c_int32, _vp, _vp]),
 }
+# the certificate audit hooks (include/vers_hip_audit.h), in the same library
+AUDIT_SIGNATURES = {
+    "vers_ivf_test_last_coarse": (C.c_int32, [_vp, C.c_uint32, _vp, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_double)]),
+    "vers_test_assign_filter": (C.c_int32, [C.c_int32, _vp, C.c_uint32, C.c_uint32, _vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int32, C.c_uint32,
+                                            _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+}
 _lib = None
 
 
@@ -32,7 +38,7 @@ def lib():
         if not os.path.exists(LIB_PATH):
             raise ImportError(f"{LIB_PATH} is missing: build it with `python -m vers_amd.build`")
         L = C.CDLL(LIB_PATH)
-        for name, (res, args) in SIGNATURES.items():
+        for name, (res, args) in list(SIGNATURES.items()) + list(AUDIT_SIGNATURES.items()):
             fn = getattr(L, name)
             fn.restype, fn.argtypes = res, args
         _lib = L
@@ -55,14 +61,55 @@ def last_vals(index, q: int, cap: int = 8192):
 
 
 def mfma(kind: int, A: np.ndarray, B: np.ndarray, device: int = 0) -> np.ndarray:
-    """A [rows, K] x B [K, cols] on one wave of the matrix-core instruction `kind`, f32 result"""
+    """A [rows, K] x B [K, cols] on one wave of the matrix-core instruction `kind`, f32 result.
+    kind 4 (bf16x3): A [2, 32, K], B [2, K, 32] bf16 bit patterns, hi plane then lo plane"""
     A = np.ascontiguousarray(A); B = np.ascontiguousarray(B)
     rows, cols = (64, 16) if kind == 3 else (32, 32)
-    assert A.shape[0] == rows and B.shape[1] == cols and A.shape[1] == B.shape[0] and A.dtype == B.dtype
-    assert A.dtype == (np.uint16 if kind <= 1 else np.float32)
+    if kind == 4:
+        assert A.shape[0] == 2 and B.shape[0] == 2
+        a2, b2 = A[0], B[0]
+    else:
+        a2, b2 = A, B
+    assert a2.shape[0] == rows and b2.shape[1] == cols and a2.shape[1] == b2.shape[0] and A.dtype == B.dtype
+    assert A.dtype == (np.uint16 if kind in (0, 1, 4) else np.float32)
     out = np.zeros((rows, cols), dtype=np.float32)
-    check(lib().vers_test_mfma(device, kind, _ptr(A), _ptr(B), A.shape[1], _ptr(out)))
+    check(lib().vers_test_mfma(device, kind, _ptr(A), _ptr(B), a2.shape[1], _ptr(out)))
     return out
+
+
+def last_coarse(index, q: int):
+    """(G row [k], info dict) of query q of the last batched search on `index` whose coarse quantiser ran on the matrix cores"""
+    k = int(index.centroids.shape[0])
+    g = np.zeros(k, dtype=np.float32)
+    n = C.c_uint32(0); info = (C.c_double * 8)()
+    check(lib().vers_ivf_test_last_coarse(index._h, q, _ptr(g), k, C.byref(n), info))
+    keys = ("qn", "cmax2", "d_pad", "metric", "x3", "slack", "E", "P")
+    return g[:n.value].copy(), dict(zip(keys, (float(x) for x in info)))
+
+
+ASSIGN_MODES = {0: "f32 MFMA", 1: "bf16x3", 2: "fp16 x1 (dist_gemm_x3w_kernel<2,1>)", 3: "fp16 x1 (dist_gemm_h_kernel)", 4: "as the options decide"}
+
+
+def assign_filter(X: np.ndarray, Cn: np.ndarray, metric: int, mode: int, device: int = 0) -> dict:
+    """one batch of the matrix-core assign pass with the filter forced to `mode` (ASSIGN_MODES): what its certificate and tile
+    re-scan saw, per point and per (tile, point), and the final assignment (include/vers_hip_test.h)"""
+    X = np.asarray(X, dtype=np.float32); Cn = np.asarray(Cn, dtype=np.float32)
+    n, d = X.shape
+    k = Cn.shape[0]
+    ld = (d + 3) // 4 * 4
+    Xp = np.zeros((n, ld), dtype=np.float32); Xp[:, :d] = X
+    Cp = np.zeros((k, ld), dtype=np.float32); Cp[:, :d] = Cn
+    n_tiles = (k + 127) // 128
+    r = {"cand": np.zeros(n, np.uint32), "g2": np.zeros(n, np.float32), "E": np.zeros(n, np.float32), "queued": np.zeros(n, np.uint8),
+         "thr": np.zeros(n, np.float32), "part_v1": np.zeros((n_tiles, n), np.float32), "part_c1": np.zeros((n_tiles, n), np.uint32),
+         "part_v2": np.zeros((n_tiles, n), np.float32), "assign": np.zeros(n, np.uint32), "mind": np.zeros(n, np.float32)}
+    info = np.zeros(10, dtype=np.uint32)
+    check(lib().vers_test_assign_filter(device, _ptr(Xp), n, ld, _ptr(Cp), k, ld, d, metric, mode, _ptr(r["cand"]), _ptr(r["g2"]), _ptr(r["E"]),
+                                        _ptr(r["queued"]), _ptr(r["thr"]), _ptr(r["part_v1"]), _ptr(r["part_c1"]), _ptr(r["part_v2"]),
+                                        _ptr(r["assign"]), _ptr(r["mind"]), _ptr(info)))
+    r["queued"] = r["queued"].astype(bool)
+    r.update(zip(("n_tiles", "wide", "hi_only", "used_h", "tile_rescan", "n_queued", "n_full", "status", "batches", "mode"), (int(v) for v in info)))
+    return r
 
 
 def wave_net(keys: np.ndarray, device: int = 0) -> np.ndarray:
