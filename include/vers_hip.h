@@ -332,6 +332,41 @@ int32_t vers_ivf_build_sharded_dev(vers_ivf_t* h, const float* rows_dev, uint64_
                                    uint64_t max_iterations, const uint64_t* init_indices, const vers_comm_t* comm,
                                    uint64_t* out_assignments_local, float* out_cost, int32_t* out_kept,
                                    uint64_t* out_iterations);
+/* Removal (extension: the reference has no remove; defined in its own terms).  Removing vec id v is, on the five fields of
+ * IVFFlatIndex<N> (ivfflat.rs:8-15),
+ *     ids[assignments[v]].retain(|&x| x != v)
+ * and nothing else: `values` and `assignments` keep their entry (positions ARE vec ids: they never shift), the centroids do not move,
+ * assignments.len() -- n of vers_ivf_info, the vec id the next add hands out -- is unchanged, a removed id is never reused.  Every search
+ * of the reference walks ids[c] only (ivfflat.rs:166-178), so everything observable afterwards is what the shortened lists imply:
+ *   searches  : every mode and path ranks the surviving rows only, in their unchanged relative order; reference mode (nprobe == 0) spills
+ *               over live rows, fewer than top_k of them reachable -> VERS_ERR_INSUFFICIENT; an emptied list is skipped;
+ *               vers_ivf_search_exhaustive* ranks live rows, out_count = min(top_k, live).
+ *   getters   : vers_ivf_get_list, vers_ivf_list_lengths and the longest list of vers_ivf_info report the shortened lists.
+ *   add       : vers_ivf_add / _add_batch afterwards append behind a list's survivors, into the freed rows (capacity is kept: the freed
+ *               rows become the list's slack, storage never shrinks).
+ *   vec_ids   : any order, repeats allowed; an id that is in no list any more (removed earlier, or repeated in the call) is skipped.
+ *               *out_removed = distinct rows that left the index.  ANY id >= n -> VERS_ERR_INVALID and NOTHING is removed (all ids are
+ *               checked before anything is written).  n_ids == 0: no-op.  A streamed upload in progress: VERS_ERR_EMPTY (as add).
+ *   host ids  : staged through a bounded pinned buffer (option "remove_batch_ids" ids per chunk, default 1048576); the device holds one
+ *               bit per vec id, never the id array.
+ *   _dev      : vec_ids_dev is a device array.  comm: NULL on an unsharded handle; on a handle sharded by cluster (world > 1) the
+ *               callbacks of vers_ivf_build_sharded_dev -- EVERY rank calls with the same ids, the owner of a list removes its rows, ONE
+ *               all_gather of the per-list removed counts ([k] u32 per rank) gives every rank the new GLOBAL lengths and the same
+ *               *out_removed.  world > 1 with comm == NULL (and the host-pointer call on a sharded handle): VERS_ERR_INVALID, nothing
+ *               removed.  (A rank that fails locally before the exchange returns its error without entering it: the host aborts the
+ *               group on any non-zero return, as for the sharded build.)
+ * Synchronous; holds the handle exclusively and waits for searches in flight, like vers_ivf_add_batch.  The running maxima the search
+ * certificates charge (max |x|^2, max fp16 residual) are not re-tightened: after a removal they are still upper bounds, results are exact. */
+int32_t vers_ivf_remove_batch(vers_ivf_t* h, const uint64_t* vec_ids, uint64_t n_ids, uint64_t* out_removed);
+int32_t vers_ivf_remove_batch_dev(vers_ivf_t* h, const uint64_t* vec_ids_dev, uint64_t n_ids, const vers_comm_t* comm,
+                                  uint64_t* out_removed);
+/* Vectors currently in the lists (sum of the global list lengths) = n of vers_ivf_info minus everything removed. */
+int32_t vers_ivf_live_count(vers_ivf_t* h, uint64_t* out_live);
+/* The remove calls of this process by PHASE (host wall clock in ms, the stream synchronised at each phase's end).  out[8]: [0] calls,
+ * [1] ids passed, [2] rows removed, [3] staging of the ids (host copy through the pinned buffer), [4] marking (bitmap, range check, the
+ * pass over row_ids, a sharded handle's exchange), [5] compaction, [6] length tables, [7] derived arrays (|x|^2, shadow, row-major
+ * copy of the touched tiles).  reset != 0 zeroes them. */
+int32_t vers_remove_phases(double* out8, int32_t reset);
 /* Process-wide switches: every one is a named option set here (or, for a process one does not control from inside, through the ONE
  * environment variable VERS_OPTIONS="name=value,name=value", read once; besides it the library reads only VERS_SHADOW and
  * VERS_ROWMAJOR, the two memory switches of INTEGRATION.md = options "shadow" / "rowmajor").  Unknown name: VERS_ERR_INVALID.
@@ -368,7 +403,7 @@ int32_t vers_ivf_build_sharded_dev(vers_ivf_t* h, const float* rows_dev, uint64_
  *   "wide_k" (1)        results of 49 .. 200 keys (batches, nprobe >= 1) stay on the matrix-core list scan with candidate lists four keys
  *                       per lane wide; 0 = the ordered chains, 64 ranks per pass.
  *   "coarse1" (1), "scan1t" (1), "ref_as_nprobe1" (1), "assign_tiles" (1), "assign_tiles_min" (64), "seg_rows" (0), "pre_slack" (0),
- *   "upload_stage_mb" (256)   kernel-choice and sizing knobs of DESIGN.md section 5.
+ *   "upload_stage_mb" (256), "add_batch_rows" (131072), "remove_batch_ids" (1048576)   kernel-choice and sizing knobs of DESIGN.md section 5.
  *   "scan_debug" (0), "poison_alloc" (-1), "poison_slack_bits" (-1), "test_fail_sharded" (0)   diagnosis: phase stamps / skipped
  *                       phases, new device buffers filled with a byte, slack rows filled with an f32 bit pattern, the next n sharded
  *                       searches fail locally. */

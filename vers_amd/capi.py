@@ -58,6 +58,9 @@ SIGNATURES = {
     "vers_ivf_add": (C.c_int32, [_vp, _vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "vers_ivf_add_batch": (C.c_int32, [_vp, _vp, C.c_uint64, C.c_uint64, _vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "vers_ivf_add_batch_dev": (C.c_int32, [_vp, _vp, C.c_uint64, C.c_uint64, _vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "vers_ivf_remove_batch": (C.c_int32, [_vp, _vp, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "vers_ivf_remove_batch_dev": (C.c_int32, [_vp, _vp, C.c_uint64, _vp, C.POINTER(C.c_uint64)]),
+    "vers_ivf_live_count": (C.c_int32, [_vp, C.POINTER(C.c_uint64)]),
     "vers_ivf_search": (C.c_int32, [_vp, _vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, _vp, _vp, _vp]),
     "vers_ivf_search_dev": (C.c_int32, [_vp, _vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, _vp, _vp, _vp, _vp]),
     "vers_ivf_poll": (C.c_int32, [_vp, _vp]),
@@ -97,6 +100,7 @@ SIGNATURES = {
     "vers_build_stats": (C.c_int32, [C.POINTER(C.c_double), C.c_int32]),
     "vers_build_phases": (C.c_int32, [C.POINTER(C.c_double), C.c_int32]),
     "vers_add_batch_phases": (C.c_int32, [C.POINTER(C.c_double), C.c_int32]),
+    "vers_remove_phases": (C.c_int32, [C.POINTER(C.c_double), C.c_int32]),
     "vers_kmeans_update": (C.c_int32, [C.c_int32, _vp, C.c_uint64, C.c_uint64, _vp, C.c_uint64, C.c_uint32, _vp]),
     "vers_kmeans_cost": (C.c_int32, [C.c_int32, _vp, C.c_uint64, C.c_uint64, _vp, C.c_uint64, C.c_uint64, _vp, C.c_uint32,
                                      C.POINTER(C.c_float)]),
@@ -306,6 +310,14 @@ def add_batch_phases(reset=False) -> dict:
     v = (C.c_double * 9)()
     check(lib().vers_add_batch_phases(v, 1 if reset else 0))
     keys = ("calls", "rows", "relayouts", "stage_ms", "assign_ms", "group_ms", "relayout_ms", "place_ms", "derive_ms")
+    return dict(zip(keys, (float(x) for x in v)))
+
+
+def remove_phases(reset=False) -> dict:
+    """The remove_batch calls of this process by phase, host wall clock in ms (vers_remove_phases)."""
+    v = (C.c_double * 8)()
+    check(lib().vers_remove_phases(v, 1 if reset else 0))
+    keys = ("calls", "ids", "removed", "stage_ms", "mark_ms", "compact_ms", "tables_ms", "derive_ms")
     return dict(zip(keys, (float(x) for x in v)))
 
 

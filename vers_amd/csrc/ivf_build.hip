@@ -322,14 +322,130 @@ __global__ void row_norms_tiles_kernel(const float* rows, uint32_t ld, const uin
   if (i >= n_rows) return;
   row_norm_blocked(rows, ld, row_ids, (uint64_t)tiles[i >> 6] * 64 + (i & 63), xnorm, xmax2_bits);
 }
-// the row-major copy (vers_ivf::rows_rm, all ld columns as refresh_norms writes it) of the listed tiles
-__global__ void from_blocked_tiles_kernel(const float* in, uint32_t ld, const uint32_t* tiles, uint64_t n_rows, float* out) {
-  const uint64_t total = n_rows * ld;
-  for (uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (uint64_t)gridDim.x * blockDim.x) {
-    const uint64_t i = t / ld;
-    const uint32_t j = (uint32_t)(t % ld);
-    const uint64_t r = (uint64_t)tiles[i >> 6] * 64 + (i & 63);
-    out[r * ld + j] = in[(r >> 6) * 64ull * ld + ((uint64_t)(j >> 2) * 64 + (r & 63)) * 4 + (j & 3)];
+// The row-major copy (vers_ivf::rows_rm, all ld columns as refresh_norms writes it) of the listed tiles: one BLOCK per tile, gather_tiles_kernel
+// backwards -- the tile's 1 KiB pieces are read as they lie, turned through LDS 64 float4 columns at a time, and every row leaves as one
+// contiguous run.  (Until the removal work a thread per element read its float out of a 16-byte piece 1 KiB from its neighbour's: 37.7 ms for
+// the 155 k tiles a removal of 65,536 random ids touches at cfg3 -- three times the compaction itself.)
+__global__ __launch_bounds__(256) void tiles_to_rowmajor_kernel(const float* in, uint32_t ld, const uint32_t* tiles, float* out) {
+  extern __shared__ __attribute__((aligned(16))) f32x4 tl[];  // [64][kGatherCols4 + 1]
+  const uint64_t t = tiles[blockIdx.x];
+  const uint32_t ld4 = ld / 4;
+  const f32x4* tile = reinterpret_cast<const f32x4*>(in + t * 64ull * ld);
+  f32x4* rm = reinterpret_cast<f32x4*>(out + t * 64ull * ld);
+  constexpr uint32_t kPitch = kGatherCols4 + 1;
+  for (uint32_t c0 = 0; c0 < ld4; c0 += kGatherCols4) {
+    const uint32_t nc = ld4 - c0 < kGatherCols4 ? ld4 - c0 : kGatherCols4;
+    for (uint32_t i = threadIdx.x; i < 64u * nc; i += 256u) {  // a piece's 64 rows by consecutive threads: 1 KiB contiguous
+      const uint32_t j = i / 64u, r = i % 64u;
+      tl[r * kPitch + j] = tile[(uint64_t)(c0 + j) * 64 + r];
+    }
+    __syncthreads();
+    for (uint32_t i = threadIdx.x; i < 64u * kGatherCols4; i += 256u) {  // a row's float4s by consecutive threads
+      const uint32_t r = i / kGatherCols4, j = i % kGatherCols4;
+      if (j < nc) rm[(uint64_t)r * ld4 + c0 + j] = tl[r * kPitch + j];
+    }
+    __syncthreads();
+  }
+}
+
+// ---- vers_ivf_remove_batch: marking and in-place compaction of the lists that lose rows ------------------------------------------------
+// The ids of a call become one bit per vec id; *bad != 0: one of them is >= n_total (nothing of the index has been written by then).
+__global__ void remove_mark_ids_kernel(const uint64_t* ids, uint64_t m, uint64_t n_total, uint32_t* bitmap, uint32_t* bad) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= m) return;
+  const uint64_t v = ids[i];
+  if (v >= n_total) { *bad = 1u; return; }
+  atomicOr(&bitmap[v >> 5], 1u << (v & 31));
+}
+
+// One pass over row_ids: a stored row whose vec id is marked counts for its list and lowers the list's first tile that loses a row.
+// The list of a storage row comes from the CURRENT offsets (the last list with list_off <= r: lists without storage -- another rank's --
+// share their offset with the next one that has some), not from tile_list, which a re-layout leaves stale.
+__global__ void remove_scan_rows_kernel(const uint32_t* row_ids, uint64_t cap_rows, const uint32_t* bitmap, uint64_t n_total, const uint32_t* list_off,
+                                        uint32_t k, uint32_t* rm_cnt, uint32_t* first_tile) {
+  for (uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; r < cap_rows; r += (uint64_t)gridDim.x * blockDim.x) {
+    const uint32_t id = row_ids[r];
+    if (id == 0xFFFFFFFFu || id >= n_total || !((bitmap[id >> 5] >> (id & 31)) & 1u)) continue;
+    uint32_t lo = 0, hi = k;
+    while (hi - lo > 1) {
+      const uint32_t mid = lo + (hi - lo) / 2;
+      if (list_off[mid] <= r) lo = mid;
+      else hi = mid;
+    }
+    atomicAdd(&rm_cnt[lo], 1u);
+    atomicMin(&first_tile[lo], (uint32_t)(r >> 6));
+  }
+}
+
+// One list that loses rows: its first storage row (a tile boundary), its length before the call, its first tile (list-relative) with a marked row.
+struct RemoveJob {
+  uint32_t off, len, first;
+};
+constexpr uint32_t kRmWaves = 8;  // waves per block of remove_compact_kernel
+constexpr uint32_t kRmCols4 = 4;  // float4 columns a wave holds in registers per step
+
+// One BLOCK per job walks the list's tiles in ascending order from `first`.  Destination row j takes the j-th surviving row s(j): s is
+// monotone and s(j) >= j, so the sources of a destination tile lie in that tile or behind it and the move is safe IN PLACE --
+//   map  : the block gathers the next 64 survivors (windows of row_ids from the first source not yet consumed, a ballot scan over the
+//          bitmap test) into LDS; row_ids[j0 .. j0+64) are written after the window reads (later windows start at s(j0+63)+1 >= j0+64).
+//   rows : source and destination are both tile layout, and a float4 COLUMN of a tile is its own 1 KiB piece: rows move within their
+//          column only.  Each wave owns the columns == its index (mod kRmWaves x kRmCols4 groups): it reads the 64 sources of a destination
+//          piece (mostly runs of consecutive 16-byte pieces) into registers and then writes the whole 1 KiB piece -- all loads of a piece
+//          precede its stores in the one wave that touches that column, and no other wave ever does.  One barrier pair per tile (the map).
+// Rows [new length, old length) become slack: row_ids 0xFFFFFFFF and zeros, as gather_tiles_kernel writes it.
+__global__ __launch_bounds__(kRmWaves * 64) void remove_compact_kernel(const RemoveJob* jobs, const uint32_t* bitmap, uint64_t n_total, uint32_t ld,
+                                                                       float* rows, uint32_t* row_ids) {
+  __shared__ uint32_t s_src[kWave], s_id[kWave], s_wsum[kRmWaves];
+  __shared__ uint32_t s_pos;
+  const RemoveJob jb = jobs[blockIdx.x];
+  const uint32_t tid = threadIdx.x, lane = tid & 63u, wv = tid >> 6;
+  const uint32_t ld4 = ld / 4;
+  f32x4* const base4 = reinterpret_cast<f32x4*>(rows) + (uint64_t)jb.off * ld4;  // tile t of the list: base4 + t * 64 * ld4
+  uint32_t* const ids = row_ids + jb.off;
+  uint32_t pos = jb.first * 64u;  // first source row (list-relative) not yet consumed; the same in every thread
+  for (uint32_t j0 = jb.first * 64u; j0 < jb.len; j0 += 64u) {
+    uint32_t have = 0;
+    while (have < 64u && pos < jb.len) {
+      const uint32_t idx = pos + tid;
+      const uint32_t id = idx < jb.len ? ids[idx] : 0xFFFFFFFFu;
+      const bool surv = id != 0xFFFFFFFFu && (id >= n_total || !((bitmap[id >> 5] >> (id & 31)) & 1u));
+      const unsigned long long mask = __ballot(surv);
+      const uint32_t pre = (uint32_t)__popcll(mask & ((1ull << lane) - 1ull));
+      if (lane == 0) s_wsum[wv] = (uint32_t)__popcll(mask);
+      __syncthreads();
+      uint32_t woff = 0, total = 0;
+#pragma unroll
+      for (uint32_t w = 0; w < kRmWaves; ++w) {
+        const uint32_t s = s_wsum[w];
+        if (w < wv) woff += s;
+        total += s;
+      }
+      const uint32_t p = have + woff + pre;
+      if (surv && p < 64u) { s_src[p] = idx; s_id[p] = id; }
+      if (surv && p == 63u) s_pos = idx + 1u;
+      __syncthreads();
+      if (have + total >= 64u) { pos = s_pos; have = 64u; }
+      else { pos += kRmWaves * 64u; have += total; }
+    }
+    if (tid < 64u && tid >= have) s_src[tid] = 0xFFFFFFFFu;
+    __syncthreads();
+    if (tid < 64u) ids[j0 + tid] = s_src[tid] != 0xFFFFFFFFu ? s_id[tid] : 0xFFFFFFFFu;  // (j0 + 63 < round_up(len, 64) <= the list's capacity)
+    const uint32_t src = s_src[lane], src0 = src != 0xFFFFFFFFu ? src : 0u;
+    const f32x4* const sp = base4 + (uint64_t)(src0 >> 6) * 64u * ld4 + (src0 & 63u);
+    f32x4* const dp = base4 + (uint64_t)(j0 >> 6) * 64u * ld4 + lane;
+    for (uint32_t cb = wv * kRmCols4; cb < ld4; cb += kRmWaves * kRmCols4) {
+      f32x4 v[kRmCols4];
+#pragma unroll
+      for (uint32_t u = 0; u < kRmCols4; ++u) {
+        v[u] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+        if (src != 0xFFFFFFFFu && cb + u < ld4) v[u] = sp[(uint64_t)(cb + u) * 64u];
+      }
+      __builtin_amdgcn_wave_barrier();  // every load of the pieces above is issued before the first store below
+#pragma unroll
+      for (uint32_t u = 0; u < kRmCols4; ++u)
+        if (cb + u < ld4) dp[(uint64_t)(cb + u) * 64u] = v[u];
+    }
+    __syncthreads();  // the map of this tile is read by every wave until here
   }
 }
 
@@ -534,13 +650,7 @@ int32_t plan_storage(vers_ivf* h, const uint32_t* lens, uint32_t k, hipStream_t 
       VERS_HIP_TRY(hipMemcpy(h->slot_len.p, sl.data(), (size_t)k * 4, hipMemcpyHostToDevice));
     }
   }
-  {
-    std::vector<uint32_t> asc(h->h_len);
-    std::sort(asc.begin(), asc.end());
-    h->len_asc_prefix.assign(k, 0);
-    uint64_t run = 0;
-    for (uint32_t i = 0; i < k; ++i) { run += asc[i]; h->len_asc_prefix[i] = run; }
-  }
+  h->set_len_asc_prefix();
   h->cap_rows = off;
   {
     std::vector<uint32_t> tl((size_t)(off / 64) ? (size_t)(off / 64) : 1, 0u);
@@ -1374,20 +1484,23 @@ int32_t upload_end_locked(vers_ivf* h) {
 constexpr int kAddBatchPhases = 9;
 static std::mutex g_ab_mu;
 static double g_ab[kAddBatchPhases] = {};  // calls, rows, re-layouts, stage, assign, group, relayout, place, derive (ms)
+constexpr int kRemovePhases = 8;
+static double g_rm[kRemovePhases] = {};  // vers_remove_phases: calls, ids, rows removed, stage, mark, compact, tables, derive (ms)
 struct AbClock {
   int slot;
+  double* acc;
   std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
-  explicit AbClock(int s) : slot(s) {}
+  explicit AbClock(int s, double* a = g_ab) : slot(s), acc(a) {}
   int32_t done() {  // the phase's work is finished when its clock stops
     VERS_HIP_TRY(hipStreamSynchronize(nullptr));
     std::lock_guard<std::mutex> lk(g_ab_mu);
-    g_ab[slot] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    acc[slot] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return VERS_OK;
   }
 };
-static void ab_count(int slot, double v) {
+static void ab_count(int slot, double v, double* acc = g_ab) {
   std::lock_guard<std::mutex> lk(g_ab_mu);
-  g_ab[slot] += v;
+  acc[slot] += v;
 }
 
 // |x|^2 (+ maximum), fp16 shadow (+ residual maximum) and row-major copy of the listed tiles: refresh_norms for a tile list, one launch per array
@@ -1407,8 +1520,9 @@ static int32_t refresh_tiles(vers_ivf* h, const uint32_t* tiles, uint32_t nt, hi
     h->shadow_valid = false;  // rows changed without their shadow following (as refresh_norms)
   }
   if (h->rows_rm.p) {
-    const uint64_t blocks = std::min<uint64_t>(65536, (n_rows * h->ld + 255) / 256);
-    hipLaunchKernelGGL(from_blocked_tiles_kernel, dim3((unsigned)blocks), dim3(256), 0, st, h->rows.as<float>(), h->ld, tiles, n_rows, h->rows_rm.as<float>());
+    const size_t lds = 64 * (size_t)(kGatherCols4 + 1) * sizeof(f32x4);
+    if (int32_t rc = scan_prepare_launch(tiles_to_rowmajor_kernel, lds)) return rc;
+    hipLaunchKernelGGL(tiles_to_rowmajor_kernel, dim3(nt), dim3(256), lds, st, (const float*)h->rows.as<float>(), h->ld, tiles, h->rows_rm.as<float>());
     VERS_HIP_TRY(hipGetLastError());
   }
   hipLaunchKernelGGL(row_norms_tiles_kernel, dim3((unsigned)((n_rows + 255) / 256)), dim3(256), 0, st, h->rows.as<float>(), h->ld,
@@ -1624,6 +1738,147 @@ int32_t add_batch_locked(vers_ivf* h, const float* rows_host, uint64_t row_strid
     if (rc) return rc;
     if (nan) return fail(VERS_ERR_NAN, "NaN distance in add_batch at row " + std::to_string(s0 + got) + " (reference panics)");
   }
+  return VERS_OK;
+}
+
+// ---- remove_batch: ids[assignments[v]].retain(|&x| x != v) for many v (see vers_hip.h) -----------------------------------------------
+// ids_host != nullptr: the ids go through the pinned buffer in chunks of option "remove_batch_ids" (default 1M ids = 8 MB), otherwise
+// ids_dev is read where it lies.  Nothing of the index is written before every id has passed the range check.
+int32_t remove_batch_locked(vers_ivf* h, const uint64_t* ids_host, const uint64_t* ids_dev, uint64_t n_ids, const vers_comm_t* comm,
+                            uint64_t* out_removed) {
+  VERS_HIP_TRY(hipDeviceSynchronize());  // searches still in flight on any stream read the rows and tables this call changes
+  if (out_removed) *out_removed = 0;
+  if (h->world > 1 && (comm == nullptr || comm->world != h->world || comm->rank != h->rank || !comm->all_gather))
+    return fail(VERS_ERR_INVALID, "vers_ivf_remove_batch: a sharded handle needs vers_ivf_remove_batch_dev with the build's vers_comm_t (every rank calls)");
+  if (n_ids == 0) return VERS_OK;
+  if (h->k == 0) {
+    if (h->up.open) return fail(VERS_ERR_EMPTY, "remove_batch while a streamed upload is in progress: the handle holds no index until vers_ivf_upload_end");
+    return fail(VERS_ERR_INVALID, "vers_ivf_remove_batch: vec id out of range (the index holds no vectors)");
+  }
+  const uint32_t k = h->k;
+  const uint64_t n = h->n_total;
+  const hipStream_t st = nullptr;
+  auto& rm = h->rm;
+  const size_t words = (size_t)((n + 31) / 32);
+  const uint64_t chunk = std::min<uint64_t>(n_ids, (uint64_t)std::max<int64_t>(1, opt_get("remove_batch_ids", 1 << 20)));
+  if (int32_t rc = rm.bitmap.reserve((words ? words : 1) * sizeof(uint32_t))) return rc;
+  if (int32_t rc = rm.cnt.reserve((2 * (size_t)k + 1) * sizeof(uint32_t))) return rc;
+  if (h->world > 1)
+    if (int32_t rc = rm.gath.reserve((size_t)h->world * k * sizeof(uint32_t))) return rc;
+  if (ids_host) {
+    if (int32_t rc = rm.ids.reserve(chunk * sizeof(uint64_t))) return rc;
+    if (rm.pin_cap < chunk * sizeof(uint64_t)) {
+      rm.free_pin();
+      VERS_HIP_TRY(hipHostMalloc(&rm.pin, chunk * sizeof(uint64_t), hipHostMallocDefault));
+      rm.pin_cap = chunk * sizeof(uint64_t);
+    }
+  }
+  uint32_t* const rm_cnt = rm.cnt.as<uint32_t>();
+  uint32_t* const first_tile = rm_cnt + k;
+  uint32_t* const bad = rm_cnt + 2 * (size_t)k;
+  ab_count(0, 1.0, g_rm);
+  ab_count(1, (double)n_ids, g_rm);
+  // 1. the ids as one bit per vec id, range-checked
+  VERS_HIP_TRY(hipMemsetAsync(rm.bitmap.p, 0, (words ? words : 1) * sizeof(uint32_t), st));
+  VERS_HIP_TRY(hipMemsetAsync(rm_cnt, 0, (size_t)k * sizeof(uint32_t), st));
+  VERS_HIP_TRY(hipMemsetAsync(first_tile, 0xFF, (size_t)k * sizeof(uint32_t), st));
+  VERS_HIP_TRY(hipMemsetAsync(bad, 0, sizeof(uint32_t), st));
+  for (uint64_t s0 = 0; s0 < n_ids; s0 += chunk) {
+    const uint64_t m = std::min<uint64_t>(chunk, n_ids - s0);
+    const uint64_t* src = ids_dev ? ids_dev + s0 : rm.ids.as<uint64_t>();
+    if (ids_host) {
+      AbClock clk(3, g_rm);
+      std::memcpy(rm.pin, ids_host + s0, (size_t)m * sizeof(uint64_t));
+      VERS_HIP_TRY(hipMemcpyAsync(rm.ids.p, rm.pin, (size_t)m * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+      if (int32_t rc = clk.done()) return rc;
+    }
+    AbClock clk(4, g_rm);
+    hipLaunchKernelGGL(remove_mark_ids_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, src, m, n, rm.bitmap.as<uint32_t>(), bad);
+    VERS_HIP_TRY(hipGetLastError());
+    if (int32_t rc = clk.done()) return rc;  // (the pinned chunk and rm.ids are free again)
+  }
+  std::vector<uint32_t> cnt_own(2 * (size_t)k), tot(k);
+  {
+    // 2. one pass over row_ids: rows removed per list, first tile of each list that loses one
+    AbClock clk(4, g_rm);
+    uint32_t any_bad = 0;
+    VERS_HIP_TRY(hipMemcpy(&any_bad, bad, sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (any_bad) return fail(VERS_ERR_INVALID, "vers_ivf_remove_batch: vec id >= n (assignments.len() = " + std::to_string(n) + "): nothing removed");
+    if (h->cap_rows) {
+      const uint64_t blocks = std::min<uint64_t>((uint64_t)h->n_cu * 8, (h->cap_rows + 255) / 256);
+      hipLaunchKernelGGL(remove_scan_rows_kernel, dim3((unsigned)blocks), dim3(256), 0, st, (const uint32_t*)h->row_ids.as<uint32_t>(), h->cap_rows,
+                         (const uint32_t*)rm.bitmap.as<uint32_t>(), n, (const uint32_t*)h->list_off.as<uint32_t>(), k, rm_cnt, first_tile);
+      VERS_HIP_TRY(hipGetLastError());
+    }
+    VERS_HIP_TRY(hipMemcpy(cnt_own.data(), rm_cnt, 2 * (size_t)k * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (h->world > 1) {  // the one exchange of the call: every rank's counts (zero for lists it does not own), summed
+      if (int32_t rc = comm_rc(comm->all_gather(comm->ctx, rm_cnt, rm.gath.p, (uint64_t)k * sizeof(uint32_t)), "all_gather")) return rc;
+      std::vector<uint32_t> all((size_t)h->world * k);
+      VERS_HIP_TRY(hipMemcpy(all.data(), rm.gath.p, all.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+      for (uint32_t c = 0; c < k; ++c) {
+        uint64_t s = 0;
+        for (uint32_t r = 0; r < h->world; ++r) s += all[(size_t)r * k + c];
+        tot[c] = (uint32_t)std::min<uint64_t>(s, 0xFFFFFFFFull);
+      }
+    } else {
+      std::copy(cnt_own.begin(), cnt_own.begin() + k, tot.begin());
+    }
+    if (int32_t rc = clk.done()) return rc;
+  }
+  // 3. jobs of the owned lists that lose rows, the tiles they touch, the new global lengths -- all checked before anything is written
+  std::vector<uint32_t> nl(h->h_len);
+  std::vector<RemoveJob> jobs;
+  std::vector<uint32_t> tiles;
+  uint64_t removed = 0;
+  for (uint32_t c = 0; c < k; ++c) {
+    if (tot[c] > h->h_len[c]) return fail(VERS_ERR_HIP, "vers_ivf_remove_batch: more rows of a list marked than it holds (inconsistent index)");
+    nl[c] -= tot[c];
+    removed += tot[c];
+    if (!cnt_own[c]) continue;
+    const uint32_t t0 = h->h_off[c] / 64u, t_end = (uint32_t)(((uint64_t)h->h_off[c] + h->h_len[c] + 63) / 64), ft = cnt_own[k + c];
+    if (h->h_owner[c] != h->rank || ft < t0 || ft >= t_end || (uint64_t)t_end * 64 > (uint64_t)h->h_off[c] + h->h_cap[c] || (uint64_t)t_end * 64 > h->cap_rows)
+      return fail(VERS_ERR_HIP, "vers_ivf_remove_batch: a marked row lies outside its list (inconsistent index)");
+    jobs.push_back(RemoveJob{h->h_off[c], h->h_len[c], ft - t0});
+    for (uint32_t t = ft; t < t_end; ++t) tiles.push_back(t);
+  }
+  if (removed == 0) return VERS_OK;
+  const uint32_t nj = (uint32_t)jobs.size(), nt = (uint32_t)tiles.size();
+  const size_t jobs_b = (size_t)nj * sizeof(RemoveJob);
+  {
+    AbClock clk(5, g_rm);
+    if (nj) {
+      if (int32_t rc = rm.jobs.reserve(jobs_b + (size_t)nt * sizeof(uint32_t))) return rc;
+      VERS_HIP_TRY(hipMemcpy(rm.jobs.p, jobs.data(), jobs_b, hipMemcpyHostToDevice));
+      VERS_HIP_TRY(hipMemcpy(rm.jobs.as<char>() + jobs_b, tiles.data(), (size_t)nt * sizeof(uint32_t), hipMemcpyHostToDevice));
+      hipLaunchKernelGGL(remove_compact_kernel, dim3(nj), dim3(kRmWaves * 64), 0, st, (const RemoveJob*)rm.jobs.p, (const uint32_t*)rm.bitmap.as<uint32_t>(), n,
+                         h->ld, h->rows.as<float>(), h->row_ids.as<uint32_t>());
+      VERS_HIP_TRY(hipGetLastError());
+    }
+    if (int32_t rc = clk.done()) return rc;
+  }
+  {
+    // 4. tables: lengths by list and by slot (the slot ORDER is a scheduling heuristic and stays), the host's copies, and what the
+    // host derives from the lengths: the longest list and len_asc_prefix (reference-mode depth, reference-mode batches as nprobe = 1)
+    AbClock clk(6, g_rm);
+    std::vector<uint32_t> sl(k);
+    for (uint32_t c = 0; c < k; ++c) sl[h->h_slot[c]] = nl[c];
+    VERS_HIP_TRY(hipMemcpy(h->list_len.p, nl.data(), (size_t)k * sizeof(uint32_t), hipMemcpyHostToDevice));
+    VERS_HIP_TRY(hipMemcpy(h->slot_len.p, sl.data(), (size_t)k * sizeof(uint32_t), hipMemcpyHostToDevice));
+    h->h_len = nl;
+    h->max_len = 0;
+    for (uint32_t c = 0; c < k; ++c) h->max_len = std::max(h->max_len, nl[c]);
+    h->set_len_asc_prefix();
+    if (int32_t rc = clk.done()) return rc;
+  }
+  {
+    // 5. derived arrays of the touched tiles.  The running maxima in pre_misc (max |x|^2, max fp16 residual) only grow: after a removal
+    // they are still upper bounds of what the certificates charge, merely not tight.
+    AbClock clk(7, g_rm);
+    if (int32_t rc = refresh_tiles(h, (const uint32_t*)(rm.jobs.as<char>() + jobs_b), nt, st)) return rc;
+    if (int32_t rc = clk.done()) return rc;
+  }
+  ab_count(2, (double)removed, g_rm);
+  if (out_removed) *out_removed = removed;
   return VERS_OK;
 }
 }  // namespace ivf
@@ -1843,6 +2098,38 @@ int32_t vers_ivf_add_batch_dev(vers_ivf_t* h, const float* rows_dev, uint64_t n,
   std::unique_lock<std::shared_mutex> lk(h->index);
   DeviceGuard g(h->device);
   return add_batch_locked(h, nullptr, 0, rows_dev, ld_floats, n, nullptr, out_clusters_dev, out_first_vec_id, out_added);
+}
+
+int32_t vers_ivf_remove_batch(vers_ivf_t* h, const uint64_t* vec_ids, uint64_t n_ids, uint64_t* out_removed) {
+  if (!h || (n_ids && !vec_ids)) return fail(VERS_ERR_INVALID, "vers_ivf_remove_batch: bad arguments");
+  std::unique_lock<std::shared_mutex> lk(h->index);
+  DeviceGuard g(h->device);
+  return remove_batch_locked(h, vec_ids, nullptr, n_ids, nullptr, out_removed);
+}
+
+int32_t vers_ivf_remove_batch_dev(vers_ivf_t* h, const uint64_t* vec_ids_dev, uint64_t n_ids, const vers_comm_t* comm, uint64_t* out_removed) {
+  if (!h || (n_ids && !vec_ids_dev)) return fail(VERS_ERR_INVALID, "vers_ivf_remove_batch_dev: bad arguments");
+  std::unique_lock<std::shared_mutex> lk(h->index);
+  DeviceGuard g(h->device);
+  return remove_batch_locked(h, nullptr, vec_ids_dev, n_ids, comm, out_removed);
+}
+
+int32_t vers_ivf_live_count(vers_ivf_t* h, uint64_t* out_live) {
+  if (!h || !out_live) return fail(VERS_ERR_INVALID, "vers_ivf_live_count: bad arguments");
+  std::shared_lock<std::shared_mutex> lk(h->index);
+  uint64_t live = 0;
+  for (uint32_t c = 0; c < h->k; ++c) live += h->h_len[c];
+  *out_live = live;
+  return VERS_OK;
+}
+
+int32_t vers_remove_phases(double* out, int32_t reset) {
+  std::lock_guard<std::mutex> lk(g_ab_mu);
+  if (out)
+    for (int i = 0; i < kRemovePhases; ++i) out[i] = g_rm[i];
+  if (reset)
+    for (double& v : g_rm) v = 0.0;
+  return VERS_OK;
 }
 
 int32_t vers_add_batch_phases(double* out, int32_t reset) {

@@ -160,6 +160,7 @@ int32_t vers_ivf_destroy(vers_ivf_t* h) {
   if (h->st_pin) (void)hipHostFree(h->st_pin);
   h->up.close();
   h->ab.free_pin();
+  h->rm.free_pin();
   delete h;
   return VERS_OK;
 }

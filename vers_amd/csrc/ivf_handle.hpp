@@ -134,8 +134,16 @@ struct vers_ivf {
   // Reference mode from device pointers cannot come back for a deeper ranking (the host-pointer entry retries; a _dev call
   // only latches a status), so the depth is decided UP FRONT from what the host knows: the walk of ivfflat.rs:166-195 stops
   // once top_k rows are gathered, and ANY P lists hold at least the sum of the P SHORTEST lists' lengths.  len_asc_prefix[i]
-  // = rows in the i + 1 shortest lists (as of build / upload; add() only lengthens lists, the bound stays valid).
+  // = rows in the i + 1 shortest lists as of build / upload / the last removal: add() only lengthens lists, the bound stays valid;
+  // remove_batch shortens them and recomputes it from the new global lengths (set_len_asc_prefix).
   std::vector<uint64_t> len_asc_prefix;
+  void set_len_asc_prefix() {  // from h_len
+    std::vector<uint32_t> asc(h_len);
+    std::sort(asc.begin(), asc.end());
+    len_asc_prefix.assign(asc.size(), 0);
+    uint64_t run = 0;
+    for (size_t i = 0; i < asc.size(); ++i) { run += asc[i]; len_asc_prefix[i] = run; }
+  }
   uint32_t lists_that_always_suffice(uint32_t top_k) const {  // smallest P such that every set of P lists holds >= top_k rows (k if none)
     const auto it = std::lower_bound(len_asc_prefix.begin(), len_asc_prefix.end(), (uint64_t)top_k);
     return it == len_asc_prefix.end() ? (uint32_t)len_asc_prefix.size() : (uint32_t)(it - len_asc_prefix.begin()) + 1u;
@@ -181,6 +189,18 @@ struct vers_ivf {
       pin = nullptr; pin_cap = 0;
     }
   } ab;
+  // vers_ivf_remove_batch / _remove_batch_dev (ivf_build.hip): scratch kept between calls (the callers hold the handle exclusively).
+  // bitmap: one bit per vec id | ids: one staged chunk of the host call | cnt: u32 [k] rows removed per list, [k] first tile that
+  // loses a row, [1] range-check flag | gath: the ranks' counts of a sharded handle | jobs: compaction jobs + the touched tiles.
+  struct RemoveState {
+    DevBuf bitmap, ids, cnt, gath, jobs;
+    void* pin = nullptr;  // pinned staging of the host-pointer call: one chunk of ids
+    size_t pin_cap = 0;
+    void free_pin() {
+      if (pin) (void)hipHostFree(pin);
+      pin = nullptr; pin_cap = 0;
+    }
+  } rm;
   // matrix-core list scan (prescan.hip.h): |x|^2 per storage row, [0] max |x|^2 bits, [1] certificate failures (running)
   DevBuf xnorm, pre_misc;
   // fp16 shadow of the rows for the matrix-core pre-selection (+50 % corpus memory; VERS_SHADOW=0 or a failed

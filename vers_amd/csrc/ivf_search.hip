@@ -357,7 +357,7 @@ int32_t search_dev_locked(vers_ivf* h, const float* q_dev, uint64_t ldq_in, uint
   if (h->k == 0) return fail(VERS_ERR_INSUFFICIENT, "search on an index without centroids (reference: index out of bounds, ivfflat.rs:169)");
   // The reference's own mode (nprobe = 0: the nearest list, spilling into the next ones while the result is short, ivfflat.rs:166-195) IS
   // nprobe = 1 whenever no list is shorter than top_k -- nothing can spill: the nearest list's top_k by (distance, list position) either
-  // way.  The handle knows its shortest list (lists_that_always_suffice; add() only lengthens lists), so a BATCH in that mode takes
+  // way.  The handle knows its shortest list (lists_that_always_suffice: add() only lengthens lists, remove_batch recomputes it), so a BATCH in that mode takes
   // the nprobe path: the matrix-core scan of the fp16 shadow + exact finish instead of the ordered chains over the f32 rows (half the
   // bytes: 1.52 -> 0.7 ms per 1024 queries at cfg3).  Single queries keep the f32 tile-per-block scan (scan1t_kernel: one list is
   // latency-bound, the exact finish would cost more than it saves).  option "ref_as_nprobe1" = 0: the ordered chains (A/B runs).

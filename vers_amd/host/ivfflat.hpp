@@ -114,6 +114,33 @@ class IVFFlatIndex {
     check(rc);
   }
 
+  // Removal (extension, vers_ivf_remove_batch): ids[assignments[v]].retain(|&x| x != v) for every listed v.  values and assignments keep
+  // their entries (positions are vec ids).  An id >= assignments.size() throws and removes nothing.  Returns the rows that left the index.
+  size_t remove_batch(const std::vector<size_t>& vec_ids) {
+    std::vector<uint64_t> v(vec_ids.begin(), vec_ids.end());
+    uint64_t removed = 0;
+    check(vers_ivf_remove_batch(handle(), v.data(), v.size(), &removed));
+    size_t gone = 0;
+    std::vector<bool> mark(assignments.size(), false);
+    for (size_t x : vec_ids) mark[x] = true;
+    for (auto& l : ids) {
+      size_t w = 0;
+      for (size_t x : l)
+        if (!mark[x]) l[w++] = x;
+      gone += l.size() - w;
+      l.resize(w);
+    }
+    if (gone != removed) throw Panic(VERS_ERR_INVALID, "remove_batch: the device removed another number of rows than the host lists hold");
+    return gone;
+  }
+
+  // vectors currently in the lists (vers_ivf_live_count)
+  size_t live_count() const {
+    uint64_t live = 0;
+    check(vers_ivf_live_count(handle(), &live));
+    return (size_t)live;
+  }
+
   // Index::search_approximate (ivfflat.rs:153-198)
   std::vector<std::pair<size_t, float>> search_approximate(const Vector<N>& query, size_t top_k) const {
     std::vector<uint64_t> oi(top_k ? top_k : 1);
@@ -171,6 +198,16 @@ class IVFFlatIndex {
       std::vector<uint64_t> a(assignments.begin(), assignments.end());
       check(vers_ivf_upload(h_, values.empty() ? nullptr : values[0].v, values.size(), sizeof(Vector<N>),
                             centroids.empty() ? nullptr : centroids[0].v, centroids.size(), sizeof(Vector<N>), a.data()));
+      // vers_ivf_upload implies ids[c] = every position with assignments == c: positions missing from the loaded lists were removed
+      // before the index was saved and leave the cache again (none in a file the reference wrote)
+      std::vector<bool> in_list(assignments.size(), false);
+      for (auto& l : ids)
+        for (size_t x : l)
+          if (x < in_list.size()) in_list[x] = true;
+      std::vector<uint64_t> gone;
+      for (size_t v = 0; v < in_list.size(); ++v)
+        if (!in_list[v]) gone.push_back(v);
+      if (!gone.empty() && !centroids.empty()) check(vers_ivf_remove_batch(h_, gone.data(), gone.size(), nullptr));
     }
     return h_;
   }

@@ -121,6 +121,36 @@ class IVFFlatIndex:
                                            C.byref(added)))
         return int(first.value), int(added.value)
 
+    # -- removal (extension; the reference has none): ids[assignments[v]].retain(|&x| x != v) ---------
+    def remove_batch(self, vec_ids):
+        """Removes the listed vec ids from their inverted lists (vers_ivf_remove_batch): `ids` loses them, `values` and
+        `assignments` keep their entries (positions are vec ids).  Any order, repeats allowed, ids already gone are skipped;
+        an id >= len(assignments) raises and removes nothing.  Returns the number of rows that left the index."""
+        v = np.ascontiguousarray(np.asarray(vec_ids, dtype=np.uint64).reshape(-1))
+        removed = C.c_uint64(0)
+        check(lib().vers_ivf_remove_batch(self._h, _ptr(v) if v.size else None, v.size, C.byref(removed)))
+        gone = set(v.tolist())
+        expect = 0
+        for c, lst in enumerate(self.ids):
+            kept = [x for x in lst if x not in gone]
+            expect += len(lst) - len(kept)
+            self.ids[c] = kept
+        assert removed.value == expect, (removed.value, expect)
+        return int(removed.value)
+
+    def remove_batch_dev(self, ids_ptr: int, n: int, comm=None):
+        """vers_ivf_remove_batch_dev on a device array of u64 vec ids; comm: the vers_amd.dist.TorchComm of a sharded handle
+        (every rank calls with the same ids).  The host fields are NOT mirrored.  Returns the number of rows removed."""
+        removed = C.c_uint64(0)
+        check(lib().vers_ivf_remove_batch_dev(self._h, _vp(ids_ptr) if n else None, n, comm.ptr() if comm is not None else None,
+                                              C.byref(removed)))
+        return int(removed.value)
+
+    def live_count(self):
+        live = C.c_uint64(0)
+        check(lib().vers_ivf_live_count(self._h, C.byref(live)))
+        return int(live.value)
+
     # -- Index::search_approximate (ivfflat.rs:153-198) ---------------------------------------------
     def search_approximate(self, query, top_k: int):
         ids, dist, cnt = self.search_batch(np.asarray(query, dtype=np.float32).reshape(1, self.d), top_k, nprobe=0)
@@ -352,6 +382,16 @@ class IVFFlatIndex:
         self.num_centroids, self.values, self.centroids = f["num_centroids"], f["values"], f["centroids"]
         self.assignments, self.ids = f["assignments"], f["ids"]
         self._upload()
+        # vers_ivf_upload implies ids[c] = every position with assignments == c; positions missing from the file's lists were
+        # removed before it was saved and leave the device cache again (none in a file the reference wrote)
+        in_list = np.zeros(len(self.assignments), dtype=bool)
+        for lst in self.ids:
+            in_list[np.asarray(lst, dtype=np.int64)] = True
+        gone = np.flatnonzero(~in_list).astype(np.uint64)
+        if gone.size and len(self.centroids):
+            removed = C.c_uint64(0)
+            check(lib().vers_ivf_remove_batch(self._h, _ptr(gone), gone.size, C.byref(removed)))
+            assert removed.value == gone.size, (removed.value, gone.size)
         return self
 
 
