@@ -343,7 +343,7 @@ int32_t vers_ivf_build_sharded_dev(vers_ivf_t* h, const float* rows_dev, uint64_
  *               vers_ivf_search_exhaustive* ranks live rows, out_count = min(top_k, live).
  *   getters   : vers_ivf_get_list, vers_ivf_list_lengths and the longest list of vers_ivf_info report the shortened lists.
  *   add       : vers_ivf_add / _add_batch afterwards append behind a list's survivors, into the freed rows (capacity is kept: the freed
- *               rows become the list's slack, storage never shrinks).
+ *               rows become the list's slack; vers_ivf_compact gives the storage back).
  *   vec_ids   : any order, repeats allowed; an id that is in no list any more (removed earlier, or repeated in the call) is skipped.
  *               *out_removed = distinct rows that left the index.  ANY id >= n -> VERS_ERR_INVALID and NOTHING is removed (all ids are
  *               checked before anything is written).  n_ids == 0: no-op.  A streamed upload in progress: VERS_ERR_EMPTY (as add).
@@ -356,7 +356,8 @@ int32_t vers_ivf_build_sharded_dev(vers_ivf_t* h, const float* rows_dev, uint64_
  *               removed.  (A rank that fails locally before the exchange returns its error without entering it: the host aborts the
  *               group on any non-zero return, as for the sharded build.)
  * Synchronous; holds the handle exclusively and waits for searches in flight, like vers_ivf_add_batch.  The running maxima the search
- * certificates charge (max |x|^2, max fp16 residual) are not re-tightened: after a removal they are still upper bounds, results are exact. */
+ * certificates charge (max |x|^2, max fp16 residual) are not re-tightened by a removal: they stay upper bounds, results are exact;
+ * vers_ivf_compact recomputes them over the rows the lists still hold. */
 int32_t vers_ivf_remove_batch(vers_ivf_t* h, const uint64_t* vec_ids, uint64_t n_ids, uint64_t* out_removed);
 int32_t vers_ivf_remove_batch_dev(vers_ivf_t* h, const uint64_t* vec_ids_dev, uint64_t n_ids, const vers_comm_t* comm,
                                   uint64_t* out_removed);
@@ -367,6 +368,31 @@ int32_t vers_ivf_live_count(vers_ivf_t* h, uint64_t* out_live);
  * pass over row_ids, a sharded handle's exchange), [5] compaction, [6] length tables, [7] derived arrays (|x|^2, shadow, row-major
  * copy of the touched tiles).  reset != 0 zeroes them. */
 int32_t vers_remove_phases(double* out8, int32_t reset);
+/* Compaction (extension; in the reference's terms: nothing -- ids[c].shrink_to_fit()).  Nothing observable through the reference's five
+ * fields changes: n of vers_ivf_info, the vec id the next add hands out, centroids, live count, every list's rows, ids and order, and every
+ * search result in every mode and on every path, bit for bit.  What changes is the storage behind them:
+ *   storage   : every owned list goes back to the capacity a fresh upload of the CURRENT lengths plans (len + max(8, len / 16) rounded up
+ *               to 64 rows; lists in ascending order on tile boundaries; 0 for another rank's list), with every table as after that
+ *               upload.  *out_rows_before / *out_rows_after (nullable): storage rows of this handle before and after.
+ *   maxima    : max |x|^2 and the fp16 residual maximum the search certificates charge are recomputed over the rows the lists hold --
+ *               an outlier that was added and removed stops widening every later certificate window -- and the fp16 shadow's
+ *               self-retirement state restarts as at an upload: a shadow that an element beyond +-65504 had retired comes back once
+ *               that row is removed.
+ *   options   : "shadow", "rowmajor" and "memory" are read as a build reads them (a handle compacted under "memory" = 1 drops its
+ *               row-major copy).  "compact_fused" (1): one kernel moves a tile and writes its shadow, row-major rows, |x|^2 and maxima
+ *               from the same read; 0: copies, then the passes of an upload over the new storage.  Same bits either way.
+ *   memory    : the old shadow and row-major copy are released before the new arrays are allocated; the old tiles are freed after the
+ *               move.  When the new derived arrays do not fit beside the old tiles the call takes the unfused sequence (new tiles, move,
+ *               free, derive) instead of failing; when not even the new tiles fit: VERS_ERR_HIP, the OLD index stays intact and
+ *               searchable.
+ *   sharded   : purely local (list lengths are global already): no communicator, ranks call it or not independently.
+ * Synchronous; holds the handle exclusively and waits for searches in flight, like vers_ivf_add_batch.  No centroids: VERS_OK, nothing to
+ * do, both outputs 0.  A streamed upload in progress: VERS_ERR_EMPTY (as add / remove). */
+int32_t vers_ivf_compact(vers_ivf_t* h, uint64_t* out_rows_before, uint64_t* out_rows_after);
+/* The compact calls of this process by PHASE (host wall clock in ms, the stream synchronised at each phase's end).  out[8]: [0] calls,
+ * [1] storage rows before, [2] storage rows after (summed over the calls), [3] planning + allocation, [4] the move (fused: with every
+ * derived array), [5] derived arrays on the unfused path, [6] tables, [7] reserved.  reset != 0 zeroes them. */
+int32_t vers_compact_phases(double* out8, int32_t reset);
 /* Process-wide switches: every one is a named option set here (or, for a process one does not control from inside, through the ONE
  * environment variable VERS_OPTIONS="name=value,name=value", read once; besides it the library reads only VERS_SHADOW and
  * VERS_ROWMAJOR, the two memory switches of INTEGRATION.md = options "shadow" / "rowmajor").  Unknown name: VERS_ERR_INVALID.
@@ -403,7 +429,8 @@ int32_t vers_remove_phases(double* out8, int32_t reset);
  *   "wide_k" (1)        results of 49 .. 200 keys (batches, nprobe >= 1) stay on the matrix-core list scan with candidate lists four keys
  *                       per lane wide; 0 = the ordered chains, 64 ranks per pass.
  *   "coarse1" (1), "scan1t" (1), "ref_as_nprobe1" (1), "assign_tiles" (1), "assign_tiles_min" (64), "seg_rows" (0), "pre_slack" (0),
- *   "upload_stage_mb" (256), "add_batch_rows" (131072), "remove_batch_ids" (1048576)   kernel-choice and sizing knobs of DESIGN.md section 5.
+ *   "upload_stage_mb" (256), "add_batch_rows" (131072), "remove_batch_ids" (1048576), "compact_fused" (1)   kernel-choice and sizing knobs of
+ *                       DESIGN.md section 5.
  *   "scan_debug" (0), "poison_alloc" (-1), "poison_slack_bits" (-1), "test_fail_sharded" (0)   diagnosis: phase stamps / skipped
  *                       phases, new device buffers filled with a byte, slack rows filled with an f32 bit pattern, the next n sharded
  *                       searches fail locally. */

@@ -101,6 +101,8 @@ SIGNATURES = {
     "vers_build_phases": (C.c_int32, [C.POINTER(C.c_double), C.c_int32]),
     "vers_add_batch_phases": (C.c_int32, [C.POINTER(C.c_double), C.c_int32]),
     "vers_remove_phases": (C.c_int32, [C.POINTER(C.c_double), C.c_int32]),
+    "vers_ivf_compact": (C.c_int32, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "vers_compact_phases": (C.c_int32, [C.POINTER(C.c_double), C.c_int32]),
     "vers_kmeans_update": (C.c_int32, [C.c_int32, _vp, C.c_uint64, C.c_uint64, _vp, C.c_uint64, C.c_uint32, _vp]),
     "vers_kmeans_cost": (C.c_int32, [C.c_int32, _vp, C.c_uint64, C.c_uint64, _vp, C.c_uint64, C.c_uint64, _vp, C.c_uint32,
                                      C.POINTER(C.c_float)]),
@@ -318,6 +320,14 @@ def remove_phases(reset=False) -> dict:
     v = (C.c_double * 8)()
     check(lib().vers_remove_phases(v, 1 if reset else 0))
     keys = ("calls", "ids", "removed", "stage_ms", "mark_ms", "compact_ms", "tables_ms", "derive_ms")
+    return dict(zip(keys, (float(x) for x in v)))
+
+
+def compact_phases(reset=False) -> dict:
+    """The compact calls of this process by phase, host wall clock in ms (vers_compact_phases)."""
+    v = (C.c_double * 8)()
+    check(lib().vers_compact_phases(v, 1 if reset else 0))
+    keys = ("calls", "rows_before", "rows_after", "plan_ms", "move_ms", "derive_ms", "tables_ms", "reserved")
     return dict(zip(keys, (float(x) for x in v)))
 
 

@@ -348,6 +348,98 @@ __global__ __launch_bounds__(256) void tiles_to_rowmajor_kernel(const float* in,
   }
 }
 
+// ---- vers_ivf_compact: whole tiles move to a tighter storage plan, every derived array written from the one read -------------------------
+// Lists start on tile boundaries and a removal has already closed the gaps inside a list, so the ceil(len / 64) tiles of an owned list
+// move as they lie: one job = one tile, from the old storage to the new one.
+struct CompactJob {
+  uint32_t src, dst;  // tile indices (storage row / 64) in the old and in the new plan
+};
+// One BLOCK per job.  The tile's 1 KiB pieces are read ONCE, kGatherCols4 float4 columns per pass (a tile of d = 768 is 196 KB: more than
+// the CU's LDS), and from that one read leave as
+//   * the destination f32 tile, whole pieces, straight from the registers that loaded them;
+//   * the row-major rows (dst_rm != nullptr), whole-row runs out of LDS -- tiles_to_rowmajor_kernel's second half;
+//   * the fp16 shadow tile (dst_h != nullptr) in row_to_f16's A-operand layout, the same conversion, one 1 KiB piece per wave store;
+//   * |x|^2 (wave 0, a row per lane) and the fp16 residual (wave 1, a row per lane; only with a shadow, as refresh_norms): the f32
+//     chains of row_norm_blocked / row_shadow_residual over the columns in storage order, the accumulator staying in its register from
+//     pass to pass -- the same sums bit for bit.  Both maxima: one atomicMax per block after a reduction over the wave that holds them.
+// A row whose row_ids entry is 0xFFFFFFFF (slack inside a list's last tile) moves like the others -- nothing may depend on what it
+// holds -- but gets xnorm 0.0f and raises no maximum.  row_ids of the tile are copied by the same block.
+// The barriers order LDS traffic only: nothing a block writes to memory is read by it, its stores stay in flight across the passes.
+__global__ __launch_bounds__(256) void compact_tiles_kernel(const CompactJob* jobs, uint32_t ld, const float* src_rows, const uint32_t* src_ids,
+                                                            float* dst_rows, uint32_t* dst_ids, uint16_t* dst_h, float* dst_rm, float* xnorm,
+                                                            uint32_t* xmax2_bits, uint32_t* rmax2_bits) {
+  extern __shared__ __attribute__((aligned(16))) f32x4 tl[];  // [64][kGatherCols4 + 1]
+  const CompactJob jb = jobs[blockIdx.x];
+  const uint32_t tid = threadIdx.x, ld4 = ld / 4;
+  const f32x4* in = reinterpret_cast<const f32x4*>(src_rows + (uint64_t)jb.src * 64ull * ld);
+  f32x4* out = reinterpret_cast<f32x4*>(dst_rows + (uint64_t)jb.dst * 64ull * ld);
+  f32x4* rm = dst_rm ? reinterpret_cast<f32x4*>(dst_rm + (uint64_t)jb.dst * 64ull * ld) : nullptr;
+  uint16_t* sh = dst_h ? dst_h + (uint64_t)jb.dst * 64ull * ld : nullptr;
+  uint32_t my_id = 0xFFFFFFFFu;  // waves 0 and 1: the vec id of row tid % 64
+  if (tid < 128u) my_id = src_ids[(uint64_t)jb.src * 64ull + (tid & 63u)];
+  if (tid < 64u) dst_ids[(uint64_t)jb.dst * 64ull + tid] = my_id;
+  float acc = 0.0f;  // wave 0: |x|^2 of row tid, wave 1: residual of row tid - 64
+  constexpr uint32_t kPitch = kGatherCols4 + 1;
+  for (uint32_t c0 = 0; c0 < ld4; c0 += kGatherCols4) {
+    const uint32_t nc = ld4 - c0 < kGatherCols4 ? ld4 - c0 : kGatherCols4;  // (ld is a multiple of 64: nc is a multiple of 16)
+    for (uint32_t i = tid; i < 64u * nc; i += 256u) {  // a piece's 64 rows by consecutive threads: 1 KiB contiguous in, 1 KiB contiguous out
+      const uint32_t j = i / 64u, r = i % 64u;
+      const f32x4 v = in[(uint64_t)(c0 + j) * 64 + r];
+      out[(uint64_t)(c0 + j) * 64 + r] = v;
+      tl[r * kPitch + j] = v;
+    }
+    lds_barrier();
+    if (rm)
+      for (uint32_t i = tid; i < 64u * kGatherCols4; i += 256u) {  // a row's float4s by consecutive threads
+        const uint32_t r = i / kGatherCols4, j = i % kGatherCols4;
+        if (j < nc) rm[(uint64_t)r * ld4 + c0 + j] = tl[r * kPitch + j];
+      }
+    if (sh)
+      for (uint32_t i = tid; i < 32u * nc; i += 256u) {  // a shadow piece (16 columns x 32 rows) by the 64 lanes of a wave
+        const uint32_t piece = i / 64u, l = i % 64u;
+        const uint32_t r = (piece & 1u) * 32u + (l & 31u), g = (piece >> 1) * 2u + (l >> 5);  // row, group of 8 columns of this pass
+        f16x8_t o;
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+          const f32x4 x = tl[r * kPitch + 2u * g + h];
+#pragma unroll
+          for (int u = 0; u < 4; ++u) o[4 * h + u] = (_Float16)x[u];  // v_cvt_f16_f32: RNE, inf / NaN preserved (row_to_f16)
+        }
+        *reinterpret_cast<f16x8_t*>(sh + ((uint64_t)(c0 / 2u) * 64u + i) * 8u) = o;  // piece (c0 / 4 + piece / 2, piece % 2), lane l
+      }
+    if (tid < 64u) {
+      const f32x4* row = tl + tid * kPitch;
+      for (uint32_t j = 0; j < nc; ++j) {
+        const f32x4 v = row[j];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) acc = __fadd_rn(acc, __fmul_rn(v[u], v[u]));
+      }
+    } else if (tid < 128u && sh) {
+      const f32x4* row = tl + (tid - 64u) * kPitch;
+      for (uint32_t j = 0; j < nc; ++j) {
+        const f32x4 v = row[j];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          const float dlt = v[u] - (float)(_Float16)v[u];
+          acc = __fadd_rn(acc, __fmul_rn(dlt, dlt));
+        }
+      }
+    }
+    lds_barrier();
+  }
+  if (tid < 128u) {
+    const bool holds_vector = my_id != 0xFFFFFFFFu;
+    if (tid < 64u) xnorm[(uint64_t)jb.dst * 64ull + tid] = holds_vector ? acc : 0.0f;
+    uint32_t top = holds_vector && acc == acc ? __float_as_uint(acc) : 0u;  // acc >= 0: bit order == value order
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {
+      const uint32_t other = (uint32_t)__shfl_xor((int)top, o);
+      top = other > top ? other : top;
+    }
+    if ((tid & 63u) == 0 && top != 0u && (tid < 64u || sh)) atomicMax(tid < 64u ? xmax2_bits : rmax2_bits, top);
+  }
+}
+
 // ---- vers_ivf_remove_batch: marking and in-place compaction of the lists that lose rows ------------------------------------------------
 // The ids of a call become one bit per vec id; *bad != 0: one of them is >= n_total (nothing of the index has been written by then).
 __global__ void remove_mark_ids_kernel(const uint64_t* ids, uint64_t m, uint64_t n_total, uint32_t* bitmap, uint32_t* bad) {
@@ -609,10 +701,57 @@ struct Agreement {
 
 // Storage plan from the GLOBAL list lengths: owners (LPT when sharded), offsets and capacities of the owned lists,
 // device tables, zeroed row ids.
+// The storage rule, shared by plan_storage and vers_ivf_compact: offsets and capacities of the lists this rank owns (h_owner / rank),
+// lists in ascending order, each starting on a tile boundary; another rank's list gets no storage.  *total = storage rows.
+static int32_t plan_capacities(const vers_ivf* h, const uint32_t* lens, uint32_t k, std::vector<uint32_t>& offs, std::vector<uint32_t>& caps,
+                               uint64_t* total) {
+  offs.assign(k, 0);
+  caps.assign(k, 0);
+  uint64_t off = 0;
+  for (uint32_t c = 0; c < k; ++c) {
+    const uint32_t len = lens[c];
+    const bool mine = h->h_owner[c] == h->rank;
+    // slack for `add` behind the list: 1/16 of its length, at least 8 rows, then up to the tile boundary the next list starts on.
+    // (Rounds 1-5 kept at least 64: at k = 65536 over 6.25M rows -- lists of ~95 rows -- that alone doubled the storage; a list
+    // that outgrows its slack is re-laid-out with 1/8 of head-room, relayout().)
+    const uint32_t cap = mine ? round_up(len + std::max<uint32_t>(8u, len / 16u), 64u) : 0u;
+    offs[c] = (uint32_t)off;
+    caps[c] = cap;
+    off += cap;
+    if (off > 0xFFFFFFFFull) return fail(VERS_ERR_INVALID, "more than 2^32-1 storage rows on one GPU");
+  }
+  *total = off;
+  return VERS_OK;
+}
+// Slot tables from h_len / h_off: longest lists first (stable: ties by index); add() changes lengths by one at a time, the order is kept as it is
+static int32_t write_slot_tables(vers_ivf* h, uint32_t k) {
+  std::vector<uint32_t> ord(k), so(k ? k : 1), sl(k ? k : 1);
+  for (uint32_t c = 0; c < k; ++c) ord[c] = c;
+  std::stable_sort(ord.begin(), ord.end(), [&](uint32_t x, uint32_t y) { return h->h_len[x] > h->h_len[y]; });
+  h->h_slot.assign(k, 0);
+  for (uint32_t i = 0; i < k; ++i) { h->h_slot[ord[i]] = i; so[i] = h->h_off[ord[i]]; sl[i] = h->h_len[ord[i]]; }
+  if (int32_t rc = h->list_slot.reserve((k ? k : 1) * sizeof(uint32_t))) return rc;
+  if (int32_t rc = h->slot_off.reserve((k ? k : 1) * sizeof(uint32_t))) return rc;
+  if (int32_t rc = h->slot_len.reserve((k ? k : 1) * sizeof(uint32_t))) return rc;
+  if (k) {
+    VERS_HIP_TRY(hipMemcpy(h->list_slot.p, h->h_slot.data(), (size_t)k * 4, hipMemcpyHostToDevice));
+    VERS_HIP_TRY(hipMemcpy(h->slot_off.p, so.data(), (size_t)k * 4, hipMemcpyHostToDevice));
+    VERS_HIP_TRY(hipMemcpy(h->slot_len.p, sl.data(), (size_t)k * 4, hipMemcpyHostToDevice));
+  }
+  return VERS_OK;
+}
+// tile_list from h_off / h_cap / cap_rows
+static int32_t write_tile_list(vers_ivf* h, uint32_t k) {
+  std::vector<uint32_t> tl((size_t)(h->cap_rows / 64) ? (size_t)(h->cap_rows / 64) : 1, 0u);
+  for (uint32_t c = 0; c < k; ++c)
+    for (uint32_t r = 0; r < h->h_cap[c]; r += 64) tl[(h->h_off[c] + r) / 64] = c;
+  if (int32_t rc = h->tile_list.reserve(tl.size() * sizeof(uint32_t))) return rc;
+  VERS_HIP_TRY(hipMemcpy(h->tile_list.p, tl.data(), tl.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+  return VERS_OK;
+}
+
 int32_t plan_storage(vers_ivf* h, const uint32_t* lens, uint32_t k, hipStream_t st) {
   h->h_len.assign(lens, lens + k);
-  h->h_off.assign(k, 0);
-  h->h_cap.assign(k, 0);
   uint64_t off = 0;
   h->max_len = 0;
   h->h_owner.assign(k, 0);
@@ -620,45 +759,14 @@ int32_t plan_storage(vers_ivf* h, const uint32_t* lens, uint32_t k, hipStream_t 
     std::vector<uint64_t> l64(h->h_len.begin(), h->h_len.end());
     shard_plan(l64.data(), k, h->world, h->h_owner.data());
   }
-  for (uint32_t c = 0; c < k; ++c) {
-    const uint32_t len = h->h_len[c];
-    const bool mine = h->h_owner[c] == h->rank;
-    // slack for `add` behind the list: 1/16 of its length, at least 8 rows, then up to the tile boundary the next list starts on.
-    // (Rounds 1-5 kept at least 64: at k = 65536 over 6.25M rows -- lists of ~95 rows -- that alone doubled the storage; a list
-    // that outgrows its slack is re-laid-out with 1/8 of head-room, relayout().)
-    const uint32_t cap = mine ? round_up(len + std::max<uint32_t>(8u, len / 16u), 64u) : 0u;
-    h->h_off[c] = (uint32_t)off;
-    h->h_cap[c] = cap;
-    off += cap;
-    h->max_len = std::max(h->max_len, len);
-    if (off > 0xFFFFFFFFull) return fail(VERS_ERR_INVALID, "more than 2^32-1 storage rows on one GPU");
-  }
+  if (int32_t rc = plan_capacities(h, h->h_len.data(), k, h->h_off, h->h_cap, &off)) return rc;
+  for (uint32_t c = 0; c < k; ++c) h->max_len = std::max(h->max_len, h->h_len[c]);
   if (int32_t rc = h->owner.reserve(k ? k : 1)) return rc;
   if (k) VERS_HIP_TRY(hipMemcpyAsync(h->owner.p, h->h_owner.data(), k, hipMemcpyHostToDevice, st));
-  {  // longest lists first (stable: ties by index); add() changes lengths by one at a time, the order is kept as it is
-    std::vector<uint32_t> ord(k), so(k ? k : 1), sl(k ? k : 1);
-    for (uint32_t c = 0; c < k; ++c) ord[c] = c;
-    std::stable_sort(ord.begin(), ord.end(), [&](uint32_t x, uint32_t y) { return h->h_len[x] > h->h_len[y]; });
-    h->h_slot.assign(k, 0);
-    for (uint32_t i = 0; i < k; ++i) { h->h_slot[ord[i]] = i; so[i] = h->h_off[ord[i]]; sl[i] = h->h_len[ord[i]]; }
-    if (int32_t rc = h->list_slot.reserve((k ? k : 1) * sizeof(uint32_t))) return rc;
-    if (int32_t rc = h->slot_off.reserve((k ? k : 1) * sizeof(uint32_t))) return rc;
-    if (int32_t rc = h->slot_len.reserve((k ? k : 1) * sizeof(uint32_t))) return rc;
-    if (k) {
-      VERS_HIP_TRY(hipMemcpy(h->list_slot.p, h->h_slot.data(), (size_t)k * 4, hipMemcpyHostToDevice));
-      VERS_HIP_TRY(hipMemcpy(h->slot_off.p, so.data(), (size_t)k * 4, hipMemcpyHostToDevice));
-      VERS_HIP_TRY(hipMemcpy(h->slot_len.p, sl.data(), (size_t)k * 4, hipMemcpyHostToDevice));
-    }
-  }
+  if (int32_t rc = write_slot_tables(h, k)) return rc;
   h->set_len_asc_prefix();
   h->cap_rows = off;
-  {
-    std::vector<uint32_t> tl((size_t)(off / 64) ? (size_t)(off / 64) : 1, 0u);
-    for (uint32_t c = 0; c < k; ++c)
-      for (uint32_t r = 0; r < h->h_cap[c]; r += 64) tl[(h->h_off[c] + r) / 64] = c;
-    if (int32_t rc = h->tile_list.reserve(tl.size() * sizeof(uint32_t))) return rc;
-    VERS_HIP_TRY(hipMemcpy(h->tile_list.p, tl.data(), tl.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-  }
+  if (int32_t rc = write_tile_list(h, k)) return rc;
   if (int32_t rc = h->rows.reserve((off ? off : 1) * (size_t)h->ld * sizeof(float))) return rc;
   if (int32_t rc = h->row_ids.reserve((off ? off : 1) * sizeof(uint32_t))) return rc;
   if (int32_t rc = h->list_off.reserve((k ? k : 1) * sizeof(uint32_t))) return rc;
@@ -1881,6 +1989,153 @@ int32_t remove_batch_locked(vers_ivf* h, const uint64_t* ids_host, const uint64_
   if (out_removed) *out_removed = removed;
   return VERS_OK;
 }
+
+// ---- compact: back to plan_storage's capacities for the CURRENT lengths (see vers_hip.h) ------------------------------------------------
+constexpr int kCompactPhases = 8;
+static double g_cp[kCompactPhases] = {};  // vers_compact_phases: calls, storage rows before, after, plan + allocation, move, derive (unfused), tables (ms), reserved
+
+// The shadow and the row-major copy of `rows` storage rows, decided as a build decides them (refresh_norms: options "shadow", "rowmajor",
+// "memory"; both are optional memory with the same head-room left for the searches) and allocated through DevBuf::reserve.  *fits = false:
+// a copy the options ask for found no room.
+static void reserve_derived(vers_ivf* h, uint64_t rows, DevBuf& bf, DevBuf& rm, bool* fits) {
+  *fits = true;
+  const size_t n = (size_t)(rows ? rows : 1) * h->ld;
+  size_t free_b = 0, total_b = 0;
+  if (shadow_mode() != 0) {
+    (void)hipMemGetInfo(&free_b, &total_b);
+    if (n * sizeof(uint16_t) + (size_t(4) << 30) > free_b || bf.reserve(n * sizeof(uint16_t)) != VERS_OK) { (void)hipGetLastError(); bf.release(); *fits = false; }
+  }
+  const int rm_opt = (int)opt_get("rowmajor", -1);
+  const int rm_mode = rm_opt < 0 && opt_get("memory", 0) == 1 ? 0 : rm_opt;
+  (void)hipMemGetInfo(&free_b, &total_b);
+  if (rm_mode == 1 || (rm_mode < 0 && n * sizeof(float) <= total_b / 4)) {
+    if (n * sizeof(float) + (size_t(2) << 30) > free_b || rm.reserve(n * sizeof(float)) != VERS_OK) { (void)hipGetLastError(); rm.release(); *fits = false; }
+  }
+}
+
+int32_t compact_locked(vers_ivf* h, uint64_t* out_before, uint64_t* out_after) {
+  VERS_HIP_TRY(hipDeviceSynchronize());  // searches still in flight on any stream read the storage this call replaces
+  if (out_before) *out_before = 0;
+  if (out_after) *out_after = 0;
+  if (h->up.open) return fail(VERS_ERR_EMPTY, "compact while a streamed upload is in progress: the handle holds no index until vers_ivf_upload_end");
+  if (h->k == 0) return VERS_OK;
+  const uint32_t k = h->k, ld = h->ld;
+  const hipStream_t st = nullptr;
+  const uint64_t before = h->cap_rows;
+  std::vector<uint32_t> noff, ncap;
+  std::vector<CompactJob> jobs;
+  uint64_t total = 0;
+  DevBuf nrows, nids, nxn, nbf, nrm, djobs, nmisc;
+  const size_t lds = 64 * (size_t)(kGatherCols4 + 1) * sizeof(f32x4);
+  bool fused = opt_get("compact_fused", 1) != 0;
+  {
+    AbClock clk(3, g_cp);
+    if (int32_t rc = plan_capacities(h, h->h_len.data(), k, noff, ncap, &total)) return rc;
+    for (uint32_t c = 0; c < k; ++c) {
+      if (!h->h_len[c] || h->h_owner[c] != h->rank) continue;
+      const uint32_t nt = (h->h_len[c] + 63u) / 64u;
+      if (h->h_off[c] % 64u || (uint64_t)nt * 64 > h->h_cap[c] || (uint64_t)h->h_off[c] + h->h_cap[c] > h->cap_rows)
+        return fail(VERS_ERR_HIP, "vers_ivf_compact: a list lies outside its storage (inconsistent index)");
+      for (uint32_t t = 0; t < nt; ++t) jobs.push_back(CompactJob{h->h_off[c] / 64u + t, noff[c] / 64u + t});  // (t < nt <= ncap[c] / 64)
+    }
+    if (int32_t rc = h->pre_misc.reserve(64)) return rc;
+    if (int32_t rc = nmisc.reserve(64)) return rc;  // the new maxima: pre_misc keeps the old ones until the move is done
+    if (int32_t rc = scan_prepare_launch(compact_tiles_kernel, lds)) return rc;
+    // the old shadow and row-major copy go first: they are derived, the new ones take their room
+    h->shadow_valid = false;
+    h->rows_bf.release();
+    h->rows_rm.release();
+    const size_t rows_b = (size_t)(total ? total : 1) * ld * sizeof(float), ids_b = (size_t)(total ? total : 1) * sizeof(uint32_t);
+    if (nrows.reserve(rows_b) != VERS_OK || nids.reserve(ids_b) != VERS_OK) {
+      (void)hipGetLastError();
+      nrows.release(); nids.release();
+      if (int32_t rc = refresh_norms(h, 0, h->cap_rows, st)) return rc;  // the old index stays, with its derived arrays back
+      VERS_HIP_TRY(hipStreamSynchronize(st));
+      return fail(VERS_ERR_HIP, "vers_ivf_compact: the new tiles do not fit beside the old ones; the index is unchanged");
+    }
+    if (fused) {
+      bool fits = true;
+      reserve_derived(h, total, nbf, nrm, &fits);
+      if (fits && (nxn.reserve(ids_b) != VERS_OK || djobs.reserve((jobs.size() ? jobs.size() : 1) * sizeof(CompactJob)) != VERS_OK)) { (void)hipGetLastError(); fits = false; }
+      if (!fits) {  // not beside the old tiles: the unfused sequence allocates them once those are gone
+        nbf.release(); nrm.release(); nxn.release(); djobs.release();
+        fused = false;
+      }
+    }
+    VERS_HIP_TRY(hipMemsetAsync(nids.p, 0xFF, ids_b, st));  // slack tiles of the new plan: no vector (their rows stay as allocated)
+    if (int32_t rc = clk.done()) return rc;
+  }
+  ab_count(0, 1.0, g_cp);
+  ab_count(1, (double)before, g_cp);
+  ab_count(2, (double)total, g_cp);
+  {
+    AbClock clk(4, g_cp);
+    if (fused) {
+      VERS_HIP_TRY(hipMemsetAsync(nxn.p, 0, (size_t)(total ? total : 1) * sizeof(float), st));  // |x|^2 of a row without a vector: 0.0f
+      VERS_HIP_TRY(hipMemsetAsync(nmisc.p, 0, 64, st));  // both maxima and the failure counter restart, as at an upload
+      if (!jobs.empty()) {
+        VERS_HIP_TRY(hipMemcpyAsync(djobs.p, jobs.data(), jobs.size() * sizeof(CompactJob), hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(compact_tiles_kernel, dim3((unsigned)jobs.size()), dim3(256), lds, st, (const CompactJob*)djobs.p, ld,
+                           (const float*)h->rows.as<float>(), (const uint32_t*)h->row_ids.as<uint32_t>(), nrows.as<float>(), nids.as<uint32_t>(),
+                           nbf.as<uint16_t>(), nrm.as<float>(), nxn.as<float>(), nmisc.as<uint32_t>(), nmisc.as<uint32_t>() + 2);
+        VERS_HIP_TRY(hipGetLastError());
+      }
+      VERS_HIP_TRY(hipMemcpyAsync(h->pre_misc.p, nmisc.p, 64, hipMemcpyDeviceToDevice, st));  // (a failure above leaves the old index and its maxima)
+    } else {
+      for (uint32_t c = 0; c < k; ++c) {  // relayout_for's copies with the new plan: whole 64-row tiles move as they are
+        if (!h->h_len[c] || h->h_owner[c] != h->rank) continue;
+        VERS_HIP_TRY(hipMemcpyAsync(nrows.as<float>() + (size_t)noff[c] * ld, h->rows.as<float>() + (size_t)h->h_off[c] * ld,
+                                    (size_t)round_up(h->h_len[c], 64) * ld * sizeof(float), hipMemcpyDeviceToDevice, st));
+        VERS_HIP_TRY(hipMemcpyAsync(nids.as<uint32_t>() + noff[c], h->row_ids.as<uint32_t>() + h->h_off[c], (size_t)h->h_len[c] * sizeof(uint32_t),
+                                    hipMemcpyDeviceToDevice, st));
+      }
+    }
+    VERS_HIP_TRY(hipDeviceSynchronize());
+    std::swap(h->rows.p, nrows.p); std::swap(h->rows.cap, nrows.cap);
+    std::swap(h->row_ids.p, nids.p); std::swap(h->row_ids.cap, nids.cap);
+    nrows.release(); nids.release();
+    if (fused) {
+      std::swap(h->xnorm.p, nxn.p); std::swap(h->xnorm.cap, nxn.cap);
+      std::swap(h->rows_bf.p, nbf.p); std::swap(h->rows_bf.cap, nbf.cap);
+      std::swap(h->rows_rm.p, nrm.p); std::swap(h->rows_rm.cap, nrm.cap);
+      nxn.release();
+    } else {
+      h->xnorm.release();  // (refresh_norms sizes it for the new plan)
+    }
+    if (int32_t rc = clk.done()) return rc;
+  }
+  {
+    // tables, as after a fresh upload of the same lists: offsets, slots (order re-derived), tile -> list, the host's copies
+    AbClock clk(6, g_cp);
+    h->h_off = noff; h->h_cap = ncap; h->cap_rows = total;
+    VERS_HIP_TRY(hipMemcpy(h->list_off.p, h->h_off.data(), (size_t)k * 4, hipMemcpyHostToDevice));
+    if (int32_t rc = write_slot_tables(h, k)) return rc;
+    h->set_len_asc_prefix();
+    if (int32_t rc = write_tile_list(h, k)) return rc;
+    if (fused) {  // what a full refresh_norms restarts besides the arrays
+      for (auto& w : h->pool)
+        for (auto& a : w->ahead) a.valid = false;
+      h->shadow_valid = shadow_mode() != 0 && h->rows_bf.p != nullptr;
+      h->shadow_off = false; h->shadow_queries = 0;
+      if (shadow_mode() != 0) {
+        if (!h->fail_watch) VERS_HIP_TRY(hipHostMalloc((void**)&h->fail_watch, 64, hipHostMallocDefault));
+        *h->fail_watch = 0;
+      }
+    }
+    if (int32_t rc = clk.done()) return rc;
+  }
+  if (!fused) {
+    AbClock clk(5, g_cp);
+    bool fits = true;
+    reserve_derived(h, total, h->rows_bf, h->rows_rm, &fits);  // (what finds no room even now is optional memory: refresh_norms goes without)
+    if (int32_t rc = refresh_norms(h, 0, h->cap_rows, st)) return rc;
+    if (int32_t rc = clk.done()) return rc;
+  }
+  VERS_HIP_TRY(hipDeviceSynchronize());
+  if (out_before) *out_before = before;
+  if (out_after) *out_after = total;
+  return VERS_OK;
+}
 }  // namespace ivf
 }  // namespace vers
 
@@ -2120,6 +2375,22 @@ int32_t vers_ivf_live_count(vers_ivf_t* h, uint64_t* out_live) {
   uint64_t live = 0;
   for (uint32_t c = 0; c < h->k; ++c) live += h->h_len[c];
   *out_live = live;
+  return VERS_OK;
+}
+
+int32_t vers_ivf_compact(vers_ivf_t* h, uint64_t* out_rows_before, uint64_t* out_rows_after) {
+  if (!h) return fail(VERS_ERR_INVALID, "vers_ivf_compact: null handle");
+  std::unique_lock<std::shared_mutex> lk(h->index);
+  DeviceGuard g(h->device);
+  return compact_locked(h, out_rows_before, out_rows_after);
+}
+
+int32_t vers_compact_phases(double* out, int32_t reset) {
+  std::lock_guard<std::mutex> lk(g_ab_mu);
+  if (out)
+    for (int i = 0; i < kCompactPhases; ++i) out[i] = g_cp[i];
+  if (reset)
+    for (double& v : g_cp) v = 0.0;
   return VERS_OK;
 }
 

@@ -134,6 +134,14 @@ class IVFFlatIndex {
     return gone;
   }
 
+  // Compaction (extension, vers_ivf_compact): the device storage goes back to the capacities a fresh upload of the current lists plans and
+  // the certificate maxima are recomputed; none of the five fields changes.  Returns {storage rows before, storage rows after}.
+  std::pair<uint64_t, uint64_t> compact() {
+    uint64_t before = 0, after = 0;
+    check(vers_ivf_compact(handle(), &before, &after));
+    return {before, after};
+  }
+
   // vectors currently in the lists (vers_ivf_live_count)
   size_t live_count() const {
     uint64_t live = 0;

@@ -146,6 +146,14 @@ class IVFFlatIndex:
                                               C.byref(removed)))
         return int(removed.value)
 
+    def compact(self):
+        """vers_ivf_compact: every list back to the capacity a fresh upload of the current lengths plans, the certificate maxima
+        recomputed over the rows the lists hold.  Nothing of the five fields changes (the host mirror is left as it is).  Returns
+        (storage rows before, storage rows after)."""
+        before, after = C.c_uint64(0), C.c_uint64(0)
+        check(lib().vers_ivf_compact(self._h, C.byref(before), C.byref(after)))
+        return int(before.value), int(after.value)
+
     def live_count(self):
         live = C.c_uint64(0)
         check(lib().vers_ivf_live_count(self._h, C.byref(live)))
