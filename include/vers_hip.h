@@ -393,6 +393,40 @@ int32_t vers_ivf_compact(vers_ivf_t* h, uint64_t* out_rows_before, uint64_t* out
  * [1] storage rows before, [2] storage rows after (summed over the calls), [3] planning + allocation, [4] the move (fused: with every
  * derived array), [5] derived arrays on the unfused path, [6] tables, [7] reserved.  reset != 0 zeroes them. */
 int32_t vers_compact_phases(double* out8, int32_t reset);
+/* Range search (extension; the reference has search_approximate only).  In the reference's terms: for query q, rank the lists as
+ * search_approximate does (ivfflat.rs:155-161: first minimum, stable), take the P = min(nprobe, k) nearest, and return EVERY row of
+ * `ids[c]` of those lists whose distance D(q, values[id]) -- the index's metric, the reference's bits: sequential f32, multiply and add
+ * rounded separately -- is <= radius[q], a plain f32 comparison (so for squared L2 a negative radius selects nothing, +inf every row of the
+ * probed lists).  No top_k: the result has whatever size the radius gives it.
+ *   layout   : CSR.  Query q's results are out_ids / out_dist[out_lims[q] .. out_lims[q + 1]); out_lims[0] = 0, out_lims[b] = *out_total.
+ *   order    : default = the nprobe mode's global stable order, ascending (distance, probe rank, position in the list): exactly the
+ *              leading entries with distance <= radius[q] of vers_ivf_search(top_k = all rows of the probed lists, nprobe) -- ids,
+ *              order and distance bits.  flags & VERS_RANGE_WALK_ORDER: walk order instead -- probe rank, then position in the list,
+ *              the order search_approximate concatenates in; a stable sort of it by distance gives the default order.
+ *   rows     : the lists as they are NOW: rows added since the build are in, removed rows are not, storage slack is never visited.
+ *   protocol : synchronous (the host must learn the total before anything can be written), like add / remove / compact.  *out_total is
+ *              always the full count.  *out_total > cap: VERS_OK, out_lims complete, out_ids / out_dist UNTOUCHED -- come back with
+ *              arrays of *out_total entries.  cap == 0 with NULL out_ids / out_dist is the size query.
+ *   handle   : taken the way searches take it -- shared with other searches, a workspace leased per stream, excluded by add / remove /
+ *              compact.  _dev: every pointer but out_total is a device pointer, the work is queued on `stream` and the call waits for it.
+ *   errors   : VERS_ERR_NAN a NaN distance on any scanned row (as every search), outputs untouched; VERS_ERR_INVALID a NaN radius,
+ *              nprobe == 0 (the reference's spill walk is defined by top_k and has no range meaning), unknown flag bits, more than
+ *              2^32 - 1 results in one call or 2^32 - 1 (query, probe, row segment) slots of the plan -- b x min(nprobe, k) x segments
+ *              of the longest list -- (either way: split the batch), a handle sharded by cluster (world > 1: a sharded range search needs a
+ *              variable-size exchange; not implemented); VERS_ERR_INSUFFICIENT no centroids (as search; a streamed upload in progress
+ *              is seen as an empty index); VERS_ERR_HIP scratch for the result staging did not fit, outputs untouched.
+ *   edges    : b == 0 is a no-op with *out_total = 0.  A probed list that is empty contributes nothing. */
+#define VERS_RANGE_WALK_ORDER 1u
+int32_t vers_ivf_range_search(vers_ivf_t* h, const float* queries, uint64_t q_stride_bytes, uint32_t b, const float* radius /* [b] */,
+                              uint32_t nprobe, uint32_t flags, uint64_t* out_lims /* [b+1] */, uint64_t* out_ids, float* out_dist,
+                              uint64_t cap, uint64_t* out_total);
+int32_t vers_ivf_range_search_dev(vers_ivf_t* h, const float* queries_dev, uint64_t ldq_floats, uint32_t b, const float* radius_dev,
+                                  uint32_t nprobe, uint32_t flags, uint64_t* out_lims_dev, uint64_t* out_ids_dev, float* out_dist_dev,
+                                  uint64_t cap, uint64_t* out_total /* host */, void* stream);
+/* The range calls of this process by PHASE (HIP events on the call's stream, ms).  out[8]: [0] calls, [1] queries, [2] results, [3] staging +
+ * coarse quantiser + plan, [4] count pass, [5] prefix scan + read-back of the total, [6] fill pass, [7] sort + decode (0 in walk order).
+ * Calls that end in an error are not counted.  reset != 0 zeroes them. */
+int32_t vers_range_phases(double* out8, int32_t reset);
 /* Process-wide switches: every one is a named option set here (or, for a process one does not control from inside, through the ONE
  * environment variable VERS_OPTIONS="name=value,name=value", read once; besides it the library reads only VERS_SHADOW and
  * VERS_ROWMAJOR, the two memory switches of INTEGRATION.md = options "shadow" / "rowmajor").  Unknown name: VERS_ERR_INVALID.

@@ -12,6 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("VERS_LIB_PATH") or os.path.join(_HERE, "lib", "libvers_hip.so")
 
 OK, ERR_INVALID, ERR_NAN, ERR_INSUFFICIENT, ERR_HIP, ERR_EMPTY, ERR_COMM = 0, 1, 2, 3, 4, 5, 6
+RANGE_WALK_ORDER = 1
 METRIC_L2SQ, METRIC_COSDIST = 0, 1
 MAX_TOPK = 64
 
@@ -103,6 +104,11 @@ SIGNATURES = {
     "vers_remove_phases": (C.c_int32, [C.POINTER(C.c_double), C.c_int32]),
     "vers_ivf_compact": (C.c_int32, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "vers_compact_phases": (C.c_int32, [C.POINTER(C.c_double), C.c_int32]),
+    "vers_ivf_range_search": (C.c_int32, [_vp, _vp, C.c_uint64, C.c_uint32, _vp, C.c_uint32, C.c_uint32, _vp, _vp, _vp, C.c_uint64,
+                                          C.POINTER(C.c_uint64)]),
+    "vers_ivf_range_search_dev": (C.c_int32, [_vp, _vp, C.c_uint64, C.c_uint32, _vp, C.c_uint32, C.c_uint32, _vp, _vp, _vp, C.c_uint64,
+                                              C.POINTER(C.c_uint64), _vp]),
+    "vers_range_phases": (C.c_int32, [C.POINTER(C.c_double), C.c_int32]),
     "vers_kmeans_update": (C.c_int32, [C.c_int32, _vp, C.c_uint64, C.c_uint64, _vp, C.c_uint64, C.c_uint32, _vp]),
     "vers_kmeans_cost": (C.c_int32, [C.c_int32, _vp, C.c_uint64, C.c_uint64, _vp, C.c_uint64, C.c_uint64, _vp, C.c_uint32,
                                      C.POINTER(C.c_float)]),
@@ -328,6 +334,14 @@ def compact_phases(reset=False) -> dict:
     v = (C.c_double * 8)()
     check(lib().vers_compact_phases(v, 1 if reset else 0))
     keys = ("calls", "rows_before", "rows_after", "plan_ms", "move_ms", "derive_ms", "tables_ms", "reserved")
+    return dict(zip(keys, (float(x) for x in v)))
+
+
+def range_phases(reset=False) -> dict:
+    """The range-search calls of this process by phase, HIP events on the call's stream in ms (vers_range_phases)."""
+    v = (C.c_double * 8)()
+    check(lib().vers_range_phases(v, 1 if reset else 0))
+    keys = ("calls", "queries", "results", "plan_ms", "count_ms", "scan_ms", "fill_ms", "sort_ms")
     return dict(zip(keys, (float(x) for x in v)))
 
 

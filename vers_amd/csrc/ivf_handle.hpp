@@ -43,6 +43,11 @@ struct SearchWs {
   DevBuf seg_bounds, stamps, quad_counter, fb_part, fb_ctr, c1_ctr;  // (c1_ctr: coarse1_kernel's finished-blocks counter)
   DevBuf clower, lower;  // lower bounds of multi-pass results (coarse ranking of more than 64 lists; top_k > 64)
   DevBuf qp, qil, cpart, probe, pj, lists, pairs, items, groups, qblocks, partials, status, o_ids, o_dist, o_cnt, xpart;
+  // range search (ivf_search.hip: range_dev_locked): hits per (query, probe, segment) slot | their exclusive prefix | radii, CSR limits and
+  // results of a host-pointer call | [0..1] total, [2] status, [3] NaN-radius flag | (key, id) staging of the sorted order + rocPRIM's temporary
+  DevBuf rg_counts, rg_base, rg_rad, rg_lims, rg_misc, rg_stage, rg_tmp;
+  uint32_t* rg_pin = nullptr;  // pinned [4]: where a range call reads its total, status word and NaN-radius flag after its first synchronisation
+  hipEvent_t rg_ev[6] = {};  // phase boundaries of the most recent range call (vers_range_phases), created on first use
   DevBuf g_send, g_recv;  // sharded search without the host in the loop: this rank's [2][b][top_k] partial | the world's
   bool g_poisoned = false;  // g_send holds the poison mark of a locally failed batch (cleared before the next partial is written)
   static constexpr uint32_t kEvRing = 64;  // scan-launch timing ring (measurement hook)
@@ -493,8 +498,10 @@ struct SearchPlan {
   const float* qp = nullptr;  // staged (padded) queries
   SearchWs::CoarseAhead* took = nullptr;  // the look-ahead slot this search consumed, if any
 };
+// chains_only: the plan of the ordered-chain list scan whatever the batch (IvfSrc<QG> items, QG 1 / 8 / 16, a single query included) --
+// no item records, no matrix-core scan: what the range search walks (range.hip.h)
 int32_t plan_search(vers_ivf* h, const float* q_dev, uint64_t ldq_in, uint32_t b, uint32_t top_k, uint32_t nprobe, hipStream_t st,
-                    SearchPlan& s);
+                    SearchPlan& s, bool chains_only = false);
 
 // ---- ivf_search.hip ----------------------------------------------------------------------------------------------------
 int32_t search_dev_locked(vers_ivf* h, const float* q_dev, uint64_t ldq_in, uint32_t b, uint32_t top_k, uint32_t nprobe,

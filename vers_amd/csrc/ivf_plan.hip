@@ -608,7 +608,7 @@ int32_t coarse(vers_ivf* h, const float* qp, uint32_t b, uint32_t P, hipStream_t
 // Geometry, staging, coarse quantiser and planning of one search call: everything up to the list scan's launch.  On return the
 // per-batch tables of the leased workspace are final (in stream order) and `s` says which scan the search runs.
 int32_t plan_search(vers_ivf* h, const float* q_dev, uint64_t ldq_in, uint32_t b, uint32_t top_k, uint32_t nprobe, hipStream_t st,
-                    SearchPlan& s) {
+                    SearchPlan& s, bool chains_only) {
   const int ref_mode = nprobe == 0;
   { const int ev = scan_events_ref().load(); W->ev_on = ev == 1 || (ev == 2 && b > 1); }
   // reference mode ranks the 48 nearest lists (48 + 16 slack = one key per lane in the MFMA pre-selection);
@@ -621,7 +621,7 @@ int32_t plan_search(vers_ivf* h, const float* q_dev, uint64_t ldq_in, uint32_t b
   const uint32_t P = ref_mode ? std::min<uint32_t>(h->k, P_ref) : std::min<uint32_t>(nprobe, h->k);
   // one key per lane is the width of every list in the kernels: more ranked lists (P > 64) or more results (top_k > 64)
   // are produced 64 ranks per pass (ScanParams::lower), on the ordered-chain kernels
-  const bool one1 = b == 1 && P <= (uint32_t)kMaxTopK;  // single query: coarse merge + plan fused in plan1_kernel
+  const bool one1 = !chains_only && b == 1 && P <= (uint32_t)kMaxTopK;  // single query: coarse merge + plan fused in plan1_kernel
   // ... and the coarse scan with them in coarse1_kernel (option "coarse1" = 0: the ordered-chain scan + plan1_kernel, for A/B runs)
   const bool c1_on = opt_get("coarse1", 1) != 0;
   const bool one1_fused = one1 && c1_on;
@@ -710,7 +710,7 @@ int32_t plan_search(vers_ivf* h, const float* q_dev, uint64_t ldq_in, uint32_t b
                         (size_t)h->ld * sizeof(float) + 24576 <= 160u * 1024u;  // (the finish: the query + 8 KB of exchange area + 14 KB of static buffers)
   // (any nprobe up to kPreMaxP: the work items carry (query, list) pairs; only the RANKING of more than 48 lists leaves the matrix cores
   // -- one key per lane in the selection -- and runs exactly, 64 ranks per pass.  Rounds 1-5 sent nprobe > 64 to the ordered chains.)
-  const bool use_pre = one1_pre || (pre_batch && !ref_mode && pre_mode != 0 && (top_k + kPreMinSlack <= kPreMaxKp || wide_k) && P <= kPreMaxP && pre_nq != 0);
+  const bool use_pre = !chains_only && (one1_pre || (pre_batch && !ref_mode && pre_mode != 0 && (top_k + kPreMinSlack <= kPreMaxKp || wide_k) && P <= kPreMaxP && pre_nq != 0));
   if (use_pre && !one1_pre) QG = (int)pre_nq;
   const uint32_t k_keep = use_pre ? kp : std::min<uint32_t>(top_k, kMaxTopK);
   // 64 result ranks per pass; no pass beyond the rows the index holds (top_k = 100000 on 1000 rows: 16 passes, not 1563)

@@ -11,6 +11,7 @@
 #include "ivf_src.hip.h"
 #include "single.hip.h"
 #include "finish_wide.hip.h"
+#include "range.hip.h"
 
 namespace vers {
 
@@ -653,6 +654,140 @@ int32_t host_io_end(vers_ivf* h, const HostIo& io, uint32_t b, uint32_t top_k, u
   return VERS_OK;
 }
 
+// ---- range search (range.hip.h) ---------------------------------------------------------------------------------------
+constexpr int kRangePhases = 8;
+static std::mutex g_rg_mu;
+static double g_rg[kRangePhases] = {};  // vers_range_phases: calls, queries, results, plan, count, prefix + total, fill, sort + decode (ms)
+
+// one pass over the planned items; launch bounds as launch_ivf_scan's
+template <int QG, bool FILL>
+int32_t launch_range_scan(vers_ivf* h, const IvfSrc<QG>& src, uint32_t items_bound, RangeParams p, hipStream_t st) {
+  p.next_quad = nullptr;
+  if (QG != 1) {
+    if (int32_t rc = W->quad_counter.reserve(16)) return rc;
+    VERS_HIP_TRY(hipMemsetAsync(W->quad_counter.p, 0, 16, st));
+    p.next_quad = W->quad_counter.as<uint32_t>();
+  }
+  const size_t lds = scan_lds_bytes(QG, h->ld);
+  if (int32_t rc = h->metric ? scan_prepare_launch(range_scan_kernel<QG, 1, FILL, IvfSrc<QG>>, lds) : scan_prepare_launch(range_scan_kernel<QG, 0, FILL, IvfSrc<QG>>, lds)) return rc;
+  uint32_t blocks = (items_bound + kWavesPerBlock - 1) / kWavesPerBlock;
+  const uint32_t max_blocks = (uint32_t)h->n_cu * scan_blocks_per_cu(QG, h->ld);
+  if (blocks > max_blocks) blocks = max_blocks;
+  if (blocks == 0) blocks = 1;
+  if (h->metric) hipLaunchKernelGGL((range_scan_kernel<QG, 1, FILL, IvfSrc<QG>>), dim3(blocks), dim3(kWave * kWavesPerBlock), lds, st, src, p);
+  else hipLaunchKernelGGL((range_scan_kernel<QG, 0, FILL, IvfSrc<QG>>), dim3(blocks), dim3(kWave * kWavesPerBlock), lds, st, src, p);
+  VERS_HIP_TRY(hipGetLastError());
+  return VERS_OK;
+}
+
+// Range search of b >= 1 queries on `st`: plan, count launch, scan, sync and total, fill, sort, sync.  The caller holds the index shared, a
+// leased workspace and status word 1 (HostStatusSlot: the call synchronises and consumes its status itself).  own_out: ids / distances go to
+// the workspace's o_ids / o_dist, sized by the total (the host-pointer call copies them out), else to ids_dev / dist_dev -- when total <= cap.
+int32_t range_dev_locked(vers_ivf* h, const float* q_dev, uint64_t ldq_in, uint32_t b, const float* radius_dev, uint32_t nprobe, uint32_t flags,
+                         uint64_t* lims_dev, uint64_t* ids_dev, float* dist_dev, uint64_t cap, bool own_out, uint64_t* out_total, hipStream_t st) {
+  for (auto& e : W->rg_ev)
+    if (!e) VERS_HIP_TRY(hipEventCreate(&e));
+  VERS_HIP_TRY(hipEventRecord(W->rg_ev[0], st));
+  SearchPlan s;
+  if (int32_t rc = plan_search(h, q_dev, ldq_in, b, 1, nprobe, st, s, true)) return rc;  // (top_k = 1: the partial slots no kernel here reads stay small)
+  struct AheadGuard {  // a look-ahead slot the plan consumed is free again behind whatever this call queued, on EVERY way out
+    SearchPlan& s; hipStream_t st;
+    ~AheadGuard() {
+      if (s.took && hipEventRecord(s.took->freed, st) == hipSuccess) s.took->freed_rec = true;
+    }
+  } ahead_guard{s, st};
+  W->tot_valid = true;
+  const uint32_t P = s.P, S_max = s.S_max;
+  const uint64_t per_q = (uint64_t)P * S_max, n_slots = (uint64_t)b * per_q;
+  if (n_slots >= 0xFFFFFFFFull) return fail(VERS_ERR_INVALID, "vers_ivf_range_search: batch too large (query x probe x segment slots); split the batch");
+  auto fill_src = [&](auto& src) {
+    src.rows = h->rows.as<float>(); src.ld = h->ld; src.list_off = h->slot_off.as<uint32_t>();
+    src.list_len = h->slot_len.as<uint32_t>(); src.items = W->items.as<ItemDesc>(); src.n_items_dev = &s.tot->n_items;
+    src.cnt = s.cnt; src.pair_off = s.pair_off; src.pairs = W->pairs.as<uint32_t>(); src.group_off = s.group_off;
+    src.qblocks = W->qblocks.as<float>(); src.qp = s.qp; src.ldq = h->ldq; src.P = P; src.S_max = S_max; src.k_keep = s.k_keep;
+    src.seg_rows = s.seg_rows; src.seg_target = s.seg_target; src.pj_pref = s.pj_pref; src.partials = W->partials.as<uint64_t>();
+    src.bound_per_pair = 0u;
+  };
+  auto pass = [&](auto fill_tag, const RangeParams& rp) -> int32_t {
+    constexpr bool FILL = decltype(fill_tag)::value;
+    if (s.QG == 1) { IvfSrc<1> src; fill_src(src); return launch_range_scan<1, FILL>(h, src, (uint32_t)s.items_bound, rp, st); }
+    if (s.QG == 8) { IvfSrc<8> src; fill_src(src); return launch_range_scan<8, FILL>(h, src, (uint32_t)s.items_bound, rp, st); }
+    IvfSrc<16> src; fill_src(src);
+    return launch_range_scan<16, FILL>(h, src, (uint32_t)s.items_bound, rp, st);
+  };
+  const size_t scan_tmp = range_scan_temp_bytes((size_t)n_slots + 1);
+  if (int32_t rc = W->rg_counts.reserve(((size_t)n_slots + 1) * sizeof(uint32_t))) return rc;
+  if (int32_t rc = W->rg_base.reserve(((size_t)n_slots + 1) * sizeof(uint64_t))) return rc;
+  if (int32_t rc = W->rg_misc.reserve(16)) return rc;
+  if (int32_t rc = W->rg_tmp.reserve(scan_tmp)) return rc;
+  VERS_HIP_TRY(hipMemsetAsync(W->rg_counts.p, 0, ((size_t)n_slots + 1) * sizeof(uint32_t), st));  // (+ one zero count: the prefix's last entry is the total)
+  VERS_HIP_TRY(hipMemsetAsync(W->rg_misc.p, 0, 16, st));
+  RangeParams rp;
+  rp.ld = h->ld; rp.n_chunks = h->ld / kChunk; rp.status = W->st_word(); rp.radius = radius_dev; rp.counts = W->rg_counts.as<uint32_t>();
+  rp.base = W->rg_base.as<uint64_t>(); rp.row_ids = h->row_ids.as<uint32_t>(); rp.out_keys = nullptr; rp.out_ids = nullptr; rp.out_dist = nullptr; rp.next_quad = nullptr;
+  VERS_HIP_TRY(hipEventRecord(W->rg_ev[1], st));
+  if (int32_t rc = pass(std::false_type{}, rp)) return rc;
+  VERS_HIP_TRY(hipEventRecord(W->rg_ev[2], st));
+  if (int32_t rc = range_scan_counts(W->rg_counts.as<uint32_t>(), W->rg_base.as<uint64_t>(), (size_t)n_slots + 1, W->rg_tmp.p, scan_tmp, st)) return rc;
+  hipLaunchKernelGGL(range_lims_kernel, dim3((b + 1 + 255) / 256), dim3(256), 0, st, (const uint64_t*)W->rg_base.as<uint64_t>(), per_q, b, radius_dev,
+                     (const uint32_t*)W->st_word(), lims_dev, W->rg_misc.as<uint32_t>());
+  VERS_HIP_TRY(hipGetLastError());
+  if (!W->rg_pin) VERS_HIP_TRY(hipHostMalloc((void**)&W->rg_pin, 16, hipHostMallocDefault));  // pinned landing words: total | status | NaN radius
+  VERS_HIP_TRY(hipMemcpyAsync(W->rg_pin, W->rg_misc.p, 16, hipMemcpyDeviceToHost, st));
+  VERS_HIP_TRY(hipEventRecord(W->rg_ev[3], st));
+  VERS_HIP_TRY(hipStreamSynchronize(st));
+  uint32_t misc[4];
+  std::memcpy(misc, W->rg_pin, sizeof(misc));
+  if (int32_t rc = status_to_rc(h, misc[2], W->st_slot)) return rc == kRetrySpill ? VERS_ERR_INVALID : rc;
+  if (misc[3]) return fail(VERS_ERR_INVALID, "vers_ivf_range_search: NaN radius");
+  const uint64_t total = ((uint64_t)misc[1] << 32) | misc[0];
+  if (total > 0xFFFFFFFFull) return fail(VERS_ERR_INVALID, "vers_ivf_range_search: more than 2^32 - 1 results in one call; split the batch");
+  *out_total = total;
+  float ms[5] = {};
+  auto phases = [&](int n_ev) {
+    for (int i = 0; i + 1 < n_ev; ++i) (void)hipEventElapsedTime(&ms[i], W->rg_ev[i], W->rg_ev[i + 1]);
+    std::lock_guard<std::mutex> lk(g_rg_mu);
+    g_rg[0] += 1.0; g_rg[1] += (double)b; g_rg[2] += (double)total;
+    for (int i = 0; i < 5; ++i) g_rg[3 + i] += (double)ms[i];
+  };
+  if (total == 0 || total > cap) { phases(4); return VERS_OK; }  // (too small a buffer: the limits are complete, ids / distances untouched)
+  if (own_out) {
+    if (int32_t rc = W->o_ids.reserve((size_t)total * sizeof(uint64_t))) return rc;
+    if (int32_t rc = W->o_dist.reserve((size_t)total * sizeof(float))) return rc;
+    ids_dev = W->o_ids.as<uint64_t>(); dist_dev = W->o_dist.as<float>();
+  }
+  const bool walk = (flags & VERS_RANGE_WALK_ORDER) != 0;
+  size_t sort_tmp = 0;
+  uint64_t *k_in = nullptr, *k_out = nullptr, *i_in = nullptr;
+  if (!walk) {  // staging of the sorted order: keys in | keys out | ids in, + rocPRIM's temporary
+    sort_tmp = range_sort_temp_bytes((uint32_t)total, b);
+    if (int32_t rc = W->rg_stage.reserve(3 * (size_t)total * sizeof(uint64_t))) return rc;
+    if (int32_t rc = W->rg_tmp.reserve(sort_tmp)) return rc;
+    k_in = W->rg_stage.as<uint64_t>(); k_out = k_in + total; i_in = k_out + total;
+  }
+  rp.out_keys = walk ? nullptr : k_in; rp.out_ids = walk ? ids_dev : i_in; rp.out_dist = dist_dev;
+  if (int32_t rc = pass(std::true_type{}, rp)) return rc;
+  VERS_HIP_TRY(hipEventRecord(W->rg_ev[4], st));
+  if (!walk) {
+    if (int32_t rc = range_sort_segments(k_in, k_out, i_in, ids_dev, (uint32_t)total, b, lims_dev, W->rg_tmp.p, sort_tmp, st)) return rc;
+    hipLaunchKernelGGL(range_decode_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (const uint64_t*)k_out, total, dist_dev);
+    VERS_HIP_TRY(hipGetLastError());
+  }
+  VERS_HIP_TRY(hipEventRecord(W->rg_ev[5], st));
+  VERS_HIP_TRY(hipStreamSynchronize(st));
+  phases(6);
+  return VERS_OK;
+}
+
+// what both entry points refuse before they touch the device
+static int32_t range_check(vers_ivf* h, const char* who, uint32_t nprobe, uint32_t flags) {
+  if (flags & ~VERS_RANGE_WALK_ORDER) return fail(VERS_ERR_INVALID, std::string(who) + ": unknown flag bits");
+  if (nprobe == 0) return fail(VERS_ERR_INVALID, std::string(who) + ": nprobe must be at least 1 (the reference's spill walk is defined by top_k: it has no range meaning)");
+  if (h->world > 1) return fail(VERS_ERR_INVALID, std::string(who) + ": the handle is sharded by cluster; a sharded range search is not implemented");
+  if (h->k == 0) return fail(VERS_ERR_INSUFFICIENT, "range search on an index without centroids (reference: index out of bounds, ivfflat.rs:169)");
+  return VERS_OK;
+}
+
 }  // namespace ivf
 }  // namespace vers
 
@@ -1025,6 +1160,68 @@ int32_t vers_ivf_search_exhaustive(vers_ivf_t* h, const float* queries, uint64_t
   if (int32_t rc = exhaustive_dev_locked(h, io.q_dev, h->d, b, top_k, metric, io.ids_dev, io.dist_dev, io.cnt_dev, W->io_stream)) return rc;
   const int32_t rc = host_io_end(h, io, b, top_k, out_ids, out_dist, out_count);
   return rc == kRetrySpill ? VERS_ERR_INVALID : rc;
+}
+
+int32_t vers_ivf_range_search_dev(vers_ivf_t* h, const float* queries_dev, uint64_t ldq_floats, uint32_t b, const float* radius_dev, uint32_t nprobe,
+                                  uint32_t flags, uint64_t* out_lims_dev, uint64_t* out_ids_dev, float* out_dist_dev, uint64_t cap, uint64_t* out_total,
+                                  void* stream) {
+  if (!h) return fail(VERS_ERR_INVALID, "null handle");
+  if (!out_total) return fail(VERS_ERR_INVALID, "vers_ivf_range_search_dev: out_total is required");
+  *out_total = 0;
+  if (b && (!queries_dev || ldq_floats < h->d || !radius_dev || !out_lims_dev || (cap && (!out_ids_dev || !out_dist_dev))))
+    return fail(VERS_ERR_INVALID, "vers_ivf_range_search_dev: bad arguments");
+  if (b == 0) return VERS_OK;
+  std::shared_lock<std::shared_mutex> lk(h->index);
+  if (int32_t rc = range_check(h, "vers_ivf_range_search_dev", nprobe, flags)) return rc;
+  DeviceGuard g(h->device);
+  WsLease lease(h, true, (hipStream_t)stream);
+  if (lease.rc) return lease.rc;
+  if (int32_t rc = lease.order_on((hipStream_t)stream)) return rc;
+  HostStatusSlot slot(h);
+  return range_dev_locked(h, queries_dev, ldq_floats, b, radius_dev, nprobe, flags, out_lims_dev, out_ids_dev, out_dist_dev, cap, false, out_total,
+                          (hipStream_t)stream);
+}
+
+int32_t vers_ivf_range_search(vers_ivf_t* h, const float* queries, uint64_t q_stride_bytes, uint32_t b, const float* radius, uint32_t nprobe, uint32_t flags,
+                              uint64_t* out_lims, uint64_t* out_ids, float* out_dist, uint64_t cap, uint64_t* out_total) {
+  if (!h) return fail(VERS_ERR_INVALID, "null handle");
+  if (!out_total) return fail(VERS_ERR_INVALID, "vers_ivf_range_search: out_total is required");
+  *out_total = 0;
+  if (b && (!queries || q_stride_bytes < (uint64_t)h->d * 4 || q_stride_bytes % 4 || !radius || !out_lims || (cap && (!out_ids || !out_dist))))
+    return fail(VERS_ERR_INVALID, "vers_ivf_range_search: bad arguments");
+  if (b == 0) return VERS_OK;
+  for (uint32_t i = 0; i < b; ++i)
+    if (radius[i] != radius[i]) return fail(VERS_ERR_INVALID, "vers_ivf_range_search: NaN radius");
+  std::shared_lock<std::shared_mutex> lk(h->index);
+  if (int32_t rc = range_check(h, "vers_ivf_range_search", nprobe, flags)) return rc;
+  DeviceGuard g(h->device);
+  WsLease lease(h);
+  if (lease.rc) return lease.rc;
+  HostStatusSlot slot(h);
+  HostIo io;
+  if (int32_t rc = host_io_begin(h, queries, q_stride_bytes, b, 0, io)) return rc;  // (the pinned query staging of every host-pointer call)
+  lease.st = W->io_stream;
+  if (int32_t rc = W->rg_rad.reserve((size_t)b * sizeof(float))) return rc;
+  if (int32_t rc = W->rg_lims.reserve(((size_t)b + 1) * sizeof(uint64_t))) return rc;
+  VERS_HIP_TRY(hipMemcpyAsync(W->rg_rad.p, radius, (size_t)b * sizeof(float), hipMemcpyHostToDevice, W->io_stream));
+  uint64_t total = 0;
+  if (int32_t rc = range_dev_locked(h, io.q_dev, h->d, b, W->rg_rad.as<float>(), nprobe, flags, W->rg_lims.as<uint64_t>(), nullptr, nullptr, cap, true, &total,
+                                    W->io_stream)) return rc;
+  VERS_HIP_TRY(hipMemcpy(out_lims, W->rg_lims.p, ((size_t)b + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost));
+  *out_total = total;
+  if (total == 0 || total > cap) return VERS_OK;
+  VERS_HIP_TRY(hipMemcpy(out_ids, W->o_ids.p, (size_t)total * sizeof(uint64_t), hipMemcpyDeviceToHost));
+  VERS_HIP_TRY(hipMemcpy(out_dist, W->o_dist.p, (size_t)total * sizeof(float), hipMemcpyDeviceToHost));
+  return VERS_OK;
+}
+
+int32_t vers_range_phases(double* out8, int32_t reset) {
+  std::lock_guard<std::mutex> lk(g_rg_mu);
+  if (out8)
+    for (int i = 0; i < kRangePhases; ++i) out8[i] = g_rg[i];
+  if (reset)
+    for (double& v : g_rg) v = 0.0;
+  return VERS_OK;
 }
 
 }  // extern "C"

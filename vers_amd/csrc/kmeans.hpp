@@ -11,6 +11,12 @@ namespace vers {
 size_t group_by_cluster_temp_bytes(uint32_t n, uint32_t k);
 int32_t group_by_cluster(const uint32_t* assign, uint32_t n, uint32_t k, uint32_t* sorted_ids, void* temp,
                          size_t temp_bytes, hipStream_t st);
+// range search: exclusive u64 prefix of u32 counts; per-segment ascending sort of (u64 key, u64 id) pairs, lims [segments + 1]
+size_t range_scan_temp_bytes(size_t n);
+int32_t range_scan_counts(const uint32_t* counts, uint64_t* base, size_t n, void* temp, size_t temp_bytes, hipStream_t st);
+size_t range_sort_temp_bytes(uint32_t n, uint32_t segments);
+int32_t range_sort_segments(const uint64_t* keys_in, uint64_t* keys_out, const uint64_t* ids_in, uint64_t* ids_out, uint32_t n, uint32_t segments,
+                            const uint64_t* lims, void* temp, size_t temp_bytes, hipStream_t st);
 
 // ---- kmeans.hip ---------------------------------------------------------------------
 // Simple owning device buffer (grow-only).

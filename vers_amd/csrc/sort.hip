@@ -2,6 +2,8 @@
 // ids sorted by (cluster, ascending row index) == the reference's inverted lists
 // `ids[cluster].push(vec_id)` in ascending vec_id (ivfflat.rs:123-127).  Uses rocPRIM's
 // LSD radix sort, which is stable.
+// + the two rocPRIM steps of the range search (range.hip.h): the prefix over the per-slot hit counts and the per-query sort of
+// (key, id) pairs.  rocPRIM is instantiated in this translation unit only.
 #include <cstdlib>
 #include <cstring>
 
@@ -41,6 +43,32 @@ int32_t group_by_cluster(const uint32_t* assign, uint32_t n, uint32_t k, uint32_
   VERS_HIP_TRY(hipGetLastError());
   VERS_HIP_TRY(rocprim::radix_sort_pairs((void*)rp_tmp, rp_bytes, assign, keys_out, (const uint32_t*)iota, sorted_ids,
                                          (size_t)n, 0u, bits, st));
+  return VERS_OK;
+}
+
+// ---- range search: counts -> offsets, per-query sort ---------------------------------------------------------------
+// base[i] = counts[0] + ... + counts[i - 1] as u64, i in [0, n): the caller appends a zero count so that base[n - 1] is the total
+size_t range_scan_temp_bytes(size_t n) {
+  size_t bytes = 0;
+  (void)rocprim::exclusive_scan(nullptr, bytes, (const uint32_t*)nullptr, (uint64_t*)nullptr, (uint64_t)0, n, rocprim::plus<uint64_t>(), (hipStream_t) nullptr);
+  return bytes + 256;
+}
+int32_t range_scan_counts(const uint32_t* counts, uint64_t* base, size_t n, void* temp, size_t temp_bytes, hipStream_t st) {
+  if (n == 0) return VERS_OK;
+  VERS_HIP_TRY(rocprim::exclusive_scan(temp, temp_bytes, counts, base, (uint64_t)0, n, rocprim::plus<uint64_t>(), st));
+  return VERS_OK;
+}
+// segment s = [lims[s], lims[s + 1]) of (keys_in, ids_in) sorted ascending by the whole 64-bit key into (keys_out, ids_out); n < 2^32
+size_t range_sort_temp_bytes(uint32_t n, uint32_t segments) {
+  size_t bytes = 0;
+  (void)rocprim::segmented_radix_sort_pairs(nullptr, bytes, (const uint64_t*)nullptr, (uint64_t*)nullptr, (const uint64_t*)nullptr, (uint64_t*)nullptr, n, segments,
+                                            (const uint64_t*)nullptr, (const uint64_t*)nullptr, 0u, 64u, (hipStream_t) nullptr);
+  return bytes + 256;
+}
+int32_t range_sort_segments(const uint64_t* keys_in, uint64_t* keys_out, const uint64_t* ids_in, uint64_t* ids_out, uint32_t n, uint32_t segments,
+                            const uint64_t* lims, void* temp, size_t temp_bytes, hipStream_t st) {
+  if (n == 0 || segments == 0) return VERS_OK;
+  VERS_HIP_TRY(rocprim::segmented_radix_sort_pairs(temp, temp_bytes, keys_in, keys_out, ids_in, ids_out, n, segments, lims, lims + 1, 0u, 64u, st));
   return VERS_OK;
 }
 

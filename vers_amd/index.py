@@ -35,6 +35,7 @@ class IVFFlatIndex:
         self.ids = []  # list of python lists of vec ids
         self.cost = np.float32(np.inf)
         self.iterations = None
+        self._range_cap = 0  # range_search: the previous call's total, offered as the next call's capacity
 
     def close(self):
         if self._h:
@@ -181,6 +182,41 @@ class IVFFlatIndex:
         cnt = np.zeros(b, dtype=np.uint32)
         check(lib().vers_ivf_search_exhaustive(self._h, _ptr(q), 4 * self.d, b, top_k, metric, _ptr(ids), _ptr(dist), _ptr(cnt)))
         return ids[:, :top_k], dist[:, :top_k], cnt
+
+    # -- range search (extension; the reference has search_approximate only) ---------------------------
+    def range_search(self, queries, radius, nprobe: int, walk_order: bool = False):
+        """Every row of the min(nprobe, k) nearest lists of each query with distance <= radius (vers_ivf_range_search).  radius: a
+        scalar or one value per query.  -> (lims [b + 1] u64, ids u64, dist f32), CSR: query q owns [lims[q], lims[q + 1]).  Default
+        order: ascending (distance, probe rank, list position) = the head of search_batch(top_k = all, nprobe); walk_order: probe
+        rank, then list position.  The first call offers the previous call's total as capacity (0 the first time: a size query);
+        a second call follows when that was too small."""
+        q = np.ascontiguousarray(np.atleast_2d(queries), dtype=np.float32)
+        b = q.shape[0]
+        r = np.ascontiguousarray(np.broadcast_to(np.asarray(radius, dtype=np.float32).reshape(-1), (b,)) if np.ndim(radius) else
+                                 np.full(b, radius, dtype=np.float32))
+        flags = capi.RANGE_WALK_ORDER if walk_order else 0
+        lims = np.zeros(b + 1, dtype=np.uint64)
+        cap = int(self._range_cap)
+        total = C.c_uint64(0)
+        while True:
+            ids = np.zeros(cap, dtype=np.uint64); dist = np.zeros(cap, dtype=np.float32)
+            check(lib().vers_ivf_range_search(self._h, _ptr(q), 4 * self.d, b, _ptr(r), nprobe, flags, _ptr(lims), _ptr(ids) if cap else None,
+                                              _ptr(dist) if cap else None, cap, C.byref(total)))
+            if total.value <= cap:
+                break
+            cap = int(total.value)
+        self._range_cap = int(total.value)
+        return lims, ids[:total.value], dist[:total.value]
+
+    def range_search_dev(self, q_ptr: int, ldq: int, b: int, radius_ptr: int, nprobe: int, flags: int, lims_ptr: int, ids_ptr: int,
+                         dist_ptr: int, cap: int, stream: int = 0) -> int:
+        """vers_ivf_range_search_dev on raw device pointers; synchronous.  Returns the total: ids / distances were written only when it
+        is <= cap."""
+        total = C.c_uint64(0)
+        check(lib().vers_ivf_range_search_dev(self._h, _vp(q_ptr), ldq, b, _vp(radius_ptr), nprobe, flags, _vp(lims_ptr),
+                                              _vp(ids_ptr) if ids_ptr else None, _vp(dist_ptr) if dist_ptr else None, cap, C.byref(total),
+                                              _vp(stream)))
+        return int(total.value)
 
     # -- device cache -----------------------------------------------------------------------------------
     def _upload(self):
