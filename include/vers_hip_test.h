@@ -12,8 +12,9 @@ extern "C" {
  * device memory in production) with `value` (inf, NaN, 1e30 ...) and rebuilds the derived arrays.  Results and certificate
  * statistics must not depend on what those rows hold (tests/test_prescan_gpu.py). */
 int32_t vers_ivf_test_poison_slack(vers_ivf_t* h, float value);
-/* TEST HOOK: the raw pre-filter values of query q of the most recent batched nprobe search on this handle -- every (row, val)
- * the matrix-core list scan left in its partial lists (up to kp per probed list quad), the row as its vec_id, `val` exactly as
+/* TEST HOOK: the raw pre-filter values of query q of the most recent nprobe search on this handle that ran a pre-filter scan -- a
+ * batch on the matrix cores (up to kp keys per probed list quad) or ONE query on the fp16 shadow (scan1h_kernel: q = 0, up to kp keys
+ * per 64..256-row record of a probed list) -- every (row, val) the scan left in its partial lists, the row as its vec_id, `val` exactly as
  * the certificate saw it (|x|^2 - 2 <x~, q>, or -<x~, q> for the cosine distance) and the bound the certificate charges that
  * candidate.  The test computes the reference's distance of each row and checks | val + |q|^2 - D_ref | <= bound.
  * out_info[8]: |q|^2, max |x|^2, shadow residual R^2, the bound for rows outside the list, its candidate-independent part,

@@ -53,11 +53,11 @@ def test_product_boundary_carries_no_test_hooks():
 
 
 def test_certificate_audit_hooks_live_in_the_test_library():
-    """include/vers_hip_audit.h: the coarse / assign certificate audit hooks -- declared there only, bound by testhooks.AUDIT_SIGNATURES,
+    """include/vers_hip_audit.h: the coarse / assign certificate audit hooks and the flat shadow's -- declared there only, bound by testhooks.AUDIT_SIGNATURES,
     exported by libvers_hip_test.so and not by the product library."""
     from vers_amd import testhooks
     names = header_functions("vers_hip_audit.h")
-    assert names == ["vers_ivf_test_last_coarse", "vers_test_assign_filter"]
+    assert names == ["vers_flat_test_last_vals", "vers_flat_test_shadow_state", "vers_ivf_test_last_coarse", "vers_test_assign_filter"]
     assert sorted(testhooks.AUDIT_SIGNATURES) == names
     assert not set(names) & set(header_functions()) and not set(names) & set(header_functions("vers_hip_test.h"))
     so = vbuild.build()

@@ -139,6 +139,11 @@ __global__ __launch_bounds__(kWave * kT1Waves) void scan1t_kernel(Scan1Args a, S
 // (rows_to_f16_kernel) -- with the f32 query from LDS (v_fma_mix: an fp16 x f32 product is exact in the fma), two independent chains
 // per lane (h = 0, 1); lanes l and l ^ 32 hold the two column halves of the same rows and are added at the end: a val per lane.
 // The bound is pre_bound's with shadow = 1: the rows' measured residual, and an f32 accumulation of d products in any order.
+// Term (3) of that bound was MEASURED for the matrix cores; for this kernel it follows from the arithmetic: a lane's chain is d / 2 fused
+// steps (the fp16 x f32 product is exact inside the fma: one rounding per step), the two half-row sums are added once, then xn + dot:
+// | dot - <x~, q'> | <= (d / 2 + 1) u sum_j |x~_j q'_j| <= (d + 2) u |x||q| for q' = -2 q, under the 4 d u |x||q| charged with shadow = 1
+// (d >= 1); the final add's u |val| is inside term (4)'s 16 u S.  Audited value by value, one query at a time, with the products all of
+// one sign so that the roundings cannot cancel: tests/test_certificate_single_gpu.py (DESIGN.md section 1 has the worst ratios).
 // A record (plan1_block) is up to 4 tiles of one list: a block, a wave per tile; the waves' 64 keys are sorted and merged pairwise
 // through LDS, the kp smallest go to the record's partial slot.
 constexpr int kS1hWaves = 4;

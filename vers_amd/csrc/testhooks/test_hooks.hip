@@ -151,9 +151,9 @@ int32_t vers_ivf_test_last_vals(vers_ivf_t* h, uint32_t q, uint64_t* out_vec_ids
   if (!h || !out_n || (cap && (!out_vec_ids || !out_vals || !out_bound))) return fail(VERS_ERR_INVALID, "bad arguments");
   std::shared_lock<std::shared_mutex> lk(h->index);
   UseLastWs use_ws(h);
-  if (!use_ws.ok || !W->last_pre.valid) return fail(VERS_ERR_INVALID, "vers_ivf_test_last_vals: the most recent search did not run the matrix-core list scan");
+  if (!use_ws.ok || !W->last_pre.valid) return fail(VERS_ERR_INVALID, "vers_ivf_test_last_vals: the most recent search ran no pre-filter list scan (a batch on the matrix cores, or one query on the fp16 shadow)");
   const auto lp = W->last_pre;
-  if (q >= lp.b) return fail(VERS_ERR_INVALID, "vers_ivf_test_last_vals: no such query in the last batch");
+  if (q >= lp.b) return fail(VERS_ERR_INVALID, "vers_ivf_test_last_vals: no such query in the last search");
   DeviceGuard g(h->device);
   VERS_HIP_TRY(hipDeviceSynchronize());
   const uint32_t P = lp.P, S = lp.S_max, kp = lp.kp;
@@ -186,19 +186,22 @@ int32_t vers_ivf_test_last_vals(vers_ivf_t* h, uint32_t q, uint64_t* out_vec_ids
   uint32_t n = 0;
   for (uint32_t j = 0; j < P; ++j) {
     if (pl[j] == kNoList) continue;
-    uint32_t off_j = 0;
+    // the list's vec ids in ONE copy (a single query with short records dumps ~100 k keys: a copy per key took seconds)
+    uint32_t off_j = 0, len_j = 0;
     VERS_HIP_TRY(hipMemcpy(&off_j, h->slot_off.as<uint32_t>() + pl[j], 4, hipMemcpyDeviceToHost));
+    VERS_HIP_TRY(hipMemcpy(&len_j, h->slot_len.as<uint32_t>() + pl[j], 4, hipMemcpyDeviceToHost));
+    std::vector<uint32_t> vids(len_j);
+    if (len_j) VERS_HIP_TRY(hipMemcpy(vids.data(), h->row_ids.as<uint32_t>() + off_j, (size_t)len_j * 4, hipMemcpyDeviceToHost));
     for (uint32_t sq = 0; sq < pn[j] && sq < S; ++sq)
       for (uint32_t i = 0; i < kp; ++i) {
         const uint64_t key = keys[((size_t)j * S + sq) * kp + i];
         if (key == kKeyMax) continue;
+        const uint32_t pos = (uint32_t)key - pp[j];  // position in the list: sequence number - the probe's first
+        if (pos >= len_j) return fail(VERS_ERR_INVALID, "vers_ivf_test_last_vals: a dumped key's sequence number lies outside its probe's list");
         if (n < cap) {
-          const uint32_t row = off_j + ((uint32_t)key - pp[j]);
-          uint32_t vid = 0;
-          VERS_HIP_TRY(hipMemcpy(&vid, h->row_ids.as<uint32_t>() + row, 4, hipMemcpyDeviceToHost));
           const uint32_t vb = order_bits_to_f32_bits((uint32_t)(key >> 32));
           float v; memcpy(&v, &vb, 4);
-          out_vec_ids[n] = vid; out_vals[n] = v; out_bound[n] = pb.of((double)v);
+          out_vec_ids[n] = vids[pos]; out_vals[n] = v; out_bound[n] = pb.of((double)v);
         }
         ++n;
       }

@@ -27,6 +27,8 @@ AUDIT_SIGNATURES = {
     "vers_ivf_test_last_coarse": (C.c_int32, [_vp, C.c_uint32, _vp, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_double)]),
     "vers_test_assign_filter": (C.c_int32, [C.c_int32, _vp, C.c_uint32, C.c_uint32, _vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int32, C.c_uint32,
                                             _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "vers_flat_test_shadow_state": (C.c_int32, [_vp, C.POINTER(C.c_double)]),
+    "vers_flat_test_last_vals": (C.c_int32, [_vp, _vp, C.c_uint32, C.c_uint32, _vp, _vp, _vp, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_double)]),
 }
 _lib = None
 
@@ -51,11 +53,37 @@ def poison_slack(index, value: float):
 
 
 def last_vals(index, q: int, cap: int = 8192):
-    """(vec_ids, vals, per-candidate bounds, info dict) of query q of the last batched nprobe search on `index`"""
+    """(vec_ids, vals, per-candidate bounds, info dict) of query q of the last nprobe search on `index` that ran a pre-filter list scan: a
+    batch on the matrix cores, or a single query on the fp16 shadow (scan1h_kernel; q = 0)"""
     ids = np.zeros(cap, dtype=np.uint64); vals = np.zeros(cap, dtype=np.float32); bnd = np.zeros(cap, dtype=np.float64)
     n = C.c_uint32(0); info = (C.c_double * 8)()
     check(lib().vers_ivf_test_last_vals(index._h, q, _ptr(ids), _ptr(vals), _ptr(bnd), cap, C.byref(n), info))
     m = min(n.value, cap)
+    keys = ("qn", "xmax2", "r2", "bound_outside", "bound_common", "kp", "shadow", "metric")
+    return ids[:m].copy(), vals[:m].copy(), bnd[:m].copy(), dict(zip(keys, (float(x) for x in info)))
+
+
+def flat_shadow_state(fc) -> dict:
+    """the fp16 shadow of `fc` (vers_amd.capi.FlatCorpus) as the device holds it: present, n_slots, xmax2, r2, failed, ld, n, rows_built"""
+    st = (C.c_double * 8)()
+    check(lib().vers_flat_test_shadow_state(fc._h, st))
+    keys = ("present", "n_slots", "xmax2", "r2", "failed", "ld", "n", "rows_built")
+    r = dict(zip(keys, (float(x) for x in st)))
+    for k in ("n_slots", "failed", "ld", "n", "rows_built"):
+        r[k] = int(r[k])
+    r["present"] = bool(r["present"])
+    return r
+
+
+def flat_last_vals(fc, query, top_k: int, metric: int = 0, cap: int = 65536):
+    """(vec_ids, vals, per-candidate bounds, info dict) of the last single-query search on `fc`, which ran on the shadow with this query,
+    top_k and metric: every non-empty key of the scan's slots (last_vals' conventions)"""
+    q = np.ascontiguousarray(query, dtype=np.float32).reshape(fc.d)
+    ids = np.zeros(cap, dtype=np.uint64); vals = np.zeros(cap, dtype=np.float32); bnd = np.zeros(cap, dtype=np.float64)
+    n = C.c_uint32(0); info = (C.c_double * 8)()
+    check(lib().vers_flat_test_last_vals(fc._h, _ptr(q), top_k, metric, _ptr(ids), _ptr(vals), _ptr(bnd), cap, C.byref(n), info))
+    assert n.value <= cap, (n.value, cap)
+    m = n.value
     keys = ("qn", "xmax2", "r2", "bound_outside", "bound_common", "kp", "shadow", "metric")
     return ids[:m].copy(), vals[:m].copy(), bnd[:m].copy(), dict(zip(keys, (float(x) for x in info)))
 
