@@ -267,7 +267,9 @@ int32_t vers_ivf_search_exhaustive_dev(vers_ivf_t* h, const float* queries_dev, 
 int32_t vers_ivf_info(vers_ivf_t* h, uint64_t* out_n, uint64_t* out_k, uint64_t* out_max_list_len);
 int32_t vers_ivf_list_lengths(vers_ivf_t* h, uint64_t* out_lengths /* [k] */);
 /* Measurement hook: the most recent inverted-list scan launch -- duration (HIP events on its
- * stream), rows of the union of probed lists (algorithmic), rows actually streamed, work items. */
+ * stream), rows of the union of probed lists (algorithmic), rows actually streamed, work items.
+ * out_streamed_rows is the PLANNED figure (rows x query groups): tiles the scan abandons early
+ * (option "pre_prune") still count whole; vers_ivf_prune_stats has what was skipped. */
 int32_t vers_ivf_last_scan(vers_ivf_t* h, float* out_ms, uint64_t* out_union_rows,
                            uint64_t* out_streamed_rows, uint32_t* out_items);
 
@@ -429,7 +431,7 @@ int32_t vers_ivf_range_search_dev(vers_ivf_t* h, const float* queries_dev, uint6
 int32_t vers_range_phases(double* out8, int32_t reset);
 /* Process-wide switches: every one is a named option set here (or, for a process one does not control from inside, through the ONE
  * environment variable VERS_OPTIONS="name=value,name=value", read once; besides it the library reads only VERS_SHADOW and
- * VERS_ROWMAJOR, the two memory switches of INTEGRATION.md = options "shadow" / "rowmajor").  Unknown name: VERS_ERR_INVALID.
+ * VERS_ROWMAJOR, the two memory switches of INTEGRATION.md = options "shadow" / "rowmajor", and VERS_PRE_PRUNE = option "pre_prune").  Unknown name: VERS_ERR_INVALID.
  * Results are bit-identical under every setting: the switches choose between exact paths and pre-filters behind exact finishes.
  *  Memory:
  *   "shadow" (1)        indexes built / uploaded from now on keep an fp16 shadow of their rows for the list scans
@@ -447,6 +449,10 @@ int32_t vers_range_phases(double* out8, int32_t reset);
  *                       queries on average; smaller batches run as consecutive single queries.
  *   "scan_reserve_cus" (-1 = auto: 64 while another batch of the handle is in flight on another stream, else 0) compute units the
  *                       persistent matrix-core list scan leaves free for the other batches' latency-bound kernels and the exchange.
+ *   "pre_prune" (1)     the batched list scan (fp16 shadow, hi-only query blocks, squared L2) stops reading a 64-row tile once the
+ *                       columns read so far prove that none of its rows can pass any of its queries' thresholds; 0 = every tile is
+ *                       read whole.  Not on sharded handles (measured: only cost there).  "pre_prune_first" (2): the first 64-column
+ *                       step boundary at which a wave tests.
  *   "scan_events" (2)   HIP event records around list-scan launches (vers_ivf_last_scan / vers_ivf_scan_times): 1 always, 0 never,
  *                       2 for batches only (the two records cost a single-query call 5.5-6 us).
  *  A/B and forced paths (tests, measurements):
@@ -533,6 +539,11 @@ int32_t vers_ivf_coarse_stats(vers_ivf_t* h, uint64_t* out_mfma_batches, uint64_
  * exact re-score + certificate, csrc/prescan.hip.h) and queries whose certificate failed and were re-scanned
  * exactly.  Results are bit-identical either way; option "prescan" = 0 keeps the ordered-chain scan for every batch. */
 int32_t vers_ivf_prescan_stats(vers_ivf_t* h, uint64_t* out_batches, uint64_t* out_fallback_queries);
+/* Early abandon of the batched list scan (option "pre_prune"): 64-column steps whose math ran | steps of abandoned tiles that ran no
+ * math (one of them per abandoned tile was still read: it was in flight) | tiles abandoned -- [3] of the most recent matrix-core
+ * scan (zeros when it ran with the switch off or on a path the switch does not cover) and [3] summed over the handle's life.  Either
+ * pointer may be NULL.  HBM bytes not read = (steps - tiles) x 8 KiB. */
+int32_t vers_ivf_prune_stats(vers_ivf_t* h, uint64_t* out_last, uint64_t* out_total);
 /* An fp16 shadow copy of the stored rows (+50 % corpus memory) feeds the matrix-core pre-selection of batched searches:
  * half the HBM bytes per list scan, a ~2x wider certificate window, the same exact f32 finish -- results stay
  * bit-identical.  On by default (VERS_SHADOW=0 or vers_set_option("shadow", 0) before build / upload: f32 rows feed the

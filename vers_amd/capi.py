@@ -84,6 +84,7 @@ SIGNATURES = {
     "vers_ivf_last_finish_ms": (C.c_int32, [_vp, C.POINTER(C.c_float)]),
     "vers_ivf_coarse_stats": (C.c_int32, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "vers_ivf_prescan_stats": (C.c_int32, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "vers_ivf_prune_stats": (C.c_int32, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "vers_ivf_shadow_state": (C.c_int32, [_vp, C.POINTER(C.c_int32), C.POINTER(C.c_uint64)]),
     "vers_ivf_layout_bytes": (C.c_int32, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "vers_ivf_build_sharded_dev": (C.c_int32, [_vp, _vp, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64,
@@ -150,7 +151,7 @@ def lib():
 def env_option(name: str, default: int) -> int:
     """What the library starts option `name` with in THIS environment: VERS_OPTIONS="name=value,..." (csrc/core.hip's table; the two
     documented switches VERS_SHADOW / VERS_ROWMAJOR are options "shadow" / "rowmajor"), else `default`.  vers_set_option overrides."""
-    alias = {"shadow": "VERS_SHADOW", "rowmajor": "VERS_ROWMAJOR"}
+    alias = {"shadow": "VERS_SHADOW", "rowmajor": "VERS_ROWMAJOR", "pre_prune": "VERS_PRE_PRUNE"}
     val = os.environ.get(alias[name]) if name in alias else None
     for kv in os.environ.get("VERS_OPTIONS", "").split(","):
         k, _, v = kv.partition("=")

@@ -16,10 +16,11 @@ int32_t fail(int32_t status, const std::string& msg) {
 }
 // ---- the option table -----------------------------------------------------------------------------------------------------------
 // Every switch of the library is a named 64-bit option: set by vers_set_option(name, value) (include/vers_hip.h lists the names), read
-// where it is used.  The ENVIRONMENT is read for exactly three names, once, when the first option is read:
+// where it is used.  The ENVIRONMENT is read for exactly four names, once, when the first option is read:
 //   VERS_OPTIONS="name=value,name=value"   the same names and values as vers_set_option (A/B runs and tests of a process one does not
 //                                          control from inside: value in any base strtoll(.., 0) takes)
 //   VERS_SHADOW=0|1, VERS_ROWMAJOR=0|1     the two memory switches INTEGRATION.md documents (= options "shadow", "rowmajor")
+//   VERS_PRE_PRUNE=0|1                     the list scan's early abandon of tiles (= option "pre_prune")
 // (the optional RCCL adapter, a separate library, reads VERS_RCCL_TIMEOUT_S).
 namespace {
 struct OptEntry { const char* name; std::atomic<int64_t> v{0}; std::atomic<bool> set{false}; };
@@ -28,7 +29,7 @@ OptEntry g_opts[] = {
     {"prescan"}, {"pre_slack"}, {"seg_rows"}, {"pre_narrow"}, {"pre_wide"}, {"pre_hi_only"}, {"coarse"}, {"coarse1"}, {"scan1t"},
     {"ref_as_nprobe1"}, {"assign"}, {"assign_tiles"}, {"assign_tiles_min"}, {"upload_stage_mb"}, {"scan_debug"},
     {"poison_alloc"}, {"poison_slack_bits"}, {"test_fail_sharded"}, {"memory"}, {"wide_k"}, {"assign_terms"}, {"assign_glds"},
-    {"add_batch_rows"}, {"remove_batch_ids"}, {"compact_fused"},
+    {"add_batch_rows"}, {"remove_batch_ids"}, {"compact_fused"}, {"pre_prune"}, {"pre_prune_first"},
 };
 OptEntry* opt_find(const char* name) {
   for (OptEntry& e : g_opts)
@@ -44,6 +45,7 @@ void opt_env_once() {
     };
     if (const char* s = getenv("VERS_SHADOW")) put("shadow", s);
     if (const char* s = getenv("VERS_ROWMAJOR")) put("rowmajor", s);
+    if (const char* s = getenv("VERS_PRE_PRUNE")) put("pre_prune", s);
     if (const char* s = getenv("VERS_OPTIONS")) {
       std::string all(s);
       size_t i = 0;

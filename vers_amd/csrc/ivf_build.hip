@@ -567,6 +567,10 @@ int32_t poison_slack(vers_ivf* h, float value, hipStream_t st) {
 // |x|^2 of storage rows [r_begin, r_end) for the matrix-core list scan; a full refresh also resets the maximum
 int32_t refresh_norms(vers_ivf* h, uint64_t r_begin, uint64_t r_end, hipStream_t st) {
   if (int32_t rc = h->pre_misc.reserve(64)) return rc;
+  if (!h->prune_ctr.p) {  // the list scan's early-abandon totals: zeroed HERE, synchronously, under the exclusive lock -- scans on any stream only ever add
+    if (int32_t rc = h->prune_ctr.reserve(64)) return rc;
+    VERS_HIP_TRY(hipMemset(h->prune_ctr.p, 0, 64));
+  }
   const bool full = r_begin == 0 && r_end == h->cap_rows;
   if (full) {
     if (int32_t rc = h->xnorm.reserve((h->cap_rows ? h->cap_rows : 1) * sizeof(float))) return rc;

@@ -97,6 +97,8 @@ struct SearchWs {
   struct LastCoarse { bool valid = false; uint32_t b = 0, P = 0; int x3 = 0; float cmax2 = 0.0f; } last_coarse;
   DevBuf coarse_qe;
   GroupTotals last_tot{};
+  DevBuf prune_tab;                      // [b][ld / 64] early-abandon table of the batch (prescan.hip.h, prune_table_kernel)
+  const uint32_t* prune_last = nullptr;  // device: the last matrix-core scan's step counters (nullptr: it ran with the early abandon off)
   const GroupTotals* tot_dev = nullptr;  // device totals of the last planned search
   bool tot_valid = false;
   // lease bookkeeping
@@ -208,6 +210,7 @@ struct vers_ivf {
   } rm;
   // matrix-core list scan (prescan.hip.h): |x|^2 per storage row, [0] max |x|^2 bits, [1] certificate failures (running)
   DevBuf xnorm, pre_misc;
+  DevBuf prune_ctr;  // u64 [3] steps executed | steps without math | tiles abandoned by the list scan's early abandon, over the handle's life
   // fp16 shadow of the rows for the matrix-core pre-selection (+50 % corpus memory; VERS_SHADOW=0 or a failed
   // allocation: the f32 rows feed it).  The wider certificate window makes it sensitive to data with many near-ties:
   // the failure counter is watched through a pinned word and the shadow is switched off for the handle when more

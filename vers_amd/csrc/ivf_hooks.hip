@@ -104,6 +104,26 @@ int32_t vers_ivf_prescan_stats(vers_ivf_t* h, uint64_t* out_batches, uint64_t* o
   return VERS_OK;
 }
 
+int32_t vers_ivf_prune_stats(vers_ivf_t* h, uint64_t* out_last /* [3] */, uint64_t* out_total /* [3] */) {
+  if (!h) return fail(VERS_ERR_INVALID, "null handle");
+  DeviceGuard g(h->device);
+  unsigned long long tot[3] = {0, 0, 0};
+  uint32_t last[3] = {0, 0, 0};
+  {
+    UseLastWs use_ws(h);
+    if (use_ws.ok && W->prune_last != nullptr) {
+      if (W->used && W->done) VERS_HIP_TRY(hipEventSynchronize(W->done));
+      VERS_HIP_TRY(hipMemcpy(last, W->prune_last, sizeof(last), hipMemcpyDeviceToHost));
+    }
+  }
+  if (h->prune_ctr.p) VERS_HIP_TRY(hipMemcpy(tot, h->prune_ctr.p, sizeof(tot), hipMemcpyDeviceToHost));
+  for (int i = 0; i < 3; ++i) {
+    if (out_last) out_last[i] = last[i];
+    if (out_total) out_total[i] = tot[i];
+  }
+  return VERS_OK;
+}
+
 int32_t vers_ivf_scan_times(vers_ivf_t* h, float* out_ms, uint32_t cap, uint32_t* out_n, int32_t reset) {
   if (!h || !out_n || (cap && !out_ms)) return fail(VERS_ERR_INVALID, "bad arguments");
   DeviceGuard g(h->device);

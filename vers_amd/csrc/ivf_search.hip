@@ -288,7 +288,7 @@ int32_t launch_scan1h(vers_ivf* h, const Scan1hArgs& a, uint32_t items_bound, hi
 // the matrix-core list scan (prescan.hip.h); timed through the same event ring as launch_ivf_scan
 template <int NQ>
 int32_t launch_prescan(vers_ivf* h, const IvfSrc<NQ>& src, uint32_t items_bound, uint32_t kp, uint32_t* qflags, uint32_t* quad_ctr,
-                       bool shadow, bool hi_only, hipStream_t st) {
+                       bool shadow, bool hi_only, uint32_t b, hipStream_t st) {
   PreParams p;
   p.rows_bf = shadow ? h->rows_bf.as<uint16_t>() : nullptr;
   p.ld = h->ld;
@@ -308,18 +308,47 @@ int32_t launch_prescan(vers_ivf* h, const IvfSrc<NQ>& src, uint32_t items_bound,
   }
   p.next_quad = (p.debug & 32u) ? nullptr : quad_ctr;  // zeroed with the planning tables
   hi_only = hi_only && shadow;
+  // Early abandon of tiles whose first columns rule every row out (prescan.hip.h, prune_lower): hi-only query blocks on the shadow,
+  // squared L2, rows of at least three steps (one boundary with a step left to save).  option "pre_prune" = 0: every tile is read whole.
+  const uint32_t n_steps = h->ld / 64u;
+  // (the table's rows must fit LDS beside what the planner chose the block width for: prescan_lds_bytes_g)
+  // Not on a sharded handle: a rank holds an eighth of the lists, its launch is short and the lists that are some query's nearest sit
+  // mostly on other ranks -- thresholds arrive too late to abandon anything, and the test is not free (profiles/r07_summary.txt).
+  const bool prune = hi_only && h->metric == 0 && h->world == 1 && opt_get("pre_prune", 1) != 0 && n_steps >= 3 && n_steps <= kPruneMaxSteps && h->pre_misc.p != nullptr && h->prune_ctr.p != nullptr &&
+                     prescan_lds_bytes_g(h->ld, kp, NQ, true, true) <= 160u * 1024u;
+  p.prune_tab = nullptr; p.prune_first = 0; p.prune_until = 0; p.prune_om = 0.0f; p.prune_last = nullptr; p.prune_tot = nullptr;
+  W->prune_last = nullptr;
+  if (prune) {
+    if (int32_t rc = W->prune_tab.reserve((size_t)b * n_steps * sizeof(float))) return rc;
+    hipLaunchKernelGGL(prune_table_kernel, dim3((b + 3) / 4), dim3(256), 0, st, src.qp, src.ldq, h->ld, b, (const uint32_t*)h->pre_misc.as<uint32_t>(),
+                       W->prune_tab.as<float>());
+    VERS_HIP_TRY(hipGetLastError());
+    p.prune_tab = W->prune_tab.as<float>();
+    p.prune_first = (uint32_t)std::max<int64_t>(1, std::min<int64_t>(opt_get("pre_prune_first", 2), n_steps));
+    p.prune_until = std::max<uint32_t>(p.prune_first, n_steps / 2u);
+    p.prune_om = (float)(1.0 - prune_eps(h->ld));  // (rounds to nearest: eps carries a few u of slack for it)
+    p.prune_last = quad_ctr + 1;  // (the three words behind the hand-out counter: zeroed with it)
+    p.prune_tot = h->prune_ctr.as<unsigned long long>();
+    W->prune_last = quad_ctr + 1;
+  }
   if (NQ == kPreQWide && !hi_only) return fail(VERS_ERR_INVALID, "internal: 64-query blocks exist on the fp16 shadow with the hi-only query block");
-  const size_t lds = prescan_lds_bytes_g(h->ld, kp, NQ, hi_only);
+  const size_t lds = prescan_lds_bytes_g(h->ld, kp, NQ, hi_only, prune);
   const bool wide_lists = kp > kPreMaxKp;  // (candidate lists of more than one key per lane: plan_search chose hi-only blocks of 32 or 16 queries on the shadow)
   if (wide_lists && (!hi_only || NQ == kPreQWide || kp > kWideMaxKp)) return fail(VERS_ERR_INVALID, "internal: wide candidate lists need the fp16 shadow with hi-only query blocks of <= 32 queries");
+  // (prune: the instantiation that abandons tiles early; without it -- switch off, cosine distance, sharded handle, hi + lo or f32
+  // blocks -- the kernel is the one it was before the early abandon existed)
+  using Kern = void (*)(IvfSrc<NQ>, PreParams);
+  Kern kern;
   if constexpr (NQ == kPreQWide) {
-    if (int32_t rc = scan_prepare_launch(prescan_kernel_g<true, NQ, IvfSrc<NQ>, false>, lds)) return rc;
+    kern = prune ? (Kern)prescan_kernel_g<true, NQ, IvfSrc<NQ>, false, false, true> : (Kern)prescan_kernel_g<true, NQ, IvfSrc<NQ>, false>;
   } else if (wide_lists) {
-    if (int32_t rc = scan_prepare_launch(prescan_kernel_g<true, NQ, IvfSrc<NQ>, false, true>, lds)) return rc;
+    kern = prune ? (Kern)prescan_kernel_g<true, NQ, IvfSrc<NQ>, false, true, true> : (Kern)prescan_kernel_g<true, NQ, IvfSrc<NQ>, false, true>;
+  } else if (hi_only) {
+    kern = prune ? (Kern)prescan_kernel_g<true, NQ, IvfSrc<NQ>, false, false, true> : (Kern)prescan_kernel_g<true, NQ, IvfSrc<NQ>, false>;
   } else {
-    if (int32_t rc = hi_only ? scan_prepare_launch(prescan_kernel_g<true, NQ, IvfSrc<NQ>, false>, lds)
-                     : shadow ? scan_prepare_launch(prescan_kernel_g<true, NQ, IvfSrc<NQ>>, lds) : scan_prepare_launch(prescan_kernel_g<false, NQ, IvfSrc<NQ>>, lds)) return rc;
+    kern = shadow ? (Kern)prescan_kernel_g<true, NQ, IvfSrc<NQ>> : (Kern)prescan_kernel_g<false, NQ, IvfSrc<NQ>>;
   }
+  if (int32_t rc = scan_prepare_launch(kern, lds)) return rc;
   uint32_t blocks = (items_bound + kWavesPerBlock - 1) / kWavesPerBlock;
   uint32_t per_cu = std::max<uint32_t>(1, std::min<uint32_t>(2, (uint32_t)((160u * 1024u) / lds)));  // 1 at d = 768 (measured: as fast as 2)
   const uint32_t reserve = scan_reserve(h, st);  // (vers_set_option "scan_reserve_cus"; auto: only while another batch is in flight)
@@ -328,15 +357,7 @@ int32_t launch_prescan(vers_ivf* h, const IvfSrc<NQ>& src, uint32_t items_bound,
   if (blocks == 0) blocks = 1;
   const uint32_t slot = (uint32_t)(W->ev_count % SearchWs::kEvRing);
   if (W->ev_on) VERS_HIP_TRY(hipEventRecord(W->ev0[slot], st));
-  if constexpr (NQ == kPreQWide) {
-    hipLaunchKernelGGL((prescan_kernel_g<true, NQ, IvfSrc<NQ>, false>), dim3(blocks), dim3(kWave * kPreWavesG), lds, st, src, p);
-  } else if (wide_lists) {
-    hipLaunchKernelGGL((prescan_kernel_g<true, NQ, IvfSrc<NQ>, false, true>), dim3(blocks), dim3(kWave * kPreWavesG), lds, st, src, p);
-  } else {
-    if (hi_only) hipLaunchKernelGGL((prescan_kernel_g<true, NQ, IvfSrc<NQ>, false>), dim3(blocks), dim3(kWave * kPreWavesG), lds, st, src, p);
-    else if (shadow) hipLaunchKernelGGL((prescan_kernel_g<true, NQ, IvfSrc<NQ>>), dim3(blocks), dim3(kWave * kPreWavesG), lds, st, src, p);
-    else hipLaunchKernelGGL((prescan_kernel_g<false, NQ, IvfSrc<NQ>>), dim3(blocks), dim3(kWave * kPreWavesG), lds, st, src, p);
-  }
+  hipLaunchKernelGGL(kern, dim3(blocks), dim3(kWave * kPreWavesG), lds, st, src, p);
   VERS_HIP_TRY(hipGetLastError());
   if (W->ev_on) {
     VERS_HIP_TRY(hipEventRecord(W->ev1[slot], st));
@@ -418,9 +439,9 @@ int32_t search_dev_locked(vers_ivf* h, const float* q_dev, uint64_t ldq_in, uint
       sa.rows_h = h->rows_bf.as<uint16_t>(); sa.xnorm = h->xnorm.as<float>(); sa.recs = W->items.as<Item1Rec>(); sa.n_items_dev = &tot->n_items; sa.qp = qp;
       sa.partials = W->partials.as<uint64_t>(); sa.qflags = qflags; sa.ld = h->ld; sa.kp = kp; sa.metric = (uint32_t)h->metric;
       if (int32_t rc2 = launch_scan1h(h, sa, (uint32_t)items_bound, st)) return rc2;
-    } else if (int32_t rc2 = QG == kPreQWide     ? launch_prescan(h, src_w, (uint32_t)items_bound, kp, qflags, quad_ctr, use_shadow, hi_only, st)
-                             : QG == kPreQNarrow ? launch_prescan(h, src_n, (uint32_t)items_bound, kp, qflags, quad_ctr, use_shadow, hi_only, st)
-                                                 : launch_prescan(h, src, (uint32_t)items_bound, kp, qflags, quad_ctr, use_shadow, hi_only, st)) return rc2;
+    } else if (int32_t rc2 = QG == kPreQWide     ? launch_prescan(h, src_w, (uint32_t)items_bound, kp, qflags, quad_ctr, use_shadow, hi_only, b, st)
+                             : QG == kPreQNarrow ? launch_prescan(h, src_n, (uint32_t)items_bound, kp, qflags, quad_ctr, use_shadow, hi_only, b, st)
+                                                 : launch_prescan(h, src, (uint32_t)items_bound, kp, qflags, quad_ctr, use_shadow, hi_only, b, st)) return rc2;
     if (int32_t rc2 = start_pending_ahead(h, st)) return rc2;  // the next batch's coarse quantiser: under this batch's exact finish
     RescoreArgs a;
     a.partials = W->partials.as<uint64_t>(); a.P = P; a.S_max = S_max; a.kp = kp; a.top_k = top_k; a.d_pad = h->ld;

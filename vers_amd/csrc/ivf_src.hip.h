@@ -84,6 +84,10 @@ struct IvfSrc {
     const ItemDesc d = items[it];
     return pairs[pair_off[d.list] + d.group * QG + qi];
   }
+  __device__ __forceinline__ uint32_t query_index(uint32_t it, uint32_t qi) const {  // the batch's query in slot qi
+    const ItemDesc d = items[it];
+    return pairs[pair_off[d.list] + d.group * QG + qi] / P;
+  }
   __device__ __forceinline__ const float* query_row(uint32_t it, uint32_t qi) const {  // padded query of slot qi
     const ItemDesc d = items[it];
     return qp + (uint64_t)(pairs[pair_off[d.list] + d.group * QG + qi] / P) * ldq;

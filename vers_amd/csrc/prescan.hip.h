@@ -37,6 +37,7 @@ namespace vers {
 typedef __attribute__((ext_vector_type(16))) float f32x16_t;
 typedef __attribute__((ext_vector_type(8))) _Float16 f16x8_t;
 typedef __attribute__((ext_vector_type(4))) _Float16 f16x4_t;
+typedef __attribute__((ext_vector_type(2))) _Float16 f16x2_t;
 
 constexpr int kPreQ = 32;        // queries per group: two sets of 16 (one 16x16x1 4-block MFMA covers 64 rows x 16 queries)
 // Round 5: the WIDE variant on the fp16 shadow -- 64 queries per block as two sets of 32 (two B operands per row piece), the query
@@ -64,7 +65,17 @@ struct PreParams {
   uint32_t debug;
   uint32_t metric;      // 0: val = |x|^2 - 2<x,q> ~ D_ref - |q|^2 ; 1 (cosine distance 1 - dot): val = -<x,q> ~ D_ref - 1
   unsigned long long* stamps;
+  // abandoning tiles early (prune_lower below; fp16 shadow, hi-only query blocks, squared L2): nullptr = off
+  const float* prune_tab;   // [b][ld / 64] per query and step boundary: prune_tail_entry (prune_table_kernel)
+  uint32_t prune_first;     // the first step boundary (columns consumed / 64) at which a wave tests
+  uint32_t prune_until;     // ... and the last: half the row (abandoning later saves little; the test is not free)
+  float prune_om;           // 1 - eps of prune_lower
+  uint32_t* prune_last;     // [3] steps executed | steps without math | tiles abandoned, this launch (zeroed with the planning tables)
+  unsigned long long* prune_tot;  // [3] the same over the handle's life
 };
+
+// (defined next to pre_bound, below)
+__host__ __device__ inline float prune_lower(float acc_min, float m_p, float om_eps, float tail);
 
 
 // f32 tiles -> fp16 shadow tiles (round to nearest even), laid out as the A operand of v_mfma_f32_32x32x16_f16: a
@@ -178,8 +189,14 @@ __host__ __device__ inline uint32_t pre_cap(uint32_t kp) { return kp <= 40u ? 64
 // against the CU's 160 KB of LDS; 16 queries fit up to d = 2304).  Same kernel, same MFMA (half its query columns idle).
 // hi_only: the fp16 query block WITHOUT its lo half (2 B per element instead of 4): 32 queries fit up to d = 2304, 16 up to
 // d = 4608; the certificate charges the query's measured fp16 residual instead (pre_bound, Rq2).
-inline size_t prescan_lds_bytes_g(uint32_t ld, uint32_t kp, uint32_t nq = 32, bool hi_only = false) {  // query block | hand-out word | buffers | cnt, done, thr, locks
-  return (size_t)ld * nq * (hi_only ? sizeof(uint16_t) : sizeof(float)) + 16 + (size_t)nq * pre_cap(kp) * sizeof(uint64_t) + 6 * kPreCtl * sizeof(uint32_t);  // (+ pair | sequence base of the quad's queries)
+// with_table: a hi-only block that abandons tiles early carries the quad's rows of the early-abandon table behind the control arrays:
+// nq x ld / 64 floats (3 KB for 64 queries at d = 768, 3.8 KB at d = 960 -- 64-query blocks still fit up to there).  The PLANNER
+// chooses the block width without it (the same choice whatever "pre_prune" says, and the same as before the table existed); the
+// launch adds it where it still fits the CU's 160 KB and runs with the early abandon off where it does not (the last 64 .. 192
+// columns below each width's limit: ld 2240, wide lists 1472, 16-query blocks 4672 .. 4800).
+inline size_t prescan_lds_bytes_g(uint32_t ld, uint32_t kp, uint32_t nq = 32, bool hi_only = false, bool with_table = false) {  // query block | hand-out word | buffers | cnt, done, thr, locks
+  return (size_t)ld * nq * (hi_only ? sizeof(uint16_t) : sizeof(float)) + 16 + (size_t)nq * pre_cap(kp) * sizeof(uint64_t) + 6 * kPreCtl * sizeof(uint32_t) +  // (+ pair | sequence base of the quad's queries)
+         (hi_only && with_table ? (size_t)nq * (ld / 64u) * sizeof(float) : 0);
 }
 constexpr int kPreQNarrow = 16;
 
@@ -223,9 +240,13 @@ __device__ __forceinline__ uint64_t buffer_sorted(const uint64_t* bq, uint32_t n
 // dropped half would have contributed, |<x~, q' - fp16(q')>| <= |x~| |q' - fp16(q')|, is charged to the certificate with the query's
 // MEASURED residual (ivf_rescore_kernel sums it next to |q|^2).
 // WIDE: candidate lists of more than one key per lane (kp in (64, kWideMaxKp], cap 256): the compaction is a four-register sort.
-template <bool BF, int NQ, bool LO, bool WIDE, class Src, class Stage>
+// steps a wave ran the math of | steps it did not (the rest of abandoned tiles) | tiles abandoned: wave-uniform, summed per block at the
+// end of the launch
+struct PruneCtr { uint32_t exec, skipped, tiles; };
+
+template <bool BF, int NQ, bool LO, bool WIDE, bool PR, class Src, class Stage>
 __device__ __forceinline__ void prescan_item_g(const Src& src, const PreParams& p, uint32_t it, const ItemView<NQ>& v, int half, int lane,
-                                               const float* qm, uint64_t* cbuf, uint32_t* ctl, Stage&& stage) {
+                                               const float* qm, uint64_t* cbuf, uint32_t* ctl, PruneCtr& pc, Stage&& stage) {
   const uint32_t n_tiles = (v.nrows + kWave - 1) / kWave;
   const uint32_t t_per = (n_tiles + kPreParts - 1) / kPreParts;  // (half = the wave's index among those of its segment)
   const uint32_t t_begin = (uint32_t)half * t_per < n_tiles ? (uint32_t)half * t_per : n_tiles;
@@ -234,6 +255,7 @@ __device__ __forceinline__ void prescan_item_g(const Src& src, const PreParams& 
     stage();
     return;
   }
+  constexpr bool PRUNE = PR;  // the instantiations that may abandon a tile early (below): launched only with the table in place
   constexpr int kSets = BF ? (NQ > 32 ? 2 : 1) : 2;   // query columns a lane serves (accumulator layouts: see above)
   constexpr int kSetW = BF ? 32 : 16;                  // query columns per set: one MFMA's N
   constexpr int kAcc = BF ? 2 * kSets : 2;             // accumulators: fp16 rows [set][row half of the tile], f32 rows [set]
@@ -266,7 +288,6 @@ __device__ __forceinline__ void prescan_item_g(const Src& src, const PreParams& 
   u32x4 buf[R][kLoads];
   float xn[R];
   uint32_t gthr[R][2];
-  const uint32_t n_steps = (t_end - t_begin) * nch;
   uint32_t ti = t_begin, ci = 0;
   uint32_t vslot[2] = {0, 0};
   auto issue_next = [&](auto btag, bool with_thr) {
@@ -305,6 +326,7 @@ __device__ __forceinline__ void prescan_item_g(const Src& src, const PreParams& 
   // 16 vals of ONE query column (lane & 15), rows 16*(e>>2) + 4*quarter + (e&3): one compare per register against the
   // lane's threshold decides whether anything happens at all.
   // (BF: S = 0 and `h` is the row half of the tile the accumulator covers)
+  bool dead = false;  // (wave-uniform) the tile that ends is an ABANDONED one (below): nothing of it passes, fold only clears
   auto fold = [&](auto set_tag, f32x16_t& a, uint32_t t, uint32_t h) {
     constexpr int S = decltype(set_tag)::value;
     constexpr uint32_t kRowStep = BF ? 8u : 16u;  // rows between the lane's register groups of four
@@ -325,6 +347,7 @@ __device__ __forceinline__ void prescan_item_g(const Src& src, const PreParams& 
     uint32_t pm = 0;
 #pragma unroll
     for (int e = 0; e < 16; ++e) pm |= a[e] <= thr[S] ? 1u << e : 0u;
+    if (PRUNE && dead) pm = 0;
     if (__ballot(pm != 0) != 0 && !(p.debug & 1u)) {
       const uint32_t q = (uint32_t)(S * kSetW + n);
       uint64_t* const bq = cbuf + (size_t)q * cap;
@@ -470,6 +493,17 @@ __device__ __forceinline__ void prescan_item_g(const Src& src, const PreParams& 
     }
   }
   uint32_t tc = t_begin, cc = 0;
+  // EARLY ABANDON (hi-only blocks on the shadow, squared L2; prune_lower): np[hf] = the lane's share of |x~_P|^2 of its row of tile half
+  // hf -- the 8 columns per column block its row pieces hold --, ptab = the quad's rows of the per-query table (stage()).  `skip`: the
+  // step in flight belongs to a tile the wave has left; it is consumed without math.
+  const bool prune_on = PRUNE && p.prune_tab != nullptr;  // (wave-uniform)
+  const float* const ptab = reinterpret_cast<const float*>(ctl + 6 * kPreCtl);
+  // ADAPTIVE OFF: a tile the wave had to read whole switches the test (and the norm's dot products) off for the rest of the ITEM -- its
+  // other tiles hold rows of the same list against the same queries --; the next item starts with it on again.  On data without
+  // cluster contrast nothing is ever abandoned and the test costs one tile in an item's share (measured: profiles/r07_summary.txt).
+  bool pon = prune_on;  // (wave-uniform)
+  float np[2] = {0.0f, 0.0f};
+  bool skip = false;
   unsigned long long t_math = 0, t_fold = 0, t_issue = 0;
   const unsigned long long tp1 = stamp ? __builtin_amdgcn_s_memtime() : 0ull;
   uint32_t fold_tile = 0;
@@ -487,11 +521,13 @@ __device__ __forceinline__ void prescan_item_g(const Src& src, const PreParams& 
       if (two) fold(Set1{}, acc[1], fold_tile, 0u);
     }
   };
-  auto step = [&](auto btag, uint32_t s0) {
+  auto step = [&](auto btag) {
     constexpr int B = decltype(btag)::value;
     const unsigned long long ti0 = stamp ? __builtin_amdgcn_s_memtime() : 0ull;
     issue_next(std::integral_constant<int, (B + R - 1) % R>{}, true);
-    if (s0 + B < n_steps) {
+    if (PRUNE && skip) {
+      skip = false;
+    } else {
       unsigned long long t1 = 0, t2 = 0;
       if (stamp) { t1 = __builtin_amdgcn_s_memtime(); t_issue += t1 - ti0; }
       if (!(p.debug & 2u)) {
@@ -536,6 +572,17 @@ __device__ __forceinline__ void prescan_item_g(const Src& src, const PreParams& 
                   acc[kAcc - 2 + hf] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8_t, buf[B][2 * cb + hf]), bh2, acc[kAcc - 2 + hf], 0, 0, 0);
               }
           }
+          if constexpr (PRUNE)
+            if (pon && cc < p.prune_until) {  // |x~|^2 of the step's row pieces: packed fp16 dot products into the running f32 (every term >= 0)
+#pragma unroll
+              for (int i = 0; i < kLoads; ++i) {
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                  const f16x2_t h2 = __builtin_bit_cast(f16x2_t, buf[B][i][u]);
+                  np[i & 1] = __builtin_amdgcn_fdot2(h2, h2, np[i & 1], false);
+                }
+              }
+            }
         }
       } else {
         acc[0][0] += __uint_as_float(buf[B][0][0] ^ buf[B][kLoads - 1][3]);
@@ -545,8 +592,49 @@ __device__ __forceinline__ void prescan_item_g(const Src& src, const PreParams& 
         t2 = __builtin_amdgcn_s_memtime();
         t_math += t2 - t1;
       }
-      if (++cc == nch) {
+      if constexpr (PRUNE) pc.exec += 1;
+      // The tile ends here when its last step is done -- or, EARLY ABANDON, at a step boundary inside it with at least one of its steps
+      // not issued yet, if for every live query column the smallest val the unread columns could still bring any row to (prune_lower)
+      // lies above the lane's threshold -- fold would drop every row -- and the tile's 64 |x|^2 are finite (a row with a NaN in a
+      // column not read yet must reach fold's non-finite check).  Every comparison is false on a NaN: no pruning then.
+      bool leave = ++cc == nch;  // (wave-uniform)
+      if constexpr (PRUNE) {
+        if (!leave && pon && cc >= p.prune_first && cc <= p.prune_until && cc + 1 < nch) {
+          float r0 = np[0] + __shfl_xor(np[0], 32, kWave), r1 = np[1] + __shfl_xor(np[1], 32, kWave);  // whole rows' |x~_P|^2
+          float m = r0 < r1 ? r0 : r1;
+#pragma unroll
+          for (int off = 16; off > 0; off >>= 1) {
+            const float o = __shfl_xor(m, off, kWave);
+            m = o < m ? o : m;
+          }
+          bool keep = !(__builtin_fabsf(xn[B]) < __builtin_inff());
+#pragma unroll
+          for (int s = 0; s < kSets; ++s) {
+            if (live[s]) {
+              // (a NaN in acc[..][0] makes the comparison below false; one in another element is skipped by these minima -- harmless:
+              // an abandoned tile still goes through fold(), whose non-finite check on the partial accumulators sets `bad`)
+              float am = acc[2 * s][0];
+#pragma unroll
+              for (int e = 0; e < 16; ++e) {
+                am = acc[2 * s][e] < am ? acc[2 * s][e] : am;
+                am = acc[2 * s + 1][e] < am ? acc[2 * s + 1][e] : am;
+              }
+              keep |= !(prune_lower(am, m, p.prune_om, ptab[(uint32_t)(s * kSetW + n) * nch + cc]) > thr[s]);
+            }
+          }
+          if (__ballot(keep) == 0) {
+            pc.skipped += nch - cc;
+            pc.tiles += 1;
+            if (tc + 1 < t_end) { ti = tc + 1; ci = 0; }  // (issue_next: on to the next tile; the step in flight is this tile's next one)
+            skip = true;
+            leave = dead = true;
+          }
+        }
+      }
+      if (leave) {
         cc = 0;
+        if (!(PRUNE && dead)) {
+        if constexpr (PRUNE) pon = false;  // (read whole: no more tests in this item)
 #pragma unroll
         for (int s = 0; s < 2; ++s) {
           if (live[s]) {
@@ -576,16 +664,21 @@ __device__ __forceinline__ void prescan_item_g(const Src& src, const PreParams& 
           acc[0] = __builtin_amdgcn_mfma_f32_16x16x1f32(xn[B], nrm, acc[0], 0, 0, 0);  // + |x_row|^2 for every query column
           if (two) acc[1] = __builtin_amdgcn_mfma_f32_16x16x1f32(xn[B], nrm, acc[1], 0, 0, 0);
         }
+        }
         fold_tile = tc;
         ++tc;
-        run_folds();
+        run_folds();  // (an abandoned tile: nothing passes, the accumulators are cleared)
+        dead = false;
+        np[0] = np[1] = 0.0f;
         if (stamp) t_fold += __builtin_amdgcn_s_memtime() - t2;
       }
     }
   };
-  for (uint32_t s0 = 0; s0 < n_steps; s0 += R) {
-    step(std::integral_constant<int, 0>{}, s0);
-    step(std::integral_constant<int, 1>{}, s0);
+  for (;;) {  // until the wave's tiles are done (an abandoned tile ends early)
+    step(std::integral_constant<int, 0>{});
+    if (tc >= t_end) break;
+    step(std::integral_constant<int, 1>{});
+    if (tc >= t_end) break;
   }
   const unsigned long long te0 = stamp ? __builtin_amdgcn_s_memtime() : 0ull;
   if (stamp && lane == 0) {
@@ -603,10 +696,13 @@ __device__ __forceinline__ void prescan_item_g(const Src& src, const PreParams& 
   if (stamp && lane == 0) atomicAdd(p.stamps + 11, __builtin_amdgcn_s_memtime() - te0);
 }
 
-template <bool BF, int NQ, class Src, bool LO = true, bool WIDE = false>
+// PR: the variant that abandons tiles early (hi-only blocks on the shadow; launched when the early abandon is on for the call: with PR =
+// false the kernel is the one it was before the early abandon existed -- no table in LDS, no norms, no tests)
+template <bool BF, int NQ, class Src, bool LO = true, bool WIDE = false, bool PR = false>
 __global__ __launch_bounds__(kWave * kPreWavesG) __attribute__((amdgpu_waves_per_eu(kPreWpe, kPreWpe))) void prescan_kernel_g(Src src, PreParams p) {
   static_assert(NQ == kPreQ || NQ == kPreQNarrow || (NQ == kPreQWide && BF && !LO), "32 queries per block, the narrow variant's 16, or 64 with the hi-only block on the shadow");
   static_assert(BF || LO, "the hi-only query block belongs to the fp16 shadow");
+  static_assert(!PR || (BF && !LO), "tiles are abandoned early on the fp16 shadow with hi-only query blocks");
   static_assert(!WIDE || (BF && !LO && NQ <= kPreQ), "wide lists: fp16 shadow, hi-only query blocks of 32 or 16 queries (256 keys x 32 queries = 64 KB of buffers)");
   const int lane = threadIdx.x & 63;
   const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -628,6 +724,7 @@ __global__ __launch_bounds__(kWave * kPreWavesG) __attribute__((amdgpu_waves_per
   constexpr uint32_t kMaxRun = 8;
   uint32_t run_first = 0xFFFFFFFFu, run_last = 0, prev_nq = 0;  // the quads whose lists still sit in LDS (one merged run)
   uint32_t cur_list = 0xFFFFFFFFu, cur_group = 0;
+  PruneCtr pc = {0u, 0u, 0u};
   auto write_out = [&]() {  // block-wide, between barriers: the finished run's buffers -> sorted kp keys in its first quad's partial slots
     if (run_first == 0xFFFFFFFFu) return;
     for (uint32_t qi = (uint32_t)wid; qi < prev_nq; qi += kPreWavesG) {  // a wave per query
@@ -689,7 +786,12 @@ __global__ __launch_bounds__(kWave * kPreWavesG) __attribute__((amdgpu_waves_per
     // holds <= 16 queries, so that all threads load) and its row pointer is resolved here, ahead of the barrier.
     const uint32_t ns = (NQ > 32 && v.nq > 32u) ? 64u : ((NQ > 16 && (BF || v.nq > 16)) ? 32u : 16u);
     const uint32_t slot = threadIdx.x & (ns - 1u), cg0 = threadIdx.x / ns, cg_step = (kWave * kPreWavesG) / ns;
-    const float* qrow = (!cont && slot < v.nq) ? src.query_row(it, slot) : nullptr;
+    const uint32_t qix = (!cont && slot < v.nq) ? src.query_index(it, slot) : 0xFFFFFFFFu;
+    const float* qrow = qix != 0xFFFFFFFFu ? src.qp + (uint64_t)qix * src.ldq : nullptr;
+    // the slot's row of the early-abandon table ([b][ld / 64])
+    constexpr bool PRUNE = PR;
+    const uint32_t pt_n = p.ld / 64u;
+    const float* ptrow = (PRUNE && p.prune_tab != nullptr && qrow != nullptr) ? p.prune_tab + (uint64_t)qix * pt_n : nullptr;
     auto stage = [&]() {
       const unsigned long long ts0 = (p.debug & 16u) ? __builtin_amdgcn_s_memtime() : 0ull;
       // the first kStageU loads of every thread go out BEFORE the barriers (they fly while the slowest wave of the
@@ -703,6 +805,18 @@ __global__ __launch_bounds__(kWave * kPreWavesG) __attribute__((amdgpu_waves_per
         const uint32_t cg = cg0 + (uint32_t)u * cg_step;
         x[u] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
         if (qrow != nullptr && cg < n_cg) x[u] = *reinterpret_cast<const f32x4*>(qrow + 4 * cg);
+      }
+      // ... and so do the slot's entries of the early-abandon table: thread (slot, cg0) takes boundaries cg0, cg0 + cg_step, ... (two
+      // rounds cover 16 boundaries of a 64-query block -- d <= 1024 --; more of them are loaded behind the barriers)
+      constexpr int kTabU = 2;
+      float pt[kTabU];
+      if constexpr (PRUNE) {
+#pragma unroll
+        for (int u = 0; u < kTabU; ++u) {
+          const uint32_t c = cg0 + (uint32_t)u * cg_step;
+          pt[u] = __builtin_inff();  // (an empty slot never lets a tile go)
+          if (ptrow != nullptr && c < pt_n) pt[u] = ptrow[c];
+        }
       }
       __syncthreads();  // every wave is done with the previous quad: its lists are final
       const unsigned long long ts1 = (p.debug & 16u) ? __builtin_amdgcn_s_memtime() : 0ull;
@@ -742,6 +856,17 @@ __global__ __launch_bounds__(kWave * kPreWavesG) __attribute__((amdgpu_waves_per
         if (qrow != nullptr) y = *reinterpret_cast<const f32x4*>(qrow + 4 * cg);
         put(cg, qscale * y);
       }
+      if constexpr (PRUNE) {
+        if (p.prune_tab != nullptr) {  // (block-uniform)
+          float* const tb = reinterpret_cast<float*>(ctl + 6 * kPreCtl);  // [slot][ld / 64]
+#pragma unroll
+          for (int u = 0; u < kTabU; ++u) {
+            const uint32_t c = cg0 + (uint32_t)u * cg_step;
+            if (c < pt_n) tb[slot * pt_n + c] = pt[u];
+          }
+          for (uint32_t c = cg0 + kTabU * cg_step; c < pt_n; c += cg_step) tb[slot * pt_n + c] = ptrow != nullptr ? ptrow[c] : __builtin_inff();
+        }
+      }
       __syncthreads();
       if ((p.debug & 16u) && lane == 0) {
         atomicAdd(p.stamps + 3, __builtin_amdgcn_s_memtime() - ts1);
@@ -750,10 +875,10 @@ __global__ __launch_bounds__(kWave * kPreWavesG) __attribute__((amdgpu_waves_per
       }
     };
     if (cont) {  // same query block, same buffers: nothing to stage, nothing to wait for
-      prescan_item_g<BF, NQ, LO, WIDE>(src, p, it, v, wid >> 2, lane, qlds, buf, ctl, [] {});
+      prescan_item_g<BF, NQ, LO, WIDE, PR>(src, p, it, v, wid >> 2, lane, qlds, buf, ctl, pc, [] {});
       run_last = bi;
     } else {
-      prescan_item_g<BF, NQ, LO, WIDE>(src, p, it, v, wid >> 2, lane, qlds, buf, ctl, stage);
+      prescan_item_g<BF, NQ, LO, WIDE, PR>(src, p, it, v, wid >> 2, lane, qlds, buf, ctl, pc, stage);
       run_first = run_last = bi;
       cur_list = d0.list; cur_group = d0.group;
       prev_nq = v.nq;
@@ -762,6 +887,21 @@ __global__ __launch_bounds__(kWave * kPreWavesG) __attribute__((amdgpu_waves_per
   }
   __syncthreads();
   write_out();
+  if (PR && p.prune_tab != nullptr) {  // the waves' step counters: summed in the hand-out words, three atomics per counter set and block
+    __syncthreads();
+    if (threadIdx.x < 3) nq_lds[1 + threadIdx.x] = 0u;
+    __syncthreads();
+    if (lane == 0) {
+      atomicAdd(nq_lds + 1, pc.exec);
+      atomicAdd(nq_lds + 2, pc.skipped);
+      atomicAdd(nq_lds + 3, pc.tiles);
+    }
+    __syncthreads();
+    if (threadIdx.x < 3 && nq_lds[1 + threadIdx.x] != 0u) {
+      atomicAdd(p.prune_last + threadIdx.x, nq_lds[1 + threadIdx.x]);
+      atomicAdd(p.prune_tot + threadIdx.x, (unsigned long long)nq_lds[1 + threadIdx.x]);
+    }
+  }
   if ((p.debug & 16u) && blockIdx.x == 0 && threadIdx.x == 0)
     p.stamps[7] = ((__builtin_amdgcn_s_memtime() - clk0) << 20) / ((__builtin_amdgcn_s_memrealtime() - rt0) | 1ull);
 }
@@ -821,6 +961,74 @@ __host__ __device__ inline PreBound pre_bound(double qn, double xmax2, double R2
   b.offset = qnU;
   if (b.common > b.global) b.common = b.global;  // (never looser than the bound it replaces)
   return b;
+}
+
+// ---- abandoning a tile early (squared L2, fp16 shadow, hi-only query blocks): what its unread columns can still bring ----------------
+// After the columns P = [0, c) of a tile a wave holds acc_P[row][n] = <x~_P, q'_P> as the matrix cores summed it; S = [c, ld) is unread.
+// With h = -q' / 2 (exact), sum_S (x~_j - h_j)^2 >= 0 gives <x~_S, q'_S> >= -|x~_S|^2 - |h_S|^2; |x~_S|^2 = |x~|^2 - |x~_P|^2; and the
+// stored |x|^2 (xn, an ordered f32 sum over the f32 row) is at least |x~|^2 - rho, rho = (2 xmax + R) R + (d + 1) u xmax^2 (R = the
+// measured shadow residual, |x|^2 - |x~|^2 = <x - x~, x + x~>).  So the val the kernel would complete for the row -- acc_P, the suffix's
+// products accumulated on top, + xn -- is at least
+//     acc_P + |x~_P|^2 - |h_S|^2 - rho - common
+// (`common` of pre_bound covers the accumulation's roundings, the xn k-step and more).  A tile is left when this, with the row terms
+// replaced by their minima over the tile (acc_min, m_p <= every row's |x~_P|^2 as the kernel sums it: (1 - eps) takes its roundings,
+// eps = (d + 2) u), exceeds the threshold of EVERY live query column: fold would have dropped every val.  The per-query part
+//     tail(c) = |h_S|^2 (1 + eps) + rho + common + 16 u S      (S = |q|^2 + max |x|^2: the three f32 roundings of prune_lower itself)
+// is tabulated per batch (prune_table_kernel), rounded UP to f32.  A NaN in the table, the threshold, the norm or |x|^2 makes the comparison false -> the tile is read.
+__host__ __device__ inline float prune_round_up(double x) {  // the smallest f32 >= x (x > 0; NaN / inf pass through)
+  float f = (float)x;
+  if ((double)f < x) {
+    uint32_t bits = __builtin_bit_cast(uint32_t, f);
+    f = __builtin_bit_cast(float, bits + 1u);
+  }
+  return f;
+}
+__host__ __device__ inline double prune_eps(uint32_t d_pad) { return ((double)d_pad + 2.0) * 5.9604644775390625e-08; }
+__host__ __device__ inline double prune_rho(double xmax2, double R2, uint32_t d_pad) {
+  const double xm = __builtin_sqrt(xmax2), R = __builtin_sqrt(R2 * 1.01);  // (R2: an f32 sum, inflated for its roundings as in pre_bound)
+  return 1.01 * ((2.0 * xm + R) * R + ((double)d_pad + 1.0) * 5.9604644775390625e-08 * xmax2);
+}
+// hS2 = |h_S|^2 as summed in f32 (any order), qn = |q|^2 likewise, Rq2 = the staged query's squared fp16 residual (pre_bound)
+__host__ __device__ inline float prune_tail_entry(double hS2, double qn, double xmax2, double R2, double Rq2, uint32_t d_pad) {
+  const PreBound pb = pre_bound(qn, xmax2, R2, d_pad, 0, 2, Rq2);
+  const double S = pb.offset + xmax2;
+  return prune_round_up(hS2 * (1.0 + prune_eps(d_pad)) + prune_rho(xmax2, R2, d_pad) + pb.common + 16.0 * 5.9604644775390625e-08 * S);
+}
+__host__ __device__ inline float prune_lower(float acc_min, float m_p, float om_eps, float tail) { return (acc_min + m_p * om_eps) - tail; }
+// --------------------------------------------------------------------------------------------------------------------------------------
+
+// The table of a batch: a wave per query.  tab[q][c], c = 1 .. ld / 64 - 1 (entry 0 is never read): prune_tail_entry of the columns
+// from 64 c on.  h_j = -fp16(-2 q_j) / 2 exactly as stage() rounds the operand.  At most 128 steps (d <= 8192).
+constexpr uint32_t kPruneMaxSteps = 128;
+static __global__ __launch_bounds__(256) void prune_table_kernel(const float* qp, uint32_t ldq, uint32_t ld, uint32_t b, const uint32_t* misc, float* tab) {
+  const uint32_t q = blockIdx.x * 4u + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  if (q >= b) return;  // (whole waves)
+  const float* qrow = qp + (uint64_t)q * ldq;
+  const uint32_t nch = ld / 64u;
+  float qn = 0.0f, rq = 0.0f, mine0 = 0.0f, mine1 = 0.0f;
+  for (uint32_t s = 0; s < nch; ++s) {
+    const float v = qrow[s * 64u + (uint32_t)lane];
+    const float y = -2.0f * v, hi = (float)(_Float16)y, dl = y - hi, h = -0.5f * hi;
+    qn = __fadd_rn(qn, __fmul_rn(v, v));
+    rq = __fadd_rn(rq, __fmul_rn(dl, dl));
+    float t = __fmul_rn(h, h);
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) t = __fadd_rn(t, __shfl_xor(t, off, kWave));
+    if (s == (uint32_t)lane) mine0 = t;
+    if (s == (uint32_t)lane + 64u) mine1 = t;
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) { qn += __shfl_xor(qn, off, kWave); rq += __shfl_xor(rq, off, kWave); }
+  double suf0 = 0.0, suf1 = 0.0;  // the lane's boundaries: c = lane and c = lane + 64
+  for (uint32_t s = 0; s < nch; ++s) {
+    const float t = s < 64u ? __shfl(mine0, (int)s, kWave) : __shfl(mine1, (int)(s - 64u), kWave);
+    if (s >= (uint32_t)lane) suf0 += (double)t;
+    if (s >= (uint32_t)lane + 64u) suf1 += (double)t;
+  }
+  const double xmax2 = (double)__uint_as_float(misc[0]), R2 = (double)__uint_as_float(misc[2]);
+  if ((uint32_t)lane < nch) tab[(uint64_t)q * nch + lane] = prune_tail_entry(suf0, (double)qn, xmax2, R2, (double)rq, ld);
+  if ((uint32_t)lane + 64u < nch) tab[(uint64_t)q * nch + lane + 64u] = prune_tail_entry(suf1, (double)qn, xmax2, R2, (double)rq, ld);
 }
 
 }  // namespace vers

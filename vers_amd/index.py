@@ -256,6 +256,14 @@ class IVFFlatIndex:
         check(lib().vers_ivf_prescan_stats(self._h, C.byref(a), C.byref(b)))
         return dict(batches=a.value, fallback_queries=b.value)
 
+    def prune_stats(self):
+        """Early abandon of the batched list scan (option "pre_prune"): 64-column steps executed, steps of abandoned tiles that ran
+        no math and tiles abandoned -- of the last matrix-core scan and over the handle's life."""
+        last = (C.c_uint64 * 3)(); tot = (C.c_uint64 * 3)()
+        check(lib().vers_ivf_prune_stats(self._h, last, tot))
+        keys = ("steps_executed", "steps_skipped", "tiles_abandoned")
+        return dict(last=dict(zip(keys, (int(v) for v in last))), total=dict(zip(keys, (int(v) for v in tot))))
+
     def last_finish_ms(self):
         ms = C.c_float(0)
         check(lib().vers_ivf_last_finish_ms(self._h, C.byref(ms)))
