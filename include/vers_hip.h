@@ -426,9 +426,45 @@ int32_t vers_ivf_range_search_dev(vers_ivf_t* h, const float* queries_dev, uint6
                                   uint32_t nprobe, uint32_t flags, uint64_t* out_lims_dev, uint64_t* out_ids_dev, float* out_dist_dev,
                                   uint64_t cap, uint64_t* out_total /* host */, void* stream);
 /* The range calls of this process by PHASE (HIP events on the call's stream, ms).  out[8]: [0] calls, [1] queries, [2] results, [3] staging +
- * coarse quantiser + plan, [4] count pass, [5] prefix scan + read-back of the total, [6] fill pass, [7] sort + decode (0 in walk order).
- * Calls that end in an error are not counted.  reset != 0 zeroes them. */
+ * coarse quantiser + plan (the exhaustive calls below: the query staging alone), [4] count pass, [5] prefix scan + read-back of the total,
+ * [6] fill pass, [7] sort + decode (0 in walk order).  Calls that end in an error are not counted.  reset != 0 zeroes them. */
 int32_t vers_range_phases(double* out8, int32_t reset);
+/* EXHAUSTIVE range search: the ground truth beside vers_ivf_range_search, as vers_flat_search / vers_ivf_search_exhaustive are beside the
+ * approximate top-k search.  For query q: EVERY row whose distance D(q, row) -- `metric` as in vers_flat_search / vers_ivf_search_exhaustive,
+ * the reference's bits: sequential f32, multiply and add rounded separately -- is <= radius[q], a plain f32 comparison (squared L2: a
+ * negative radius selects nothing; +inf every row).
+ *   rows     : flat handle: every uploaded row.  IVF handle: every row that is in a list NOW -- added rows are in, removed rows are out,
+ *              storage slack is never a result.
+ *   layout   : CSR, exactly as vers_ivf_range_search: out_lims[0] = 0, out_lims[b] = *out_total, query q owns [out_lims[q], out_lims[q+1]).
+ *   order    : default = ascending (distance, vec id), utils::search_exhaustive's stable order (utils.rs:68-82, ties to the lower index):
+ *              EXACTLY the leading entries with distance <= radius[q] of vers_flat_search / vers_ivf_search_exhaustive with top_k = all
+ *              rows -- ids, order and distance bits.  flags & VERS_RANGE_WALK_ORDER: storage order, unsorted -- flat: ascending vec id;
+ *              IVF: ascending cluster, then position in the list = vers_ivf_get_list(0), (1), ... concatenated and filtered by the
+ *              radius.  A stable sort of the flat walk order by distance gives the default order.
+ *   protocol : as vers_ivf_range_search -- synchronous; *out_total always the full count; *out_total > cap: VERS_OK, out_lims complete,
+ *              out_ids / out_dist UNTOUCHED; cap == 0 with NULL arrays is the size query; b == 0: *out_total = 0.
+ *   handle   : flat: under the handle's mutex, like vers_flat_search.  IVF: the way searches take it -- shared, a leased workspace --
+ *              excluded by add / remove / compact.  _dev: every pointer but out_total is a device pointer, the work is queued on `stream`
+ *              and the call waits for it.
+ *   errors   : VERS_ERR_NAN a NaN distance on any scanned live row, outputs untouched; VERS_ERR_INVALID a NaN radius, unknown flag bits,
+ *              metric > VERS_METRIC_COSDIST, more than 2^32 - 1 results or 2^32 - 1 (query, row segment) slots in one call (split the
+ *              batch), IVF only: a handle sharded by cluster (world > 1), for vers_ivf_range_search's reason; VERS_ERR_HIP scratch for
+ *              the result staging did not fit, outputs untouched.
+ *   NOT an error, total 0 and every limit 0 (what the exhaustive top-k search makes of it): an empty flat corpus, an IVF handle without
+ *              centroids or with a streamed upload in progress.
+ * vers_range_phases counts these calls too; its slot [3] is then the query staging alone (there is no coarse quantiser and no plan). */
+int32_t vers_flat_range_search(vers_flat_t* h, const float* queries, uint64_t q_stride_bytes, uint32_t b, const float* radius /* [b] */,
+                               uint32_t metric, uint32_t flags, uint64_t* out_lims /* [b+1] */, uint64_t* out_ids, float* out_dist,
+                               uint64_t cap, uint64_t* out_total);
+int32_t vers_flat_range_search_dev(vers_flat_t* h, const float* queries_dev, uint64_t ldq_floats, uint32_t b, const float* radius_dev,
+                                   uint32_t metric, uint32_t flags, uint64_t* out_lims_dev, uint64_t* out_ids_dev, float* out_dist_dev,
+                                   uint64_t cap, uint64_t* out_total /* host */, void* stream);
+int32_t vers_ivf_range_search_exhaustive(vers_ivf_t* h, const float* queries, uint64_t q_stride_bytes, uint32_t b, const float* radius /* [b] */,
+                                         uint32_t metric, uint32_t flags, uint64_t* out_lims /* [b+1] */, uint64_t* out_ids, float* out_dist,
+                                         uint64_t cap, uint64_t* out_total);
+int32_t vers_ivf_range_search_exhaustive_dev(vers_ivf_t* h, const float* queries_dev, uint64_t ldq_floats, uint32_t b, const float* radius_dev,
+                                             uint32_t metric, uint32_t flags, uint64_t* out_lims_dev, uint64_t* out_ids_dev,
+                                             float* out_dist_dev, uint64_t cap, uint64_t* out_total /* host */, void* stream);
 /* Process-wide switches: every one is a named option set here (or, for a process one does not control from inside, through the ONE
  * environment variable VERS_OPTIONS="name=value,name=value", read once; besides it the library reads only VERS_SHADOW and
  * VERS_ROWMAJOR, the two memory switches of INTEGRATION.md = options "shadow" / "rowmajor", and VERS_PRE_PRUNE = option "pre_prune").  Unknown name: VERS_ERR_INVALID.
@@ -470,7 +506,9 @@ int32_t vers_range_phases(double* out8, int32_t reset);
  *                       per lane wide; 0 = the ordered chains, 64 ranks per pass.
  *   "coarse1" (1), "scan1t" (1), "ref_as_nprobe1" (1), "assign_tiles" (1), "assign_tiles_min" (64), "seg_rows" (0), "pre_slack" (0),
  *   "upload_stage_mb" (256), "add_batch_rows" (131072), "remove_batch_ids" (1048576), "compact_fused" (1)   kernel-choice and sizing knobs of
- *                       DESIGN.md section 5.
+ *                       DESIGN.md section 5.  "seg_rows", when non-zero, also fixes the row-segment length of the two exhaustive range
+ *                       scans (vers_flat_range_search, vers_ivf_range_search_exhaustive), rounded up to 64 and capped at what one buffer
+ *                       descriptor addresses; vers_flat_search and vers_ivf_search_exhaustive keep their own sizing.
  *   "scan_debug" (0), "poison_alloc" (-1), "poison_slack_bits" (-1), "test_fail_sharded" (0)   diagnosis: phase stamps / skipped
  *                       phases, new device buffers filled with a byte, slack rows filled with an f32 bit pattern, the next n sharded
  *                       searches fail locally. */

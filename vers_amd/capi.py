@@ -110,6 +110,14 @@ SIGNATURES = {
     "vers_ivf_range_search_dev": (C.c_int32, [_vp, _vp, C.c_uint64, C.c_uint32, _vp, C.c_uint32, C.c_uint32, _vp, _vp, _vp, C.c_uint64,
                                               C.POINTER(C.c_uint64), _vp]),
     "vers_range_phases": (C.c_int32, [C.POINTER(C.c_double), C.c_int32]),
+    "vers_flat_range_search": (C.c_int32, [_vp, _vp, C.c_uint64, C.c_uint32, _vp, C.c_uint32, C.c_uint32, _vp, _vp, _vp, C.c_uint64,
+                                           C.POINTER(C.c_uint64)]),
+    "vers_flat_range_search_dev": (C.c_int32, [_vp, _vp, C.c_uint64, C.c_uint32, _vp, C.c_uint32, C.c_uint32, _vp, _vp, _vp, C.c_uint64,
+                                               C.POINTER(C.c_uint64), _vp]),
+    "vers_ivf_range_search_exhaustive": (C.c_int32, [_vp, _vp, C.c_uint64, C.c_uint32, _vp, C.c_uint32, C.c_uint32, _vp, _vp, _vp, C.c_uint64,
+                                                     C.POINTER(C.c_uint64)]),
+    "vers_ivf_range_search_exhaustive_dev": (C.c_int32, [_vp, _vp, C.c_uint64, C.c_uint32, _vp, C.c_uint32, C.c_uint32, _vp, _vp, _vp, C.c_uint64,
+                                                         C.POINTER(C.c_uint64), _vp]),
     "vers_kmeans_update": (C.c_int32, [C.c_int32, _vp, C.c_uint64, C.c_uint64, _vp, C.c_uint64, C.c_uint32, _vp]),
     "vers_kmeans_cost": (C.c_int32, [C.c_int32, _vp, C.c_uint64, C.c_uint64, _vp, C.c_uint64, C.c_uint64, _vp, C.c_uint32,
                                      C.POINTER(C.c_float)]),
@@ -175,6 +183,13 @@ def _ptr(a):
     return a.ctypes.data_as(_vp)
 
 
+def range_radii(radius, b: int) -> np.ndarray:
+    """a scalar or one value per query -> f32 [b]"""
+    if np.ndim(radius):
+        return np.ascontiguousarray(np.broadcast_to(np.asarray(radius, dtype=np.float32).reshape(-1), (b,)))
+    return np.full(b, radius, dtype=np.float32)
+
+
 class FlatCorpus:
     """Brute-force scan over rows in HBM -- utils::search_exhaustive (utils.rs:68-82)."""
 
@@ -222,6 +237,38 @@ class FlatCorpus:
 
     def poll(self, stream: int = 0):
         check(lib().vers_flat_poll(self._h, _vp(stream)))
+
+    def range_search(self, queries: np.ndarray, radius, metric: int = METRIC_L2SQ, walk_order: bool = False):
+        """Every uploaded row with distance <= radius (vers_flat_range_search).  radius: a scalar or one value per query.
+        -> (lims [b + 1] u64, ids u64, dist f32), CSR: query q owns [lims[q], lims[q + 1]).  Default order: ascending (distance, vec id) =
+        the head of search(top_k = all rows); walk_order: ascending vec id.  The first call offers the previous call's total as capacity
+        (0 the first time: a size query); a second call follows when that was too small."""
+        q = np.ascontiguousarray(np.atleast_2d(queries), dtype=np.float32)
+        b = q.shape[0]
+        r = range_radii(radius, b)
+        flags = RANGE_WALK_ORDER if walk_order else 0
+        lims = np.zeros(b + 1, dtype=np.uint64)
+        cap = int(getattr(self, "_range_cap", 0))
+        total = C.c_uint64(0)
+        while True:
+            ids = np.zeros(cap, dtype=np.uint64); dist = np.zeros(cap, dtype=np.float32)
+            check(lib().vers_flat_range_search(self._h, _ptr(q), 4 * q.shape[1], b, _ptr(r), metric, flags, _ptr(lims), _ptr(ids) if cap else None,
+                                               _ptr(dist) if cap else None, cap, C.byref(total)))
+            if total.value <= cap:
+                break
+            cap = int(total.value)
+        self._range_cap = int(total.value)
+        return lims, ids[:total.value], dist[:total.value]
+
+    def range_search_dev(self, q_ptr: int, ldq: int, b: int, radius_ptr: int, metric: int, flags: int, lims_ptr: int, ids_ptr: int,
+                         dist_ptr: int, cap: int, stream: int = 0) -> int:
+        """vers_flat_range_search_dev on raw device pointers; synchronous.  Returns the total: ids / distances were written only when it
+        is <= cap."""
+        total = C.c_uint64(0)
+        check(lib().vers_flat_range_search_dev(self._h, _vp(q_ptr), ldq, b, _vp(radius_ptr), metric, flags, _vp(lims_ptr),
+                                               _vp(ids_ptr) if ids_ptr else None, _vp(dist_ptr) if dist_ptr else None, cap, C.byref(total),
+                                               _vp(stream)))
+        return int(total.value)
 
     def last_scan_ms(self) -> float:
         ms = C.c_float(0)

@@ -1,11 +1,16 @@
 // flat.hip -- brute-force scan behind vers_flat_* (replaces utils::search_exhaustive,
 // /root/reference/vers/src/utils.rs:68-82).
 #include <algorithm>
+#include <cstring>
 #include <mutex>
+#include <string>
+#include <type_traits>
 #include <new>
 #include <vector>
 
 #include "flat_handle.hpp"
+#include "kmeans.hpp"
+#include "range.hip.h"
 #include "scan.hip.h"
 #include "util.hip.h"
 
@@ -45,6 +50,11 @@ struct FlatSrc {
     return partials + ((uint64_t)(qg * QG + qi) * n_segs + seg) * k;
   }
   __device__ __forceinline__ uint32_t bound_slot(uint32_t it, int qi) const { return (it / n_segs_pad) * QG + qi; }
+  // range walk (range.hip.h): vec id = row number, every row below n is live
+  static constexpr int kRangeRows = kRangeRowsFlat;
+  __device__ __forceinline__ uint32_t range_query(uint32_t it, int qi) const { return (it / n_segs_pad) * QG + qi; }
+  __device__ __forceinline__ uint64_t range_slot(uint32_t it, int qi) const { return (uint64_t)range_query(it, qi) * n_segs + it % n_segs_pad; }
+  __device__ __forceinline__ uint32_t storage_row(uint32_t it) const { return (it % n_segs_pad) * seg_rows; }
 };
 
 // one block per query: the k smallest keys of its n_segs partial slots -> (id, dist) at ranks rank0 .. rank0 + k - 1 of output
@@ -179,6 +189,136 @@ int32_t flat_search_dev_locked(vers_flat* h, const float* q_dev, uint64_t ldq, u
   return VERS_OK;
 }
 
+// ---- range search (range.hip.h): every uploaded row within the radius ---------------------------------------------------------------
+template <int QG, int METRIC, bool FILL>
+int32_t launch_flat_range(vers_flat* h, const FlatSrc<QG, false>& src, uint32_t n_items, const RangeParams& p, hipStream_t st) {
+  const size_t lds = scan_lds_bytes(QG, h->ld);
+  if (int32_t rc = scan_prepare_launch(range_scan_kernel<QG, METRIC, FILL, FlatSrc<QG, false>>, lds)) return rc;
+  const uint32_t max_blocks = (uint32_t)h->n_cu * scan_blocks_per_cu(QG, h->ld);
+  uint32_t blocks = (n_items + kWavesPerBlock - 1) / kWavesPerBlock;
+  if (blocks > max_blocks) blocks = max_blocks;
+  if (blocks == 0) blocks = 1;
+  hipLaunchKernelGGL((range_scan_kernel<QG, METRIC, FILL, FlatSrc<QG, false>>), dim3(blocks), dim3(kWave * kWavesPerBlock), lds, st, src, p);
+  VERS_HIP_TRY(hipGetLastError());
+  return VERS_OK;
+}
+
+// Range search of b >= 1 queries on `st`: stage, count launch, prefix scan, limits, ONE synchronisation for total / status / NaN radius, fill,
+// sort, decode, synchronisation.  The caller holds the handle's mutex.  own_out: ids / distances go to o_ids / o_dist, sized by the total
+// (the host-pointer call copies them out), else to ids_dev / dist_dev -- when total <= cap.  An empty corpus walks one empty item per query
+// group: total 0, every limit 0, the radii still checked.
+int32_t flat_range_dev_locked(vers_flat* h, const float* q_dev, uint64_t ldq, uint32_t b, const float* radius_dev, uint32_t metric, uint32_t flags,
+                              uint64_t* lims_dev, uint64_t* ids_dev, float* dist_dev, uint64_t cap, bool own_out, uint64_t* out_total, hipStream_t st) {
+  for (auto& e : h->rg_ev)
+    if (!e) VERS_HIP_TRY(hipEventCreate(&e));
+  VERS_HIP_TRY(hipEventRecord(h->rg_ev[0], st));
+  const int QG = b == 1 ? 1 : 8;
+  const uint32_t n_qg = (b + QG - 1) / QG;
+  if (int32_t rc = grow(h->rg_q, h->rg_q_cap, (size_t)n_qg * h->ld * QG)) return rc;
+  if (int32_t rc = launch_stage_queries(q_dev, ldq, h->d, h->rg_q, h->ld, b, (uint32_t)QG, st)) return rc;
+  // segments as vers_flat_search sizes them (one item per resident wave when possible), or as option "seg_rows" fixes them
+  const uint32_t target_items = (uint32_t)h->n_cu * scan_blocks_per_cu(QG, h->ld) * kWavesPerBlock;
+  const uint64_t per = (h->n * n_qg + target_items - 1) / target_items;
+  const int64_t fixed = opt_get("seg_rows", 0);
+  const uint32_t seg_rows = (uint32_t)std::min<uint64_t>(round_up64(fixed > 0 ? (uint64_t)fixed : (per ? per : 1), kWave), max_seg_rows(h->ld));
+  uint32_t n_segs = (uint32_t)((h->n + seg_rows - 1) / seg_rows);
+  if (n_segs == 0) n_segs = 1;
+  const uint32_t n_segs_pad = QG == 1 ? n_segs : round_up(n_segs, 4);
+  const uint64_t n_slots = (uint64_t)b * n_segs;
+  if (n_slots >= 0xFFFFFFFFull || (uint64_t)n_segs_pad * n_qg >= 0xFFFFFFFFull)
+    return fail(VERS_ERR_INVALID, "vers_flat_range_search: batch too large (query x segment slots); split the batch");
+  const uint32_t n_items = n_segs_pad * n_qg;
+  const size_t scan_tmp = range_scan_temp_bytes((size_t)n_slots + 1);
+  if (int32_t rc = grow(h->rg_counts, h->rg_counts_cap, (size_t)n_slots + 1)) return rc;
+  if (int32_t rc = grow(h->rg_base, h->rg_base_cap, (size_t)n_slots + 1)) return rc;
+  if (int32_t rc = grow(h->rg_misc, h->rg_misc_cap, (size_t)4)) return rc;
+  if (int32_t rc = grow(h->rg_tmp, h->rg_tmp_cap, scan_tmp)) return rc;
+  uint32_t* status = h->status_dev + 1;  // (word 0 belongs to the top-k calls and vers_flat_poll)
+  VERS_HIP_TRY(hipMemsetAsync(h->rg_counts, 0, ((size_t)n_slots + 1) * sizeof(uint32_t), st));  // (+ one zero count: the prefix's last entry is the total)
+  VERS_HIP_TRY(hipMemsetAsync(h->rg_misc, 0, 16, st));
+  VERS_HIP_TRY(hipMemsetAsync(status, 0, sizeof(uint32_t), st));
+  RangeParams rp;
+  rp.ld = h->ld; rp.n_chunks = h->ld / kChunk; rp.status = status; rp.radius = radius_dev; rp.counts = h->rg_counts; rp.base = h->rg_base;
+  rp.row_ids = nullptr; rp.out_keys = nullptr; rp.out_ids = nullptr; rp.out_dist = nullptr; rp.next_quad = nullptr;
+  auto pass = [&](auto fill_tag) -> int32_t {
+    constexpr bool FILL = decltype(fill_tag)::value;
+    auto fill = [&](auto& src) {
+      src.rows = h->rows; src.n = h->n; src.ld = h->ld; src.seg_rows = seg_rows; src.n_segs = n_segs; src.n_segs_pad = n_segs_pad;
+      src.queries = h->rg_q; src.ldq = h->ld; src.b = b; src.partials = nullptr; src.k = 0; src.ids = nullptr;
+    };
+    if (QG == 1) {
+      FlatSrc<1, false> src; fill(src);
+      return metric == VERS_METRIC_L2SQ ? launch_flat_range<1, 0, FILL>(h, src, n_items, rp, st) : launch_flat_range<1, 1, FILL>(h, src, n_items, rp, st);
+    }
+    FlatSrc<8, false> src; fill(src);
+    return metric == VERS_METRIC_L2SQ ? launch_flat_range<8, 0, FILL>(h, src, n_items, rp, st) : launch_flat_range<8, 1, FILL>(h, src, n_items, rp, st);
+  };
+  VERS_HIP_TRY(hipEventRecord(h->rg_ev[1], st));
+  if (int32_t rc = pass(std::false_type{})) return rc;
+  VERS_HIP_TRY(hipEventRecord(h->rg_ev[2], st));
+  if (int32_t rc = range_scan_counts(h->rg_counts, h->rg_base, (size_t)n_slots + 1, h->rg_tmp, scan_tmp, st)) return rc;
+  hipLaunchKernelGGL(range_lims_kernel, dim3((b + 1 + 255) / 256), dim3(256), 0, st, (const uint64_t*)h->rg_base, (uint64_t)n_segs, b, radius_dev,
+                     (const uint32_t*)status, lims_dev, h->rg_misc);
+  VERS_HIP_TRY(hipGetLastError());
+  if (!h->rg_pin) VERS_HIP_TRY(hipHostMalloc((void**)&h->rg_pin, 16, hipHostMallocDefault));  // pinned landing words: total | status | NaN radius
+  VERS_HIP_TRY(hipMemcpyAsync(h->rg_pin, h->rg_misc, 16, hipMemcpyDeviceToHost, st));
+  VERS_HIP_TRY(hipEventRecord(h->rg_ev[3], st));
+  VERS_HIP_TRY(hipStreamSynchronize(st));
+  uint32_t misc[4];
+  std::memcpy(misc, h->rg_pin, sizeof(misc));
+  if (misc[2] & 1u) return fail(VERS_ERR_NAN, "NaN distance (the reference panics in partial_cmp().unwrap())");
+  if (misc[3]) return fail(VERS_ERR_INVALID, "vers_flat_range_search: NaN radius");
+  const uint64_t total = ((uint64_t)misc[1] << 32) | misc[0];
+  if (total > 0xFFFFFFFFull) return fail(VERS_ERR_INVALID, "vers_flat_range_search: more than 2^32 - 1 results in one call; split the batch");
+  *out_total = total;
+  float ms[5] = {};
+  auto phases = [&](int n_ev) {
+    for (int i = 0; i + 1 < n_ev; ++i) (void)hipEventElapsedTime(&ms[i], h->rg_ev[i], h->rg_ev[i + 1]);
+    range_phases_add(b, total, ms);
+  };
+  if (total == 0 || total > cap) { phases(4); return VERS_OK; }  // (too small a buffer: the limits are complete, ids / distances untouched)
+  if (own_out) {
+    if (total > h->o_cap) {
+      size_t c0 = h->o_cap, c1 = h->o_cap, c2 = h->o_cap;
+      if (int32_t rc = grow(h->o_ids, c0, (size_t)total)) return rc;
+      if (int32_t rc = grow(h->o_dist, c1, (size_t)total)) return rc;
+      if (int32_t rc = grow(h->o_cnt, c2, (size_t)total)) return rc;
+      h->o_cap = (size_t)total;
+    }
+    ids_dev = h->o_ids; dist_dev = h->o_dist;
+  }
+  const bool walk = (flags & VERS_RANGE_WALK_ORDER) != 0;
+  size_t sort_tmp = 0;
+  uint64_t *k_in = nullptr, *k_out = nullptr;
+  if (!walk) {  // staging of the sorted order: keys in | keys out (the key's low word is the id), + rocPRIM's temporary
+    sort_tmp = range_sort_keys_temp_bytes((uint32_t)total, b);
+    if (int32_t rc = grow(h->rg_stage, h->rg_stage_cap, 2 * (size_t)total)) return rc;
+    if (int32_t rc = grow(h->rg_tmp, h->rg_tmp_cap, sort_tmp)) return rc;
+    k_in = h->rg_stage; k_out = k_in + total;
+  }
+  rp.out_keys = k_in; rp.out_ids = walk ? ids_dev : nullptr; rp.out_dist = walk ? dist_dev : nullptr;
+  if (int32_t rc = pass(std::true_type{})) return rc;
+  VERS_HIP_TRY(hipEventRecord(h->rg_ev[4], st));
+  if (!walk) {
+    if (int32_t rc = range_sort_segment_keys(k_in, k_out, (uint32_t)total, b, lims_dev, h->rg_tmp, sort_tmp, st)) return rc;
+    hipLaunchKernelGGL(range_decode_ids_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (const uint64_t*)k_out, total, ids_dev, dist_dev);
+    VERS_HIP_TRY(hipGetLastError());
+  }
+  VERS_HIP_TRY(hipEventRecord(h->rg_ev[5], st));
+  VERS_HIP_TRY(hipStreamSynchronize(st));
+  phases(6);
+  return VERS_OK;
+}
+
+// what both range entry points refuse before they touch the device
+int32_t range_check(vers_flat* h, const char* who, uint32_t metric, uint32_t flags, const uint64_t* out_total) {
+  if (!h) return fail(VERS_ERR_INVALID, "null handle");
+  if (!out_total) return fail(VERS_ERR_INVALID, std::string(who) + ": out_total is required");
+  if (metric > VERS_METRIC_COSDIST) return fail(VERS_ERR_INVALID, "unknown metric");
+  if (flags & ~VERS_RANGE_WALK_ORDER) return fail(VERS_ERR_INVALID, std::string(who) + ": unknown flag bits");
+  return VERS_OK;
+}
+
 int32_t check_args(vers_flat* h, uint32_t top_k, uint32_t metric) {
   if (!h) return fail(VERS_ERR_INVALID, "null handle");
   if (metric > VERS_METRIC_COSDIST) return fail(VERS_ERR_INVALID, "unknown metric");
@@ -226,6 +366,12 @@ int32_t vers_flat_destroy(vers_flat_t* h) {
     if (p) (void)hipFree(p);
   if (h->ev0) (void)hipEventDestroy(h->ev0);
   if (h->ev1) (void)hipEventDestroy(h->ev1);
+  for (void* p : {(void*)h->rg_q, (void*)h->rg_counts, (void*)h->rg_base, (void*)h->rg_misc, (void*)h->rg_stage, (void*)h->rg_tmp, (void*)h->rg_rad,
+                  (void*)h->rg_lims})
+    if (p) (void)hipFree(p);
+  if (h->rg_pin) (void)hipHostFree(h->rg_pin);
+  for (hipEvent_t e : h->rg_ev)
+    if (e) (void)hipEventDestroy(e);
   delete h;
   return VERS_OK;
 }
@@ -332,6 +478,48 @@ int32_t vers_flat_search(vers_flat_t* h, const float* queries, uint64_t q_stride
       rc = fail(VERS_ERR_HIP, "result download failed");
   } while (0);
   return rc;
+}
+
+int32_t vers_flat_range_search_dev(vers_flat_t* h, const float* queries_dev, uint64_t ldq_floats, uint32_t b, const float* radius_dev, uint32_t metric,
+                                   uint32_t flags, uint64_t* out_lims_dev, uint64_t* out_ids_dev, float* out_dist_dev, uint64_t cap, uint64_t* out_total,
+                                   void* stream) {
+  if (int32_t rc = range_check(h, "vers_flat_range_search_dev", metric, flags, out_total)) return rc;
+  *out_total = 0;
+  if (b && (!queries_dev || ldq_floats < h->d || !radius_dev || !out_lims_dev || (cap && (!out_ids_dev || !out_dist_dev))))
+    return fail(VERS_ERR_INVALID, "vers_flat_range_search_dev: bad arguments");
+  if (b == 0) return VERS_OK;
+  std::lock_guard<std::mutex> lk(h->mu);
+  DeviceGuard g(h->device);
+  return flat_range_dev_locked(h, queries_dev, ldq_floats, b, radius_dev, metric, flags, out_lims_dev, out_ids_dev, out_dist_dev, cap, false, out_total,
+                               (hipStream_t)stream);
+}
+
+int32_t vers_flat_range_search(vers_flat_t* h, const float* queries, uint64_t q_stride_bytes, uint32_t b, const float* radius, uint32_t metric,
+                               uint32_t flags, uint64_t* out_lims, uint64_t* out_ids, float* out_dist, uint64_t cap, uint64_t* out_total) {
+  if (int32_t rc = range_check(h, "vers_flat_range_search", metric, flags, out_total)) return rc;
+  *out_total = 0;
+  if (b && (!queries || q_stride_bytes < (uint64_t)h->d * 4 || q_stride_bytes % 4 || !radius || !out_lims || (cap && (!out_ids || !out_dist))))
+    return fail(VERS_ERR_INVALID, "vers_flat_range_search: bad arguments");
+  if (b == 0) return VERS_OK;
+  for (uint32_t i = 0; i < b; ++i)
+    if (radius[i] != radius[i]) return fail(VERS_ERR_INVALID, "vers_flat_range_search: NaN radius");
+  std::lock_guard<std::mutex> lk(h->mu);
+  DeviceGuard g(h->device);
+  if (int32_t rc = grow(h->q_up, h->q_up_cap, (size_t)b * h->ld)) return rc;
+  if (int32_t rc = grow(h->rg_rad, h->rg_rad_cap, (size_t)b)) return rc;
+  if (int32_t rc = grow(h->rg_lims, h->rg_lims_cap, (size_t)b + 1)) return rc;
+  if (hipMemset(h->q_up, 0, (size_t)b * h->ld * sizeof(float)) != hipSuccess ||
+      hipMemcpy2D(h->q_up, (size_t)h->ld * 4, queries, q_stride_bytes, (size_t)h->d * 4, b, hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy(h->rg_rad, radius, (size_t)b * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)
+    return fail(VERS_ERR_HIP, "query upload failed");
+  uint64_t total = 0;
+  if (int32_t rc = flat_range_dev_locked(h, h->q_up, h->ld, b, h->rg_rad, metric, flags, h->rg_lims, nullptr, nullptr, cap, true, &total, nullptr)) return rc;
+  VERS_HIP_TRY(hipMemcpy(out_lims, h->rg_lims, ((size_t)b + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost));
+  *out_total = total;
+  if (total == 0 || total > cap) return VERS_OK;
+  VERS_HIP_TRY(hipMemcpy(out_ids, h->o_ids, (size_t)total * sizeof(uint64_t), hipMemcpyDeviceToHost));
+  VERS_HIP_TRY(hipMemcpy(out_dist, h->o_dist, (size_t)total * sizeof(float), hipMemcpyDeviceToHost));
+  return VERS_OK;
 }
 
 int32_t vers_flat_last_scan_ms(vers_flat_t* h, float* out_ms) {

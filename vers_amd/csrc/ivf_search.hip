@@ -679,6 +679,13 @@ int32_t host_io_end(vers_ivf* h, const HostIo& io, uint32_t b, uint32_t top_k, u
 constexpr int kRangePhases = 8;
 static std::mutex g_rg_mu;
 static double g_rg[kRangePhases] = {};  // vers_range_phases: calls, queries, results, plan, count, prefix + total, fill, sort + decode (ms)
+}  // namespace ivf
+void range_phases_add(uint32_t b, uint64_t total, const float* ms5) {  // (the flat handle's range calls are counted here too: flat.hip)
+  std::lock_guard<std::mutex> lk(ivf::g_rg_mu);
+  ivf::g_rg[0] += 1.0; ivf::g_rg[1] += (double)b; ivf::g_rg[2] += (double)total;
+  for (int i = 0; i < 5; ++i) ivf::g_rg[3 + i] += (double)ms5[i];
+}
+namespace ivf {
 
 // one pass over the planned items; launch bounds as launch_ivf_scan's
 template <int QG, bool FILL>
@@ -767,9 +774,7 @@ int32_t range_dev_locked(vers_ivf* h, const float* q_dev, uint64_t ldq_in, uint3
   float ms[5] = {};
   auto phases = [&](int n_ev) {
     for (int i = 0; i + 1 < n_ev; ++i) (void)hipEventElapsedTime(&ms[i], W->rg_ev[i], W->rg_ev[i + 1]);
-    std::lock_guard<std::mutex> lk(g_rg_mu);
-    g_rg[0] += 1.0; g_rg[1] += (double)b; g_rg[2] += (double)total;
-    for (int i = 0; i < 5; ++i) g_rg[3 + i] += (double)ms[i];
+    range_phases_add(b, total, ms);
   };
   if (total == 0 || total > cap) { phases(4); return VERS_OK; }  // (too small a buffer: the limits are complete, ids / distances untouched)
   if (own_out) {
@@ -797,6 +802,125 @@ int32_t range_dev_locked(vers_ivf* h, const float* q_dev, uint64_t ldq_in, uint3
   VERS_HIP_TRY(hipEventRecord(W->rg_ev[5], st));
   VERS_HIP_TRY(hipStreamSynchronize(st));
   phases(6);
+  return VERS_OK;
+}
+
+// ---- exhaustive range search: every row that is in a list NOW, over the storage rows (SegSrc<QG, true>: exhaustive_dev_locked's items) ----
+template <int QG, bool FILL>
+int32_t launch_range_seg_scan(vers_ivf* h, const SegSrc<QG, true>& src, uint32_t n_items, int metric, const RangeParams& p, hipStream_t st) {
+  const size_t lds = scan_lds_bytes(QG, h->ld);
+  if (int32_t rc = metric ? scan_prepare_launch(range_scan_kernel<QG, 1, FILL, SegSrc<QG, true>>, lds) : scan_prepare_launch(range_scan_kernel<QG, 0, FILL, SegSrc<QG, true>>, lds)) return rc;
+  uint32_t blocks = (n_items + kWavesPerBlock - 1) / kWavesPerBlock;
+  const uint32_t max_blocks = (uint32_t)h->n_cu * scan_blocks_per_cu(QG, h->ld);
+  if (blocks > max_blocks) blocks = max_blocks;
+  if (blocks == 0) blocks = 1;
+  if (metric) hipLaunchKernelGGL((range_scan_kernel<QG, 1, FILL, SegSrc<QG, true>>), dim3(blocks), dim3(kWave * kWavesPerBlock), lds, st, src, p);
+  else hipLaunchKernelGGL((range_scan_kernel<QG, 0, FILL, SegSrc<QG, true>>), dim3(blocks), dim3(kWave * kWavesPerBlock), lds, st, src, p);
+  VERS_HIP_TRY(hipGetLastError());
+  return VERS_OK;
+}
+
+// As range_dev_locked, without a plan: stage, count launch, scan, sync and total, fill, sort, sync.  The caller holds the index shared, a leased
+// workspace and status word 1.  An index without centroids (a streamed upload in progress included) is scanned as zero rows: total 0, every
+// limit 0, the radii still checked -- what the exhaustive top-k search makes of it.
+int32_t range_exhaustive_dev_locked(vers_ivf* h, const float* q_dev, uint64_t ldq_in, uint32_t b, const float* radius_dev, uint32_t metric, uint32_t flags,
+                                    uint64_t* lims_dev, uint64_t* ids_dev, float* dist_dev, uint64_t cap, bool own_out, uint64_t* out_total, hipStream_t st) {
+  for (auto& e : W->rg_ev)
+    if (!e) VERS_HIP_TRY(hipEventCreate(&e));
+  VERS_HIP_TRY(hipEventRecord(W->rg_ev[0], st));
+  const uint64_t n_rows = (h->k == 0 || h->up.open) ? 0 : h->cap_rows;
+  const int QG = b == 1 ? 1 : 8;
+  const uint32_t n_qg = (b + QG - 1) / QG;
+  if (int32_t rc = W->qil.reserve((size_t)n_qg * h->ldq * QG * sizeof(float))) return rc;
+  if (int32_t rc = launch_stage_queries(q_dev, ldq_in, h->d, W->qil.as<float>(), h->ldq, b, QG, st)) return rc;
+  // segments as exhaustive_dev_locked sizes them, or as option "seg_rows" fixes them
+  const uint32_t target_items = (uint32_t)h->n_cu * scan_blocks_per_cu(QG, h->ld) * kWavesPerBlock;
+  const uint64_t per = (n_rows * n_qg + target_items - 1) / target_items;
+  const long fixed = knobs().seg_rows;
+  const uint32_t seg_rows = (uint32_t)std::min<uint64_t>(round_up64(fixed > 0 ? (uint64_t)fixed : (per ? per : 1), kWave), max_seg_rows(h->ld));
+  uint32_t n_segs = (uint32_t)((n_rows + seg_rows - 1) / seg_rows);
+  if (n_segs == 0) n_segs = 1;
+  const uint32_t n_segs_pad = QG == 1 ? n_segs : round_up(n_segs, 4);
+  const uint64_t n_slots = (uint64_t)b * n_segs;
+  if (n_slots >= 0xFFFFFFFFull || (uint64_t)n_segs_pad * n_qg >= 0xFFFFFFFFull)
+    return fail(VERS_ERR_INVALID, "vers_ivf_range_search_exhaustive: batch too large (query x segment slots); split the batch");
+  const uint32_t n_items = n_segs_pad * n_qg;
+  const size_t scan_tmp = range_scan_temp_bytes((size_t)n_slots + 1);
+  if (int32_t rc = W->rg_counts.reserve(((size_t)n_slots + 1) * sizeof(uint32_t))) return rc;
+  if (int32_t rc = W->rg_base.reserve(((size_t)n_slots + 1) * sizeof(uint64_t))) return rc;
+  if (int32_t rc = W->rg_misc.reserve(16)) return rc;
+  if (int32_t rc = W->rg_tmp.reserve(scan_tmp)) return rc;
+  VERS_HIP_TRY(hipMemsetAsync(W->rg_counts.p, 0, ((size_t)n_slots + 1) * sizeof(uint32_t), st));  // (+ one zero count: the prefix's last entry is the total)
+  VERS_HIP_TRY(hipMemsetAsync(W->rg_misc.p, 0, 16, st));
+  RangeParams rp;
+  rp.ld = h->ld; rp.n_chunks = h->ld / kChunk; rp.status = W->st_word(); rp.radius = radius_dev; rp.counts = W->rg_counts.as<uint32_t>();
+  rp.base = W->rg_base.as<uint64_t>(); rp.row_ids = h->row_ids.as<uint32_t>(); rp.out_keys = nullptr; rp.out_ids = nullptr; rp.out_dist = nullptr; rp.next_quad = nullptr;
+  auto pass = [&](auto fill_tag) -> int32_t {
+    constexpr bool FILL = decltype(fill_tag)::value;
+    auto fill = [&](auto& src) {
+      src.rows = h->rows.as<float>(); src.n = n_rows; src.ld = h->ld; src.seg_rows = seg_rows; src.n_segs = n_segs; src.n_segs_pad = n_segs_pad;
+      src.queries = W->qil.as<float>(); src.ldq = h->ldq; src.b = b; src.partials = nullptr; src.k = 0; src.ids = h->row_ids.as<uint32_t>();
+    };
+    if (QG == 1) { SegSrc<1, true> src; fill(src); return launch_range_seg_scan<1, FILL>(h, src, n_items, (int)metric, rp, st); }
+    SegSrc<8, true> src; fill(src);
+    return launch_range_seg_scan<8, FILL>(h, src, n_items, (int)metric, rp, st);
+  };
+  VERS_HIP_TRY(hipEventRecord(W->rg_ev[1], st));
+  if (int32_t rc = pass(std::false_type{})) return rc;
+  VERS_HIP_TRY(hipEventRecord(W->rg_ev[2], st));
+  if (int32_t rc = range_scan_counts(W->rg_counts.as<uint32_t>(), W->rg_base.as<uint64_t>(), (size_t)n_slots + 1, W->rg_tmp.p, scan_tmp, st)) return rc;
+  hipLaunchKernelGGL(range_lims_kernel, dim3((b + 1 + 255) / 256), dim3(256), 0, st, (const uint64_t*)W->rg_base.as<uint64_t>(), (uint64_t)n_segs, b, radius_dev,
+                     (const uint32_t*)W->st_word(), lims_dev, W->rg_misc.as<uint32_t>());
+  VERS_HIP_TRY(hipGetLastError());
+  if (!W->rg_pin) VERS_HIP_TRY(hipHostMalloc((void**)&W->rg_pin, 16, hipHostMallocDefault));  // pinned landing words: total | status | NaN radius
+  VERS_HIP_TRY(hipMemcpyAsync(W->rg_pin, W->rg_misc.p, 16, hipMemcpyDeviceToHost, st));
+  VERS_HIP_TRY(hipEventRecord(W->rg_ev[3], st));
+  VERS_HIP_TRY(hipStreamSynchronize(st));
+  uint32_t misc[4];
+  std::memcpy(misc, W->rg_pin, sizeof(misc));
+  if (int32_t rc = status_to_rc(h, misc[2], W->st_slot)) return rc == kRetrySpill ? VERS_ERR_INVALID : rc;
+  if (misc[3]) return fail(VERS_ERR_INVALID, "vers_ivf_range_search_exhaustive: NaN radius");
+  const uint64_t total = ((uint64_t)misc[1] << 32) | misc[0];
+  if (total > 0xFFFFFFFFull) return fail(VERS_ERR_INVALID, "vers_ivf_range_search_exhaustive: more than 2^32 - 1 results in one call; split the batch");
+  *out_total = total;
+  float ms[5] = {};
+  auto phases = [&](int n_ev) {
+    for (int i = 0; i + 1 < n_ev; ++i) (void)hipEventElapsedTime(&ms[i], W->rg_ev[i], W->rg_ev[i + 1]);
+    range_phases_add(b, total, ms);
+  };
+  if (total == 0 || total > cap) { phases(4); return VERS_OK; }  // (too small a buffer: the limits are complete, ids / distances untouched)
+  if (own_out) {
+    if (int32_t rc = W->o_ids.reserve((size_t)total * sizeof(uint64_t))) return rc;
+    if (int32_t rc = W->o_dist.reserve((size_t)total * sizeof(float))) return rc;
+    ids_dev = W->o_ids.as<uint64_t>(); dist_dev = W->o_dist.as<float>();
+  }
+  const bool walk = (flags & VERS_RANGE_WALK_ORDER) != 0;
+  size_t sort_tmp = 0;
+  uint64_t *k_in = nullptr, *k_out = nullptr;
+  if (!walk) {  // staging of the sorted order: keys in | keys out (the key's low word is the id), + rocPRIM's temporary
+    sort_tmp = range_sort_keys_temp_bytes((uint32_t)total, b);
+    if (int32_t rc = W->rg_stage.reserve(2 * (size_t)total * sizeof(uint64_t))) return rc;
+    if (int32_t rc = W->rg_tmp.reserve(sort_tmp)) return rc;
+    k_in = W->rg_stage.as<uint64_t>(); k_out = k_in + total;
+  }
+  rp.out_keys = k_in; rp.out_ids = walk ? ids_dev : nullptr; rp.out_dist = walk ? dist_dev : nullptr;
+  if (int32_t rc = pass(std::true_type{})) return rc;
+  VERS_HIP_TRY(hipEventRecord(W->rg_ev[4], st));
+  if (!walk) {
+    if (int32_t rc = range_sort_segment_keys(k_in, k_out, (uint32_t)total, b, lims_dev, W->rg_tmp.p, sort_tmp, st)) return rc;
+    hipLaunchKernelGGL(range_decode_ids_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (const uint64_t*)k_out, total, ids_dev, dist_dev);
+    VERS_HIP_TRY(hipGetLastError());
+  }
+  VERS_HIP_TRY(hipEventRecord(W->rg_ev[5], st));
+  VERS_HIP_TRY(hipStreamSynchronize(st));
+  phases(6);
+  return VERS_OK;
+}
+
+// what both exhaustive entry points refuse before they touch the device
+static int32_t range_exhaustive_check(vers_ivf* h, const char* who, uint32_t flags) {
+  if (flags & ~VERS_RANGE_WALK_ORDER) return fail(VERS_ERR_INVALID, std::string(who) + ": unknown flag bits");
+  if (h->world > 1) return fail(VERS_ERR_INVALID, std::string(who) + ": the handle is sharded by cluster; a sharded range search is not implemented");
   return VERS_OK;
 }
 
@@ -1228,6 +1352,61 @@ int32_t vers_ivf_range_search(vers_ivf_t* h, const float* queries, uint64_t q_st
   uint64_t total = 0;
   if (int32_t rc = range_dev_locked(h, io.q_dev, h->d, b, W->rg_rad.as<float>(), nprobe, flags, W->rg_lims.as<uint64_t>(), nullptr, nullptr, cap, true, &total,
                                     W->io_stream)) return rc;
+  VERS_HIP_TRY(hipMemcpy(out_lims, W->rg_lims.p, ((size_t)b + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost));
+  *out_total = total;
+  if (total == 0 || total > cap) return VERS_OK;
+  VERS_HIP_TRY(hipMemcpy(out_ids, W->o_ids.p, (size_t)total * sizeof(uint64_t), hipMemcpyDeviceToHost));
+  VERS_HIP_TRY(hipMemcpy(out_dist, W->o_dist.p, (size_t)total * sizeof(float), hipMemcpyDeviceToHost));
+  return VERS_OK;
+}
+
+int32_t vers_ivf_range_search_exhaustive_dev(vers_ivf_t* h, const float* queries_dev, uint64_t ldq_floats, uint32_t b, const float* radius_dev,
+                                             uint32_t metric, uint32_t flags, uint64_t* out_lims_dev, uint64_t* out_ids_dev, float* out_dist_dev,
+                                             uint64_t cap, uint64_t* out_total, void* stream) {
+  if (!h) return fail(VERS_ERR_INVALID, "null handle");
+  if (!out_total) return fail(VERS_ERR_INVALID, "vers_ivf_range_search_exhaustive_dev: out_total is required");
+  *out_total = 0;
+  if (metric > VERS_METRIC_COSDIST) return fail(VERS_ERR_INVALID, "unknown metric");
+  if (b && (!queries_dev || ldq_floats < h->d || !radius_dev || !out_lims_dev || (cap && (!out_ids_dev || !out_dist_dev))))
+    return fail(VERS_ERR_INVALID, "vers_ivf_range_search_exhaustive_dev: bad arguments");
+  if (b == 0) return VERS_OK;
+  std::shared_lock<std::shared_mutex> lk(h->index);
+  if (int32_t rc = range_exhaustive_check(h, "vers_ivf_range_search_exhaustive_dev", flags)) return rc;
+  DeviceGuard g(h->device);
+  WsLease lease(h, true, (hipStream_t)stream);
+  if (lease.rc) return lease.rc;
+  if (int32_t rc = lease.order_on((hipStream_t)stream)) return rc;
+  HostStatusSlot slot(h);
+  return range_exhaustive_dev_locked(h, queries_dev, ldq_floats, b, radius_dev, metric, flags, out_lims_dev, out_ids_dev, out_dist_dev, cap, false,
+                                     out_total, (hipStream_t)stream);
+}
+
+int32_t vers_ivf_range_search_exhaustive(vers_ivf_t* h, const float* queries, uint64_t q_stride_bytes, uint32_t b, const float* radius, uint32_t metric,
+                                         uint32_t flags, uint64_t* out_lims, uint64_t* out_ids, float* out_dist, uint64_t cap, uint64_t* out_total) {
+  if (!h) return fail(VERS_ERR_INVALID, "null handle");
+  if (!out_total) return fail(VERS_ERR_INVALID, "vers_ivf_range_search_exhaustive: out_total is required");
+  *out_total = 0;
+  if (metric > VERS_METRIC_COSDIST) return fail(VERS_ERR_INVALID, "unknown metric");
+  if (b && (!queries || q_stride_bytes < (uint64_t)h->d * 4 || q_stride_bytes % 4 || !radius || !out_lims || (cap && (!out_ids || !out_dist))))
+    return fail(VERS_ERR_INVALID, "vers_ivf_range_search_exhaustive: bad arguments");
+  if (b == 0) return VERS_OK;
+  for (uint32_t i = 0; i < b; ++i)
+    if (radius[i] != radius[i]) return fail(VERS_ERR_INVALID, "vers_ivf_range_search_exhaustive: NaN radius");
+  std::shared_lock<std::shared_mutex> lk(h->index);
+  if (int32_t rc = range_exhaustive_check(h, "vers_ivf_range_search_exhaustive", flags)) return rc;
+  DeviceGuard g(h->device);
+  WsLease lease(h);
+  if (lease.rc) return lease.rc;
+  HostStatusSlot slot(h);
+  HostIo io;
+  if (int32_t rc = host_io_begin(h, queries, q_stride_bytes, b, 0, io)) return rc;  // (the pinned query staging of every host-pointer call)
+  lease.st = W->io_stream;
+  if (int32_t rc = W->rg_rad.reserve((size_t)b * sizeof(float))) return rc;
+  if (int32_t rc = W->rg_lims.reserve(((size_t)b + 1) * sizeof(uint64_t))) return rc;
+  VERS_HIP_TRY(hipMemcpyAsync(W->rg_rad.p, radius, (size_t)b * sizeof(float), hipMemcpyHostToDevice, W->io_stream));
+  uint64_t total = 0;
+  if (int32_t rc = range_exhaustive_dev_locked(h, io.q_dev, h->d, b, W->rg_rad.as<float>(), metric, flags, W->rg_lims.as<uint64_t>(), nullptr, nullptr, cap, true,
+                                               &total, W->io_stream)) return rc;
   VERS_HIP_TRY(hipMemcpy(out_lims, W->rg_lims.p, ((size_t)b + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost));
   *out_total = total;
   if (total == 0 || total > cap) return VERS_OK;

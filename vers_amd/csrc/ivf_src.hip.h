@@ -41,6 +41,11 @@ struct SegSrc {
     return partials + ((uint64_t)(qg * QG + qi) * n_segs + seg) * k;
   }
   __device__ __forceinline__ uint32_t bound_slot(uint32_t it, int qi) const { return (it / n_segs_pad) * QG + qi; }
+  // range walk (range.hip.h): storage rows of the index, slack and freed rows among them
+  static constexpr int kRangeRows = kRangeRowsStored;
+  __device__ __forceinline__ uint32_t range_query(uint32_t it, int qi) const { return (it / n_segs_pad) * QG + qi; }
+  __device__ __forceinline__ uint64_t range_slot(uint32_t it, int qi) const { return (uint64_t)range_query(it, qi) * n_segs + it % n_segs_pad; }
+  __device__ __forceinline__ uint32_t storage_row(uint32_t it) const { return (it % n_segs_pad) * seg_rows; }
 };
 
 // inverted-list scan: item = (list, query group of the list, row segment of the list)
@@ -113,6 +118,10 @@ struct IvfSrc {
     return bound_per_pair ? pr : pr / P * P;
   }
   __device__ __forceinline__ uint32_t slot_of_pair(uint32_t pr) const { return bound_per_pair ? pr : pr / P * P; }
+  // range walk (range.hip.h): the rows of a list are all live; slot = pair * S_max + segment
+  static constexpr int kRangeRows = kRangeRowsListed;
+  __device__ __forceinline__ uint32_t range_query(uint32_t it, int qi) const { return pair_of(it, qi) / P; }
+  __device__ __forceinline__ uint64_t range_slot(uint32_t it, int qi) const { return (uint64_t)pair_of(it, qi) * S_max + items[it].seg; }
 };
 
 // Single query (planned by plan1_block): an item is a 16-byte RECORD -- where its rows are, how many, the sequence number of the

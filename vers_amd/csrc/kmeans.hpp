@@ -17,6 +17,9 @@ int32_t range_scan_counts(const uint32_t* counts, uint64_t* base, size_t n, void
 size_t range_sort_temp_bytes(uint32_t n, uint32_t segments);
 int32_t range_sort_segments(const uint64_t* keys_in, uint64_t* keys_out, const uint64_t* ids_in, uint64_t* ids_out, uint32_t n, uint32_t segments,
                             const uint64_t* lims, void* temp, size_t temp_bytes, hipStream_t st);
+size_t range_sort_keys_temp_bytes(uint32_t n, uint32_t segments);  // keys alone
+int32_t range_sort_segment_keys(const uint64_t* keys_in, uint64_t* keys_out, uint32_t n, uint32_t segments, const uint64_t* lims, void* temp,
+                                size_t temp_bytes, hipStream_t st);
 
 // ---- kmeans.hip ---------------------------------------------------------------------
 // Simple owning device buffer (grow-only).

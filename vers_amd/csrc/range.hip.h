@@ -13,8 +13,24 @@
 //
 // The walk is scan_kernel's (scan.hip.h): the same items (IvfSrc<QG>, QG 1 / 8 / 16), quads sharing one LDS query block, the same
 // register prefetch ring over (tile, chunk) steps -- built from TileLoader, tile_chunk_compute and ItemView as they are.
+//
+// + the EXHAUSTIVE range search (vers_flat_range_search, vers_ivf_range_search_exhaustive): the same two passes over the segment items of
+// the exhaustive top-k scans (FlatSrc / SegSrc<QG, true>, QG 1 / 8; slot = q * n_segs + segment, which is query-major too).  One walk
+// serves the three sources; what it asks of a source beyond scan_kernel's contract:
+//   uint32_t range_query(it, qi) const    the batch's query behind slot qi of the item (its radius)
+//   uint64_t range_slot(it, qi) const     the count slot of (item, query); one item per slot, a query's slots contiguous and ascending in walk order
+//   uint32_t storage_row(it) const        the item's first storage row (row_ids index / row number)
+//   static constexpr int kRangeRows       what a row of the item is (the constants: scan.hip.h) --
+//       kRangeRowsListed  a row of an inverted list: live, vec id = row_ids[storage row]; the sort key carries the walk's sequence number
+//                         (ties in probe-rank order) and the ids are staged beside the keys
+//       kRangeRowsStored  a storage row of the index: row_ids[storage row] == 0xFFFFFFFF marks slack and freed rows, which are no result --
+//                         in the count pass and in the fill pass alike, or the positions drift.  The id is loaded only for tiles in which
+//                         some lane is within its radius (or NaN), behind the wave-uniform ballot: no load inside the streaming loop otherwise
+//       kRangeRowsFlat    a row of the flat corpus: vec id = row number, every row below n is live, no id load at all
+//     Stored / Flat: the sort key is make_key(dist, vec id) -- utils::search_exhaustive's stable order -- so the sorted keys alone
+//     decode to (id, distance) and no id array is staged.
 #pragma once
-#include "ivf_src.hip.h"
+#include "scan.hip.h"
 
 #pragma clang fp contract(off)
 
@@ -38,16 +54,17 @@ struct RangeParams {
 template <int QG, int NP, int METRIC, bool FILL, class Src>
 __device__ __forceinline__ void range_item(const Src& src, const RangeParams& p, uint32_t it, const ItemView<QG>& v, int lane, bool& nan_seen) {
   // Per-query constants once, lane qi = query qi, read back with v_readlane (scan_item: no memory load inside the streaming loop).
+  constexpr bool kKeyId = Src::kRangeRows != kRangeRowsListed;  // the sort key's low word is the vec id itself
   const bool live = lane < QG && lane < (int)v.nq;
   uint32_t vrad = 0, vseq = 0, vhits = 0;  // vhits: the query's hits in the item's tiles so far
   uint64_t vslot = 0, vbase = 0;
   if (live) {
-    const uint32_t pr = src.pair_of(it, lane);
-    vrad = __float_as_uint(p.radius[pr / src.P]);
-    vslot = (uint64_t)pr * src.S_max + src.items[it].seg;
-    if (FILL) vseq = src.seq_base(it, lane);
+    vrad = __float_as_uint(p.radius[src.range_query(it, lane)]);
+    vslot = src.range_slot(it, lane);
+    if (FILL && !kKeyId) vseq = src.seq_base(it, lane);
   }
   uint32_t srow0 = 0;
+  if constexpr (!FILL && Src::kRangeRows == kRangeRowsStored) srow0 = src.storage_row(it);
   if constexpr (FILL) {
     const uint32_t had = live ? p.counts[vslot] : 0u;
     if (__ballot(had != 0u) == 0) return;  // nothing to store for any query of the item: not a byte of it is loaded (wave-uniform)
@@ -66,14 +83,28 @@ __device__ __forceinline__ void range_item(const Src& src, const RangeParams& p,
     const uint32_t row = t * kWave + lane;
     const bool valid = row < v.nrows;  // rows of the last tile beyond the segment: slack, never a result
     if constexpr (!FILL) {
+      bool ok = valid;
+      if constexpr (Src::kRangeRows == kRangeRowsStored) {
+        // is the row a vector at all?  Asked only when the answer matters: some lane is within its radius or NaN (wave-uniform)
+        bool ask = false;
+#pragma unroll
+        for (int qi = 0; qi < QG; ++qi)
+          if (qi < 2 * NP && qi < (int)v.nq) {
+            const float a = acc[qi >> 1][qi & 1];
+            const float dist = METRIC == 0 ? a : __fsub_rn(1.0f, a);
+            ask |= valid && !(dist > __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)vrad, qi)));
+          }
+        if (__ballot(ask) != 0) ok = valid && p.row_ids[srow0 + row] != 0xFFFFFFFFu;
+        else ok = false;  // (nothing to count, nothing to report)
+      }
 #pragma unroll
       for (int qi = 0; qi < QG; ++qi) {
         if (qi < 2 * NP && qi < (int)v.nq) {
           const float a = acc[qi >> 1][qi & 1];
           const float dist = METRIC == 0 ? a : __fsub_rn(1.0f, a);
-          nan_seen |= valid && (dist != dist);
+          nan_seen |= ok && (dist != dist);
           const float r = __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)vrad, qi));
-          const uint32_t n = (uint32_t)__popcll(__ballot(valid && dist <= r));
+          const uint32_t n = (uint32_t)__popcll(__ballot(ok && dist <= r));
           if (lane == qi) vhits += n;
         }
         acc[qi >> 1][qi & 1] = 0.0f;
@@ -88,19 +119,23 @@ __device__ __forceinline__ void range_item(const Src& src, const RangeParams& p,
           any |= valid && dist <= __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)vrad, qi));
         }
       if (__ballot(any) != 0) {  // (wave-uniform; a tile without a hit -- most of them at a small radius -- issues no memory operation)
-        const uint64_t id = valid ? (uint64_t)p.row_ids[srow0 + row] : 0ull;
+        uint32_t id32 = srow0 + row;  // (kRangeRowsFlat: the row number is the vec id)
+        bool ok = valid;
+        if constexpr (Src::kRangeRows != kRangeRowsFlat) id32 = valid ? p.row_ids[srow0 + row] : 0xFFFFFFFFu;
+        if constexpr (Src::kRangeRows == kRangeRowsStored) ok = valid && id32 != 0xFFFFFFFFu;  // the count pass's rule, to the letter
+        const uint64_t id = id32;
 #pragma unroll
         for (int qi = 0; qi < QG; ++qi)
           if (qi < 2 * NP && qi < (int)v.nq) {
             const float a = acc[qi >> 1][qi & 1];
             const float dist = METRIC == 0 ? a : __fsub_rn(1.0f, a);
-            const bool hit = valid && dist <= __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)vrad, qi));
+            const bool hit = ok && dist <= __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)vrad, qi));
             const uint64_t m = __ballot(hit);
             if (m) {
               const uint64_t pos = readlane64(vbase, qi) + (uint32_t)__builtin_amdgcn_readlane((int)vhits, qi) + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
               if (hit) {
-                p.out_ids[pos] = id;
-                if (p.out_keys != nullptr) p.out_keys[pos] = make_key(dist, (uint32_t)__builtin_amdgcn_readlane((int)vseq, qi) + row);
+                if (!kKeyId || p.out_keys == nullptr) p.out_ids[pos] = id;
+                if (p.out_keys != nullptr) p.out_keys[pos] = make_key(dist, kKeyId ? id32 : (uint32_t)__builtin_amdgcn_readlane((int)vseq, qi) + row);
                 else p.out_dist[pos] = dist;
               }
               if (lane == qi) vhits += (uint32_t)__popcll(m);
@@ -162,6 +197,7 @@ __global__ __launch_bounds__(kWave * kWavesPerBlock) void range_scan_kernel(Src 
     }
   } else {
     static_assert(QG == 8 || QG == 16, "query groups are 1, 8 or 16 wide");
+    static_assert(QG == 8 || Src::kRangeRows == kRangeRowsListed, "segment sources group 8 queries");
     static_assert(kWavesPerBlock == 4, "items are padded to quads");
     extern __shared__ __attribute__((aligned(16))) float qlds[];
     const uint32_t n_quads = n_items / 4;
@@ -205,7 +241,7 @@ __global__ __launch_bounds__(kWave * kWavesPerBlock) void range_scan_kernel(Src 
 
 // CSR limits off the prefix: lims[q] = base[q * slots_per_query] (q = b: the total); the radii are checked on the way (a NaN radius is
 // an argument error, and the device-pointer call sees them here first).  misc: [0..1] total (u64) | [2] status word | [3] NaN radius.
-__global__ void range_lims_kernel(const uint64_t* base, uint64_t slots_per_query, uint32_t b, const float* radius, const uint32_t* status,
+static __global__ void range_lims_kernel(const uint64_t* base, uint64_t slots_per_query, uint32_t b, const float* radius, const uint32_t* status,
                                   uint64_t* lims, uint32_t* misc) {
   const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
   if (q > b) return;
@@ -221,9 +257,22 @@ __global__ void range_lims_kernel(const uint64_t* base, uint64_t slots_per_query
 }
 
 // sorted order: the distances back out of the sorted keys' high words
-__global__ void range_decode_kernel(const uint64_t* keys, uint64_t n, float* out_dist) {
+static __global__ void range_decode_kernel(const uint64_t* keys, uint64_t n, float* out_dist) {
   const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) out_dist[i] = __uint_as_float(order_bits_to_f32_bits((uint32_t)(keys[i] >> 32)));
 }
+
+// sorted order of the exhaustive range search: (vec id, distance) out of the sorted keys alone -- low word | high word
+static __global__ void range_decode_ids_kernel(const uint64_t* keys, uint64_t n, uint64_t* out_ids, float* out_dist) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) {
+    const uint64_t k = keys[i];
+    out_ids[i] = (uint32_t)k;
+    out_dist[i] = __uint_as_float(order_bits_to_f32_bits((uint32_t)(k >> 32)));
+  }
+}
+
+// vers_range_phases (ivf_search.hip): one finished range call of b queries and `total` results; ms = plan, count, prefix + total, fill, sort
+void range_phases_add(uint32_t b, uint64_t total, const float* ms5);
 
 }  // namespace vers

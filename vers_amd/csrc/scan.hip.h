@@ -446,6 +446,8 @@ __device__ __forceinline__ void tile_chunk_compute2(f32x2 (&accA)[QG / 2], f32x2
 //   static constexpr bool kStreamOnce        rows are read once per launch: non-temporal tile loads
 //   const uint32_t* seq_ids(it) const
 //   uint32_t bound_slot(it, qi) const        index into ScanParams::bounds of the merge group of (it, qi)
+// (+ what the range walk asks of a source: range.hip.h)
+constexpr int kRangeRowsListed = 0, kRangeRowsStored = 1, kRangeRowsFlat = 2;  // Src::kRangeRows
 template <int QG>
 struct ItemView {
   const float* rows;   // first tile of the item (blocked layout, 64-row aligned)

@@ -3,7 +3,7 @@
 // `ids[cluster].push(vec_id)` in ascending vec_id (ivfflat.rs:123-127).  Uses rocPRIM's
 // LSD radix sort, which is stable.
 // + the two rocPRIM steps of the range search (range.hip.h): the prefix over the per-slot hit counts and the per-query sort of
-// (key, id) pairs.  rocPRIM is instantiated in this translation unit only.
+// (key, id) pairs -- of keys alone for the exhaustive range search.  rocPRIM is instantiated in this translation unit only.
 #include <cstdlib>
 #include <cstring>
 
@@ -69,6 +69,19 @@ int32_t range_sort_segments(const uint64_t* keys_in, uint64_t* keys_out, const u
                             const uint64_t* lims, void* temp, size_t temp_bytes, hipStream_t st) {
   if (n == 0 || segments == 0) return VERS_OK;
   VERS_HIP_TRY(rocprim::segmented_radix_sort_pairs(temp, temp_bytes, keys_in, keys_out, ids_in, ids_out, n, segments, lims, lims + 1, 0u, 64u, st));
+  return VERS_OK;
+}
+// the same for keys alone (exhaustive range search: the key's low word IS the id)
+size_t range_sort_keys_temp_bytes(uint32_t n, uint32_t segments) {
+  size_t bytes = 0;
+  (void)rocprim::segmented_radix_sort_keys(nullptr, bytes, (const uint64_t*)nullptr, (uint64_t*)nullptr, n, segments, (const uint64_t*)nullptr,
+                                           (const uint64_t*)nullptr, 0u, 64u, (hipStream_t) nullptr);
+  return bytes + 256;
+}
+int32_t range_sort_segment_keys(const uint64_t* keys_in, uint64_t* keys_out, uint32_t n, uint32_t segments, const uint64_t* lims, void* temp,
+                                size_t temp_bytes, hipStream_t st) {
+  if (n == 0 || segments == 0) return VERS_OK;
+  VERS_HIP_TRY(rocprim::segmented_radix_sort_keys(temp, temp_bytes, keys_in, keys_out, n, segments, lims, lims + 1, 0u, 64u, st));
   return VERS_OK;
 }
 

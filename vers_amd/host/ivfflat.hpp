@@ -175,6 +175,21 @@ class IVFFlatIndex {
     return out;
   }
 
+  // Exhaustive range search (extension, vers_ivf_range_search_exhaustive): EVERY row in a list now with distance <= radius under `metric`,
+  // ascending by (distance, vec id) -- the head of utils::search_exhaustive's order; walk_order: list by list, ascending list position.
+  std::vector<std::pair<size_t, float>> range_search_exhaustive(const Vector<N>& query, float radius, uint32_t metric = VERS_METRIC_L2SQ,
+                                                                bool walk_order = false) const {
+    const uint32_t flags = walk_order ? VERS_RANGE_WALK_ORDER : 0u;
+    uint64_t lims[2] = {0, 0}, total = 0;
+    check(vers_ivf_range_search_exhaustive(handle(), query.v, sizeof(Vector<N>), 1, &radius, metric, flags, lims, nullptr, nullptr, 0, &total));  // size query
+    std::vector<uint64_t> oi(total ? total : 1);
+    std::vector<float> od(total ? total : 1);
+    if (total) check(vers_ivf_range_search_exhaustive(handle(), query.v, sizeof(Vector<N>), 1, &radius, metric, flags, lims, oi.data(), od.data(), total, &total));
+    std::vector<std::pair<size_t, float>> out;
+    for (uint64_t i = 0; i < total && i < oi.size(); ++i) out.emplace_back((size_t)oi[i], od[i]);
+    return out;
+  }
+
   // Index::save_index (base.rs:31-43): bincode 1.3 default options -- LE, u64 lengths, fields in order, no tags
   void save_index(const std::string& path) const {
     FILE* f = std::fopen(path.c_str(), "wb");

@@ -218,6 +218,37 @@ class IVFFlatIndex:
                                               _vp(stream)))
         return int(total.value)
 
+    def range_search_exhaustive(self, queries, radius, metric: int = capi.METRIC_L2SQ, walk_order: bool = False):
+        """Every row that is in a list now with distance <= radius (vers_ivf_range_search_exhaustive): the ground truth of range_search.
+        -> (lims, ids, dist) like range_search, by the same two-call protocol.  Default order: ascending (distance, vec id) = the head of
+        search_exhaustive(top_k = all rows); walk_order: ascending cluster, then list position (get_list(0), (1), ... concatenated)."""
+        q = np.ascontiguousarray(np.atleast_2d(queries), dtype=np.float32)
+        b = q.shape[0]
+        r = capi.range_radii(radius, b)
+        flags = capi.RANGE_WALK_ORDER if walk_order else 0
+        lims = np.zeros(b + 1, dtype=np.uint64)
+        cap = int(self._range_cap)
+        total = C.c_uint64(0)
+        while True:
+            ids = np.zeros(cap, dtype=np.uint64); dist = np.zeros(cap, dtype=np.float32)
+            check(lib().vers_ivf_range_search_exhaustive(self._h, _ptr(q), 4 * self.d, b, _ptr(r), metric, flags, _ptr(lims),
+                                                         _ptr(ids) if cap else None, _ptr(dist) if cap else None, cap, C.byref(total)))
+            if total.value <= cap:
+                break
+            cap = int(total.value)
+        self._range_cap = int(total.value)
+        return lims, ids[:total.value], dist[:total.value]
+
+    def range_search_exhaustive_dev(self, q_ptr: int, ldq: int, b: int, radius_ptr: int, metric: int, flags: int, lims_ptr: int, ids_ptr: int,
+                                    dist_ptr: int, cap: int, stream: int = 0) -> int:
+        """vers_ivf_range_search_exhaustive_dev on raw device pointers; synchronous.  Returns the total: ids / distances were written only
+        when it is <= cap."""
+        total = C.c_uint64(0)
+        check(lib().vers_ivf_range_search_exhaustive_dev(self._h, _vp(q_ptr), ldq, b, _vp(radius_ptr), metric, flags, _vp(lims_ptr),
+                                                         _vp(ids_ptr) if ids_ptr else None, _vp(dist_ptr) if dist_ptr else None, cap,
+                                                         C.byref(total), _vp(stream)))
+        return int(total.value)
+
     # -- device cache -----------------------------------------------------------------------------------
     def _upload(self):
         v = np.ascontiguousarray(self.values, dtype=np.float32)
