@@ -489,6 +489,9 @@ int32_t vers_ivf_range_search_exhaustive_dev(vers_ivf_t* h, const float* queries
  *                       columns read so far prove that none of its rows can pass any of its queries' thresholds; 0 = every tile is
  *                       read whole.  Not on sharded handles (measured: only cost there).  "pre_prune_first" (2): the first 64-column
  *                       step boundary at which a wave tests.
+ *   "pre_hot_single" (1) where tiles are abandoned early, the scan's blocks take the quads of the hot lists (some query's nearest:
+ *                       the first of the work order) one at a time, so that thresholds are tight before the bulk is read; 0 = guided
+ *                       runs of up to 8 quads from the first quad on.
  *   "scan_events" (2)   HIP event records around list-scan launches (vers_ivf_last_scan / vers_ivf_scan_times): 1 always, 0 never,
  *                       2 for batches only (the two records cost a single-query call 5.5-6 us).
  *  A/B and forced paths (tests, measurements):

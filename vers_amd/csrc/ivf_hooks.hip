@@ -25,6 +25,8 @@ int32_t vers_ivf_last_scan(vers_ivf_t* h, float* out_ms, uint64_t* out_union_row
   if (out_union_rows) *out_union_rows = t.union_rows;
   if (out_streamed_rows) *out_streamed_rows = t.streamed_rows;
   if (out_items) *out_items = t.n_items;
+  if (scan_debug_flags() & 16u)  // diagnosis only: the work order the batch was planned with (tests/test_prescan_handout_gpu.py reads the hot count here)
+    fprintf(stderr, "[vers stamps] work order: %u items, the first %u of hot lists\n", t.n_items, t.hot_items);
   if ((scan_debug_flags() & 16u) && W->stamps.p) {  // diagnosis only: per-wave phase cycles of the last launch
     unsigned long long sv[64] = {};
     VERS_HIP_TRY(hipMemcpy(sv, W->stamps.p, std::min<size_t>(512, W->stamps.cap), hipMemcpyDeviceToHost));

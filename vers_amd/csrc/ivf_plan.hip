@@ -163,7 +163,7 @@ __device__ __forceinline__ uint32_t group_lists(const GroupArgs& a, uint32_t* ta
     }
     __syncthreads();
     if (threadIdx.x == 0) {
-      a.tot->n_items = ci + ch; a.tot->n_groups = cg; a.tot->n_pairs = cp; a.tot->pad = 0;
+      a.tot->n_items = ci + ch; a.tot->n_groups = cg; a.tot->n_pairs = cp; a.tot->hot_items = ch;
       a.tot->union_rows = ur; a.tot->streamed_rows = sr;
     }
   }
@@ -316,7 +316,7 @@ __device__ __forceinline__ void plan1_block(const Plan1Args& a, uint64_t (*sh)[k
   const uint32_t n_items = (uint32_t)__shfl(item0 + n_s, kWave - 1, kWave);
   const uint32_t rows_scanned = (uint32_t)__shfl(excl_scan(scan ? len : 0u) + (scan ? len : 0u), kWave - 1, kWave);
   if (lane == 0) {
-    a.tot->n_items = n_items; a.tot->n_groups = (uint32_t)__popcll(smask); a.tot->n_pairs = a.tot->n_groups; a.tot->pad = 0;
+    a.tot->n_items = n_items; a.tot->n_groups = (uint32_t)__popcll(smask); a.tot->n_pairs = a.tot->n_groups; a.tot->hot_items = 0;
     a.tot->union_rows = rows_scanned; a.tot->streamed_rows = rows_scanned;
   }
 }

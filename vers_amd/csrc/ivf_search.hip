@@ -316,7 +316,7 @@ int32_t launch_prescan(vers_ivf* h, const IvfSrc<NQ>& src, uint32_t items_bound,
   // mostly on other ranks -- thresholds arrive too late to abandon anything, and the test is not free (profiles/r07_summary.txt).
   const bool prune = hi_only && h->metric == 0 && h->world == 1 && opt_get("pre_prune", 1) != 0 && n_steps >= 3 && n_steps <= kPruneMaxSteps && h->pre_misc.p != nullptr && h->prune_ctr.p != nullptr &&
                      prescan_lds_bytes_g(h->ld, kp, NQ, true, true) <= 160u * 1024u;
-  p.prune_tab = nullptr; p.prune_first = 0; p.prune_until = 0; p.prune_om = 0.0f; p.prune_last = nullptr; p.prune_tot = nullptr;
+  p.prune_tab = nullptr; p.prune_first = 0; p.prune_until = 0; p.prune_om = 0.0f; p.prune_last = nullptr; p.prune_tot = nullptr; p.hot_single = 0u;
   W->prune_last = nullptr;
   if (prune) {
     if (int32_t rc = W->prune_tab.reserve((size_t)b * n_steps * sizeof(float))) return rc;
@@ -330,6 +330,8 @@ int32_t launch_prescan(vers_ivf* h, const IvfSrc<NQ>& src, uint32_t items_bound,
     p.prune_last = quad_ctr + 1;  // (the three words behind the hand-out counter: zeroed with it)
     p.prune_tot = h->prune_ctr.as<unsigned long long>();
     W->prune_last = quad_ctr + 1;
+    // the hot lists' quads singly (pre_run_len): only where thresholds can let tiles go.  option "pre_hot_single" = 0: guided runs throughout.
+    p.hot_single = opt_get("pre_hot_single", 1) != 0 ? 1u : 0u;
   }
   if (NQ == kPreQWide && !hi_only) return fail(VERS_ERR_INVALID, "internal: 64-query blocks exist on the fp16 shadow with the hi-only query block");
   const size_t lds = prescan_lds_bytes_g(h->ld, kp, NQ, hi_only, prune);
@@ -414,7 +416,7 @@ int32_t search_dev_locked(vers_ivf* h, const float* q_dev, uint64_t ldq_in, uint
   SearchWs::CoarseAhead* const took = s.took;
   auto fill_src = [&](auto& src) {
     src.rows = h->rows.as<float>(); src.ld = h->ld; src.list_off = h->slot_off.as<uint32_t>();  // (items name lists by slot)
-    src.list_len = h->slot_len.as<uint32_t>(); src.items = W->items.as<ItemDesc>(); src.n_items_dev = &tot->n_items;
+    src.list_len = h->slot_len.as<uint32_t>(); src.items = W->items.as<ItemDesc>(); src.totals = tot;
     src.cnt = cnt; src.pair_off = pair_off; src.pairs = W->pairs.as<uint32_t>(); src.group_off = group_off;
     src.qblocks = W->qblocks.as<float>(); src.qp = qp; src.ldq = h->ldq; src.P = P; src.S_max = S_max; src.k_keep = k_keep;
     src.seg_rows = seg_rows; src.seg_target = seg_target; src.pj_pref = pj_pref; src.partials = W->partials.as<uint64_t>();
@@ -730,7 +732,7 @@ int32_t range_dev_locked(vers_ivf* h, const float* q_dev, uint64_t ldq_in, uint3
   if (n_slots >= 0xFFFFFFFFull) return fail(VERS_ERR_INVALID, "vers_ivf_range_search: batch too large (query x probe x segment slots); split the batch");
   auto fill_src = [&](auto& src) {
     src.rows = h->rows.as<float>(); src.ld = h->ld; src.list_off = h->slot_off.as<uint32_t>();
-    src.list_len = h->slot_len.as<uint32_t>(); src.items = W->items.as<ItemDesc>(); src.n_items_dev = &s.tot->n_items;
+    src.list_len = h->slot_len.as<uint32_t>(); src.items = W->items.as<ItemDesc>(); src.totals = s.tot;
     src.cnt = s.cnt; src.pair_off = s.pair_off; src.pairs = W->pairs.as<uint32_t>(); src.group_off = s.group_off;
     src.qblocks = W->qblocks.as<float>(); src.qp = s.qp; src.ldq = h->ldq; src.P = P; src.S_max = S_max; src.k_keep = s.k_keep;
     src.seg_rows = s.seg_rows; src.seg_target = s.seg_target; src.pj_pref = s.pj_pref; src.partials = W->partials.as<uint64_t>();

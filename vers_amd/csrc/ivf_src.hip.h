@@ -58,7 +58,7 @@ struct IvfSrc {
   const uint32_t* list_off;  // storage row of each (local) list
   const uint32_t* list_len;
   const ItemDesc* items;
-  const uint32_t* n_items_dev;
+  const GroupTotals* totals;   // the batch's totals on the device (group_scatter_kernel): the work order's length and its hot part
   const uint32_t* cnt;        // pairs per list
   const uint32_t* pair_off;   // first pair of each list
   const uint32_t* pairs;      // pair -> q*P + j
@@ -70,7 +70,8 @@ struct IvfSrc {
   const uint32_t* pj_pref;    // [b*P] sequence base of probe j of query q
   uint64_t* partials;         // [b*P*S_max][k_keep]
 
-  __device__ __forceinline__ uint32_t n_items() const { return *n_items_dev; }
+  __device__ __forceinline__ uint32_t n_items() const { return totals->n_items; }
+  __device__ __forceinline__ uint32_t hot_items() const { return totals->hot_items; }  // items of the hot lists, the first of the work order
   __device__ __forceinline__ void get(uint32_t it, ItemView<QG>& v) const {
     const ItemDesc d = items[it];
     const bool real = d.seg != kNoSeg;

@@ -44,7 +44,8 @@ struct GroupDesc {
   uint32_t pair_start, nq;
 };
 struct GroupTotals {
-  uint32_t n_items, n_groups, n_pairs, pad;
+  uint32_t n_items, n_groups, n_pairs;
+  uint32_t hot_items;      // items of the hot lists: they come first in the work order (the list scan's hand-out reads it, pre_run_len)
   uint64_t union_rows;     // sum of len over lists probed by at least one query (algorithmic rows)
   uint64_t streamed_rows;  // rows the scan items actually stream (a list is re-read per query group)
 };

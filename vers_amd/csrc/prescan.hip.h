@@ -56,6 +56,7 @@ constexpr uint32_t kPreMaxP = 1024;  // most probed lists per query on the matri
 
 struct PreParams {
   uint32_t ld, n_chunks, kp;
+  uint32_t hot_single;  // != 0: the quads of the hot lists are handed out singly (pre_run_len below; Src::hot_items() says how many there are)
   uint32_t* status;
   uint32_t* bounds32;   // per merge group: order bits of the smallest known kp-th val (0xFFFFFFFF = none yet)
   uint32_t* qflags;     // per merge group: != 0 -> a non-finite val was seen, the query must be re-done exactly
@@ -76,6 +77,7 @@ struct PreParams {
 
 // (defined next to pre_bound, below)
 __host__ __device__ inline float prune_lower(float acc_min, float m_p, float om_eps, float tail);
+__host__ __device__ inline uint32_t pre_run_len(uint32_t seen, uint32_t n_quads, uint32_t hot_quads, uint32_t n_blocks);
 
 
 // f32 tiles -> fp16 shadow tiles (round to nearest even), laid out as the A operand of v_mfma_f32_32x32x16_f16: a
@@ -716,12 +718,12 @@ __global__ __launch_bounds__(kWave * kPreWavesG) __attribute__((amdgpu_waves_per
   const unsigned long long clk0 = (p.debug & 16u) ? __builtin_amdgcn_s_memtime() : 0ull;
   const unsigned long long rt0 = (p.debug & 16u) ? __builtin_amdgcn_s_memrealtime() : 0ull;
   // Quads are handed out in RUNS (guided self-scheduling): a block takes `remaining / (2 * blocks)` consecutive quads at a time,
-  // at most kMaxRun, down to one at the end of the launch -- long stretches while there is plenty of work, single quads when
+  // at most kPreMaxRun, down to one at the end of the launch -- long stretches while there is plenty of work, single quads when
   // the last CUs are being filled.  Consecutive quads of one (list, query group) share their query block and their candidate
   // buffers: the block stages ONCE for them and leaves ONE partial slot (the first quad's; the others' are written empty).
   // That is what lets the host cut the lists of a SHARDED scan into finer quads (2.7 whole-list quads per CU at 8 ranks left
   // the last third of the launch half empty) without paying the 6 us of staging per quad.
-  constexpr uint32_t kMaxRun = 8;
+  // With the early abandon on, the quads of the HOT lists -- the first of the work order -- go out ONE at a time (pre_run_len).
   uint32_t run_first = 0xFFFFFFFFu, run_last = 0, prev_nq = 0;  // the quads whose lists still sit in LDS (one merged run)
   uint32_t cur_list = 0xFFFFFFFFu, cur_group = 0;
   PruneCtr pc = {0u, 0u, 0u};
@@ -762,9 +764,13 @@ __global__ __launch_bounds__(kWave * kPreWavesG) __attribute__((amdgpu_waves_per
     uint32_t start = b0, count = 1;
     if (p.next_quad != nullptr) {
       if (threadIdx.x == 0) {
+        // (the hot count is read here, next to the counter -- two independent loads --, not kept in a register for the whole launch;
+        // only the instantiations that abandon tiles are ever launched with the switch set)
+        uint32_t hot_quads = 0u;
+        if constexpr (PR)
+          if (p.hot_single != 0u) hot_quads = src.hot_items() / 4u;
         const uint32_t seen = __hip_atomic_load(p.next_quad, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        uint32_t r = seen < n_quads ? (n_quads - seen) / (2u * n_res) : 1u;
-        r = r < 1u ? 1u : (r > kMaxRun ? kMaxRun : r);
+        const uint32_t r = pre_run_len(seen, n_quads, hot_quads, n_res);
         nq_lds[0] = atomicAdd(p.next_quad, r);
         nq_lds[1] = r;
       }
@@ -995,6 +1001,23 @@ __host__ __device__ inline float prune_tail_entry(double hS2, double qn, double 
   return prune_round_up(hS2 * (1.0 + prune_eps(d_pad)) + prune_rho(xmax2, R2, d_pad) + pb.common + 16.0 * 5.9604644775390625e-08 * S);
 }
 __host__ __device__ inline float prune_lower(float acc_min, float m_p, float om_eps, float tail) { return (acc_min + m_p * om_eps) - tail; }
+
+// ---- the hand-out of quads: how many consecutive quads a block takes when it has seen `seen` of n_quads handed out ------------------
+// A threshold is tight once its query's nearest list -- a HOT list, the first hot_quads of the work order -- has been scanned, and a
+// tile of another list is abandoned only when EVERY query of its block is tight.  Runs of kPreMaxRun whole hot lists per block kept
+// two thirds of the blocks on hot lists for more than half of a launch while the others read cold lists whole (DESIGN.md section
+// 3b): inside the hot region a run is ONE quad, so that every block works on hot lists until there are none left.  (Not "the rest of
+// the list's quads": where a list ends is in its item descriptors, a load the counter's atomic would have to wait for; two quads of
+// one list on two blocks are legal -- each run fills its first quad's slot -- and each brings the list's queries a threshold of its
+// own half.)  Behind the hot region: guided self-scheduling, remaining / (2 * blocks) clamped to 1 .. kPreMaxRun, as ever.
+// hot_quads = 0: that rule for every `seen`.  A hot count beyond n_quads is clamped.  `seen` may be stale (the counter moves between
+// a block's load and its atomicAdd): a run computed behind the hot region still starts behind it, the counter only grows.
+constexpr uint32_t kPreMaxRun = 8;
+__host__ __device__ inline uint32_t pre_run_len(uint32_t seen, uint32_t n_quads, uint32_t hot_quads, uint32_t n_blocks) {
+  if (seen < (hot_quads < n_quads ? hot_quads : n_quads)) return 1u;
+  const uint32_t r = seen < n_quads ? (n_quads - seen) / (2u * n_blocks) : 1u;
+  return r < 1u ? 1u : (r > kPreMaxRun ? kPreMaxRun : r);
+}
 // --------------------------------------------------------------------------------------------------------------------------------------
 
 // The table of a batch: a wave per query.  tab[q][c], c = 1 .. ld / 64 - 1 (entry 0 is never read): prune_tail_entry of the columns
