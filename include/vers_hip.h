@@ -414,8 +414,8 @@ int32_t vers_compact_phases(double* out8, int32_t reset);
  *   errors   : VERS_ERR_NAN a NaN distance on any scanned row (as every search), outputs untouched; VERS_ERR_INVALID a NaN radius,
  *              nprobe == 0 (the reference's spill walk is defined by top_k and has no range meaning), unknown flag bits, more than
  *              2^32 - 1 results in one call or 2^32 - 1 (query, probe, row segment) slots of the plan -- b x min(nprobe, k) x segments
- *              of the longest list -- (either way: split the batch), a handle sharded by cluster (world > 1: a sharded range search needs a
- *              variable-size exchange; not implemented); VERS_ERR_INSUFFICIENT no centroids (as search; a streamed upload in progress
+ *              of the longest list -- (either way: split the batch), a handle sharded by cluster (world > 1: its range search needs a
+ *              variable-size exchange -- vers_ivf_range_search_sharded_dev below); VERS_ERR_INSUFFICIENT no centroids (as search; a streamed upload in progress
  *              is seen as an empty index); VERS_ERR_HIP scratch for the result staging did not fit, outputs untouched.
  *   edges    : b == 0 is a no-op with *out_total = 0.  A probed list that is empty contributes nothing. */
 #define VERS_RANGE_WALK_ORDER 1u
@@ -448,7 +448,7 @@ int32_t vers_range_phases(double* out8, int32_t reset);
  *              and the call waits for it.
  *   errors   : VERS_ERR_NAN a NaN distance on any scanned live row, outputs untouched; VERS_ERR_INVALID a NaN radius, unknown flag bits,
  *              metric > VERS_METRIC_COSDIST, more than 2^32 - 1 results or 2^32 - 1 (query, row segment) slots in one call (split the
- *              batch), IVF only: a handle sharded by cluster (world > 1), for vers_ivf_range_search's reason; VERS_ERR_HIP scratch for
+ *              batch), IVF only: a handle sharded by cluster (world > 1: vers_ivf_range_search_exhaustive_sharded_dev); VERS_ERR_HIP scratch for
  *              the result staging did not fit, outputs untouched.
  *   NOT an error, total 0 and every limit 0 (what the exhaustive top-k search makes of it): an empty flat corpus, an IVF handle without
  *              centroids or with a streamed upload in progress.
@@ -465,6 +465,70 @@ int32_t vers_ivf_range_search_exhaustive(vers_ivf_t* h, const float* queries, ui
 int32_t vers_ivf_range_search_exhaustive_dev(vers_ivf_t* h, const float* queries_dev, uint64_t ldq_floats, uint32_t b, const float* radius_dev,
                                              uint32_t metric, uint32_t flags, uint64_t* out_lims_dev, uint64_t* out_ids_dev,
                                              float* out_dist_dev, uint64_t cap, uint64_t* out_total /* host */, void* stream);
+/* SHARDED range search: the range calls on handles sharded by cluster (vers_ivf_set_shard / vers_ivf_build_sharded_dev), where the calls
+ * above return VERS_ERR_INVALID.  The result is the unsharded index's, bit for bit -- limits, ids, order, distance bits.  Three layers:
+ *
+ * 1. A rank's PARTIAL: vers_ivf_range_search_partial_dev / vers_ivf_range_search_exhaustive_partial_dev run the count pass, prefix scan and
+ *    fill pass over the lists (probed call) or rows (exhaustive call) THIS handle stores and return CSR of (key, id) pairs instead of
+ *    (id, distance): out_keys_dev / out_ids_dev[out_lims_dev[q] .. out_lims_dev[q + 1]).
+ *      keys     : probed call: (order bits of the distance) << 32 | the row's sequence number in the query's probe order, counted over the
+ *                 GLOBAL list lengths -- the same number on every rank.  Exhaustive call: (order bits) << 32 | vec id.  Either way the keys
+ *                 of one query are unique across ranks and ascend in the unsharded call's default order.
+ *      order    : default = each query's run ascending by key.  VERS_RANGE_WALK_ORDER, probed call: this rank's walk order = ascending
+ *                 sequence number (the key's low word).  Exhaustive call: VERS_ERR_INVALID -- storage order across ranks has no key the
+ *                 ranks share; a walk order of the exhaustive search on sharded handles is out of scope.
+ *      protocol : that of vers_ivf_range_search_dev on the LOCAL count: *out_total = this rank's count; > cap: VERS_OK, out_lims complete,
+ *                 the arrays untouched; cap == 0 with NULL arrays is the size query.  Synchronous.
+ *      handles  : sharded or not (world == 1: the whole result as keys).  Errors as the unsharded calls; the 2^32 - 1 limits apply to the
+ *                 local counts.
+ *
+ * 2. The MERGE: vers_range_merge_dev turns `world` partials into the result, on `stream`, without a handle and without synchronising.
+ *      input    : rank r's run for query q is keys_dev[r * rank_stride + rank_lims_dev[r * (b + 1) + q] ..), ids_dev the same way;
+ *                 rank_lims_dev = every rank's out_lims, [world][b + 1] u64.  One gathered [world][2][T_max] buffer serves both arrays with
+ *                 ids_dev = keys_dev + T_max and rank_stride = 2 * T_max.  Elements behind a rank's total (padding) are never read.
+ *      output   : out_lims_dev[q] = SUM_r rank_lims[r][q] (q = 0 .. b; the last one the global total); out_ids_dev / out_dist_dev must hold
+ *                 that many entries; the distance is decoded from the key's high word.  flags & VERS_RANGE_WALK_ORDER: the runs ascend by
+ *                 the key's low word and are merged by it (partials made with the same flag).
+ *      how      : one thread per gathered entry: its position is out_lims[q] + its index in its own run + the number of smaller keys in
+ *                 every other rank's run (a bisection each).  No atomics: the same bytes on every run.
+ *      errors   : VERS_ERR_INVALID, before anything touches a device: world == 0 (or > 65535), unknown flag bits, b > 0 with NULL
+ *                 rank_lims_dev / out_lims_dev, rank_stride > 0 with a NULL array.  b == 0: no-op.  rank_stride == 0: the limits alone.
+ *
+ * 3. END TO END: vers_ivf_range_search_sharded_dev / vers_ivf_range_search_exhaustive_sharded_dev.  EVERY rank calls, with the same queries,
+ *    radii, nprobe / metric, flags and THE SAME cap (the decision to exchange results depends on it).  comm: the callbacks of
+ *    vers_ivf_build_sharded_dev, of which all_gather alone is used (synchronous, as in vers_ivf_remove_batch_dev); NULL on an unsharded
+ *    handle (world 1: no exchange).
+ *      exchange 1 : [b + 1] u64 per rank -- this rank's per-query counts and its local status word.  Afterwards every rank knows the global
+ *                   limits and total, every rank's total and the worst status.  This is the AGREEMENT round: if any rank failed locally (a
+ *                   NaN distance, a NaN radius, scratch that did not fit; option "test_fail_sharded" injects one), every rank returns the
+ *                   first failing rank's status, outputs untouched, and nobody enters exchange 2.
+ *      exchange 2 : only if 0 < total <= cap: ONE all_gather of 2 * 8 * max_r T_r bytes per rank (keys | ids, padded to the largest rank's
+ *                   count T_r), then the merge.
+ *      result     : *out_total = the GLOBAL total and out_lims_dev complete whenever the call returns VERS_OK; > cap: ids / distances
+ *                   untouched, as in the unsharded protocol; the 2^32 - 1 limit applies to the global total (VERS_ERR_INVALID everywhere).
+ *      errors     : before any exchange (so every rank must pass arguments that fail alike): a comm whose rank / world disagree with the
+ *                   handle's, nprobe == 0, unknown flag bits, VERS_RANGE_WALK_ORDER on the exhaustive call, bad pointers, no centroids
+ *                   (probed call).  After the agreement round a local failure (the gather buffers did not fit, VERS_ERR_COMM from a
+ *                   callback) has no round left to be told in: the host aborts the group on a non-zero return, as for the sharded build.
+ *    Synchronous, like every range call.  vers_range_phases counts the local part of these calls. */
+int32_t vers_ivf_range_search_partial_dev(vers_ivf_t* h, const float* queries_dev, uint64_t ldq_floats, uint32_t b, const float* radius_dev,
+                                          uint32_t nprobe, uint32_t flags, uint64_t* out_lims_dev /* [b+1] */, uint64_t* out_keys_dev,
+                                          uint64_t* out_ids_dev, uint64_t cap, uint64_t* out_total /* host */, void* stream);
+int32_t vers_ivf_range_search_exhaustive_partial_dev(vers_ivf_t* h, const float* queries_dev, uint64_t ldq_floats, uint32_t b,
+                                                     const float* radius_dev, uint32_t metric, uint32_t flags, uint64_t* out_lims_dev,
+                                                     uint64_t* out_keys_dev, uint64_t* out_ids_dev, uint64_t cap,
+                                                     uint64_t* out_total /* host */, void* stream);
+int32_t vers_range_merge_dev(const uint64_t* keys_dev, const uint64_t* ids_dev, uint64_t rank_stride /* elements */,
+                             const uint64_t* rank_lims_dev /* [world][b+1] */, uint32_t world, uint32_t b, uint32_t flags,
+                             uint64_t* out_lims_dev /* [b+1] */, uint64_t* out_ids_dev, float* out_dist_dev, void* stream);
+int32_t vers_ivf_range_search_sharded_dev(vers_ivf_t* h, const vers_comm_t* comm /* NULL = world 1 */, const float* queries_dev,
+                                          uint64_t ldq_floats, uint32_t b, const float* radius_dev, uint32_t nprobe, uint32_t flags,
+                                          uint64_t* out_lims_dev, uint64_t* out_ids_dev, float* out_dist_dev, uint64_t cap,
+                                          uint64_t* out_total /* host */, void* stream);
+int32_t vers_ivf_range_search_exhaustive_sharded_dev(vers_ivf_t* h, const vers_comm_t* comm /* NULL = world 1 */, const float* queries_dev,
+                                                     uint64_t ldq_floats, uint32_t b, const float* radius_dev, uint32_t metric,
+                                                     uint32_t flags, uint64_t* out_lims_dev, uint64_t* out_ids_dev, float* out_dist_dev,
+                                                     uint64_t cap, uint64_t* out_total /* host */, void* stream);
 /* Process-wide switches: every one is a named option set here (or, for a process one does not control from inside, through the ONE
  * environment variable VERS_OPTIONS="name=value,name=value", read once; besides it the library reads only VERS_SHADOW and
  * VERS_ROWMAJOR, the two memory switches of INTEGRATION.md = options "shadow" / "rowmajor", and VERS_PRE_PRUNE = option "pre_prune").  Unknown name: VERS_ERR_INVALID.

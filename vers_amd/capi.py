@@ -118,6 +118,15 @@ SIGNATURES = {
                                                      C.POINTER(C.c_uint64)]),
     "vers_ivf_range_search_exhaustive_dev": (C.c_int32, [_vp, _vp, C.c_uint64, C.c_uint32, _vp, C.c_uint32, C.c_uint32, _vp, _vp, _vp, C.c_uint64,
                                                          C.POINTER(C.c_uint64), _vp]),
+    "vers_ivf_range_search_partial_dev": (C.c_int32, [_vp, _vp, C.c_uint64, C.c_uint32, _vp, C.c_uint32, C.c_uint32, _vp, _vp, _vp, C.c_uint64,
+                                                      C.POINTER(C.c_uint64), _vp]),
+    "vers_ivf_range_search_exhaustive_partial_dev": (C.c_int32, [_vp, _vp, C.c_uint64, C.c_uint32, _vp, C.c_uint32, C.c_uint32, _vp, _vp, _vp,
+                                                                 C.c_uint64, C.POINTER(C.c_uint64), _vp]),
+    "vers_range_merge_dev": (C.c_int32, [_vp, _vp, C.c_uint64, _vp, C.c_uint32, C.c_uint32, C.c_uint32, _vp, _vp, _vp, _vp]),
+    "vers_ivf_range_search_sharded_dev": (C.c_int32, [_vp, _vp, _vp, C.c_uint64, C.c_uint32, _vp, C.c_uint32, C.c_uint32, _vp, _vp, _vp, C.c_uint64,
+                                                      C.POINTER(C.c_uint64), _vp]),
+    "vers_ivf_range_search_exhaustive_sharded_dev": (C.c_int32, [_vp, _vp, _vp, C.c_uint64, C.c_uint32, _vp, C.c_uint32, C.c_uint32, _vp, _vp, _vp,
+                                                                 C.c_uint64, C.POINTER(C.c_uint64), _vp]),
     "vers_kmeans_update": (C.c_int32, [C.c_int32, _vp, C.c_uint64, C.c_uint64, _vp, C.c_uint64, C.c_uint32, _vp]),
     "vers_kmeans_cost": (C.c_int32, [C.c_int32, _vp, C.c_uint64, C.c_uint64, _vp, C.c_uint64, C.c_uint64, _vp, C.c_uint32,
                                      C.POINTER(C.c_float)]),

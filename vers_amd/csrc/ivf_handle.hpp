@@ -46,6 +46,7 @@ struct SearchWs {
   // range search (ivf_search.hip: range_dev_locked): hits per (query, probe, segment) slot | their exclusive prefix | radii, CSR limits and
   // results of a host-pointer call | [0..1] total, [2] status, [3] NaN-radius flag | (key, id) staging of the sorted order + rocPRIM's temporary
   DevBuf rg_counts, rg_base, rg_rad, rg_lims, rg_misc, rg_stage, rg_tmp;
+  DevBuf rg_rlims;  // sharded range search: every rank's CSR limits [world][b + 1] (range_merge.hip.h); the gather itself goes through g_send / g_recv
   uint32_t* rg_pin = nullptr;  // pinned [4]: where a range call reads its total, status word and NaN-radius flag after its first synchronisation
   hipEvent_t rg_ev[6] = {};  // phase boundaries of the most recent range call (vers_range_phases), created on first use
   DevBuf g_send, g_recv;  // sharded search without the host in the loop: this rank's [2][b][top_k] partial | the world's

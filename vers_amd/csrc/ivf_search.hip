@@ -4,7 +4,9 @@
 // cross-GPU merge of partial results, host-pointer staging, and the search entry points of the C ABI.
 #include <chrono>
 #include <cstring>
+#include <functional>
 #include <limits>
+#include <vector>
 
 #include "finish.hip.h"
 #include "flat_shadow.hpp"
@@ -12,6 +14,7 @@
 #include "single.hip.h"
 #include "finish_wide.hip.h"
 #include "range.hip.h"
+#include "range_merge.hip.h"
 
 namespace vers {
 
@@ -710,11 +713,23 @@ int32_t launch_range_scan(vers_ivf* h, const IvfSrc<QG>& src, uint32_t items_bou
   return VERS_OK;
 }
 
+// A range call that ends in (key, id) pairs instead of (id, distance) -- a rank's PARTIAL of a sharded range search: the same count pass,
+// prefix scan and fill pass over the lists (rows) this handle stores, the keys always staged, the segmented sort without the decode.
+struct RangePartial {
+  uint64_t* keys = nullptr;  // where the keys go, beside ids_dev
+  // The sharded call, between the count and the fill: told the local total, it agrees with the peers (exchange 1), names where keys and ids
+  // go and may call the fill off (go = false).  Without it: the cap protocol of the unsharded calls, on the local total.
+  std::function<int32_t(uint64_t local_total, uint64_t*& keys, uint64_t*& ids, bool& go)> decide;
+};
+
 // Range search of b >= 1 queries on `st`: plan, count launch, scan, sync and total, fill, sort, sync.  The caller holds the index shared, a
 // leased workspace and status word 1 (HostStatusSlot: the call synchronises and consumes its status itself).  own_out: ids / distances go to
 // the workspace's o_ids / o_dist, sized by the total (the host-pointer call copies them out), else to ids_dev / dist_dev -- when total <= cap.
+// part: (key, id) pairs instead -- default order ascending by key, walk order ascending sequence number (a sharded rank walks its probes in
+// rank order); dist_dev is not used.
 int32_t range_dev_locked(vers_ivf* h, const float* q_dev, uint64_t ldq_in, uint32_t b, const float* radius_dev, uint32_t nprobe, uint32_t flags,
-                         uint64_t* lims_dev, uint64_t* ids_dev, float* dist_dev, uint64_t cap, bool own_out, uint64_t* out_total, hipStream_t st) {
+                         uint64_t* lims_dev, uint64_t* ids_dev, float* dist_dev, uint64_t cap, bool own_out, uint64_t* out_total, hipStream_t st,
+                         RangePartial* part = nullptr) {
   for (auto& e : W->rg_ev)
     if (!e) VERS_HIP_TRY(hipEventCreate(&e));
   VERS_HIP_TRY(hipEventRecord(W->rg_ev[0], st));
@@ -778,7 +793,10 @@ int32_t range_dev_locked(vers_ivf* h, const float* q_dev, uint64_t ldq_in, uint3
     for (int i = 0; i + 1 < n_ev; ++i) (void)hipEventElapsedTime(&ms[i], W->rg_ev[i], W->rg_ev[i + 1]);
     range_phases_add(b, total, ms);
   };
-  if (total == 0 || total > cap) { phases(4); return VERS_OK; }  // (too small a buffer: the limits are complete, ids / distances untouched)
+  bool go = total != 0 && total <= cap;  // (too small a buffer: the limits are complete, ids / distances untouched)
+  if (part && part->decide)
+    if (int32_t rc = part->decide(total, part->keys, ids_dev, go)) return rc;
+  if (!go) { phases(4); return VERS_OK; }
   if (own_out) {
     if (int32_t rc = W->o_ids.reserve((size_t)total * sizeof(uint64_t))) return rc;
     if (int32_t rc = W->o_dist.reserve((size_t)total * sizeof(float))) return rc;
@@ -787,19 +805,22 @@ int32_t range_dev_locked(vers_ivf* h, const float* q_dev, uint64_t ldq_in, uint3
   const bool walk = (flags & VERS_RANGE_WALK_ORDER) != 0;
   size_t sort_tmp = 0;
   uint64_t *k_in = nullptr, *k_out = nullptr, *i_in = nullptr;
-  if (!walk) {  // staging of the sorted order: keys in | keys out | ids in, + rocPRIM's temporary
+  if (!walk) {  // staging of the sorted order: keys in | keys out | ids in, + rocPRIM's temporary (a partial's sorted keys are its result: keys in | ids in)
     sort_tmp = range_sort_temp_bytes((uint32_t)total, b);
-    if (int32_t rc = W->rg_stage.reserve(3 * (size_t)total * sizeof(uint64_t))) return rc;
+    if (int32_t rc = W->rg_stage.reserve((part ? 2 : 3) * (size_t)total * sizeof(uint64_t))) return rc;
     if (int32_t rc = W->rg_tmp.reserve(sort_tmp)) return rc;
-    k_in = W->rg_stage.as<uint64_t>(); k_out = k_in + total; i_in = k_out + total;
+    k_in = W->rg_stage.as<uint64_t>(); k_out = part ? part->keys : k_in + total; i_in = k_in + (part ? 1 : 2) * total;
   }
-  rp.out_keys = walk ? nullptr : k_in; rp.out_ids = walk ? ids_dev : i_in; rp.out_dist = dist_dev;
+  if (part) { rp.out_keys = walk ? part->keys : k_in; rp.out_ids = walk ? ids_dev : i_in; rp.out_dist = nullptr; }  // (a key beside every id, in walk order too)
+  else { rp.out_keys = walk ? nullptr : k_in; rp.out_ids = walk ? ids_dev : i_in; rp.out_dist = dist_dev; }
   if (int32_t rc = pass(std::true_type{}, rp)) return rc;
   VERS_HIP_TRY(hipEventRecord(W->rg_ev[4], st));
   if (!walk) {
     if (int32_t rc = range_sort_segments(k_in, k_out, i_in, ids_dev, (uint32_t)total, b, lims_dev, W->rg_tmp.p, sort_tmp, st)) return rc;
-    hipLaunchKernelGGL(range_decode_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (const uint64_t*)k_out, total, dist_dev);
-    VERS_HIP_TRY(hipGetLastError());
+    if (!part) {
+      hipLaunchKernelGGL(range_decode_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (const uint64_t*)k_out, total, dist_dev);
+      VERS_HIP_TRY(hipGetLastError());
+    }
   }
   VERS_HIP_TRY(hipEventRecord(W->rg_ev[5], st));
   VERS_HIP_TRY(hipStreamSynchronize(st));
@@ -826,7 +847,8 @@ int32_t launch_range_seg_scan(vers_ivf* h, const SegSrc<QG, true>& src, uint32_t
 // workspace and status word 1.  An index without centroids (a streamed upload in progress included) is scanned as zero rows: total 0, every
 // limit 0, the radii still checked -- what the exhaustive top-k search makes of it.
 int32_t range_exhaustive_dev_locked(vers_ivf* h, const float* q_dev, uint64_t ldq_in, uint32_t b, const float* radius_dev, uint32_t metric, uint32_t flags,
-                                    uint64_t* lims_dev, uint64_t* ids_dev, float* dist_dev, uint64_t cap, bool own_out, uint64_t* out_total, hipStream_t st) {
+                                    uint64_t* lims_dev, uint64_t* ids_dev, float* dist_dev, uint64_t cap, bool own_out, uint64_t* out_total, hipStream_t st,
+                                    RangePartial* part = nullptr) {
   for (auto& e : W->rg_ev)
     if (!e) VERS_HIP_TRY(hipEventCreate(&e));
   VERS_HIP_TRY(hipEventRecord(W->rg_ev[0], st));
@@ -890,27 +912,31 @@ int32_t range_exhaustive_dev_locked(vers_ivf* h, const float* q_dev, uint64_t ld
     for (int i = 0; i + 1 < n_ev; ++i) (void)hipEventElapsedTime(&ms[i], W->rg_ev[i], W->rg_ev[i + 1]);
     range_phases_add(b, total, ms);
   };
-  if (total == 0 || total > cap) { phases(4); return VERS_OK; }  // (too small a buffer: the limits are complete, ids / distances untouched)
+  bool go = total != 0 && total <= cap;  // (too small a buffer: the limits are complete, ids / distances untouched)
+  if (part && part->decide)
+    if (int32_t rc = part->decide(total, part->keys, ids_dev, go)) return rc;
+  if (!go) { phases(4); return VERS_OK; }
   if (own_out) {
     if (int32_t rc = W->o_ids.reserve((size_t)total * sizeof(uint64_t))) return rc;
     if (int32_t rc = W->o_dist.reserve((size_t)total * sizeof(float))) return rc;
     ids_dev = W->o_ids.as<uint64_t>(); dist_dev = W->o_dist.as<float>();
   }
-  const bool walk = (flags & VERS_RANGE_WALK_ORDER) != 0;
+  const bool walk = (flags & VERS_RANGE_WALK_ORDER) != 0 && !part;  // (a partial has no walk order: storage order across ranks has no key; refused by its entry points)
   size_t sort_tmp = 0;
   uint64_t *k_in = nullptr, *k_out = nullptr;
   if (!walk) {  // staging of the sorted order: keys in | keys out (the key's low word is the id), + rocPRIM's temporary
     sort_tmp = range_sort_keys_temp_bytes((uint32_t)total, b);
     if (int32_t rc = W->rg_stage.reserve(2 * (size_t)total * sizeof(uint64_t))) return rc;
     if (int32_t rc = W->rg_tmp.reserve(sort_tmp)) return rc;
-    k_in = W->rg_stage.as<uint64_t>(); k_out = k_in + total;
+    k_in = W->rg_stage.as<uint64_t>(); k_out = part ? part->keys : k_in + total;
   }
   rp.out_keys = k_in; rp.out_ids = walk ? ids_dev : nullptr; rp.out_dist = walk ? dist_dev : nullptr;
   if (int32_t rc = pass(std::true_type{})) return rc;
   VERS_HIP_TRY(hipEventRecord(W->rg_ev[4], st));
   if (!walk) {
     if (int32_t rc = range_sort_segment_keys(k_in, k_out, (uint32_t)total, b, lims_dev, W->rg_tmp.p, sort_tmp, st)) return rc;
-    hipLaunchKernelGGL(range_decode_ids_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (const uint64_t*)k_out, total, ids_dev, dist_dev);
+    if (part) hipLaunchKernelGGL(range_key_ids_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (const uint64_t*)k_out, total, ids_dev);
+    else hipLaunchKernelGGL(range_decode_ids_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (const uint64_t*)k_out, total, ids_dev, dist_dev);
     VERS_HIP_TRY(hipGetLastError());
   }
   VERS_HIP_TRY(hipEventRecord(W->rg_ev[5], st));
@@ -920,17 +946,21 @@ int32_t range_exhaustive_dev_locked(vers_ivf* h, const float* q_dev, uint64_t ld
 }
 
 // what both exhaustive entry points refuse before they touch the device
-static int32_t range_exhaustive_check(vers_ivf* h, const char* who, uint32_t flags) {
+static int32_t range_exhaustive_check(vers_ivf* h, const char* who, uint32_t flags, bool partial = false) {
   if (flags & ~VERS_RANGE_WALK_ORDER) return fail(VERS_ERR_INVALID, std::string(who) + ": unknown flag bits");
-  if (h->world > 1) return fail(VERS_ERR_INVALID, std::string(who) + ": the handle is sharded by cluster; a sharded range search is not implemented");
+  if (partial && (flags & VERS_RANGE_WALK_ORDER))
+    return fail(VERS_ERR_INVALID, std::string(who) + ": no walk order across ranks (storage order has no key the ranks share); use the default order");
+  if (h->world > 1 && !partial)
+    return fail(VERS_ERR_INVALID, std::string(who) + ": the handle is sharded by cluster; use vers_ivf_range_search_exhaustive_sharded_dev (or the partial call + vers_range_merge_dev)");
   return VERS_OK;
 }
 
 // what both entry points refuse before they touch the device
-static int32_t range_check(vers_ivf* h, const char* who, uint32_t nprobe, uint32_t flags) {
+static int32_t range_check(vers_ivf* h, const char* who, uint32_t nprobe, uint32_t flags, bool partial = false) {
   if (flags & ~VERS_RANGE_WALK_ORDER) return fail(VERS_ERR_INVALID, std::string(who) + ": unknown flag bits");
   if (nprobe == 0) return fail(VERS_ERR_INVALID, std::string(who) + ": nprobe must be at least 1 (the reference's spill walk is defined by top_k: it has no range meaning)");
-  if (h->world > 1) return fail(VERS_ERR_INVALID, std::string(who) + ": the handle is sharded by cluster; a sharded range search is not implemented");
+  if (h->world > 1 && !partial)
+    return fail(VERS_ERR_INVALID, std::string(who) + ": the handle is sharded by cluster; use vers_ivf_range_search_sharded_dev (or the partial call + vers_range_merge_dev)");
   if (h->k == 0) return fail(VERS_ERR_INSUFFICIENT, "range search on an index without centroids (reference: index out of bounds, ivfflat.rs:169)");
   return VERS_OK;
 }
@@ -1415,6 +1445,212 @@ int32_t vers_ivf_range_search_exhaustive(vers_ivf_t* h, const float* queries, ui
   VERS_HIP_TRY(hipMemcpy(out_ids, W->o_ids.p, (size_t)total * sizeof(uint64_t), hipMemcpyDeviceToHost));
   VERS_HIP_TRY(hipMemcpy(out_dist, W->o_dist.p, (size_t)total * sizeof(float), hipMemcpyDeviceToHost));
   return VERS_OK;
+}
+
+// ---- sharded range search: a rank's partial, the cross-rank merge, and the two exchanges around them (vers_hip.h) ----
+int32_t vers_ivf_range_search_partial_dev(vers_ivf_t* h, const float* queries_dev, uint64_t ldq_floats, uint32_t b, const float* radius_dev, uint32_t nprobe,
+                                          uint32_t flags, uint64_t* out_lims_dev, uint64_t* out_keys_dev, uint64_t* out_ids_dev, uint64_t cap, uint64_t* out_total,
+                                          void* stream) {
+  if (!h) return fail(VERS_ERR_INVALID, "null handle");
+  if (!out_total) return fail(VERS_ERR_INVALID, "vers_ivf_range_search_partial_dev: out_total is required");
+  *out_total = 0;
+  if (b && (!queries_dev || ldq_floats < h->d || !radius_dev || !out_lims_dev || (cap && (!out_keys_dev || !out_ids_dev))))
+    return fail(VERS_ERR_INVALID, "vers_ivf_range_search_partial_dev: bad arguments");
+  if (b == 0) return VERS_OK;
+  std::shared_lock<std::shared_mutex> lk(h->index);
+  if (int32_t rc = range_check(h, "vers_ivf_range_search_partial_dev", nprobe, flags, true)) return rc;
+  DeviceGuard g(h->device);
+  WsLease lease(h, true, (hipStream_t)stream);
+  if (lease.rc) return lease.rc;
+  if (int32_t rc = lease.order_on((hipStream_t)stream)) return rc;
+  HostStatusSlot slot(h);
+  RangePartial part;
+  part.keys = out_keys_dev;
+  return range_dev_locked(h, queries_dev, ldq_floats, b, radius_dev, nprobe, flags, out_lims_dev, out_ids_dev, nullptr, cap, false, out_total, (hipStream_t)stream,
+                          &part);
+}
+
+int32_t vers_ivf_range_search_exhaustive_partial_dev(vers_ivf_t* h, const float* queries_dev, uint64_t ldq_floats, uint32_t b, const float* radius_dev,
+                                                     uint32_t metric, uint32_t flags, uint64_t* out_lims_dev, uint64_t* out_keys_dev, uint64_t* out_ids_dev,
+                                                     uint64_t cap, uint64_t* out_total, void* stream) {
+  if (!h) return fail(VERS_ERR_INVALID, "null handle");
+  if (!out_total) return fail(VERS_ERR_INVALID, "vers_ivf_range_search_exhaustive_partial_dev: out_total is required");
+  *out_total = 0;
+  if (metric > VERS_METRIC_COSDIST) return fail(VERS_ERR_INVALID, "unknown metric");
+  if (b && (!queries_dev || ldq_floats < h->d || !radius_dev || !out_lims_dev || (cap && (!out_keys_dev || !out_ids_dev))))
+    return fail(VERS_ERR_INVALID, "vers_ivf_range_search_exhaustive_partial_dev: bad arguments");
+  if (b == 0) return VERS_OK;
+  std::shared_lock<std::shared_mutex> lk(h->index);
+  if (int32_t rc = range_exhaustive_check(h, "vers_ivf_range_search_exhaustive_partial_dev", flags, true)) return rc;
+  DeviceGuard g(h->device);
+  WsLease lease(h, true, (hipStream_t)stream);
+  if (lease.rc) return lease.rc;
+  if (int32_t rc = lease.order_on((hipStream_t)stream)) return rc;
+  HostStatusSlot slot(h);
+  RangePartial part;
+  part.keys = out_keys_dev;
+  return range_exhaustive_dev_locked(h, queries_dev, ldq_floats, b, radius_dev, metric, flags, out_lims_dev, out_ids_dev, nullptr, cap, false, out_total,
+                                     (hipStream_t)stream, &part);
+}
+
+int32_t vers_range_merge_dev(const uint64_t* keys_dev, const uint64_t* ids_dev, uint64_t rank_stride, const uint64_t* rank_lims_dev, uint32_t world, uint32_t b,
+                             uint32_t flags, uint64_t* out_lims_dev, uint64_t* out_ids_dev, float* out_dist_dev, void* stream) {
+  if (world == 0 || world > 65535u) return fail(VERS_ERR_INVALID, "vers_range_merge_dev: world must be 1 .. 65535");
+  if (flags & ~VERS_RANGE_WALK_ORDER) return fail(VERS_ERR_INVALID, "vers_range_merge_dev: unknown flag bits");
+  if (b && (!rank_lims_dev || !out_lims_dev || (rank_stride && (!keys_dev || !ids_dev || !out_ids_dev || !out_dist_dev))))
+    return fail(VERS_ERR_INVALID, "vers_range_merge_dev: bad arguments");
+  if (b == 0) return VERS_OK;
+  if (int32_t rc = launch_range_merge(keys_dev, ids_dev, rank_stride, rank_lims_dev, world, b, (flags & VERS_RANGE_WALK_ORDER) != 0, out_lims_dev, out_ids_dev,
+                                      out_dist_dev, (hipStream_t)stream))
+    return fail(rc, "vers_range_merge_dev: launch failed");
+  return VERS_OK;
+}
+
+// local count -> exchange 1 (counts + status: the agreement round) -> local fill into the send buffer -> exchange 2 (keys | ids, padded to
+// the largest rank) -> merge.  exhaustive_metric < 0: the probed lists.
+static int32_t range_sharded_common(vers_ivf_t* h, const vers_comm_t* comm, const float* queries_dev, uint64_t ldq_floats, uint32_t b, const float* radius_dev,
+                                    uint32_t nprobe, int exhaustive_metric, uint32_t flags, uint64_t* out_lims_dev, uint64_t* out_ids_dev, float* out_dist_dev,
+                                    uint64_t cap, uint64_t* out_total, void* stream) {
+  const std::string who = exhaustive_metric >= 0 ? "vers_ivf_range_search_exhaustive_sharded_dev" : "vers_ivf_range_search_sharded_dev";
+  if (!h) return fail(VERS_ERR_INVALID, "null handle");
+  if (!out_total) return fail(VERS_ERR_INVALID, who + ": out_total is required");
+  *out_total = 0;
+  if (exhaustive_metric > (int)VERS_METRIC_COSDIST) return fail(VERS_ERR_INVALID, "unknown metric");
+  if (b && (!queries_dev || ldq_floats < h->d || !radius_dev || !out_lims_dev || (cap && (!out_ids_dev || !out_dist_dev)))) return fail(VERS_ERR_INVALID, who + ": bad arguments");
+  if (comm && (comm->world == 0 || comm->rank >= comm->world || comm->world > 65535u || !comm->all_gather)) return fail(VERS_ERR_INVALID, who + ": incomplete vers_comm_t");
+  if (b == 0) return VERS_OK;
+  std::shared_lock<std::shared_mutex> lk(h->index);
+  const uint32_t world = comm ? comm->world : 1u;
+  if (world != h->world || (comm && world > 1 && comm->rank != h->rank))
+    return fail(VERS_ERR_INVALID, who + ": the handle is sharded as rank " + std::to_string(h->rank) + " of " + std::to_string(h->world) + ", the communicator says otherwise");
+  if (int32_t rc = exhaustive_metric >= 0 ? range_exhaustive_check(h, who.c_str(), flags, true) : range_check(h, who.c_str(), nprobe, flags, true)) return rc;
+  DeviceGuard gd(h->device);
+  hipStream_t st = (hipStream_t)stream;
+  WsLease lease(h, true, st);
+  if (lease.rc) return lease.rc;
+  if (int32_t rc = lease.order_on(st)) return rc;
+  HostStatusSlot slot(h);
+  const uint32_t me = comm ? comm->rank : 0u;
+  const size_t nw = (size_t)b + 1;  // words of exchange 1 per rank: b counts | the status
+  std::vector<uint64_t> all((size_t)world * nw, 0), rank_lims((size_t)world * nw, 0), lims(nw, 0);
+  uint64_t g_total = 0, t_max = 0;
+  bool agreed = false;
+  // Exchange 1.  EVERY way out of the local count leads here exactly once -- a rank that failed (a NaN distance, a NaN radius, scratch that
+  // did not fit, the injected failure) enters with zero counts and its status, so that nobody waits for it and everybody leaves with the
+  // same verdict: the first failing rank's status, in rank order.
+  auto exchange1 = [&](int32_t local_rc, bool have_lims) -> int32_t {
+    agreed = true;
+    const std::string local_why = local_rc ? std::string(vers_last_error()) : std::string();
+    uint64_t* mine = all.data() + (size_t)me * nw;
+    if (!local_rc && have_lims) {
+      if (hipMemcpy(lims.data(), W->rg_lims.p, nw * sizeof(uint64_t), hipMemcpyDeviceToHost) != hipSuccess) local_rc = fail(VERS_ERR_HIP, who + ": reading the local limits failed");
+      else
+        for (uint32_t q = 0; q < b; ++q) mine[q] = lims[q + 1] - lims[q];
+    }
+    mine[b] = (uint64_t)(uint32_t)local_rc;
+    if (comm) {
+      int32_t rc = W->g_send.reserve(nw * sizeof(uint64_t));
+      if (!rc) rc = W->g_recv.reserve((size_t)world * nw * sizeof(uint64_t));
+      if (!rc && hipMemcpy(W->g_send.p, mine, nw * sizeof(uint64_t), hipMemcpyHostToDevice) != hipSuccess) rc = VERS_ERR_HIP;
+      if (!rc && hipStreamSynchronize(st) != hipSuccess) rc = VERS_ERR_HIP;
+      if (rc)  // (nothing the library can send: the host aborts the group on a non-zero return, as for the sharded build)
+        return local_rc ? local_rc : fail(rc, who + ": the exchange buffers could not be set up -- this rank cannot join the agreement round; abort the group");
+      if (int32_t crc = comm->all_gather(comm->ctx, W->g_send.p, W->g_recv.p, nw * sizeof(uint64_t)))
+        return local_rc ? local_rc : fail(VERS_ERR_COMM, "vers_comm_t::all_gather reported failure (status " + std::to_string(crc) + ")");
+      if (hipMemcpy(all.data(), W->g_recv.p, (size_t)world * nw * sizeof(uint64_t), hipMemcpyDeviceToHost) != hipSuccess)
+        return local_rc ? local_rc : fail(VERS_ERR_HIP, who + ": reading the gathered counts failed");
+    }
+    for (uint32_t r = 0; r < world; ++r) {
+      const int32_t s = (int32_t)(uint32_t)all[(size_t)r * nw + b];
+      if (s == 0) continue;
+      if (r == me) return fail(s, local_why);
+      return fail(s, who + ": rank " + std::to_string(r) + " reported status " + std::to_string(s) + "; no rank wrote a result");
+    }
+    for (uint32_t r = 0; r < world; ++r) {
+      uint64_t* rl = rank_lims.data() + (size_t)r * nw;
+      rl[0] = 0;
+      for (uint32_t q = 0; q < b; ++q) rl[q + 1] = rl[q] + all[(size_t)r * nw + q];
+      t_max = std::max(t_max, rl[b]);
+    }
+    for (uint32_t q = 0; q <= b; ++q) {
+      uint64_t sum = 0;
+      for (uint32_t r = 0; r < world; ++r) sum += rank_lims[(size_t)r * nw + q];
+      lims[q] = sum;
+    }
+    g_total = lims[b];
+    if (g_total > 0xFFFFFFFFull) return fail(VERS_ERR_INVALID, who + ": more than 2^32 - 1 results in one call; split the batch");
+    VERS_HIP_TRY(hipMemcpy(out_lims_dev, lims.data(), nw * sizeof(uint64_t), hipMemcpyHostToDevice));
+    *out_total = g_total;
+    return VERS_OK;
+  };
+  uint64_t local_total = 0;
+  bool gather = false;  // 0 < global total <= cap: exchange 2 and the merge follow
+  RangePartial part;
+  part.decide = [&](uint64_t total, uint64_t*& keys, uint64_t*& ids, bool& go) -> int32_t {
+    local_total = total;
+    int32_t lrc = VERS_OK;
+    if (total != 0 && total <= cap) {  // the fill's staging BEFORE the agreement: scratch that does not fit is a status the peers learn
+      lrc = W->rg_stage.reserve(2 * (size_t)total * sizeof(uint64_t));
+      if (!lrc && !(flags & VERS_RANGE_WALK_ORDER))
+        lrc = W->rg_tmp.reserve(exhaustive_metric >= 0 ? range_sort_keys_temp_bytes((uint32_t)total, b) : range_sort_temp_bytes((uint32_t)total, b));
+    }
+    if (int32_t rc = exchange1(lrc, true)) return rc;
+    go = false;
+    gather = g_total != 0 && g_total <= cap;
+    if (!gather) return VERS_OK;
+    // (past the agreement a local failure has no round left to be told in: the host aborts the group on a non-zero return)
+    if (int32_t rc = W->g_recv.reserve((size_t)world * 2 * t_max * sizeof(uint64_t))) return rc;
+    if (comm)
+      if (int32_t rc = W->g_send.reserve(2 * (size_t)t_max * sizeof(uint64_t))) return rc;
+    uint64_t* mine = comm ? W->g_send.as<uint64_t>() : W->g_recv.as<uint64_t>();
+    VERS_HIP_TRY(hipMemsetAsync(mine, 0xFF, 2 * (size_t)t_max * sizeof(uint64_t), st));  // the padding behind a shorter rank: defined bytes, never read by the merge
+    keys = mine; ids = mine + t_max;
+    go = total != 0;
+    return VERS_OK;
+  };
+  int32_t rc = VERS_OK;
+  if (test_fail_sharded_ref().load() > 0 && test_fail_sharded_ref().fetch_sub(1) > 0) rc = fail(VERS_ERR_HIP, who + ": injected local failure (test hook)");
+  if (!rc) {
+    rc = W->rg_lims.reserve(nw * sizeof(uint64_t));
+    if (!rc)
+      rc = exhaustive_metric >= 0 ? range_exhaustive_dev_locked(h, queries_dev, ldq_floats, b, radius_dev, (uint32_t)exhaustive_metric, flags, W->rg_lims.as<uint64_t>(),
+                                                                nullptr, nullptr, cap, false, &local_total, st, &part)
+                                  : range_dev_locked(h, queries_dev, ldq_floats, b, radius_dev, nprobe, flags, W->rg_lims.as<uint64_t>(), nullptr, nullptr, cap, false,
+                                                     &local_total, st, &part);
+  }
+  if (!agreed) {  // the local count did not get as far as the agreement: enter it with the failure
+    const int32_t arc = exchange1(rc ? rc : fail(VERS_ERR_HIP, who + ": the local count ended without a verdict"), false);
+    *out_total = 0;
+    return arc;
+  }
+  if (rc) { *out_total = 0; return rc; }
+  *out_total = g_total;  // (the local call left its own total there)
+  if (!gather) return VERS_OK;
+  VERS_HIP_TRY(hipStreamSynchronize(st));  // (the callbacks are synchronous: the partial is in place)
+  if (comm) {
+    if (int32_t crc = comm->all_gather(comm->ctx, W->g_send.p, W->g_recv.p, 2 * t_max * sizeof(uint64_t)))
+      return fail(VERS_ERR_COMM, "vers_comm_t::all_gather reported failure (status " + std::to_string(crc) + ")");
+  }
+  if (int32_t rrc = W->rg_rlims.reserve((size_t)world * nw * sizeof(uint64_t))) return rrc;
+  VERS_HIP_TRY(hipMemcpy(W->rg_rlims.p, rank_lims.data(), (size_t)world * nw * sizeof(uint64_t), hipMemcpyHostToDevice));
+  if (int32_t mrc = launch_range_merge(W->g_recv.as<uint64_t>(), W->g_recv.as<uint64_t>() + t_max, 2 * t_max, W->rg_rlims.as<uint64_t>(), world, b,
+                                       (flags & VERS_RANGE_WALK_ORDER) != 0, out_lims_dev, out_ids_dev, out_dist_dev, st))
+    return fail(mrc, who + ": the merge could not be launched");
+  VERS_HIP_TRY(hipStreamSynchronize(st));
+  return VERS_OK;
+}
+
+int32_t vers_ivf_range_search_sharded_dev(vers_ivf_t* h, const vers_comm_t* comm, const float* queries_dev, uint64_t ldq_floats, uint32_t b, const float* radius_dev,
+                                          uint32_t nprobe, uint32_t flags, uint64_t* out_lims_dev, uint64_t* out_ids_dev, float* out_dist_dev, uint64_t cap,
+                                          uint64_t* out_total, void* stream) {
+  return range_sharded_common(h, comm, queries_dev, ldq_floats, b, radius_dev, nprobe, -1, flags, out_lims_dev, out_ids_dev, out_dist_dev, cap, out_total, stream);
+}
+
+int32_t vers_ivf_range_search_exhaustive_sharded_dev(vers_ivf_t* h, const vers_comm_t* comm, const float* queries_dev, uint64_t ldq_floats, uint32_t b,
+                                                     const float* radius_dev, uint32_t metric, uint32_t flags, uint64_t* out_lims_dev, uint64_t* out_ids_dev,
+                                                     float* out_dist_dev, uint64_t cap, uint64_t* out_total, void* stream) {
+  if (metric > VERS_METRIC_COSDIST) return fail(VERS_ERR_INVALID, "unknown metric");
+  return range_sharded_common(h, comm, queries_dev, ldq_floats, b, radius_dev, 1, (int)metric, flags, out_lims_dev, out_ids_dev, out_dist_dev, cap, out_total, stream);
 }
 
 int32_t vers_range_phases(double* out8, int32_t reset) {

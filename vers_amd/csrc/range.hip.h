@@ -29,6 +29,8 @@
 //       kRangeRowsFlat    a row of the flat corpus: vec id = row number, every row below n is live, no id load at all
 //     Stored / Flat: the sort key is make_key(dist, vec id) -- utils::search_exhaustive's stable order -- so the sorted keys alone
 //     decode to (id, distance) and no id array is staged.
+// On a handle sharded by cluster the same passes run over the lists (rows) the rank stores and end in (key, id) pairs; the cross-rank merge
+// is range_merge.hip.h.
 #pragma once
 #include "scan.hip.h"
 
@@ -44,9 +46,10 @@ struct RangeParams {
   uint32_t* counts;         // [b * P * S_max]: hits per slot = pair * S_max + segment (zeroed before the count pass)
   const uint64_t* base;     // FILL: exclusive prefix of counts
   const uint32_t* row_ids;  // storage row -> vec id
-  uint64_t* out_keys;       // FILL, sorted order: make_key(dist, seq) staging; nullptr = walk order (out_dist gets the distance itself)
+  uint64_t* out_keys;       // FILL, sorted order: make_key(dist, seq) staging; nullptr = walk order (out_dist gets the distance itself).
+                            // A rank's partial of a sharded search (RangePartial, ivf_search.hip) keeps the keys in walk order too: the caller's array
   uint64_t* out_ids;        // FILL: ids (staging in sorted order, the caller's array in walk order)
-  float* out_dist;          // FILL, walk order
+  float* out_dist;          // FILL, walk order without keys
   uint32_t* next_quad;      // batched kernels: dynamic quad hand-out counter (zeroed per launch) or nullptr
 };
 

@@ -449,6 +449,53 @@ class IVFFlatIndex:
         check(lib().vers_topk_merge_dev(_vp(keys_ptr), _vp(ids_ptr), rank_stride, world, b, top_k, nprobe, _vp(out_ids_ptr),
                                         _vp(out_dist_ptr), _vp(out_cnt_ptr), _vp(stream)))
 
+    # -- range search on handles sharded by cluster ------------------------------------------------------------
+    def range_search_partial_dev(self, q_ptr: int, ldq: int, b: int, radius_ptr: int, nprobe: int, flags: int, lims_ptr: int, keys_ptr: int,
+                                 ids_ptr: int, cap: int, stream: int = 0, exhaustive_metric=None) -> int:
+        """This rank's part of a range search as CSR of (key, vec id) pairs for merge_range_partials_dev
+        (vers_ivf_range_search_partial_dev; exhaustive_metric given: vers_ivf_range_search_exhaustive_partial_dev over this rank's rows,
+        `nprobe` unused).  Synchronous.  Returns the LOCAL total: keys / ids were written only when it is <= cap."""
+        total = C.c_uint64(0)
+        if exhaustive_metric is None:
+            check(lib().vers_ivf_range_search_partial_dev(self._h, _vp(q_ptr), ldq, b, _vp(radius_ptr), nprobe, flags, _vp(lims_ptr),
+                                                          _vp(keys_ptr) if keys_ptr else None, _vp(ids_ptr) if ids_ptr else None, cap,
+                                                          C.byref(total), _vp(stream)))
+        else:
+            check(lib().vers_ivf_range_search_exhaustive_partial_dev(self._h, _vp(q_ptr), ldq, b, _vp(radius_ptr), exhaustive_metric, flags,
+                                                                     _vp(lims_ptr), _vp(keys_ptr) if keys_ptr else None,
+                                                                     _vp(ids_ptr) if ids_ptr else None, cap, C.byref(total), _vp(stream)))
+        return int(total.value)
+
+    @staticmethod
+    def merge_range_partials_dev(keys_ptr: int, ids_ptr: int, rank_stride: int, rank_lims_ptr: int, world: int, b: int, flags: int,
+                                 out_lims_ptr: int, out_ids_ptr: int, out_dist_ptr: int, stream: int = 0):
+        """vers_range_merge_dev: `world` partials (rank r's arrays at r * rank_stride elements, its limits at rank_lims[r]) -> the CSR result;
+        queued on `stream`, not synchronised."""
+        check(lib().vers_range_merge_dev(_vp(keys_ptr) if keys_ptr else None, _vp(ids_ptr) if ids_ptr else None, rank_stride, _vp(rank_lims_ptr),
+                                         world, b, flags, _vp(out_lims_ptr), _vp(out_ids_ptr) if out_ids_ptr else None,
+                                         _vp(out_dist_ptr) if out_dist_ptr else None, _vp(stream)))
+
+    def range_search_sharded_dev(self, comm, q_ptr: int, ldq: int, b: int, radius_ptr: int, nprobe: int, flags: int, lims_ptr: int,
+                                 ids_ptr: int, dist_ptr: int, cap: int, stream: int = 0) -> int:
+        """Range search over lists sharded by cluster, end to end (vers_ivf_range_search_sharded_dev): every rank calls with the same
+        arguments and the same cap; comm: the vers_amd.dist.TorchComm of the sharded handle (None on an unsharded one).  Returns the
+        GLOBAL total: ids / distances were written only when it is <= cap."""
+        total = C.c_uint64(0)
+        check(lib().vers_ivf_range_search_sharded_dev(self._h, comm.ptr() if comm is not None else None, _vp(q_ptr), ldq, b, _vp(radius_ptr),
+                                                      nprobe, flags, _vp(lims_ptr), _vp(ids_ptr) if ids_ptr else None,
+                                                      _vp(dist_ptr) if dist_ptr else None, cap, C.byref(total), _vp(stream)))
+        return int(total.value)
+
+    def range_search_exhaustive_sharded_dev(self, comm, q_ptr: int, ldq: int, b: int, radius_ptr: int, metric: int, flags: int, lims_ptr: int,
+                                            ids_ptr: int, dist_ptr: int, cap: int, stream: int = 0) -> int:
+        """The exhaustive twin of range_search_sharded_dev (vers_ivf_range_search_exhaustive_sharded_dev); default order only."""
+        total = C.c_uint64(0)
+        check(lib().vers_ivf_range_search_exhaustive_sharded_dev(self._h, comm.ptr() if comm is not None else None, _vp(q_ptr), ldq, b,
+                                                                 _vp(radius_ptr), metric, flags, _vp(lims_ptr),
+                                                                 _vp(ids_ptr) if ids_ptr else None, _vp(dist_ptr) if dist_ptr else None, cap,
+                                                                 C.byref(total), _vp(stream)))
+        return int(total.value)
+
     def poll(self, stream: int = 0):
         check(lib().vers_ivf_poll(self._h, _vp(stream)))
 
