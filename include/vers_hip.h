@@ -465,6 +465,52 @@ int32_t vers_ivf_range_search_exhaustive(vers_ivf_t* h, const float* queries, ui
 int32_t vers_ivf_range_search_exhaustive_dev(vers_ivf_t* h, const float* queries_dev, uint64_t ldq_floats, uint32_t b, const float* radius_dev,
                                              uint32_t metric, uint32_t flags, uint64_t* out_lims_dev, uint64_t* out_ids_dev,
                                              float* out_dist_dev, uint64_t cap, uint64_t* out_total /* host */, void* stream);
+/* FILTERED top-k search (extension; the reference has search_approximate only): the top_k nearest among the vec ids the caller is allowed
+ * to see -- a tenant, a time window, an ACL, a category.  A filter is a VIRTUAL REMOVAL: with A the set of allowed vec ids, a filtered call
+ * returns, bit for bit (ids, order, distance bits, out_count), what the unfiltered call of the same mode returns on an index from which every
+ * vec id not in A has been removed by vers_ivf_remove_batch -- `ids[c].retain(|v| A.contains(v))` for the duration of the call.  The index
+ * itself is not touched.
+ *   bitmap   : allowed_bits holds u64 words, one bitmap per call, shared by the batch: bit (v & 63) of word (v >> 6) set = vec id v is
+ *              allowed.  n_bits = the number of valid bits: ids >= n_bits are not allowed, bits of the last word at or beyond n_bits are
+ *              ignored and may hold anything.  n_bits may be smaller or larger than n; bits of ids that were removed or are >= n select
+ *              nothing.  n_bits == 0 (allowed_bits may then be NULL) is the empty filter.
+ *   probed   : vers_ivf_search_filtered, nprobe >= 1.  The lists are ranked exactly as without a filter (the centroids do not depend on it;
+ *              lists the filter empties still count as probed); results are the allowed rows of the min(nprobe, k) nearest lists in the one
+ *              global stable order ascending (distance, probe rank, list position); out_count[q] = min(top_k, allowed rows in q's probed
+ *              lists) -- it may be 0, which is not an error.
+ *   exhaustive: vers_ivf_search_exhaustive_filtered.  The allowed rows that are in a list NOW, ascending (distance, vec id);
+ *              out_count[q] = min(top_k, allowed live rows).  An index without centroids (a streamed upload in progress included): counts 0.
+ *   layout   : out_ids / out_dist [b * top_k], out_count [b], as vers_ivf_search / vers_ivf_search_exhaustive; entries beyond a query's
+ *              count are unspecified (host-pointer calls: zeros).  Any top_k and any nprobe >= 1; results beyond 64 ranks come 64 per pass.
+ *   scan     : rows outside A are NOT SCANNED: the bitmap becomes one u64 per 64-row storage tile (one pass over the row ids, every call),
+ *              and a tile without an allowed row is never loaded.  A NaN distance on a disallowed row is therefore not an error; on an
+ *              allowed scanned row it is VERS_ERR_NAN, as in every search.  The scan is the exact ordered f32 chain over the f32 rows
+ *              (like range search): no matrix-core / fp16-shadow pre-filter.
+ *   handle   : the way searches take it -- shared, one leased workspace per stream, excluded by add / remove / compact.  _dev calls enqueue
+ *              on `stream` and return without synchronising; errors found on the device latch for vers_ivf_poll, exactly as
+ *              vers_ivf_search_dev.  The host-pointer calls stage the bitmap through the workspace and synchronise.  A filtered call neither
+ *              consumes nor starts a vers_ivf_coarse_ahead_dev preparation.
+ *   errors   : VERS_ERR_INVALID n_bits > 0 with a NULL bitmap; nprobe == 0 on the probed call (the reference's spill walk depends on the
+ *              filtered list lengths: OUT OF SCOPE); metric > VERS_METRIC_COSDIST on the exhaustive call; a handle sharded by cluster
+ *              (world > 1: OUT OF SCOPE).  VERS_ERR_INSUFFICIENT no centroids on the probed call, as in vers_ivf_search.
+ *   out of scope: nprobe == 0, sharded handles, a filter per query, the flat corpus handle, a prepared (reusable) filter object.
+ * vers_ivf_filter_stats (measurement hook; functions of the data and the plan alone): out4 = the most recent filtered call of the handle,
+ * out4_total = over the handle's life; either may be NULL.  [0] tile visits the plan implied (64-row tiles of every work item, counted once
+ * per item and scan pass), [1] tile visits actually loaded, [2] items skipped before their first load, [3] allowed storage rows (popcount
+ * of the tile mask).  Bytes not read = ([0] - [1]) * 64 * ld * 4.  In the scan-timing ring (vers_ivf_scan_times) a filtered call leaves
+ * the mask kernel's record, then one record per scan pass. */
+int32_t vers_ivf_search_filtered(vers_ivf_t* h, const float* queries, uint64_t q_stride_bytes, uint32_t b, uint32_t top_k, uint32_t nprobe,
+                                 const uint64_t* allowed_bits, uint64_t n_bits, uint64_t* out_ids, float* out_dist, uint32_t* out_count);
+int32_t vers_ivf_search_filtered_dev(vers_ivf_t* h, const float* queries_dev, uint64_t ldq_floats, uint32_t b, uint32_t top_k, uint32_t nprobe,
+                                     const uint64_t* allowed_bits_dev, uint64_t n_bits, uint64_t* out_ids_dev, float* out_dist_dev,
+                                     uint32_t* out_count_dev, void* stream);
+int32_t vers_ivf_search_exhaustive_filtered(vers_ivf_t* h, const float* queries, uint64_t q_stride_bytes, uint32_t b, uint32_t top_k,
+                                            uint32_t metric, const uint64_t* allowed_bits, uint64_t n_bits, uint64_t* out_ids, float* out_dist,
+                                            uint32_t* out_count);
+int32_t vers_ivf_search_exhaustive_filtered_dev(vers_ivf_t* h, const float* queries_dev, uint64_t ldq_floats, uint32_t b, uint32_t top_k,
+                                                uint32_t metric, const uint64_t* allowed_bits_dev, uint64_t n_bits, uint64_t* out_ids_dev,
+                                                float* out_dist_dev, uint32_t* out_count_dev, void* stream);
+int32_t vers_ivf_filter_stats(vers_ivf_t* h, uint64_t* out4, uint64_t* out4_total);
 /* SHARDED range search: the range calls on handles sharded by cluster (vers_ivf_set_shard / vers_ivf_build_sharded_dev), where the calls
  * above return VERS_ERR_INVALID.  The result is the unsharded index's, bit for bit -- limits, ids, order, distance bits.  Three layers:
  *

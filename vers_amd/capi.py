@@ -127,6 +127,12 @@ SIGNATURES = {
                                                       C.POINTER(C.c_uint64), _vp]),
     "vers_ivf_range_search_exhaustive_sharded_dev": (C.c_int32, [_vp, _vp, _vp, C.c_uint64, C.c_uint32, _vp, C.c_uint32, C.c_uint32, _vp, _vp, _vp,
                                                                  C.c_uint64, C.POINTER(C.c_uint64), _vp]),
+    "vers_ivf_search_filtered": (C.c_int32, [_vp, _vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, _vp, C.c_uint64, _vp, _vp, _vp]),
+    "vers_ivf_search_filtered_dev": (C.c_int32, [_vp, _vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, _vp, C.c_uint64, _vp, _vp, _vp, _vp]),
+    "vers_ivf_search_exhaustive_filtered": (C.c_int32, [_vp, _vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, _vp, C.c_uint64, _vp, _vp, _vp]),
+    "vers_ivf_search_exhaustive_filtered_dev": (C.c_int32, [_vp, _vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, _vp, C.c_uint64, _vp, _vp, _vp,
+                                                            _vp]),
+    "vers_ivf_filter_stats": (C.c_int32, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "vers_kmeans_update": (C.c_int32, [C.c_int32, _vp, C.c_uint64, C.c_uint64, _vp, C.c_uint64, C.c_uint32, _vp]),
     "vers_kmeans_cost": (C.c_int32, [C.c_int32, _vp, C.c_uint64, C.c_uint64, _vp, C.c_uint64, C.c_uint64, _vp, C.c_uint32,
                                      C.POINTER(C.c_float)]),
@@ -197,6 +203,23 @@ def range_radii(radius, b: int) -> np.ndarray:
     if np.ndim(radius):
         return np.ascontiguousarray(np.broadcast_to(np.asarray(radius, dtype=np.float32).reshape(-1), (b,)))
     return np.full(b, radius, dtype=np.float32)
+
+
+def allowed_bitmap(x, n_bits: int) -> np.ndarray:
+    """The filter of a filtered search as the C ABI takes it: u64 words, bit (v & 63) of word (v >> 6) set = vec id v is allowed,
+    ceil(n_bits / 64) words (at least one, so that the array has an address).  x: a bool array (x[v] = v is allowed) or an integer
+    array of allowed vec ids, any order, repeats allowed.  Ids / positions at or beyond n_bits are dropped: they are not allowed."""
+    n_bits = int(n_bits)
+    a = np.asarray(x)
+    if a.dtype == np.bool_:
+        ids = np.flatnonzero(a.reshape(-1)).astype(np.uint64)
+    else:
+        ids = np.asarray(a, dtype=np.uint64).reshape(-1)
+    ids = np.unique(ids[ids < np.uint64(n_bits)])
+    words = np.zeros(max(1, (n_bits + 63) // 64), dtype=np.uint64)
+    if ids.size:
+        np.bitwise_or.at(words, (ids >> np.uint64(6)).astype(np.int64), np.uint64(1) << (ids & np.uint64(63)))
+    return words
 
 
 class FlatCorpus:

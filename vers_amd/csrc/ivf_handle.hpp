@@ -46,6 +46,10 @@ struct SearchWs {
   // range search (ivf_search.hip: range_dev_locked): hits per (query, probe, segment) slot | their exclusive prefix | radii, CSR limits and
   // results of a host-pointer call | [0..1] total, [2] status, [3] NaN-radius flag | (key, id) staging of the sorted order + rocPRIM's temporary
   DevBuf rg_counts, rg_base, rg_rad, rg_lims, rg_misc, rg_stage, rg_tmp;
+  // filtered search (filter.hip.h): one u64 per 64-row storage tile | the bitmap of a host-pointer call | the call's four counters, then a slot of four
+  // words per wave a filtered scan can launch (summed into the counters by filter_stats_fold_kernel)
+  DevBuf flt_mask, flt_bits, flt_stats;
+  bool no_ahead = false;  // the plan of a filtered call neither consumes a look-ahead slot nor touches a pending request (plan_search)
   DevBuf rg_rlims;  // sharded range search: every rank's CSR limits [world][b + 1] (range_merge.hip.h); the gather itself goes through g_send / g_recv
   uint32_t* rg_pin = nullptr;  // pinned [4]: where a range call reads its total, status word and NaN-radius flag after its first synchronisation
   hipEvent_t rg_ev[6] = {};  // phase boundaries of the most recent range call (vers_range_phases), created on first use
@@ -211,6 +215,9 @@ struct vers_ivf {
   } rm;
   // matrix-core list scan (prescan.hip.h): |x|^2 per storage row, [0] max |x|^2 bits, [1] certificate failures (running)
   DevBuf xnorm, pre_misc;
+  DevBuf flt_total;  // u64 [4] vers_ivf_filter_stats over the handle's life (filter_stats_fold_kernel adds every call's counters); allocated under flt_mu
+  std::mutex flt_mu;
+  SearchWs* flt_last = nullptr;  // the workspace of the most recent filtered call (guarded by pool_mu)
   DevBuf prune_ctr;  // u64 [3] steps executed | steps without math | tiles abandoned by the list scan's early abandon, over the handle's life
   // fp16 shadow of the rows for the matrix-core pre-selection (+50 % corpus memory; VERS_SHADOW=0 or a failed
   // allocation: the f32 rows feed it).  The wider certificate window makes it sensitive to data with many near-ties:

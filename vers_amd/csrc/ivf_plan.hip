@@ -633,9 +633,10 @@ int32_t plan_search(vers_ivf* h, const float* q_dev, uint64_t ldq_in, uint32_t b
   const float* qp = nullptr;
   const uint64_t* probe = nullptr;
   SearchWs::CoarseAhead* took = nullptr;
-  for (auto& a : W->ahead)
-    if (a.valid && !ref_mode && a.q_dev == q_dev && a.ldq_in == ldq_in && a.b == b && a.P == P) took = &a;
-  {
+  if (!W->no_ahead)
+    for (auto& a : W->ahead)
+      if (a.valid && !ref_mode && a.q_dev == q_dev && a.ldq_in == ldq_in && a.b == b && a.P == P) took = &a;
+  if (!W->no_ahead) {  // (a filtered call leaves a prepared batch to the unfiltered call it was made for)
     std::lock_guard<std::mutex> lk(h->pool_mu);
     if (h->pending.set && h->pending.q_dev == q_dev && h->pending.ldq_in == ldq_in && h->pending.b == b) h->pending.set = false;  // this very batch: computed inline below
   }

@@ -15,6 +15,7 @@
 #include "finish_wide.hip.h"
 #include "range.hip.h"
 #include "range_merge.hip.h"
+#include "filter.hip.h"
 
 namespace vers {
 
@@ -573,6 +574,233 @@ int32_t exhaustive_dev_locked(vers_ivf* h, const float* q_dev, uint64_t ldq_in, 
                        out_dist, out_count, top_k > (uint32_t)kMaxTopK ? W->lower.as<uint64_t>() : (uint64_t*)nullptr);
     VERS_HIP_TRY(hipGetLastError());
   }
+  return VERS_OK;
+}
+
+// ---- filtered top-k search (filter.hip.h): a bitmap of allowed vec ids per call = a virtual removal of the others -------------------
+// The tile mask of the call over `n_rows` storage rows + its zeroed counters.  The mask kernel is bracketed by a record of the scan-timing
+// ring (vers_ivf_scan_times: a filtered call leaves the mask kernel's record, then one per scan pass).
+static size_t filter_wave_slots(const vers_ivf* h) { return (size_t)h->n_cu * 3 * kWavesPerBlock; }
+static int32_t filter_begin(vers_ivf* h, const uint64_t* bits_dev, uint64_t n_bits, uint64_t n_rows, hipStream_t st, FilterParams& f) {
+  { const int ev = scan_events_ref().load(); W->ev_on = ev == 1 || ev == 2; }
+  const uint64_t n_tiles = (n_rows + kWave - 1) / kWave;
+  if (int32_t rc = W->flt_mask.reserve(std::max<size_t>(1, n_tiles) * sizeof(uint64_t))) return rc;
+  // the call's four counters | a slot of four words per wave a filtered scan can launch (filter_scan_kernel: at most 3 blocks per CU)
+  const size_t stat_words = kFltStats + filter_wave_slots(h) * 4;
+  if (int32_t rc = W->flt_stats.reserve(stat_words * sizeof(unsigned long long))) return rc;
+  {
+    std::lock_guard<std::mutex> lk(h->flt_mu);
+    if (!h->flt_total.p) {
+      if (int32_t rc = h->flt_total.reserve(kFltStats * sizeof(unsigned long long))) return rc;
+      VERS_HIP_TRY(hipMemset(h->flt_total.p, 0, kFltStats * sizeof(unsigned long long)));
+    }
+  }
+  VERS_HIP_TRY(hipMemsetAsync(W->flt_stats.p, 0, stat_words * sizeof(unsigned long long), st));
+  f.tile_mask = W->flt_mask.as<uint64_t>();
+  f.stats = W->flt_stats.as<unsigned long long>();
+  f.wave_slots = f.stats + kFltStats;
+  const uint32_t slot = (uint32_t)(W->ev_count % SearchWs::kEvRing);
+  if (W->ev_on) VERS_HIP_TRY(hipEventRecord(W->ev0[slot], st));
+  if (n_bits == 0 || n_tiles == 0) {  // the empty filter: nothing is allowed
+    VERS_HIP_TRY(hipMemsetAsync(W->flt_mask.p, 0, std::max<size_t>(1, n_tiles) * sizeof(uint64_t), st));
+  } else {
+    const uint64_t blocks = std::min<uint64_t>((uint64_t)h->n_cu, (n_tiles + kFltMaskThreads / kWave - 1) / (kFltMaskThreads / kWave));
+    hipLaunchKernelGGL(filter_tile_mask_kernel, dim3((unsigned)blocks), dim3(kFltMaskThreads), 0, st, (const uint32_t*)h->row_ids.as<uint32_t>(), n_rows, bits_dev, n_bits,
+                       W->flt_mask.as<uint64_t>(), f.stats);
+    VERS_HIP_TRY(hipGetLastError());
+  }
+  if (W->ev_on) {
+    VERS_HIP_TRY(hipEventRecord(W->ev1[slot], st));
+    W->ev_count += 1;
+  }
+  return VERS_OK;
+}
+
+// the call's counters into the handle's totals, and the workspace noted for vers_ivf_filter_stats
+static int32_t filter_end(vers_ivf* h, hipStream_t st) {
+  hipLaunchKernelGGL(filter_stats_fold_kernel, dim3(1), dim3(kFltFoldThreads), 0, st, (const unsigned long long*)(W->flt_stats.as<unsigned long long>() + kFltStats),
+                     (uint32_t)filter_wave_slots(h), W->flt_stats.as<unsigned long long>(), h->flt_total.as<unsigned long long>());
+  VERS_HIP_TRY(hipGetLastError());
+  std::lock_guard<std::mutex> lk(h->pool_mu);
+  h->flt_last = W;
+  return VERS_OK;
+}
+
+// one pass of the filtered scan over the planned items; launch bounds and timing ring as launch_ivf_scan's
+template <int QG>
+int32_t launch_filter_ivf_scan(vers_ivf* h, const IvfSrc<QG>& src, uint32_t items_bound, const FilterParams& f, hipStream_t st, const uint64_t* lower) {
+  ScanParams p;
+  p.ld = h->ld;
+  p.n_chunks = h->ld / kChunk;
+  p.k = src.k_keep;
+  p.status = W->st_word();
+  p.debug = 0;
+  p.stamps = nullptr;
+  p.bounds = QG != 1 ? W->partials.as<uint64_t>() + W->ivf_bounds_off : nullptr;
+  p.lower = lower;
+  p.next_quad = nullptr;
+  if (QG != 1) {
+    if (int32_t rc = W->quad_counter.reserve(16)) return rc;
+    VERS_HIP_TRY(hipMemsetAsync(W->quad_counter.p, 0, 16, st));
+    p.next_quad = W->quad_counter.as<uint32_t>();
+  }
+  const size_t lds = scan_lds_bytes(QG, h->ld);
+  if (int32_t rc = h->metric ? scan_prepare_launch(filter_scan_kernel<QG, 1, IvfSrc<QG>>, lds) : scan_prepare_launch(filter_scan_kernel<QG, 0, IvfSrc<QG>>, lds)) return rc;
+  uint32_t blocks = (items_bound + kWavesPerBlock - 1) / kWavesPerBlock;
+  const uint32_t max_blocks = (uint32_t)h->n_cu * scan_blocks_per_cu(QG, h->ld);
+  if (blocks > max_blocks) blocks = max_blocks;
+  blocks = std::min<uint32_t>(blocks, (uint32_t)(filter_wave_slots(h) / kWavesPerBlock));  // (a counter slot per launched wave: filter_begin)
+  if (blocks == 0) blocks = 1;
+  const uint32_t slot = (uint32_t)(W->ev_count % SearchWs::kEvRing);
+  if (W->ev_on) VERS_HIP_TRY(hipEventRecord(W->ev0[slot], st));
+  if (h->metric) hipLaunchKernelGGL((filter_scan_kernel<QG, 1, IvfSrc<QG>>), dim3(blocks), dim3(kWave * kWavesPerBlock), lds, st, src, p, f);
+  else hipLaunchKernelGGL((filter_scan_kernel<QG, 0, IvfSrc<QG>>), dim3(blocks), dim3(kWave * kWavesPerBlock), lds, st, src, p, f);
+  VERS_HIP_TRY(hipGetLastError());
+  if (W->ev_on) {
+    VERS_HIP_TRY(hipEventRecord(W->ev1[slot], st));
+    W->ev_count += 1;
+  }
+  return VERS_OK;
+}
+
+// Filtered search over the min(nprobe, k) nearest lists, nprobe >= 1: mask kernel, the plan of the ordered-chain scan (the lists are ranked as
+// without a filter: the centroids do not depend on it), per pass the filtered scan, ivf_merge_kernel as it is.  The caller has checked nprobe,
+// the handle's sharding and its centroids.
+int32_t filtered_dev_locked(vers_ivf* h, const float* q_dev, uint64_t ldq_in, uint32_t b, uint32_t top_k, uint32_t nprobe, const uint64_t* bits_dev,
+                            uint64_t n_bits, uint64_t* out_ids, float* out_dist, uint32_t* out_count, hipStream_t st) {
+  if (b == 0) return VERS_OK;
+  if (top_k == 0) {
+    VERS_HIP_TRY(hipMemsetAsync(out_count, 0, sizeof(uint32_t) * b, st));
+    return VERS_OK;
+  }
+  FilterParams f;
+  if (int32_t rc = filter_begin(h, bits_dev, n_bits, h->cap_rows, st, f)) return rc;
+  SearchPlan s;
+  W->no_ahead = true;
+  const int32_t prc = plan_search(h, q_dev, ldq_in, b, top_k, nprobe, st, s, true);
+  W->no_ahead = false;
+  if (prc) return prc;
+  { const int ev = scan_events_ref().load(); W->ev_on = ev == 1 || ev == 2; }  // (the plan set it for an unfiltered call)
+  W->tot_valid = true;
+  const uint32_t P = s.P, S_max = s.S_max, k_keep = s.k_keep;
+  auto fill_src = [&](auto& src) {
+    src.rows = h->rows.as<float>(); src.ld = h->ld; src.list_off = h->slot_off.as<uint32_t>();
+    src.list_len = h->slot_len.as<uint32_t>(); src.items = W->items.as<ItemDesc>(); src.totals = s.tot;
+    src.cnt = s.cnt; src.pair_off = s.pair_off; src.pairs = W->pairs.as<uint32_t>(); src.group_off = s.group_off;
+    src.qblocks = W->qblocks.as<float>(); src.qp = s.qp; src.ldq = h->ldq; src.P = P; src.S_max = S_max; src.k_keep = k_keep;
+    src.seg_rows = s.seg_rows; src.seg_target = s.seg_target; src.pj_pref = s.pj_pref; src.partials = W->partials.as<uint64_t>();
+    src.bound_per_pair = 0u;
+  };
+  for (uint32_t pass = 0; pass < s.n_pass; ++pass) {  // 64 result ranks per pass (one pass for top_k <= 64)
+    const uint64_t* lower = pass ? W->lower.as<uint64_t>() : nullptr;
+    if (pass) VERS_HIP_TRY(hipMemsetAsync(W->partials.p, 0xFF, s.part_bytes, st));  // slots and pruning bounds of the previous pass
+    MergeArgs ma;
+    ma.partials = W->partials.as<uint64_t>(); ma.P = P; ma.S_max = S_max; ma.k_keep = k_keep; ma.ref_mode = 0; ma.np = s.np;
+    ma.pj_list = s.pj_list; ma.pj_pref = s.pj_pref; ma.pj_take = s.pj_take; ma.list_off = h->slot_off.as<uint32_t>(); ma.row_ids = h->row_ids.as<uint32_t>();
+    ma.top_k = top_k; ma.rank0 = pass * (uint32_t)kMaxTopK; ma.out_ids = out_ids; ma.out_dist = out_dist; ma.out_count = out_count; ma.out_keys = nullptr;
+    ma.lower_out = s.n_pass > 1 ? W->lower.as<uint64_t>() : (uint64_t*)nullptr;
+    int32_t rc;
+    if (s.QG == 1) { IvfSrc<1> src; fill_src(src); rc = launch_filter_ivf_scan(h, src, (uint32_t)s.items_bound, f, st, lower); }
+    else if (s.QG == 8) { IvfSrc<8> src; fill_src(src); rc = launch_filter_ivf_scan(h, src, (uint32_t)s.items_bound, f, st, lower); }
+    else { IvfSrc<16> src; fill_src(src); rc = launch_filter_ivf_scan(h, src, (uint32_t)s.items_bound, f, st, lower); }
+    if (rc) return rc;
+    if ((uint64_t)P * S_max <= 4096) hipLaunchKernelGGL(ivf_merge_kernel<4>, dim3(b), dim3(kWave * 4), 0, st, ma);
+    else hipLaunchKernelGGL(ivf_merge_kernel<kMergeWaves>, dim3(b), dim3(kWave * kMergeWaves), 0, st, ma);
+    VERS_HIP_TRY(hipGetLastError());
+  }
+  return filter_end(h, st);
+}
+
+template <int QG>
+int32_t launch_filter_seg_scan(vers_ivf* h, const SegSrc<QG, true>& src, uint32_t n_items, int metric, const FilterParams& f, hipStream_t st,
+                               const uint64_t* lower) {
+  ScanParams p;
+  p.ld = h->ld;
+  p.n_chunks = h->ld / kChunk;
+  p.k = src.k;
+  p.status = W->st_word();
+  p.debug = 0;
+  p.stamps = nullptr;
+  p.next_quad = nullptr;
+  p.bounds = nullptr;  // items of a query are concurrent (launch_seg_scan)
+  p.lower = lower;
+  const size_t lds = scan_lds_bytes(QG, h->ld);
+  uint32_t blocks = (n_items + kWavesPerBlock - 1) / kWavesPerBlock;
+  const uint32_t max_blocks = (uint32_t)h->n_cu * scan_blocks_per_cu(QG, h->ld);
+  if (blocks > max_blocks) blocks = max_blocks;
+  blocks = std::min<uint32_t>(blocks, (uint32_t)(filter_wave_slots(h) / kWavesPerBlock));  // (a counter slot per launched wave: filter_begin)
+  if (blocks == 0) blocks = 1;
+  if (int32_t rc = metric ? scan_prepare_launch(filter_scan_kernel<QG, 1, SegSrc<QG, true>>, lds) : scan_prepare_launch(filter_scan_kernel<QG, 0, SegSrc<QG, true>>, lds)) return rc;
+  const uint32_t slot = (uint32_t)(W->ev_count % SearchWs::kEvRing);
+  if (W->ev_on) VERS_HIP_TRY(hipEventRecord(W->ev0[slot], st));
+  if (metric) hipLaunchKernelGGL((filter_scan_kernel<QG, 1, SegSrc<QG, true>>), dim3(blocks), dim3(kWave * kWavesPerBlock), lds, st, src, p, f);
+  else hipLaunchKernelGGL((filter_scan_kernel<QG, 0, SegSrc<QG, true>>), dim3(blocks), dim3(kWave * kWavesPerBlock), lds, st, src, p, f);
+  VERS_HIP_TRY(hipGetLastError());
+  if (W->ev_on) {
+    VERS_HIP_TRY(hipEventRecord(W->ev1[slot], st));
+    W->ev_count += 1;
+  }
+  return VERS_OK;
+}
+
+// exhaustive_dev_locked's sequence with the filtered kernel: every allowed row that is in a list now, ascending (distance, vec id).  Option
+// "seg_rows" fixes the segment length here as it does for the chains.  An index without centroids (a streamed upload in progress included)
+// is scanned as zero rows: counts 0.
+int32_t exhaustive_filtered_dev_locked(vers_ivf* h, const float* q_dev, uint64_t ldq_in, uint32_t b, uint32_t top_k, uint32_t metric, const uint64_t* bits_dev,
+                                       uint64_t n_bits, uint64_t* out_ids, float* out_dist, uint32_t* out_count, hipStream_t st) {
+  if (b == 0) return VERS_OK;
+  if (top_k == 0) {
+    VERS_HIP_TRY(hipMemsetAsync(out_count, 0, sizeof(uint32_t) * b, st));
+    return VERS_OK;
+  }
+  const uint64_t n_rows = (h->k == 0 || h->up.open) ? 0 : h->cap_rows;
+  FilterParams f;
+  if (int32_t rc = filter_begin(h, bits_dev, n_bits, n_rows, st, f)) return rc;
+  const int QG = b == 1 ? 1 : 8;
+  const uint32_t n_qg = (b + QG - 1) / QG;
+  if (int32_t rc = W->qil.reserve((size_t)n_qg * h->ldq * QG * sizeof(float))) return rc;
+  if (int32_t rc = launch_stage_queries(q_dev, ldq_in, h->d, W->qil.as<float>(), h->ldq, b, QG, st)) return rc;
+  const uint32_t target_items = (uint32_t)h->n_cu * scan_blocks_per_cu(QG, h->ld) * kWavesPerBlock;
+  const uint64_t per = (n_rows * n_qg + target_items - 1) / target_items;
+  const long fixed = knobs().seg_rows;
+  const uint32_t seg_rows = (uint32_t)std::min<uint64_t>(round_up64(fixed > 0 ? (uint64_t)fixed : (per ? per : 1), kWave), max_seg_rows(h->ld));
+  uint32_t n_segs = (uint32_t)((n_rows + seg_rows - 1) / seg_rows);
+  if (n_segs == 0) n_segs = 1;
+  const uint32_t n_segs_pad = QG == 1 ? n_segs : round_up(n_segs, 4);
+  if ((uint64_t)b * n_segs >= 0xFFFFFFFFull || (uint64_t)n_segs_pad * n_qg >= 0xFFFFFFFFull)
+    return fail(VERS_ERR_INVALID, "vers_ivf_search_exhaustive_filtered: batch too large (query x segment slots); split the batch");
+  const uint32_t k_w = std::min<uint32_t>(top_k, kMaxTopK);  // one key per lane; wider results: 64 ranks per pass
+  const size_t xpart_bytes = (size_t)b * n_segs * k_w * sizeof(uint64_t);
+  if (int32_t rc = W->xpart.reserve(xpart_bytes)) return rc;
+  if (top_k > (uint32_t)kMaxTopK)
+    if (int32_t rc = W->lower.reserve((size_t)b * sizeof(uint64_t))) return rc;
+  for (uint64_t rank0 = 0; rank0 < top_k && (rank0 == 0 || rank0 < n_rows); rank0 += kMaxTopK) {
+    const uint32_t k_pass = (uint32_t)std::min<uint64_t>(kMaxTopK, top_k - rank0);
+    const uint64_t* lower = rank0 ? W->lower.as<uint64_t>() : nullptr;
+    VERS_HIP_TRY(hipMemsetAsync(W->xpart.p, 0xFF, xpart_bytes, st));  // a segment without an allowed row writes nothing: its slots read as empty
+    auto fill = [&](auto& src) {
+      src.rows = h->rows.as<float>(); src.n = n_rows; src.ld = h->ld; src.seg_rows = seg_rows; src.n_segs = n_segs; src.n_segs_pad = n_segs_pad;
+      src.queries = W->qil.as<float>(); src.ldq = h->ldq; src.b = b; src.partials = W->xpart.as<uint64_t>(); src.k = k_pass;
+      src.ids = h->row_ids.as<uint32_t>();
+    };
+    int32_t rc;
+    if (QG == 1) { SegSrc<1, true> src; fill(src); rc = launch_filter_seg_scan(h, src, n_segs_pad * n_qg, (int)metric, f, st, lower); }
+    else { SegSrc<8, true> src; fill(src); rc = launch_filter_seg_scan(h, src, n_segs_pad * n_qg, (int)metric, f, st, lower); }
+    if (rc) return rc;
+    hipLaunchKernelGGL(seg_merge_kernel, dim3(b), dim3(kWave * kMergeWaves), 0, st, W->xpart.as<uint64_t>(), n_segs, k_pass, top_k, (uint32_t)rank0, out_ids,
+                       out_dist, out_count, top_k > (uint32_t)kMaxTopK ? W->lower.as<uint64_t>() : (uint64_t*)nullptr);
+    VERS_HIP_TRY(hipGetLastError());
+  }
+  return filter_end(h, st);
+}
+
+// what the four filtered entry points refuse before they touch the device
+static int32_t filter_check(vers_ivf* h, const char* who, bool probed, uint32_t nprobe, const uint64_t* bits, uint64_t n_bits) {
+  if (n_bits != 0 && bits == nullptr) return fail(VERS_ERR_INVALID, std::string(who) + ": n_bits > 0 with a NULL bitmap");
+  if (probed && nprobe == 0)
+    return fail(VERS_ERR_INVALID, std::string(who) + ": nprobe must be at least 1 (the reference's spill walk depends on the filtered list lengths: out of scope)");
+  if (h->world > 1) return fail(VERS_ERR_INVALID, std::string(who) + ": the handle is sharded by cluster; filtered search on a sharded handle is out of scope");
+  if (probed && h->k == 0) return fail(VERS_ERR_INSUFFICIENT, "search on an index without centroids (reference: index out of bounds, ivfflat.rs:169)");
   return VERS_OK;
 }
 
@@ -1337,6 +1565,110 @@ int32_t vers_ivf_search_exhaustive(vers_ivf_t* h, const float* queries, uint64_t
   if (int32_t rc = exhaustive_dev_locked(h, io.q_dev, h->d, b, top_k, metric, io.ids_dev, io.dist_dev, io.cnt_dev, W->io_stream)) return rc;
   const int32_t rc = host_io_end(h, io, b, top_k, out_ids, out_dist, out_count);
   return rc == kRetrySpill ? VERS_ERR_INVALID : rc;
+}
+
+// ---- filtered top-k search (filter.hip.h) ----
+int32_t vers_ivf_search_filtered_dev(vers_ivf_t* h, const float* queries_dev, uint64_t ldq_floats, uint32_t b, uint32_t top_k, uint32_t nprobe,
+                                     const uint64_t* allowed_bits_dev, uint64_t n_bits, uint64_t* out_ids_dev, float* out_dist_dev, uint32_t* out_count_dev,
+                                     void* stream) {
+  if (!h) return fail(VERS_ERR_INVALID, "null handle");
+  if (b && (!queries_dev || ldq_floats < h->d || !out_count_dev || (top_k && (!out_ids_dev || !out_dist_dev))))
+    return fail(VERS_ERR_INVALID, "vers_ivf_search_filtered_dev: bad arguments");
+  std::shared_lock<std::shared_mutex> lk(h->index);
+  if (int32_t rc = filter_check(h, "vers_ivf_search_filtered_dev", true, nprobe, allowed_bits_dev, n_bits)) return rc;
+  if (b == 0) return VERS_OK;
+  DeviceGuard g(h->device);
+  WsLease lease(h, true, (hipStream_t)stream);
+  if (lease.rc) return lease.rc;
+  if (int32_t rc = lease.order_on((hipStream_t)stream)) return rc;
+  return filtered_dev_locked(h, queries_dev, ldq_floats, b, top_k, nprobe, allowed_bits_dev, n_bits, out_ids_dev, out_dist_dev, out_count_dev, (hipStream_t)stream);
+}
+
+int32_t vers_ivf_search_exhaustive_filtered_dev(vers_ivf_t* h, const float* queries_dev, uint64_t ldq_floats, uint32_t b, uint32_t top_k, uint32_t metric,
+                                                const uint64_t* allowed_bits_dev, uint64_t n_bits, uint64_t* out_ids_dev, float* out_dist_dev,
+                                                uint32_t* out_count_dev, void* stream) {
+  if (!h) return fail(VERS_ERR_INVALID, "null handle");
+  if (metric > VERS_METRIC_COSDIST) return fail(VERS_ERR_INVALID, "unknown metric");
+  if (b && (!queries_dev || ldq_floats < h->d || !out_count_dev || (top_k && (!out_ids_dev || !out_dist_dev))))
+    return fail(VERS_ERR_INVALID, "vers_ivf_search_exhaustive_filtered_dev: bad arguments");
+  std::shared_lock<std::shared_mutex> lk(h->index);
+  if (int32_t rc = filter_check(h, "vers_ivf_search_exhaustive_filtered_dev", false, 1, allowed_bits_dev, n_bits)) return rc;
+  if (b == 0) return VERS_OK;
+  DeviceGuard g(h->device);
+  WsLease lease(h, true, (hipStream_t)stream);
+  if (lease.rc) return lease.rc;
+  if (int32_t rc = lease.order_on((hipStream_t)stream)) return rc;
+  return exhaustive_filtered_dev_locked(h, queries_dev, ldq_floats, b, top_k, metric, allowed_bits_dev, n_bits, out_ids_dev, out_dist_dev, out_count_dev,
+                                        (hipStream_t)stream);
+}
+
+// host-pointer calls: queries through the pinned staging of every host-pointer call, the bitmap through the workspace, one synchronisation
+static int32_t filtered_host_common(vers_ivf_t* h, const char* who, const float* queries, uint64_t q_stride_bytes, uint32_t b, uint32_t top_k, bool probed,
+                                    uint32_t nprobe_or_metric, const uint64_t* allowed_bits, uint64_t n_bits, uint64_t* out_ids, float* out_dist, uint32_t* out_count) {
+  if (!h) return fail(VERS_ERR_INVALID, "null handle");
+  if (!probed && nprobe_or_metric > VERS_METRIC_COSDIST) return fail(VERS_ERR_INVALID, "unknown metric");
+  if (b && (!queries || q_stride_bytes < (uint64_t)h->d * 4 || q_stride_bytes % 4 || !out_count || (top_k && (!out_ids || !out_dist))))
+    return fail(VERS_ERR_INVALID, std::string(who) + ": bad arguments");
+  std::shared_lock<std::shared_mutex> lk(h->index);
+  if (int32_t rc = filter_check(h, who, probed, probed ? nprobe_or_metric : 1u, allowed_bits, n_bits)) return rc;
+  if (b == 0) return VERS_OK;
+  DeviceGuard g(h->device);
+  WsLease lease(h);
+  if (lease.rc) return lease.rc;
+  HostStatusSlot slot(h);
+  HostIo io;
+  if (int32_t rc = host_io_begin(h, queries, q_stride_bytes, b, top_k, io)) return rc;
+  lease.st = W->io_stream;
+  const size_t bit_bytes = (size_t)((n_bits + 63) / 64) * sizeof(uint64_t);
+  int32_t rc = W->flt_bits.reserve(std::max<size_t>(8, bit_bytes));
+  if (!rc && bit_bytes && hipMemcpyAsync(W->flt_bits.p, allowed_bits, bit_bytes, hipMemcpyHostToDevice, W->io_stream) != hipSuccess)
+    rc = fail(VERS_ERR_HIP, std::string(who) + ": staging the bitmap failed");
+  if (!rc && hipMemsetAsync(W->io_out.p, 0, io.out_bytes, W->io_stream) != hipSuccess) rc = fail(VERS_ERR_HIP, std::string(who) + ": hipMemsetAsync failed");  // entries past a query's count come back as zeros
+  if (!rc)
+    rc = probed ? filtered_dev_locked(h, io.q_dev, h->d, b, top_k, nprobe_or_metric, W->flt_bits.as<uint64_t>(), n_bits, io.ids_dev, io.dist_dev, io.cnt_dev, W->io_stream)
+                : exhaustive_filtered_dev_locked(h, io.q_dev, h->d, b, top_k, nprobe_or_metric, W->flt_bits.as<uint64_t>(), n_bits, io.ids_dev, io.dist_dev, io.cnt_dev,
+                                                 W->io_stream);
+  if (rc) {  // (the caller's bitmap may still be read by the staging copy)
+    (void)hipStreamSynchronize(W->io_stream);
+    return rc;
+  }
+  rc = host_io_end(h, io, b, top_k, out_ids, out_dist, out_count);
+  return rc == kRetrySpill ? VERS_ERR_INVALID : rc;
+}
+
+int32_t vers_ivf_search_filtered(vers_ivf_t* h, const float* queries, uint64_t q_stride_bytes, uint32_t b, uint32_t top_k, uint32_t nprobe,
+                                 const uint64_t* allowed_bits, uint64_t n_bits, uint64_t* out_ids, float* out_dist, uint32_t* out_count) {
+  return filtered_host_common(h, "vers_ivf_search_filtered", queries, q_stride_bytes, b, top_k, true, nprobe, allowed_bits, n_bits, out_ids, out_dist, out_count);
+}
+
+int32_t vers_ivf_search_exhaustive_filtered(vers_ivf_t* h, const float* queries, uint64_t q_stride_bytes, uint32_t b, uint32_t top_k, uint32_t metric,
+                                            const uint64_t* allowed_bits, uint64_t n_bits, uint64_t* out_ids, float* out_dist, uint32_t* out_count) {
+  return filtered_host_common(h, "vers_ivf_search_exhaustive_filtered", queries, q_stride_bytes, b, top_k, false, metric, allowed_bits, n_bits, out_ids, out_dist,
+                              out_count);
+}
+
+int32_t vers_ivf_filter_stats(vers_ivf_t* h, uint64_t* out4, uint64_t* out4_total) {
+  if (!h) return fail(VERS_ERR_INVALID, "null handle");
+  DeviceGuard g(h->device);
+  unsigned long long last[kFltStats] = {}, tot[kFltStats] = {};
+  SearchWs* ws = nullptr;
+  {
+    std::lock_guard<std::mutex> lk(h->pool_mu);
+    ws = h->flt_last;
+  }
+  if (ws && ws->flt_stats.p) {  // (a measurement hook: the caller has stopped issuing filtered calls)
+    if (ws->used && ws->done) VERS_HIP_TRY(hipEventSynchronize(ws->done));
+    VERS_HIP_TRY(hipMemcpy(last, ws->flt_stats.p, sizeof(last), hipMemcpyDeviceToHost));
+  }
+  {
+    std::lock_guard<std::mutex> lk(h->flt_mu);
+    if (h->flt_total.p) VERS_HIP_TRY(hipMemcpy(tot, h->flt_total.p, sizeof(tot), hipMemcpyDeviceToHost));
+  }
+  for (int i = 0; i < kFltStats; ++i) {
+    if (out4) out4[i] = last[i];
+    if (out4_total) out4_total[i] = tot[i];
+  }
+  return VERS_OK;
 }
 
 int32_t vers_ivf_range_search_dev(vers_ivf_t* h, const float* queries_dev, uint64_t ldq_floats, uint32_t b, const float* radius_dev, uint32_t nprobe,

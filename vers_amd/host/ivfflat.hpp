@@ -190,6 +190,44 @@ class IVFFlatIndex {
     return out;
   }
 
+  // Filtered search (extension, vers_ivf_search_filtered): the top_k nearest among the allowed rows of the min(nprobe, k) nearest lists,
+  // nprobe >= 1 -- what search over those lists returns once every vec id with allowed[v] == false (or v >= allowed.size()) has been
+  // removed; the index is not touched.  Ascending by (distance, probe rank, list position); fewer than top_k entries when fewer are allowed.
+  std::vector<std::pair<size_t, float>> search_filtered(const Vector<N>& query, size_t top_k, size_t nprobe, const std::vector<bool>& allowed) const {
+    const std::vector<uint64_t> bits = allowed_bitmap(allowed);
+    std::vector<uint64_t> oi(top_k ? top_k : 1);
+    std::vector<float> od(top_k ? top_k : 1);
+    uint32_t cnt = 0;
+    check(vers_ivf_search_filtered(handle(), query.v, sizeof(Vector<N>), 1, (uint32_t)top_k, (uint32_t)nprobe, bits.data(), allowed.size(), oi.data(), od.data(),
+                                   &cnt));
+    std::vector<std::pair<size_t, float>> out;
+    for (uint32_t i = 0; i < cnt; ++i) out.emplace_back((size_t)oi[i], od[i]);
+    return out;
+  }
+
+  // Exhaustive filtered search (extension, vers_ivf_search_exhaustive_filtered): the top_k nearest among the allowed rows that are in a list
+  // now, under `metric`, ascending by (distance, vec id).
+  std::vector<std::pair<size_t, float>> search_exhaustive_filtered(const Vector<N>& query, size_t top_k, const std::vector<bool>& allowed,
+                                                                   uint32_t metric = VERS_METRIC_L2SQ) const {
+    const std::vector<uint64_t> bits = allowed_bitmap(allowed);
+    std::vector<uint64_t> oi(top_k ? top_k : 1);
+    std::vector<float> od(top_k ? top_k : 1);
+    uint32_t cnt = 0;
+    check(vers_ivf_search_exhaustive_filtered(handle(), query.v, sizeof(Vector<N>), 1, (uint32_t)top_k, metric, bits.data(), allowed.size(), oi.data(),
+                                              od.data(), &cnt));
+    std::vector<std::pair<size_t, float>> out;
+    for (uint32_t i = 0; i < cnt; ++i) out.emplace_back((size_t)oi[i], od[i]);
+    return out;
+  }
+
+  // allowed[v] -> the u64 words of the C ABI: bit (v & 63) of word (v >> 6); at least one word, so that the array has an address
+  static std::vector<uint64_t> allowed_bitmap(const std::vector<bool>& allowed) {
+    std::vector<uint64_t> bits((allowed.size() + 63) / 64 + 1, 0);
+    for (size_t v = 0; v < allowed.size(); ++v)
+      if (allowed[v]) bits[v >> 6] |= 1ull << (v & 63);
+    return bits;
+  }
+
   // Index::save_index (base.rs:31-43): bincode 1.3 default options -- LE, u64 lengths, fields in order, no tags
   void save_index(const std::string& path) const {
     FILE* f = std::fopen(path.c_str(), "wb");

@@ -183,6 +183,63 @@ class IVFFlatIndex:
         check(lib().vers_ivf_search_exhaustive(self._h, _ptr(q), 4 * self.d, b, top_k, metric, _ptr(ids), _ptr(dist), _ptr(cnt)))
         return ids[:, :top_k], dist[:, :top_k], cnt
 
+    # -- filtered search (extension): a bitmap of allowed vec ids per call = a virtual remove_batch of the others -----
+    @staticmethod
+    def _filter_words(allowed, n_bits):
+        """allowed -> (u64 words, n_bits).  A bool array (allowed[v]; n_bits defaults to its length), an integer array of allowed vec ids
+        (n_bits defaults to the largest id + 1), or a ready (words, n_bits) pair as capi.allowed_bitmap packs it."""
+        if isinstance(allowed, tuple):
+            words, nb = allowed
+            return np.ascontiguousarray(words, dtype=np.uint64), int(nb)
+        a = np.asarray(allowed)
+        if n_bits is None:
+            n_bits = a.size if a.dtype == np.bool_ else (int(a.max()) + 1 if a.size else 0)
+        return capi.allowed_bitmap(a, n_bits), int(n_bits)
+
+    def search_filtered(self, queries, top_k: int, nprobe: int, allowed, n_bits=None):
+        """search_batch(queries, top_k, nprobe) on the index WITHOUT the vec ids `allowed` leaves out (vers_ivf_search_filtered; nprobe >= 1):
+        the allowed rows of the min(nprobe, k) nearest lists, ascending (distance, probe rank, list position); the index is not touched.
+        -> (ids [b, top_k] u64, dist [b, top_k] f32, count [b] u32); count may be 0."""
+        q = np.ascontiguousarray(np.atleast_2d(queries), dtype=np.float32)
+        b = q.shape[0]
+        words, nb = self._filter_words(allowed, n_bits)
+        ids = np.zeros((b, max(top_k, 1)), dtype=np.uint64)
+        dist = np.zeros((b, max(top_k, 1)), dtype=np.float32)
+        cnt = np.zeros(b, dtype=np.uint32)
+        check(lib().vers_ivf_search_filtered(self._h, _ptr(q), 4 * self.d, b, top_k, nprobe, _ptr(words), nb, _ptr(ids), _ptr(dist), _ptr(cnt)))
+        return ids[:, :top_k], dist[:, :top_k], cnt
+
+    def search_exhaustive_filtered(self, queries, top_k: int, allowed, metric: int = capi.METRIC_L2SQ, n_bits=None):
+        """search_exhaustive over the allowed rows that are in a list now (vers_ivf_search_exhaustive_filtered): ascending (distance, vec id)."""
+        q = np.ascontiguousarray(np.atleast_2d(queries), dtype=np.float32)
+        b = q.shape[0]
+        words, nb = self._filter_words(allowed, n_bits)
+        ids = np.zeros((b, max(top_k, 1)), dtype=np.uint64)
+        dist = np.zeros((b, max(top_k, 1)), dtype=np.float32)
+        cnt = np.zeros(b, dtype=np.uint32)
+        check(lib().vers_ivf_search_exhaustive_filtered(self._h, _ptr(q), 4 * self.d, b, top_k, metric, _ptr(words), nb, _ptr(ids), _ptr(dist),
+                                                        _ptr(cnt)))
+        return ids[:, :top_k], dist[:, :top_k], cnt
+
+    def search_filtered_dev(self, q_ptr: int, ldq: int, b: int, top_k: int, nprobe: int, bits_ptr: int, n_bits: int, ids_ptr: int, dist_ptr: int,
+                            cnt_ptr: int, stream: int = 0):
+        """vers_ivf_search_filtered_dev on raw device pointers (the bitmap too); queued on `stream`, not synchronised: poll() reports."""
+        check(lib().vers_ivf_search_filtered_dev(self._h, _vp(q_ptr), ldq, b, top_k, nprobe, _vp(bits_ptr) if bits_ptr else None, n_bits,
+                                                 _vp(ids_ptr), _vp(dist_ptr), _vp(cnt_ptr), _vp(stream)))
+
+    def search_exhaustive_filtered_dev(self, q_ptr: int, ldq: int, b: int, top_k: int, metric: int, bits_ptr: int, n_bits: int, ids_ptr: int,
+                                       dist_ptr: int, cnt_ptr: int, stream: int = 0):
+        check(lib().vers_ivf_search_exhaustive_filtered_dev(self._h, _vp(q_ptr), ldq, b, top_k, metric, _vp(bits_ptr) if bits_ptr else None, n_bits,
+                                                            _vp(ids_ptr), _vp(dist_ptr), _vp(cnt_ptr), _vp(stream)))
+
+    def filter_stats(self):
+        """vers_ivf_filter_stats: of the most recent filtered call and over the handle's life -- 64-row tile visits the plan implied, tile
+        visits actually loaded, work items skipped before their first load, allowed storage rows."""
+        last = (C.c_uint64 * 4)(); tot = (C.c_uint64 * 4)()
+        check(lib().vers_ivf_filter_stats(self._h, last, tot))
+        keys = ("tiles_planned", "tiles_loaded", "items_skipped", "rows_allowed")
+        return dict(last=dict(zip(keys, (int(v) for v in last))), total=dict(zip(keys, (int(v) for v in tot))))
+
     # -- range search (extension; the reference has search_approximate only) ---------------------------
     def range_search(self, queries, radius, nprobe: int, walk_order: bool = False):
         """Every row of the min(nprobe, k) nearest lists of each query with distance <= radius (vers_ivf_range_search).  radius: a
