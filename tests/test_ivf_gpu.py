@@ -334,6 +334,47 @@ def test_scan_events_option_times_single_query_scans_only_on_request():
         ix.close()
 
 
+def test_scan_times_records_per_kind_of_call():
+    """With scan_events = 1 every kind of call leaves a fixed number of scan_times records: one per timed launch (list scan, single-query
+    scan, matrix-core scan, the filter's mask kernel, each filtered scan pass), none for the launches that were never timed (the range
+    scans, the unfiltered exhaustive scan).  The constants are what the commit before the host-side launch helpers were shared left, call
+    by call on the same index.  + option "seg_rows" does not move the unfiltered exhaustive search's result."""
+    n, d, k = 3000, 24, 12
+    X = dg.dist_c(0x5EC1, n, d, 6, dg.default_sigma(d))
+    ix = IVFFlatIndex.build_index(k, 1, 2, X, init_indices=mg.init_draws(0x5EC1, 1, k, n))
+    Q = dg.dist_c(0x5EC2, 40, d, 6, dg.default_sigma(d))
+    allowed = (np.arange(n) % 3) != 0
+
+    def records(call):
+        call()
+        return len(ix.scan_times(reset=True))
+
+    try:
+        capi.set_option("scan_events", 1)
+        ix.search_batch(Q, 5, 3); ix.scan_times(reset=True)
+        assert records(lambda: ix.search_batch(Q, 5, 3)) == 1                          # a batch: the matrix-core scan
+        assert records(lambda: ix.search_batch(Q[1], 5, 3)) == 1                       # a single query
+        capi.set_option("prescan", 0)
+        assert records(lambda: ix.search_batch(Q, 70, 3)) == 2                         # ordered chains, 64 ranks per pass: two passes
+        capi.set_option("prescan", 1)
+        assert records(lambda: ix.search_filtered(Q, 5, 3, allowed)) == 2              # the mask kernel + one filtered pass
+        assert records(lambda: ix.search_filtered(Q, 70, 3, allowed)) == 3             # ... + two
+        assert records(lambda: ix.search_exhaustive_filtered(Q, 5, allowed)) == 2      # the mask kernel + one filtered segment scan
+        e0 = ix.search_exhaustive(Q, 5)
+        assert len(ix.scan_times(reset=True)) == 0                                     # the unfiltered segment scan is not timed
+        rad = ix.search_batch(Q, 5, 3)[1][:, -1]; ix.scan_times(reset=True)
+        lims = ix.range_search(Q, rad, 3)[0]
+        assert int(lims[-1]) >= 5 * len(Q) and len(ix.scan_times(reset=True)) == 0      # nor are the range scans
+        capi.set_option("seg_rows", 64)
+        e64 = ix.search_exhaustive(Q, 5)
+        assert np.array_equal(e0[0], e64[0]) and np.array_equal(bits(e0[1]), bits(e64[1])) and np.array_equal(e0[2], e64[2])
+    finally:
+        capi.set_option("seg_rows", 0)
+        capi.set_option("prescan", 1)
+        capi.set_option("scan_events", 2)
+        ix.close()
+
+
 def test_round4_entry_points_and_hooks():
     """vers_ivf_search_sharded_dev without an exchange (g == NULL: a single process) == vers_ivf_search_dev; its argument checks;
     the layout / finish-time / build-phase hooks report what the handle holds and ran."""

@@ -10,8 +10,7 @@
 
 #include "flat_handle.hpp"
 #include "kmeans.hpp"
-#include "range.hip.h"
-#include "scan.hip.h"
+#include "range_driver.hip.h"
 #include "util.hip.h"
 
 namespace vers {
@@ -84,8 +83,9 @@ using namespace vers;
 
 namespace {
 
-template <int QG, int METRIC>
-int32_t launch_flat_scan(vers_flat* h, const FlatSrc<QG, false>& src, uint32_t n_items, hipStream_t st, const uint64_t* lower) {
+// one pass of the top-k scan; the handle's own two events time the first pass (vers_flat_last_scan_ms), no timing ring here
+template <int QG>
+int32_t launch_flat_scan(vers_flat* h, const FlatSrc<QG, false>& src, uint32_t n_items, int metric, hipStream_t st, const uint64_t* lower) {
   ScanParams p;
   p.ld = h->ld;
   p.n_chunks = h->ld / kChunk;
@@ -96,15 +96,10 @@ int32_t launch_flat_scan(vers_flat* h, const FlatSrc<QG, false>& src, uint32_t n
   p.next_quad = nullptr;
   p.bounds = nullptr;  // every item of a query runs concurrently here: a shared bound prunes nothing and its atomics contend
   p.lower = lower;     // (top_k > 64: ranks 64p .. 64p + 63 in pass p)
-  const size_t lds = scan_lds_bytes(QG, h->ld);
-  if (int32_t rc = scan_prepare_launch(scan_kernel<QG, METRIC, FlatSrc<QG, false>>, lds)) return rc;
-  const uint32_t max_blocks = (uint32_t)h->n_cu * scan_blocks_per_cu(QG, h->ld);
-  uint32_t blocks = (n_items + kWavesPerBlock - 1) / kWavesPerBlock;
-  if (blocks > max_blocks) blocks = max_blocks;
-  if (blocks == 0) blocks = 1;
   if (lower == nullptr) VERS_HIP_TRY(hipEventRecord(h->ev0, st));  // (the measurement hook times the first pass)
-  hipLaunchKernelGGL((scan_kernel<QG, METRIC, FlatSrc<QG, false>>), dim3(blocks), dim3(kWave * kWavesPerBlock), lds, st, src, p);
-  VERS_HIP_TRY(hipGetLastError());
+  if (int32_t rc = with_metric(metric, [&](auto m) -> int32_t {
+        return launch_scan(scan_kernel<QG, decltype(m)::value, FlatSrc<QG, false>>, scan_grid(h->n_cu, QG, h->ld, n_items), kWavesPerBlock, scan_lds_bytes(QG, h->ld), st, src, p);
+      })) return rc;
   if (lower == nullptr) VERS_HIP_TRY(hipEventRecord(h->ev1, st));
   h->ev_valid = true;
   return VERS_OK;
@@ -119,8 +114,10 @@ int32_t flat_search_dev_locked(vers_flat* h, const float* q_dev, uint64_t ldq, u
     return VERS_OK;
   }
   const uint32_t ldq_pad = h->ld;
-  const int QG = b == 1 ? 1 : 8;
-  const uint32_t n_qg = (b + QG - 1) / QG;
+  // one item per resident wave when possible (static balance), at least one 64-row tile each; option "seg_rows" is not honoured here
+  const SegPlan sp = seg_plan(h->n, b, h->ld, h->n_cu, 0);
+  const int QG = sp.QG;
+  const uint32_t n_qg = sp.n_qg, n_segs = sp.n_segs;
   // queries: a single query is used in place when it is chunk-padded by construction; otherwise
   // stage a zero padded (QG > 1: interleaved) copy
   const float* q = q_dev;
@@ -144,12 +141,6 @@ int32_t flat_search_dev_locked(vers_flat* h, const float* q_dev, uint64_t ldq, u
     h->ev_valid = true;
     return VERS_OK;
   }
-  // one item per resident wave when possible (static balance), at least one 64-row tile each
-  const uint32_t target_items = (uint32_t)h->n_cu * scan_blocks_per_cu(QG, h->ld) * kWavesPerBlock;
-  uint64_t per = (h->n * n_qg + target_items - 1) / target_items;
-  uint32_t seg_rows = (uint32_t)std::min<uint64_t>(round_up64(per ? per : 1, kWave), max_seg_rows(h->ld));
-  uint32_t n_segs = (uint32_t)((h->n + seg_rows - 1) / seg_rows);
-  if (n_segs == 0) n_segs = 1;
   // one key per lane is the width of every list in the kernels: wider results come 64 ranks per pass -- keys are unique and
   // totally ordered, pass p holds exactly ranks 64p .. 64p + 63, selected by an exclusive lower bound (utils.rs:68-82 has no cap)
   const uint32_t k_w = std::min<uint32_t>(top_k, kMaxTopK);
@@ -158,27 +149,14 @@ int32_t flat_search_dev_locked(vers_flat* h, const float* q_dev, uint64_t ldq, u
   VERS_HIP_TRY(hipMemsetAsync(h->partials + h->bounds_off, 0xFF, (size_t)n_qg * QG * sizeof(uint64_t), st));
   if (top_k > (uint32_t)kMaxTopK)
     if (int32_t rc = grow(h->lower, h->lower_cap, (size_t)b)) return rc;
-  const uint32_t n_segs_pad = QG == 1 ? n_segs : round_up(n_segs, 4);
-  const uint32_t n_items = n_segs_pad * n_qg;
-
   // (a pass past the last row finds nothing: top_k = 100000 on n = 1000 is 16 passes, not 1563; 64-bit rank: no wrap near 2^32)
   for (uint64_t rank0 = 0; rank0 < top_k && (rank0 == 0 || rank0 < h->n); rank0 += kMaxTopK) {
     const uint32_t k_pass = (uint32_t)std::min<uint64_t>(kMaxTopK, top_k - rank0);
     const uint64_t* lower = rank0 ? h->lower : nullptr;
-    auto fill = [&](auto& src) {
-      src.rows = h->rows; src.n = h->n; src.ld = h->ld; src.seg_rows = seg_rows; src.n_segs = n_segs; src.n_segs_pad = n_segs_pad;
-      src.queries = q; src.ldq = ldq_use; src.b = b; src.partials = h->partials;
-      src.k = k_pass; src.ids = nullptr;
-    };
-    int32_t rc;
-    if (QG == 1) {
-      FlatSrc<1, false> src; fill(src);
-      rc = metric == VERS_METRIC_L2SQ ? launch_flat_scan<1, 0>(h, src, n_items, st, lower) : launch_flat_scan<1, 1>(h, src, n_items, st, lower);
-    } else {
-      FlatSrc<8, false> src; fill(src);
-      rc = metric == VERS_METRIC_L2SQ ? launch_flat_scan<8, 0>(h, src, n_items, st, lower) : launch_flat_scan<8, 1>(h, src, n_items, st, lower);
-    }
-    if (rc) return rc;
+    if (int32_t rc = with_qg<1, 8>(QG, [&](auto qg) -> int32_t {
+          using Src = FlatSrc<decltype(qg)::value, false>;
+          return launch_flat_scan(h, make_seg_src<Src>(h->rows, h->n, h->ld, sp, q, ldq_use, b, h->partials, k_pass, nullptr), sp.n_items, metric != VERS_METRIC_L2SQ, st, lower);
+        })) return rc;
     uint64_t* lower_out = top_k > (uint32_t)kMaxTopK ? h->lower : (uint64_t*)nullptr;
     if (n_segs <= 4096) hipLaunchKernelGGL(flat_merge_kernel<4>, dim3(b), dim3(kWave * 4), 0, st, h->partials, n_segs, k_pass, h->n, top_k, (uint32_t)rank0, out_ids,
                                            out_dist, out_count, lower_out);
@@ -190,94 +168,32 @@ int32_t flat_search_dev_locked(vers_flat* h, const float* q_dev, uint64_t ldq, u
 }
 
 // ---- range search (range.hip.h): every uploaded row within the radius ---------------------------------------------------------------
-template <int QG, int METRIC, bool FILL>
-int32_t launch_flat_range(vers_flat* h, const FlatSrc<QG, false>& src, uint32_t n_items, const RangeParams& p, hipStream_t st) {
-  const size_t lds = scan_lds_bytes(QG, h->ld);
-  if (int32_t rc = scan_prepare_launch(range_scan_kernel<QG, METRIC, FILL, FlatSrc<QG, false>>, lds)) return rc;
-  const uint32_t max_blocks = (uint32_t)h->n_cu * scan_blocks_per_cu(QG, h->ld);
-  uint32_t blocks = (n_items + kWavesPerBlock - 1) / kWavesPerBlock;
-  if (blocks > max_blocks) blocks = max_blocks;
-  if (blocks == 0) blocks = 1;
-  hipLaunchKernelGGL((range_scan_kernel<QG, METRIC, FILL, FlatSrc<QG, false>>), dim3(blocks), dim3(kWave * kWavesPerBlock), lds, st, src, p);
-  VERS_HIP_TRY(hipGetLastError());
-  return VERS_OK;
-}
-
-// Range search of b >= 1 queries on `st`: stage, count launch, prefix scan, limits, ONE synchronisation for total / status / NaN radius, fill,
-// sort, decode, synchronisation.  The caller holds the handle's mutex.  own_out: ids / distances go to o_ids / o_dist, sized by the total
-// (the host-pointer call copies them out), else to ids_dev / dist_dev -- when total <= cap.  An empty corpus walks one empty item per query
-// group: total 0, every limit 0, the radii still checked.
-int32_t flat_range_dev_locked(vers_flat* h, const float* q_dev, uint64_t ldq, uint32_t b, const float* radius_dev, uint32_t metric, uint32_t flags,
-                              uint64_t* lims_dev, uint64_t* ids_dev, float* dist_dev, uint64_t cap, bool own_out, uint64_t* out_total, hipStream_t st) {
-  for (auto& e : h->rg_ev)
-    if (!e) VERS_HIP_TRY(hipEventCreate(&e));
-  VERS_HIP_TRY(hipEventRecord(h->rg_ev[0], st));
-  const int QG = b == 1 ? 1 : 8;
-  const uint32_t n_qg = (b + QG - 1) / QG;
-  if (int32_t rc = grow(h->rg_q, h->rg_q_cap, (size_t)n_qg * h->ld * QG)) return rc;
-  if (int32_t rc = launch_stage_queries(q_dev, ldq, h->d, h->rg_q, h->ld, b, (uint32_t)QG, st)) return rc;
-  // segments as vers_flat_search sizes them (one item per resident wave when possible), or as option "seg_rows" fixes them
-  const uint32_t target_items = (uint32_t)h->n_cu * scan_blocks_per_cu(QG, h->ld) * kWavesPerBlock;
-  const uint64_t per = (h->n * n_qg + target_items - 1) / target_items;
-  const int64_t fixed = opt_get("seg_rows", 0);
-  const uint32_t seg_rows = (uint32_t)std::min<uint64_t>(round_up64(fixed > 0 ? (uint64_t)fixed : (per ? per : 1), kWave), max_seg_rows(h->ld));
-  uint32_t n_segs = (uint32_t)((h->n + seg_rows - 1) / seg_rows);
-  if (n_segs == 0) n_segs = 1;
-  const uint32_t n_segs_pad = QG == 1 ? n_segs : round_up(n_segs, 4);
-  const uint64_t n_slots = (uint64_t)b * n_segs;
-  if (n_slots >= 0xFFFFFFFFull || (uint64_t)n_segs_pad * n_qg >= 0xFFFFFFFFull)
-    return fail(VERS_ERR_INVALID, "vers_flat_range_search: batch too large (query x segment slots); split the batch");
-  const uint32_t n_items = n_segs_pad * n_qg;
-  const size_t scan_tmp = range_scan_temp_bytes((size_t)n_slots + 1);
-  if (int32_t rc = grow(h->rg_counts, h->rg_counts_cap, (size_t)n_slots + 1)) return rc;
-  if (int32_t rc = grow(h->rg_base, h->rg_base_cap, (size_t)n_slots + 1)) return rc;
-  if (int32_t rc = grow(h->rg_misc, h->rg_misc_cap, (size_t)4)) return rc;
-  if (int32_t rc = grow(h->rg_tmp, h->rg_tmp_cap, scan_tmp)) return rc;
-  uint32_t* status = h->status_dev + 1;  // (word 0 belongs to the top-k calls and vers_flat_poll)
-  VERS_HIP_TRY(hipMemsetAsync(h->rg_counts, 0, ((size_t)n_slots + 1) * sizeof(uint32_t), st));  // (+ one zero count: the prefix's last entry is the total)
-  VERS_HIP_TRY(hipMemsetAsync(h->rg_misc, 0, 16, st));
-  VERS_HIP_TRY(hipMemsetAsync(status, 0, sizeof(uint32_t), st));
-  RangeParams rp;
-  rp.ld = h->ld; rp.n_chunks = h->ld / kChunk; rp.status = status; rp.radius = radius_dev; rp.counts = h->rg_counts; rp.base = h->rg_base;
-  rp.row_ids = nullptr; rp.out_keys = nullptr; rp.out_ids = nullptr; rp.out_dist = nullptr; rp.next_quad = nullptr;
-  auto pass = [&](auto fill_tag) -> int32_t {
-    constexpr bool FILL = decltype(fill_tag)::value;
-    auto fill = [&](auto& src) {
-      src.rows = h->rows; src.n = h->n; src.ld = h->ld; src.seg_rows = seg_rows; src.n_segs = n_segs; src.n_segs_pad = n_segs_pad;
-      src.queries = h->rg_q; src.ldq = h->ld; src.b = b; src.partials = nullptr; src.k = 0; src.ids = nullptr;
-    };
-    if (QG == 1) {
-      FlatSrc<1, false> src; fill(src);
-      return metric == VERS_METRIC_L2SQ ? launch_flat_range<1, 0, FILL>(h, src, n_items, rp, st) : launch_flat_range<1, 1, FILL>(h, src, n_items, rp, st);
-    }
-    FlatSrc<8, false> src; fill(src);
-    return metric == VERS_METRIC_L2SQ ? launch_flat_range<8, 0, FILL>(h, src, n_items, rp, st) : launch_flat_range<8, 1, FILL>(h, src, n_items, rp, st);
-  };
-  VERS_HIP_TRY(hipEventRecord(h->rg_ev[1], st));
-  if (int32_t rc = pass(std::false_type{})) return rc;
-  VERS_HIP_TRY(hipEventRecord(h->rg_ev[2], st));
-  if (int32_t rc = range_scan_counts(h->rg_counts, h->rg_base, (size_t)n_slots + 1, h->rg_tmp, scan_tmp, st)) return rc;
-  hipLaunchKernelGGL(range_lims_kernel, dim3((b + 1 + 255) / 256), dim3(256), 0, st, (const uint64_t*)h->rg_base, (uint64_t)n_segs, b, radius_dev,
-                     (const uint32_t*)status, lims_dev, h->rg_misc);
-  VERS_HIP_TRY(hipGetLastError());
-  if (!h->rg_pin) VERS_HIP_TRY(hipHostMalloc((void**)&h->rg_pin, 16, hipHostMallocDefault));  // pinned landing words: total | status | NaN radius
-  VERS_HIP_TRY(hipMemcpyAsync(h->rg_pin, h->rg_misc, 16, hipMemcpyDeviceToHost, st));
-  VERS_HIP_TRY(hipEventRecord(h->rg_ev[3], st));
-  VERS_HIP_TRY(hipStreamSynchronize(st));
-  uint32_t misc[4];
-  std::memcpy(misc, h->rg_pin, sizeof(misc));
-  if (misc[2] & 1u) return fail(VERS_ERR_NAN, "NaN distance (the reference panics in partial_cmp().unwrap())");
-  if (misc[3]) return fail(VERS_ERR_INVALID, "vers_flat_range_search: NaN radius");
-  const uint64_t total = ((uint64_t)misc[1] << 32) | misc[0];
-  if (total > 0xFFFFFFFFull) return fail(VERS_ERR_INVALID, "vers_flat_range_search: more than 2^32 - 1 results in one call; split the batch");
-  *out_total = total;
-  float ms[5] = {};
-  auto phases = [&](int n_ev) {
-    for (int i = 0; i + 1 < n_ev; ++i) (void)hipEventElapsedTime(&ms[i], h->rg_ev[i], h->rg_ev[i + 1]);
-    range_phases_add(b, total, ms);
-  };
-  if (total == 0 || total > cap) { phases(4); return VERS_OK; }  // (too small a buffer: the limits are complete, ids / distances untouched)
-  if (own_out) {
+// What the range protocol (range_driver.hip.h: range_search_run) walks on the flat handle: the segment items of the top-k scan, cut as option
+// "seg_rows" says when set.  The caller holds the handle's mutex.  A host-pointer call's ids / distances go to o_ids / o_dist.  An empty corpus
+// walks one empty item per query group: total 0, every limit 0, the radii still checked.  Status: word 1 of status_dev, zeroed per call (word
+// 0 belongs to the top-k calls and vers_flat_poll); its bit 0 is a NaN distance.
+struct FlatRangeSource {
+  static constexpr bool kKeyIds = true, kPartials = false;
+  const char* who = "vers_flat_range_search";
+  vers_flat* h;
+  const float* q_dev; uint64_t ldq; uint32_t b, metric;
+  SegPlan sp{};
+  FlatRangeSource(vers_flat* hh, const float* q, uint64_t l, uint32_t bb, uint32_t m) : h(hh), q_dev(q), ldq(l), b(bb), metric(m) {}
+  uint32_t ld() const { return h->ld; }
+  uint32_t* status() const { return h->status_dev + 1; }
+  const uint32_t* row_ids() const { return nullptr; }
+  int32_t prepare(hipStream_t st, uint64_t& slots_per_query) {
+    sp = seg_plan(h->n, b, h->ld, h->n_cu, opt_get("seg_rows", 0));
+    if (int32_t rc = h->rg_q.reserve((size_t)sp.n_qg * h->ld * sp.QG * sizeof(float))) return rc;
+    if (int32_t rc = launch_stage_queries(q_dev, ldq, h->d, h->rg_q.as<float>(), h->ld, b, (uint32_t)sp.QG, st)) return rc;
+    if (sp.too_large) return fail(VERS_ERR_INVALID, "vers_flat_range_search: batch too large (query x segment slots); split the batch");
+    VERS_HIP_TRY(hipMemsetAsync(status(), 0, sizeof(uint32_t), st));
+    slots_per_query = sp.n_segs;
+    return VERS_OK;
+  }
+  int32_t status_rc(uint32_t word) const { return (word & 1u) ? fail(VERS_ERR_NAN, "NaN distance (the reference panics in partial_cmp().unwrap())") : VERS_OK; }
+  bool walk_order(uint32_t flags, bool) const { return (flags & VERS_RANGE_WALK_ORDER) != 0; }
+  int32_t own_out(uint64_t total, uint64_t*& ids, float*& dist) const {
     if (total > h->o_cap) {
       size_t c0 = h->o_cap, c1 = h->o_cap, c2 = h->o_cap;
       if (int32_t rc = grow(h->o_ids, c0, (size_t)total)) return rc;
@@ -285,29 +201,24 @@ int32_t flat_range_dev_locked(vers_flat* h, const float* q_dev, uint64_t ldq, ui
       if (int32_t rc = grow(h->o_cnt, c2, (size_t)total)) return rc;
       h->o_cap = (size_t)total;
     }
-    ids_dev = h->o_ids; dist_dev = h->o_dist;
+    ids = h->o_ids; dist = h->o_dist;
+    return VERS_OK;
   }
-  const bool walk = (flags & VERS_RANGE_WALK_ORDER) != 0;
-  size_t sort_tmp = 0;
-  uint64_t *k_in = nullptr, *k_out = nullptr;
-  if (!walk) {  // staging of the sorted order: keys in | keys out (the key's low word is the id), + rocPRIM's temporary
-    sort_tmp = range_sort_keys_temp_bytes((uint32_t)total, b);
-    if (int32_t rc = grow(h->rg_stage, h->rg_stage_cap, 2 * (size_t)total)) return rc;
-    if (int32_t rc = grow(h->rg_tmp, h->rg_tmp_cap, sort_tmp)) return rc;
-    k_in = h->rg_stage; k_out = k_in + total;
+  template <class Fill>
+  int32_t launch(Fill, const RangeParams& p, hipStream_t st) const {
+    return with_qg<1, 8>(sp.QG, [&](auto qg) -> int32_t {
+      constexpr int QG = decltype(qg)::value;
+      using Src = FlatSrc<QG, false>;
+      return launch_range_pass<QG, Fill::value>(h->n_cu, h->ld, metric != VERS_METRIC_L2SQ,
+                                                make_seg_src<Src>(h->rows, h->n, h->ld, sp, h->rg_q.as<float>(), h->ld, b, nullptr, 0, nullptr), sp.n_items, p, st);
+    });
   }
-  rp.out_keys = k_in; rp.out_ids = walk ? ids_dev : nullptr; rp.out_dist = walk ? dist_dev : nullptr;
-  if (int32_t rc = pass(std::true_type{})) return rc;
-  VERS_HIP_TRY(hipEventRecord(h->rg_ev[4], st));
-  if (!walk) {
-    if (int32_t rc = range_sort_segment_keys(k_in, k_out, (uint32_t)total, b, lims_dev, h->rg_tmp, sort_tmp, st)) return rc;
-    hipLaunchKernelGGL(range_decode_ids_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (const uint64_t*)k_out, total, ids_dev, dist_dev);
-    VERS_HIP_TRY(hipGetLastError());
-  }
-  VERS_HIP_TRY(hipEventRecord(h->rg_ev[5], st));
-  VERS_HIP_TRY(hipStreamSynchronize(st));
-  phases(6);
-  return VERS_OK;
+};
+
+int32_t flat_range_dev_locked(vers_flat* h, const float* q_dev, uint64_t ldq, uint32_t b, const float* radius_dev, uint32_t metric, uint32_t flags,
+                              uint64_t* lims_dev, uint64_t* ids_dev, float* dist_dev, uint64_t cap, bool own_out, uint64_t* out_total, hipStream_t st) {
+  FlatRangeSource src(h, q_dev, ldq, b, metric);
+  return range_search_run(src, h->rg, b, radius_dev, flags, lims_dev, ids_dev, dist_dev, cap, own_out, out_total, st);
 }
 
 // what both range entry points refuse before they touch the device
@@ -366,13 +277,8 @@ int32_t vers_flat_destroy(vers_flat_t* h) {
     if (p) (void)hipFree(p);
   if (h->ev0) (void)hipEventDestroy(h->ev0);
   if (h->ev1) (void)hipEventDestroy(h->ev1);
-  for (void* p : {(void*)h->rg_q, (void*)h->rg_counts, (void*)h->rg_base, (void*)h->rg_misc, (void*)h->rg_stage, (void*)h->rg_tmp, (void*)h->rg_rad,
-                  (void*)h->rg_lims})
-    if (p) (void)hipFree(p);
-  if (h->rg_pin) (void)hipHostFree(h->rg_pin);
-  for (hipEvent_t e : h->rg_ev)
-    if (e) (void)hipEventDestroy(e);
-  delete h;
+  h->rg.release();
+  delete h;  // (the range scratch frees its buffers with it)
   return VERS_OK;
 }
 
@@ -506,15 +412,15 @@ int32_t vers_flat_range_search(vers_flat_t* h, const float* queries, uint64_t q_
   std::lock_guard<std::mutex> lk(h->mu);
   DeviceGuard g(h->device);
   if (int32_t rc = grow(h->q_up, h->q_up_cap, (size_t)b * h->ld)) return rc;
-  if (int32_t rc = grow(h->rg_rad, h->rg_rad_cap, (size_t)b)) return rc;
-  if (int32_t rc = grow(h->rg_lims, h->rg_lims_cap, (size_t)b + 1)) return rc;
+  if (int32_t rc = h->rg_rad.reserve((size_t)b * sizeof(float))) return rc;
+  if (int32_t rc = h->rg_lims.reserve(((size_t)b + 1) * sizeof(uint64_t))) return rc;
   if (hipMemset(h->q_up, 0, (size_t)b * h->ld * sizeof(float)) != hipSuccess ||
       hipMemcpy2D(h->q_up, (size_t)h->ld * 4, queries, q_stride_bytes, (size_t)h->d * 4, b, hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemcpy(h->rg_rad, radius, (size_t)b * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)
+      hipMemcpy(h->rg_rad.p, radius, (size_t)b * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)
     return fail(VERS_ERR_HIP, "query upload failed");
   uint64_t total = 0;
-  if (int32_t rc = flat_range_dev_locked(h, h->q_up, h->ld, b, h->rg_rad, metric, flags, h->rg_lims, nullptr, nullptr, cap, true, &total, nullptr)) return rc;
-  VERS_HIP_TRY(hipMemcpy(out_lims, h->rg_lims, ((size_t)b + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost));
+  if (int32_t rc = flat_range_dev_locked(h, h->q_up, h->ld, b, h->rg_rad.as<float>(), metric, flags, h->rg_lims.as<uint64_t>(), nullptr, nullptr, cap, true, &total, nullptr)) return rc;
+  VERS_HIP_TRY(hipMemcpy(out_lims, h->rg_lims.p, ((size_t)b + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost));
   *out_total = total;
   if (total == 0 || total > cap) return VERS_OK;
   VERS_HIP_TRY(hipMemcpy(out_ids, h->o_ids, (size_t)total * sizeof(uint64_t), hipMemcpyDeviceToHost));

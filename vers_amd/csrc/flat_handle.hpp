@@ -4,6 +4,7 @@
 #include <mutex>
 
 #include "flat_shadow.hpp"
+#include "range_scratch.hpp"
 
 struct vers_flat {
   int device = 0;
@@ -31,20 +32,10 @@ struct vers_flat {
   size_t o_cap = 0;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   bool ev_valid = false;
-  // range search (flat.hip: flat_range_dev_locked; grow-only like the rest): staged queries | hits per (query, segment) slot | their exclusive
-  // prefix | [0..1] total, [2] status, [3] NaN-radius flag | keys in + keys out of the sorted order | rocPRIM's temporary | radii and CSR
-  // limits of a host-pointer call (its ids / distances land in o_ids / o_dist)
-  float* rg_q = nullptr;
-  uint32_t* rg_counts = nullptr;
-  uint64_t* rg_base = nullptr;
-  uint32_t* rg_misc = nullptr;
-  uint64_t* rg_stage = nullptr;
-  unsigned char* rg_tmp = nullptr;
-  float* rg_rad = nullptr;
-  uint64_t* rg_lims = nullptr;
-  size_t rg_q_cap = 0, rg_counts_cap = 0, rg_base_cap = 0, rg_misc_cap = 0, rg_stage_cap = 0, rg_tmp_cap = 0, rg_rad_cap = 0, rg_lims_cap = 0;
-  uint32_t* rg_pin = nullptr;  // pinned [4]: where a range call reads its total, status word and NaN-radius flag after its first synchronisation
-  hipEvent_t rg_ev[6] = {};    // phase boundaries of the most recent range call (vers_range_phases), created on first use
+  // range search (flat.hip: flat_range_dev_locked; grow-only like the rest): the protocol's scratch | staged queries | radii and CSR limits
+  // of a host-pointer call (its ids / distances land in o_ids / o_dist)
+  vers::RangeScratch rg;
+  vers::DevBuf rg_q, rg_rad, rg_lims;
   vers::FlatShadow shadow;  // fp16 shadow of the rows + what a single query's exact finish needs (flat_shadow.hpp); empty when it did not fit
   std::mutex mu;
 };

@@ -54,9 +54,7 @@ void ws_destroy(SearchWs& w) {
     if (e) (void)hipEventDestroy(e);
   if (w.evf) (void)hipEventDestroy(w.evf);
   if (w.done) (void)hipEventDestroy(w.done);
-  if (w.rg_pin) (void)hipHostFree(w.rg_pin);
-  for (auto& e : w.rg_ev)
-    if (e) (void)hipEventDestroy(e);
+  w.rg.release();
   if (w.io_pin) (void)hipHostFree(w.io_pin);
   if (w.io_stream) (void)hipStreamDestroy(w.io_stream);
   if (w.ahead_stream) {

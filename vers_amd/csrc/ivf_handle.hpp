@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "kmeans.hpp"
+#include "range_scratch.hpp"
 #include "plan.hip.h"
 #include "util.hip.h"
 #include "wide.hip.h"
@@ -43,16 +44,14 @@ struct SearchWs {
   DevBuf seg_bounds, stamps, quad_counter, fb_part, fb_ctr, c1_ctr;  // (c1_ctr: coarse1_kernel's finished-blocks counter)
   DevBuf clower, lower;  // lower bounds of multi-pass results (coarse ranking of more than 64 lists; top_k > 64)
   DevBuf qp, qil, cpart, probe, pj, lists, pairs, items, groups, qblocks, partials, status, o_ids, o_dist, o_cnt, xpart;
-  // range search (ivf_search.hip: range_dev_locked): hits per (query, probe, segment) slot | their exclusive prefix | radii, CSR limits and
-  // results of a host-pointer call | [0..1] total, [2] status, [3] NaN-radius flag | (key, id) staging of the sorted order + rocPRIM's temporary
-  DevBuf rg_counts, rg_base, rg_rad, rg_lims, rg_misc, rg_stage, rg_tmp;
+  // range search (ivf_search.hip: range_dev_locked): the protocol's scratch | radii and CSR limits of a host-pointer call (its results: o_ids / o_dist)
+  RangeScratch rg;
+  DevBuf rg_rad, rg_lims;
   // filtered search (filter.hip.h): one u64 per 64-row storage tile | the bitmap of a host-pointer call | the call's four counters, then a slot of four
   // words per wave a filtered scan can launch (summed into the counters by filter_stats_fold_kernel)
   DevBuf flt_mask, flt_bits, flt_stats;
   bool no_ahead = false;  // the plan of a filtered call neither consumes a look-ahead slot nor touches a pending request (plan_search)
   DevBuf rg_rlims;  // sharded range search: every rank's CSR limits [world][b + 1] (range_merge.hip.h); the gather itself goes through g_send / g_recv
-  uint32_t* rg_pin = nullptr;  // pinned [4]: where a range call reads its total, status word and NaN-radius flag after its first synchronisation
-  hipEvent_t rg_ev[6] = {};  // phase boundaries of the most recent range call (vers_range_phases), created on first use
   DevBuf g_send, g_recv;  // sharded search without the host in the loop: this rank's [2][b][top_k] partial | the world's
   bool g_poisoned = false;  // g_send holds the poison mark of a locally failed batch (cleared before the next partial is written)
   static constexpr uint32_t kEvRing = 64;  // scan-launch timing ring (measurement hook)

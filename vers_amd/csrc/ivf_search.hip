@@ -13,7 +13,7 @@
 #include "ivf_src.hip.h"
 #include "single.hip.h"
 #include "finish_wide.hip.h"
-#include "range.hip.h"
+#include "range_driver.hip.h"
 #include "range_merge.hip.h"
 #include "filter.hip.h"
 
@@ -189,104 +189,55 @@ __global__ void pack_exhaustive_keys_kernel(const uint64_t* ids, const float* di
 namespace vers {
 namespace ivf {
 
+static size_t filter_wave_slots(const vers_ivf* h) { return (size_t)h->n_cu * 3 * kWavesPerBlock; }  // (filter_scan_kernel: at most 3 blocks per CU)
+
+// One pass of the ordered-chain list scan over the planned items, timed through the scan-timing ring.  Without a filter, option "scan_debug"
+// decides: bit 3 switches the pruning bounds off (A/B runs), bit 4 stamps phases, bit 5 switches the hand-out counter off.  flt: the filtered
+// kernel (filter.hip.h), which knows no diagnosis switches -- bounds and counter always on for QG != 1 -- and launches no more waves than it
+// has counter slots (filter_begin).
 template <int QG>
-int32_t launch_ivf_scan(vers_ivf* h, const IvfSrc<QG>& src, uint32_t items_bound, hipStream_t st, const uint64_t* lower = nullptr) {
-  ScanParams p;
-  p.ld = h->ld;
-  p.n_chunks = h->ld / kChunk;
-  p.k = src.k_keep;
-  p.status = W->st_word();
-  p.debug = scan_debug_flags();
-  p.stamps = nullptr;
+int32_t launch_ivf_scan(vers_ivf* h, const IvfSrc<QG>& src, uint32_t items_bound, hipStream_t st, const uint64_t* lower, const FilterParams* flt = nullptr) {
+  ScanParams p = ivf_scan_params(h, src.k_keep, lower);
+  p.debug = flt ? 0u : scan_debug_flags();
   if (p.debug & 16u) {  // diagnosis only
     if (int32_t rc = W->stamps.reserve(512)) return rc;
     VERS_HIP_TRY(hipMemsetAsync(W->stamps.p, 0, 128, st));
     p.stamps = W->stamps.as<unsigned long long>();
   }
-  // pruning bounds shared between the items of a merge group (they run at different times here, unlike the flat
-  // scans); option "scan_debug" bit 3 switches them off for A/B runs
-  p.bounds = (QG != 1 && !(scan_debug_flags() & 8u)) ? W->partials.as<uint64_t>() + W->ivf_bounds_off : nullptr;
-  p.lower = lower;
-  p.next_quad = nullptr;
-  if (QG != 1 && !(scan_debug_flags() & 32u)) {
-    if (int32_t rc = W->quad_counter.reserve(16)) return rc;
-    VERS_HIP_TRY(hipMemsetAsync(W->quad_counter.p, 0, 16, st));
-    p.next_quad = W->quad_counter.as<uint32_t>();
-  }
+  // pruning bounds shared between the items of a merge group (they run at different times here, unlike the segment scans)
+  if (QG != 1 && !(p.debug & 8u)) p.bounds = W->partials.as<uint64_t>() + W->ivf_bounds_off;
+  if (QG != 1 && !(p.debug & 32u))
+    if (int32_t rc = fresh_quad_counter(st, &p.next_quad)) return rc;
   const size_t lds = scan_lds_bytes(QG, h->ld);
-  if (int32_t rc = h->metric ? scan_prepare_launch(scan_kernel<QG, 1, IvfSrc<QG>>, lds) : scan_prepare_launch(scan_kernel<QG, 0, IvfSrc<QG>>, lds)) return rc;
-  uint32_t blocks = (items_bound + kWavesPerBlock - 1) / kWavesPerBlock;
-  const uint32_t max_blocks = (uint32_t)h->n_cu * scan_blocks_per_cu(QG, h->ld);
-  if (blocks > max_blocks) blocks = max_blocks;
-  if (blocks == 0) blocks = 1;
-  const uint32_t slot = (uint32_t)(W->ev_count % SearchWs::kEvRing);
-  if (W->ev_on) VERS_HIP_TRY(hipEventRecord(W->ev0[slot], st));
-  if (h->metric) hipLaunchKernelGGL((scan_kernel<QG, 1, IvfSrc<QG>>), dim3(blocks), dim3(kWave * kWavesPerBlock), lds, st, src, p);
-  else hipLaunchKernelGGL((scan_kernel<QG, 0, IvfSrc<QG>>), dim3(blocks), dim3(kWave * kWavesPerBlock), lds, st, src, p);
-  VERS_HIP_TRY(hipGetLastError());
-  if (W->ev_on) {
-    VERS_HIP_TRY(hipEventRecord(W->ev1[slot], st));
-    W->ev_count += 1;
-  }
-  return VERS_OK;
+  const uint32_t blocks = scan_grid(h->n_cu, QG, h->ld, items_bound, flt ? (uint32_t)(filter_wave_slots(h) / kWavesPerBlock) : 0xFFFFFFFFu);
+  return with_metric(h->metric, [&](auto m) -> int32_t {
+    constexpr int M = decltype(m)::value;
+    if (flt) return launch_scan_timed(filter_scan_kernel<QG, M, IvfSrc<QG>>, blocks, kWavesPerBlock, lds, st, src, p, *flt);
+    return launch_scan_timed(scan_kernel<QG, M, IvfSrc<QG>>, blocks, kWavesPerBlock, lds, st, src, p);
+  });
 }
 
-// a single query's list scan over item records (scan1_kernel); timed through the same event ring
+// a single query's list scan over item records (scan1_kernel); timed through the same event ring.  No stamps (bit 4 of "scan_debug" masked).
 int32_t launch_scan1(vers_ivf* h, const Scan1Args& a, uint32_t items_bound, hipStream_t st, const uint64_t* lower, bool few_tiles) {
-  ScanParams p;
-  p.ld = h->ld;
-  p.n_chunks = h->ld / kChunk;
-  p.k = a.k_keep;
-  p.status = W->st_word();
+  ScanParams p = ivf_scan_params(h, a.k_keep, lower);
   p.debug = scan_debug_flags() & ~16u;
-  p.stamps = nullptr;
-  p.bounds = nullptr;
-  p.lower = lower;
-  p.next_quad = nullptr;
-  uint32_t blocks = (items_bound + kWavesPerBlock - 1) / kWavesPerBlock;  // (W->items holds items_bound + 4 records: one per launched wave)
-  const uint32_t max_blocks = (uint32_t)h->n_cu * scan_blocks_per_cu(1, h->ld);
-  if (blocks > max_blocks) blocks = max_blocks;
-  if (blocks == 0) blocks = 1;
-  const bool no_ev = !W->ev_on;
-  const uint32_t slot = (uint32_t)(W->ev_count % SearchWs::kEvRing);
   // a tile per block of 16 waves (scan1t_kernel: the whole tile in flight at once) instead of a tile per wave; option "scan1t" = 0: the latter
-  const bool t1_on = opt_get("scan1t", 1) != 0;
   // ... when the query visits few tiles -- the reference's own mode, a few probes --: with a tile per CU and round, 1361 tiles (nprobe = 32 at
   // cfg3 without a shadow) take 72 us against the tile-per-wave kernel's 58
-  if (t1_on && few_tiles && knobs().seg_rows <= 0) {  // (a record is ONE tile unless the tuning knob cut the lists differently)
-    if (int32_t rc = h->metric ? scan_prepare_launch(scan1t_kernel<1>, kT1LdsBytes) : scan_prepare_launch(scan1t_kernel<0>, kT1LdsBytes)) return rc;
-    const uint32_t t_blocks = std::max<uint32_t>(1u, std::min<uint32_t>(items_bound, (uint32_t)h->n_cu));
-    if (!no_ev) VERS_HIP_TRY(hipEventRecord(W->ev0[slot], st));
-    if (h->metric) hipLaunchKernelGGL(scan1t_kernel<1>, dim3(t_blocks), dim3(kWave * kT1Waves), kT1LdsBytes, st, a, p);
-    else hipLaunchKernelGGL(scan1t_kernel<0>, dim3(t_blocks), dim3(kWave * kT1Waves), kT1LdsBytes, st, a, p);
-  } else {
-    if (!no_ev) VERS_HIP_TRY(hipEventRecord(W->ev0[slot], st));
-    if (h->metric) hipLaunchKernelGGL(scan1_kernel<1>, dim3(blocks), dim3(kWave * kWavesPerBlock), 0, st, a, p);
-    else hipLaunchKernelGGL(scan1_kernel<0>, dim3(blocks), dim3(kWave * kWavesPerBlock), 0, st, a, p);
-  }
-  VERS_HIP_TRY(hipGetLastError());
-  if (!no_ev) {
-    VERS_HIP_TRY(hipEventRecord(W->ev1[slot], st));
-    W->ev_count += 1;
-  }
-  return VERS_OK;
+  const bool tile_per_block = opt_get("scan1t", 1) != 0 && few_tiles && knobs().seg_rows <= 0;  // (a record is ONE tile unless the tuning knob cut the lists differently)
+  return with_metric(h->metric, [&](auto m) -> int32_t {
+    constexpr int M = decltype(m)::value;
+    if (tile_per_block)
+      return launch_scan_timed(scan1t_kernel<M>, std::max<uint32_t>(1u, std::min<uint32_t>(items_bound, (uint32_t)h->n_cu)), kT1Waves, kT1LdsBytes, st, a, p);
+    // (W->items holds items_bound + 4 records: one per launched wave)
+    return launch_scan_timed(scan1_kernel<M>, scan_grid(h->n_cu, 1, h->ld, items_bound), kWavesPerBlock, 0, st, a, p);
+  });
 }
 
 // a single query's list scan on the fp16 shadow (scan1h_kernel: a block per record); timed through the same event ring
 int32_t launch_scan1h(vers_ivf* h, const Scan1hArgs& a, uint32_t items_bound, hipStream_t st) {
-  const size_t lds = scan1h_lds_bytes(h->ld);
-  if (int32_t rc = scan_prepare_launch(scan1h_kernel, lds)) return rc;
-  const uint32_t blocks = items_bound ? items_bound : 1u;  // (W->items holds items_bound + 4 records: one per launched block)
-  const bool no_ev = !W->ev_on;
-  const uint32_t slot = (uint32_t)(W->ev_count % SearchWs::kEvRing);
-  if (!no_ev) VERS_HIP_TRY(hipEventRecord(W->ev0[slot], st));
-  hipLaunchKernelGGL(scan1h_kernel, dim3(blocks), dim3(kWave * kS1hWaves), lds, st, a);
-  VERS_HIP_TRY(hipGetLastError());
-  if (!no_ev) {
-    VERS_HIP_TRY(hipEventRecord(W->ev1[slot], st));
-    W->ev_count += 1;
-  }
-  return VERS_OK;
+  // (W->items holds items_bound + 4 records: one per launched block)
+  return launch_scan_timed(scan1h_kernel, items_bound ? items_bound : 1u, kS1hWaves, scan1h_lds_bytes(h->ld), st, a);
 }
 
 // the matrix-core list scan (prescan.hip.h); timed through the same event ring as launch_ivf_scan
@@ -354,20 +305,39 @@ int32_t launch_prescan(vers_ivf* h, const IvfSrc<NQ>& src, uint32_t items_bound,
   } else {
     kern = shadow ? (Kern)prescan_kernel_g<true, NQ, IvfSrc<NQ>> : (Kern)prescan_kernel_g<false, NQ, IvfSrc<NQ>>;
   }
-  if (int32_t rc = scan_prepare_launch(kern, lds)) return rc;
-  uint32_t blocks = (items_bound + kWavesPerBlock - 1) / kWavesPerBlock;
-  uint32_t per_cu = std::max<uint32_t>(1, std::min<uint32_t>(2, (uint32_t)((160u * 1024u) / lds)));  // 1 at d = 768 (measured: as fast as 2)
+  // the grid is the prescan's own: its blocks per CU by its LDS, less the CUs it leaves to the other batches in flight
+  const uint32_t per_cu = std::max<uint32_t>(1, std::min<uint32_t>(2, (uint32_t)((160u * 1024u) / lds)));  // 1 at d = 768 (measured: as fast as 2)
   const uint32_t reserve = scan_reserve(h, st);  // (vers_set_option "scan_reserve_cus"; auto: only while another batch is in flight)
-  const uint32_t max_blocks = ((uint32_t)h->n_cu - reserve) * per_cu;
-  if (blocks > max_blocks) blocks = max_blocks;
-  if (blocks == 0) blocks = 1;
-  const uint32_t slot = (uint32_t)(W->ev_count % SearchWs::kEvRing);
-  if (W->ev_on) VERS_HIP_TRY(hipEventRecord(W->ev0[slot], st));
-  hipLaunchKernelGGL(kern, dim3(blocks), dim3(kWave * kPreWavesG), lds, st, src, p);
-  VERS_HIP_TRY(hipGetLastError());
-  if (W->ev_on) {
-    VERS_HIP_TRY(hipEventRecord(W->ev1[slot], st));
-    W->ev_count += 1;
+  const uint32_t blocks = std::max<uint32_t>(1u, std::min<uint32_t>((items_bound + kWavesPerBlock - 1) / kWavesPerBlock, ((uint32_t)h->n_cu - reserve) * per_cu));
+  return launch_scan_timed(kern, blocks, kPreWavesG, lds, st, src, p);
+}
+
+// The ordered-chain passes of a planned search: 64 result ranks per pass (one pass for top_k <= 64) -- the previous pass's slots and pruning
+// bounds reset, `scan(lower)` (this pass's list scan, the caller's: unfiltered records / items, or the filtered kernel), ivf_merge_kernel.
+// unfiltered: the call that may run in the reference's own mode (a merge group per (query, list)), publishes a host-pointer single query's
+// status with its last merge and starts a noted look-ahead behind its first scan; a filtered call does none of the three.
+template <class Scan>
+int32_t run_chain_passes(vers_ivf* h, const SearchPlan& s, uint32_t b, uint32_t top_k, uint64_t* out_ids, float* out_dist, uint32_t* out_count, uint64_t* out_keys,
+                         bool unfiltered, hipStream_t st, Scan&& scan) {
+  const int ref_mode = unfiltered ? s.ref_mode : 0;
+  for (uint32_t pass = 0; pass < s.n_pass; ++pass) {
+    const uint64_t* lower = pass ? W->lower.as<uint64_t>() : nullptr;
+    if (pass) VERS_HIP_TRY(hipMemsetAsync(W->partials.p, 0xFF, s.part_bytes, st));  // slots and pruning bounds of the previous pass
+    MergeArgs ma;
+    ma.partials = W->partials.as<uint64_t>(); ma.P = s.P; ma.S_max = s.S_max; ma.k_keep = s.k_keep; ma.ref_mode = ref_mode; ma.np = s.np;
+    ma.pj_list = s.pj_list; ma.pj_pref = s.pj_pref; ma.pj_take = s.pj_take; ma.list_off = h->slot_off.as<uint32_t>(); ma.row_ids = h->row_ids.as<uint32_t>();
+    ma.top_k = top_k; ma.rank0 = pass * (uint32_t)kMaxTopK; ma.out_ids = out_ids; ma.out_dist = out_dist; ma.out_count = out_count; ma.out_keys = out_keys;
+    ma.lower_out = s.n_pass > 1 ? W->lower.as<uint64_t>() : (uint64_t*)nullptr;
+    if (unfiltered && W->st_host && pass + 1 == s.n_pass) { ma.st_word = W->st_word(); ma.st_host = W->st_host; }
+    if (int32_t rc = scan(lower)) return rc;
+    if (unfiltered && pass == 0)
+      if (int32_t rc = start_pending_ahead(h, st)) return rc;
+    // four waves while a wave can hold its share of the slots' heads in registers (4096 slots of a merge group: two tree levels
+    // instead of four; same box, single query: 94.2 -> 91.6 us, reference mode 59.0 -> 55.3), sixteen beyond
+    const uint64_t slots_per_group = ref_mode ? s.S_max : (uint64_t)s.P * s.S_max;
+    if (slots_per_group <= 4096) hipLaunchKernelGGL(ivf_merge_kernel<4>, dim3(b), dim3(kWave * 4), 0, st, ma);
+    else hipLaunchKernelGGL(ivf_merge_kernel<kMergeWaves>, dim3(b), dim3(kWave * kMergeWaves), 0, st, ma);
+    VERS_HIP_TRY(hipGetLastError());
   }
   return VERS_OK;
 }
@@ -407,30 +377,17 @@ int32_t search_dev_locked(vers_ivf* h, const float* q_dev, uint64_t ldq_in, uint
   }
   SearchPlan s;
   if (int32_t rc = plan_search(h, q_dev, ldq_in, b, top_k, nprobe, st, s)) return rc;
-  const uint32_t P = s.P, kp = s.kp, k_keep = s.k_keep, n_pass = s.n_pass, seg_rows = s.seg_rows, seg_target = s.seg_target, S_max = s.S_max;
+  const uint32_t P = s.P, kp = s.kp, k_keep = s.k_keep, S_max = s.S_max;
   const int ref_mode = s.ref_mode, QG = s.QG, pre_mode = s.pre_mode;
   const bool one1 = s.one1, one1_pre = s.one1_pre, use_pre = s.use_pre, use_shadow = s.use_shadow, hi_only = s.pre_hi_only && !s.one1_pre;
   const uint64_t items_bound = s.items_bound;
-  const size_t part_bytes = s.part_bytes;
-  uint32_t *const pj_list = s.pj_list, *const pj_pref = s.pj_pref, *const pj_take = s.pj_take, *const np = s.np, *const pj_nq = s.pj_nq;
-  uint32_t *const cnt = s.cnt, *const pair_off = s.pair_off, *const group_off = s.group_off, *const quad_ctr = s.quad_ctr;
+  uint32_t *const pj_list = s.pj_list, *const pj_pref = s.pj_pref, *const pj_nq = s.pj_nq, *const quad_ctr = s.quad_ctr;
   uint32_t *const fail_list = s.fail_list, *const qflags = s.qflags;
   GroupTotals* const tot = s.tot;
   const float* const qp = s.qp;
   SearchWs::CoarseAhead* const took = s.took;
-  auto fill_src = [&](auto& src) {
-    src.rows = h->rows.as<float>(); src.ld = h->ld; src.list_off = h->slot_off.as<uint32_t>();  // (items name lists by slot)
-    src.list_len = h->slot_len.as<uint32_t>(); src.items = W->items.as<ItemDesc>(); src.totals = tot;
-    src.cnt = cnt; src.pair_off = pair_off; src.pairs = W->pairs.as<uint32_t>(); src.group_off = group_off;
-    src.qblocks = W->qblocks.as<float>(); src.qp = qp; src.ldq = h->ldq; src.P = P; src.S_max = S_max; src.k_keep = k_keep;
-    src.seg_rows = seg_rows; src.seg_target = seg_target; src.pj_pref = pj_pref; src.partials = W->partials.as<uint64_t>();
-    src.bound_per_pair = ref_mode ? 1u : 0u;
-  };
-  int32_t rc;
+  const uint32_t bound_per_pair = ref_mode ? 1u : 0u;
   if (use_pre) {
-    IvfSrc<kPreQ> src; fill_src(src);
-    IvfSrc<kPreQNarrow> src_n; fill_src(src_n);  // (rows too long for a 32-query block: 16 queries per block, plan_search chose QG)
-    IvfSrc<kPreQWide> src_w; fill_src(src_w);    // (64 queries per block on the shadow, query block as fp16 hi only)
     // partial lists of the exact re-scan (fail_list [b] + its count, qflags [n_pj]: in the zeroed zone above)
     uint32_t fb_blocks = kFallbackBlocks;  // (a power of two; fewer when P x top_k is large: at most 32 MB of partial lists)
     if (b == 1) fb_blocks = 32;  // (a single query: the launch that almost always finds nothing to do costs 4.3 us with 128 blocks of 16 waves to dispatch; a list per block when it does)
@@ -445,9 +402,12 @@ int32_t search_dev_locked(vers_ivf* h, const float* q_dev, uint64_t ldq_in, uint
       sa.rows_h = h->rows_bf.as<uint16_t>(); sa.xnorm = h->xnorm.as<float>(); sa.recs = W->items.as<Item1Rec>(); sa.n_items_dev = &tot->n_items; sa.qp = qp;
       sa.partials = W->partials.as<uint64_t>(); sa.qflags = qflags; sa.ld = h->ld; sa.kp = kp; sa.metric = (uint32_t)h->metric;
       if (int32_t rc2 = launch_scan1h(h, sa, (uint32_t)items_bound, st)) return rc2;
-    } else if (int32_t rc2 = QG == kPreQWide     ? launch_prescan(h, src_w, (uint32_t)items_bound, kp, qflags, quad_ctr, use_shadow, hi_only, b, st)
-                             : QG == kPreQNarrow ? launch_prescan(h, src_n, (uint32_t)items_bound, kp, qflags, quad_ctr, use_shadow, hi_only, b, st)
-                                                 : launch_prescan(h, src, (uint32_t)items_bound, kp, qflags, quad_ctr, use_shadow, hi_only, b, st)) return rc2;
+    } else {
+      // (plan_search chose QG: 64 queries per block on the shadow with the query block as fp16 hi only, 16 where rows are too long for a 32-query block)
+      if (int32_t rc2 = with_qg<kPreQWide, kPreQNarrow, kPreQ>(QG, [&](auto qg) -> int32_t {
+            return launch_prescan(h, make_ivf_src<decltype(qg)::value>(h, s, bound_per_pair), (uint32_t)items_bound, kp, qflags, quad_ctr, use_shadow, hi_only, b, st);
+          })) return rc2;
+    }
     if (int32_t rc2 = start_pending_ahead(h, st)) return rc2;  // the next batch's coarse quantiser: under this batch's exact finish
     RescoreArgs a;
     a.partials = W->partials.as<uint64_t>(); a.P = P; a.S_max = S_max; a.kp = kp; a.top_k = top_k; a.d_pad = h->ld;
@@ -489,103 +449,31 @@ int32_t search_dev_locked(vers_ivf* h, const float* q_dev, uint64_t ldq_in, uint
     if (took) { VERS_HIP_TRY(hipEventRecord(took->freed, st)); took->freed_rec = true; }
     return VERS_OK;
   }
-  // ordered-chain scans: 64 result ranks per pass (one pass for top_k <= 64)
-  for (uint32_t pass = 0; pass < n_pass; ++pass) {
-    const uint64_t* lower = pass ? W->lower.as<uint64_t>() : nullptr;
-    if (pass) VERS_HIP_TRY(hipMemsetAsync(W->partials.p, 0xFF, part_bytes, st));  // slots and pruning bounds of the previous pass
-    MergeArgs ma;
-    ma.partials = W->partials.as<uint64_t>(); ma.P = P; ma.S_max = S_max; ma.k_keep = k_keep; ma.ref_mode = ref_mode; ma.np = np;
-    ma.pj_list = pj_list; ma.pj_pref = pj_pref; ma.pj_take = pj_take; ma.list_off = h->slot_off.as<uint32_t>(); ma.row_ids = h->row_ids.as<uint32_t>();
-    ma.top_k = top_k; ma.rank0 = pass * (uint32_t)kMaxTopK; ma.out_ids = out_ids; ma.out_dist = out_dist; ma.out_count = out_count; ma.out_keys = out_keys;
-    ma.lower_out = n_pass > 1 ? W->lower.as<uint64_t>() : (uint64_t*)nullptr;
-    if (W->st_host && pass + 1 == n_pass) { ma.st_word = W->st_word(); ma.st_host = W->st_host; }
-    if (one1) {  // the single query's items are records (plan1_block)
-      Scan1Args sa;
-      sa.rows = h->rows.as<float>(); sa.recs = W->items.as<Item1Rec>(); sa.n_items_dev = &tot->n_items; sa.qp = qp;
-      sa.partials = W->partials.as<uint64_t>(); sa.k_keep = k_keep; sa.S_max = S_max; sa.bound_per_pair = ref_mode ? 1u : 0u;
-      const bool few_tiles = ref_mode || (uint64_t)P * (h->n_total / std::max<uint32_t>(1, h->k)) / kWave <= 2ull * (uint64_t)h->n_cu;
-      rc = launch_scan1(h, sa, (uint32_t)items_bound, st, lower, few_tiles);
-    } else if (QG == 1) {
-      IvfSrc<1> src; fill_src(src);
-      rc = launch_ivf_scan(h, src, (uint32_t)items_bound, st, lower);
-    } else if (QG == 8) {
-      IvfSrc<8> src; fill_src(src);
-      rc = launch_ivf_scan(h, src, (uint32_t)items_bound, st, lower);
-    } else {
-      IvfSrc<16> src; fill_src(src);
-      rc = launch_ivf_scan(h, src, (uint32_t)items_bound, st, lower);
-    }
-    if (rc) return rc;
-    if (pass == 0)
-      if (int32_t rc2 = start_pending_ahead(h, st)) return rc2;
-    // four waves while a wave can hold its share of the slots' heads in registers (4096 slots of a merge group: two tree levels
-    // instead of four; same box, single query: 94.2 -> 91.6 us, reference mode 59.0 -> 55.3), sixteen beyond
-    const uint64_t slots_per_group = ref_mode ? S_max : (uint64_t)P * S_max;
-    if (slots_per_group <= 4096) hipLaunchKernelGGL(ivf_merge_kernel<4>, dim3(b), dim3(kWave * 4), 0, st, ma);
-    else hipLaunchKernelGGL(ivf_merge_kernel<kMergeWaves>, dim3(b), dim3(kWave * kMergeWaves), 0, st, ma);
-    VERS_HIP_TRY(hipGetLastError());
-  }
+  if (int32_t rc = run_chain_passes(h, s, b, top_k, out_ids, out_dist, out_count, out_keys, /*unfiltered=*/true, st, [&](const uint64_t* lower) -> int32_t {
+        if (one1) {  // the single query's items are records (plan1_block)
+          Scan1Args sa;
+          sa.rows = h->rows.as<float>(); sa.recs = W->items.as<Item1Rec>(); sa.n_items_dev = &tot->n_items; sa.qp = qp;
+          sa.partials = W->partials.as<uint64_t>(); sa.k_keep = k_keep; sa.S_max = S_max; sa.bound_per_pair = bound_per_pair;
+          const bool few_tiles = ref_mode || (uint64_t)P * (h->n_total / std::max<uint32_t>(1, h->k)) / kWave <= 2ull * (uint64_t)h->n_cu;
+          return launch_scan1(h, sa, (uint32_t)items_bound, st, lower, few_tiles);
+        }
+        return with_qg<1, 8, 16>(QG, [&](auto qg) -> int32_t {
+          return launch_ivf_scan(h, make_ivf_src<decltype(qg)::value>(h, s, bound_per_pair), (uint32_t)items_bound, st, lower);
+        });
+      })) return rc;
   W->tot_valid = true;
   if (took) { VERS_HIP_TRY(hipEventRecord(took->freed, st)); took->freed_rec = true; }
-  return VERS_OK;
-}
-
-int32_t exhaustive_dev_locked(vers_ivf* h, const float* q_dev, uint64_t ldq_in, uint32_t b, uint32_t top_k, uint32_t metric,
-                              uint64_t* out_ids, float* out_dist, uint32_t* out_count, hipStream_t st) {
-  if (b == 0) return VERS_OK;
-  if (top_k == 0) {
-    VERS_HIP_TRY(hipMemsetAsync(out_count, 0, sizeof(uint32_t) * b, st));
-    return VERS_OK;
-  }
-  const int QG = b == 1 ? 1 : 8;
-  const uint32_t n_qg = (b + QG - 1) / QG;
-  if (int32_t rc = W->qil.reserve((size_t)n_qg * h->ldq * QG * sizeof(float))) return rc;
-  if (int32_t rc = launch_stage_queries(q_dev, ldq_in, h->d, W->qil.as<float>(), h->ldq, b, QG, st)) return rc;
-  const uint32_t target_items = (uint32_t)h->n_cu * scan_blocks_per_cu(QG, h->ld) * kWavesPerBlock;
-  uint64_t per = (h->cap_rows * n_qg + target_items - 1) / target_items;
-  const uint32_t seg_rows = (uint32_t)std::min<uint64_t>(round_up64(per ? per : 1, kWave), max_seg_rows(h->ld));
-  uint32_t n_segs = (uint32_t)((h->cap_rows + seg_rows - 1) / seg_rows);
-  if (n_segs == 0) n_segs = 1;
-  const uint32_t k_w = std::min<uint32_t>(top_k, kMaxTopK);  // one key per lane; wider results: 64 ranks per pass (utils.rs:68-82 has no cap)
-  if (int32_t rc = W->xpart.reserve((size_t)b * n_segs * k_w * sizeof(uint64_t))) return rc;
-  if (top_k > (uint32_t)kMaxTopK)
-    if (int32_t rc = W->lower.reserve((size_t)b * sizeof(uint64_t))) return rc;
-  const uint32_t n_segs_pad = QG == 1 ? n_segs : round_up(n_segs, 4);
-  // (a pass past the last stored row finds nothing; 64-bit rank: no wrap near 2^32)
-  for (uint64_t rank0 = 0; rank0 < top_k && (rank0 == 0 || rank0 < h->cap_rows); rank0 += kMaxTopK) {
-    const uint32_t k_pass = (uint32_t)std::min<uint64_t>(kMaxTopK, top_k - rank0);
-    const uint64_t* lower = rank0 ? W->lower.as<uint64_t>() : nullptr;
-    auto fill = [&](auto& src) {
-      src.rows = h->rows.as<float>(); src.n = h->cap_rows; src.ld = h->ld; src.seg_rows = seg_rows; src.n_segs = n_segs;
-      src.n_segs_pad = n_segs_pad;
-      src.queries = W->qil.as<float>(); src.ldq = h->ldq; src.b = b; src.partials = W->xpart.as<uint64_t>(); src.k = k_pass;
-      src.ids = h->row_ids.as<uint32_t>();
-    };
-    int32_t rc;
-    if (QG == 1) {
-      SegSrc<1, true> src; fill(src);
-      rc = launch_seg_scan(h, src, n_segs_pad * n_qg, (int)metric, st, lower);
-    } else {
-      SegSrc<8, true> src; fill(src);
-      rc = launch_seg_scan(h, src, n_segs_pad * n_qg, (int)metric, st, lower);
-    }
-    if (rc) return rc;
-    hipLaunchKernelGGL(seg_merge_kernel, dim3(b), dim3(kWave * kMergeWaves), 0, st, W->xpart.as<uint64_t>(), n_segs, k_pass, top_k, (uint32_t)rank0, out_ids,
-                       out_dist, out_count, top_k > (uint32_t)kMaxTopK ? W->lower.as<uint64_t>() : (uint64_t*)nullptr);
-    VERS_HIP_TRY(hipGetLastError());
-  }
   return VERS_OK;
 }
 
 // ---- filtered top-k search (filter.hip.h): a bitmap of allowed vec ids per call = a virtual removal of the others -------------------
 // The tile mask of the call over `n_rows` storage rows + its zeroed counters.  The mask kernel is bracketed by a record of the scan-timing
 // ring (vers_ivf_scan_times: a filtered call leaves the mask kernel's record, then one per scan pass).
-static size_t filter_wave_slots(const vers_ivf* h) { return (size_t)h->n_cu * 3 * kWavesPerBlock; }
 static int32_t filter_begin(vers_ivf* h, const uint64_t* bits_dev, uint64_t n_bits, uint64_t n_rows, hipStream_t st, FilterParams& f) {
   { const int ev = scan_events_ref().load(); W->ev_on = ev == 1 || ev == 2; }
   const uint64_t n_tiles = (n_rows + kWave - 1) / kWave;
   if (int32_t rc = W->flt_mask.reserve(std::max<size_t>(1, n_tiles) * sizeof(uint64_t))) return rc;
-  // the call's four counters | a slot of four words per wave a filtered scan can launch (filter_scan_kernel: at most 3 blocks per CU)
+  // the call's four counters | a slot of four words per wave a filtered scan can launch
   const size_t stat_words = kFltStats + filter_wave_slots(h) * 4;
   if (int32_t rc = W->flt_stats.reserve(stat_words * sizeof(unsigned long long))) return rc;
   {
@@ -599,21 +487,17 @@ static int32_t filter_begin(vers_ivf* h, const uint64_t* bits_dev, uint64_t n_bi
   f.tile_mask = W->flt_mask.as<uint64_t>();
   f.stats = W->flt_stats.as<unsigned long long>();
   f.wave_slots = f.stats + kFltStats;
-  const uint32_t slot = (uint32_t)(W->ev_count % SearchWs::kEvRing);
-  if (W->ev_on) VERS_HIP_TRY(hipEventRecord(W->ev0[slot], st));
-  if (n_bits == 0 || n_tiles == 0) {  // the empty filter: nothing is allowed
-    VERS_HIP_TRY(hipMemsetAsync(W->flt_mask.p, 0, std::max<size_t>(1, n_tiles) * sizeof(uint64_t), st));
-  } else {
+  return timed_scan(st, [&]() -> int32_t {
+    if (n_bits == 0 || n_tiles == 0) {  // the empty filter: nothing is allowed
+      VERS_HIP_TRY(hipMemsetAsync(W->flt_mask.p, 0, std::max<size_t>(1, n_tiles) * sizeof(uint64_t), st));
+      return VERS_OK;
+    }
     const uint64_t blocks = std::min<uint64_t>((uint64_t)h->n_cu, (n_tiles + kFltMaskThreads / kWave - 1) / (kFltMaskThreads / kWave));
     hipLaunchKernelGGL(filter_tile_mask_kernel, dim3((unsigned)blocks), dim3(kFltMaskThreads), 0, st, (const uint32_t*)h->row_ids.as<uint32_t>(), n_rows, bits_dev, n_bits,
                        W->flt_mask.as<uint64_t>(), f.stats);
     VERS_HIP_TRY(hipGetLastError());
-  }
-  if (W->ev_on) {
-    VERS_HIP_TRY(hipEventRecord(W->ev1[slot], st));
-    W->ev_count += 1;
-  }
-  return VERS_OK;
+    return VERS_OK;
+  });
 }
 
 // the call's counters into the handle's totals, and the workspace noted for vers_ivf_filter_stats
@@ -626,41 +510,61 @@ static int32_t filter_end(vers_ivf* h, hipStream_t st) {
   return VERS_OK;
 }
 
-// one pass of the filtered scan over the planned items; launch bounds and timing ring as launch_ivf_scan's
+// launch_seg_scan's filtered twin -- no bounds, no counter either -- but timed through the scan-timing ring, and no more waves than counter slots
 template <int QG>
-int32_t launch_filter_ivf_scan(vers_ivf* h, const IvfSrc<QG>& src, uint32_t items_bound, const FilterParams& f, hipStream_t st, const uint64_t* lower) {
-  ScanParams p;
-  p.ld = h->ld;
-  p.n_chunks = h->ld / kChunk;
-  p.k = src.k_keep;
-  p.status = W->st_word();
-  p.debug = 0;
-  p.stamps = nullptr;
-  p.bounds = QG != 1 ? W->partials.as<uint64_t>() + W->ivf_bounds_off : nullptr;
-  p.lower = lower;
-  p.next_quad = nullptr;
-  if (QG != 1) {
-    if (int32_t rc = W->quad_counter.reserve(16)) return rc;
-    VERS_HIP_TRY(hipMemsetAsync(W->quad_counter.p, 0, 16, st));
-    p.next_quad = W->quad_counter.as<uint32_t>();
-  }
-  const size_t lds = scan_lds_bytes(QG, h->ld);
-  if (int32_t rc = h->metric ? scan_prepare_launch(filter_scan_kernel<QG, 1, IvfSrc<QG>>, lds) : scan_prepare_launch(filter_scan_kernel<QG, 0, IvfSrc<QG>>, lds)) return rc;
-  uint32_t blocks = (items_bound + kWavesPerBlock - 1) / kWavesPerBlock;
-  const uint32_t max_blocks = (uint32_t)h->n_cu * scan_blocks_per_cu(QG, h->ld);
-  if (blocks > max_blocks) blocks = max_blocks;
-  blocks = std::min<uint32_t>(blocks, (uint32_t)(filter_wave_slots(h) / kWavesPerBlock));  // (a counter slot per launched wave: filter_begin)
-  if (blocks == 0) blocks = 1;
-  const uint32_t slot = (uint32_t)(W->ev_count % SearchWs::kEvRing);
-  if (W->ev_on) VERS_HIP_TRY(hipEventRecord(W->ev0[slot], st));
-  if (h->metric) hipLaunchKernelGGL((filter_scan_kernel<QG, 1, IvfSrc<QG>>), dim3(blocks), dim3(kWave * kWavesPerBlock), lds, st, src, p, f);
-  else hipLaunchKernelGGL((filter_scan_kernel<QG, 0, IvfSrc<QG>>), dim3(blocks), dim3(kWave * kWavesPerBlock), lds, st, src, p, f);
-  VERS_HIP_TRY(hipGetLastError());
-  if (W->ev_on) {
-    VERS_HIP_TRY(hipEventRecord(W->ev1[slot], st));
-    W->ev_count += 1;
+int32_t launch_filter_seg_scan(vers_ivf* h, const SegSrc<QG, true>& src, uint32_t n_items, int metric, const FilterParams& f, hipStream_t st,
+                               const uint64_t* lower) {
+  const ScanParams p = ivf_scan_params(h, src.k, lower);
+  const uint32_t blocks = scan_grid(h->n_cu, QG, h->ld, n_items, (uint32_t)(filter_wave_slots(h) / kWavesPerBlock));
+  return with_metric(metric, [&](auto m) -> int32_t {
+    return launch_scan_timed(filter_scan_kernel<QG, decltype(m)::value, SegSrc<QG, true>>, blocks, kWavesPerBlock, scan_lds_bytes(QG, h->ld), st, src, p, f);
+  });
+}
+
+// The exhaustive top-k scan (utils.rs:68-82 on the stored rows) of the first `n_rows` storage rows: queries staged by group, segment items,
+// per pass of 64 result ranks the segment scan and seg_merge_kernel (seq == vec id already).  What its two callers do differently is theirs
+// to say:
+//   n_rows          the unfiltered call always scans cap_rows; the filtered one scans an index without centroids as zero rows
+//   fixed_seg_rows  option "seg_rows", which only the filtered call honours (0: segments sized for one item per resident wave)
+//   flt             the filtered kernel, timed; refuses a batch whose slots do not fit 32 bits (the unfiltered call never has); resets the
+//                   slots per pass, since a segment without an allowed row writes nothing and its slots must read as empty
+static int32_t run_exhaustive_passes(vers_ivf* h, const float* q_dev, uint64_t ldq_in, uint32_t b, uint32_t top_k, uint32_t metric, uint64_t n_rows,
+                                     int64_t fixed_seg_rows, const FilterParams* flt, uint64_t* out_ids, float* out_dist, uint32_t* out_count, hipStream_t st) {
+  const SegPlan sp = seg_plan(n_rows, b, h->ld, h->n_cu, fixed_seg_rows);
+  if (int32_t rc = W->qil.reserve((size_t)sp.n_qg * h->ldq * sp.QG * sizeof(float))) return rc;
+  if (int32_t rc = launch_stage_queries(q_dev, ldq_in, h->d, W->qil.as<float>(), h->ldq, b, sp.QG, st)) return rc;
+  if (flt && sp.too_large) return fail(VERS_ERR_INVALID, "vers_ivf_search_exhaustive_filtered: batch too large (query x segment slots); split the batch");
+  const uint32_t k_w = std::min<uint32_t>(top_k, kMaxTopK);  // one key per lane; wider results: 64 ranks per pass (utils.rs:68-82 has no cap)
+  const size_t xpart_bytes = (size_t)b * sp.n_segs * k_w * sizeof(uint64_t);
+  if (int32_t rc = W->xpart.reserve(xpart_bytes)) return rc;
+  if (top_k > (uint32_t)kMaxTopK)
+    if (int32_t rc = W->lower.reserve((size_t)b * sizeof(uint64_t))) return rc;
+  uint64_t* const lower_out = top_k > (uint32_t)kMaxTopK ? W->lower.as<uint64_t>() : (uint64_t*)nullptr;
+  // (a pass past the last stored row finds nothing; 64-bit rank: no wrap near 2^32)
+  for (uint64_t rank0 = 0; rank0 < top_k && (rank0 == 0 || rank0 < n_rows); rank0 += kMaxTopK) {
+    const uint32_t k_pass = (uint32_t)std::min<uint64_t>(kMaxTopK, top_k - rank0);
+    const uint64_t* lower = rank0 ? W->lower.as<uint64_t>() : nullptr;
+    if (flt) VERS_HIP_TRY(hipMemsetAsync(W->xpart.p, 0xFF, xpart_bytes, st));
+    if (int32_t rc = with_qg<1, 8>(sp.QG, [&](auto qg) -> int32_t {
+          using Src = SegSrc<decltype(qg)::value, true>;
+          const Src src = make_seg_src<Src>(h->rows.as<float>(), n_rows, h->ld, sp, W->qil.as<float>(), h->ldq, b, W->xpart.as<uint64_t>(), k_pass, h->row_ids.as<uint32_t>());
+          return flt ? launch_filter_seg_scan(h, src, sp.n_items, (int)metric, *flt, st, lower) : launch_seg_scan(h, src, sp.n_items, (int)metric, st, lower);
+        })) return rc;
+    hipLaunchKernelGGL(seg_merge_kernel, dim3(b), dim3(kWave * kMergeWaves), 0, st, W->xpart.as<uint64_t>(), sp.n_segs, k_pass, top_k, (uint32_t)rank0, out_ids,
+                       out_dist, out_count, lower_out);
+    VERS_HIP_TRY(hipGetLastError());
   }
   return VERS_OK;
+}
+
+int32_t exhaustive_dev_locked(vers_ivf* h, const float* q_dev, uint64_t ldq_in, uint32_t b, uint32_t top_k, uint32_t metric,
+                              uint64_t* out_ids, float* out_dist, uint32_t* out_count, hipStream_t st) {
+  if (b == 0) return VERS_OK;
+  if (top_k == 0) {
+    VERS_HIP_TRY(hipMemsetAsync(out_count, 0, sizeof(uint32_t) * b, st));
+    return VERS_OK;
+  }
+  return run_exhaustive_passes(h, q_dev, ldq_in, b, top_k, metric, h->cap_rows, 0, nullptr, out_ids, out_dist, out_count, st);
 }
 
 // Filtered search over the min(nprobe, k) nearest lists, nprobe >= 1: mask kernel, the plan of the ordered-chain scan (the lists are ranked as
@@ -682,70 +586,17 @@ int32_t filtered_dev_locked(vers_ivf* h, const float* q_dev, uint64_t ldq_in, ui
   if (prc) return prc;
   { const int ev = scan_events_ref().load(); W->ev_on = ev == 1 || ev == 2; }  // (the plan set it for an unfiltered call)
   W->tot_valid = true;
-  const uint32_t P = s.P, S_max = s.S_max, k_keep = s.k_keep;
-  auto fill_src = [&](auto& src) {
-    src.rows = h->rows.as<float>(); src.ld = h->ld; src.list_off = h->slot_off.as<uint32_t>();
-    src.list_len = h->slot_len.as<uint32_t>(); src.items = W->items.as<ItemDesc>(); src.totals = s.tot;
-    src.cnt = s.cnt; src.pair_off = s.pair_off; src.pairs = W->pairs.as<uint32_t>(); src.group_off = s.group_off;
-    src.qblocks = W->qblocks.as<float>(); src.qp = s.qp; src.ldq = h->ldq; src.P = P; src.S_max = S_max; src.k_keep = k_keep;
-    src.seg_rows = s.seg_rows; src.seg_target = s.seg_target; src.pj_pref = s.pj_pref; src.partials = W->partials.as<uint64_t>();
-    src.bound_per_pair = 0u;
-  };
-  for (uint32_t pass = 0; pass < s.n_pass; ++pass) {  // 64 result ranks per pass (one pass for top_k <= 64)
-    const uint64_t* lower = pass ? W->lower.as<uint64_t>() : nullptr;
-    if (pass) VERS_HIP_TRY(hipMemsetAsync(W->partials.p, 0xFF, s.part_bytes, st));  // slots and pruning bounds of the previous pass
-    MergeArgs ma;
-    ma.partials = W->partials.as<uint64_t>(); ma.P = P; ma.S_max = S_max; ma.k_keep = k_keep; ma.ref_mode = 0; ma.np = s.np;
-    ma.pj_list = s.pj_list; ma.pj_pref = s.pj_pref; ma.pj_take = s.pj_take; ma.list_off = h->slot_off.as<uint32_t>(); ma.row_ids = h->row_ids.as<uint32_t>();
-    ma.top_k = top_k; ma.rank0 = pass * (uint32_t)kMaxTopK; ma.out_ids = out_ids; ma.out_dist = out_dist; ma.out_count = out_count; ma.out_keys = nullptr;
-    ma.lower_out = s.n_pass > 1 ? W->lower.as<uint64_t>() : (uint64_t*)nullptr;
-    int32_t rc;
-    if (s.QG == 1) { IvfSrc<1> src; fill_src(src); rc = launch_filter_ivf_scan(h, src, (uint32_t)s.items_bound, f, st, lower); }
-    else if (s.QG == 8) { IvfSrc<8> src; fill_src(src); rc = launch_filter_ivf_scan(h, src, (uint32_t)s.items_bound, f, st, lower); }
-    else { IvfSrc<16> src; fill_src(src); rc = launch_filter_ivf_scan(h, src, (uint32_t)s.items_bound, f, st, lower); }
-    if (rc) return rc;
-    if ((uint64_t)P * S_max <= 4096) hipLaunchKernelGGL(ivf_merge_kernel<4>, dim3(b), dim3(kWave * 4), 0, st, ma);
-    else hipLaunchKernelGGL(ivf_merge_kernel<kMergeWaves>, dim3(b), dim3(kWave * kMergeWaves), 0, st, ma);
-    VERS_HIP_TRY(hipGetLastError());
-  }
+  if (int32_t rc = run_chain_passes(h, s, b, top_k, out_ids, out_dist, out_count, nullptr, /*unfiltered=*/false, st, [&](const uint64_t* lower) -> int32_t {
+        return with_qg<1, 8, 16>(s.QG, [&](auto qg) -> int32_t {
+          return launch_ivf_scan(h, make_ivf_src<decltype(qg)::value>(h, s, 0u), (uint32_t)s.items_bound, st, lower, &f);
+        });
+      })) return rc;
   return filter_end(h, st);
 }
 
-template <int QG>
-int32_t launch_filter_seg_scan(vers_ivf* h, const SegSrc<QG, true>& src, uint32_t n_items, int metric, const FilterParams& f, hipStream_t st,
-                               const uint64_t* lower) {
-  ScanParams p;
-  p.ld = h->ld;
-  p.n_chunks = h->ld / kChunk;
-  p.k = src.k;
-  p.status = W->st_word();
-  p.debug = 0;
-  p.stamps = nullptr;
-  p.next_quad = nullptr;
-  p.bounds = nullptr;  // items of a query are concurrent (launch_seg_scan)
-  p.lower = lower;
-  const size_t lds = scan_lds_bytes(QG, h->ld);
-  uint32_t blocks = (n_items + kWavesPerBlock - 1) / kWavesPerBlock;
-  const uint32_t max_blocks = (uint32_t)h->n_cu * scan_blocks_per_cu(QG, h->ld);
-  if (blocks > max_blocks) blocks = max_blocks;
-  blocks = std::min<uint32_t>(blocks, (uint32_t)(filter_wave_slots(h) / kWavesPerBlock));  // (a counter slot per launched wave: filter_begin)
-  if (blocks == 0) blocks = 1;
-  if (int32_t rc = metric ? scan_prepare_launch(filter_scan_kernel<QG, 1, SegSrc<QG, true>>, lds) : scan_prepare_launch(filter_scan_kernel<QG, 0, SegSrc<QG, true>>, lds)) return rc;
-  const uint32_t slot = (uint32_t)(W->ev_count % SearchWs::kEvRing);
-  if (W->ev_on) VERS_HIP_TRY(hipEventRecord(W->ev0[slot], st));
-  if (metric) hipLaunchKernelGGL((filter_scan_kernel<QG, 1, SegSrc<QG, true>>), dim3(blocks), dim3(kWave * kWavesPerBlock), lds, st, src, p, f);
-  else hipLaunchKernelGGL((filter_scan_kernel<QG, 0, SegSrc<QG, true>>), dim3(blocks), dim3(kWave * kWavesPerBlock), lds, st, src, p, f);
-  VERS_HIP_TRY(hipGetLastError());
-  if (W->ev_on) {
-    VERS_HIP_TRY(hipEventRecord(W->ev1[slot], st));
-    W->ev_count += 1;
-  }
-  return VERS_OK;
-}
-
-// exhaustive_dev_locked's sequence with the filtered kernel: every allowed row that is in a list now, ascending (distance, vec id).  Option
-// "seg_rows" fixes the segment length here as it does for the chains.  An index without centroids (a streamed upload in progress included)
-// is scanned as zero rows: counts 0.
+// The exhaustive scan with the filtered kernel: every allowed row that is in a list now, ascending (distance, vec id).  Option "seg_rows" fixes
+// the segment length here as it does for the chains.  An index without centroids (a streamed upload in progress included) is scanned as zero
+// rows: counts 0.
 int32_t exhaustive_filtered_dev_locked(vers_ivf* h, const float* q_dev, uint64_t ldq_in, uint32_t b, uint32_t top_k, uint32_t metric, const uint64_t* bits_dev,
                                        uint64_t n_bits, uint64_t* out_ids, float* out_dist, uint32_t* out_count, hipStream_t st) {
   if (b == 0) return VERS_OK;
@@ -756,41 +607,7 @@ int32_t exhaustive_filtered_dev_locked(vers_ivf* h, const float* q_dev, uint64_t
   const uint64_t n_rows = (h->k == 0 || h->up.open) ? 0 : h->cap_rows;
   FilterParams f;
   if (int32_t rc = filter_begin(h, bits_dev, n_bits, n_rows, st, f)) return rc;
-  const int QG = b == 1 ? 1 : 8;
-  const uint32_t n_qg = (b + QG - 1) / QG;
-  if (int32_t rc = W->qil.reserve((size_t)n_qg * h->ldq * QG * sizeof(float))) return rc;
-  if (int32_t rc = launch_stage_queries(q_dev, ldq_in, h->d, W->qil.as<float>(), h->ldq, b, QG, st)) return rc;
-  const uint32_t target_items = (uint32_t)h->n_cu * scan_blocks_per_cu(QG, h->ld) * kWavesPerBlock;
-  const uint64_t per = (n_rows * n_qg + target_items - 1) / target_items;
-  const long fixed = knobs().seg_rows;
-  const uint32_t seg_rows = (uint32_t)std::min<uint64_t>(round_up64(fixed > 0 ? (uint64_t)fixed : (per ? per : 1), kWave), max_seg_rows(h->ld));
-  uint32_t n_segs = (uint32_t)((n_rows + seg_rows - 1) / seg_rows);
-  if (n_segs == 0) n_segs = 1;
-  const uint32_t n_segs_pad = QG == 1 ? n_segs : round_up(n_segs, 4);
-  if ((uint64_t)b * n_segs >= 0xFFFFFFFFull || (uint64_t)n_segs_pad * n_qg >= 0xFFFFFFFFull)
-    return fail(VERS_ERR_INVALID, "vers_ivf_search_exhaustive_filtered: batch too large (query x segment slots); split the batch");
-  const uint32_t k_w = std::min<uint32_t>(top_k, kMaxTopK);  // one key per lane; wider results: 64 ranks per pass
-  const size_t xpart_bytes = (size_t)b * n_segs * k_w * sizeof(uint64_t);
-  if (int32_t rc = W->xpart.reserve(xpart_bytes)) return rc;
-  if (top_k > (uint32_t)kMaxTopK)
-    if (int32_t rc = W->lower.reserve((size_t)b * sizeof(uint64_t))) return rc;
-  for (uint64_t rank0 = 0; rank0 < top_k && (rank0 == 0 || rank0 < n_rows); rank0 += kMaxTopK) {
-    const uint32_t k_pass = (uint32_t)std::min<uint64_t>(kMaxTopK, top_k - rank0);
-    const uint64_t* lower = rank0 ? W->lower.as<uint64_t>() : nullptr;
-    VERS_HIP_TRY(hipMemsetAsync(W->xpart.p, 0xFF, xpart_bytes, st));  // a segment without an allowed row writes nothing: its slots read as empty
-    auto fill = [&](auto& src) {
-      src.rows = h->rows.as<float>(); src.n = n_rows; src.ld = h->ld; src.seg_rows = seg_rows; src.n_segs = n_segs; src.n_segs_pad = n_segs_pad;
-      src.queries = W->qil.as<float>(); src.ldq = h->ldq; src.b = b; src.partials = W->xpart.as<uint64_t>(); src.k = k_pass;
-      src.ids = h->row_ids.as<uint32_t>();
-    };
-    int32_t rc;
-    if (QG == 1) { SegSrc<1, true> src; fill(src); rc = launch_filter_seg_scan(h, src, n_segs_pad * n_qg, (int)metric, f, st, lower); }
-    else { SegSrc<8, true> src; fill(src); rc = launch_filter_seg_scan(h, src, n_segs_pad * n_qg, (int)metric, f, st, lower); }
-    if (rc) return rc;
-    hipLaunchKernelGGL(seg_merge_kernel, dim3(b), dim3(kWave * kMergeWaves), 0, st, W->xpart.as<uint64_t>(), n_segs, k_pass, top_k, (uint32_t)rank0, out_ids,
-                       out_dist, out_count, top_k > (uint32_t)kMaxTopK ? W->lower.as<uint64_t>() : (uint64_t*)nullptr);
-    VERS_HIP_TRY(hipGetLastError());
-  }
+  if (int32_t rc = run_exhaustive_passes(h, q_dev, ldq_in, b, top_k, metric, n_rows, knobs().seg_rows, &f, out_ids, out_dist, out_count, st)) return rc;
   return filter_end(h, st);
 }
 
@@ -920,257 +737,106 @@ void range_phases_add(uint32_t b, uint64_t total, const float* ms5) {  // (the f
 }
 namespace ivf {
 
-// one pass over the planned items; launch bounds as launch_ivf_scan's
-template <int QG, bool FILL>
-int32_t launch_range_scan(vers_ivf* h, const IvfSrc<QG>& src, uint32_t items_bound, RangeParams p, hipStream_t st) {
-  p.next_quad = nullptr;
-  if (QG != 1) {
-    if (int32_t rc = W->quad_counter.reserve(16)) return rc;
-    VERS_HIP_TRY(hipMemsetAsync(W->quad_counter.p, 0, 16, st));
-    p.next_quad = W->quad_counter.as<uint32_t>();
+// What the range protocol (range_driver.hip.h: range_search_run) walks on the index.  The caller holds the index shared, a leased workspace
+// and status word 1 (HostStatusSlot: the call synchronises and consumes its status itself); a host-pointer call's ids / distances go to the
+// workspace's o_ids / o_dist.  The status word maps as every search's does, except that a spill past the ranked lists has no range meaning.
+struct IvfRangeSource {
+  vers_ivf* h;
+  uint32_t ld() const { return h->ld; }
+  uint32_t* status() const { return W->st_word(); }
+  const uint32_t* row_ids() const { return h->row_ids.as<uint32_t>(); }
+  int32_t status_rc(uint32_t word) const {
+    const int32_t rc = status_to_rc(h, word, W->st_slot);
+    return rc == kRetrySpill ? VERS_ERR_INVALID : rc;
   }
-  const size_t lds = scan_lds_bytes(QG, h->ld);
-  if (int32_t rc = h->metric ? scan_prepare_launch(range_scan_kernel<QG, 1, FILL, IvfSrc<QG>>, lds) : scan_prepare_launch(range_scan_kernel<QG, 0, FILL, IvfSrc<QG>>, lds)) return rc;
-  uint32_t blocks = (items_bound + kWavesPerBlock - 1) / kWavesPerBlock;
-  const uint32_t max_blocks = (uint32_t)h->n_cu * scan_blocks_per_cu(QG, h->ld);
-  if (blocks > max_blocks) blocks = max_blocks;
-  if (blocks == 0) blocks = 1;
-  if (h->metric) hipLaunchKernelGGL((range_scan_kernel<QG, 1, FILL, IvfSrc<QG>>), dim3(blocks), dim3(kWave * kWavesPerBlock), lds, st, src, p);
-  else hipLaunchKernelGGL((range_scan_kernel<QG, 0, FILL, IvfSrc<QG>>), dim3(blocks), dim3(kWave * kWavesPerBlock), lds, st, src, p);
-  VERS_HIP_TRY(hipGetLastError());
-  return VERS_OK;
-}
-
-// A range call that ends in (key, id) pairs instead of (id, distance) -- a rank's PARTIAL of a sharded range search: the same count pass,
-// prefix scan and fill pass over the lists (rows) this handle stores, the keys always staged, the segmented sort without the decode.
-struct RangePartial {
-  uint64_t* keys = nullptr;  // where the keys go, beside ids_dev
-  // The sharded call, between the count and the fill: told the local total, it agrees with the peers (exchange 1), names where keys and ids
-  // go and may call the fill off (go = false).  Without it: the cap protocol of the unsharded calls, on the local total.
-  std::function<int32_t(uint64_t local_total, uint64_t*& keys, uint64_t*& ids, bool& go)> decide;
+  int32_t own_out(uint64_t total, uint64_t*& ids, float*& dist) const {
+    if (int32_t rc = W->o_ids.reserve((size_t)total * sizeof(uint64_t))) return rc;
+    if (int32_t rc = W->o_dist.reserve((size_t)total * sizeof(float))) return rc;
+    ids = W->o_ids.as<uint64_t>(); dist = W->o_dist.as<float>();
+    return VERS_OK;
+  }
 };
 
-// Range search of b >= 1 queries on `st`: plan, count launch, scan, sync and total, fill, sort, sync.  The caller holds the index shared, a
-// leased workspace and status word 1 (HostStatusSlot: the call synchronises and consumes its status itself).  own_out: ids / distances go to
-// the workspace's o_ids / o_dist, sized by the total (the host-pointer call copies them out), else to ids_dev / dist_dev -- when total <= cap.
-// part: (key, id) pairs instead -- default order ascending by key, walk order ascending sequence number (a sharded rank walks its probes in
-// rank order); dist_dev is not used.
-int32_t range_dev_locked(vers_ivf* h, const float* q_dev, uint64_t ldq_in, uint32_t b, const float* radius_dev, uint32_t nprobe, uint32_t flags,
+// the rows of the min(nprobe, k) nearest lists: the plan of the ordered-chain scan (IvfSrc<QG> items, slot = pair * S_max + segment).  A partial
+// keeps walk order when asked to: ascending sequence number (a sharded rank walks its probes in rank order).
+struct ProbedRangeSource : IvfRangeSource {
+  static constexpr bool kKeyIds = false, kPartials = true;
+  const char* who = "vers_ivf_range_search";
+  const float* q_dev; uint64_t ldq_in; uint32_t b, nprobe;
+  SearchPlan s;
+  bool planned = false;
+  ProbedRangeSource(vers_ivf* hh, const float* q, uint64_t ldq, uint32_t bb, uint32_t np) : IvfRangeSource{hh}, q_dev(q), ldq_in(ldq), b(bb), nprobe(np) {}
+  hipStream_t st_ = nullptr;
+  ~ProbedRangeSource() {  // a look-ahead slot the plan consumed is free again behind whatever the call queued, on EVERY way out
+    if (planned && s.took && hipEventRecord(s.took->freed, st_) == hipSuccess) s.took->freed_rec = true;
+  }
+  int32_t prepare(hipStream_t st, uint64_t& slots_per_query) {
+    if (int32_t rc = plan_search(h, q_dev, ldq_in, b, 1, nprobe, st, s, true)) return rc;  // (top_k = 1: the partial slots no kernel here reads stay small)
+    planned = true; st_ = st;
+    W->tot_valid = true;
+    slots_per_query = (uint64_t)s.P * s.S_max;
+    if ((uint64_t)b * slots_per_query >= 0xFFFFFFFFull) return fail(VERS_ERR_INVALID, "vers_ivf_range_search: batch too large (query x probe x segment slots); split the batch");
+    return VERS_OK;
+  }
+  bool walk_order(uint32_t flags, bool) const { return (flags & VERS_RANGE_WALK_ORDER) != 0; }
+  template <class Fill>
+  int32_t launch(Fill, RangeParams p, hipStream_t st) const {  // hand-out counter as launch_ivf_scan's; no pruning: every row within the radius counts
+    return with_qg<1, 8, 16>(s.QG, [&](auto qg) -> int32_t {
+      constexpr int QG = decltype(qg)::value;
+      if (QG != 1)
+        if (int32_t rc = fresh_quad_counter(st, &p.next_quad)) return rc;
+      return launch_range_pass<QG, Fill::value>(h->n_cu, h->ld, h->metric, make_ivf_src<QG>(h, s, 0u), (uint32_t)s.items_bound, p, st);
+    });
+  }
+};
+
+// every row that is in a list NOW, over the storage rows (SegSrc<QG, true>: the exhaustive top-k scan's items, cut as option "seg_rows" says when
+// set).  An index without centroids (a streamed upload in progress included) is scanned as zero rows: total 0, every limit 0, the radii still
+// checked -- what the exhaustive top-k search makes of it.  A partial has no walk order: storage order across ranks has no key (its entry
+// points refuse the flag).
+struct StoredRangeSource : IvfRangeSource {
+  static constexpr bool kKeyIds = true, kPartials = true;
+  const char* who = "vers_ivf_range_search_exhaustive";
+  const float* q_dev; uint64_t ldq_in; uint32_t b, metric;
+  uint64_t n_rows = 0;
+  SegPlan sp{};
+  StoredRangeSource(vers_ivf* hh, const float* q, uint64_t ldq, uint32_t bb, uint32_t m) : IvfRangeSource{hh}, q_dev(q), ldq_in(ldq), b(bb), metric(m) {}
+  int32_t prepare(hipStream_t st, uint64_t& slots_per_query) {
+    n_rows = (h->k == 0 || h->up.open) ? 0 : h->cap_rows;
+    sp = seg_plan(n_rows, b, h->ld, h->n_cu, knobs().seg_rows);
+    if (int32_t rc = W->qil.reserve((size_t)sp.n_qg * h->ldq * sp.QG * sizeof(float))) return rc;
+    if (int32_t rc = launch_stage_queries(q_dev, ldq_in, h->d, W->qil.as<float>(), h->ldq, b, sp.QG, st)) return rc;
+    if (sp.too_large) return fail(VERS_ERR_INVALID, "vers_ivf_range_search_exhaustive: batch too large (query x segment slots); split the batch");
+    slots_per_query = sp.n_segs;
+    return VERS_OK;
+  }
+  bool walk_order(uint32_t flags, bool partial) const { return (flags & VERS_RANGE_WALK_ORDER) != 0 && !partial; }
+  void launch_key_ids(const uint64_t* keys, uint64_t n, uint64_t* ids, hipStream_t st) const {
+    hipLaunchKernelGGL(range_key_ids_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, keys, n, ids);
+  }
+  template <class Fill>
+  int32_t launch(Fill, const RangeParams& p, hipStream_t st) const {
+    return with_qg<1, 8>(sp.QG, [&](auto qg) -> int32_t {
+      constexpr int QG = decltype(qg)::value;
+      using Src = SegSrc<QG, true>;
+      return launch_range_pass<QG, Fill::value>(h->n_cu, h->ld, (int)metric,
+                                                make_seg_src<Src>(h->rows.as<float>(), n_rows, h->ld, sp, W->qil.as<float>(), h->ldq, b, nullptr, 0, h->row_ids.as<uint32_t>()),
+                                                sp.n_items, p, st);
+    });
+  }
+};
+
+// A range search on the index, on `st`: over the probed lists, or (probed = false) over every stored row under the metric given in place of
+// nprobe.  own_out / part: range_search_run.
+int32_t range_dev_locked(vers_ivf* h, bool probed, const float* q_dev, uint64_t ldq_in, uint32_t b, const float* radius_dev, uint32_t nprobe_or_metric, uint32_t flags,
                          uint64_t* lims_dev, uint64_t* ids_dev, float* dist_dev, uint64_t cap, bool own_out, uint64_t* out_total, hipStream_t st,
                          RangePartial* part = nullptr) {
-  for (auto& e : W->rg_ev)
-    if (!e) VERS_HIP_TRY(hipEventCreate(&e));
-  VERS_HIP_TRY(hipEventRecord(W->rg_ev[0], st));
-  SearchPlan s;
-  if (int32_t rc = plan_search(h, q_dev, ldq_in, b, 1, nprobe, st, s, true)) return rc;  // (top_k = 1: the partial slots no kernel here reads stay small)
-  struct AheadGuard {  // a look-ahead slot the plan consumed is free again behind whatever this call queued, on EVERY way out
-    SearchPlan& s; hipStream_t st;
-    ~AheadGuard() {
-      if (s.took && hipEventRecord(s.took->freed, st) == hipSuccess) s.took->freed_rec = true;
-    }
-  } ahead_guard{s, st};
-  W->tot_valid = true;
-  const uint32_t P = s.P, S_max = s.S_max;
-  const uint64_t per_q = (uint64_t)P * S_max, n_slots = (uint64_t)b * per_q;
-  if (n_slots >= 0xFFFFFFFFull) return fail(VERS_ERR_INVALID, "vers_ivf_range_search: batch too large (query x probe x segment slots); split the batch");
-  auto fill_src = [&](auto& src) {
-    src.rows = h->rows.as<float>(); src.ld = h->ld; src.list_off = h->slot_off.as<uint32_t>();
-    src.list_len = h->slot_len.as<uint32_t>(); src.items = W->items.as<ItemDesc>(); src.totals = s.tot;
-    src.cnt = s.cnt; src.pair_off = s.pair_off; src.pairs = W->pairs.as<uint32_t>(); src.group_off = s.group_off;
-    src.qblocks = W->qblocks.as<float>(); src.qp = s.qp; src.ldq = h->ldq; src.P = P; src.S_max = S_max; src.k_keep = s.k_keep;
-    src.seg_rows = s.seg_rows; src.seg_target = s.seg_target; src.pj_pref = s.pj_pref; src.partials = W->partials.as<uint64_t>();
-    src.bound_per_pair = 0u;
-  };
-  auto pass = [&](auto fill_tag, const RangeParams& rp) -> int32_t {
-    constexpr bool FILL = decltype(fill_tag)::value;
-    if (s.QG == 1) { IvfSrc<1> src; fill_src(src); return launch_range_scan<1, FILL>(h, src, (uint32_t)s.items_bound, rp, st); }
-    if (s.QG == 8) { IvfSrc<8> src; fill_src(src); return launch_range_scan<8, FILL>(h, src, (uint32_t)s.items_bound, rp, st); }
-    IvfSrc<16> src; fill_src(src);
-    return launch_range_scan<16, FILL>(h, src, (uint32_t)s.items_bound, rp, st);
-  };
-  const size_t scan_tmp = range_scan_temp_bytes((size_t)n_slots + 1);
-  if (int32_t rc = W->rg_counts.reserve(((size_t)n_slots + 1) * sizeof(uint32_t))) return rc;
-  if (int32_t rc = W->rg_base.reserve(((size_t)n_slots + 1) * sizeof(uint64_t))) return rc;
-  if (int32_t rc = W->rg_misc.reserve(16)) return rc;
-  if (int32_t rc = W->rg_tmp.reserve(scan_tmp)) return rc;
-  VERS_HIP_TRY(hipMemsetAsync(W->rg_counts.p, 0, ((size_t)n_slots + 1) * sizeof(uint32_t), st));  // (+ one zero count: the prefix's last entry is the total)
-  VERS_HIP_TRY(hipMemsetAsync(W->rg_misc.p, 0, 16, st));
-  RangeParams rp;
-  rp.ld = h->ld; rp.n_chunks = h->ld / kChunk; rp.status = W->st_word(); rp.radius = radius_dev; rp.counts = W->rg_counts.as<uint32_t>();
-  rp.base = W->rg_base.as<uint64_t>(); rp.row_ids = h->row_ids.as<uint32_t>(); rp.out_keys = nullptr; rp.out_ids = nullptr; rp.out_dist = nullptr; rp.next_quad = nullptr;
-  VERS_HIP_TRY(hipEventRecord(W->rg_ev[1], st));
-  if (int32_t rc = pass(std::false_type{}, rp)) return rc;
-  VERS_HIP_TRY(hipEventRecord(W->rg_ev[2], st));
-  if (int32_t rc = range_scan_counts(W->rg_counts.as<uint32_t>(), W->rg_base.as<uint64_t>(), (size_t)n_slots + 1, W->rg_tmp.p, scan_tmp, st)) return rc;
-  hipLaunchKernelGGL(range_lims_kernel, dim3((b + 1 + 255) / 256), dim3(256), 0, st, (const uint64_t*)W->rg_base.as<uint64_t>(), per_q, b, radius_dev,
-                     (const uint32_t*)W->st_word(), lims_dev, W->rg_misc.as<uint32_t>());
-  VERS_HIP_TRY(hipGetLastError());
-  if (!W->rg_pin) VERS_HIP_TRY(hipHostMalloc((void**)&W->rg_pin, 16, hipHostMallocDefault));  // pinned landing words: total | status | NaN radius
-  VERS_HIP_TRY(hipMemcpyAsync(W->rg_pin, W->rg_misc.p, 16, hipMemcpyDeviceToHost, st));
-  VERS_HIP_TRY(hipEventRecord(W->rg_ev[3], st));
-  VERS_HIP_TRY(hipStreamSynchronize(st));
-  uint32_t misc[4];
-  std::memcpy(misc, W->rg_pin, sizeof(misc));
-  if (int32_t rc = status_to_rc(h, misc[2], W->st_slot)) return rc == kRetrySpill ? VERS_ERR_INVALID : rc;
-  if (misc[3]) return fail(VERS_ERR_INVALID, "vers_ivf_range_search: NaN radius");
-  const uint64_t total = ((uint64_t)misc[1] << 32) | misc[0];
-  if (total > 0xFFFFFFFFull) return fail(VERS_ERR_INVALID, "vers_ivf_range_search: more than 2^32 - 1 results in one call; split the batch");
-  *out_total = total;
-  float ms[5] = {};
-  auto phases = [&](int n_ev) {
-    for (int i = 0; i + 1 < n_ev; ++i) (void)hipEventElapsedTime(&ms[i], W->rg_ev[i], W->rg_ev[i + 1]);
-    range_phases_add(b, total, ms);
-  };
-  bool go = total != 0 && total <= cap;  // (too small a buffer: the limits are complete, ids / distances untouched)
-  if (part && part->decide)
-    if (int32_t rc = part->decide(total, part->keys, ids_dev, go)) return rc;
-  if (!go) { phases(4); return VERS_OK; }
-  if (own_out) {
-    if (int32_t rc = W->o_ids.reserve((size_t)total * sizeof(uint64_t))) return rc;
-    if (int32_t rc = W->o_dist.reserve((size_t)total * sizeof(float))) return rc;
-    ids_dev = W->o_ids.as<uint64_t>(); dist_dev = W->o_dist.as<float>();
+  if (probed) {
+    ProbedRangeSource src(h, q_dev, ldq_in, b, nprobe_or_metric);
+    return range_search_run(src, W->rg, b, radius_dev, flags, lims_dev, ids_dev, dist_dev, cap, own_out, out_total, st, part);
   }
-  const bool walk = (flags & VERS_RANGE_WALK_ORDER) != 0;
-  size_t sort_tmp = 0;
-  uint64_t *k_in = nullptr, *k_out = nullptr, *i_in = nullptr;
-  if (!walk) {  // staging of the sorted order: keys in | keys out | ids in, + rocPRIM's temporary (a partial's sorted keys are its result: keys in | ids in)
-    sort_tmp = range_sort_temp_bytes((uint32_t)total, b);
-    if (int32_t rc = W->rg_stage.reserve((part ? 2 : 3) * (size_t)total * sizeof(uint64_t))) return rc;
-    if (int32_t rc = W->rg_tmp.reserve(sort_tmp)) return rc;
-    k_in = W->rg_stage.as<uint64_t>(); k_out = part ? part->keys : k_in + total; i_in = k_in + (part ? 1 : 2) * total;
-  }
-  if (part) { rp.out_keys = walk ? part->keys : k_in; rp.out_ids = walk ? ids_dev : i_in; rp.out_dist = nullptr; }  // (a key beside every id, in walk order too)
-  else { rp.out_keys = walk ? nullptr : k_in; rp.out_ids = walk ? ids_dev : i_in; rp.out_dist = dist_dev; }
-  if (int32_t rc = pass(std::true_type{}, rp)) return rc;
-  VERS_HIP_TRY(hipEventRecord(W->rg_ev[4], st));
-  if (!walk) {
-    if (int32_t rc = range_sort_segments(k_in, k_out, i_in, ids_dev, (uint32_t)total, b, lims_dev, W->rg_tmp.p, sort_tmp, st)) return rc;
-    if (!part) {
-      hipLaunchKernelGGL(range_decode_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (const uint64_t*)k_out, total, dist_dev);
-      VERS_HIP_TRY(hipGetLastError());
-    }
-  }
-  VERS_HIP_TRY(hipEventRecord(W->rg_ev[5], st));
-  VERS_HIP_TRY(hipStreamSynchronize(st));
-  phases(6);
-  return VERS_OK;
-}
-
-// ---- exhaustive range search: every row that is in a list NOW, over the storage rows (SegSrc<QG, true>: exhaustive_dev_locked's items) ----
-template <int QG, bool FILL>
-int32_t launch_range_seg_scan(vers_ivf* h, const SegSrc<QG, true>& src, uint32_t n_items, int metric, const RangeParams& p, hipStream_t st) {
-  const size_t lds = scan_lds_bytes(QG, h->ld);
-  if (int32_t rc = metric ? scan_prepare_launch(range_scan_kernel<QG, 1, FILL, SegSrc<QG, true>>, lds) : scan_prepare_launch(range_scan_kernel<QG, 0, FILL, SegSrc<QG, true>>, lds)) return rc;
-  uint32_t blocks = (n_items + kWavesPerBlock - 1) / kWavesPerBlock;
-  const uint32_t max_blocks = (uint32_t)h->n_cu * scan_blocks_per_cu(QG, h->ld);
-  if (blocks > max_blocks) blocks = max_blocks;
-  if (blocks == 0) blocks = 1;
-  if (metric) hipLaunchKernelGGL((range_scan_kernel<QG, 1, FILL, SegSrc<QG, true>>), dim3(blocks), dim3(kWave * kWavesPerBlock), lds, st, src, p);
-  else hipLaunchKernelGGL((range_scan_kernel<QG, 0, FILL, SegSrc<QG, true>>), dim3(blocks), dim3(kWave * kWavesPerBlock), lds, st, src, p);
-  VERS_HIP_TRY(hipGetLastError());
-  return VERS_OK;
-}
-
-// As range_dev_locked, without a plan: stage, count launch, scan, sync and total, fill, sort, sync.  The caller holds the index shared, a leased
-// workspace and status word 1.  An index without centroids (a streamed upload in progress included) is scanned as zero rows: total 0, every
-// limit 0, the radii still checked -- what the exhaustive top-k search makes of it.
-int32_t range_exhaustive_dev_locked(vers_ivf* h, const float* q_dev, uint64_t ldq_in, uint32_t b, const float* radius_dev, uint32_t metric, uint32_t flags,
-                                    uint64_t* lims_dev, uint64_t* ids_dev, float* dist_dev, uint64_t cap, bool own_out, uint64_t* out_total, hipStream_t st,
-                                    RangePartial* part = nullptr) {
-  for (auto& e : W->rg_ev)
-    if (!e) VERS_HIP_TRY(hipEventCreate(&e));
-  VERS_HIP_TRY(hipEventRecord(W->rg_ev[0], st));
-  const uint64_t n_rows = (h->k == 0 || h->up.open) ? 0 : h->cap_rows;
-  const int QG = b == 1 ? 1 : 8;
-  const uint32_t n_qg = (b + QG - 1) / QG;
-  if (int32_t rc = W->qil.reserve((size_t)n_qg * h->ldq * QG * sizeof(float))) return rc;
-  if (int32_t rc = launch_stage_queries(q_dev, ldq_in, h->d, W->qil.as<float>(), h->ldq, b, QG, st)) return rc;
-  // segments as exhaustive_dev_locked sizes them, or as option "seg_rows" fixes them
-  const uint32_t target_items = (uint32_t)h->n_cu * scan_blocks_per_cu(QG, h->ld) * kWavesPerBlock;
-  const uint64_t per = (n_rows * n_qg + target_items - 1) / target_items;
-  const long fixed = knobs().seg_rows;
-  const uint32_t seg_rows = (uint32_t)std::min<uint64_t>(round_up64(fixed > 0 ? (uint64_t)fixed : (per ? per : 1), kWave), max_seg_rows(h->ld));
-  uint32_t n_segs = (uint32_t)((n_rows + seg_rows - 1) / seg_rows);
-  if (n_segs == 0) n_segs = 1;
-  const uint32_t n_segs_pad = QG == 1 ? n_segs : round_up(n_segs, 4);
-  const uint64_t n_slots = (uint64_t)b * n_segs;
-  if (n_slots >= 0xFFFFFFFFull || (uint64_t)n_segs_pad * n_qg >= 0xFFFFFFFFull)
-    return fail(VERS_ERR_INVALID, "vers_ivf_range_search_exhaustive: batch too large (query x segment slots); split the batch");
-  const uint32_t n_items = n_segs_pad * n_qg;
-  const size_t scan_tmp = range_scan_temp_bytes((size_t)n_slots + 1);
-  if (int32_t rc = W->rg_counts.reserve(((size_t)n_slots + 1) * sizeof(uint32_t))) return rc;
-  if (int32_t rc = W->rg_base.reserve(((size_t)n_slots + 1) * sizeof(uint64_t))) return rc;
-  if (int32_t rc = W->rg_misc.reserve(16)) return rc;
-  if (int32_t rc = W->rg_tmp.reserve(scan_tmp)) return rc;
-  VERS_HIP_TRY(hipMemsetAsync(W->rg_counts.p, 0, ((size_t)n_slots + 1) * sizeof(uint32_t), st));  // (+ one zero count: the prefix's last entry is the total)
-  VERS_HIP_TRY(hipMemsetAsync(W->rg_misc.p, 0, 16, st));
-  RangeParams rp;
-  rp.ld = h->ld; rp.n_chunks = h->ld / kChunk; rp.status = W->st_word(); rp.radius = radius_dev; rp.counts = W->rg_counts.as<uint32_t>();
-  rp.base = W->rg_base.as<uint64_t>(); rp.row_ids = h->row_ids.as<uint32_t>(); rp.out_keys = nullptr; rp.out_ids = nullptr; rp.out_dist = nullptr; rp.next_quad = nullptr;
-  auto pass = [&](auto fill_tag) -> int32_t {
-    constexpr bool FILL = decltype(fill_tag)::value;
-    auto fill = [&](auto& src) {
-      src.rows = h->rows.as<float>(); src.n = n_rows; src.ld = h->ld; src.seg_rows = seg_rows; src.n_segs = n_segs; src.n_segs_pad = n_segs_pad;
-      src.queries = W->qil.as<float>(); src.ldq = h->ldq; src.b = b; src.partials = nullptr; src.k = 0; src.ids = h->row_ids.as<uint32_t>();
-    };
-    if (QG == 1) { SegSrc<1, true> src; fill(src); return launch_range_seg_scan<1, FILL>(h, src, n_items, (int)metric, rp, st); }
-    SegSrc<8, true> src; fill(src);
-    return launch_range_seg_scan<8, FILL>(h, src, n_items, (int)metric, rp, st);
-  };
-  VERS_HIP_TRY(hipEventRecord(W->rg_ev[1], st));
-  if (int32_t rc = pass(std::false_type{})) return rc;
-  VERS_HIP_TRY(hipEventRecord(W->rg_ev[2], st));
-  if (int32_t rc = range_scan_counts(W->rg_counts.as<uint32_t>(), W->rg_base.as<uint64_t>(), (size_t)n_slots + 1, W->rg_tmp.p, scan_tmp, st)) return rc;
-  hipLaunchKernelGGL(range_lims_kernel, dim3((b + 1 + 255) / 256), dim3(256), 0, st, (const uint64_t*)W->rg_base.as<uint64_t>(), (uint64_t)n_segs, b, radius_dev,
-                     (const uint32_t*)W->st_word(), lims_dev, W->rg_misc.as<uint32_t>());
-  VERS_HIP_TRY(hipGetLastError());
-  if (!W->rg_pin) VERS_HIP_TRY(hipHostMalloc((void**)&W->rg_pin, 16, hipHostMallocDefault));  // pinned landing words: total | status | NaN radius
-  VERS_HIP_TRY(hipMemcpyAsync(W->rg_pin, W->rg_misc.p, 16, hipMemcpyDeviceToHost, st));
-  VERS_HIP_TRY(hipEventRecord(W->rg_ev[3], st));
-  VERS_HIP_TRY(hipStreamSynchronize(st));
-  uint32_t misc[4];
-  std::memcpy(misc, W->rg_pin, sizeof(misc));
-  if (int32_t rc = status_to_rc(h, misc[2], W->st_slot)) return rc == kRetrySpill ? VERS_ERR_INVALID : rc;
-  if (misc[3]) return fail(VERS_ERR_INVALID, "vers_ivf_range_search_exhaustive: NaN radius");
-  const uint64_t total = ((uint64_t)misc[1] << 32) | misc[0];
-  if (total > 0xFFFFFFFFull) return fail(VERS_ERR_INVALID, "vers_ivf_range_search_exhaustive: more than 2^32 - 1 results in one call; split the batch");
-  *out_total = total;
-  float ms[5] = {};
-  auto phases = [&](int n_ev) {
-    for (int i = 0; i + 1 < n_ev; ++i) (void)hipEventElapsedTime(&ms[i], W->rg_ev[i], W->rg_ev[i + 1]);
-    range_phases_add(b, total, ms);
-  };
-  bool go = total != 0 && total <= cap;  // (too small a buffer: the limits are complete, ids / distances untouched)
-  if (part && part->decide)
-    if (int32_t rc = part->decide(total, part->keys, ids_dev, go)) return rc;
-  if (!go) { phases(4); return VERS_OK; }
-  if (own_out) {
-    if (int32_t rc = W->o_ids.reserve((size_t)total * sizeof(uint64_t))) return rc;
-    if (int32_t rc = W->o_dist.reserve((size_t)total * sizeof(float))) return rc;
-    ids_dev = W->o_ids.as<uint64_t>(); dist_dev = W->o_dist.as<float>();
-  }
-  const bool walk = (flags & VERS_RANGE_WALK_ORDER) != 0 && !part;  // (a partial has no walk order: storage order across ranks has no key; refused by its entry points)
-  size_t sort_tmp = 0;
-  uint64_t *k_in = nullptr, *k_out = nullptr;
-  if (!walk) {  // staging of the sorted order: keys in | keys out (the key's low word is the id), + rocPRIM's temporary
-    sort_tmp = range_sort_keys_temp_bytes((uint32_t)total, b);
-    if (int32_t rc = W->rg_stage.reserve(2 * (size_t)total * sizeof(uint64_t))) return rc;
-    if (int32_t rc = W->rg_tmp.reserve(sort_tmp)) return rc;
-    k_in = W->rg_stage.as<uint64_t>(); k_out = part ? part->keys : k_in + total;
-  }
-  rp.out_keys = k_in; rp.out_ids = walk ? ids_dev : nullptr; rp.out_dist = walk ? dist_dev : nullptr;
-  if (int32_t rc = pass(std::true_type{})) return rc;
-  VERS_HIP_TRY(hipEventRecord(W->rg_ev[4], st));
-  if (!walk) {
-    if (int32_t rc = range_sort_segment_keys(k_in, k_out, (uint32_t)total, b, lims_dev, W->rg_tmp.p, sort_tmp, st)) return rc;
-    if (part) hipLaunchKernelGGL(range_key_ids_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (const uint64_t*)k_out, total, ids_dev);
-    else hipLaunchKernelGGL(range_decode_ids_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (const uint64_t*)k_out, total, ids_dev, dist_dev);
-    VERS_HIP_TRY(hipGetLastError());
-  }
-  VERS_HIP_TRY(hipEventRecord(W->rg_ev[5], st));
-  VERS_HIP_TRY(hipStreamSynchronize(st));
-  phases(6);
-  return VERS_OK;
+  StoredRangeSource src(h, q_dev, ldq_in, b, nprobe_or_metric);
+  return range_search_run(src, W->rg, b, radius_dev, flags, lims_dev, ids_dev, dist_dev, cap, own_out, out_total, st, part);
 }
 
 // what both exhaustive entry points refuse before they touch the device
@@ -1671,158 +1337,103 @@ int32_t vers_ivf_filter_stats(vers_ivf_t* h, uint64_t* out4, uint64_t* out4_tota
   return VERS_OK;
 }
 
-int32_t vers_ivf_range_search_dev(vers_ivf_t* h, const float* queries_dev, uint64_t ldq_floats, uint32_t b, const float* radius_dev, uint32_t nprobe,
-                                  uint32_t flags, uint64_t* out_lims_dev, uint64_t* out_ids_dev, float* out_dist_dev, uint64_t cap, uint64_t* out_total,
-                                  void* stream) {
+// The four device-pointer range entries: the probed lists or (probed = false) every stored row under the metric given in place of nprobe; the
+// full result (ids + distances) or, with keys_dev in place of dist_dev, a rank's partial (keys + ids).
+static int32_t range_dev_common(vers_ivf_t* h, const char* who, bool probed, bool partial, const float* queries_dev, uint64_t ldq_floats, uint32_t b,
+                                const float* radius_dev, uint32_t nprobe_or_metric, uint32_t flags, uint64_t* out_lims_dev, uint64_t* out_keys_dev, uint64_t* out_ids_dev,
+                                float* out_dist_dev, uint64_t cap, uint64_t* out_total, void* stream) {
   if (!h) return fail(VERS_ERR_INVALID, "null handle");
-  if (!out_total) return fail(VERS_ERR_INVALID, "vers_ivf_range_search_dev: out_total is required");
+  if (!out_total) return fail(VERS_ERR_INVALID, std::string(who) + ": out_total is required");
   *out_total = 0;
-  if (b && (!queries_dev || ldq_floats < h->d || !radius_dev || !out_lims_dev || (cap && (!out_ids_dev || !out_dist_dev))))
-    return fail(VERS_ERR_INVALID, "vers_ivf_range_search_dev: bad arguments");
+  if (!probed && nprobe_or_metric > VERS_METRIC_COSDIST) return fail(VERS_ERR_INVALID, "unknown metric");
+  if (b && (!queries_dev || ldq_floats < h->d || !radius_dev || !out_lims_dev || (cap && (!out_ids_dev || (partial ? !out_keys_dev : !out_dist_dev)))))
+    return fail(VERS_ERR_INVALID, std::string(who) + ": bad arguments");
   if (b == 0) return VERS_OK;
   std::shared_lock<std::shared_mutex> lk(h->index);
-  if (int32_t rc = range_check(h, "vers_ivf_range_search_dev", nprobe, flags)) return rc;
+  if (int32_t rc = probed ? range_check(h, who, nprobe_or_metric, flags, partial) : range_exhaustive_check(h, who, flags, partial)) return rc;
   DeviceGuard g(h->device);
   WsLease lease(h, true, (hipStream_t)stream);
   if (lease.rc) return lease.rc;
   if (int32_t rc = lease.order_on((hipStream_t)stream)) return rc;
   HostStatusSlot slot(h);
-  return range_dev_locked(h, queries_dev, ldq_floats, b, radius_dev, nprobe, flags, out_lims_dev, out_ids_dev, out_dist_dev, cap, false, out_total,
-                          (hipStream_t)stream);
+  RangePartial part;
+  part.keys = out_keys_dev;
+  return range_dev_locked(h, probed, queries_dev, ldq_floats, b, radius_dev, nprobe_or_metric, flags, out_lims_dev, out_ids_dev, out_dist_dev, cap, false, out_total,
+                          (hipStream_t)stream, partial ? &part : nullptr);
 }
 
-int32_t vers_ivf_range_search(vers_ivf_t* h, const float* queries, uint64_t q_stride_bytes, uint32_t b, const float* radius, uint32_t nprobe, uint32_t flags,
-                              uint64_t* out_lims, uint64_t* out_ids, float* out_dist, uint64_t cap, uint64_t* out_total) {
-  if (!h) return fail(VERS_ERR_INVALID, "null handle");
-  if (!out_total) return fail(VERS_ERR_INVALID, "vers_ivf_range_search: out_total is required");
-  *out_total = 0;
-  if (b && (!queries || q_stride_bytes < (uint64_t)h->d * 4 || q_stride_bytes % 4 || !radius || !out_lims || (cap && (!out_ids || !out_dist))))
-    return fail(VERS_ERR_INVALID, "vers_ivf_range_search: bad arguments");
-  if (b == 0) return VERS_OK;
-  for (uint32_t i = 0; i < b; ++i)
-    if (radius[i] != radius[i]) return fail(VERS_ERR_INVALID, "vers_ivf_range_search: NaN radius");
-  std::shared_lock<std::shared_mutex> lk(h->index);
-  if (int32_t rc = range_check(h, "vers_ivf_range_search", nprobe, flags)) return rc;
-  DeviceGuard g(h->device);
-  WsLease lease(h);
-  if (lease.rc) return lease.rc;
-  HostStatusSlot slot(h);
-  HostIo io;
-  if (int32_t rc = host_io_begin(h, queries, q_stride_bytes, b, 0, io)) return rc;  // (the pinned query staging of every host-pointer call)
-  lease.st = W->io_stream;
-  if (int32_t rc = W->rg_rad.reserve((size_t)b * sizeof(float))) return rc;
-  if (int32_t rc = W->rg_lims.reserve(((size_t)b + 1) * sizeof(uint64_t))) return rc;
-  VERS_HIP_TRY(hipMemcpyAsync(W->rg_rad.p, radius, (size_t)b * sizeof(float), hipMemcpyHostToDevice, W->io_stream));
-  uint64_t total = 0;
-  if (int32_t rc = range_dev_locked(h, io.q_dev, h->d, b, W->rg_rad.as<float>(), nprobe, flags, W->rg_lims.as<uint64_t>(), nullptr, nullptr, cap, true, &total,
-                                    W->io_stream)) return rc;
-  VERS_HIP_TRY(hipMemcpy(out_lims, W->rg_lims.p, ((size_t)b + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost));
-  *out_total = total;
-  if (total == 0 || total > cap) return VERS_OK;
-  VERS_HIP_TRY(hipMemcpy(out_ids, W->o_ids.p, (size_t)total * sizeof(uint64_t), hipMemcpyDeviceToHost));
-  VERS_HIP_TRY(hipMemcpy(out_dist, W->o_dist.p, (size_t)total * sizeof(float), hipMemcpyDeviceToHost));
-  return VERS_OK;
+int32_t vers_ivf_range_search_dev(vers_ivf_t* h, const float* queries_dev, uint64_t ldq_floats, uint32_t b, const float* radius_dev, uint32_t nprobe,
+                                  uint32_t flags, uint64_t* out_lims_dev, uint64_t* out_ids_dev, float* out_dist_dev, uint64_t cap, uint64_t* out_total,
+                                  void* stream) {
+  return range_dev_common(h, "vers_ivf_range_search_dev", true, false, queries_dev, ldq_floats, b, radius_dev, nprobe, flags, out_lims_dev, nullptr, out_ids_dev,
+                          out_dist_dev, cap, out_total, stream);
 }
 
 int32_t vers_ivf_range_search_exhaustive_dev(vers_ivf_t* h, const float* queries_dev, uint64_t ldq_floats, uint32_t b, const float* radius_dev,
                                              uint32_t metric, uint32_t flags, uint64_t* out_lims_dev, uint64_t* out_ids_dev, float* out_dist_dev,
                                              uint64_t cap, uint64_t* out_total, void* stream) {
-  if (!h) return fail(VERS_ERR_INVALID, "null handle");
-  if (!out_total) return fail(VERS_ERR_INVALID, "vers_ivf_range_search_exhaustive_dev: out_total is required");
-  *out_total = 0;
-  if (metric > VERS_METRIC_COSDIST) return fail(VERS_ERR_INVALID, "unknown metric");
-  if (b && (!queries_dev || ldq_floats < h->d || !radius_dev || !out_lims_dev || (cap && (!out_ids_dev || !out_dist_dev))))
-    return fail(VERS_ERR_INVALID, "vers_ivf_range_search_exhaustive_dev: bad arguments");
-  if (b == 0) return VERS_OK;
-  std::shared_lock<std::shared_mutex> lk(h->index);
-  if (int32_t rc = range_exhaustive_check(h, "vers_ivf_range_search_exhaustive_dev", flags)) return rc;
-  DeviceGuard g(h->device);
-  WsLease lease(h, true, (hipStream_t)stream);
-  if (lease.rc) return lease.rc;
-  if (int32_t rc = lease.order_on((hipStream_t)stream)) return rc;
-  HostStatusSlot slot(h);
-  return range_exhaustive_dev_locked(h, queries_dev, ldq_floats, b, radius_dev, metric, flags, out_lims_dev, out_ids_dev, out_dist_dev, cap, false,
-                                     out_total, (hipStream_t)stream);
-}
-
-int32_t vers_ivf_range_search_exhaustive(vers_ivf_t* h, const float* queries, uint64_t q_stride_bytes, uint32_t b, const float* radius, uint32_t metric,
-                                         uint32_t flags, uint64_t* out_lims, uint64_t* out_ids, float* out_dist, uint64_t cap, uint64_t* out_total) {
-  if (!h) return fail(VERS_ERR_INVALID, "null handle");
-  if (!out_total) return fail(VERS_ERR_INVALID, "vers_ivf_range_search_exhaustive: out_total is required");
-  *out_total = 0;
-  if (metric > VERS_METRIC_COSDIST) return fail(VERS_ERR_INVALID, "unknown metric");
-  if (b && (!queries || q_stride_bytes < (uint64_t)h->d * 4 || q_stride_bytes % 4 || !radius || !out_lims || (cap && (!out_ids || !out_dist))))
-    return fail(VERS_ERR_INVALID, "vers_ivf_range_search_exhaustive: bad arguments");
-  if (b == 0) return VERS_OK;
-  for (uint32_t i = 0; i < b; ++i)
-    if (radius[i] != radius[i]) return fail(VERS_ERR_INVALID, "vers_ivf_range_search_exhaustive: NaN radius");
-  std::shared_lock<std::shared_mutex> lk(h->index);
-  if (int32_t rc = range_exhaustive_check(h, "vers_ivf_range_search_exhaustive", flags)) return rc;
-  DeviceGuard g(h->device);
-  WsLease lease(h);
-  if (lease.rc) return lease.rc;
-  HostStatusSlot slot(h);
-  HostIo io;
-  if (int32_t rc = host_io_begin(h, queries, q_stride_bytes, b, 0, io)) return rc;  // (the pinned query staging of every host-pointer call)
-  lease.st = W->io_stream;
-  if (int32_t rc = W->rg_rad.reserve((size_t)b * sizeof(float))) return rc;
-  if (int32_t rc = W->rg_lims.reserve(((size_t)b + 1) * sizeof(uint64_t))) return rc;
-  VERS_HIP_TRY(hipMemcpyAsync(W->rg_rad.p, radius, (size_t)b * sizeof(float), hipMemcpyHostToDevice, W->io_stream));
-  uint64_t total = 0;
-  if (int32_t rc = range_exhaustive_dev_locked(h, io.q_dev, h->d, b, W->rg_rad.as<float>(), metric, flags, W->rg_lims.as<uint64_t>(), nullptr, nullptr, cap, true,
-                                               &total, W->io_stream)) return rc;
-  VERS_HIP_TRY(hipMemcpy(out_lims, W->rg_lims.p, ((size_t)b + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost));
-  *out_total = total;
-  if (total == 0 || total > cap) return VERS_OK;
-  VERS_HIP_TRY(hipMemcpy(out_ids, W->o_ids.p, (size_t)total * sizeof(uint64_t), hipMemcpyDeviceToHost));
-  VERS_HIP_TRY(hipMemcpy(out_dist, W->o_dist.p, (size_t)total * sizeof(float), hipMemcpyDeviceToHost));
-  return VERS_OK;
+  return range_dev_common(h, "vers_ivf_range_search_exhaustive_dev", false, false, queries_dev, ldq_floats, b, radius_dev, metric, flags, out_lims_dev, nullptr,
+                          out_ids_dev, out_dist_dev, cap, out_total, stream);
 }
 
 // ---- sharded range search: a rank's partial, the cross-rank merge, and the two exchanges around them (vers_hip.h) ----
 int32_t vers_ivf_range_search_partial_dev(vers_ivf_t* h, const float* queries_dev, uint64_t ldq_floats, uint32_t b, const float* radius_dev, uint32_t nprobe,
                                           uint32_t flags, uint64_t* out_lims_dev, uint64_t* out_keys_dev, uint64_t* out_ids_dev, uint64_t cap, uint64_t* out_total,
                                           void* stream) {
-  if (!h) return fail(VERS_ERR_INVALID, "null handle");
-  if (!out_total) return fail(VERS_ERR_INVALID, "vers_ivf_range_search_partial_dev: out_total is required");
-  *out_total = 0;
-  if (b && (!queries_dev || ldq_floats < h->d || !radius_dev || !out_lims_dev || (cap && (!out_keys_dev || !out_ids_dev))))
-    return fail(VERS_ERR_INVALID, "vers_ivf_range_search_partial_dev: bad arguments");
-  if (b == 0) return VERS_OK;
-  std::shared_lock<std::shared_mutex> lk(h->index);
-  if (int32_t rc = range_check(h, "vers_ivf_range_search_partial_dev", nprobe, flags, true)) return rc;
-  DeviceGuard g(h->device);
-  WsLease lease(h, true, (hipStream_t)stream);
-  if (lease.rc) return lease.rc;
-  if (int32_t rc = lease.order_on((hipStream_t)stream)) return rc;
-  HostStatusSlot slot(h);
-  RangePartial part;
-  part.keys = out_keys_dev;
-  return range_dev_locked(h, queries_dev, ldq_floats, b, radius_dev, nprobe, flags, out_lims_dev, out_ids_dev, nullptr, cap, false, out_total, (hipStream_t)stream,
-                          &part);
+  return range_dev_common(h, "vers_ivf_range_search_partial_dev", true, true, queries_dev, ldq_floats, b, radius_dev, nprobe, flags, out_lims_dev, out_keys_dev,
+                          out_ids_dev, nullptr, cap, out_total, stream);
 }
 
 int32_t vers_ivf_range_search_exhaustive_partial_dev(vers_ivf_t* h, const float* queries_dev, uint64_t ldq_floats, uint32_t b, const float* radius_dev,
                                                      uint32_t metric, uint32_t flags, uint64_t* out_lims_dev, uint64_t* out_keys_dev, uint64_t* out_ids_dev,
                                                      uint64_t cap, uint64_t* out_total, void* stream) {
+  return range_dev_common(h, "vers_ivf_range_search_exhaustive_partial_dev", false, true, queries_dev, ldq_floats, b, radius_dev, metric, flags, out_lims_dev,
+                          out_keys_dev, out_ids_dev, nullptr, cap, out_total, stream);
+}
+
+// the two host-pointer range entries: queries through the pinned staging of every host-pointer call, radii and limits through the workspace
+static int32_t range_host_common(vers_ivf_t* h, const char* who, bool probed, const float* queries, uint64_t q_stride_bytes, uint32_t b, const float* radius,
+                                 uint32_t nprobe_or_metric, uint32_t flags, uint64_t* out_lims, uint64_t* out_ids, float* out_dist, uint64_t cap, uint64_t* out_total) {
   if (!h) return fail(VERS_ERR_INVALID, "null handle");
-  if (!out_total) return fail(VERS_ERR_INVALID, "vers_ivf_range_search_exhaustive_partial_dev: out_total is required");
+  if (!out_total) return fail(VERS_ERR_INVALID, std::string(who) + ": out_total is required");
   *out_total = 0;
-  if (metric > VERS_METRIC_COSDIST) return fail(VERS_ERR_INVALID, "unknown metric");
-  if (b && (!queries_dev || ldq_floats < h->d || !radius_dev || !out_lims_dev || (cap && (!out_keys_dev || !out_ids_dev))))
-    return fail(VERS_ERR_INVALID, "vers_ivf_range_search_exhaustive_partial_dev: bad arguments");
+  if (!probed && nprobe_or_metric > VERS_METRIC_COSDIST) return fail(VERS_ERR_INVALID, "unknown metric");
+  if (b && (!queries || q_stride_bytes < (uint64_t)h->d * 4 || q_stride_bytes % 4 || !radius || !out_lims || (cap && (!out_ids || !out_dist))))
+    return fail(VERS_ERR_INVALID, std::string(who) + ": bad arguments");
   if (b == 0) return VERS_OK;
+  for (uint32_t i = 0; i < b; ++i)
+    if (radius[i] != radius[i]) return fail(VERS_ERR_INVALID, std::string(who) + ": NaN radius");
   std::shared_lock<std::shared_mutex> lk(h->index);
-  if (int32_t rc = range_exhaustive_check(h, "vers_ivf_range_search_exhaustive_partial_dev", flags, true)) return rc;
+  if (int32_t rc = probed ? range_check(h, who, nprobe_or_metric, flags) : range_exhaustive_check(h, who, flags)) return rc;
   DeviceGuard g(h->device);
-  WsLease lease(h, true, (hipStream_t)stream);
+  WsLease lease(h);
   if (lease.rc) return lease.rc;
-  if (int32_t rc = lease.order_on((hipStream_t)stream)) return rc;
   HostStatusSlot slot(h);
-  RangePartial part;
-  part.keys = out_keys_dev;
-  return range_exhaustive_dev_locked(h, queries_dev, ldq_floats, b, radius_dev, metric, flags, out_lims_dev, out_ids_dev, nullptr, cap, false, out_total,
-                                     (hipStream_t)stream, &part);
+  HostIo io;
+  if (int32_t rc = host_io_begin(h, queries, q_stride_bytes, b, 0, io)) return rc;  // (the pinned query staging of every host-pointer call)
+  lease.st = W->io_stream;
+  if (int32_t rc = W->rg_rad.reserve((size_t)b * sizeof(float))) return rc;
+  if (int32_t rc = W->rg_lims.reserve(((size_t)b + 1) * sizeof(uint64_t))) return rc;
+  VERS_HIP_TRY(hipMemcpyAsync(W->rg_rad.p, radius, (size_t)b * sizeof(float), hipMemcpyHostToDevice, W->io_stream));
+  uint64_t total = 0;
+  if (int32_t rc = range_dev_locked(h, probed, io.q_dev, h->d, b, W->rg_rad.as<float>(), nprobe_or_metric, flags, W->rg_lims.as<uint64_t>(), nullptr, nullptr, cap, true,
+                                    &total, W->io_stream)) return rc;
+  VERS_HIP_TRY(hipMemcpy(out_lims, W->rg_lims.p, ((size_t)b + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost));
+  *out_total = total;
+  if (total == 0 || total > cap) return VERS_OK;
+  VERS_HIP_TRY(hipMemcpy(out_ids, W->o_ids.p, (size_t)total * sizeof(uint64_t), hipMemcpyDeviceToHost));
+  VERS_HIP_TRY(hipMemcpy(out_dist, W->o_dist.p, (size_t)total * sizeof(float), hipMemcpyDeviceToHost));
+  return VERS_OK;
+}
+
+int32_t vers_ivf_range_search(vers_ivf_t* h, const float* queries, uint64_t q_stride_bytes, uint32_t b, const float* radius, uint32_t nprobe, uint32_t flags,
+                              uint64_t* out_lims, uint64_t* out_ids, float* out_dist, uint64_t cap, uint64_t* out_total) {
+  return range_host_common(h, "vers_ivf_range_search", true, queries, q_stride_bytes, b, radius, nprobe, flags, out_lims, out_ids, out_dist, cap, out_total);
+}
+
+int32_t vers_ivf_range_search_exhaustive(vers_ivf_t* h, const float* queries, uint64_t q_stride_bytes, uint32_t b, const float* radius, uint32_t metric,
+                                         uint32_t flags, uint64_t* out_lims, uint64_t* out_ids, float* out_dist, uint64_t cap, uint64_t* out_total) {
+  return range_host_common(h, "vers_ivf_range_search_exhaustive", false, queries, q_stride_bytes, b, radius, metric, flags, out_lims, out_ids, out_dist, cap, out_total);
 }
 
 int32_t vers_range_merge_dev(const uint64_t* keys_dev, const uint64_t* ids_dev, uint64_t rank_stride, const uint64_t* rank_lims_dev, uint32_t world, uint32_t b,
@@ -1922,9 +1533,9 @@ static int32_t range_sharded_common(vers_ivf_t* h, const vers_comm_t* comm, cons
     local_total = total;
     int32_t lrc = VERS_OK;
     if (total != 0 && total <= cap) {  // the fill's staging BEFORE the agreement: scratch that does not fit is a status the peers learn
-      lrc = W->rg_stage.reserve(2 * (size_t)total * sizeof(uint64_t));
+      lrc = W->rg.stage.reserve(2 * (size_t)total * sizeof(uint64_t));
       if (!lrc && !(flags & VERS_RANGE_WALK_ORDER))
-        lrc = W->rg_tmp.reserve(exhaustive_metric >= 0 ? range_sort_keys_temp_bytes((uint32_t)total, b) : range_sort_temp_bytes((uint32_t)total, b));
+        lrc = W->rg.tmp.reserve(exhaustive_metric >= 0 ? range_sort_keys_temp_bytes((uint32_t)total, b) : range_sort_temp_bytes((uint32_t)total, b));
     }
     if (int32_t rc = exchange1(lrc, true)) return rc;
     go = false;
@@ -1945,10 +1556,8 @@ static int32_t range_sharded_common(vers_ivf_t* h, const vers_comm_t* comm, cons
   if (!rc) {
     rc = W->rg_lims.reserve(nw * sizeof(uint64_t));
     if (!rc)
-      rc = exhaustive_metric >= 0 ? range_exhaustive_dev_locked(h, queries_dev, ldq_floats, b, radius_dev, (uint32_t)exhaustive_metric, flags, W->rg_lims.as<uint64_t>(),
-                                                                nullptr, nullptr, cap, false, &local_total, st, &part)
-                                  : range_dev_locked(h, queries_dev, ldq_floats, b, radius_dev, nprobe, flags, W->rg_lims.as<uint64_t>(), nullptr, nullptr, cap, false,
-                                                     &local_total, st, &part);
+      rc = range_dev_locked(h, exhaustive_metric < 0, queries_dev, ldq_floats, b, radius_dev, exhaustive_metric >= 0 ? (uint32_t)exhaustive_metric : nprobe, flags,
+                            W->rg_lims.as<uint64_t>(), nullptr, nullptr, cap, false, &local_total, st, &part);
   }
   if (!agreed) {  // the local count did not get as far as the agreement: enter it with the failure
     const int32_t arc = exchange1(rc ? rc : fail(VERS_ERR_HIP, who + ": the local count ended without a verdict"), false);

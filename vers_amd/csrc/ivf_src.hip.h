@@ -1,9 +1,10 @@
 // ivf_src.hip.h -- how the scan engine (scan.hip.h) sees the index: work-item sources of the coarse quantiser / exhaustive scan
-// (SegSrc), the inverted-list scans (IvfSrc) and the single query's item records (Item1Rec / Rec1Src), + the launch of a
-// segment scan, which the planner (coarse quantiser) and the search (exhaustive scan) share.
+// (SegSrc), the inverted-list scans (IvfSrc) and the single query's item records (Item1Rec / Rec1Src), + what the host
+// needs to launch them on a leased workspace: the timing ring's bracket, the parameter and source fills, and the launch of a segment scan,
+// which the planner (coarse quantiser) and the search (exhaustive scan) share.
 #pragma once
 #include "ivf_handle.hpp"
-#include "scan.hip.h"
+#include "scan_launch.hip.h"
 
 namespace vers {
 
@@ -155,33 +156,77 @@ struct Scan1Args {
 
 namespace vers {
 namespace ivf {
-template <int QG, bool SEQ_IDS>
-int32_t launch_seg_scan(vers_ivf* h, const SegSrc<QG, SEQ_IDS>& src, uint32_t n_items, int metric, hipStream_t st,
-                        const uint64_t* lower = nullptr) {
+
+// ---- launching the index's scans (the leased workspace W: status word, timing ring, hand-out counter) -------------------------------
+// The bracket of the scan-timing ring (vers_ivf_scan_times, option "scan_events") around whatever launch() queues on st: a record before it
+// and, when it succeeded, one behind it and a ring entry more.
+template <class F>
+inline int32_t timed_scan(hipStream_t st, F&& launch) {
+  const uint32_t slot = (uint32_t)(W->ev_count % SearchWs::kEvRing);
+  if (W->ev_on) VERS_HIP_TRY(hipEventRecord(W->ev0[slot], st));
+  if (int32_t rc = launch()) return rc;
+  if (W->ev_on) {
+    VERS_HIP_TRY(hipEventRecord(W->ev1[slot], st));
+    W->ev_count += 1;
+  }
+  return VERS_OK;
+}
+// launch_scan inside the bracket (the launch attribute is set ahead of it)
+template <class K, class... A>
+inline int32_t launch_scan_timed(K kern, uint32_t blocks, int waves, size_t lds, hipStream_t st, const A&... args) {
+  if (int32_t rc = scan_prepare_launch(kern, lds)) return rc;
+  return timed_scan(st, [&]() -> int32_t {
+    hipLaunchKernelGGL(kern, dim3(blocks), dim3(kWave * waves), lds, st, args...);
+    VERS_HIP_TRY(hipGetLastError());
+    return VERS_OK;
+  });
+}
+
+// what every scan of the index's rows shares; as it stands: no pruning bounds, no hand-out counter, no diagnosis switches
+inline ScanParams ivf_scan_params(const vers_ivf* h, uint32_t k, const uint64_t* lower) {
   ScanParams p;
   p.ld = h->ld;
   p.n_chunks = h->ld / kChunk;
-  p.k = src.k;
+  p.k = k;
   p.status = W->st_word();
   p.debug = 0;
   p.stamps = nullptr;
+  p.bounds = nullptr;
+  p.lower = lower;  // (results of more than 64 keys: 64 ranks per pass)
   p.next_quad = nullptr;
-  p.bounds = nullptr;  // items of a query are concurrent: nothing to prune, and the atomics would contend
-  p.lower = lower;     // (P > 64 ranked lists: 64 ranks per pass)
-  const size_t lds = scan_lds_bytes(QG, h->ld);
-  uint32_t blocks = (n_items + kWavesPerBlock - 1) / kWavesPerBlock;
-  const uint32_t max_blocks = (uint32_t)h->n_cu * scan_blocks_per_cu(QG, h->ld);
-  if (blocks > max_blocks) blocks = max_blocks;
-  if (blocks == 0) blocks = 1;
-  if (metric == 0) {
-    if (int32_t rc = scan_prepare_launch(scan_kernel<QG, 0, SegSrc<QG, SEQ_IDS>>, lds)) return rc;
-    hipLaunchKernelGGL((scan_kernel<QG, 0, SegSrc<QG, SEQ_IDS>>), dim3(blocks), dim3(kWave * kWavesPerBlock), lds, st, src, p);
-  } else {
-    if (int32_t rc = scan_prepare_launch(scan_kernel<QG, 1, SegSrc<QG, SEQ_IDS>>, lds)) return rc;
-    hipLaunchKernelGGL((scan_kernel<QG, 1, SegSrc<QG, SEQ_IDS>>), dim3(blocks), dim3(kWave * kWavesPerBlock), lds, st, src, p);
-  }
-  VERS_HIP_TRY(hipGetLastError());
+  return p;
+}
+// the batched kernels' dynamic quad hand-out: the workspace's counter, zeroed on st for the launch that follows
+inline int32_t fresh_quad_counter(hipStream_t st, uint32_t** out) {
+  if (int32_t rc = W->quad_counter.reserve(16)) return rc;
+  VERS_HIP_TRY(hipMemsetAsync(W->quad_counter.p, 0, 16, st));
+  *out = W->quad_counter.as<uint32_t>();
   return VERS_OK;
+}
+
+// the planned items of a search as the list-scan kernels see them.  bound_per_pair: pruning bounds (and merges) per (query, list) -- the
+// reference's own mode -- instead of per query
+template <int QG>
+inline IvfSrc<QG> make_ivf_src(const vers_ivf* h, const SearchPlan& s, uint32_t bound_per_pair) {
+  IvfSrc<QG> src;
+  src.rows = h->rows.as<float>(); src.ld = h->ld; src.list_off = h->slot_off.as<uint32_t>();  // (items name lists by slot)
+  src.list_len = h->slot_len.as<uint32_t>(); src.items = W->items.as<ItemDesc>(); src.totals = s.tot;
+  src.cnt = s.cnt; src.pair_off = s.pair_off; src.pairs = W->pairs.as<uint32_t>(); src.group_off = s.group_off;
+  src.qblocks = W->qblocks.as<float>(); src.qp = s.qp; src.ldq = h->ldq; src.P = s.P; src.S_max = s.S_max; src.k_keep = s.k_keep;
+  src.seg_rows = s.seg_rows; src.seg_target = s.seg_target; src.pj_pref = s.pj_pref; src.partials = W->partials.as<uint64_t>();
+  src.bound_per_pair = bound_per_pair;
+  return src;
+}
+
+// a segment scan (coarse quantiser, exhaustive scan); not timed.  Items of a query are concurrent: nothing to prune, and the atomics of a
+// shared bound would contend
+template <int QG, bool SEQ_IDS>
+int32_t launch_seg_scan(vers_ivf* h, const SegSrc<QG, SEQ_IDS>& src, uint32_t n_items, int metric, hipStream_t st,
+                        const uint64_t* lower = nullptr) {
+  const ScanParams p = ivf_scan_params(h, src.k, lower);
+  return with_metric(metric, [&](auto m) -> int32_t {
+    return launch_scan(scan_kernel<QG, decltype(m)::value, SegSrc<QG, SEQ_IDS>>, scan_grid(h->n_cu, QG, h->ld, n_items), kWavesPerBlock, scan_lds_bytes(QG, h->ld), st, src, p);
+  });
 }
 
 }  // namespace ivf

@@ -782,15 +782,7 @@ __global__ __launch_bounds__(kWave * kWavesPerBlock) void scan_kernel(Src src, S
   if (__ballot(nan_seen) != 0 && lane == 0) atomicOr(p.status, 1u);
 }
 
-// dynamic LDS of a batched scan launch (one interleaved query block) and the resident blocks per CU it allows
-inline size_t scan_lds_bytes(int QG, uint32_t ld) { return QG == 1 ? 0 : (size_t)ld * QG * sizeof(float) + 16; }
-inline uint32_t scan_blocks_per_cu(int QG, uint32_t ld) {
-  if (QG == 1) return 3;                                   // 12 waves/CU at <= 168 VGPRs
-  const size_t b = scan_lds_bytes(QG, ld);
-  const uint32_t by_lds = (uint32_t)((160u * 1024u) / (b ? b : 1));
-  const uint32_t by_vgpr = 2;                              // two tiles per step: <= 256 VGPRs, 8 waves/CU
-  return by_lds < 1 ? 1 : (by_lds > by_vgpr ? by_vgpr : by_lds);
-}
+// (scan_lds_bytes / scan_blocks_per_cu / scan_grid -- the dynamic LDS of a batched scan launch, the resident blocks per CU, the grid: seg_plan.hpp)
 template <class K>
 inline int32_t scan_prepare_launch(K kernel, size_t lds_bytes) {
   if (lds_bytes > 160u * 1024u) return fail(VERS_ERR_INVALID, "vector dimension too large for a batched scan (query block exceeds LDS)");
