@@ -511,6 +511,56 @@ int32_t vers_ivf_search_exhaustive_filtered_dev(vers_ivf_t* h, const float* quer
                                                 uint32_t metric, const uint64_t* allowed_bits_dev, uint64_t n_bits, uint64_t* out_ids_dev,
                                                 float* out_dist_dev, uint32_t* out_count_dev, void* stream);
 int32_t vers_ivf_filter_stats(vers_ivf_t* h, uint64_t* out4, uint64_t* out4_total);
+/* FILTERED RANGE search (extension): every ALLOWED vector within a radius -- dedup or threshold retrieval inside one tenant, a time window,
+ * an ACL.  The composition of the range calls and the filtered top-k calls above, and nothing else:
+ *   semantics: a filter is a VIRTUAL REMOVAL, exactly as in vers_ivf_search_filtered.  With A the set of allowed vec ids, a filtered range call
+ *              returns, bit for bit (limits, ids, order, distance bits, *out_total), what the unfiltered range call of the same mode --
+ *              vers_ivf_range_search / vers_ivf_range_search_exhaustive -- returns on an index from which every vec id not in A has been
+ *              removed by vers_ivf_remove_batch.  The index itself is not touched.
+ *   bitmap   : that of vers_ivf_search_filtered, to the letter: u64 words, one bitmap per call shared by the batch; n_bits valid bits, ids
+ *              >= n_bits are not allowed, bits of the last word at or beyond n_bits are ignored; bits of removed ids or of ids >= n select
+ *              nothing; n_bits == 0 (allowed_bits may then be NULL) is the empty filter: total 0, every limit 0.
+ *   layout, order, radii, protocol: those of the range calls, to the letter.  CSR (out_lims [b + 1], out_lims[b] = *out_total); default order
+ *              ascending (distance, probe rank, list position) on the probed call, ascending (distance, vec id) on the exhaustive call;
+ *              flags & VERS_RANGE_WALK_ORDER: probe rank then list position / storage order, restricted to the allowed rows; radius[q] per
+ *              query, a plain f32 `<=`.  Synchronous; *out_total is always the full count; *out_total > cap: VERS_OK, out_lims complete,
+ *              out_ids / out_dist UNTOUCHED; cap == 0 with NULL arrays is the size query; b == 0 is a no-op with *out_total = 0.
+ *   scan     : rows outside A are NOT SCANNED, in the count pass or in the fill pass: a 64-row storage tile without an allowed row is never
+ *              loaded, a work item without one returns before its first load.  A NaN distance on a disallowed row is therefore not an
+ *              error; on an ALLOWED scanned row it is VERS_ERR_NAN, outputs untouched.  The scan is the exact ordered f32 chain over the
+ *              f32 rows.
+ *   handle   : the way range searches take it -- shared, one leased workspace, excluded by add / remove / compact.  _dev: every pointer but
+ *              out_total is a device pointer (the bitmap too), the work is queued on `stream` and the call waits for it.  The host-pointer
+ *              calls stage the bitmap through the workspace.  A filtered range call neither consumes nor starts a vers_ivf_coarse_ahead_dev
+ *              preparation.
+ *   errors   : the union of the parents', checked before the device is touched where the parents do so.  VERS_ERR_INVALID a NaN radius,
+ *              nprobe == 0, unknown flag bits, n_bits > 0 with a NULL bitmap, metric > VERS_METRIC_COSDIST on the exhaustive call, a handle
+ *              sharded by cluster (world > 1: OUT OF SCOPE), more than 2^32 - 1 results or 2^32 - 1 slots in one call (split the batch).
+ *              VERS_ERR_INSUFFICIENT no centroids on the probed call (a streamed upload in progress is seen as an empty index); the
+ *              exhaustive call on such a handle: VERS_OK, total 0, every limit 0.  VERS_ERR_NAN as above.  VERS_ERR_HIP scratch for the
+ *              result staging did not fit, outputs untouched.
+ *   out of scope (refused, not approximated): sharded handles and partials, a filter per query, the flat corpus handle, a prepared
+ *              (reusable) filter object, any fp16 / matrix-core pre-filter.
+ * vers_ivf_filter_stats covers these calls: [3] comes from the mask kernel; [0..2] -- planned tile visits, loaded tile visits, items skipped
+ * before their first load -- are counted in the COUNT pass only, so they do not depend on the radius: what the fill pass skips for lack of
+ * hits is range search's own saving, not the filter's.  vers_range_phases counts these calls; its slot [3] then also covers the mask kernel.
+ * In the scan-timing ring (vers_ivf_scan_times) a filtered range call leaves the mask kernel's record and none for the range passes. */
+int32_t vers_ivf_range_search_filtered(vers_ivf_t* h, const float* queries, uint64_t q_stride_bytes, uint32_t b, const float* radius /* [b] */,
+                                       uint32_t nprobe, uint32_t flags, const uint64_t* allowed_bits, uint64_t n_bits,
+                                       uint64_t* out_lims /* [b+1] */, uint64_t* out_ids, float* out_dist, uint64_t cap, uint64_t* out_total);
+int32_t vers_ivf_range_search_filtered_dev(vers_ivf_t* h, const float* queries_dev, uint64_t ldq_floats, uint32_t b, const float* radius_dev,
+                                           uint32_t nprobe, uint32_t flags, const uint64_t* allowed_bits_dev, uint64_t n_bits,
+                                           uint64_t* out_lims_dev, uint64_t* out_ids_dev, float* out_dist_dev, uint64_t cap,
+                                           uint64_t* out_total /* host */, void* stream);
+int32_t vers_ivf_range_search_exhaustive_filtered(vers_ivf_t* h, const float* queries, uint64_t q_stride_bytes, uint32_t b,
+                                                  const float* radius /* [b] */, uint32_t metric, uint32_t flags, const uint64_t* allowed_bits,
+                                                  uint64_t n_bits, uint64_t* out_lims /* [b+1] */, uint64_t* out_ids, float* out_dist,
+                                                  uint64_t cap, uint64_t* out_total);
+int32_t vers_ivf_range_search_exhaustive_filtered_dev(vers_ivf_t* h, const float* queries_dev, uint64_t ldq_floats, uint32_t b,
+                                                      const float* radius_dev, uint32_t metric, uint32_t flags,
+                                                      const uint64_t* allowed_bits_dev, uint64_t n_bits, uint64_t* out_lims_dev,
+                                                      uint64_t* out_ids_dev, float* out_dist_dev, uint64_t cap,
+                                                      uint64_t* out_total /* host */, void* stream);
 /* SHARDED range search: the range calls on handles sharded by cluster (vers_ivf_set_shard / vers_ivf_build_sharded_dev), where the calls
  * above return VERS_ERR_INVALID.  The result is the unsharded index's, bit for bit -- limits, ids, order, distance bits.  Three layers:
  *

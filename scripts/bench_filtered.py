@@ -19,6 +19,7 @@ Prints ONE JSON line.
 
     python scripts/bench_filtered.py
     python scripts/bench_filtered.py --rows 10000000 --d 768 --nlist 4096 --nprobe 32
+    python scripts/bench_filtered.py --range        # the filtered RANGE search: range_main below
 """
 from __future__ import annotations
 
@@ -44,6 +45,117 @@ def mms(v):
     return {"median": round(float(np.median(v)), 4), "min": round(float(v.min()), 4), "max": round(float(v.max()), 4)}
 
 
+def range_main(args):
+    """--range: the filtered RANGE search (vers_ivf_range_search_filtered_dev), same corpus and index.  Filters: selectivity 1, random 1 %,
+    random 0.1 %, a contiguous 1 % id range.  Radii: each query's 10th / 100th-nearest ALLOWED probed distance (from a filtered top-k search
+    with top_k = 100; the last allowed one where fewer are allowed).  Per (batch, filter, radius), over --reps repeats alternating with the
+    yardstick, as median [min, max]:
+      wall_ms    host clock around the synchronous call + the device-to-host copy of limits, ids and distances
+      plan_ms / count_ms / prefix_ms / fill_ms / sort_ms   vers_range_phases (plan_ms includes the tile-mask kernel)
+      total, tiles_planned / tiles_loaded / items_skipped / rows_allowed (vers_ivf_filter_stats: the count pass)
+    Yardstick, same process, same radii: vers_ivf_range_search_dev (unchanged code = the parent commit's kernels) -- at selectivity 1 the
+    same result; for the selective filters followed by the HOST-SIDE DISCARD a caller without this feature runs: copy the whole result
+    out, keep the entries whose id is allowed, rebuild the limits.  The kept count must equal the filtered call's total.  Prints ONE JSON line."""
+    import torch
+    from tests import datagen as dg
+    from vers_amd import capi
+    from vers_amd.index import IVFFlatIndex
+
+    torch.cuda.set_device(0)
+    n, d, nlist, nprobe = args.rows, args.d, args.nlist, args.nprobe
+    ld = (d + 3) // 4 * 4
+    ld_rows = (d + 63) // 64 * 64
+    n_modes = max(1, args.modes_per_list * nlist)
+    sigma = float(dg.default_sigma(d))
+    SEED_X, SEED_C = 0x5EED0001, 0x5EEDC0DE   # bench.py's corpus
+    X = torch.empty(n, ld, dtype=torch.float32, device="cuda")
+    capi.gen_rows_dev(X.data_ptr(), n, d, ld, 1, SEED_X, SEED_C, n_modes, sigma)
+    init = (dg.mix64(np.uint64(0xB01D) + np.arange(nlist, dtype=np.uint64)) % np.uint64(n)).astype(np.uint64)
+    index = IVFFlatIndex(d)
+    t0 = time.perf_counter()
+    assert index.build_dev(X.data_ptr(), n, nlist, 1, args.kmeans_iters, init)
+    t_build = time.perf_counter() - t0
+    log(f"[bench_filtered --range] index built in {t_build:.2f} s")
+
+    rng = np.random.default_rng(0xF117E2)
+    filters = {"random_1": np.ones(n, dtype=bool), "random_0.01": rng.random(n) < 0.01, "random_0.001": rng.random(n) < 0.001}
+    lo = n // 3
+    contiguous = np.zeros(n, dtype=bool); contiguous[lo:lo + n // 100] = True
+    filters["contiguous_0.01"] = contiguous
+    words = {k: torch.from_numpy(capi.allowed_bitmap(v, n).view(np.int64)).cuda() for k, v in filters.items()}
+    PH = (("plan_ms", "plan_ms"), ("count_ms", "count_ms"), ("prefix_ms", "scan_ms"), ("fill_ms", "fill_ms"), ("sort_ms", "sort_ms"))
+    out = {}
+    for b in (int(x) for x in args.batches.split(",")):
+        Q = torch.empty(b, ld, dtype=torch.float32, device="cuda")
+        capi.gen_rows_dev(Q.data_ptr(), b, d, ld, 1, SEED_X + 1, SEED_C, n_modes, sigma)
+        lims = torch.zeros(b + 1, dtype=torch.int64, device="cuda")
+        res = {}
+        for name, allowed in filters.items():
+            # radii: the 10th / 100th-nearest allowed probed distance of each query
+            oi = torch.zeros(b, 100, dtype=torch.int64, device="cuda"); od = torch.zeros(b, 100, device="cuda"); oc = torch.zeros(b, dtype=torch.int32, device="cuda")
+            index.search_filtered_dev(Q.data_ptr(), ld, b, 100, nprobe, words[name].data_ptr(), n, oi.data_ptr(), od.data_ptr(), oc.data_ptr())
+            index.poll(); torch.cuda.synchronize()
+            odh, och = od.cpu().numpy(), oc.cpu().numpy().astype(np.int64)
+            for m in (10, 100):
+                col = np.clip(np.minimum(m, och) - 1, 0, 99)
+                rad_h = np.where(och > 0, odh[np.arange(b), col], np.float32(0)).astype(np.float32)
+                rad = torch.from_numpy(rad_h).cuda()
+                # capacities: one size query each
+                tot_f = index.range_search_filtered_dev(Q.data_ptr(), ld, b, rad.data_ptr(), nprobe, 0, words[name].data_ptr(), n, lims.data_ptr(), 0, 0, 0)
+                tot_u = index.range_search_dev(Q.data_ptr(), ld, b, rad.data_ptr(), nprobe, 0, lims.data_ptr(), 0, 0, 0)
+                cap = max(tot_f, tot_u, 1)
+                ids = torch.zeros(cap, dtype=torch.int64, device="cuda"); dist = torch.zeros(cap, dtype=torch.float32, device="cuda")
+
+                def filtered():
+                    capi.range_phases(reset=True)
+                    torch.cuda.synchronize()
+                    t = time.perf_counter()
+                    total = index.range_search_filtered_dev(Q.data_ptr(), ld, b, rad.data_ptr(), nprobe, 0, words[name].data_ptr(), n, lims.data_ptr(), ids.data_ptr(),
+                                                            dist.data_ptr(), cap)
+                    lh, ih, dh = lims.cpu().numpy(), ids[:total].cpu().numpy(), dist[:total].cpu().numpy()
+                    wall = (time.perf_counter() - t) * 1e3
+                    ph = capi.range_phases(reset=True)
+                    st = index.filter_stats()["last"]
+                    return {"wall_ms": wall, **{k: ph[src] for k, src in PH}, "total": total, **st}
+
+                def yardstick():
+                    capi.range_phases(reset=True)
+                    torch.cuda.synchronize()
+                    t = time.perf_counter()
+                    total = index.range_search_dev(Q.data_ptr(), ld, b, rad.data_ptr(), nprobe, 0, lims.data_ptr(), ids.data_ptr(), dist.data_ptr(), cap)
+                    lh, ih, dh = lims.cpu().numpy(), ids[:total].cpu().numpy(), dist[:total].cpu().numpy()
+                    kept = total
+                    if name != "random_1":   # the host-side discard
+                        keep = allowed[ih]
+                        ih, dh = ih[keep], dh[keep]
+                        lh = np.concatenate([[0], np.cumsum(keep)])[lh]
+                        kept = int(lh[-1])
+                    wall = (time.perf_counter() - t) * 1e3
+                    ph = capi.range_phases(reset=True)
+                    return {"wall_ms": wall, **{k: ph[src] for k, src in PH}, "total": total, "kept": kept}
+
+                filtered(); yardstick()   # warm-up of both shapes
+                runs_f, runs_y = [], []
+                for _ in range(args.reps):
+                    runs_f.append(filtered()); runs_y.append(yardstick())
+                keys = ("wall_ms",) + tuple(k for k, _ in PH)
+                st = {k: runs_f[0][k] for k in ("total", "tiles_planned", "tiles_loaded", "items_skipped", "rows_allowed")}
+                assert all(all(r[k] == st[k] for k in st) for r in runs_f), "totals and counters are functions of the data and the plan"
+                assert all(r["kept"] == st["total"] for r in runs_y), "the discard keeps what the filtered call returns"
+                res[f"{name}/r{m}"] = {"filtered": {**{k: mms([r[k] for r in runs_f]) for k in keys}, **st,
+                                                    "tiles_loaded_fraction": round(st["tiles_loaded"] / max(1, st["tiles_planned"]), 4),
+                                                    "bytes_not_read_per_pass": (st["tiles_planned"] - st["tiles_loaded"]) * 64 * ld_rows * 4},
+                                       "unfiltered" + ("" if name == "random_1" else "+host_discard"): {**{k: mms([r[k] for r in runs_y]) for k in keys},
+                                                                                                       "total": runs_y[0]["total"]}}
+                del ids, dist
+        out[f"batch{b}"] = res
+        log(f"[bench_filtered --range] batch {b}: {json.dumps(res)}")
+    line = {"metric": f"vers_ivf_range_search_filtered_dev in ms, IVFFlat (N={n} d={d} nlist={nlist}) nprobe={nprobe}", "build_s": round(t_build, 2), "reps": args.reps, **out}
+    index.close()
+    print(json.dumps(line), flush=True)
+    return 0
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", type=int, default=1_000_000)
@@ -55,8 +167,11 @@ def main():
     ap.add_argument("--top-k", type=int, default=10)
     ap.add_argument("--batches", default="1,64,1024")
     ap.add_argument("--reps", type=int, default=7)
+    ap.add_argument("--range", action="store_true", help="the filtered RANGE search instead (vers_ivf_range_search_filtered_dev): see range_main")
     args = ap.parse_args()
     assert args.reps >= 5, "at least 5 alternating repeats per point"
+    if args.range:
+        return range_main(args)
 
     import torch
     from tests import datagen as dg

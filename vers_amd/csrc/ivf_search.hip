@@ -16,6 +16,7 @@
 #include "range_driver.hip.h"
 #include "range_merge.hip.h"
 #include "filter.hip.h"
+#include "filter_range.hip.h"
 
 namespace vers {
 
@@ -839,6 +840,92 @@ int32_t range_dev_locked(vers_ivf* h, bool probed, const float* q_dev, uint64_t 
   return range_search_run(src, W->rg, b, radius_dev, flags, lims_dev, ids_dev, dist_dev, cap, own_out, out_total, st, part);
 }
 
+// ---- filtered range search (filter_range.hip.h): the range protocol over the allowed rows of a per-call bitmap -----------------------
+// one pass of the filtered range walk; not timed by the scan-timing ring (no range pass is), and no more waves than counter slots (filter_begin)
+template <int QG, bool FILL, class Src>
+static int32_t launch_filter_range_pass(vers_ivf* h, int metric, const Src& src, uint32_t items, const RangeParams& p, const FilterParams& f, hipStream_t st) {
+  const uint32_t blocks = scan_grid(h->n_cu, QG, h->ld, items, (uint32_t)(filter_wave_slots(h) / kWavesPerBlock));
+  return with_metric(metric, [&](auto m) -> int32_t {
+    return launch_scan(filter_range_scan_kernel<QG, decltype(m)::value, FILL, Src>, blocks, kWavesPerBlock, scan_lds_bytes(QG, h->ld), st, src, p, f);
+  });
+}
+
+// ProbedRangeSource behind a filter: the mask kernel (with its record in the scan-timing ring) opens the first phase, the plan is the
+// unfiltered one (the lists are ranked as without a filter) but neither consumes nor starts a look-ahead, both passes run the filtered kernel.
+struct FilteredProbedRangeSource : ProbedRangeSource {
+  static constexpr bool kPartials = false;
+  const char* who = "vers_ivf_range_search_filtered";
+  const uint64_t* bits_dev; uint64_t n_bits;
+  FilterParams f{};
+  FilteredProbedRangeSource(vers_ivf* hh, const float* q, uint64_t ldq, uint32_t bb, uint32_t np, const uint64_t* bits, uint64_t nb)
+      : ProbedRangeSource(hh, q, ldq, bb, np), bits_dev(bits), n_bits(nb) {}
+  int32_t prepare(hipStream_t st, uint64_t& slots_per_query) {
+    if (int32_t rc = filter_begin(h, bits_dev, n_bits, h->cap_rows, st, f)) return rc;
+    W->no_ahead = true;
+    const int32_t rc = ProbedRangeSource::prepare(st, slots_per_query);
+    W->no_ahead = false;
+    return rc;
+  }
+  template <class Fill>
+  int32_t launch(Fill, RangeParams p, hipStream_t st) const {
+    return with_qg<1, 8, 16>(s.QG, [&](auto qg) -> int32_t {
+      constexpr int QG = decltype(qg)::value;
+      if (QG != 1)
+        if (int32_t rc = fresh_quad_counter(st, &p.next_quad)) return rc;
+      return launch_filter_range_pass<QG, Fill::value>(h, h->metric, make_ivf_src<QG>(h, s, 0u), (uint32_t)s.items_bound, p, f, st);
+    });
+  }
+};
+
+// StoredRangeSource behind a filter: the mask covers the rows the scan covers (none on an index without centroids).
+struct FilteredStoredRangeSource : StoredRangeSource {
+  static constexpr bool kPartials = false;
+  const char* who = "vers_ivf_range_search_exhaustive_filtered";
+  const uint64_t* bits_dev; uint64_t n_bits;
+  FilterParams f{};
+  FilteredStoredRangeSource(vers_ivf* hh, const float* q, uint64_t ldq, uint32_t bb, uint32_t m, const uint64_t* bits, uint64_t nb)
+      : StoredRangeSource(hh, q, ldq, bb, m), bits_dev(bits), n_bits(nb) {}
+  int32_t prepare(hipStream_t st, uint64_t& slots_per_query) {
+    if (int32_t rc = filter_begin(h, bits_dev, n_bits, (h->k == 0 || h->up.open) ? 0 : h->cap_rows, st, f)) return rc;
+    return StoredRangeSource::prepare(st, slots_per_query);
+  }
+  template <class Fill>
+  int32_t launch(Fill, const RangeParams& p, hipStream_t st) const {
+    return with_qg<1, 8>(sp.QG, [&](auto qg) -> int32_t {
+      constexpr int QG = decltype(qg)::value;
+      using Src = SegSrc<QG, true>;
+      return launch_filter_range_pass<QG, Fill::value>(h, (int)metric,
+                                                       make_seg_src<Src>(h->rows.as<float>(), n_rows, h->ld, sp, W->qil.as<float>(), h->ldq, b, nullptr, 0, h->row_ids.as<uint32_t>()),
+                                                       sp.n_items, p, f, st);
+    });
+  }
+};
+
+// A filtered range search on the index, on `st`: mask kernel + counters, the range protocol, the counters folded.  A call that fails leaves
+// vers_ivf_filter_stats where it was.
+int32_t range_filtered_dev_locked(vers_ivf* h, bool probed, const float* q_dev, uint64_t ldq_in, uint32_t b, const float* radius_dev, uint32_t nprobe_or_metric,
+                                  uint32_t flags, const uint64_t* bits_dev, uint64_t n_bits, uint64_t* lims_dev, uint64_t* ids_dev, float* dist_dev, uint64_t cap,
+                                  bool own_out, uint64_t* out_total, hipStream_t st) {
+  if (probed) {
+    FilteredProbedRangeSource src(h, q_dev, ldq_in, b, nprobe_or_metric, bits_dev, n_bits);
+    if (int32_t rc = range_search_run(src, W->rg, b, radius_dev, flags, lims_dev, ids_dev, dist_dev, cap, own_out, out_total, st)) return rc;
+    return filter_end(h, st);
+  }
+  FilteredStoredRangeSource src(h, q_dev, ldq_in, b, nprobe_or_metric, bits_dev, n_bits);
+  if (int32_t rc = range_search_run(src, W->rg, b, radius_dev, flags, lims_dev, ids_dev, dist_dev, cap, own_out, out_total, st)) return rc;
+  return filter_end(h, st);
+}
+
+// what the four filtered range entry points refuse before they touch the device: the union of the two parents' checks
+static int32_t range_filter_check(vers_ivf* h, const char* who, bool probed, uint32_t nprobe, uint32_t flags, const uint64_t* bits, uint64_t n_bits) {
+  if (flags & ~VERS_RANGE_WALK_ORDER) return fail(VERS_ERR_INVALID, std::string(who) + ": unknown flag bits");
+  if (n_bits != 0 && bits == nullptr) return fail(VERS_ERR_INVALID, std::string(who) + ": n_bits > 0 with a NULL bitmap");
+  if (probed && nprobe == 0) return fail(VERS_ERR_INVALID, std::string(who) + ": nprobe must be at least 1 (the reference's spill walk is defined by top_k: it has no range meaning)");
+  if (h->world > 1) return fail(VERS_ERR_INVALID, std::string(who) + ": the handle is sharded by cluster; filtered range search on a sharded handle is out of scope");
+  if (probed && h->k == 0) return fail(VERS_ERR_INSUFFICIENT, "range search on an index without centroids (reference: index out of bounds, ivfflat.rs:169)");
+  return VERS_OK;
+}
+
 // what both exhaustive entry points refuse before they touch the device
 static int32_t range_exhaustive_check(vers_ivf* h, const char* who, uint32_t flags, bool partial = false) {
   if (flags & ~VERS_RANGE_WALK_ORDER) return fail(VERS_ERR_INVALID, std::string(who) + ": unknown flag bits");
@@ -1434,6 +1521,103 @@ int32_t vers_ivf_range_search(vers_ivf_t* h, const float* queries, uint64_t q_st
 int32_t vers_ivf_range_search_exhaustive(vers_ivf_t* h, const float* queries, uint64_t q_stride_bytes, uint32_t b, const float* radius, uint32_t metric,
                                          uint32_t flags, uint64_t* out_lims, uint64_t* out_ids, float* out_dist, uint64_t cap, uint64_t* out_total) {
   return range_host_common(h, "vers_ivf_range_search_exhaustive", false, queries, q_stride_bytes, b, radius, metric, flags, out_lims, out_ids, out_dist, cap, out_total);
+}
+
+// ---- filtered range search (filter_range.hip.h): the probed lists or (probed = false) every stored row under the metric given in place of nprobe ----
+static int32_t range_filtered_dev_common(vers_ivf_t* h, const char* who, bool probed, const float* queries_dev, uint64_t ldq_floats, uint32_t b, const float* radius_dev,
+                                         uint32_t nprobe_or_metric, uint32_t flags, const uint64_t* allowed_bits_dev, uint64_t n_bits, uint64_t* out_lims_dev,
+                                         uint64_t* out_ids_dev, float* out_dist_dev, uint64_t cap, uint64_t* out_total, void* stream) {
+  if (!h) return fail(VERS_ERR_INVALID, "null handle");
+  if (!out_total) return fail(VERS_ERR_INVALID, std::string(who) + ": out_total is required");
+  *out_total = 0;
+  if (!probed && nprobe_or_metric > VERS_METRIC_COSDIST) return fail(VERS_ERR_INVALID, "unknown metric");
+  if (b && (!queries_dev || ldq_floats < h->d || !radius_dev || !out_lims_dev || (cap && (!out_ids_dev || !out_dist_dev))))
+    return fail(VERS_ERR_INVALID, std::string(who) + ": bad arguments");
+  if (b == 0) return VERS_OK;
+  std::shared_lock<std::shared_mutex> lk(h->index);
+  if (int32_t rc = range_filter_check(h, who, probed, probed ? nprobe_or_metric : 1u, flags, allowed_bits_dev, n_bits)) return rc;
+  DeviceGuard g(h->device);
+  WsLease lease(h, true, (hipStream_t)stream);
+  if (lease.rc) return lease.rc;
+  if (int32_t rc = lease.order_on((hipStream_t)stream)) return rc;
+  HostStatusSlot slot(h);
+  return range_filtered_dev_locked(h, probed, queries_dev, ldq_floats, b, radius_dev, nprobe_or_metric, flags, allowed_bits_dev, n_bits, out_lims_dev, out_ids_dev,
+                                   out_dist_dev, cap, false, out_total, (hipStream_t)stream);
+}
+
+int32_t vers_ivf_range_search_filtered_dev(vers_ivf_t* h, const float* queries_dev, uint64_t ldq_floats, uint32_t b, const float* radius_dev, uint32_t nprobe,
+                                           uint32_t flags, const uint64_t* allowed_bits_dev, uint64_t n_bits, uint64_t* out_lims_dev, uint64_t* out_ids_dev,
+                                           float* out_dist_dev, uint64_t cap, uint64_t* out_total, void* stream) {
+  return range_filtered_dev_common(h, "vers_ivf_range_search_filtered_dev", true, queries_dev, ldq_floats, b, radius_dev, nprobe, flags, allowed_bits_dev, n_bits,
+                                   out_lims_dev, out_ids_dev, out_dist_dev, cap, out_total, stream);
+}
+
+int32_t vers_ivf_range_search_exhaustive_filtered_dev(vers_ivf_t* h, const float* queries_dev, uint64_t ldq_floats, uint32_t b, const float* radius_dev,
+                                                      uint32_t metric, uint32_t flags, const uint64_t* allowed_bits_dev, uint64_t n_bits, uint64_t* out_lims_dev,
+                                                      uint64_t* out_ids_dev, float* out_dist_dev, uint64_t cap, uint64_t* out_total, void* stream) {
+  return range_filtered_dev_common(h, "vers_ivf_range_search_exhaustive_filtered_dev", false, queries_dev, ldq_floats, b, radius_dev, metric, flags, allowed_bits_dev,
+                                   n_bits, out_lims_dev, out_ids_dev, out_dist_dev, cap, out_total, stream);
+}
+
+// host-pointer calls: range_host_common's staging (queries pinned, radii and limits through the workspace) + filtered_host_common's (the bitmap
+// through the workspace)
+static int32_t range_filtered_host_common(vers_ivf_t* h, const char* who, bool probed, const float* queries, uint64_t q_stride_bytes, uint32_t b, const float* radius,
+                                          uint32_t nprobe_or_metric, uint32_t flags, const uint64_t* allowed_bits, uint64_t n_bits, uint64_t* out_lims, uint64_t* out_ids,
+                                          float* out_dist, uint64_t cap, uint64_t* out_total) {
+  if (!h) return fail(VERS_ERR_INVALID, "null handle");
+  if (!out_total) return fail(VERS_ERR_INVALID, std::string(who) + ": out_total is required");
+  *out_total = 0;
+  if (!probed && nprobe_or_metric > VERS_METRIC_COSDIST) return fail(VERS_ERR_INVALID, "unknown metric");
+  if (b && (!queries || q_stride_bytes < (uint64_t)h->d * 4 || q_stride_bytes % 4 || !radius || !out_lims || (cap && (!out_ids || !out_dist))))
+    return fail(VERS_ERR_INVALID, std::string(who) + ": bad arguments");
+  if (b == 0) return VERS_OK;
+  for (uint32_t i = 0; i < b; ++i)
+    if (radius[i] != radius[i]) return fail(VERS_ERR_INVALID, std::string(who) + ": NaN radius");
+  std::shared_lock<std::shared_mutex> lk(h->index);
+  if (int32_t rc = range_filter_check(h, who, probed, probed ? nprobe_or_metric : 1u, flags, allowed_bits, n_bits)) return rc;
+  DeviceGuard g(h->device);
+  WsLease lease(h);
+  if (lease.rc) return lease.rc;
+  HostStatusSlot slot(h);
+  HostIo io;
+  if (int32_t rc = host_io_begin(h, queries, q_stride_bytes, b, 0, io)) return rc;  // (the pinned query staging of every host-pointer call)
+  lease.st = W->io_stream;
+  if (int32_t rc = W->rg_rad.reserve((size_t)b * sizeof(float))) return rc;
+  if (int32_t rc = W->rg_lims.reserve(((size_t)b + 1) * sizeof(uint64_t))) return rc;
+  const size_t bit_bytes = (size_t)((n_bits + 63) / 64) * sizeof(uint64_t);
+  if (int32_t rc = W->flt_bits.reserve(std::max<size_t>(8, bit_bytes))) return rc;
+  VERS_HIP_TRY(hipMemcpyAsync(W->rg_rad.p, radius, (size_t)b * sizeof(float), hipMemcpyHostToDevice, W->io_stream));
+  uint64_t total = 0;
+  int32_t rc = VERS_OK;
+  if (bit_bytes && hipMemcpyAsync(W->flt_bits.p, allowed_bits, bit_bytes, hipMemcpyHostToDevice, W->io_stream) != hipSuccess)
+    rc = fail(VERS_ERR_HIP, std::string(who) + ": staging the bitmap failed");
+  if (!rc)
+    rc = range_filtered_dev_locked(h, probed, io.q_dev, h->d, b, W->rg_rad.as<float>(), nprobe_or_metric, flags, W->flt_bits.as<uint64_t>(), n_bits,
+                                   W->rg_lims.as<uint64_t>(), nullptr, nullptr, cap, true, &total, W->io_stream);
+  if (rc) {  // (the caller's bitmap and radii may still be read by the staging copies)
+    (void)hipStreamSynchronize(W->io_stream);
+    return rc;
+  }
+  VERS_HIP_TRY(hipMemcpy(out_lims, W->rg_lims.p, ((size_t)b + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost));
+  *out_total = total;
+  if (total == 0 || total > cap) return VERS_OK;
+  VERS_HIP_TRY(hipMemcpy(out_ids, W->o_ids.p, (size_t)total * sizeof(uint64_t), hipMemcpyDeviceToHost));
+  VERS_HIP_TRY(hipMemcpy(out_dist, W->o_dist.p, (size_t)total * sizeof(float), hipMemcpyDeviceToHost));
+  return VERS_OK;
+}
+
+int32_t vers_ivf_range_search_filtered(vers_ivf_t* h, const float* queries, uint64_t q_stride_bytes, uint32_t b, const float* radius, uint32_t nprobe, uint32_t flags,
+                                       const uint64_t* allowed_bits, uint64_t n_bits, uint64_t* out_lims, uint64_t* out_ids, float* out_dist, uint64_t cap,
+                                       uint64_t* out_total) {
+  return range_filtered_host_common(h, "vers_ivf_range_search_filtered", true, queries, q_stride_bytes, b, radius, nprobe, flags, allowed_bits, n_bits, out_lims, out_ids,
+                                    out_dist, cap, out_total);
+}
+
+int32_t vers_ivf_range_search_exhaustive_filtered(vers_ivf_t* h, const float* queries, uint64_t q_stride_bytes, uint32_t b, const float* radius, uint32_t metric,
+                                                  uint32_t flags, const uint64_t* allowed_bits, uint64_t n_bits, uint64_t* out_lims, uint64_t* out_ids, float* out_dist,
+                                                  uint64_t cap, uint64_t* out_total) {
+  return range_filtered_host_common(h, "vers_ivf_range_search_exhaustive_filtered", false, queries, q_stride_bytes, b, radius, metric, flags, allowed_bits, n_bits,
+                                    out_lims, out_ids, out_dist, cap, out_total);
 }
 
 int32_t vers_range_merge_dev(const uint64_t* keys_dev, const uint64_t* ids_dev, uint64_t rank_stride, const uint64_t* rank_lims_dev, uint32_t world, uint32_t b,

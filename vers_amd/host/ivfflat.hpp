@@ -220,6 +220,44 @@ class IVFFlatIndex {
     return out;
   }
 
+  // Filtered range search (extension, vers_ivf_range_search_filtered): range_search over the lists once every vec id with allowed[v] == false
+  // (or v >= allowed.size()) has been removed; the index is not touched.  Order as range_search.
+  std::vector<std::pair<size_t, float>> range_search_filtered(const Vector<N>& query, float radius, size_t nprobe, const std::vector<bool>& allowed,
+                                                              bool walk_order = false) const {
+    const std::vector<uint64_t> bits = allowed_bitmap(allowed);
+    const uint32_t flags = walk_order ? VERS_RANGE_WALK_ORDER : 0u;
+    uint64_t lims[2] = {0, 0}, total = 0;
+    check(vers_ivf_range_search_filtered(handle(), query.v, sizeof(Vector<N>), 1, &radius, (uint32_t)nprobe, flags, bits.data(), allowed.size(), lims, nullptr,
+                                         nullptr, 0, &total));  // size query
+    std::vector<uint64_t> oi(total ? total : 1);
+    std::vector<float> od(total ? total : 1);
+    if (total)
+      check(vers_ivf_range_search_filtered(handle(), query.v, sizeof(Vector<N>), 1, &radius, (uint32_t)nprobe, flags, bits.data(), allowed.size(), lims, oi.data(),
+                                           od.data(), total, &total));
+    std::vector<std::pair<size_t, float>> out;
+    for (uint64_t i = 0; i < total && i < oi.size(); ++i) out.emplace_back((size_t)oi[i], od[i]);
+    return out;
+  }
+
+  // Exhaustive filtered range search (extension, vers_ivf_range_search_exhaustive_filtered): every allowed row in a list now with distance <=
+  // radius under `metric`.  Order as range_search_exhaustive.
+  std::vector<std::pair<size_t, float>> range_search_exhaustive_filtered(const Vector<N>& query, float radius, const std::vector<bool>& allowed,
+                                                                         uint32_t metric = VERS_METRIC_L2SQ, bool walk_order = false) const {
+    const std::vector<uint64_t> bits = allowed_bitmap(allowed);
+    const uint32_t flags = walk_order ? VERS_RANGE_WALK_ORDER : 0u;
+    uint64_t lims[2] = {0, 0}, total = 0;
+    check(vers_ivf_range_search_exhaustive_filtered(handle(), query.v, sizeof(Vector<N>), 1, &radius, metric, flags, bits.data(), allowed.size(), lims, nullptr,
+                                                    nullptr, 0, &total));  // size query
+    std::vector<uint64_t> oi(total ? total : 1);
+    std::vector<float> od(total ? total : 1);
+    if (total)
+      check(vers_ivf_range_search_exhaustive_filtered(handle(), query.v, sizeof(Vector<N>), 1, &radius, metric, flags, bits.data(), allowed.size(), lims, oi.data(),
+                                                      od.data(), total, &total));
+    std::vector<std::pair<size_t, float>> out;
+    for (uint64_t i = 0; i < total && i < oi.size(); ++i) out.emplace_back((size_t)oi[i], od[i]);
+    return out;
+  }
+
   // allowed[v] -> the u64 words of the C ABI: bit (v & 63) of word (v >> 6); at least one word, so that the array has an address
   static std::vector<uint64_t> allowed_bitmap(const std::vector<bool>& allowed) {
     std::vector<uint64_t> bits((allowed.size() + 63) / 64 + 1, 0);

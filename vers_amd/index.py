@@ -306,6 +306,56 @@ class IVFFlatIndex:
                                                          C.byref(total), _vp(stream)))
         return int(total.value)
 
+    # -- filtered range search (extension): range search on the index WITHOUT the vec ids `allowed` leaves out -----
+    def _range_filtered(self, fn, queries, radius, arg, allowed, n_bits, walk_order):
+        q = np.ascontiguousarray(np.atleast_2d(queries), dtype=np.float32)
+        b = q.shape[0]
+        r = capi.range_radii(radius, b)
+        words, nb = self._filter_words(allowed, n_bits)
+        flags = capi.RANGE_WALK_ORDER if walk_order else 0
+        lims = np.zeros(b + 1, dtype=np.uint64)
+        cap = int(self._range_cap)
+        total = C.c_uint64(0)
+        while True:
+            ids = np.zeros(cap, dtype=np.uint64); dist = np.zeros(cap, dtype=np.float32)
+            check(fn(self._h, _ptr(q), 4 * self.d, b, _ptr(r), arg, flags, _ptr(words) if words.size else None, nb, _ptr(lims),
+                     _ptr(ids) if cap else None, _ptr(dist) if cap else None, cap, C.byref(total)))
+            if total.value <= cap:
+                break
+            cap = int(total.value)
+        self._range_cap = int(total.value)
+        return lims, ids[:total.value], dist[:total.value]
+
+    def range_search_filtered(self, queries, radius, nprobe: int, allowed, n_bits=None, walk_order: bool = False):
+        """range_search(queries, radius, nprobe) on the index WITHOUT the vec ids `allowed` leaves out (vers_ivf_range_search_filtered): every
+        allowed row of the min(nprobe, k) nearest lists with distance <= radius; the index is not touched.  allowed / n_bits as
+        search_filtered.  -> (lims, ids, dist) like range_search, by the same two-call protocol."""
+        return self._range_filtered(lib().vers_ivf_range_search_filtered, queries, radius, nprobe, allowed, n_bits, walk_order)
+
+    def range_search_exhaustive_filtered(self, queries, radius, allowed, metric: int = capi.METRIC_L2SQ, n_bits=None, walk_order: bool = False):
+        """range_search_exhaustive over the allowed rows that are in a list now (vers_ivf_range_search_exhaustive_filtered)."""
+        return self._range_filtered(lib().vers_ivf_range_search_exhaustive_filtered, queries, radius, metric, allowed, n_bits, walk_order)
+
+    def range_search_filtered_dev(self, q_ptr: int, ldq: int, b: int, radius_ptr: int, nprobe: int, flags: int, bits_ptr: int, n_bits: int,
+                                  lims_ptr: int, ids_ptr: int, dist_ptr: int, cap: int, stream: int = 0) -> int:
+        """vers_ivf_range_search_filtered_dev on raw device pointers (the bitmap too); synchronous.  Returns the total: ids / distances were
+        written only when it is <= cap."""
+        total = C.c_uint64(0)
+        check(lib().vers_ivf_range_search_filtered_dev(self._h, _vp(q_ptr), ldq, b, _vp(radius_ptr), nprobe, flags, _vp(bits_ptr) if bits_ptr else None,
+                                                       n_bits, _vp(lims_ptr), _vp(ids_ptr) if ids_ptr else None, _vp(dist_ptr) if dist_ptr else None,
+                                                       cap, C.byref(total), _vp(stream)))
+        return int(total.value)
+
+    def range_search_exhaustive_filtered_dev(self, q_ptr: int, ldq: int, b: int, radius_ptr: int, metric: int, flags: int, bits_ptr: int,
+                                             n_bits: int, lims_ptr: int, ids_ptr: int, dist_ptr: int, cap: int, stream: int = 0) -> int:
+        """vers_ivf_range_search_exhaustive_filtered_dev on raw device pointers (the bitmap too); synchronous.  Returns the total."""
+        total = C.c_uint64(0)
+        check(lib().vers_ivf_range_search_exhaustive_filtered_dev(self._h, _vp(q_ptr), ldq, b, _vp(radius_ptr), metric, flags,
+                                                                  _vp(bits_ptr) if bits_ptr else None, n_bits, _vp(lims_ptr),
+                                                                  _vp(ids_ptr) if ids_ptr else None, _vp(dist_ptr) if dist_ptr else None, cap,
+                                                                  C.byref(total), _vp(stream)))
+        return int(total.value)
+
     # -- device cache -----------------------------------------------------------------------------------
     def _upload(self):
         v = np.ascontiguousarray(self.values, dtype=np.float32)
