@@ -493,7 +493,8 @@ int32_t vers_ivf_range_search_exhaustive_dev(vers_ivf_t* h, const float* queries
  *   errors   : VERS_ERR_INVALID n_bits > 0 with a NULL bitmap; nprobe == 0 on the probed call (the reference's spill walk depends on the
  *              filtered list lengths: OUT OF SCOPE); metric > VERS_METRIC_COSDIST on the exhaustive call; a handle sharded by cluster
  *              (world > 1: OUT OF SCOPE).  VERS_ERR_INSUFFICIENT no centroids on the probed call, as in vers_ivf_search.
- *   out of scope: nprobe == 0, sharded handles, a filter per query, the flat corpus handle, a prepared (reusable) filter object.
+ *   out of scope: nprobe == 0, sharded handles, the flat corpus handle, a prepared (reusable) filter object.  (A filter per query: the _multi
+ *              calls below.)
  * vers_ivf_filter_stats (measurement hook; functions of the data and the plan alone): out4 = the most recent filtered call of the handle,
  * out4_total = over the handle's life; either may be NULL.  [0] tile visits the plan implied (64-row tiles of every work item, counted once
  * per item and scan pass), [1] tile visits actually loaded, [2] items skipped before their first load, [3] allowed storage rows (popcount
@@ -510,6 +511,51 @@ int32_t vers_ivf_search_exhaustive_filtered(vers_ivf_t* h, const float* queries,
 int32_t vers_ivf_search_exhaustive_filtered_dev(vers_ivf_t* h, const float* queries_dev, uint64_t ldq_floats, uint32_t b, uint32_t top_k,
                                                 uint32_t metric, const uint64_t* allowed_bits_dev, uint64_t n_bits, uint64_t* out_ids_dev,
                                                 float* out_dist_dev, uint32_t* out_count_dev, void* stream);
+/* FILTERED top-k search with a FILTER PER QUERY: one batch whose queries belong to different allowed sets (tenants, ACLs, time windows).
+ *   semantics: nothing new.  With filter_of[q] = f, row q of a _multi call is bit for bit (ids, order, distance bits, out_count[q]) row q of
+ *              vers_ivf_search_filtered / vers_ivf_search_exhaustive_filtered made with bitmap f on the same handle, with the same queries,
+ *              top_k and nprobe / metric.  The ranking of the lists, both result orders, counts of 0, any top_k and any nprobe >= 1, the
+ *              output layout, the handle, lease and stream rules and vers_ivf_poll's latching on the _dev calls are the per-call ones, to
+ *              the letter.
+ *   filters  : n_filters bitmaps of u64 words, bitmap f at filters + f * filter_stride_words, filter_stride_words >= ceil(n_bits / 64).
+ *              One n_bits serves all bitmaps with the meaning it has above: ids >= n_bits are not allowed, bits of a bitmap's last word at
+ *              or beyond n_bits are ignored, bits of removed ids or ids >= n select nothing; n_bits == 0: every filter is empty, filters may
+ *              be NULL.  Words between two bitmaps (a stride larger than needed) are never read as bits.
+ *   filter_of: [b] u32, the bitmap query q uses.  At most VERS_FILTER_MAX distinct bitmaps per call: a batch with more distinct allowed
+ *              sets is split by the caller.  A query that may see everything uses a bitmap of ones covering n.
+ *   errors   : VERS_ERR_INVALID n_filters == 0 with b > 0; n_filters > VERS_FILTER_MAX; n_bits > 0 with NULL filters; NULL filter_of with
+ *              b > 0; filter_stride_words < ceil(n_bits / 64); and the per-call ones (nprobe == 0, the metric, a handle sharded by cluster,
+ *              the exhaustive call's batch too large).  VERS_ERR_INSUFFICIENT no centroids on the probed call.  Host-pointer calls: an entry
+ *              of filter_of >= n_filters is VERS_ERR_INVALID.  _dev calls: filter_of is NOT read on the host; an entry >= n_filters selects
+ *              the EMPTY filter (out_count[q] = 0) and never indexes outside the masks.  VERS_ERR_NAN counts a NaN distance only for a
+ *              (query, row) pair whose row is allowed for THAT query and scanned: a NaN row allowed by a bitmap no query of the batch uses,
+ *              or only for queries that do not probe its list, is not an error.
+ *   scan     : the mask pass writes a u64 per storage row (bit f: bitmap f allows the row's vector) and one per 64-row tile (bit f: bitmap f
+ *              allows some row of it); a tile is loaded for a group of queries when some query of the group is allowed a row of it, and each
+ *              query takes only its own rows from it.  b == 0 is a no-op, top_k == 0 zeroes the counts.  The host-pointer calls stage the
+ *              bitmaps and filter_of through the workspace.
+ *   stats    : vers_ivf_filter_stats covers these calls: [0..2] as above (a tile counts as loaded when some live query of the work item is
+ *              allowed a row of it); [3] = allowed (bitmap, storage row) pairs, summed over the call's n_filters bitmaps.  The scan-timing
+ *              ring gets the mask kernel's record, then one per scan pass.
+ *   out of scope (refused, not approximated): a filter per query on the range calls, sharded handles and partials, the flat corpus handle,
+ *              nprobe == 0, more than VERS_FILTER_MAX bitmaps per call, a prepared (reusable) mask, re-grouping a list's queries by filter
+ *              in the plan, any fp16 / matrix-core pre-filter. */
+#define VERS_FILTER_MAX 64
+int32_t vers_ivf_search_filtered_multi(vers_ivf_t* h, const float* queries, uint64_t q_stride_bytes, uint32_t b, uint32_t top_k, uint32_t nprobe,
+                                       const uint64_t* filters, uint64_t filter_stride_words, uint32_t n_filters, uint64_t n_bits,
+                                       const uint32_t* filter_of /* [b] */, uint64_t* out_ids, float* out_dist, uint32_t* out_count);
+int32_t vers_ivf_search_filtered_multi_dev(vers_ivf_t* h, const float* queries_dev, uint64_t ldq_floats, uint32_t b, uint32_t top_k, uint32_t nprobe,
+                                           const uint64_t* filters_dev, uint64_t filter_stride_words, uint32_t n_filters, uint64_t n_bits,
+                                           const uint32_t* filter_of_dev, uint64_t* out_ids_dev, float* out_dist_dev, uint32_t* out_count_dev,
+                                           void* stream);
+int32_t vers_ivf_search_exhaustive_filtered_multi(vers_ivf_t* h, const float* queries, uint64_t q_stride_bytes, uint32_t b, uint32_t top_k,
+                                                  uint32_t metric, const uint64_t* filters, uint64_t filter_stride_words, uint32_t n_filters,
+                                                  uint64_t n_bits, const uint32_t* filter_of /* [b] */, uint64_t* out_ids, float* out_dist,
+                                                  uint32_t* out_count);
+int32_t vers_ivf_search_exhaustive_filtered_multi_dev(vers_ivf_t* h, const float* queries_dev, uint64_t ldq_floats, uint32_t b, uint32_t top_k,
+                                                      uint32_t metric, const uint64_t* filters_dev, uint64_t filter_stride_words,
+                                                      uint32_t n_filters, uint64_t n_bits, const uint32_t* filter_of_dev, uint64_t* out_ids_dev,
+                                                      float* out_dist_dev, uint32_t* out_count_dev, void* stream);
 int32_t vers_ivf_filter_stats(vers_ivf_t* h, uint64_t* out4, uint64_t* out4_total);
 /* FILTERED RANGE search (extension): every ALLOWED vector within a radius -- dedup or threshold retrieval inside one tenant, a time window,
  * an ACL.  The composition of the range calls and the filtered top-k calls above, and nothing else:

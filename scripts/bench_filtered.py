@@ -20,6 +20,7 @@ Prints ONE JSON line.
     python scripts/bench_filtered.py
     python scripts/bench_filtered.py --rows 10000000 --d 768 --nlist 4096 --nprobe 32
     python scripts/bench_filtered.py --range        # the filtered RANGE search: range_main below
+    python scripts/bench_filtered.py --multi        # a filter per query against one per-call search per tenant: multi_main below
 """
 from __future__ import annotations
 
@@ -156,6 +157,118 @@ def range_main(args):
     return 0
 
 
+def multi_main(args):
+    """--multi: a batch whose queries belong to different tenants (vers_ivf_search_filtered_multi_dev), same corpus and index.  Batches of 64
+    and 1024, the queries assigned round-robin to F = 1, 8, 64 tenants (query q: tenant q % F); two tenant layouts: `contiguous` (tenant f
+    owns the vec ids [f n / F, (f + 1) n / F)) and `random` (every id drawn a tenant).  Per combination, over --reps repeats ALTERNATING between
+    the three, each a window of --inner back-to-back calls between two device events, ms PER CALL as median [min, max]:
+      multi      (a) the one multi call
+      per_call   (b) what a caller does today: F vers_ivf_search_filtered_dev calls, call f over tenant f's queries (rows f, f + F, ... of the
+                 batch, addressed through the query stride: no gather) into a tenant-major block, then the result rows put back in batch order
+                 (one index_select per output array)
+      whole      (c) F = 1 only: the per-call search of the whole batch -- the price of the new kernel at no benefit
+    + vers_ivf_filter_stats of (a) and summed over (b)'s calls, as tile fractions.  (a)'s rows are checked equal to (b)'s before timing.
+    Prints ONE JSON line."""
+    import torch
+    from tests import datagen as dg
+    from vers_amd import capi
+    from vers_amd.index import IVFFlatIndex
+
+    torch.cuda.set_device(0)
+    n, d, nlist, nprobe, top_k = args.rows, args.d, args.nlist, args.nprobe, args.top_k
+    ld = (d + 3) // 4 * 4
+    n_modes = max(1, args.modes_per_list * nlist)
+    sigma = float(dg.default_sigma(d))
+    SEED_X, SEED_C = 0x5EED0001, 0x5EEDC0DE   # bench.py's corpus
+    X = torch.empty(n, ld, dtype=torch.float32, device="cuda")
+    capi.gen_rows_dev(X.data_ptr(), n, d, ld, 1, SEED_X, SEED_C, n_modes, sigma)
+    init = (dg.mix64(np.uint64(0xB01D) + np.arange(nlist, dtype=np.uint64)) % np.uint64(n)).astype(np.uint64)
+    index = IVFFlatIndex(d)
+    t0 = time.perf_counter()
+    assert index.build_dev(X.data_ptr(), n, nlist, 1, args.kmeans_iters, init)
+    t_build = time.perf_counter() - t0
+    log(f"[bench_filtered --multi] index built in {t_build:.2f} s")
+
+    rng = np.random.default_rng(0xF117E3)
+    draw = rng.integers(0, 64, n)
+    KEYS = ("tiles_planned", "tiles_loaded", "items_skipped", "rows_allowed")
+    out = {}
+    for b in (int(x) for x in args.multi_batches.split(",")):
+        Q = torch.empty(b, ld, dtype=torch.float32, device="cuda")
+        capi.gen_rows_dev(Q.data_ptr(), b, d, ld, 1, SEED_X + 1, SEED_C, n_modes, sigma)
+        res = {}
+        for F in (1, 8, 64):
+            assert b % F == 0
+            bf = b // F
+            for layout in (("contiguous", "random") if F > 1 else ("all",)):
+                tenant = (np.arange(n, dtype=np.int64) * F) // n if layout != "random" else draw % F
+                words_h = capi.allowed_bitmaps([tenant == f for f in range(F)], n)
+                stride = words_h.shape[1]
+                words = torch.from_numpy(words_h.view(np.int64)).cuda()
+                fo = torch.from_numpy((np.arange(b) % F).astype(np.int32)).cuda()
+                # batch row of tenant-major row f * bf + i is i * F + f; back[q] = the tenant-major row of batch row q
+                back = torch.from_numpy(((np.arange(b) % F) * bf + np.arange(b) // F).astype(np.int64)).cuda()
+                oi = torch.zeros(b, top_k, dtype=torch.int64, device="cuda"); od = torch.zeros(b, top_k, device="cuda"); oc = torch.zeros(b, dtype=torch.int32, device="cuda")
+                ti = torch.zeros(b, top_k, dtype=torch.int64, device="cuda"); td = torch.zeros(b, top_k, device="cuda"); tc = torch.zeros(b, dtype=torch.int32, device="cuda")
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                got = {}
+
+                def multi():
+                    index.search_filtered_multi_dev(Q.data_ptr(), ld, b, top_k, nprobe, words.data_ptr(), stride, F, n, fo.data_ptr(), oi.data_ptr(), od.data_ptr(),
+                                                    oc.data_ptr())
+
+                def per_call(stats=None):
+                    for f in range(F):
+                        index.search_filtered_dev(Q.data_ptr() + 4 * ld * f, ld * F, bf, top_k, nprobe, words.data_ptr() + 8 * stride * f, n,
+                                                  ti.data_ptr() + 8 * top_k * bf * f, td.data_ptr() + 4 * top_k * bf * f, tc.data_ptr() + 4 * bf * f)
+                        if stats is not None:
+                            st = index.filter_stats()["last"]
+                            for k in KEYS:
+                                stats[k] = stats.get(k, 0) + st[k]
+                    got["ids"], got["dist"], got["cnt"] = ti.index_select(0, back), td.index_select(0, back), tc.index_select(0, back)
+
+                def whole():
+                    index.search_filtered_dev(Q.data_ptr(), ld, b, top_k, nprobe, words.data_ptr(), n, ti.data_ptr(), td.data_ptr(), tc.data_ptr())
+
+                def timed(fn):
+                    torch.cuda.synchronize()
+                    e0.record()
+                    for _ in range(args.inner):
+                        fn()
+                    e1.record()
+                    index.poll(); torch.cuda.synchronize()
+                    return e0.elapsed_time(e1) / args.inner
+
+                # warm-up of every shape the timed window uses; (a)'s rows are (b)'s; the counters
+                multi(); index.poll(); torch.cuda.synchronize()
+                st_a = index.filter_stats()["last"]
+                st_b = {}
+                per_call(st_b); index.poll(); torch.cuda.synchronize()
+                cnt = oc.cpu().numpy()
+                assert np.array_equal(cnt, got["cnt"].cpu().numpy()), "counts of the multi call and of the per-call calls differ"
+                live = torch.arange(top_k, device="cuda")[None, :] < oc[:, None]
+                assert bool(((oi == got["ids"]) | ~live).all()) and bool(((od.view(torch.int32) == got["dist"].view(torch.int32)) | ~live).all()), "rows differ"
+                whole(); index.poll(); torch.cuda.synchronize()
+                kinds = {"multi": multi, "per_call": per_call, **({"whole": whole} if F == 1 else {})}
+                runs = {k: [] for k in kinds}
+                for _ in range(args.reps):
+                    for k, fn in kinds.items():
+                        runs[k].append(timed(fn))
+                frac = lambda st: round(st["tiles_loaded"] / max(1, st["tiles_planned"]), 4)
+                res[f"F{F}/{layout}"] = {**{k: mms(v) for k, v in runs.items()},
+                                         "multi_over_per_call": round(float(np.median(runs["multi"]) / np.median(runs["per_call"])), 3),
+                                         "multi_stats": {**st_a, "tiles_loaded_fraction": frac(st_a)},
+                                         "per_call_stats": {**st_b, "tiles_loaded_fraction": frac(st_b)},
+                                         "mean_count": round(float(cnt.mean()), 2)}
+                log(f"[bench_filtered --multi] batch {b} F{F}/{layout}: {json.dumps(res[f'F{F}/{layout}'])}")
+        out[f"batch{b}"] = res
+    line = {"metric": f"vers_ivf_search_filtered_multi_dev in ms per call, IVFFlat (N={n} d={d} nlist={nlist}) nprobe={nprobe} top_k={top_k}",
+            "build_s": round(t_build, 2), "reps": args.reps, "inner": args.inner, **out}
+    index.close()
+    print(json.dumps(line), flush=True)
+    return 0
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", type=int, default=1_000_000)
@@ -168,10 +281,15 @@ def main():
     ap.add_argument("--batches", default="1,64,1024")
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--range", action="store_true", help="the filtered RANGE search instead (vers_ivf_range_search_filtered_dev): see range_main")
+    ap.add_argument("--multi", action="store_true", help="a filter per query instead (vers_ivf_search_filtered_multi_dev) against one per-call search per tenant: see multi_main")
+    ap.add_argument("--multi-batches", default="64,1024", help="--multi: the batch sizes (multiples of 64)")
+    ap.add_argument("--inner", type=int, default=8, help="--multi: back-to-back calls per timed window")
     args = ap.parse_args()
     assert args.reps >= 5, "at least 5 alternating repeats per point"
     if args.range:
         return range_main(args)
+    if args.multi:
+        return multi_main(args)
 
     import torch
     from tests import datagen as dg

@@ -132,6 +132,14 @@ SIGNATURES = {
     "vers_ivf_search_exhaustive_filtered": (C.c_int32, [_vp, _vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, _vp, C.c_uint64, _vp, _vp, _vp]),
     "vers_ivf_search_exhaustive_filtered_dev": (C.c_int32, [_vp, _vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, _vp, C.c_uint64, _vp, _vp, _vp,
                                                             _vp]),
+    "vers_ivf_search_filtered_multi": (C.c_int32, [_vp, _vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, _vp, C.c_uint64, C.c_uint32, C.c_uint64, _vp,
+                                                   _vp, _vp, _vp]),
+    "vers_ivf_search_filtered_multi_dev": (C.c_int32, [_vp, _vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, _vp, C.c_uint64, C.c_uint32, C.c_uint64,
+                                                       _vp, _vp, _vp, _vp, _vp]),
+    "vers_ivf_search_exhaustive_filtered_multi": (C.c_int32, [_vp, _vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, _vp, C.c_uint64, C.c_uint32,
+                                                              C.c_uint64, _vp, _vp, _vp, _vp]),
+    "vers_ivf_search_exhaustive_filtered_multi_dev": (C.c_int32, [_vp, _vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, _vp, C.c_uint64, C.c_uint32,
+                                                                  C.c_uint64, _vp, _vp, _vp, _vp, _vp]),
     "vers_ivf_filter_stats": (C.c_int32, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "vers_ivf_range_search_filtered": (C.c_int32, [_vp, _vp, C.c_uint64, C.c_uint32, _vp, C.c_uint32, C.c_uint32, _vp, C.c_uint64, _vp, _vp, _vp,
                                                    C.c_uint64, C.POINTER(C.c_uint64)]),
@@ -228,6 +236,24 @@ def allowed_bitmap(x, n_bits: int) -> np.ndarray:
     if ids.size:
         np.bitwise_or.at(words, (ids >> np.uint64(6)).astype(np.int64), np.uint64(1) << (ids & np.uint64(63)))
     return words
+
+
+FILTER_MAX = 64  # VERS_FILTER_MAX: bitmaps per call of the searches with a filter per query
+
+
+def allowed_bitmaps(filters, n_bits: int, stride_words=None) -> np.ndarray:
+    """The filters of a search with a filter per query as the C ABI takes them: u64 [len(filters), stride_words], row f = allowed_bitmap(
+    filters[f], n_bits) -- one n_bits for all.  stride_words defaults to the words one bitmap needs (at least one); a larger stride leaves
+    zero padding behind each bitmap."""
+    n_bits = int(n_bits)
+    need = max(1, (n_bits + 63) // 64)
+    stride = need if stride_words is None else int(stride_words)
+    if stride < need:
+        raise ValueError("stride_words is smaller than one bitmap")
+    out = np.zeros((len(filters), stride), dtype=np.uint64)
+    for f, x in enumerate(filters):
+        out[f, :need] = allowed_bitmap(x, n_bits)
+    return out
 
 
 class FlatCorpus:

@@ -50,6 +50,7 @@ struct SearchWs {
   // filtered search (filter.hip.h): one u64 per 64-row storage tile | the bitmap of a host-pointer call | the call's four counters, then a slot of four
   // words per wave a filtered scan can launch (summed into the counters by filter_stats_fold_kernel)
   DevBuf flt_mask, flt_bits, flt_stats;
+  DevBuf flt_rows, flt_of;  // a filter per query (filter_multi.hip.h): the row_sets words; the staged filter_of of a host-pointer call
   bool no_ahead = false;  // the plan of a filtered call neither consumes a look-ahead slot nor touches a pending request (plan_search)
   DevBuf rg_rlims;  // sharded range search: every rank's CSR limits [world][b + 1] (range_merge.hip.h); the gather itself goes through g_send / g_recv
   DevBuf g_send, g_recv;  // sharded search without the host in the loop: this rank's [2][b][top_k] partial | the world's

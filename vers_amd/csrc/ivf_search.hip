@@ -16,6 +16,7 @@
 #include "range_driver.hip.h"
 #include "range_merge.hip.h"
 #include "filter.hip.h"
+#include "filter_multi.hip.h"
 #include "filter_range.hip.h"
 
 namespace vers {
@@ -192,12 +193,20 @@ namespace ivf {
 
 static size_t filter_wave_slots(const vers_ivf* h) { return (size_t)h->n_cu * 3 * kWavesPerBlock; }  // (filter_scan_kernel: at most 3 blocks per CU)
 
+// The filtered kernel a scan launches: none, the per-call mask's (filter.hip.h) or the per-query sets' (filter_multi.hip.h).  The drivers pass
+// the choice down; nothing else about a pass differs between the two.
+struct FilterChoice {
+  const FilterParams* one = nullptr;
+  const FilterMultiParams* multi = nullptr;
+  explicit operator bool() const { return one != nullptr || multi != nullptr; }
+};
+
 // One pass of the ordered-chain list scan over the planned items, timed through the scan-timing ring.  Without a filter, option "scan_debug"
 // decides: bit 3 switches the pruning bounds off (A/B runs), bit 4 stamps phases, bit 5 switches the hand-out counter off.  flt: the filtered
 // kernel (filter.hip.h), which knows no diagnosis switches -- bounds and counter always on for QG != 1 -- and launches no more waves than it
-// has counter slots (filter_begin).
+// has counter slots (filter_begin).  The per-query kernel (filter_multi.hip.h) is launched the same way.
 template <int QG>
-int32_t launch_ivf_scan(vers_ivf* h, const IvfSrc<QG>& src, uint32_t items_bound, hipStream_t st, const uint64_t* lower, const FilterParams* flt = nullptr) {
+int32_t launch_ivf_scan(vers_ivf* h, const IvfSrc<QG>& src, uint32_t items_bound, hipStream_t st, const uint64_t* lower, FilterChoice flt = {}) {
   ScanParams p = ivf_scan_params(h, src.k_keep, lower);
   p.debug = flt ? 0u : scan_debug_flags();
   if (p.debug & 16u) {  // diagnosis only
@@ -213,7 +222,8 @@ int32_t launch_ivf_scan(vers_ivf* h, const IvfSrc<QG>& src, uint32_t items_bound
   const uint32_t blocks = scan_grid(h->n_cu, QG, h->ld, items_bound, flt ? (uint32_t)(filter_wave_slots(h) / kWavesPerBlock) : 0xFFFFFFFFu);
   return with_metric(h->metric, [&](auto m) -> int32_t {
     constexpr int M = decltype(m)::value;
-    if (flt) return launch_scan_timed(filter_scan_kernel<QG, M, IvfSrc<QG>>, blocks, kWavesPerBlock, lds, st, src, p, *flt);
+    if (flt.multi) return launch_scan_timed(filter_multi_scan_kernel<QG, M, IvfSrc<QG>>, blocks, kWavesPerBlock, lds, st, src, p, *flt.multi);
+    if (flt.one) return launch_scan_timed(filter_scan_kernel<QG, M, IvfSrc<QG>>, blocks, kWavesPerBlock, lds, st, src, p, *flt.one);
     return launch_scan_timed(scan_kernel<QG, M, IvfSrc<QG>>, blocks, kWavesPerBlock, lds, st, src, p);
   });
 }
@@ -468,13 +478,9 @@ int32_t search_dev_locked(vers_ivf* h, const float* q_dev, uint64_t ldq_in, uint
 }
 
 // ---- filtered top-k search (filter.hip.h): a bitmap of allowed vec ids per call = a virtual removal of the others -------------------
-// The tile mask of the call over `n_rows` storage rows + its zeroed counters.  The mask kernel is bracketed by a record of the scan-timing
-// ring (vers_ivf_scan_times: a filtered call leaves the mask kernel's record, then one per scan pass).
-static int32_t filter_begin(vers_ivf* h, const uint64_t* bits_dev, uint64_t n_bits, uint64_t n_rows, hipStream_t st, FilterParams& f) {
+// the call's zeroed counters, for either filtered kernel: the call's four | a slot of four words per wave a filtered scan can launch
+static int32_t filter_counters_begin(vers_ivf* h, hipStream_t st, unsigned long long*& stats, unsigned long long*& wave_slots) {
   { const int ev = scan_events_ref().load(); W->ev_on = ev == 1 || ev == 2; }
-  const uint64_t n_tiles = (n_rows + kWave - 1) / kWave;
-  if (int32_t rc = W->flt_mask.reserve(std::max<size_t>(1, n_tiles) * sizeof(uint64_t))) return rc;
-  // the call's four counters | a slot of four words per wave a filtered scan can launch
   const size_t stat_words = kFltStats + filter_wave_slots(h) * 4;
   if (int32_t rc = W->flt_stats.reserve(stat_words * sizeof(unsigned long long))) return rc;
   {
@@ -485,9 +491,18 @@ static int32_t filter_begin(vers_ivf* h, const uint64_t* bits_dev, uint64_t n_bi
     }
   }
   VERS_HIP_TRY(hipMemsetAsync(W->flt_stats.p, 0, stat_words * sizeof(unsigned long long), st));
+  stats = W->flt_stats.as<unsigned long long>();
+  wave_slots = stats + kFltStats;
+  return VERS_OK;
+}
+
+// The tile mask of the call over `n_rows` storage rows + its zeroed counters.  The mask kernel is bracketed by a record of the scan-timing
+// ring (vers_ivf_scan_times: a filtered call leaves the mask kernel's record, then one per scan pass).
+static int32_t filter_begin(vers_ivf* h, const uint64_t* bits_dev, uint64_t n_bits, uint64_t n_rows, hipStream_t st, FilterParams& f) {
+  const uint64_t n_tiles = (n_rows + kWave - 1) / kWave;
+  if (int32_t rc = W->flt_mask.reserve(std::max<size_t>(1, n_tiles) * sizeof(uint64_t))) return rc;
+  if (int32_t rc = filter_counters_begin(h, st, f.stats, f.wave_slots)) return rc;
   f.tile_mask = W->flt_mask.as<uint64_t>();
-  f.stats = W->flt_stats.as<unsigned long long>();
-  f.wave_slots = f.stats + kFltStats;
   return timed_scan(st, [&]() -> int32_t {
     if (n_bits == 0 || n_tiles == 0) {  // the empty filter: nothing is allowed
       VERS_HIP_TRY(hipMemsetAsync(W->flt_mask.p, 0, std::max<size_t>(1, n_tiles) * sizeof(uint64_t), st));
@@ -496,6 +511,41 @@ static int32_t filter_begin(vers_ivf* h, const uint64_t* bits_dev, uint64_t n_bi
     const uint64_t blocks = std::min<uint64_t>((uint64_t)h->n_cu, (n_tiles + kFltMaskThreads / kWave - 1) / (kFltMaskThreads / kWave));
     hipLaunchKernelGGL(filter_tile_mask_kernel, dim3((unsigned)blocks), dim3(kFltMaskThreads), 0, st, (const uint32_t*)h->row_ids.as<uint32_t>(), n_rows, bits_dev, n_bits,
                        W->flt_mask.as<uint64_t>(), f.stats);
+    VERS_HIP_TRY(hipGetLastError());
+    return VERS_OK;
+  });
+}
+
+// The bitmaps of a call with a filter per query (filter_multi.hip.h): n_filters bitmaps `stride_words` apart, one n_bits for all, and the
+// batch's filter_of, all on the device.
+struct FilterMultiSpec {
+  uint64_t stride_words;
+  uint32_t n_filters;
+  const uint32_t* filter_of;
+};
+
+// filter_begin's twin for a filter per query: row_sets (8 bytes per storage row, whole tiles) and tile_sets (in the per-call mask's buffer)
+// over `n_rows` storage rows + the zeroed counters; the mask kernel inside the same bracket of the scan-timing ring.
+static int32_t filter_multi_begin(vers_ivf* h, const uint64_t* filters_dev, uint64_t n_bits, const FilterMultiSpec& ms, uint64_t n_rows, hipStream_t st,
+                                  FilterMultiParams& f) {
+  const uint64_t n_tiles = (n_rows + kWave - 1) / kWave;
+  const size_t tile_bytes = std::max<size_t>(1, n_tiles) * sizeof(uint64_t), row_bytes = tile_bytes * kWave;
+  if (int32_t rc = W->flt_mask.reserve(tile_bytes)) return rc;
+  if (int32_t rc = W->flt_rows.reserve(row_bytes)) return rc;
+  if (int32_t rc = filter_counters_begin(h, st, f.stats, f.wave_slots)) return rc;
+  f.tile_sets = W->flt_mask.as<uint64_t>();
+  f.row_sets = W->flt_rows.as<uint64_t>();
+  f.filter_of = ms.filter_of;
+  f.n_filters = ms.n_filters;
+  return timed_scan(st, [&]() -> int32_t {
+    if (n_bits == 0 || n_tiles == 0) {  // every filter is empty: nothing is allowed
+      VERS_HIP_TRY(hipMemsetAsync(W->flt_mask.p, 0, tile_bytes, st));
+      VERS_HIP_TRY(hipMemsetAsync(W->flt_rows.p, 0, row_bytes, st));
+      return VERS_OK;
+    }
+    const uint64_t blocks = std::min<uint64_t>((uint64_t)h->n_cu, (n_tiles + kFltMaskThreads / kWave - 1) / (kFltMaskThreads / kWave));
+    hipLaunchKernelGGL(filter_multi_mask_kernel, dim3((unsigned)blocks), dim3(kFltMaskThreads), 0, st, (const uint32_t*)h->row_ids.as<uint32_t>(), n_rows, filters_dev,
+                       ms.stride_words, ms.n_filters, n_bits, W->flt_rows.as<uint64_t>(), W->flt_mask.as<uint64_t>(), f.stats);
     VERS_HIP_TRY(hipGetLastError());
     return VERS_OK;
   });
@@ -513,12 +563,14 @@ static int32_t filter_end(vers_ivf* h, hipStream_t st) {
 
 // launch_seg_scan's filtered twin -- no bounds, no counter either -- but timed through the scan-timing ring, and no more waves than counter slots
 template <int QG>
-int32_t launch_filter_seg_scan(vers_ivf* h, const SegSrc<QG, true>& src, uint32_t n_items, int metric, const FilterParams& f, hipStream_t st,
+int32_t launch_filter_seg_scan(vers_ivf* h, const SegSrc<QG, true>& src, uint32_t n_items, int metric, FilterChoice f, hipStream_t st,
                                const uint64_t* lower) {
   const ScanParams p = ivf_scan_params(h, src.k, lower);
   const uint32_t blocks = scan_grid(h->n_cu, QG, h->ld, n_items, (uint32_t)(filter_wave_slots(h) / kWavesPerBlock));
   return with_metric(metric, [&](auto m) -> int32_t {
-    return launch_scan_timed(filter_scan_kernel<QG, decltype(m)::value, SegSrc<QG, true>>, blocks, kWavesPerBlock, scan_lds_bytes(QG, h->ld), st, src, p, f);
+    if (f.multi)
+      return launch_scan_timed(filter_multi_scan_kernel<QG, decltype(m)::value, SegSrc<QG, true>>, blocks, kWavesPerBlock, scan_lds_bytes(QG, h->ld), st, src, p, *f.multi);
+    return launch_scan_timed(filter_scan_kernel<QG, decltype(m)::value, SegSrc<QG, true>>, blocks, kWavesPerBlock, scan_lds_bytes(QG, h->ld), st, src, p, *f.one);
   });
 }
 
@@ -530,7 +582,7 @@ int32_t launch_filter_seg_scan(vers_ivf* h, const SegSrc<QG, true>& src, uint32_
 //   flt             the filtered kernel, timed; refuses a batch whose slots do not fit 32 bits (the unfiltered call never has); resets the
 //                   slots per pass, since a segment without an allowed row writes nothing and its slots must read as empty
 static int32_t run_exhaustive_passes(vers_ivf* h, const float* q_dev, uint64_t ldq_in, uint32_t b, uint32_t top_k, uint32_t metric, uint64_t n_rows,
-                                     int64_t fixed_seg_rows, const FilterParams* flt, uint64_t* out_ids, float* out_dist, uint32_t* out_count, hipStream_t st) {
+                                     int64_t fixed_seg_rows, FilterChoice flt, uint64_t* out_ids, float* out_dist, uint32_t* out_count, hipStream_t st) {
   const SegPlan sp = seg_plan(n_rows, b, h->ld, h->n_cu, fixed_seg_rows);
   if (int32_t rc = W->qil.reserve((size_t)sp.n_qg * h->ldq * sp.QG * sizeof(float))) return rc;
   if (int32_t rc = launch_stage_queries(q_dev, ldq_in, h->d, W->qil.as<float>(), h->ldq, b, sp.QG, st)) return rc;
@@ -549,7 +601,7 @@ static int32_t run_exhaustive_passes(vers_ivf* h, const float* q_dev, uint64_t l
     if (int32_t rc = with_qg<1, 8>(sp.QG, [&](auto qg) -> int32_t {
           using Src = SegSrc<decltype(qg)::value, true>;
           const Src src = make_seg_src<Src>(h->rows.as<float>(), n_rows, h->ld, sp, W->qil.as<float>(), h->ldq, b, W->xpart.as<uint64_t>(), k_pass, h->row_ids.as<uint32_t>());
-          return flt ? launch_filter_seg_scan(h, src, sp.n_items, (int)metric, *flt, st, lower) : launch_seg_scan(h, src, sp.n_items, (int)metric, st, lower);
+          return flt ? launch_filter_seg_scan(h, src, sp.n_items, (int)metric, flt, st, lower) : launch_seg_scan(h, src, sp.n_items, (int)metric, st, lower);
         })) return rc;
     hipLaunchKernelGGL(seg_merge_kernel, dim3(b), dim3(kWave * kMergeWaves), 0, st, W->xpart.as<uint64_t>(), sp.n_segs, k_pass, top_k, (uint32_t)rank0, out_ids,
                        out_dist, out_count, lower_out);
@@ -565,21 +617,24 @@ int32_t exhaustive_dev_locked(vers_ivf* h, const float* q_dev, uint64_t ldq_in, 
     VERS_HIP_TRY(hipMemsetAsync(out_count, 0, sizeof(uint32_t) * b, st));
     return VERS_OK;
   }
-  return run_exhaustive_passes(h, q_dev, ldq_in, b, top_k, metric, h->cap_rows, 0, nullptr, out_ids, out_dist, out_count, st);
+  return run_exhaustive_passes(h, q_dev, ldq_in, b, top_k, metric, h->cap_rows, 0, FilterChoice{}, out_ids, out_dist, out_count, st);
 }
 
 // Filtered search over the min(nprobe, k) nearest lists, nprobe >= 1: mask kernel, the plan of the ordered-chain scan (the lists are ranked as
 // without a filter: the centroids do not depend on it), per pass the filtered scan, ivf_merge_kernel as it is.  The caller has checked nprobe,
-// the handle's sharding and its centroids.
+// the handle's sharding and its centroids.  multi: bits_dev holds the bitmaps of a call with a filter per query; the mask kernel and the scan
+// kernel are then filter_multi.hip.h's, everything else is the same.
 int32_t filtered_dev_locked(vers_ivf* h, const float* q_dev, uint64_t ldq_in, uint32_t b, uint32_t top_k, uint32_t nprobe, const uint64_t* bits_dev,
-                            uint64_t n_bits, uint64_t* out_ids, float* out_dist, uint32_t* out_count, hipStream_t st) {
+                            uint64_t n_bits, uint64_t* out_ids, float* out_dist, uint32_t* out_count, hipStream_t st, const FilterMultiSpec* multi = nullptr) {
   if (b == 0) return VERS_OK;
   if (top_k == 0) {
     VERS_HIP_TRY(hipMemsetAsync(out_count, 0, sizeof(uint32_t) * b, st));
     return VERS_OK;
   }
   FilterParams f;
-  if (int32_t rc = filter_begin(h, bits_dev, n_bits, h->cap_rows, st, f)) return rc;
+  FilterMultiParams fm;
+  if (int32_t rc = multi ? filter_multi_begin(h, bits_dev, n_bits, *multi, h->cap_rows, st, fm) : filter_begin(h, bits_dev, n_bits, h->cap_rows, st, f)) return rc;
+  const FilterChoice flt{multi ? nullptr : &f, multi ? &fm : nullptr};
   SearchPlan s;
   W->no_ahead = true;
   const int32_t prc = plan_search(h, q_dev, ldq_in, b, top_k, nprobe, st, s, true);
@@ -589,7 +644,7 @@ int32_t filtered_dev_locked(vers_ivf* h, const float* q_dev, uint64_t ldq_in, ui
   W->tot_valid = true;
   if (int32_t rc = run_chain_passes(h, s, b, top_k, out_ids, out_dist, out_count, nullptr, /*unfiltered=*/false, st, [&](const uint64_t* lower) -> int32_t {
         return with_qg<1, 8, 16>(s.QG, [&](auto qg) -> int32_t {
-          return launch_ivf_scan(h, make_ivf_src<decltype(qg)::value>(h, s, 0u), (uint32_t)s.items_bound, st, lower, &f);
+          return launch_ivf_scan(h, make_ivf_src<decltype(qg)::value>(h, s, 0u), (uint32_t)s.items_bound, st, lower, flt);
         });
       })) return rc;
   return filter_end(h, st);
@@ -599,7 +654,7 @@ int32_t filtered_dev_locked(vers_ivf* h, const float* q_dev, uint64_t ldq_in, ui
 // the segment length here as it does for the chains.  An index without centroids (a streamed upload in progress included) is scanned as zero
 // rows: counts 0.
 int32_t exhaustive_filtered_dev_locked(vers_ivf* h, const float* q_dev, uint64_t ldq_in, uint32_t b, uint32_t top_k, uint32_t metric, const uint64_t* bits_dev,
-                                       uint64_t n_bits, uint64_t* out_ids, float* out_dist, uint32_t* out_count, hipStream_t st) {
+                                       uint64_t n_bits, uint64_t* out_ids, float* out_dist, uint32_t* out_count, hipStream_t st, const FilterMultiSpec* multi = nullptr) {
   if (b == 0) return VERS_OK;
   if (top_k == 0) {
     VERS_HIP_TRY(hipMemsetAsync(out_count, 0, sizeof(uint32_t) * b, st));
@@ -607,8 +662,10 @@ int32_t exhaustive_filtered_dev_locked(vers_ivf* h, const float* q_dev, uint64_t
   }
   const uint64_t n_rows = (h->k == 0 || h->up.open) ? 0 : h->cap_rows;
   FilterParams f;
-  if (int32_t rc = filter_begin(h, bits_dev, n_bits, n_rows, st, f)) return rc;
-  if (int32_t rc = run_exhaustive_passes(h, q_dev, ldq_in, b, top_k, metric, n_rows, knobs().seg_rows, &f, out_ids, out_dist, out_count, st)) return rc;
+  FilterMultiParams fm;
+  if (int32_t rc = multi ? filter_multi_begin(h, bits_dev, n_bits, *multi, n_rows, st, fm) : filter_begin(h, bits_dev, n_bits, n_rows, st, f)) return rc;
+  const FilterChoice flt{multi ? nullptr : &f, multi ? &fm : nullptr};
+  if (int32_t rc = run_exhaustive_passes(h, q_dev, ldq_in, b, top_k, metric, n_rows, knobs().seg_rows, flt, out_ids, out_dist, out_count, st)) return rc;
   return filter_end(h, st);
 }
 
@@ -1398,6 +1455,112 @@ int32_t vers_ivf_search_exhaustive_filtered(vers_ivf_t* h, const float* queries,
                                             const uint64_t* allowed_bits, uint64_t n_bits, uint64_t* out_ids, float* out_dist, uint32_t* out_count) {
   return filtered_host_common(h, "vers_ivf_search_exhaustive_filtered", queries, q_stride_bytes, b, top_k, false, metric, allowed_bits, n_bits, out_ids, out_dist,
                               out_count);
+}
+
+// ---- filtered top-k search with a filter per query (filter_multi.hip.h) ----
+// what the four entry points refuse before they touch the device: their own arguments, then the per-call checks
+static int32_t filter_multi_check(vers_ivf* h, const char* who, bool probed, uint32_t nprobe, uint32_t b, const uint64_t* filters, uint64_t stride_words,
+                                  uint32_t n_filters, uint64_t n_bits, const uint32_t* filter_of) {
+  if (b != 0 && n_filters == 0) return fail(VERS_ERR_INVALID, std::string(who) + ": n_filters == 0");
+  if (n_filters > VERS_FILTER_MAX)
+    return fail(VERS_ERR_INVALID, std::string(who) + ": more than VERS_FILTER_MAX bitmaps in one call; split the batch by allowed set");
+  if (b != 0 && filter_of == nullptr) return fail(VERS_ERR_INVALID, std::string(who) + ": NULL filter_of");
+  if (n_bits != 0 && stride_words < (n_bits + 63) / 64) return fail(VERS_ERR_INVALID, std::string(who) + ": filter_stride_words is smaller than ceil(n_bits / 64)");
+  return filter_check(h, who, probed, nprobe, filters, n_bits);
+}
+
+static int32_t filtered_multi_dev_common(vers_ivf_t* h, const char* who, bool probed, const float* queries_dev, uint64_t ldq_floats, uint32_t b, uint32_t top_k,
+                                         uint32_t nprobe_or_metric, const uint64_t* filters_dev, uint64_t stride_words, uint32_t n_filters, uint64_t n_bits,
+                                         const uint32_t* filter_of_dev, uint64_t* out_ids_dev, float* out_dist_dev, uint32_t* out_count_dev, void* stream) {
+  if (!h) return fail(VERS_ERR_INVALID, "null handle");
+  if (!probed && nprobe_or_metric > VERS_METRIC_COSDIST) return fail(VERS_ERR_INVALID, "unknown metric");
+  if (b && (!queries_dev || ldq_floats < h->d || !out_count_dev || (top_k && (!out_ids_dev || !out_dist_dev))))
+    return fail(VERS_ERR_INVALID, std::string(who) + ": bad arguments");
+  std::shared_lock<std::shared_mutex> lk(h->index);
+  if (int32_t rc = filter_multi_check(h, who, probed, probed ? nprobe_or_metric : 1u, b, filters_dev, stride_words, n_filters, n_bits, filter_of_dev)) return rc;
+  if (b == 0) return VERS_OK;
+  DeviceGuard g(h->device);
+  WsLease lease(h, true, (hipStream_t)stream);
+  if (lease.rc) return lease.rc;
+  if (int32_t rc = lease.order_on((hipStream_t)stream)) return rc;
+  const FilterMultiSpec ms{stride_words, n_filters, filter_of_dev};
+  return probed ? filtered_dev_locked(h, queries_dev, ldq_floats, b, top_k, nprobe_or_metric, filters_dev, n_bits, out_ids_dev, out_dist_dev, out_count_dev,
+                                      (hipStream_t)stream, &ms)
+                : exhaustive_filtered_dev_locked(h, queries_dev, ldq_floats, b, top_k, nprobe_or_metric, filters_dev, n_bits, out_ids_dev, out_dist_dev, out_count_dev,
+                                                 (hipStream_t)stream, &ms);
+}
+
+int32_t vers_ivf_search_filtered_multi_dev(vers_ivf_t* h, const float* queries_dev, uint64_t ldq_floats, uint32_t b, uint32_t top_k, uint32_t nprobe,
+                                           const uint64_t* filters_dev, uint64_t filter_stride_words, uint32_t n_filters, uint64_t n_bits,
+                                           const uint32_t* filter_of_dev, uint64_t* out_ids_dev, float* out_dist_dev, uint32_t* out_count_dev, void* stream) {
+  return filtered_multi_dev_common(h, "vers_ivf_search_filtered_multi_dev", true, queries_dev, ldq_floats, b, top_k, nprobe, filters_dev, filter_stride_words, n_filters,
+                                   n_bits, filter_of_dev, out_ids_dev, out_dist_dev, out_count_dev, stream);
+}
+
+int32_t vers_ivf_search_exhaustive_filtered_multi_dev(vers_ivf_t* h, const float* queries_dev, uint64_t ldq_floats, uint32_t b, uint32_t top_k, uint32_t metric,
+                                                      const uint64_t* filters_dev, uint64_t filter_stride_words, uint32_t n_filters, uint64_t n_bits,
+                                                      const uint32_t* filter_of_dev, uint64_t* out_ids_dev, float* out_dist_dev, uint32_t* out_count_dev,
+                                                      void* stream) {
+  return filtered_multi_dev_common(h, "vers_ivf_search_exhaustive_filtered_multi_dev", false, queries_dev, ldq_floats, b, top_k, metric, filters_dev,
+                                   filter_stride_words, n_filters, n_bits, filter_of_dev, out_ids_dev, out_dist_dev, out_count_dev, stream);
+}
+
+// host-pointer calls: filtered_host_common's staging, with the bitmaps packed to ceil(n_bits / 64) words each and filter_of beside them.  An
+// entry of filter_of at or beyond n_filters is refused here, where it can be read.
+static int32_t filtered_multi_host_common(vers_ivf_t* h, const char* who, const float* queries, uint64_t q_stride_bytes, uint32_t b, uint32_t top_k, bool probed,
+                                          uint32_t nprobe_or_metric, const uint64_t* filters, uint64_t stride_words, uint32_t n_filters, uint64_t n_bits,
+                                          const uint32_t* filter_of, uint64_t* out_ids, float* out_dist, uint32_t* out_count) {
+  if (!h) return fail(VERS_ERR_INVALID, "null handle");
+  if (!probed && nprobe_or_metric > VERS_METRIC_COSDIST) return fail(VERS_ERR_INVALID, "unknown metric");
+  if (b && (!queries || q_stride_bytes < (uint64_t)h->d * 4 || q_stride_bytes % 4 || !out_count || (top_k && (!out_ids || !out_dist))))
+    return fail(VERS_ERR_INVALID, std::string(who) + ": bad arguments");
+  std::shared_lock<std::shared_mutex> lk(h->index);
+  if (int32_t rc = filter_multi_check(h, who, probed, probed ? nprobe_or_metric : 1u, b, filters, stride_words, n_filters, n_bits, filter_of)) return rc;
+  for (uint32_t q = 0; q < b; ++q)
+    if (filter_of[q] >= n_filters) return fail(VERS_ERR_INVALID, std::string(who) + ": filter_of[" + std::to_string(q) + "] is not below n_filters");
+  if (b == 0) return VERS_OK;
+  DeviceGuard g(h->device);
+  WsLease lease(h);
+  if (lease.rc) return lease.rc;
+  HostStatusSlot slot(h);
+  HostIo io;
+  if (int32_t rc = host_io_begin(h, queries, q_stride_bytes, b, top_k, io)) return rc;
+  lease.st = W->io_stream;
+  const size_t words = (size_t)((n_bits + 63) / 64), bit_bytes = words * sizeof(uint64_t);
+  int32_t rc = W->flt_bits.reserve(std::max<size_t>(8, bit_bytes * n_filters));
+  if (!rc) rc = W->flt_of.reserve((size_t)b * sizeof(uint32_t));
+  if (!rc && bit_bytes &&
+      hipMemcpy2DAsync(W->flt_bits.p, bit_bytes, filters, (size_t)stride_words * sizeof(uint64_t), bit_bytes, n_filters, hipMemcpyHostToDevice, W->io_stream) != hipSuccess)
+    rc = fail(VERS_ERR_HIP, std::string(who) + ": staging the bitmaps failed");
+  if (!rc && hipMemcpyAsync(W->flt_of.p, filter_of, (size_t)b * sizeof(uint32_t), hipMemcpyHostToDevice, W->io_stream) != hipSuccess)
+    rc = fail(VERS_ERR_HIP, std::string(who) + ": staging filter_of failed");
+  if (!rc && hipMemsetAsync(W->io_out.p, 0, io.out_bytes, W->io_stream) != hipSuccess) rc = fail(VERS_ERR_HIP, std::string(who) + ": hipMemsetAsync failed");  // entries past a query's count come back as zeros
+  if (!rc) {
+    const FilterMultiSpec ms{(uint64_t)words, n_filters, W->flt_of.as<uint32_t>()};
+    rc = probed ? filtered_dev_locked(h, io.q_dev, h->d, b, top_k, nprobe_or_metric, W->flt_bits.as<uint64_t>(), n_bits, io.ids_dev, io.dist_dev, io.cnt_dev, W->io_stream, &ms)
+                : exhaustive_filtered_dev_locked(h, io.q_dev, h->d, b, top_k, nprobe_or_metric, W->flt_bits.as<uint64_t>(), n_bits, io.ids_dev, io.dist_dev, io.cnt_dev,
+                                                 W->io_stream, &ms);
+  }
+  if (rc) {  // (the caller's bitmaps may still be read by the staging copies)
+    (void)hipStreamSynchronize(W->io_stream);
+    return rc;
+  }
+  rc = host_io_end(h, io, b, top_k, out_ids, out_dist, out_count);
+  return rc == kRetrySpill ? VERS_ERR_INVALID : rc;
+}
+
+int32_t vers_ivf_search_filtered_multi(vers_ivf_t* h, const float* queries, uint64_t q_stride_bytes, uint32_t b, uint32_t top_k, uint32_t nprobe,
+                                       const uint64_t* filters, uint64_t filter_stride_words, uint32_t n_filters, uint64_t n_bits, const uint32_t* filter_of,
+                                       uint64_t* out_ids, float* out_dist, uint32_t* out_count) {
+  return filtered_multi_host_common(h, "vers_ivf_search_filtered_multi", queries, q_stride_bytes, b, top_k, true, nprobe, filters, filter_stride_words, n_filters, n_bits,
+                                    filter_of, out_ids, out_dist, out_count);
+}
+
+int32_t vers_ivf_search_exhaustive_filtered_multi(vers_ivf_t* h, const float* queries, uint64_t q_stride_bytes, uint32_t b, uint32_t top_k, uint32_t metric,
+                                                  const uint64_t* filters, uint64_t filter_stride_words, uint32_t n_filters, uint64_t n_bits,
+                                                  const uint32_t* filter_of, uint64_t* out_ids, float* out_dist, uint32_t* out_count) {
+  return filtered_multi_host_common(h, "vers_ivf_search_exhaustive_filtered_multi", queries, q_stride_bytes, b, top_k, false, metric, filters, filter_stride_words,
+                                    n_filters, n_bits, filter_of, out_ids, out_dist, out_count);
 }
 
 int32_t vers_ivf_filter_stats(vers_ivf_t* h, uint64_t* out4, uint64_t* out4_total) {

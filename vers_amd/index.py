@@ -232,6 +232,56 @@ class IVFFlatIndex:
         check(lib().vers_ivf_search_exhaustive_filtered_dev(self._h, _vp(q_ptr), ldq, b, top_k, metric, _vp(bits_ptr) if bits_ptr else None, n_bits,
                                                             _vp(ids_ptr), _vp(dist_ptr), _vp(cnt_ptr), _vp(stream)))
 
+    # -- filtered search with a filter per query: query q of the batch uses bitmap filter_of[q] -----
+    @staticmethod
+    def _filters_words(filters, n_bits):
+        """filters -> (u64 [n_filters, stride] words, n_bits).  A sequence of bool arrays / id arrays (n_bits defaults to the largest any of
+        them needs) or a ready (words [n_filters, stride], n_bits) pair as capi.allowed_bitmaps packs it."""
+        if isinstance(filters, tuple):
+            words, nb = filters
+            words = np.ascontiguousarray(words, dtype=np.uint64)
+            return words.reshape(len(words), -1), int(nb)
+        arrs = [np.asarray(a) for a in filters]
+        if n_bits is None:
+            n_bits = max([a.size if a.dtype == np.bool_ else (int(a.max()) + 1 if a.size else 0) for a in arrs], default=0)
+        return capi.allowed_bitmaps(arrs, n_bits), int(n_bits)
+
+    def _filtered_multi(self, fn, queries, top_k, arg, filters, filter_of, n_bits):
+        q = np.ascontiguousarray(np.atleast_2d(queries), dtype=np.float32)
+        b = q.shape[0]
+        words, nb = self._filters_words(filters, n_bits)
+        fo = np.ascontiguousarray(np.broadcast_to(np.asarray(filter_of, dtype=np.uint32).reshape(-1), (b,)))
+        ids = np.zeros((b, max(top_k, 1)), dtype=np.uint64)
+        dist = np.zeros((b, max(top_k, 1)), dtype=np.float32)
+        cnt = np.zeros(b, dtype=np.uint32)
+        check(fn(self._h, _ptr(q), 4 * self.d, b, top_k, arg, _ptr(words), words.shape[1] if words.size else 0, words.shape[0], nb, _ptr(fo), _ptr(ids),
+                 _ptr(dist), _ptr(cnt)))
+        return ids[:, :top_k], dist[:, :top_k], cnt
+
+    def search_filtered_multi(self, queries, top_k: int, nprobe: int, filters, filter_of, n_bits=None):
+        """One batch whose queries use different filters (vers_ivf_search_filtered_multi; nprobe >= 1): row q is row q of
+        search_filtered(queries, top_k, nprobe, filters[filter_of[q]]), bit for bit.  At most capi.FILTER_MAX filters per call.
+        -> (ids [b, top_k] u64, dist [b, top_k] f32, count [b] u32); count may be 0."""
+        return self._filtered_multi(lib().vers_ivf_search_filtered_multi, queries, top_k, nprobe, filters, filter_of, n_bits)
+
+    def search_exhaustive_filtered_multi(self, queries, top_k: int, filters, filter_of, metric: int = capi.METRIC_L2SQ, n_bits=None):
+        """search_exhaustive_filtered with a filter per query (vers_ivf_search_exhaustive_filtered_multi)."""
+        return self._filtered_multi(lib().vers_ivf_search_exhaustive_filtered_multi, queries, top_k, metric, filters, filter_of, n_bits)
+
+    def search_filtered_multi_dev(self, q_ptr: int, ldq: int, b: int, top_k: int, nprobe: int, filters_ptr: int, stride_words: int, n_filters: int,
+                                  n_bits: int, filter_of_ptr: int, ids_ptr: int, dist_ptr: int, cnt_ptr: int, stream: int = 0):
+        """vers_ivf_search_filtered_multi_dev on raw device pointers (bitmaps and filter_of too); queued on `stream`, not synchronised: poll()
+        reports.  A filter_of entry at or beyond n_filters selects the empty filter."""
+        check(lib().vers_ivf_search_filtered_multi_dev(self._h, _vp(q_ptr), ldq, b, top_k, nprobe, _vp(filters_ptr) if filters_ptr else None, stride_words,
+                                                       n_filters, n_bits, _vp(filter_of_ptr) if filter_of_ptr else None, _vp(ids_ptr), _vp(dist_ptr),
+                                                       _vp(cnt_ptr), _vp(stream)))
+
+    def search_exhaustive_filtered_multi_dev(self, q_ptr: int, ldq: int, b: int, top_k: int, metric: int, filters_ptr: int, stride_words: int,
+                                             n_filters: int, n_bits: int, filter_of_ptr: int, ids_ptr: int, dist_ptr: int, cnt_ptr: int, stream: int = 0):
+        check(lib().vers_ivf_search_exhaustive_filtered_multi_dev(self._h, _vp(q_ptr), ldq, b, top_k, metric, _vp(filters_ptr) if filters_ptr else None,
+                                                                  stride_words, n_filters, n_bits, _vp(filter_of_ptr) if filter_of_ptr else None,
+                                                                  _vp(ids_ptr), _vp(dist_ptr), _vp(cnt_ptr), _vp(stream)))
+
     def filter_stats(self):
         """vers_ivf_filter_stats: of the most recent filtered call and over the handle's life -- 64-row tile visits the plan implied, tile
         visits actually loaded, work items skipped before their first load, allowed storage rows."""
