@@ -698,6 +698,15 @@ int32_t vers_ivf_range_search_exhaustive_sharded_dev(vers_ivf_t* h, const vers_c
  *   "pre_hot_single" (1) where tiles are abandoned early, the scan's blocks take the quads of the hot lists (some query's nearest:
  *                       the first of the work order) one at a time, so that thresholds are tight before the bulk is read; 0 = guided
  *                       runs of up to 8 quads from the first quad on.
+ *   "pre_head" (1)      an int8 copy of the first "pre_head_cols" (384; multiples of 64 in 256 .. 512, clipped to the row length - 64)
+ *                       columns of every stored row, built with the index (+ that many bytes per storage row; optional memory like the
+ *                       shadow) -- where tiles are abandoned early the list scan then runs as three launches: the hot lists, a filter
+ *                       that rules whole cold quads out from the int8 head (half the bytes of the fp16 prefix), the cold quads it left.
+ *                       Results are bit-identical.  Read when the index is built / uploaded / compacted (whether there is a head) and
+ *                       per search (whether it is used); add, add_batch and remove_batch invalidate the head until the next
+ *                       vers_ivf_compact (vers_ivf_head_state).  0 = no head, one launch.  "pre_head_backoff" (1): after a scan in which
+ *                       fewer than 1/8 of the quads the filter tested were ruled out (rows without cluster contrast) the handle's
+ *                       next 64 batches run as one launch, then the filter is tried again; 0 = never back off.
  *   "scan_events" (2)   HIP event records around list-scan launches (vers_ivf_last_scan / vers_ivf_scan_times): 1 always, 0 never,
  *                       2 for batches only (the two records cost a single-query call 5.5-6 us).
  *  A/B and forced paths (tests, measurements):
@@ -789,8 +798,15 @@ int32_t vers_ivf_prescan_stats(vers_ivf_t* h, uint64_t* out_batches, uint64_t* o
 /* Early abandon of the batched list scan (option "pre_prune"): 64-column steps whose math ran | steps of abandoned tiles that ran no
  * math (one of them per abandoned tile was still read: it was in flight) | tiles abandoned -- [3] of the most recent matrix-core
  * scan (zeros when it ran with the switch off or on a path the switch does not cover) and [3] summed over the handle's life.  Either
- * pointer may be NULL.  HBM bytes not read = (steps - tiles) x 8 KiB. */
+ * pointer may be NULL.  HBM bytes not read = (steps - tiles) x 8 KiB.  A tile the int8 head's filter ruled out (option "pre_head") counts
+ * as abandoned before its first step: all its steps without math, none of them in flight (vers_ivf_head_state has the filter's own
+ * counters and what it read instead). */
 int32_t vers_ivf_prune_stats(vers_ivf_t* h, uint64_t* out_last, uint64_t* out_total);
+/* The int8 head of the stored rows (option "pre_head"): whether the handle holds a VALID one (built by build / upload / compact;
+ * invalidated by add, add_batch, remove_batch), its bytes and its columns per row, and the filter's counters -- quads tested | quads
+ * ruled out | 64-column head steps (4 KiB each) read -- [3] of the most recent list scan (zeros when that scan was a single launch)
+ * and [3] over the handle's life.  Any pointer may be NULL. */
+int32_t vers_ivf_head_state(vers_ivf_t* h, int32_t* out_valid, uint64_t* out_bytes, uint32_t* out_cols, uint64_t* out_last, uint64_t* out_total);
 /* An fp16 shadow copy of the stored rows (+50 % corpus memory) feeds the matrix-core pre-selection of batched searches:
  * half the HBM bytes per list scan, a ~2x wider certificate window, the same exact f32 finish -- results stay
  * bit-identical.  On by default (VERS_SHADOW=0 or vers_set_option("shadow", 0) before build / upload: f32 rows feed the

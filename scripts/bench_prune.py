@@ -2,7 +2,8 @@
 index of ROWS x D rows in NLIST lists, NPROBE probes, one batch in flight.  DIST=c: the clustered generator of bench.py (16 modes per
 list: cluster contrast, most tiles of the lists that are nobody's nearest are abandoned); DIST=u: uniform rows and queries (no
 contrast: nothing is abandoned, the test must cost nothing).  Prints one JSON line: step and list-scan time, queries per second,
-the step counters of the last launch (vers_ivf_prune_stats; absent on a build without them) and the re-scanned queries.
+the step counters of the last launch (vers_ivf_prune_stats; absent on a build without them), the int8 head's state and filter
+counters (vers_ivf_head_state; option "pre_head" through VERS_OPTIONS) and the re-scanned queries.
 usage: [DIST=u] [ROWS=2000000] [D=768] [NLIST=1024] [BATCH=1024] [NPROBE=32] [STEPS=20] [PRUNE=0|1] python scripts/bench_prune.py"""
 import json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -37,5 +38,6 @@ ls = ix.last_scan()
 out = {"dist": dist, "rows": n, "d": d, "nlist": nlist, "batch": B, "nprobe": nprobe, "step_ms": round(dt * 1e3, 4),
        "list_scan_ms": round(float(np.mean(ix.scan_times())), 4), "queries_per_sec": round(B / dt, 1),
        "planned_gb": round(ls["streamed_rows"] * (2 * d + 4) / 1e9, 3), "rescanned_queries": int(ix.prescan_stats()["fallback_queries"]),
-       "prune_last": ix.prune_stats()["last"] if hasattr(ix, "prune_stats") else None}
+       "prune_last": ix.prune_stats()["last"] if hasattr(ix, "prune_stats") else None,
+       "head": ix.head_state() if hasattr(ix, "head_state") else None}
 print(json.dumps(out))

@@ -14,6 +14,7 @@
 #include "gemm.hip.h"
 #include "ivf_handle.hpp"
 #include "prescan.hip.h"
+#include "head_filter.hip.h"
 
 namespace vers {
 
@@ -564,6 +565,61 @@ int32_t poison_slack(vers_ivf* h, float value, hipStream_t st) {
   return VERS_OK;
 }
 
+// The int8 head of the whole index (head_filter.hip.h) from the rows as the shadow rounds them: the maximum over the head columns of the
+// stored rows -> the scale; the head; its measured residual.  H = option "pre_head_cols" (default 384) in multiples of 64, clipped to
+// ld - 64 (a boundary needs a step left to save); no head below 256 columns, on a sharded handle, for the cosine distance or without
+// the shadow.  Optional memory like the shadow: a failed allocation, or a non-finite maximum or residual, leaves head_valid false and
+// every search as it was.  Synchronises st (build, compact and the test hooks: never a search).
+int32_t build_head(vers_ivf* h, hipStream_t st) {
+  h->head_valid = false;
+  h->head_backoff = 0;
+  if (h->head_watch) *h->head_watch = 0;
+  uint32_t H = (uint32_t)std::max<int64_t>(0, std::min<int64_t>(opt_get("pre_head_cols", 384), kHeadMaxCols)) / 64u * 64u;
+  if (h->ld >= 64u) H = std::min<uint32_t>(H, (h->ld - 64u) / 64u * 64u);
+  else H = 0;
+  const bool want = opt_get("pre_head", kPreHeadDefault) != 0 && H >= kHeadMinCols && h->world == 1 && h->metric == 0 && shadow_mode() != 0 && h->shadow_valid &&
+                    h->pre_misc.p != nullptr && h->cap_rows != 0;
+  if (!want) {
+    h->rows_h8.release();
+    h->head_cols = 0;
+    return VERS_OK;
+  }
+  if (!h->head_ctr.p) {
+    if (int32_t rc = h->head_ctr.reserve(64)) return rc;
+    VERS_HIP_TRY(hipMemset(h->head_ctr.p, 0, 64));
+  }
+  if (!h->head_watch) {
+    VERS_HIP_TRY(hipHostMalloc((void**)&h->head_watch, 64, hipHostMallocDefault));
+    *h->head_watch = 0;
+  }
+  const size_t need = (size_t)h->cap_rows * H;
+  if (need > h->rows_h8.cap) {
+    h->rows_h8.release();
+    size_t free_b = 0, total_b = 0;
+    (void)hipMemGetInfo(&free_b, &total_b);
+    void* ph = nullptr;
+    if (need + (size_t(4) << 30) <= free_b && hipMalloc(&ph, need) == hipSuccess) { h->rows_h8.p = ph; h->rows_h8.cap = need; dev_mem_account((int64_t)need); }
+    else (void)hipGetLastError();
+  }
+  h->head_cols = H;
+  if (h->rows_h8.p == nullptr) return VERS_OK;
+  uint32_t* misc = h->pre_misc.as<uint32_t>();
+  VERS_HIP_TRY(hipMemsetAsync(misc + kHeadMiscMax, 0, 2 * sizeof(uint32_t), st));
+  const unsigned row_blocks = (unsigned)((h->cap_rows + 255) / 256);
+  hipLaunchKernelGGL(head_max_kernel, dim3(row_blocks), dim3(256), 0, st, (const float*)h->rows.as<float>(), h->ld, (const uint32_t*)h->row_ids.as<uint32_t>(),
+                     h->cap_rows, H, misc + kHeadMiscMax);
+  hipLaunchKernelGGL(head_write_kernel, dim3((unsigned)((h->cap_rows * (H / 16u) + 255) / 256)), dim3(256), 0, st, (const float*)h->rows.as<float>(), h->ld,
+                     (const uint32_t*)h->row_ids.as<uint32_t>(), h->cap_rows, H, (const uint32_t*)(misc + kHeadMiscMax), h->rows_h8.as<int8_t>());
+  hipLaunchKernelGGL(head_resid_kernel, dim3(row_blocks), dim3(256), 0, st, (const float*)h->rows.as<float>(), h->ld, (const uint32_t*)h->row_ids.as<uint32_t>(),
+                     h->cap_rows, H, (const uint32_t*)(misc + kHeadMiscMax), misc + kHeadMiscRh2);
+  VERS_HIP_TRY(hipGetLastError());
+  float mr[2] = {0.0f, 0.0f};
+  VERS_HIP_TRY(hipMemcpyAsync(mr, misc + kHeadMiscMax, sizeof(mr), hipMemcpyDeviceToHost, st));
+  VERS_HIP_TRY(hipStreamSynchronize(st));
+  h->head_valid = std::isfinite(mr[0]) && std::isfinite(mr[1]) && std::isfinite(head_scale(mr[0]));
+  return VERS_OK;
+}
+
 // |x|^2 of storage rows [r_begin, r_end) for the matrix-core list scan; a full refresh also resets the maximum
 int32_t refresh_norms(vers_ivf* h, uint64_t r_begin, uint64_t r_end, hipStream_t st) {
   if (int32_t rc = h->pre_misc.reserve(64)) return rc;
@@ -582,6 +638,7 @@ int32_t refresh_norms(vers_ivf* h, uint64_t r_begin, uint64_t r_end, hipStream_t
   // vers_set_option("shadow", 0) at build / upload time.
   const bool shadow = shadow_mode() != 0;
   if (full) h->shadow_valid = false;
+  h->head_valid = false;  // rows change: a full refresh builds the int8 head again (below), a partial one leaves it invalid
   if (shadow) {
     if (full) {
       const size_t need = (h->cap_rows ? h->cap_rows : 1) * (size_t)h->ld * sizeof(uint16_t);
@@ -637,6 +694,7 @@ int32_t refresh_norms(vers_ivf* h, uint64_t r_begin, uint64_t r_end, hipStream_t
                        h->row_ids.as<uint32_t>(), r_begin, r_end, h->xnorm.as<float>(), h->pre_misc.as<uint32_t>());
     VERS_HIP_TRY(hipGetLastError());
   }
+  if (full) return build_head(h, st);
   return VERS_OK;
 }
 
@@ -1618,6 +1676,7 @@ static void ab_count(int slot, double v, double* acc = g_ab) {
 // |x|^2 (+ maximum), fp16 shadow (+ residual maximum) and row-major copy of the listed tiles: refresh_norms for a tile list, one launch per array
 static int32_t refresh_tiles(vers_ivf* h, const uint32_t* tiles, uint32_t nt, hipStream_t st) {
   if (nt == 0) return VERS_OK;
+  h->head_valid = false;  // the int8 head does not follow tile lists: the list scan is one launch again until a compact or a full refresh
   const uint64_t n_rows = (uint64_t)nt * 64;
   if (shadow_mode() != 0) {
     if (h->shadow_valid) {
@@ -2047,7 +2106,9 @@ int32_t compact_locked(vers_ivf* h, uint64_t* out_before, uint64_t* out_after) {
     if (int32_t rc = scan_prepare_launch(compact_tiles_kernel, lds)) return rc;
     // the old shadow and row-major copy go first: they are derived, the new ones take their room
     h->shadow_valid = false;
+    h->head_valid = false;
     h->rows_bf.release();
+    h->rows_h8.release();
     h->rows_rm.release();
     const size_t rows_b = (size_t)(total ? total : 1) * ld * sizeof(float), ids_b = (size_t)(total ? total : 1) * sizeof(uint32_t);
     if (nrows.reserve(rows_b) != VERS_OK || nids.reserve(ids_b) != VERS_OK) {
@@ -2134,6 +2195,8 @@ int32_t compact_locked(vers_ivf* h, uint64_t* out_before, uint64_t* out_after) {
     reserve_derived(h, total, h->rows_bf, h->rows_rm, &fits);  // (what finds no room even now is optional memory: refresh_norms goes without)
     if (int32_t rc = refresh_norms(h, 0, h->cap_rows, st)) return rc;
     if (int32_t rc = clk.done()) return rc;
+  } else {
+    if (int32_t rc = build_head(h, st)) return rc;  // (the fused pass wrote every other derived array; the head is derived from the new tiles here)
   }
   VERS_HIP_TRY(hipDeviceSynchronize());
   if (out_before) *out_before = before;

@@ -158,6 +158,7 @@ int32_t vers_ivf_destroy(vers_ivf_t* h) {
   (void)hipDeviceSynchronize();
   for (auto& w : h->pool) ws_destroy(*w);
   if (h->fail_watch) (void)hipHostFree(h->fail_watch);
+  if (h->head_watch) (void)hipHostFree(h->head_watch);
   if (h->st_pin) (void)hipHostFree(h->st_pin);
   h->up.close();
   h->ab.free_pin();

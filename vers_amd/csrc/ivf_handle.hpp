@@ -104,6 +104,8 @@ struct SearchWs {
   GroupTotals last_tot{};
   DevBuf prune_tab;                      // [b][ld / 64] early-abandon table of the batch (prescan.hip.h, prune_table_kernel)
   const uint32_t* prune_last = nullptr;  // device: the last matrix-core scan's step counters (nullptr: it ran with the early abandon off)
+  DevBuf head_q8, head_q;                // the batch's int8 query rows [b][H] and { head_extra, s_n } [b][2] (prune_table_kernel; head_filter.hip.h)
+  const uint32_t* head_last = nullptr;   // device: the last split scan's filter counters (nullptr: the scan was one launch)
   const GroupTotals* tot_dev = nullptr;  // device totals of the last planned search
   bool tot_valid = false;
   // lease bookkeeping
@@ -232,6 +234,19 @@ struct vers_ivf {
   // of the f32 rows (81 GB instead of 49 GB of 288 at N = 10M d = 768); a failed allocation or rows beyond the quarter
   // (N > 23M at d = 768) leave the tile gather in charge.  Same bits either way (tests run both).
   DevBuf rows_rm;
+  // int8 head of the stored rows (head_filter.hip.h): the first head_cols columns of every storage row, one scale for the whole index, in
+  // the shadow's 64-row tiles.  Derived from the rows like the shadow and optional like it (head_cols bytes per storage row); built on a
+  // full refresh_norms and by vers_ivf_compact, INVALIDATED by every other writer of the rows (add, add_batch, remove_batch): the list
+  // scan is then the single launch it was.  pre_misc [4] = max |x~| over the head columns, [5] = Rh2 (prescan.hip.h: kHeadMisc*).
+  DevBuf rows_h8;
+  uint32_t head_cols = 0;
+  bool head_valid = false;  // (written under the exclusive lock, like shadow_valid)
+  DevBuf head_ctr;          // u64 [3] quads tested | quads dead | head steps read by head_filter_kernel, over the handle's life
+  // BACK-OFF: on rows without cluster contrast the filter rules nothing out and the two extra launch boundaries are pure cost.  The
+  // filter's last block writes 1 to the pinned word when fewer than 1/8 of the quads it tested died; the next search that sees it
+  // clears it and the handle's scans stay single launches for the next kHeadBackoff batches, then try again.
+  uint32_t* head_watch = nullptr;
+  std::atomic<uint32_t> head_backoff{0};
   std::atomic<bool> shadow_off{false};
   bool shadow_valid = false;            // rows_bf mirrors every stored row of the CURRENT index (written under the exclusive lock)
   uint32_t* fail_watch = nullptr;       // pinned: cumulative certificate failures as of the last finished batch
@@ -521,6 +536,7 @@ int32_t upload_queries(const float* queries, uint64_t stride_bytes, uint32_t b, 
 
 // ---- ivf_build.hip -----------------------------------------------------------------------------------------------------
 int32_t refresh_norms(vers_ivf* h, uint64_t r_begin, uint64_t r_end, hipStream_t st);
+int32_t build_head(vers_ivf* h, hipStream_t st);  // the int8 head of the whole index from its rows (synchronises st); leaves head_valid
 int32_t poison_slack(vers_ivf* h, float value, hipStream_t st);  // test hook / option "poison_slack_bits": rows that hold no vector <- value
 
 }  // namespace ivf

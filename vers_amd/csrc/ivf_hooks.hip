@@ -126,6 +126,30 @@ int32_t vers_ivf_prune_stats(vers_ivf_t* h, uint64_t* out_last /* [3] */, uint64
   return VERS_OK;
 }
 
+int32_t vers_ivf_head_state(vers_ivf_t* h, int32_t* out_valid, uint64_t* out_bytes, uint32_t* out_cols, uint64_t* out_last /* [3] */, uint64_t* out_total /* [3] */) {
+  if (!h) return fail(VERS_ERR_INVALID, "null handle");
+  DeviceGuard g(h->device);
+  unsigned long long tot[3] = {0, 0, 0};
+  uint32_t last[3] = {0, 0, 0};
+  {
+    UseLastWs use_ws(h);
+    if (use_ws.ok && W->head_last != nullptr) {
+      if (W->used && W->done) VERS_HIP_TRY(hipEventSynchronize(W->done));
+      VERS_HIP_TRY(hipMemcpy(last, W->head_last, sizeof(last), hipMemcpyDeviceToHost));
+    }
+  }
+  if (h->head_ctr.p) VERS_HIP_TRY(hipMemcpy(tot, h->head_ctr.p, sizeof(tot), hipMemcpyDeviceToHost));
+  const bool valid = h->head_valid && h->rows_h8.p != nullptr;
+  if (out_valid) *out_valid = valid ? 1 : 0;
+  if (out_bytes) *out_bytes = h->rows_h8.p ? (uint64_t)h->cap_rows * h->head_cols : 0;
+  if (out_cols) *out_cols = h->head_cols;
+  for (int i = 0; i < 3; ++i) {
+    if (out_last) out_last[i] = last[i];
+    if (out_total) out_total[i] = tot[i];
+  }
+  return VERS_OK;
+}
+
 int32_t vers_ivf_scan_times(vers_ivf_t* h, float* out_ms, uint32_t cap, uint32_t* out_n, int32_t reset) {
   if (!h || !out_n || (cap && !out_ms)) return fail(VERS_ERR_INVALID, "bad arguments");
   DeviceGuard g(h->device);

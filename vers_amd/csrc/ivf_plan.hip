@@ -753,9 +753,12 @@ int32_t plan_search(vers_ivf* h, const float* q_dev, uint64_t ldq_in, uint32_t b
   // pj: list, pref, take per (q, j); np per q.   lists: cnt, fill | pair_off, group_off, item_off | totals
   if (int32_t rc = W->pj.reserve((4 * n_pj + b) * sizeof(uint32_t))) return rc;
   // one zero-initialised zone per batch (ONE memset): cnt, fill, hot per list | quad hand-out counter | queue of
-  // uncertified queries + its count | non-finite flags per (query, probe)
-  const size_t zero_words = 3 * (size_t)k_l + 4 + (use_pre ? (size_t)b + 4 + n_pj : 0);
+  // uncertified queries + its count | non-finite flags per (query, probe).  The counter's twelve words: hand-out | the early abandon's
+  // three step counters | the cold launch's hand-out of a split scan | the head filter's three counters | its count of finished
+  // blocks | three spare (ivf_search.hip: launch_prescan)
+  const size_t zero_words = 3 * (size_t)k_l + 12 + (use_pre ? (size_t)b + 4 + n_pj : 0);
   W->prune_last = nullptr;  // (points into the zone below: set again by the scan that counts into it)
+  W->head_last = nullptr;
   if (int32_t rc = W->lists.reserve((zero_words + 3 * (size_t)k_l) * sizeof(uint32_t) + sizeof(GroupTotals) + 64)) return rc;
   if (int32_t rc = W->pairs.reserve(n_pj * sizeof(uint32_t))) return rc;
   if (int32_t rc = W->items.reserve(one1 ? (items_bound + 4) * sizeof(Item1Rec) : std::max<uint64_t>(1, items_bound) * sizeof(ItemDesc))) return rc;
@@ -774,7 +777,7 @@ int32_t plan_search(vers_ivf* h, const float* q_dev, uint64_t ldq_in, uint32_t b
   uint32_t* fill = cnt + k_l;
   uint32_t* hot = fill + k_l;  // lists that are the nearest list of some query: scanned first
   uint32_t* quad_ctr = hot + k_l;
-  uint32_t* fail_list = quad_ctr + 4;            // (matrix-core scan only)
+  uint32_t* fail_list = quad_ctr + 12;            // (matrix-core scan only)
   uint32_t* qflags = fail_list + b + 4;
   uint32_t* pair_off = cnt + zero_words;
   uint32_t* group_off = pair_off + k_l;

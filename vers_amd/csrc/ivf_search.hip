@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "finish.hip.h"
+#include "head_filter.hip.h"
 #include "flat_shadow.hpp"
 #include "ivf_src.hip.h"
 #include "single.hip.h"
@@ -284,10 +285,31 @@ int32_t launch_prescan(vers_ivf* h, const IvfSrc<NQ>& src, uint32_t items_bound,
                      prescan_lds_bytes_g(h->ld, kp, NQ, true, true) <= 160u * 1024u;
   p.prune_tab = nullptr; p.prune_first = 0; p.prune_until = 0; p.prune_om = 0.0f; p.prune_last = nullptr; p.prune_tot = nullptr; p.hot_single = 0u;
   W->prune_last = nullptr;
+  W->head_last = nullptr;
+  // The int8 head (head_filter.hip.h): where tiles are abandoned early and the handle holds a valid head, the scan is THREE launches -- the
+  // hot quads, the head's filter over the cold ones, the cold quads the filter left.  option "pre_head" = 0, an invalid head, candidate
+  // lists of more than one key per lane or a hand-out switched off for diagnosis: one launch, as ever.
+  const uint32_t H = h->head_cols;
+  bool head_rest = false;  // the back-off (vers_ivf::head_watch): this batch sits the split out
+  if (h->head_watch != nullptr && opt_get("pre_head_backoff", 1) != 0) {
+    if (*(volatile uint32_t*)h->head_watch != 0u) {
+      *(volatile uint32_t*)h->head_watch = 0u;
+      h->head_backoff.store(kHeadBackoff, std::memory_order_relaxed);
+    }
+    uint32_t left = h->head_backoff.load(std::memory_order_relaxed);
+    while (left != 0u && !h->head_backoff.compare_exchange_weak(left, left - 1u, std::memory_order_relaxed)) {}
+    head_rest = left != 0u;
+  }
+  const bool split = prune && !head_rest && opt_get("pre_head", kPreHeadDefault) != 0 && h->head_valid && h->rows_h8.p != nullptr && H >= kHeadMinCols && H <= kHeadMaxCols && H + 64u <= h->ld &&
+                     kp <= kPreMaxKp && !(p.debug & 32u) && h->head_ctr.p != nullptr && h->head_watch != nullptr && opt_get("pre_hot_single", 1) != 0;
   if (prune) {
     if (int32_t rc = W->prune_tab.reserve((size_t)b * n_steps * sizeof(float))) return rc;
+    if (split) {
+      if (int32_t rc = W->head_q8.reserve((size_t)b * H)) return rc;
+      if (int32_t rc = W->head_q.reserve((size_t)b * 2 * sizeof(float))) return rc;
+    }
     hipLaunchKernelGGL(prune_table_kernel, dim3((b + 3) / 4), dim3(256), 0, st, src.qp, src.ldq, h->ld, b, (const uint32_t*)h->pre_misc.as<uint32_t>(),
-                       W->prune_tab.as<float>());
+                       W->prune_tab.as<float>(), split ? H : 0u, split ? W->head_q8.as<int8_t>() : (int8_t*)nullptr, split ? W->head_q.as<float>() : (float*)nullptr);
     VERS_HIP_TRY(hipGetLastError());
     p.prune_tab = W->prune_tab.as<float>();
     p.prune_first = (uint32_t)std::max<int64_t>(1, std::min<int64_t>(opt_get("pre_prune_first", 2), n_steps));
@@ -320,7 +342,31 @@ int32_t launch_prescan(vers_ivf* h, const IvfSrc<NQ>& src, uint32_t items_bound,
   const uint32_t per_cu = std::max<uint32_t>(1, std::min<uint32_t>(2, (uint32_t)((160u * 1024u) / lds)));  // 1 at d = 768 (measured: as fast as 2)
   const uint32_t reserve = scan_reserve(h, st);  // (vers_set_option "scan_reserve_cus"; auto: only while another batch is in flight)
   const uint32_t blocks = std::max<uint32_t>(1u, std::min<uint32_t>((items_bound + kWavesPerBlock - 1) / kWavesPerBlock, ((uint32_t)h->n_cu - reserve) * per_cu));
-  return launch_scan_timed(kern, blocks, kPreWavesG, lds, st, src, p);
+  if (!split) return launch_scan_timed(kern, blocks, kPreWavesG, lds, st, src, p);
+  // the split scan: one bracket of the timing ring around all three launches (vers_ivf_scan_times keeps meaning "the list scan")
+  HeadParams hp;
+  hp.rows_h8 = h->rows_h8.as<int8_t>(); hp.q8 = W->head_q8.as<int8_t>(); hp.qhead = W->head_q.as<float>(); hp.prune_tab = p.prune_tab; hp.xnorm = p.xnorm;
+  hp.bounds32 = p.bounds32; hp.misc = h->pre_misc.as<uint32_t>(); hp.H = H; hp.n_steps = n_steps; hp.kp = kp; hp.om = p.prune_om;
+  hp.last = quad_ctr + 5;  // (zeroed with the hand-out counters)
+  hp.tot = h->head_ctr.as<unsigned long long>();
+  hp.done = quad_ctr + 8;
+  hp.prune_last = p.prune_last; hp.prune_tot = p.prune_tot;
+  hp.watch = h->head_watch;
+  W->head_last = quad_ctr + 5;
+  if (int32_t rc = scan_prepare_launch(kern, lds)) return rc;
+  return timed_scan(st, [&]() -> int32_t {
+    PreParams ph = p, pc = p;
+    ph.hot_single = kPreHotOnly;
+    pc.hot_single = kPreColdOnly;
+    pc.next_quad = quad_ctr + 4;  // the cold launch's own counter: starts at zero, counts from the first cold quad
+    hipLaunchKernelGGL(kern, dim3(blocks), dim3(kWave * kPreWavesG), lds, st, src, ph);
+    // a block per cold quad, striding; how many there are is on the device (GroupTotals): the grid is what the CUs hold at once
+    const uint32_t fblocks = std::max<uint32_t>(1u, std::min<uint32_t>((items_bound + 3u) / 4u, ((uint32_t)h->n_cu - reserve) * 2u));  // (two blocks per compute unit: the kernel is compiled for two waves per SIMD)
+    hipLaunchKernelGGL((head_filter_kernel<NQ, IvfSrc<NQ>>), dim3(fblocks), dim3(kWave * kHeadWaves), 0, st, src, hp);
+    hipLaunchKernelGGL(kern, dim3(blocks), dim3(kWave * kPreWavesG), lds, st, src, pc);
+    VERS_HIP_TRY(hipGetLastError());
+    return VERS_OK;
+  });
 }
 
 // The ordered-chain passes of a planned search: 64 result ranks per pass (one pass for top_k <= 64) -- the previous pass's slots and pruning

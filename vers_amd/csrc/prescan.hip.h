@@ -54,9 +54,17 @@ constexpr uint32_t kPreMaxKp = 64;  // widest list: one sorted key per lane
 constexpr uint32_t kPreMinSlack = 16;
 constexpr uint32_t kPreMaxP = 1024;  // most probed lists per query on the matrix-core scan (tables and slots grow with b x nprobe)
 
+// hot_single of a SPLIT scan (ivf_search.hip: launch_prescan; the int8 head's filter, head_filter.hip.h, runs between the two launches)
+constexpr uint32_t kPreHotOnly = 2u;   // the quads of the hot lists alone, singly
+constexpr uint32_t kPreColdOnly = 3u;  // the quads behind them, guided; next_quad is a counter of this launch's own
+// bit of ItemDesc::group in a quad's FIRST item: head_filter_kernel ruled the quad out, the cold launch skips it.  (Nothing behind the
+// scan reads the item descriptors: the exact finish and the fallback go by pairs and lists.)
+constexpr uint32_t kQuadDead = 0x80000000u;
+constexpr int64_t kPreHeadDefault = 1;  // option "pre_head": the head is built (at build / upload / compact time) and used (per search) unless it says 0
+
 struct PreParams {
   uint32_t ld, n_chunks, kp;
-  uint32_t hot_single;  // != 0: the quads of the hot lists are handed out singly (pre_run_len below; Src::hot_items() says how many there are)
+  uint32_t hot_single;  // != 0: the quads of the hot lists are handed out singly (pre_run_len below; Src::hot_items() says how many there are); 2, 3: see above
   uint32_t* status;
   uint32_t* bounds32;   // per merge group: order bits of the smallest known kp-th val (0xFFFFFFFF = none yet)
   uint32_t* qflags;     // per merge group: != 0 -> a non-finite val was seen, the query must be re-done exactly
@@ -761,26 +769,38 @@ __global__ __launch_bounds__(kWave * kPreWavesG) __attribute__((amdgpu_waves_per
   };
   const uint32_t n_res = gridDim.x;
   for (uint32_t b0 = blockIdx.x;; b0 += gridDim.x) {
-    uint32_t start = b0, count = 1;
+    uint32_t start = b0, count = 1, lim = n_quads;
     if (p.next_quad != nullptr) {
       if (threadIdx.x == 0) {
         // (the hot count is read here, next to the counter -- two independent loads --, not kept in a register for the whole launch;
         // only the instantiations that abandon tiles are ever launched with the switch set)
-        uint32_t hot_quads = 0u;
-        if constexpr (PR)
+        // hot_single also names the REGION of a split scan (kPreHotOnly / kPreColdOnly: the int8 head's filter runs between the two
+        // launches): the hot quads alone, singly; or the quads behind them, guided, through a counter that starts at zero
+        uint32_t hot_quads = 0u, base = 0u, upto = n_quads;
+        if constexpr (PR) {
           if (p.hot_single != 0u) hot_quads = src.hot_items() / 4u;
-        const uint32_t seen = __hip_atomic_load(p.next_quad, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const uint32_t r = pre_run_len(seen, n_quads, hot_quads, n_res);
-        nq_lds[0] = atomicAdd(p.next_quad, r);
+          if (p.hot_single == kPreHotOnly) upto = hot_quads < n_quads ? hot_quads : n_quads;
+          if (p.hot_single == kPreColdOnly) { base = hot_quads < n_quads ? hot_quads : n_quads; hot_quads = 0u; }
+        }
+        const uint32_t seen = base + __hip_atomic_load(p.next_quad, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const uint32_t r = pre_run_len(seen, upto, hot_quads, n_res);
+        nq_lds[0] = base + atomicAdd(p.next_quad, r);
         nq_lds[1] = r;
+        if constexpr (PR) nq_lds[2] = upto;
       }
       __syncthreads();
       start = nq_lds[0]; count = nq_lds[1];
+      if constexpr (PR) lim = (uint32_t)__builtin_amdgcn_readfirstlane((int)nq_lds[2]);
     }
-    if (start >= n_quads) break;
-    const uint32_t end = start + count < n_quads ? start + count : n_quads;
+    if (start >= lim) break;
+    const uint32_t end = start + count < lim ? start + count : lim;
     for (uint32_t bi = start; bi < end; ++bi) {
     const ItemDesc d0 = src.items[4 * bi];
+    if constexpr (PR)
+      if (d0.group & kQuadDead) {  // (block-uniform) the head filter ruled every tile of the quad out and filled its partial slots; a skipped quad also ends a run (`cont` below)
+        __syncthreads();  // (a block that skips a whole run meets no other barrier before thread 0 rewrites the hand-out words)
+        continue;
+      }
     // (block-uniform.  Only the quad right behind the run's last one: the slots written empty must be this block's own)
     const bool cont = run_first != 0xFFFFFFFFu && bi == run_last + 1 && d0.list == cur_list && d0.group == cur_group;
     const uint32_t it = bi * 4 + (wid & 3);
@@ -1018,12 +1038,59 @@ __host__ __device__ inline uint32_t pre_run_len(uint32_t seen, uint32_t n_quads,
   const uint32_t r = seen < n_quads ? (n_quads - seen) / (2u * n_blocks) : 1u;
   return r < 1u ? 1u : (r > kPreMaxRun ? kPreMaxRun : r);
 }
+
+// ---- the int8 head: ruling a cold tile out from an int8 copy of its first H columns (head_filter.hip.h) -----------------------------
+// P = the head columns consumed so far, S the rest.  The head stores X_j = head_quant(x~_j, s_x), x~ the fp16 shadow value and s_x ONE
+// scale for the whole index; the query's image is Q_j = head_quant(q'_j, s_n), q' = fp16(-2 q) as stage() rounds it, s_n per query.
+// With a = s_x X, delta = x~_P - a, b = s_n Q, eps = q'_P - b:
+//     <x~_P, q'_P> = <a, b> + <a, eps> + <delta, q'_P> >= s_x s_n I - |a| |eps| - Rh |q'_P|,      I = sum_P X_j Q_j (exact in i32)
+// with Rh >= |delta| the MEASURED residual of the head over the stored rows (whole head: a prefix's is no larger) and
+// |a| <= |x~_P| + Rh <= sqrt(xmax2) + R + Rh; and |x~_P| >= |a| - Rh gives |x~_P|^2 >= (s_x sqrt(sum_P X^2) - Rh)_+^2.  Put into prune_lower's
+// inequality (above) in place of acc_P and m_p, with the minima over a tile's live rows, the val the scan would complete for any of them is
+// at least
+//     s_x s_n I_min + (s_x sqrt(N_min) - Rh)_+^2 (1 - eps_f) - [ tail(c) + head_extra ]
+// head_extra = Rh |q'_H| + (sqrt(xmax2) + R + Rh) |eps_H| over the WHOLE head (>= any prefix's), per query, rounded up.  The test runs in
+// f64: its own roundings (2^-53 relative) are taken by the 1e-12 factors.  Every comparison is false on a NaN.
+__host__ __device__ inline float head_scale(float max_abs) { return max_abs / 127.0f; }
+__host__ __device__ inline int32_t head_quant(float v, float s) {  // clamp(rint(v / s), -127, 127); 0 without a usable scale or value
+  if (!(s > 0.0f) || !(s < __builtin_inff())) return 0;
+  float t = __builtin_rintf(v / s);
+  t = t < -127.0f ? -127.0f : t;
+  t = t > 127.0f ? 127.0f : t;
+  return t == t ? (int32_t)t : 0;
+}
+// what the quantised element leaves behind (f64: the product is exact, the difference rounds at 2^-53)
+__host__ __device__ inline double head_resid(float v, float s, int32_t X) { return (double)v - (double)s * (double)X; }
+// qP2 = |q'_H|^2, eps2 = |eps_H|^2 (f64 sums), Rh2 = the head's measured squared residual (an f32, rounded up where it was summed)
+__host__ __device__ inline float head_extra(double qP2, double eps2, double xmax2, double R2, double Rh2) {
+  const double Rh = __builtin_sqrt(Rh2 * 1.01), R = __builtin_sqrt(R2 * 1.01), xm = __builtin_sqrt(xmax2);
+  return prune_round_up(1.01 * (Rh * __builtin_sqrt(qP2) + (xm + R + Rh) * __builtin_sqrt(eps2)));
+}
+// bracket = tail(c) + head_extra, rounded up.  head_lower = head_lower_dot on top of head_norm_term: the kernel evaluates the norm's term
+// once per boundary and the rest once per query set.
+__host__ __device__ inline double head_norm_term(uint32_t N_min, float s_x, double Rh2, double om_eps) {  // (s_x sqrt(N_min) - Rh)_+^2 (1 - eps_f), rounded down
+  if (!(__builtin_fabsf(s_x) < __builtin_inff()) || !(Rh2 >= 0.0)) return __builtin_nan("");
+  double t = (double)s_x * __builtin_sqrt((double)N_min) * (1.0 - 1e-12) - __builtin_sqrt(Rh2 * 1.01);
+  t = t > 0.0 ? t : 0.0;
+  return t * t * om_eps * (1.0 - 1e-12);
+}
+__host__ __device__ inline double head_lower_dot(int32_t I_min, double norm_term, float s_x, float s_n, float bracket) {
+  if (!(__builtin_fabsf(s_x) < __builtin_inff()) || !(__builtin_fabsf(s_n) < __builtin_inff())) return __builtin_nan("");
+  const double dot = (double)s_x * (double)s_n * (double)I_min;
+  return (dot - __builtin_fabs(dot) * 1e-12) + norm_term - (double)bracket * (1.0 + 1e-12);
+}
+__host__ __device__ inline double head_lower(int32_t I_min, uint32_t N_min, float s_x, float s_n, double Rh2, double om_eps, float bracket) {
+  return head_lower_dot(I_min, head_norm_term(N_min, s_x, Rh2, om_eps), s_x, s_n, bracket);
+}
 // --------------------------------------------------------------------------------------------------------------------------------------
 
 // The table of a batch: a wave per query.  tab[q][c], c = 1 .. ld / 64 - 1 (entry 0 is never read): prune_tail_entry of the columns
 // from 64 c on.  h_j = -fp16(-2 q_j) / 2 exactly as stage() rounds the operand.  At most 128 steps (d <= 8192).
 constexpr uint32_t kPruneMaxSteps = 128;
-static __global__ __launch_bounds__(256) void prune_table_kernel(const float* qp, uint32_t ldq, uint32_t ld, uint32_t b, const uint32_t* misc, float* tab) {
+// The int8 head's part (H != 0; head_filter.hip.h): the query's int8 row q8[q][H] and qhead[q] = { head_extra, s_n }.
+constexpr uint32_t kHeadMiscMax = 4, kHeadMiscRh2 = 5;  // words of pre_misc: max |x~| over the head columns of the stored rows | Rh2 (f32 bits)
+static __global__ __launch_bounds__(256) void prune_table_kernel(const float* qp, uint32_t ldq, uint32_t ld, uint32_t b, const uint32_t* misc, float* tab,
+                                                                 uint32_t H = 0, int8_t* q8 = nullptr, float* qhead = nullptr) {
   const uint32_t q = blockIdx.x * 4u + (threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
   if (q >= b) return;  // (whole waves)
@@ -1052,6 +1119,35 @@ static __global__ __launch_bounds__(256) void prune_table_kernel(const float* qp
   const double xmax2 = (double)__uint_as_float(misc[0]), R2 = (double)__uint_as_float(misc[2]);
   if ((uint32_t)lane < nch) tab[(uint64_t)q * nch + lane] = prune_tail_entry(suf0, (double)qn, xmax2, R2, (double)rq, ld);
   if ((uint32_t)lane + 64u < nch) tab[(uint64_t)q * nch + lane + 64u] = prune_tail_entry(suf1, (double)qn, xmax2, R2, (double)rq, ld);
+  if (H != 0u) {  // (kernel-uniform)
+    const uint32_t hs = H / 64u;
+    float hmax = 0.0f;
+    for (uint32_t s = 0; s < hs; ++s) {
+      const float a = __builtin_fabsf((float)(_Float16)(-2.0f * qrow[s * 64u + (uint32_t)lane]));
+      hmax = a > hmax ? a : hmax;  // (a NaN is skipped here and caught by its residual below)
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+      const float o = __shfl_xor(hmax, off, kWave);
+      hmax = o > hmax ? o : hmax;
+    }
+    const float sn = head_scale(hmax);
+    double e2 = 0.0, p2 = 0.0;
+    for (uint32_t s = 0; s < hs; ++s) {
+      const float hi = (float)(_Float16)(-2.0f * qrow[s * 64u + (uint32_t)lane]);
+      const int32_t Q = head_quant(hi, sn);
+      const double e = head_resid(hi, sn, Q);
+      e2 += e * e;
+      p2 += (double)hi * (double)hi;
+      q8[(uint64_t)q * H + s * 64u + (uint32_t)lane] = (int8_t)Q;
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) { e2 += __shfl_xor(e2, off, kWave); p2 += __shfl_xor(p2, off, kWave); }
+    if (lane == 0) {
+      qhead[2u * q] = head_extra(p2, e2, xmax2, R2, (double)__uint_as_float(misc[kHeadMiscRh2]));
+      qhead[2u * q + 1u] = sn;
+    }
+  }
 }
 
 }  // namespace vers

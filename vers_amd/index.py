@@ -452,6 +452,16 @@ class IVFFlatIndex:
         keys = ("steps_executed", "steps_skipped", "tiles_abandoned")
         return dict(last=dict(zip(keys, (int(v) for v in last))), total=dict(zip(keys, (int(v) for v in tot))))
 
+    def head_state(self):
+        """The int8 head of the stored rows (option "pre_head"): valid, bytes, columns per row, and the filter's counters of the last
+        list scan and over the handle's life."""
+        v = C.c_int32(0); nb = C.c_uint64(0); cols = C.c_uint32(0)
+        last = (C.c_uint64 * 3)(); tot = (C.c_uint64 * 3)()
+        check(lib().vers_ivf_head_state(self._h, C.byref(v), C.byref(nb), C.byref(cols), last, tot))
+        keys = ("quads_tested", "quads_dead", "head_steps")
+        return dict(valid=bool(v.value), bytes=int(nb.value), cols=int(cols.value), last=dict(zip(keys, (int(x) for x in last))),
+                    total=dict(zip(keys, (int(x) for x in tot))))
+
     def last_finish_ms(self):
         ms = C.c_float(0)
         check(lib().vers_ivf_last_finish_ms(self._h, C.byref(ms)))
