@@ -12,6 +12,10 @@
 // dead by H makes the quad live and the block stops reading.  A quad whose tiles are all dead gets kKeyMax in its partial slots -- what
 // write_out leaves for the later quads of a run -- and the mark the cold launch skips it by (kQuadDead).  Dropping a dead quad drops only
 // rows whose val exceeds a threshold fold would have compared them with: the results stay bit-identical.
+//
+// Nearly every tile is decided at the first boundary, so a wave treats the first 256 columns of its segment's tiles as ONE stream and keeps
+// a ring of kHeadRing 4 KiB steps of it in flight across tile ends and verdicts; its next segment's first loads go out before the barriers
+// of the quad change (scripts/probe/head_stream_probe.hip).
 #pragma once
 #include "prescan.hip.h"
 
@@ -21,9 +25,21 @@ typedef __attribute__((ext_vector_type(4))) int i32x4_t;
 typedef __attribute__((ext_vector_type(16))) int i32x16_t;
 
 constexpr uint32_t kHeadMinCols = 256, kHeadMaxCols = 512;  // H: a multiple of 64 in this range (the first test is at 256 columns)
-constexpr uint32_t kHeadFirst = kHeadMinCols / 64u;         // the first boundary a wave tests at
+constexpr uint32_t kHeadFirst = kHeadPrefix;                // the first boundary a wave tests at (prescan.hip.h: the prefix of the stream)
+static_assert(kHeadFirst * 64u == kHeadMinCols, "the first test is at the smallest head");
 constexpr uint32_t kHeadBnd = kHeadMaxCols / 64u - kHeadFirst + 1u;  // boundaries tested at most
 constexpr int kHeadWaves = 4;                               // a wave per segment of the quad
+// slots of the ring a wave keeps ahead in its stream of tile prefixes (head_stream_pos, prescan.hip.h): 2 or 4 -- a divisor of the prefix,
+// so that the slot of a tile's step s is the constant s % kHeadRing.  scripts/probe/head_stream_probe.hip: 4 streams fastest.
+constexpr int kHeadRing = 4;
+static_assert(kHeadPrefix % kHeadRing == 0,"the ring's slots are indexed by the step within a tile's prefix");
+template <int N, class F>
+static __device__ __forceinline__ void head_static_for(F&& f) {  // f(integral_constant<int, 0>) ... f(integral_constant<int, N - 1>)
+  if constexpr (N > 0) {
+    head_static_for<N - 1>(f);
+    f(std::integral_constant<int, N - 1>{});
+  }
+}
 
 // ---- the derive pass (ivf_build.hip: build_head) ---------------------------------------------------------------------------------------
 // element (r, c) of the blocked f32 rows as the shadow holds it: fp16, round to nearest even
@@ -123,8 +139,48 @@ __global__ __launch_bounds__(kWave * kHeadWaves) __attribute__((amdgpu_waves_per
   const float sx = head_scale(__uint_as_float(hp.misc[kHeadMiscMax]));
   const double Rh2 = (double)__uint_as_float(hp.misc[kHeadMiscRh2]);
   if (threadIdx.x < 4) ctr_l[threadIdx.x] = 0u;
-  uint32_t steps_read = 0;  // (wave-uniform)
+  uint32_t steps_read = 0;  // (wave-uniform) 4 KiB steps requested, those dropped at a live verdict included
+  // The wave's segment and its ring.  The first kHeadFirst steps of the segment's tiles are one stream (head_stream_pos); slot s % R holds
+  // step s of the current tile and is issued again -- R positions on, usually the next tile's -- as soon as the step's math has read it, so
+  // that loads stay in flight through a tile's last math, its verdict and into the next tile.  Only the slot of the prefix's LAST step
+  // waits for the verdict: the steps a tile that survives the first test reads on demand go through it, and the given-up tile's own later
+  // steps are never in flight.  Every load of the ring is unconditional; a position past the segment's end re-reads its last step.
+  constexpr int R = kHeadRing, kLastSlot = (int)(kHeadFirst - 1u) % R;
+  u32x4 ring[R][4];
+  uint32_t n_tiles = 0, nrows = 0, row_s = 0;  // (wave-uniform)
+  const u32x4* sp = nullptr;                   // the segment's head (+ lane)
+  float xn_next = 0.0f;                        // |x|^2 of the lane's row of the tile the ring is about to reach
+  auto issue = [&](auto stag, uint32_t p) {    // stream position p of the segment (n_tiles != 0) -> slot
+    constexpr int sl = decltype(stag)::value;
+    const HeadStreamPos at = head_stream_pos(p, n_tiles);
+    const u32x4* a = sp + ((size_t)at.tile * hs + at.step) * 256u;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) ring[sl][i] = __builtin_nontemporal_load(a + (size_t)i * 64u);
+    steps_read += p < head_stream_len(n_tiles) ? 1u : 0u;
+  };
+  // a segment's rows from its descriptor, by the source's own rule (Src::seg_span, storage_row); a quad beyond the launch's: no tiles
+  auto item_of = [&](uint32_t bi) { return bi < n_quads ? src.items[4 * bi + (uint32_t)wid] : ItemDesc{0u, 0u, kNoSeg}; };
+  struct Seg { uint32_t nrows, row_s; };
+  auto resolve = [&](const ItemDesc& d) {
+    Seg sg;
+    src.seg_span(d, sg.row_s, sg.nrows);
+    return sg;
+  };
+  auto enter = [&](const Seg& sg) {  // make the segment the wave's own; its first R loads go out
+    nrows = sg.nrows;
+    row_s = sg.row_s;
+    n_tiles = (nrows + kWave - 1) / kWave;
+    sp = reinterpret_cast<const u32x4*>(hp.rows_h8 + (uint64_t)row_s * H) + lane;
+    if (head_stream_len(n_tiles) != 0u) {  // (a segment without tiles has no position: nothing is issued)
+      xn_next = hp.xnorm[(uint64_t)row_s + lane];
+      head_static_for<R>([&](auto r) { issue(r, (uint32_t)decltype(r)::value); });
+    }
+  };
+  enter(resolve(item_of(hot_quads + blockIdx.x)));
   for (uint32_t bi = hot_quads + blockIdx.x; bi < n_quads; bi += gridDim.x) {
+    // the next quad's segment: its descriptor is requested here, resolved behind the staging barriers and entered at the end of this
+    // quad's tiles -- none of the three dependent loads stands between the last tile and the next segment's first loads
+    const ItemDesc d_next = item_of(bi + gridDim.x);
     __syncthreads();  // the previous quad's operands and verdict are done with
     const ItemDesc d0 = src.items[4 * bi];
     const uint32_t c0 = src.cnt[d0.list] - d0.group * (uint32_t)NQ;
@@ -148,26 +204,21 @@ __global__ __launch_bounds__(kWave * kHeadWaves) __attribute__((amdgpu_waves_per
       *reinterpret_cast<u32x4*>(qb + ((size_t)j * NQ + slot) * 16u) = *reinterpret_cast<const u32x4*>(hp.q8 + (uint64_t)qix_l[slot] * H + 16u * j);
     }
     __syncthreads();
-    // a wave per segment of the quad
-    const uint32_t it = 4 * bi + (uint32_t)wid;
-    ItemView<NQ> v;
-    src.get(it, v);
-    const uint32_t n_tiles = (v.nrows + kWave - 1) / kWave;
-    const uint32_t row_s = src.storage_row(it);
-    const bool two = NQ > 32 && nq > 32u;  // (block-uniform)
+    // a wave per segment of the quad: the segment was entered, and its first R steps requested, before the barriers above
+    const Seg seg_next = resolve(d_next);
     if (lane == 0 && n_tiles != 0u) atomicAdd(&tiles_l, n_tiles);
     const int n = lane & 31;
+    // The second query set's MFMAs run for every group of a 64-query block, also one of <= 32 queries: twice the matrix work for such a
+    // group, on operand slots 32 .. 63 that the staging above did not write (integer products of whatever LDS holds; its columns are
+    // masked out of the verdict: q < nq).  A block-uniform branch inside a step's math made the compiler keep the ring's new loads in registers of their own
+    // and copy them at the loop's end, behind a wait for them -- and the matrix cores are far from being the limit here.
+    constexpr bool two = NQ > 32;
     for (uint32_t t = 0; t < n_tiles; ++t) {
       if (__hip_atomic_load(&live_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) != 0u) break;  // (wave-uniform: one LDS word)
-      const uint32_t rows_t = v.nrows - t * kWave < (uint32_t)kWave ? v.nrows - t * kWave : (uint32_t)kWave;
-      const float xn = hp.xnorm[(uint64_t)row_s + t * kWave + lane];
-      const u32x4* tp = reinterpret_cast<const u32x4*>(hp.rows_h8 + ((uint64_t)row_s + (uint64_t)t * kWave) * H) + lane;
-      u32x4 buf[2][4];
-      auto load = [&](auto btag, uint32_t s) {
-        constexpr int b = decltype(btag)::value;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) buf[b][i] = __builtin_nontemporal_load(tp + (size_t)(4u * s + (uint32_t)i) * 64u);
-      };
+      const uint32_t rows_t = nrows - t * kWave < (uint32_t)kWave ? nrows - t * kWave : (uint32_t)kWave;
+      const float xn = xn_next;  // requested a tile ago; the next tile's (the last one's again behind it) goes out now
+      xn_next = hp.xnorm[(uint64_t)row_s + (t + 1u < n_tiles ? t + 1u : t) * kWave + lane];
+      const uint32_t p0 = t * kHeadFirst;  // the tile's first position in the stream
       i32x16_t acc[2][2];
 #pragma unroll
       for (int a = 0; a < 2; ++a)
@@ -179,32 +230,28 @@ __global__ __launch_bounds__(kWave * kHeadWaves) __attribute__((amdgpu_waves_per
       bool dead = false;  // (wave-uniform)
       // a tile can be dead only if its 64 |x|^2 are finite (the rule pre_prune applies)
       const bool finite = __ballot(!(__builtin_fabsf(xn) < __builtin_inff())) == 0;
-      auto step = [&](auto btag, uint32_t s) {  // -> true: the tile's verdict is in
-        constexpr int b = decltype(btag)::value;
-        // the next step flies during this one's math -- but not across a boundary that is tested: no step is in flight when a tile is given up
-        if (s + 1u < kHeadFirst) load(std::integral_constant<int, b ^ 1>{}, s + 1u);
-        steps_read += 1u;
+      auto math = [&](auto stag, uint32_t s) {  // step s of the tile, from slot
+        constexpr int b = decltype(stag)::value;
 #pragma unroll
         for (int cbi = 0; cbi < 2; ++cbi) {
           const uint32_t j = (2u * s + (uint32_t)cbi) * 2u + (uint32_t)(lane >> 5);
           const i32x4_t b0 = *reinterpret_cast<const i32x4_t*>(qb + ((size_t)j * NQ + (uint32_t)(n & (NQ - 1))) * 16u);
 #pragma unroll
           for (int h = 0; h < 2; ++h) {
-            const i32x4_t ar = __builtin_bit_cast(i32x4_t, buf[b][2 * cbi + h]);
+            const i32x4_t ar = __builtin_bit_cast(i32x4_t, ring[b][2 * cbi + h]);
             acc[0][h] = __builtin_amdgcn_mfma_i32_32x32x32_i8(ar, b0, acc[0][h], 0, 0, 0);
 #pragma unroll
             for (int u = 0; u < 4; ++u) nsq[h] = __builtin_amdgcn_sdot4(ar[u], ar[u], nsq[h], false);
           }
-          if constexpr (NQ > 32)
-            if (two) {
+          if constexpr (two) {
               const i32x4_t b1 = *reinterpret_cast<const i32x4_t*>(qb + ((size_t)j * NQ + 32u + (uint32_t)n) * 16u);
 #pragma unroll
               for (int h = 0; h < 2; ++h)
-                acc[1][h] = __builtin_amdgcn_mfma_i32_32x32x32_i8(__builtin_bit_cast(i32x4_t, buf[b][2 * cbi + h]), b1, acc[1][h], 0, 0, 0);
+                acc[1][h] = __builtin_amdgcn_mfma_i32_32x32x32_i8(__builtin_bit_cast(i32x4_t, ring[b][2 * cbi + h]), b1, acc[1][h], 0, 0, 0);
             }
         }
-        const uint32_t c = s + 1u;  // columns consumed / 64
-        if (c < kHeadFirst) return false;
+      };
+      auto verdict = [&](uint32_t c) {  // c = columns consumed / 64 (>= kHeadFirst) -> true: the tile is dead at this boundary
         // sum of X^2 of whole rows (the lane's 16 columns per column block + the other k half's), minimum over the tile's live rows
         uint32_t nm = 0xFFFFFFFFu;
 #pragma unroll
@@ -221,7 +268,7 @@ __global__ __launch_bounds__(kWave * kHeadWaves) __attribute__((amdgpu_waves_per
         bool keep = !finite;
 #pragma unroll
         for (int a = 0; a < 2; ++a) {
-          if (a == 1 && !two) break;
+          if (a == 1 && !two) break;  // (compile-time)
           const uint32_t q = (uint32_t)(a * 32 + n);
           // the lane's query column: rows 32 h + 8 (e >> 2) + 4 (lane >> 5) + (e & 3) of the tile
           int im = 0x7FFFFFFF;
@@ -237,21 +284,34 @@ __global__ __launch_bounds__(kWave * kHeadWaves) __attribute__((amdgpu_waves_per
           if (q < nq && q < (uint32_t)NQ)
             keep |= !(head_lower_dot(im, nterm, sx, sn_l[q], brk_l[q][c - kHeadFirst]) > (double)thr_l[q]);
         }
-        if (__ballot(keep) == 0) { dead = true; return true; }
-        if (c >= hs) return true;
-        load(std::integral_constant<int, b ^ 1>{}, s + 1u);  // (kHeadFirst <= s + 1 < hs: the step was not prefetched)
-        return false;
+        return __ballot(keep) == 0;
       };
-      load(std::integral_constant<int, 0>{}, 0u);
-      for (uint32_t s = 0; s < hs; s += 2) {
-        if (step(std::integral_constant<int, 0>{}, s)) break;
-        if (step(std::integral_constant<int, 1>{}, s + 1u)) break;  // (s + 1 < hs: a verdict at hs ended the loop above)
+      // the prefix: every slot but the last goes out again the moment its step is consumed
+      head_static_for<(int)kHeadFirst>([&](auto st) {
+        constexpr int s = decltype(st)::value, sl = s % R;
+        math(std::integral_constant<int, sl>{}, (uint32_t)s);
+        if constexpr (s + 1 < (int)kHeadFirst) issue(std::integral_constant<int, sl>{}, p0 + (uint32_t)s + (uint32_t)R);
+      });
+      dead = verdict(kHeadFirst);
+      // a tile that survives the first test (few do) reads its later steps on demand, one at a time, through the free slot: the next tile's
+      // prefix waits in the other slots and is consumed afterwards, not fetched twice
+      for (uint32_t s = kHeadFirst; !dead && s < hs; ++s) {
+        const u32x4* a = sp + ((size_t)t * hs + s) * 256u;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) ring[kLastSlot][i] = __builtin_nontemporal_load(a + (size_t)i * 64u);
+        steps_read += 1u;
+        math(std::integral_constant<int, kLastSlot>{}, s);
+        dead = verdict(s + 1u);
       }
+      issue(std::integral_constant<int, kLastSlot>{}, p0 + kHeadFirst - 1u + (uint32_t)R);
       if (!dead) {
         if (lane == 0) __hip_atomic_store(&live_flag, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         break;
       }
     }
+    // on to the wave's segment of the block's next quad, ahead of the barriers: what the ring still holds of this one -- re-reads of the
+    // last step at a segment's end, up to R steps of the tiles a live verdict leaves unread -- is dropped
+    enter(seg_next);
     __syncthreads();
     if (live_flag == 0u) {  // (block-uniform) every tile of the quad is ruled out for every query of the group
       const uint32_t kp = hp.kp;

@@ -103,6 +103,18 @@ struct IvfSrc {
     const ItemDesc d = items[it];
     return list_off[d.list] + (d.seg != kNoSeg ? d.seg * list_seg_rows(list_len[d.list], seg_rows, seg_target) : 0u);
   }
+  // get's v.nrows and storage_row of a descriptor ALREADY loaded, for the head filter's look-ahead (head_filter.hip.h), which requests
+  // the descriptor a quad early.  The rule is the two functions' above, restated beside them and not shared with them: the list scan's
+  // kernels are held to their register figures, and routing get through a helper moved two of them.  tests/test_head_stream_gpu.py
+  // fails on any difference (a wrong segment gives wrong verdicts).
+  __device__ __forceinline__ void seg_span(const ItemDesc& d, uint32_t& row_s, uint32_t& nrows) const {
+    const bool real = d.seg != kNoSeg;
+    const uint32_t len = list_len[d.list];
+    const uint32_t sr = list_seg_rows(len, seg_rows, seg_target);
+    const uint32_t r0 = real ? d.seg * sr : 0;
+    row_s = list_off[d.list] + r0;
+    nrows = real ? (len - r0 < sr ? len - r0 : sr) : 0u;
+  }
   __device__ __forceinline__ uint32_t seq_base(uint32_t it, int qi) const {
     const ItemDesc d = items[it];
     return pj_pref[pairs[pair_off[d.list] + d.group * QG + qi]] + d.seg * list_seg_rows(list_len[d.list], seg_rows, seg_target);

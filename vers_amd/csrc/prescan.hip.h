@@ -1039,6 +1039,25 @@ __host__ __device__ inline uint32_t pre_run_len(uint32_t seen, uint32_t n_quads,
   return r < 1u ? 1u : (r > kPreMaxRun ? kPreMaxRun : r);
 }
 
+// ---- the head filter's stream of tile prefixes (head_filter.hip.h): which 4 KiB step a wave requests at stream position p -----------
+// A wave of the filter walks the tiles of its segment; nearly every tile is decided after its first kHeadPrefix steps (256 columns), so
+// those prefixes form ONE stream -- (tile 0, steps 0 .. 3), (tile 1, steps 0 .. 3), ... -- of head_stream_len positions that the wave
+// keeps a ring of loads ahead in, across tile ends.  Loads of a ring are unconditional: a position past the end re-reads the last valid
+// step (it hits cache), so no address outside the segment's own tiles is ever formed.  A segment without tiles has no position at all:
+// its wave issues nothing.
+constexpr uint32_t kHeadPrefix = 4;
+struct HeadStreamPos {
+  uint32_t tile, step;
+};
+__host__ __device__ inline uint32_t head_stream_len(uint32_t n_tiles) { return n_tiles * kHeadPrefix; }
+// (total: for a segment without tiles it answers (0, 0) and the caller, who asks head_stream_len first, requests nothing)
+__host__ __device__ inline HeadStreamPos head_stream_pos(uint32_t p, uint32_t n_tiles) {
+  const uint32_t len = head_stream_len(n_tiles);
+  const uint32_t last = len != 0u ? len - 1u : 0u;
+  const uint32_t pc = p < last ? p : last;
+  return HeadStreamPos{pc / kHeadPrefix, pc % kHeadPrefix};
+}
+
 // ---- the int8 head: ruling a cold tile out from an int8 copy of its first H columns (head_filter.hip.h) -----------------------------
 // P = the head columns consumed so far, S the rest.  The head stores X_j = head_quant(x~_j, s_x), x~ the fp16 shadow value and s_x ONE
 // scale for the whole index; the query's image is Q_j = head_quant(q'_j, s_n), q' = fp16(-2 q) as stage() rounds it, s_n per query.
