@@ -537,9 +537,9 @@ int32_t vers_ivf_search_exhaustive_filtered_dev(vers_ivf_t* h, const float* quer
  *   stats    : vers_ivf_filter_stats covers these calls: [0..2] as above (a tile counts as loaded when some live query of the work item is
  *              allowed a row of it); [3] = allowed (bitmap, storage row) pairs, summed over the call's n_filters bitmaps.  The scan-timing
  *              ring gets the mask kernel's record, then one per scan pass.
- *   out of scope (refused, not approximated): a filter per query on the range calls, sharded handles and partials, the flat corpus handle,
- *              nprobe == 0, more than VERS_FILTER_MAX bitmaps per call, a prepared (reusable) mask, re-grouping a list's queries by filter
- *              in the plan, any fp16 / matrix-core pre-filter. */
+ *   out of scope (refused, not approximated): sharded handles and partials, the flat corpus handle, nprobe == 0, more than VERS_FILTER_MAX
+ *              bitmaps per call, a prepared (reusable) mask, re-grouping a list's queries by filter in the plan, any fp16 / matrix-core
+ *              pre-filter.  (A filter per query on the range calls: the vers_ivf_range_search_*filtered_multi calls below.) */
 #define VERS_FILTER_MAX 64
 int32_t vers_ivf_search_filtered_multi(vers_ivf_t* h, const float* queries, uint64_t q_stride_bytes, uint32_t b, uint32_t top_k, uint32_t nprobe,
                                        const uint64_t* filters, uint64_t filter_stride_words, uint32_t n_filters, uint64_t n_bits,
@@ -585,8 +585,8 @@ int32_t vers_ivf_filter_stats(vers_ivf_t* h, uint64_t* out4, uint64_t* out4_tota
  *              VERS_ERR_INSUFFICIENT no centroids on the probed call (a streamed upload in progress is seen as an empty index); the
  *              exhaustive call on such a handle: VERS_OK, total 0, every limit 0.  VERS_ERR_NAN as above.  VERS_ERR_HIP scratch for the
  *              result staging did not fit, outputs untouched.
- *   out of scope (refused, not approximated): sharded handles and partials, a filter per query, the flat corpus handle, a prepared
- *              (reusable) filter object, any fp16 / matrix-core pre-filter.
+ *   out of scope (refused, not approximated): sharded handles and partials, the flat corpus handle, a prepared (reusable) filter object,
+ *              any fp16 / matrix-core pre-filter.  (A filter per query: the _multi calls below.)
  * vers_ivf_filter_stats covers these calls: [3] comes from the mask kernel; [0..2] -- planned tile visits, loaded tile visits, items skipped
  * before their first load -- are counted in the COUNT pass only, so they do not depend on the radius: what the fill pass skips for lack of
  * hits is range search's own saving, not the filter's.  vers_range_phases counts these calls; its slot [3] then also covers the mask kernel.
@@ -607,6 +607,55 @@ int32_t vers_ivf_range_search_exhaustive_filtered_dev(vers_ivf_t* h, const float
                                                       const uint64_t* allowed_bits_dev, uint64_t n_bits, uint64_t* out_lims_dev,
                                                       uint64_t* out_ids_dev, float* out_dist_dev, uint64_t cap,
                                                       uint64_t* out_total /* host */, void* stream);
+/* FILTERED RANGE search with a FILTER PER QUERY: one batch whose queries belong to different allowed sets, everything within a radius.  The
+ * composition of the filtered range calls and the top-k _multi calls above, and nothing else:
+ *   semantics: nothing new.  With filter_of[q] = f, query q's CSR segment of a _multi call holds, bit for bit (count, ids, order, distance
+ *              bits), query q's segment of vers_ivf_range_search_filtered / vers_ivf_range_search_exhaustive_filtered made with bitmap f on
+ *              the same handle, with the same queries, radii, nprobe / metric and flags.  out_lims is the running sum, *out_total the full
+ *              count.
+ *   filters, filter_stride_words, n_filters, n_bits, filter_of: those of vers_ivf_search_filtered_multi, to the letter (n_bits == 0 with NULL
+ *              filters included: every filter is empty, total 0, every limit 0).
+ *   layout, order, radii, protocol, handle: those of the filtered range calls, to the letter.  *out_total > cap: VERS_OK, out_lims complete,
+ *              out_ids / out_dist UNTOUCHED; cap == 0 with NULL arrays is the size query; b == 0 is a no-op with *out_total = 0.  _dev: every
+ *              pointer but out_total is a device pointer (the bitmaps and filter_of too).  The host-pointer calls stage the bitmaps (packed
+ *              to ceil(n_bits / 64) words each) and filter_of through the workspace.
+ *   scan     : the mask pass of the top-k _multi calls, once per call and before the count pass.  A tile is loaded for a group of queries when
+ *              some query of the group is allowed a row of it, in the count pass and in the fill pass alike, and each query takes only its
+ *              own rows from it.  VERS_ERR_NAN counts a NaN distance only for a (query, row) pair whose row is allowed for THAT query and
+ *              scanned; outputs untouched.
+ *   errors   : the union of the parents', checked before the device is touched where the parents do so.  VERS_ERR_INVALID a NaN radius,
+ *              nprobe == 0, unknown flag bits, n_filters == 0 with b > 0, n_filters > VERS_FILTER_MAX, n_bits > 0 with NULL filters, NULL
+ *              filter_of with b > 0, filter_stride_words < ceil(n_bits / 64), metric > VERS_METRIC_COSDIST on the exhaustive call, a handle
+ *              sharded by cluster, more than 2^32 - 1 results or 2^32 - 1 slots in one call.  VERS_ERR_INSUFFICIENT no centroids on the probed
+ *              call; the exhaustive call on such a handle: VERS_OK, total 0, every limit 0.  Host-pointer calls: an entry of filter_of >=
+ *              n_filters is VERS_ERR_INVALID.  _dev calls: filter_of is NOT read on the host; an entry >= n_filters selects the EMPTY filter
+ *              (query q's segment is empty) and never indexes outside the masks.
+ *   stats    : vers_ivf_filter_stats covers these calls: [0..2] from the COUNT pass only (a tile counts as loaded when some live query of the
+ *              work item is allowed a row of it), [3] = allowed (bitmap, storage row) pairs from the mask kernel.  vers_range_phases counts
+ *              these calls, its slot [3] covering the mask kernel; the scan-timing ring gets the mask kernel's record and none for the range
+ *              passes.
+ *   out of scope (refused, not approximated): sharded handles and partials, the flat corpus handle, nprobe == 0, more than VERS_FILTER_MAX
+ *              bitmaps per call, a prepared (reusable) mask, re-grouping a list's queries by filter in the plan, any fp16 / matrix-core
+ *              pre-filter. */
+int32_t vers_ivf_range_search_filtered_multi(vers_ivf_t* h, const float* queries, uint64_t q_stride_bytes, uint32_t b, const float* radius /* [b] */,
+                                             uint32_t nprobe, uint32_t flags, const uint64_t* filters, uint64_t filter_stride_words,
+                                             uint32_t n_filters, uint64_t n_bits, const uint32_t* filter_of /* [b] */,
+                                             uint64_t* out_lims /* [b+1] */, uint64_t* out_ids, float* out_dist, uint64_t cap, uint64_t* out_total);
+int32_t vers_ivf_range_search_filtered_multi_dev(vers_ivf_t* h, const float* queries_dev, uint64_t ldq_floats, uint32_t b, const float* radius_dev,
+                                                 uint32_t nprobe, uint32_t flags, const uint64_t* filters_dev, uint64_t filter_stride_words,
+                                                 uint32_t n_filters, uint64_t n_bits, const uint32_t* filter_of_dev, uint64_t* out_lims_dev,
+                                                 uint64_t* out_ids_dev, float* out_dist_dev, uint64_t cap, uint64_t* out_total /* host */,
+                                                 void* stream);
+int32_t vers_ivf_range_search_exhaustive_filtered_multi(vers_ivf_t* h, const float* queries, uint64_t q_stride_bytes, uint32_t b,
+                                                        const float* radius /* [b] */, uint32_t metric, uint32_t flags, const uint64_t* filters,
+                                                        uint64_t filter_stride_words, uint32_t n_filters, uint64_t n_bits,
+                                                        const uint32_t* filter_of /* [b] */, uint64_t* out_lims /* [b+1] */, uint64_t* out_ids,
+                                                        float* out_dist, uint64_t cap, uint64_t* out_total);
+int32_t vers_ivf_range_search_exhaustive_filtered_multi_dev(vers_ivf_t* h, const float* queries_dev, uint64_t ldq_floats, uint32_t b,
+                                                            const float* radius_dev, uint32_t metric, uint32_t flags, const uint64_t* filters_dev,
+                                                            uint64_t filter_stride_words, uint32_t n_filters, uint64_t n_bits,
+                                                            const uint32_t* filter_of_dev, uint64_t* out_lims_dev, uint64_t* out_ids_dev,
+                                                            float* out_dist_dev, uint64_t cap, uint64_t* out_total /* host */, void* stream);
 /* SHARDED range search: the range calls on handles sharded by cluster (vers_ivf_set_shard / vers_ivf_build_sharded_dev), where the calls
  * above return VERS_ERR_INVALID.  The result is the unsharded index's, bit for bit -- limits, ids, order, distance bits.  Three layers:
  *

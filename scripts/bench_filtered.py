@@ -21,6 +21,7 @@ Prints ONE JSON line.
     python scripts/bench_filtered.py --rows 10000000 --d 768 --nlist 4096 --nprobe 32
     python scripts/bench_filtered.py --range        # the filtered RANGE search: range_main below
     python scripts/bench_filtered.py --multi        # a filter per query against one per-call search per tenant: multi_main below
+    python scripts/bench_filtered.py --range --multi   # the same for the RANGE search: range_multi_main below
 """
 from __future__ import annotations
 
@@ -269,6 +270,160 @@ def multi_main(args):
     return 0
 
 
+def range_multi_main(args):
+    """--range --multi: a RANGE batch whose queries belong to different tenants (vers_ivf_range_search_filtered_multi_dev), same corpus and
+    index.  Batches of 64 and 1024 over F = 1, 8, 64 tenants.  Tenants round-robin and contiguous, on both sides: the vec ids (`round_robin`:
+    id v belongs to tenant v % F, every tile holds rows of every tenant; `contiguous`: tenant f owns the ids [f n / F, (f + 1) n / F)) and
+    the queries (`rr`: query q on tenant q % F; `blocks`: q // (b / F), so that a group of queries shares few bitmaps).  Radii: each query's
+    10th / 100th-nearest probed distance among the rows its OWN bitmap allows (a filtered-multi top-k search with top_k = 100; the last
+    allowed one where fewer are allowed).  Range calls are synchronous, so the clock is the host's around each variant, the device
+    synchronised before and after; ms as median [min, max] over --reps repeats ALTERNATING between the variants:
+      multi      (a) the one multi call, result in query order
+      per_call   (b) what a caller does without it: F vers_ivf_range_search_filtered_dev calls, call f over tenant f's queries (rr: rows f,
+                 f + F, ... of the batch, addressed through the query stride; the radii gathered per tenant beforehand) into a tenant-major CSR
+                 block, then the segments put back in query order on the device (limits by a prefix sum, ids / distances by one gather each)
+      whole      (c) F = 1 only: the per-call filtered range call of the whole batch -- the price of the new kernel at no benefit
+    + vers_ivf_filter_stats of (a) and summed over (b)'s calls, as tile fractions.  Before timing, (a)'s limits, ids and distance bits are
+    asserted equal to (b)'s.  Prints ONE JSON line."""
+    import torch
+    from tests import datagen as dg
+    from vers_amd import capi
+    from vers_amd.index import IVFFlatIndex
+
+    torch.cuda.set_device(0)
+    n, d, nlist, nprobe = args.rows, args.d, args.nlist, args.nprobe
+    ld = (d + 3) // 4 * 4
+    n_modes = max(1, args.modes_per_list * nlist)
+    sigma = float(dg.default_sigma(d))
+    SEED_X, SEED_C = 0x5EED0001, 0x5EEDC0DE   # bench.py's corpus
+    X = torch.empty(n, ld, dtype=torch.float32, device="cuda")
+    capi.gen_rows_dev(X.data_ptr(), n, d, ld, 1, SEED_X, SEED_C, n_modes, sigma)
+    init = (dg.mix64(np.uint64(0xB01D) + np.arange(nlist, dtype=np.uint64)) % np.uint64(n)).astype(np.uint64)
+    index = IVFFlatIndex(d)
+    t0 = time.perf_counter()
+    assert index.build_dev(X.data_ptr(), n, nlist, 1, args.kmeans_iters, init)
+    t_build = time.perf_counter() - t0
+    log(f"[bench_filtered --range --multi] index built in {t_build:.2f} s")
+
+    KEYS = ("tiles_planned", "tiles_loaded", "items_skipped", "rows_allowed")
+    out = {}
+    for b in (int(x) for x in args.multi_batches.split(",")):
+        Q = torch.empty(b, ld, dtype=torch.float32, device="cuda")
+        capi.gen_rows_dev(Q.data_ptr(), b, d, ld, 1, SEED_X + 1, SEED_C, n_modes, sigma)
+        res = {}
+        for F in (1, 8, 64):
+            assert b % F == 0
+            bf = b // F
+            for layout in (("round_robin", "contiguous") if F > 1 else ("all",)):
+                tenant = (np.arange(n, dtype=np.int64) * F) // n if layout != "round_robin" else np.arange(n, dtype=np.int64) % F
+                words_h = capi.allowed_bitmaps([tenant == f for f in range(F)], n)
+                stride = words_h.shape[1]
+                words = torch.from_numpy(words_h.view(np.int64)).cuda()
+                for assign in (("rr", "blocks") if F > 1 else ("rr",)):
+                    # query q on tenant q % F (rr) or q // (b / F) (blocks); tenant-major row f * bf + i is batch row i * F + f (rr) or itself
+                    # (blocks); back[q] = the tenant-major row of batch row q
+                    ar = np.arange(b)
+                    fo_h = ar % F if assign == "rr" else ar // bf
+                    tm_rows = torch.from_numpy(((ar % bf) * F + ar // bf if assign == "rr" else ar).astype(np.int64)).cuda()
+                    back = torch.from_numpy(((ar % F) * bf + ar // F if assign == "rr" else ar).astype(np.int64)).cuda()
+                    q_off, q_ld = (4 * ld, ld * F) if assign == "rr" else (4 * ld * bf, ld)   # tenant f's queries: Q + f q_off, q_ld floats apart
+                    fo = torch.from_numpy(fo_h.astype(np.int32)).cuda()
+                    oi = torch.zeros(b, 100, dtype=torch.int64, device="cuda"); od = torch.zeros(b, 100, device="cuda"); oc = torch.zeros(b, dtype=torch.int32, device="cuda")
+                    index.search_filtered_multi_dev(Q.data_ptr(), ld, b, 100, nprobe, words.data_ptr(), stride, F, n, fo.data_ptr(), oi.data_ptr(), od.data_ptr(), oc.data_ptr())
+                    index.poll(); torch.cuda.synchronize()
+                    odh, och = od.cpu().numpy(), oc.cpu().numpy().astype(np.int64)
+                    for m in (10, 100):
+                        col = np.clip(np.minimum(m, och) - 1, 0, 99)
+                        rad_h = np.where(och > 0, odh[np.arange(b), col], np.float32(0)).astype(np.float32)
+                        rad = torch.from_numpy(rad_h).cuda()
+                        rad_tm = rad.index_select(0, tm_rows).contiguous()   # the radii per tenant, as the caller of (b) holds them
+                        lims = torch.zeros(b + 1, dtype=torch.int64, device="cuda")
+                        total = index.range_search_filtered_multi_dev(Q.data_ptr(), ld, b, rad.data_ptr(), nprobe, 0, words.data_ptr(), stride, F, n, fo.data_ptr(),
+                                                                      lims.data_ptr(), 0, 0, 0)   # the size query
+                        cap = max(total, 1)
+                        ids = torch.zeros(cap, dtype=torch.int64, device="cuda"); dist = torch.zeros(cap, dtype=torch.float32, device="cuda")
+                        t_lims = torch.zeros(F * (bf + 1), dtype=torch.int64, device="cuda")   # call f's limits: [f (bf + 1), (f + 1)(bf + 1))
+                        t_ids = torch.zeros(cap, dtype=torch.int64, device="cuda"); t_dist = torch.zeros(cap, dtype=torch.float32, device="cuda")
+                        w_lims = torch.zeros(b + 1, dtype=torch.int64, device="cuda")
+                        w_ids = torch.zeros(cap, dtype=torch.int64, device="cuda"); w_dist = torch.zeros(cap, dtype=torch.float32, device="cuda")
+                        got = {}
+                        ar_b = torch.arange(b, device="cuda")
+
+                        def multi():
+                            t = index.range_search_filtered_multi_dev(Q.data_ptr(), ld, b, rad.data_ptr(), nprobe, 0, words.data_ptr(), stride, F, n, fo.data_ptr(),
+                                                                      lims.data_ptr(), ids.data_ptr(), dist.data_ptr(), cap)
+                            assert t == total
+
+                        def per_call(stats=None):
+                            off = 0
+                            for f in range(F):
+                                t = index.range_search_filtered_dev(Q.data_ptr() + q_off * f, q_ld, bf, rad_tm.data_ptr() + 4 * bf * f, nprobe, 0,
+                                                                    words.data_ptr() + 8 * stride * f, n, t_lims.data_ptr() + 8 * (bf + 1) * f,
+                                                                    t_ids.data_ptr() + 8 * off, t_dist.data_ptr() + 4 * off, cap - off)
+                                assert off + t <= cap
+                                if stats is not None:
+                                    st = index.filter_stats()["last"]
+                                    for k in KEYS:
+                                        stats[k] = stats.get(k, 0) + st[k]
+                                off += t
+                            # the segments back in query order: counts and block starts per tenant-major row, limits by a prefix sum, one gather each
+                            tl = t_lims.view(F, bf + 1)
+                            cnt_tm = (tl[:, 1:] - tl[:, :-1]).reshape(-1)
+                            base = torch.cumsum(tl[:, -1], 0) - tl[:, -1]                    # where call f's block starts
+                            start_tm = (tl[:, :-1] + base[:, None]).reshape(-1)
+                            cnt_q = cnt_tm.index_select(0, back)
+                            q_lims = torch.zeros(b + 1, dtype=torch.int64, device="cuda")
+                            q_lims[1:] = torch.cumsum(cnt_q, 0)
+                            owner = torch.repeat_interleave(ar_b, cnt_q, output_size=off)
+                            src = start_tm.index_select(0, back).index_select(0, owner) + (torch.arange(off, device="cuda") - q_lims.index_select(0, owner))
+                            got["lims"], got["ids"], got["dist"] = q_lims, t_ids.index_select(0, src), t_dist.index_select(0, src)
+
+                        def whole():
+                            t = index.range_search_filtered_dev(Q.data_ptr(), ld, b, rad.data_ptr(), nprobe, 0, words.data_ptr(), n, w_lims.data_ptr(), w_ids.data_ptr(),
+                                                                w_dist.data_ptr(), cap)
+                            assert t == total
+
+                        def timed(fn):
+                            torch.cuda.synchronize()
+                            t = time.perf_counter()
+                            fn()
+                            torch.cuda.synchronize()
+                            return (time.perf_counter() - t) * 1e3
+
+                        # warm-up of every shape the timed window uses; (a)'s result is (b)'s; the counters
+                        multi(); torch.cuda.synchronize()
+                        st_a = index.filter_stats()["last"]
+                        st_b = {}
+                        per_call(st_b); torch.cuda.synchronize()
+                        assert torch.equal(lims, got["lims"]), "limits of the multi call and of the per-call calls differ"
+                        assert torch.equal(ids[:total], got["ids"]), "ids differ"
+                        assert torch.equal(dist[:total].view(torch.int32), got["dist"].view(torch.int32)), "distance bits differ"
+                        kinds = {"multi": multi, "per_call": per_call}
+                        if F == 1:
+                            whole(); torch.cuda.synchronize()
+                            assert torch.equal(lims, w_lims) and torch.equal(ids[:total], w_ids[:total]) and torch.equal(dist[:total].view(torch.int32), w_dist[:total].view(torch.int32))
+                            kinds["whole"] = whole
+                        runs = {k: [] for k in kinds}
+                        for _ in range(args.reps):
+                            for k, fn in kinds.items():
+                                runs[k].append(timed(fn))
+                        frac = lambda st: round(st["tiles_loaded"] / max(1, st["tiles_planned"]), 4)
+                        key = f"F{F}/{layout}/{assign}/r{m}"
+                        res[key] = {**{k: mms(v) for k, v in runs.items()},
+                                    "multi_over_per_call": round(float(np.median(runs["multi"]) / np.median(runs["per_call"])), 3),
+                                    "total": total,
+                                    "multi_stats": {**st_a, "tiles_loaded_fraction": frac(st_a)},
+                                    "per_call_stats": {**st_b, "tiles_loaded_fraction": frac(st_b)}}
+                        log(f"[bench_filtered --range --multi] batch {b} {key}: {json.dumps(res[key])}")
+                        del ids, dist, t_ids, t_dist, w_ids, w_dist
+        out[f"batch{b}"] = res
+    line = {"metric": f"vers_ivf_range_search_filtered_multi_dev in ms per call (host clock), IVFFlat (N={n} d={d} nlist={nlist}) nprobe={nprobe}",
+            "build_s": round(t_build, 2), "reps": args.reps, **out}
+    index.close()
+    print(json.dumps(line), flush=True)
+    return 0
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", type=int, default=1_000_000)
@@ -282,10 +437,12 @@ def main():
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--range", action="store_true", help="the filtered RANGE search instead (vers_ivf_range_search_filtered_dev): see range_main")
     ap.add_argument("--multi", action="store_true", help="a filter per query instead (vers_ivf_search_filtered_multi_dev) against one per-call search per tenant: see multi_main")
-    ap.add_argument("--multi-batches", default="64,1024", help="--multi: the batch sizes (multiples of 64)")
+    ap.add_argument("--multi-batches", default="64,1024", help="--multi: the batch sizes (multiples of 64); with --range too")
     ap.add_argument("--inner", type=int, default=8, help="--multi: back-to-back calls per timed window")
     args = ap.parse_args()
     assert args.reps >= 5, "at least 5 alternating repeats per point"
+    if args.range and args.multi:
+        return range_multi_main(args)
     if args.range:
         return range_main(args)
     if args.multi:

@@ -150,6 +150,15 @@ SIGNATURES = {
                                                               _vp, _vp, C.c_uint64, C.POINTER(C.c_uint64)]),
     "vers_ivf_range_search_exhaustive_filtered_dev": (C.c_int32, [_vp, _vp, C.c_uint64, C.c_uint32, _vp, C.c_uint32, C.c_uint32, _vp, C.c_uint64,
                                                                   _vp, _vp, _vp, C.c_uint64, C.POINTER(C.c_uint64), _vp]),
+    "vers_ivf_range_search_filtered_multi": (C.c_int32, [_vp, _vp, C.c_uint64, C.c_uint32, _vp, C.c_uint32, C.c_uint32, _vp, C.c_uint64, C.c_uint32,
+                                                         C.c_uint64, _vp, _vp, _vp, _vp, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "vers_ivf_range_search_filtered_multi_dev": (C.c_int32, [_vp, _vp, C.c_uint64, C.c_uint32, _vp, C.c_uint32, C.c_uint32, _vp, C.c_uint64, C.c_uint32,
+                                                             C.c_uint64, _vp, _vp, _vp, _vp, C.c_uint64, C.POINTER(C.c_uint64), _vp]),
+    "vers_ivf_range_search_exhaustive_filtered_multi": (C.c_int32, [_vp, _vp, C.c_uint64, C.c_uint32, _vp, C.c_uint32, C.c_uint32, _vp, C.c_uint64,
+                                                                    C.c_uint32, C.c_uint64, _vp, _vp, _vp, _vp, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "vers_ivf_range_search_exhaustive_filtered_multi_dev": (C.c_int32, [_vp, _vp, C.c_uint64, C.c_uint32, _vp, C.c_uint32, C.c_uint32, _vp, C.c_uint64,
+                                                                        C.c_uint32, C.c_uint64, _vp, _vp, _vp, _vp, C.c_uint64, C.POINTER(C.c_uint64),
+                                                                        _vp]),
     "vers_kmeans_update": (C.c_int32, [C.c_int32, _vp, C.c_uint64, C.c_uint64, _vp, C.c_uint64, C.c_uint32, _vp]),
     "vers_kmeans_cost": (C.c_int32, [C.c_int32, _vp, C.c_uint64, C.c_uint64, _vp, C.c_uint64, C.c_uint64, _vp, C.c_uint32,
                                      C.POINTER(C.c_float)]),

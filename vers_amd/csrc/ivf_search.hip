@@ -19,6 +19,7 @@
 #include "filter.hip.h"
 #include "filter_multi.hip.h"
 #include "filter_range.hip.h"
+#include "filter_range_multi.hip.h"
 
 namespace vers {
 
@@ -1019,6 +1020,83 @@ int32_t range_filtered_dev_locked(vers_ivf* h, bool probed, const float* q_dev, 
   return filter_end(h, st);
 }
 
+// ---- filtered range search with a filter per query (filter_range_multi.hip.h) ----
+// launch_filter_range_pass's twin for the per-query sets
+template <int QG, bool FILL, class Src>
+static int32_t launch_filter_range_multi_pass(vers_ivf* h, int metric, const Src& src, uint32_t items, const RangeParams& p, const FilterMultiParams& f, hipStream_t st) {
+  const uint32_t blocks = scan_grid(h->n_cu, QG, h->ld, items, (uint32_t)(filter_wave_slots(h) / kWavesPerBlock));
+  return with_metric(metric, [&](auto m) -> int32_t {
+    return launch_scan(filter_range_multi_scan_kernel<QG, decltype(m)::value, FILL, Src>, blocks, kWavesPerBlock, scan_lds_bytes(QG, h->ld), st, src, p, f);
+  });
+}
+
+// FilteredProbedRangeSource with a filter per query: filter_multi_begin's mask kernel opens the first phase, both passes run the per-query kernel.
+struct FilteredMultiProbedRangeSource : ProbedRangeSource {
+  static constexpr bool kPartials = false;
+  const char* who = "vers_ivf_range_search_filtered_multi";
+  const uint64_t* bits_dev; uint64_t n_bits;
+  FilterMultiSpec ms;
+  FilterMultiParams f{};
+  FilteredMultiProbedRangeSource(vers_ivf* hh, const float* q, uint64_t ldq, uint32_t bb, uint32_t np, const uint64_t* bits, uint64_t nb, const FilterMultiSpec& m)
+      : ProbedRangeSource(hh, q, ldq, bb, np), bits_dev(bits), n_bits(nb), ms(m) {}
+  int32_t prepare(hipStream_t st, uint64_t& slots_per_query) {
+    if (int32_t rc = filter_multi_begin(h, bits_dev, n_bits, ms, h->cap_rows, st, f)) return rc;
+    W->no_ahead = true;
+    const int32_t rc = ProbedRangeSource::prepare(st, slots_per_query);
+    W->no_ahead = false;
+    return rc;
+  }
+  template <class Fill>
+  int32_t launch(Fill, RangeParams p, hipStream_t st) const {
+    return with_qg<1, 8, 16>(s.QG, [&](auto qg) -> int32_t {
+      constexpr int QG = decltype(qg)::value;
+      if (QG != 1)
+        if (int32_t rc = fresh_quad_counter(st, &p.next_quad)) return rc;
+      return launch_filter_range_multi_pass<QG, Fill::value>(h, h->metric, make_ivf_src<QG>(h, s, 0u), (uint32_t)s.items_bound, p, f, st);
+    });
+  }
+};
+
+// FilteredStoredRangeSource with a filter per query: the sets cover the rows the scan covers (none on an index without centroids).
+struct FilteredMultiStoredRangeSource : StoredRangeSource {
+  static constexpr bool kPartials = false;
+  const char* who = "vers_ivf_range_search_exhaustive_filtered_multi";
+  const uint64_t* bits_dev; uint64_t n_bits;
+  FilterMultiSpec ms;
+  FilterMultiParams f{};
+  FilteredMultiStoredRangeSource(vers_ivf* hh, const float* q, uint64_t ldq, uint32_t bb, uint32_t m, const uint64_t* bits, uint64_t nb, const FilterMultiSpec& mm)
+      : StoredRangeSource(hh, q, ldq, bb, m), bits_dev(bits), n_bits(nb), ms(mm) {}
+  int32_t prepare(hipStream_t st, uint64_t& slots_per_query) {
+    if (int32_t rc = filter_multi_begin(h, bits_dev, n_bits, ms, (h->k == 0 || h->up.open) ? 0 : h->cap_rows, st, f)) return rc;
+    return StoredRangeSource::prepare(st, slots_per_query);
+  }
+  template <class Fill>
+  int32_t launch(Fill, const RangeParams& p, hipStream_t st) const {
+    return with_qg<1, 8>(sp.QG, [&](auto qg) -> int32_t {
+      constexpr int QG = decltype(qg)::value;
+      using Src = SegSrc<QG, true>;
+      return launch_filter_range_multi_pass<QG, Fill::value>(h, (int)metric,
+                                                             make_seg_src<Src>(h->rows.as<float>(), n_rows, h->ld, sp, W->qil.as<float>(), h->ldq, b, nullptr, 0, h->row_ids.as<uint32_t>()),
+                                                             sp.n_items, p, f, st);
+    });
+  }
+};
+
+// range_filtered_dev_locked with a filter per query: bits_dev holds the bitmaps `ms` describes.  A call that fails leaves vers_ivf_filter_stats
+// where it was.
+int32_t range_filtered_multi_dev_locked(vers_ivf* h, bool probed, const float* q_dev, uint64_t ldq_in, uint32_t b, const float* radius_dev, uint32_t nprobe_or_metric,
+                                        uint32_t flags, const uint64_t* bits_dev, uint64_t n_bits, const FilterMultiSpec& ms, uint64_t* lims_dev, uint64_t* ids_dev,
+                                        float* dist_dev, uint64_t cap, bool own_out, uint64_t* out_total, hipStream_t st) {
+  if (probed) {
+    FilteredMultiProbedRangeSource src(h, q_dev, ldq_in, b, nprobe_or_metric, bits_dev, n_bits, ms);
+    if (int32_t rc = range_search_run(src, W->rg, b, radius_dev, flags, lims_dev, ids_dev, dist_dev, cap, own_out, out_total, st)) return rc;
+    return filter_end(h, st);
+  }
+  FilteredMultiStoredRangeSource src(h, q_dev, ldq_in, b, nprobe_or_metric, bits_dev, n_bits, ms);
+  if (int32_t rc = range_search_run(src, W->rg, b, radius_dev, flags, lims_dev, ids_dev, dist_dev, cap, own_out, out_total, st)) return rc;
+  return filter_end(h, st);
+}
+
 // what the four filtered range entry points refuse before they touch the device: the union of the two parents' checks
 static int32_t range_filter_check(vers_ivf* h, const char* who, bool probed, uint32_t nprobe, uint32_t flags, const uint64_t* bits, uint64_t n_bits) {
   if (flags & ~VERS_RANGE_WALK_ORDER) return fail(VERS_ERR_INVALID, std::string(who) + ": unknown flag bits");
@@ -1827,6 +1905,131 @@ int32_t vers_ivf_range_search_exhaustive_filtered(vers_ivf_t* h, const float* qu
                                                   uint64_t cap, uint64_t* out_total) {
   return range_filtered_host_common(h, "vers_ivf_range_search_exhaustive_filtered", false, queries, q_stride_bytes, b, radius, metric, flags, allowed_bits, n_bits,
                                     out_lims, out_ids, out_dist, cap, out_total);
+}
+
+// ---- filtered range search with a filter per query (filter_range_multi.hip.h) ----
+// what the four entry points refuse before they touch the device: the _multi calls' own arguments, then the filtered range checks
+static int32_t range_filter_multi_check(vers_ivf* h, const char* who, bool probed, uint32_t nprobe, uint32_t flags, uint32_t b, const uint64_t* filters,
+                                        uint64_t stride_words, uint32_t n_filters, uint64_t n_bits, const uint32_t* filter_of) {
+  if (b != 0 && n_filters == 0) return fail(VERS_ERR_INVALID, std::string(who) + ": n_filters == 0");
+  if (n_filters > VERS_FILTER_MAX)
+    return fail(VERS_ERR_INVALID, std::string(who) + ": more than VERS_FILTER_MAX bitmaps in one call; split the batch by allowed set");
+  if (b != 0 && filter_of == nullptr) return fail(VERS_ERR_INVALID, std::string(who) + ": NULL filter_of");
+  if (n_bits != 0 && stride_words < (n_bits + 63) / 64) return fail(VERS_ERR_INVALID, std::string(who) + ": filter_stride_words is smaller than ceil(n_bits / 64)");
+  return range_filter_check(h, who, probed, nprobe, flags, filters, n_bits);
+}
+
+static int32_t range_filtered_multi_dev_common(vers_ivf_t* h, const char* who, bool probed, const float* queries_dev, uint64_t ldq_floats, uint32_t b,
+                                               const float* radius_dev, uint32_t nprobe_or_metric, uint32_t flags, const uint64_t* filters_dev, uint64_t stride_words,
+                                               uint32_t n_filters, uint64_t n_bits, const uint32_t* filter_of_dev, uint64_t* out_lims_dev, uint64_t* out_ids_dev,
+                                               float* out_dist_dev, uint64_t cap, uint64_t* out_total, void* stream) {
+  if (!h) return fail(VERS_ERR_INVALID, "null handle");
+  if (!out_total) return fail(VERS_ERR_INVALID, std::string(who) + ": out_total is required");
+  *out_total = 0;
+  if (!probed && nprobe_or_metric > VERS_METRIC_COSDIST) return fail(VERS_ERR_INVALID, "unknown metric");
+  if (b && (!queries_dev || ldq_floats < h->d || !radius_dev || !out_lims_dev || (cap && (!out_ids_dev || !out_dist_dev))))
+    return fail(VERS_ERR_INVALID, std::string(who) + ": bad arguments");
+  if (b == 0) return VERS_OK;
+  std::shared_lock<std::shared_mutex> lk(h->index);
+  if (int32_t rc = range_filter_multi_check(h, who, probed, probed ? nprobe_or_metric : 1u, flags, b, filters_dev, stride_words, n_filters, n_bits, filter_of_dev))
+    return rc;
+  DeviceGuard g(h->device);
+  WsLease lease(h, true, (hipStream_t)stream);
+  if (lease.rc) return lease.rc;
+  if (int32_t rc = lease.order_on((hipStream_t)stream)) return rc;
+  HostStatusSlot slot(h);
+  const FilterMultiSpec ms{stride_words, n_filters, filter_of_dev};
+  return range_filtered_multi_dev_locked(h, probed, queries_dev, ldq_floats, b, radius_dev, nprobe_or_metric, flags, filters_dev, n_bits, ms, out_lims_dev, out_ids_dev,
+                                         out_dist_dev, cap, false, out_total, (hipStream_t)stream);
+}
+
+int32_t vers_ivf_range_search_filtered_multi_dev(vers_ivf_t* h, const float* queries_dev, uint64_t ldq_floats, uint32_t b, const float* radius_dev, uint32_t nprobe,
+                                                 uint32_t flags, const uint64_t* filters_dev, uint64_t filter_stride_words, uint32_t n_filters, uint64_t n_bits,
+                                                 const uint32_t* filter_of_dev, uint64_t* out_lims_dev, uint64_t* out_ids_dev, float* out_dist_dev, uint64_t cap,
+                                                 uint64_t* out_total, void* stream) {
+  return range_filtered_multi_dev_common(h, "vers_ivf_range_search_filtered_multi_dev", true, queries_dev, ldq_floats, b, radius_dev, nprobe, flags, filters_dev,
+                                         filter_stride_words, n_filters, n_bits, filter_of_dev, out_lims_dev, out_ids_dev, out_dist_dev, cap, out_total, stream);
+}
+
+int32_t vers_ivf_range_search_exhaustive_filtered_multi_dev(vers_ivf_t* h, const float* queries_dev, uint64_t ldq_floats, uint32_t b, const float* radius_dev,
+                                                            uint32_t metric, uint32_t flags, const uint64_t* filters_dev, uint64_t filter_stride_words,
+                                                            uint32_t n_filters, uint64_t n_bits, const uint32_t* filter_of_dev, uint64_t* out_lims_dev,
+                                                            uint64_t* out_ids_dev, float* out_dist_dev, uint64_t cap, uint64_t* out_total, void* stream) {
+  return range_filtered_multi_dev_common(h, "vers_ivf_range_search_exhaustive_filtered_multi_dev", false, queries_dev, ldq_floats, b, radius_dev, metric, flags,
+                                         filters_dev, filter_stride_words, n_filters, n_bits, filter_of_dev, out_lims_dev, out_ids_dev, out_dist_dev, cap, out_total,
+                                         stream);
+}
+
+// host-pointer calls: range_filtered_host_common's staging (queries pinned, radii and limits through the workspace) + filtered_multi_host_common's
+// (the bitmaps packed to ceil(n_bits / 64) words each and filter_of beside them).  An entry of filter_of at or beyond n_filters is refused here,
+// where it can be read.
+static int32_t range_filtered_multi_host_common(vers_ivf_t* h, const char* who, bool probed, const float* queries, uint64_t q_stride_bytes, uint32_t b,
+                                                const float* radius, uint32_t nprobe_or_metric, uint32_t flags, const uint64_t* filters, uint64_t stride_words,
+                                                uint32_t n_filters, uint64_t n_bits, const uint32_t* filter_of, uint64_t* out_lims, uint64_t* out_ids, float* out_dist,
+                                                uint64_t cap, uint64_t* out_total) {
+  if (!h) return fail(VERS_ERR_INVALID, "null handle");
+  if (!out_total) return fail(VERS_ERR_INVALID, std::string(who) + ": out_total is required");
+  *out_total = 0;
+  if (!probed && nprobe_or_metric > VERS_METRIC_COSDIST) return fail(VERS_ERR_INVALID, "unknown metric");
+  if (b && (!queries || q_stride_bytes < (uint64_t)h->d * 4 || q_stride_bytes % 4 || !radius || !out_lims || (cap && (!out_ids || !out_dist))))
+    return fail(VERS_ERR_INVALID, std::string(who) + ": bad arguments");
+  if (b == 0) return VERS_OK;
+  for (uint32_t i = 0; i < b; ++i)
+    if (radius[i] != radius[i]) return fail(VERS_ERR_INVALID, std::string(who) + ": NaN radius");
+  std::shared_lock<std::shared_mutex> lk(h->index);
+  if (int32_t rc = range_filter_multi_check(h, who, probed, probed ? nprobe_or_metric : 1u, flags, b, filters, stride_words, n_filters, n_bits, filter_of)) return rc;
+  for (uint32_t q = 0; q < b; ++q)
+    if (filter_of[q] >= n_filters) return fail(VERS_ERR_INVALID, std::string(who) + ": filter_of[" + std::to_string(q) + "] is not below n_filters");
+  DeviceGuard g(h->device);
+  WsLease lease(h);
+  if (lease.rc) return lease.rc;
+  HostStatusSlot slot(h);
+  HostIo io;
+  if (int32_t rc = host_io_begin(h, queries, q_stride_bytes, b, 0, io)) return rc;  // (the pinned query staging of every host-pointer call)
+  lease.st = W->io_stream;
+  if (int32_t rc = W->rg_rad.reserve((size_t)b * sizeof(float))) return rc;
+  if (int32_t rc = W->rg_lims.reserve(((size_t)b + 1) * sizeof(uint64_t))) return rc;
+  const size_t words = (size_t)((n_bits + 63) / 64), bit_bytes = words * sizeof(uint64_t);
+  if (int32_t rc = W->flt_bits.reserve(std::max<size_t>(8, bit_bytes * n_filters))) return rc;
+  if (int32_t rc = W->flt_of.reserve((size_t)b * sizeof(uint32_t))) return rc;
+  VERS_HIP_TRY(hipMemcpyAsync(W->rg_rad.p, radius, (size_t)b * sizeof(float), hipMemcpyHostToDevice, W->io_stream));
+  uint64_t total = 0;
+  int32_t rc = VERS_OK;
+  if (bit_bytes &&
+      hipMemcpy2DAsync(W->flt_bits.p, bit_bytes, filters, (size_t)stride_words * sizeof(uint64_t), bit_bytes, n_filters, hipMemcpyHostToDevice, W->io_stream) != hipSuccess)
+    rc = fail(VERS_ERR_HIP, std::string(who) + ": staging the bitmaps failed");
+  if (!rc && hipMemcpyAsync(W->flt_of.p, filter_of, (size_t)b * sizeof(uint32_t), hipMemcpyHostToDevice, W->io_stream) != hipSuccess)
+    rc = fail(VERS_ERR_HIP, std::string(who) + ": staging filter_of failed");
+  if (!rc) {
+    const FilterMultiSpec ms{(uint64_t)words, n_filters, W->flt_of.as<uint32_t>()};
+    rc = range_filtered_multi_dev_locked(h, probed, io.q_dev, h->d, b, W->rg_rad.as<float>(), nprobe_or_metric, flags, W->flt_bits.as<uint64_t>(), n_bits, ms,
+                                         W->rg_lims.as<uint64_t>(), nullptr, nullptr, cap, true, &total, W->io_stream);
+  }
+  if (rc) {  // (the caller's bitmaps, filter_of and radii may still be read by the staging copies)
+    (void)hipStreamSynchronize(W->io_stream);
+    return rc;
+  }
+  VERS_HIP_TRY(hipMemcpy(out_lims, W->rg_lims.p, ((size_t)b + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost));
+  *out_total = total;
+  if (total == 0 || total > cap) return VERS_OK;
+  VERS_HIP_TRY(hipMemcpy(out_ids, W->o_ids.p, (size_t)total * sizeof(uint64_t), hipMemcpyDeviceToHost));
+  VERS_HIP_TRY(hipMemcpy(out_dist, W->o_dist.p, (size_t)total * sizeof(float), hipMemcpyDeviceToHost));
+  return VERS_OK;
+}
+
+int32_t vers_ivf_range_search_filtered_multi(vers_ivf_t* h, const float* queries, uint64_t q_stride_bytes, uint32_t b, const float* radius, uint32_t nprobe,
+                                             uint32_t flags, const uint64_t* filters, uint64_t filter_stride_words, uint32_t n_filters, uint64_t n_bits,
+                                             const uint32_t* filter_of, uint64_t* out_lims, uint64_t* out_ids, float* out_dist, uint64_t cap, uint64_t* out_total) {
+  return range_filtered_multi_host_common(h, "vers_ivf_range_search_filtered_multi", true, queries, q_stride_bytes, b, radius, nprobe, flags, filters,
+                                          filter_stride_words, n_filters, n_bits, filter_of, out_lims, out_ids, out_dist, cap, out_total);
+}
+
+int32_t vers_ivf_range_search_exhaustive_filtered_multi(vers_ivf_t* h, const float* queries, uint64_t q_stride_bytes, uint32_t b, const float* radius, uint32_t metric,
+                                                        uint32_t flags, const uint64_t* filters, uint64_t filter_stride_words, uint32_t n_filters, uint64_t n_bits,
+                                                        const uint32_t* filter_of, uint64_t* out_lims, uint64_t* out_ids, float* out_dist, uint64_t cap,
+                                                        uint64_t* out_total) {
+  return range_filtered_multi_host_common(h, "vers_ivf_range_search_exhaustive_filtered_multi", false, queries, q_stride_bytes, b, radius, metric, flags, filters,
+                                          filter_stride_words, n_filters, n_bits, filter_of, out_lims, out_ids, out_dist, cap, out_total);
 }
 
 int32_t vers_range_merge_dev(const uint64_t* keys_dev, const uint64_t* ids_dev, uint64_t rank_stride, const uint64_t* rank_lims_dev, uint32_t world, uint32_t b,

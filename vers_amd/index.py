@@ -406,6 +406,64 @@ class IVFFlatIndex:
                                                                   C.byref(total), _vp(stream)))
         return int(total.value)
 
+    # -- filtered range search with a filter per query: query q of the batch uses bitmap filter_of[q] -----
+    def _range_filtered_multi(self, fn, queries, radius, arg, filters, filter_of, n_bits, walk_order):
+        q = np.ascontiguousarray(np.atleast_2d(queries), dtype=np.float32)
+        b = q.shape[0]
+        r = capi.range_radii(radius, b)
+        words, nb = self._filters_words(filters, n_bits)
+        fo = np.ascontiguousarray(np.broadcast_to(np.asarray(filter_of, dtype=np.uint32).reshape(-1), (b,)))
+        flags = capi.RANGE_WALK_ORDER if walk_order else 0
+        lims = np.zeros(b + 1, dtype=np.uint64)
+        cap = int(self._range_cap)
+        total = C.c_uint64(0)
+        while True:
+            ids = np.zeros(cap, dtype=np.uint64); dist = np.zeros(cap, dtype=np.float32)
+            check(fn(self._h, _ptr(q), 4 * self.d, b, _ptr(r), arg, flags, _ptr(words) if words.size else None, words.shape[1] if words.size else 0,
+                     words.shape[0], nb, _ptr(fo), _ptr(lims), _ptr(ids) if cap else None, _ptr(dist) if cap else None, cap, C.byref(total)))
+            if total.value <= cap:
+                break
+            cap = int(total.value)
+        self._range_cap = int(total.value)
+        return lims, ids[:total.value], dist[:total.value]
+
+    def range_search_filtered_multi(self, queries, radius, nprobe: int, filters, filter_of, n_bits=None, walk_order: bool = False):
+        """One range batch whose queries use different filters (vers_ivf_range_search_filtered_multi; nprobe >= 1): query q's segment is
+        query q's segment of range_search_filtered(queries, radius, nprobe, filters[filter_of[q]]), bit for bit.  filters / filter_of /
+        n_bits as search_filtered_multi.  -> (lims, ids, dist) like range_search, by the same two-call protocol."""
+        return self._range_filtered_multi(lib().vers_ivf_range_search_filtered_multi, queries, radius, nprobe, filters, filter_of, n_bits, walk_order)
+
+    def range_search_exhaustive_filtered_multi(self, queries, radius, filters, filter_of, metric: int = capi.METRIC_L2SQ, n_bits=None,
+                                               walk_order: bool = False):
+        """range_search_exhaustive_filtered with a filter per query (vers_ivf_range_search_exhaustive_filtered_multi)."""
+        return self._range_filtered_multi(lib().vers_ivf_range_search_exhaustive_filtered_multi, queries, radius, metric, filters, filter_of, n_bits,
+                                          walk_order)
+
+    def range_search_filtered_multi_dev(self, q_ptr: int, ldq: int, b: int, radius_ptr: int, nprobe: int, flags: int, filters_ptr: int,
+                                        stride_words: int, n_filters: int, n_bits: int, filter_of_ptr: int, lims_ptr: int, ids_ptr: int, dist_ptr: int,
+                                        cap: int, stream: int = 0) -> int:
+        """vers_ivf_range_search_filtered_multi_dev on raw device pointers (bitmaps and filter_of too); synchronous.  Returns the total: ids /
+        distances were written only when it is <= cap.  A filter_of entry at or beyond n_filters selects the empty filter."""
+        total = C.c_uint64(0)
+        check(lib().vers_ivf_range_search_filtered_multi_dev(self._h, _vp(q_ptr), ldq, b, _vp(radius_ptr), nprobe, flags,
+                                                             _vp(filters_ptr) if filters_ptr else None, stride_words, n_filters, n_bits,
+                                                             _vp(filter_of_ptr) if filter_of_ptr else None, _vp(lims_ptr),
+                                                             _vp(ids_ptr) if ids_ptr else None, _vp(dist_ptr) if dist_ptr else None, cap,
+                                                             C.byref(total), _vp(stream)))
+        return int(total.value)
+
+    def range_search_exhaustive_filtered_multi_dev(self, q_ptr: int, ldq: int, b: int, radius_ptr: int, metric: int, flags: int, filters_ptr: int,
+                                                   stride_words: int, n_filters: int, n_bits: int, filter_of_ptr: int, lims_ptr: int, ids_ptr: int,
+                                                   dist_ptr: int, cap: int, stream: int = 0) -> int:
+        """vers_ivf_range_search_exhaustive_filtered_multi_dev on raw device pointers (bitmaps and filter_of too); synchronous.  Returns the total."""
+        total = C.c_uint64(0)
+        check(lib().vers_ivf_range_search_exhaustive_filtered_multi_dev(self._h, _vp(q_ptr), ldq, b, _vp(radius_ptr), metric, flags,
+                                                                        _vp(filters_ptr) if filters_ptr else None, stride_words, n_filters, n_bits,
+                                                                        _vp(filter_of_ptr) if filter_of_ptr else None, _vp(lims_ptr),
+                                                                        _vp(ids_ptr) if ids_ptr else None, _vp(dist_ptr) if dist_ptr else None, cap,
+                                                                        C.byref(total), _vp(stream)))
+        return int(total.value)
+
     # -- device cache -----------------------------------------------------------------------------------
     def _upload(self):
         v = np.ascontiguousarray(self.values, dtype=np.float32)
