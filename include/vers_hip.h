@@ -494,7 +494,7 @@ int32_t vers_ivf_range_search_exhaustive_dev(vers_ivf_t* h, const float* queries
  *              filtered list lengths: OUT OF SCOPE); metric > VERS_METRIC_COSDIST on the exhaustive call; a handle sharded by cluster
  *              (world > 1: OUT OF SCOPE).  VERS_ERR_INSUFFICIENT no centroids on the probed call, as in vers_ivf_search.
  *   out of scope: nprobe == 0, sharded handles, the flat corpus handle, a prepared (reusable) filter object.  (A filter per query: the _multi
- *              calls below.)
+ *              calls below.  A depth per query, for filters that leave nprobe lists short of top_k rows: the _adaptive calls below.)
  * vers_ivf_filter_stats (measurement hook; functions of the data and the plan alone): out4 = the most recent filtered call of the handle,
  * out4_total = over the handle's life; either may be NULL.  [0] tile visits the plan implied (64-row tiles of every work item, counted once
  * per item and scan pass), [1] tile visits actually loaded, [2] items skipped before their first load, [3] allowed storage rows (popcount
@@ -539,7 +539,8 @@ int32_t vers_ivf_search_exhaustive_filtered_dev(vers_ivf_t* h, const float* quer
  *              ring gets the mask kernel's record, then one per scan pass.
  *   out of scope (refused, not approximated): sharded handles and partials, the flat corpus handle, nprobe == 0, more than VERS_FILTER_MAX
  *              bitmaps per call, a prepared (reusable) mask, re-grouping a list's queries by filter in the plan, any fp16 / matrix-core
- *              pre-filter.  (A filter per query on the range calls: the vers_ivf_range_search_*filtered_multi calls below.) */
+ *              pre-filter.  (A filter per query on the range calls: the vers_ivf_range_search_*filtered_multi calls below.  A depth per
+ *              query: vers_ivf_search_filtered_multi_adaptive below.) */
 #define VERS_FILTER_MAX 64
 int32_t vers_ivf_search_filtered_multi(vers_ivf_t* h, const float* queries, uint64_t q_stride_bytes, uint32_t b, uint32_t top_k, uint32_t nprobe,
                                        const uint64_t* filters, uint64_t filter_stride_words, uint32_t n_filters, uint64_t n_bits,
@@ -557,6 +558,48 @@ int32_t vers_ivf_search_exhaustive_filtered_multi_dev(vers_ivf_t* h, const float
                                                       uint32_t n_filters, uint64_t n_bits, const uint32_t* filter_of_dev, uint64_t* out_ids_dev,
                                                       float* out_dist_dev, uint32_t* out_count_dev, void* stream);
 int32_t vers_ivf_filter_stats(vers_ivf_t* h, uint64_t* out4, uint64_t* out4_total);
+/* ADAPTIVE DEPTH for the probed filtered calls: every query of the batch probes lists until enough allowed rows are in reach, instead of one
+ * nprobe sized for the batch's worst query.  Under a selective filter out_count[q] of the plain calls is often below top_k; the depth a query
+ * needs depends on its list ranking and on the allowed rows per list only, and the device knows both before the scan starts.
+ *   semantics: nothing new for the results.  For query q let L_0, L_1, ... be its lists in the order vers_ivf_search ranks them, a_j the number
+ *              of live rows of L_j that q's bitmap allows, A_P = a_0 + ... + a_{P-1}, P_min = min(nprobe_min, k), P_max = min(nprobe_max, k).
+ *              P_q is the smallest P in [P_min, P_max] with A_P >= min_allowed, or P_max if there is none (min_allowed == 0: P_q = P_min).
+ *              Lists the filter empties, and empty lists, count as probed.  Row q of an adaptive call is bit for bit (ids, order, distance
+ *              bits, out_count[q]) row q of vers_ivf_search_filtered -- of vers_ivf_search_filtered_multi for the _multi calls -- made with
+ *              nprobe = P_q on the same handle, with the same queries, top_k and bitmap(s).  min_allowed = top_k asks for full results
+ *              wherever nprobe_max lists hold them.
+ *   out_nprobe: [b] u32, out_nprobe[q] = P_q; may be NULL.  The _dev calls take a device array.  top_k == 0: nothing is probed, zeros.
+ *   rules    : the bitmap / filters, n_bits, filter_of and VERS_FILTER_MAX, the output layout, the handle, lease and stream rules,
+ *              vers_ivf_poll's latching on the _dev calls, b == 0 (a no-op), top_k == 0 (zeroes the counts) and the staging of the
+ *              host-pointer calls are those of the filtered calls above, to the letter.  On the _dev calls an entry of filter_of at or
+ *              beyond n_filters selects the empty filter: every a_j is 0, so P_q = P_max and out_count[q] = 0.  VERS_ERR_NAN counts a NaN
+ *              distance only on a (query, row) pair whose row is allowed for that query and lies in one of its P_q lists.
+ *   errors   : VERS_ERR_INVALID nprobe_min == 0; nprobe_max < nprobe_min; and those of the filtered calls (a handle sharded by cluster
+ *              included).  VERS_ERR_INSUFFICIENT no centroids.
+ *   cost     : behind the mask pass one small kernel counts the allowed rows per list (per bitmap and list on the _multi calls), and the
+ *              lists are ranked to P_max for every query.  The planning tables and the partial result slots are sized by b x P_max, as those
+ *              of the plain call at nprobe = nprobe_max; the SCAN visits each query's P_q lists only.
+ *   stats    : vers_ivf_filter_stats covers these calls as it covers the plain ones.  The scan-timing ring gets the mask kernel's record,
+ *              then the allowed-count kernel's, then one per scan pass.
+ *   out of scope (refused or absent, not approximated): sharded handles and partials, the range calls (no top_k to aim for), the exhaustive
+ *              calls (nothing to adapt), nprobe == 0. */
+int32_t vers_ivf_search_filtered_adaptive(vers_ivf_t* h, const float* queries, uint64_t q_stride_bytes, uint32_t b, uint32_t top_k,
+                                          uint32_t nprobe_min, uint32_t nprobe_max, uint32_t min_allowed, const uint64_t* allowed_bits,
+                                          uint64_t n_bits, uint64_t* out_ids, float* out_dist, uint32_t* out_count, uint32_t* out_nprobe);
+int32_t vers_ivf_search_filtered_adaptive_dev(vers_ivf_t* h, const float* queries_dev, uint64_t ldq_floats, uint32_t b, uint32_t top_k,
+                                              uint32_t nprobe_min, uint32_t nprobe_max, uint32_t min_allowed, const uint64_t* allowed_bits_dev,
+                                              uint64_t n_bits, uint64_t* out_ids_dev, float* out_dist_dev, uint32_t* out_count_dev,
+                                              uint32_t* out_nprobe_dev, void* stream);
+int32_t vers_ivf_search_filtered_multi_adaptive(vers_ivf_t* h, const float* queries, uint64_t q_stride_bytes, uint32_t b, uint32_t top_k,
+                                                uint32_t nprobe_min, uint32_t nprobe_max, uint32_t min_allowed, const uint64_t* filters,
+                                                uint64_t filter_stride_words, uint32_t n_filters, uint64_t n_bits,
+                                                const uint32_t* filter_of /* [b] */, uint64_t* out_ids, float* out_dist, uint32_t* out_count,
+                                                uint32_t* out_nprobe);
+int32_t vers_ivf_search_filtered_multi_adaptive_dev(vers_ivf_t* h, const float* queries_dev, uint64_t ldq_floats, uint32_t b, uint32_t top_k,
+                                                    uint32_t nprobe_min, uint32_t nprobe_max, uint32_t min_allowed, const uint64_t* filters_dev,
+                                                    uint64_t filter_stride_words, uint32_t n_filters, uint64_t n_bits,
+                                                    const uint32_t* filter_of_dev, uint64_t* out_ids_dev, float* out_dist_dev,
+                                                    uint32_t* out_count_dev, uint32_t* out_nprobe_dev, void* stream);
 /* FILTERED RANGE search (extension): every ALLOWED vector within a radius -- dedup or threshold retrieval inside one tenant, a time window,
  * an ACL.  The composition of the range calls and the filtered top-k calls above, and nothing else:
  *   semantics: a filter is a VIRTUAL REMOVAL, exactly as in vers_ivf_search_filtered.  With A the set of allowed vec ids, a filtered range call

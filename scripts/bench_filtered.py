@@ -22,6 +22,7 @@ Prints ONE JSON line.
     python scripts/bench_filtered.py --range        # the filtered RANGE search: range_main below
     python scripts/bench_filtered.py --multi        # a filter per query against one per-call search per tenant: multi_main below
     python scripts/bench_filtered.py --range --multi   # the same for the RANGE search: range_multi_main below
+    python scripts/bench_filtered.py --adaptive     # a depth per query against one nprobe for the batch: adaptive_main below
 """
 from __future__ import annotations
 
@@ -424,6 +425,127 @@ def range_multi_main(args):
     return 0
 
 
+def adaptive_main(args):
+    """--adaptive: the filtered search to a depth per query (vers_ivf_search_filtered_adaptive_dev), same corpus and index.  Filters: random 1 %,
+    random 0.1 %, a contiguous 1 % id range.  min_allowed = top_k, nprobe_min = --nprobe, nprobe_max = --nprobe-max (default: nlist).  Per (batch, filter):
+      depth            the distribution of P_q = out_nprobe (mean, median, max)
+      short            the share of queries with out_count < top_k, under the adaptive call and under the plain call at nprobe_min
+      recall           recall@top_k against vers_ivf_search_exhaustive_filtered_dev, for both
+    and, over --reps repeats ALTERNATING between the variants, whole-call ms (device events around the call) and the records the call leaves
+    in the scan-timing ring (mask_ms, count_ms of the adaptive calls, scan_ms), as median [min, max]:
+      adaptive         the call as described
+      adaptive_m0      min_allowed = 0: every depth is nprobe_min, the scan is the plain call's; what differs is the count kernel, the plan not
+                       fused into the selection, and the ranking of nprobe_max lists
+      adaptive_m0_p    ... with nprobe_max = nprobe_min as well: the count kernel and the unfused plan alone
+      plain_min        (a) vers_ivf_search_filtered_dev at nprobe_min (unchanged code = the parent commit's kernels)
+      plain_max        (b) the same at nprobe = max_q P_q, the one setting that serves every query without this feature
+      exhaustive       (c) vers_ivf_search_exhaustive_filtered_dev
+    (The rows themselves are held to the oracle by tests/test_filtered_adaptive_gpu.py, not here.)  Prints ONE JSON line."""
+    import torch
+    from tests import datagen as dg
+    from vers_amd import capi
+    from vers_amd.index import IVFFlatIndex
+
+    torch.cuda.set_device(0)
+    n, d, nlist, p_min, top_k = args.rows, args.d, args.nlist, args.nprobe, args.top_k
+    p_max, m = (args.nprobe_max or nlist), top_k
+    ld = (d + 3) // 4 * 4
+    n_modes = max(1, args.modes_per_list * nlist)
+    sigma = float(dg.default_sigma(d))
+    SEED_X, SEED_C = 0x5EED0001, 0x5EEDC0DE   # bench.py's corpus
+    X = torch.empty(n, ld, dtype=torch.float32, device="cuda")
+    capi.gen_rows_dev(X.data_ptr(), n, d, ld, 1, SEED_X, SEED_C, n_modes, sigma)
+    init = (dg.mix64(np.uint64(0xB01D) + np.arange(nlist, dtype=np.uint64)) % np.uint64(n)).astype(np.uint64)
+    index = IVFFlatIndex(d)
+    t0 = time.perf_counter()
+    assert index.build_dev(X.data_ptr(), n, nlist, 1, args.kmeans_iters, init)
+    t_build = time.perf_counter() - t0
+    log(f"[bench_filtered --adaptive] index built in {t_build:.2f} s")
+
+    rng = np.random.default_rng(0xF117E2)
+    filters = {"random_0.01": rng.random(n) < 0.01, "random_0.001": rng.random(n) < 0.001}
+    lo = n // 3
+    contiguous = np.zeros(n, dtype=bool); contiguous[lo:lo + n // 100] = True
+    filters["contiguous_0.01"] = contiguous
+    words = {k: torch.from_numpy(capi.allowed_bitmap(v, n).view(np.int64)).cuda() for k, v in filters.items()}
+    found = capi.env_option("scan_events", 2)
+    out = {}
+    try:
+        capi.set_option("scan_events", 1)
+        for b in (int(x) for x in args.batches.split(",")):
+            Q = torch.empty(b, ld, dtype=torch.float32, device="cuda")
+            capi.gen_rows_dev(Q.data_ptr(), b, d, ld, 1, SEED_X + 1, SEED_C, n_modes, sigma)
+            oi = torch.zeros(b, top_k, dtype=torch.int64, device="cuda"); od = torch.zeros(b, top_k, device="cuda")
+            oc = torch.zeros(b, dtype=torch.int32, device="cuda"); on = torch.zeros(b, dtype=torch.int32, device="cuda")
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            res = {}
+            for name in filters:
+                w = words[name].data_ptr()
+
+                def adaptive(lo_=p_min, hi_=p_max, m_=m):
+                    index.search_filtered_adaptive_dev(Q.data_ptr(), ld, b, top_k, lo_, hi_, m_, w, n, oi.data_ptr(), od.data_ptr(), oc.data_ptr(), on.data_ptr())
+
+                def plain(nprobe):
+                    index.search_filtered_dev(Q.data_ptr(), ld, b, top_k, nprobe, w, n, oi.data_ptr(), od.data_ptr(), oc.data_ptr())
+
+                def exhaustive():
+                    index.search_exhaustive_filtered_dev(Q.data_ptr(), ld, b, top_k, capi.METRIC_L2SQ, w, n, oi.data_ptr(), od.data_ptr(), oc.data_ptr())
+
+                def result(fn):
+                    fn(); index.poll(); torch.cuda.synchronize()
+                    return oi.cpu().numpy().copy(), oc.cpu().numpy().astype(np.int64).copy()
+
+                def recall(ids, cnt, ex_ids, ex_cnt):
+                    hit = sum(len(np.intersect1d(ids[q, :cnt[q]], ex_ids[q, :ex_cnt[q]])) for q in range(b))
+                    return round(hit / max(1, int(ex_cnt.sum())), 4)
+
+                # results first (also the warm-up of the shapes): depths, short counts, recall
+                ex_ids, ex_cnt = result(exhaustive)
+                a_ids, a_cnt = result(adaptive)
+                depth = on.cpu().numpy().astype(np.int64)
+                p_ids, p_cnt = result(lambda: plain(p_min))
+                deep = int(depth.max())
+                variants = {"adaptive": (adaptive, 3), "adaptive_m0": (lambda: adaptive(p_min, p_max, 0), 3), "adaptive_m0_p": (lambda: adaptive(p_min, p_min, 0), 3),
+                            "plain_min": (lambda: plain(p_min), 2), "plain_max": (lambda: plain(deep), 2), "exhaustive": (exhaustive, 2)}
+
+                def timed(fn, n_rec):
+                    index.scan_times(reset=True)
+                    torch.cuda.synchronize()
+                    e0.record(); fn(); e1.record()
+                    index.poll(); torch.cuda.synchronize()
+                    ring = index.scan_times(reset=True)
+                    assert len(ring) == n_rec, (len(ring), n_rec)
+                    r = {"call_ms": e0.elapsed_time(e1), "mask_ms": float(ring[0]), "scan_ms": float(ring[-1])}
+                    if n_rec == 3:
+                        r["count_ms"] = float(ring[1])
+                    return r
+
+                for fn, n_rec in variants.values():
+                    timed(fn, n_rec)
+                runs = {k: [] for k in variants}
+                for _ in range(args.reps):
+                    for k, (fn, n_rec) in variants.items():
+                        runs[k].append(timed(fn, n_rec))
+                med = lambda k, f: float(np.median([r[f] for r in runs[k]]))
+                res[name] = {"depth": {"mean": round(float(depth.mean()), 2), "median": float(np.median(depth)), "max": deep},
+                             "short": {"adaptive": round(float((a_cnt < top_k).mean()), 4), "plain_min": round(float((p_cnt < top_k).mean()), 4)},
+                             "recall": {"adaptive": recall(a_ids, a_cnt, ex_ids, ex_cnt), "plain_min": recall(p_ids, p_cnt, ex_ids, ex_cnt)},
+                             **{k: {f: mms([r[f] for r in v]) for f in v[0]} for k, v in runs.items()},
+                             "m0_minus_plain_min_call_ms": round(med("adaptive_m0", "call_ms") - med("plain_min", "call_ms"), 4),
+                             "m0_p_minus_plain_min_call_ms": round(med("adaptive_m0_p", "call_ms") - med("plain_min", "call_ms"), 4),
+                             "adaptive_over_plain_max_call": round(med("adaptive", "call_ms") / med("plain_max", "call_ms"), 3),
+                             "adaptive_over_exhaustive_call": round(med("adaptive", "call_ms") / med("exhaustive", "call_ms"), 3)}
+                log(f"[bench_filtered --adaptive] batch {b} {name}: {json.dumps(res[name])}")
+            out[f"batch{b}"] = res
+    finally:
+        capi.set_option("scan_events", found)
+    line = {"metric": f"vers_ivf_search_filtered_adaptive_dev in ms, IVFFlat (N={n} d={d} nlist={nlist}) nprobe_min={p_min} nprobe_max={p_max} min_allowed={m} top_k={top_k}",
+            "build_s": round(t_build, 2), "reps": args.reps, **out}
+    index.close()
+    print(json.dumps(line), flush=True)
+    return 0
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", type=int, default=1_000_000)
@@ -437,10 +559,14 @@ def main():
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--range", action="store_true", help="the filtered RANGE search instead (vers_ivf_range_search_filtered_dev): see range_main")
     ap.add_argument("--multi", action="store_true", help="a filter per query instead (vers_ivf_search_filtered_multi_dev) against one per-call search per tenant: see multi_main")
+    ap.add_argument("--adaptive", action="store_true", help="the adaptive depth (vers_ivf_search_filtered_adaptive_dev) against the plain and exhaustive filtered calls: see adaptive_main")
+    ap.add_argument("--nprobe-max", type=int, default=0, help="--adaptive: nprobe_max (0: nlist)")
     ap.add_argument("--multi-batches", default="64,1024", help="--multi: the batch sizes (multiples of 64); with --range too")
     ap.add_argument("--inner", type=int, default=8, help="--multi: back-to-back calls per timed window")
     args = ap.parse_args()
     assert args.reps >= 5, "at least 5 alternating repeats per point"
+    if args.adaptive:
+        return adaptive_main(args)
     if args.range and args.multi:
         return range_multi_main(args)
     if args.range:

@@ -141,6 +141,14 @@ SIGNATURES = {
                                                               C.c_uint64, _vp, _vp, _vp, _vp]),
     "vers_ivf_search_exhaustive_filtered_multi_dev": (C.c_int32, [_vp, _vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, _vp, C.c_uint64, C.c_uint32,
                                                                   C.c_uint64, _vp, _vp, _vp, _vp, _vp]),
+    "vers_ivf_search_filtered_adaptive": (C.c_int32, [_vp, _vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _vp, C.c_uint64,
+                                                      _vp, _vp, _vp, _vp]),
+    "vers_ivf_search_filtered_adaptive_dev": (C.c_int32, [_vp, _vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _vp, C.c_uint64,
+                                                          _vp, _vp, _vp, _vp, _vp]),
+    "vers_ivf_search_filtered_multi_adaptive": (C.c_int32, [_vp, _vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _vp, C.c_uint64,
+                                                            C.c_uint32, C.c_uint64, _vp, _vp, _vp, _vp, _vp]),
+    "vers_ivf_search_filtered_multi_adaptive_dev": (C.c_int32, [_vp, _vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _vp,
+                                                                C.c_uint64, C.c_uint32, C.c_uint64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "vers_ivf_filter_stats": (C.c_int32, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "vers_ivf_range_search_filtered": (C.c_int32, [_vp, _vp, C.c_uint64, C.c_uint32, _vp, C.c_uint32, C.c_uint32, _vp, C.c_uint64, _vp, _vp, _vp,
                                                    C.c_uint64, C.POINTER(C.c_uint64)]),

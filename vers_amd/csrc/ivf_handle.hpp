@@ -25,6 +25,7 @@
 
 namespace vers {
 void shard_plan(const uint64_t* lens, uint64_t k, uint32_t world, uint8_t* owner);
+struct AdaptiveQ;  // filter_adaptive.hip.h
 constexpr int32_t kRetrySpill = 1001;  // internal: reference-mode spill ran past the ranked lists, retry deeper if possible
 }  // namespace vers
 
@@ -51,6 +52,7 @@ struct SearchWs {
   // words per wave a filtered scan can launch (summed into the counters by filter_stats_fold_kernel)
   DevBuf flt_mask, flt_bits, flt_stats;
   DevBuf flt_rows, flt_of;  // a filter per query (filter_multi.hip.h): the row_sets words; the staged filter_of of a host-pointer call
+  DevBuf flt_alen, flt_np;  // adaptive depth (filter_adaptive.hip.h): allowed rows per (bitmap, list); the staged out_nprobe of a host-pointer call
   bool no_ahead = false;  // the plan of a filtered call neither consumes a look-ahead slot nor touches a pending request (plan_search)
   DevBuf rg_rlims;  // sharded range search: every rank's CSR limits [world][b + 1] (range_merge.hip.h); the gather itself goes through g_send / g_recv
   DevBuf g_send, g_recv;  // sharded search without the host in the loop: this rank's [2][b][top_k] partial | the world's
@@ -526,8 +528,11 @@ struct SearchPlan {
 };
 // chains_only: the plan of the ordered-chain list scan whatever the batch (IvfSrc<QG> items, QG 1 / 8 / 16, a single query included) --
 // no item records, no matrix-core scan: what the range search walks (range.hip.h)
+// adaptive (nullable; with chains_only, nprobe >= 1 = nprobe_max): the lists are ranked WITHOUT the plan fused into the selection and
+// plan_queries_adaptive_kernel (filter_adaptive.hip.h) plans in plan_queries_kernel's place -- every query to its own depth; the tables are
+// sized by b x min(nprobe, k) all the same
 int32_t plan_search(vers_ivf* h, const float* q_dev, uint64_t ldq_in, uint32_t b, uint32_t top_k, uint32_t nprobe, hipStream_t st,
-                    SearchPlan& s, bool chains_only = false);
+                    SearchPlan& s, bool chains_only = false, const AdaptiveQ* adaptive = nullptr);
 
 // ---- ivf_search.hip ----------------------------------------------------------------------------------------------------
 int32_t search_dev_locked(vers_ivf* h, const float* q_dev, uint64_t ldq_in, uint32_t b, uint32_t top_k, uint32_t nprobe,

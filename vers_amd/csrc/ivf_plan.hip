@@ -3,6 +3,7 @@
 // otherwise), the per-query plan (which lists, sequence bases, the reference's spill plan) and the re-grouping of the
 // (query, list) pairs BY LIST into work items -- all on the device, no cross-block waiting (plan.hip.h).
 #include "gemm.hip.h"
+#include "filter_adaptive.hip.h"
 #include "ivf_src.hip.h"
 #include "prescan.hip.h"
 
@@ -608,7 +609,7 @@ int32_t coarse(vers_ivf* h, const float* qp, uint32_t b, uint32_t P, hipStream_t
 // Geometry, staging, coarse quantiser and planning of one search call: everything up to the list scan's launch.  On return the
 // per-batch tables of the leased workspace are final (in stream order) and `s` says which scan the search runs.
 int32_t plan_search(vers_ivf* h, const float* q_dev, uint64_t ldq_in, uint32_t b, uint32_t top_k, uint32_t nprobe, hipStream_t st,
-                    SearchPlan& s, bool chains_only) {
+                    SearchPlan& s, bool chains_only, const AdaptiveQ* adaptive) {
   const int ref_mode = nprobe == 0;
   { const int ev = scan_events_ref().load(); W->ev_on = ev == 1 || (ev == 2 && b > 1); }
   // reference mode ranks the 48 nearest lists (48 + 16 slack = one key per lane in the MFMA pre-selection);
@@ -811,11 +812,12 @@ int32_t plan_search(vers_ivf* h, const float* q_dev, uint64_t ldq_in, uint32_t b
     if (h->d == h->ldq && (reinterpret_cast<uintptr_t>(q_dev) & 15u) == 0 && (b == 1 || (ldq_in == h->ldq && b % kGemmBM == 0))) qp = q_dev;
     else if (int32_t rc = stage_plain_queries(h, q_dev, ldq_in, b, &qp, st)) return rc;
     // the zeroed zone: by the coarse contraction's own launch when the ranking runs on the matrix cores (coarse_mfma), else here
-    const bool zero_in_coarse = !one1 && zero_words <= 0xFFFFFFFFull && coarse_uses_mfma(h, qp, b, P);
+    // (an adaptive plan is not made in the selection's tail: the zone gets its memset)
+    const bool zero_in_coarse = !adaptive && !one1 && zero_words <= 0xFFFFFFFFull && coarse_uses_mfma(h, qp, b, P);
     if (zero_in_coarse) pq.zero_words = (uint32_t)zero_words;
     else if (!one1) VERS_HIP_TRY(hipMemsetAsync(cnt, 0, zero_words * sizeof(uint32_t), st));
     if (!one1_fused)
-      if (int32_t rc = coarse(h, qp, b, P, st, one1 ? &n_segs_c : nullptr, one1 ? nullptr : &pq, &planned)) return rc;
+      if (int32_t rc = coarse(h, qp, b, P, st, one1 ? &n_segs_c : nullptr, one1 || adaptive ? nullptr : &pq, &planned)) return rc;
     probe = W->probe.as<uint64_t>();
   }
 
@@ -858,7 +860,10 @@ int32_t plan_search(vers_ivf* h, const float* q_dev, uint64_t ldq_in, uint32_t b
     VERS_HIP_TRY(hipGetLastError());
   } else {
   // (also a single query with P > 64)
-  if (!planned) {
+  if (adaptive) {  // every query to its own depth (filter_adaptive.hip.h)
+    hipLaunchKernelGGL(plan_queries_adaptive_kernel, dim3((b + 3) / 4), dim3(kAdpThreads), 0, st, pq, *adaptive, probe);
+    VERS_HIP_TRY(hipGetLastError());
+  } else if (!planned) {
     hipLaunchKernelGGL(plan_queries_kernel, dim3((b + 3) / 4), dim3(256), 0, st, pq, probe);
     VERS_HIP_TRY(hipGetLastError());
   }

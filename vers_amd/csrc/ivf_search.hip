@@ -18,6 +18,7 @@
 #include "range_merge.hip.h"
 #include "filter.hip.h"
 #include "filter_multi.hip.h"
+#include "filter_adaptive.hip.h"
 #include "filter_range.hip.h"
 #include "filter_range_multi.hip.h"
 
@@ -571,6 +572,12 @@ struct FilterMultiSpec {
   const uint32_t* filter_of;
 };
 
+// An adaptive call's own arguments (filter_adaptive.hip.h): the call's nprobe is nprobe_max; out_nprobe is on the device, nullable.
+struct AdaptiveSpec {
+  uint32_t nprobe_min, min_allowed;
+  uint32_t* out_nprobe;
+};
+
 // filter_begin's twin for a filter per query: row_sets (8 bytes per storage row, whole tiles) and tile_sets (in the per-call mask's buffer)
 // over `n_rows` storage rows + the zeroed counters; the mask kernel inside the same bracket of the scan-timing ring.
 static int32_t filter_multi_begin(vers_ivf* h, const uint64_t* filters_dev, uint64_t n_bits, const FilterMultiSpec& ms, uint64_t n_rows, hipStream_t st,
@@ -671,20 +678,42 @@ int32_t exhaustive_dev_locked(vers_ivf* h, const float* q_dev, uint64_t ldq_in, 
 // without a filter: the centroids do not depend on it), per pass the filtered scan, ivf_merge_kernel as it is.  The caller has checked nprobe,
 // the handle's sharding and its centroids.  multi: bits_dev holds the bitmaps of a call with a filter per query; the mask kernel and the scan
 // kernel are then filter_multi.hip.h's, everything else is the same.
+// adaptive: nprobe is nprobe_max and every query probes to its own depth (filter_adaptive.hip.h) -- behind the mask kernel the allowed rows
+// per list are counted (a record of the scan-timing ring of its own, between the mask's and the passes'), and the plan is the adaptive one.
 int32_t filtered_dev_locked(vers_ivf* h, const float* q_dev, uint64_t ldq_in, uint32_t b, uint32_t top_k, uint32_t nprobe, const uint64_t* bits_dev,
-                            uint64_t n_bits, uint64_t* out_ids, float* out_dist, uint32_t* out_count, hipStream_t st, const FilterMultiSpec* multi = nullptr) {
+                            uint64_t n_bits, uint64_t* out_ids, float* out_dist, uint32_t* out_count, hipStream_t st, const FilterMultiSpec* multi = nullptr,
+                            const AdaptiveSpec* adaptive = nullptr) {
   if (b == 0) return VERS_OK;
   if (top_k == 0) {
     VERS_HIP_TRY(hipMemsetAsync(out_count, 0, sizeof(uint32_t) * b, st));
+    if (adaptive && adaptive->out_nprobe) VERS_HIP_TRY(hipMemsetAsync(adaptive->out_nprobe, 0, sizeof(uint32_t) * b, st));  // (nothing is probed)
     return VERS_OK;
   }
   FilterParams f;
   FilterMultiParams fm;
   if (int32_t rc = multi ? filter_multi_begin(h, bits_dev, n_bits, *multi, h->cap_rows, st, fm) : filter_begin(h, bits_dev, n_bits, h->cap_rows, st, f)) return rc;
   const FilterChoice flt{multi ? nullptr : &f, multi ? &fm : nullptr};
+  AdaptiveQ aq;
+  if (adaptive) {
+    const uint32_t n_sets = multi ? multi->n_filters : 1u;
+    if (int32_t rc = W->flt_alen.reserve((size_t)n_sets * h->k * sizeof(uint32_t))) return rc;
+    aq.p_min = std::min<uint32_t>(adaptive->nprobe_min, h->k); aq.min_allowed = adaptive->min_allowed; aq.allowed_len = W->flt_alen.as<uint32_t>();
+    aq.filter_of = multi ? multi->filter_of : (const uint32_t*)nullptr; aq.n_filters = n_sets; aq.out_nprobe = adaptive->out_nprobe;
+    if (int32_t rc = timed_scan(st, [&]() -> int32_t {
+          const uint32_t blocks = (h->k + kAdpThreads / kWave - 1) / (kAdpThreads / kWave);
+          if (multi)
+            hipLaunchKernelGGL(filter_multi_allowed_len_kernel, dim3(blocks), dim3(kAdpThreads), 0, st, fm.row_sets, fm.tile_sets, (const uint32_t*)h->list_off.as<uint32_t>(),
+                               (const uint32_t*)h->list_len.as<uint32_t>(), h->k, n_sets, W->flt_alen.as<uint32_t>());
+          else
+            hipLaunchKernelGGL(filter_allowed_len_kernel, dim3(blocks), dim3(kAdpThreads), 0, st, f.tile_mask, (const uint32_t*)h->list_off.as<uint32_t>(),
+                               (const uint32_t*)h->list_len.as<uint32_t>(), h->k, W->flt_alen.as<uint32_t>());
+          VERS_HIP_TRY(hipGetLastError());
+          return VERS_OK;
+        })) return rc;
+  }
   SearchPlan s;
   W->no_ahead = true;
-  const int32_t prc = plan_search(h, q_dev, ldq_in, b, top_k, nprobe, st, s, true);
+  const int32_t prc = plan_search(h, q_dev, ldq_in, b, top_k, nprobe, st, s, true, adaptive ? &aq : nullptr);
   W->no_ahead = false;
   if (prc) return prc;
   { const int ev = scan_events_ref().load(); W->ev_on = ev == 1 || ev == 2; }  // (the plan set it for an unfiltered call)
@@ -723,6 +752,18 @@ static int32_t filter_check(vers_ivf* h, const char* who, bool probed, uint32_t 
     return fail(VERS_ERR_INVALID, std::string(who) + ": nprobe must be at least 1 (the reference's spill walk depends on the filtered list lengths: out of scope)");
   if (h->world > 1) return fail(VERS_ERR_INVALID, std::string(who) + ": the handle is sharded by cluster; filtered search on a sharded handle is out of scope");
   if (probed && h->k == 0) return fail(VERS_ERR_INSUFFICIENT, "search on an index without centroids (reference: index out of bounds, ivfflat.rs:169)");
+  return VERS_OK;
+}
+
+// what the four adaptive entry points refuse on top of that (filter_adaptive.hip.h); nullptr: not an adaptive call
+struct AdaptiveArgs {
+  uint32_t nprobe_min, min_allowed;
+  uint32_t* out_nprobe;  // host or device as the call's other outputs, nullable
+};
+static int32_t adaptive_check(const char* who, const AdaptiveArgs* ad, uint32_t nprobe_max) {
+  if (ad == nullptr) return VERS_OK;
+  if (ad->nprobe_min == 0) return fail(VERS_ERR_INVALID, std::string(who) + ": nprobe_min must be at least 1");
+  if (nprobe_max < ad->nprobe_min) return fail(VERS_ERR_INVALID, std::string(who) + ": nprobe_max is below nprobe_min");
   return VERS_OK;
 }
 
@@ -1502,20 +1543,39 @@ int32_t vers_ivf_search_exhaustive(vers_ivf_t* h, const float* queries, uint64_t
 }
 
 // ---- filtered top-k search (filter.hip.h) ----
-int32_t vers_ivf_search_filtered_dev(vers_ivf_t* h, const float* queries_dev, uint64_t ldq_floats, uint32_t b, uint32_t top_k, uint32_t nprobe,
-                                     const uint64_t* allowed_bits_dev, uint64_t n_bits, uint64_t* out_ids_dev, float* out_dist_dev, uint32_t* out_count_dev,
-                                     void* stream) {
+// (ad: the adaptive call's arguments, nprobe then being nprobe_max)
+static int32_t filtered_dev_common(vers_ivf_t* h, const char* who, const float* queries_dev, uint64_t ldq_floats, uint32_t b, uint32_t top_k, uint32_t nprobe,
+                                   const uint64_t* allowed_bits_dev, uint64_t n_bits, uint64_t* out_ids_dev, float* out_dist_dev, uint32_t* out_count_dev,
+                                   void* stream, const AdaptiveArgs* ad = nullptr) {
   if (!h) return fail(VERS_ERR_INVALID, "null handle");
   if (b && (!queries_dev || ldq_floats < h->d || !out_count_dev || (top_k && (!out_ids_dev || !out_dist_dev))))
-    return fail(VERS_ERR_INVALID, "vers_ivf_search_filtered_dev: bad arguments");
+    return fail(VERS_ERR_INVALID, std::string(who) + ": bad arguments");
+  if (int32_t rc = adaptive_check(who, ad, nprobe)) return rc;
   std::shared_lock<std::shared_mutex> lk(h->index);
-  if (int32_t rc = filter_check(h, "vers_ivf_search_filtered_dev", true, nprobe, allowed_bits_dev, n_bits)) return rc;
+  if (int32_t rc = filter_check(h, who, true, nprobe, allowed_bits_dev, n_bits)) return rc;
   if (b == 0) return VERS_OK;
   DeviceGuard g(h->device);
   WsLease lease(h, true, (hipStream_t)stream);
   if (lease.rc) return lease.rc;
   if (int32_t rc = lease.order_on((hipStream_t)stream)) return rc;
-  return filtered_dev_locked(h, queries_dev, ldq_floats, b, top_k, nprobe, allowed_bits_dev, n_bits, out_ids_dev, out_dist_dev, out_count_dev, (hipStream_t)stream);
+  const AdaptiveSpec as{ad ? ad->nprobe_min : 0u, ad ? ad->min_allowed : 0u, ad ? ad->out_nprobe : (uint32_t*)nullptr};
+  return filtered_dev_locked(h, queries_dev, ldq_floats, b, top_k, nprobe, allowed_bits_dev, n_bits, out_ids_dev, out_dist_dev, out_count_dev, (hipStream_t)stream,
+                             nullptr, ad ? &as : nullptr);
+}
+
+int32_t vers_ivf_search_filtered_dev(vers_ivf_t* h, const float* queries_dev, uint64_t ldq_floats, uint32_t b, uint32_t top_k, uint32_t nprobe,
+                                     const uint64_t* allowed_bits_dev, uint64_t n_bits, uint64_t* out_ids_dev, float* out_dist_dev, uint32_t* out_count_dev,
+                                     void* stream) {
+  return filtered_dev_common(h, "vers_ivf_search_filtered_dev", queries_dev, ldq_floats, b, top_k, nprobe, allowed_bits_dev, n_bits, out_ids_dev, out_dist_dev,
+                             out_count_dev, stream);
+}
+
+int32_t vers_ivf_search_filtered_adaptive_dev(vers_ivf_t* h, const float* queries_dev, uint64_t ldq_floats, uint32_t b, uint32_t top_k, uint32_t nprobe_min,
+                                              uint32_t nprobe_max, uint32_t min_allowed, const uint64_t* allowed_bits_dev, uint64_t n_bits, uint64_t* out_ids_dev,
+                                              float* out_dist_dev, uint32_t* out_count_dev, uint32_t* out_nprobe_dev, void* stream) {
+  const AdaptiveArgs ad{nprobe_min, min_allowed, out_nprobe_dev};
+  return filtered_dev_common(h, "vers_ivf_search_filtered_adaptive_dev", queries_dev, ldq_floats, b, top_k, nprobe_max, allowed_bits_dev, n_bits, out_ids_dev,
+                             out_dist_dev, out_count_dev, stream, &ad);
 }
 
 int32_t vers_ivf_search_exhaustive_filtered_dev(vers_ivf_t* h, const float* queries_dev, uint64_t ldq_floats, uint32_t b, uint32_t top_k, uint32_t metric,
@@ -1538,11 +1598,13 @@ int32_t vers_ivf_search_exhaustive_filtered_dev(vers_ivf_t* h, const float* quer
 
 // host-pointer calls: queries through the pinned staging of every host-pointer call, the bitmap through the workspace, one synchronisation
 static int32_t filtered_host_common(vers_ivf_t* h, const char* who, const float* queries, uint64_t q_stride_bytes, uint32_t b, uint32_t top_k, bool probed,
-                                    uint32_t nprobe_or_metric, const uint64_t* allowed_bits, uint64_t n_bits, uint64_t* out_ids, float* out_dist, uint32_t* out_count) {
+                                    uint32_t nprobe_or_metric, const uint64_t* allowed_bits, uint64_t n_bits, uint64_t* out_ids, float* out_dist, uint32_t* out_count,
+                                    const AdaptiveArgs* ad = nullptr) {
   if (!h) return fail(VERS_ERR_INVALID, "null handle");
   if (!probed && nprobe_or_metric > VERS_METRIC_COSDIST) return fail(VERS_ERR_INVALID, "unknown metric");
   if (b && (!queries || q_stride_bytes < (uint64_t)h->d * 4 || q_stride_bytes % 4 || !out_count || (top_k && (!out_ids || !out_dist))))
     return fail(VERS_ERR_INVALID, std::string(who) + ": bad arguments");
+  if (int32_t rc = adaptive_check(who, ad, nprobe_or_metric)) return rc;
   std::shared_lock<std::shared_mutex> lk(h->index);
   if (int32_t rc = filter_check(h, who, probed, probed ? nprobe_or_metric : 1u, allowed_bits, n_bits)) return rc;
   if (b == 0) return VERS_OK;
@@ -1558,8 +1620,12 @@ static int32_t filtered_host_common(vers_ivf_t* h, const char* who, const float*
   if (!rc && bit_bytes && hipMemcpyAsync(W->flt_bits.p, allowed_bits, bit_bytes, hipMemcpyHostToDevice, W->io_stream) != hipSuccess)
     rc = fail(VERS_ERR_HIP, std::string(who) + ": staging the bitmap failed");
   if (!rc && hipMemsetAsync(W->io_out.p, 0, io.out_bytes, W->io_stream) != hipSuccess) rc = fail(VERS_ERR_HIP, std::string(who) + ": hipMemsetAsync failed");  // entries past a query's count come back as zeros
+  const bool want_np = ad && ad->out_nprobe;
+  if (!rc && want_np) rc = W->flt_np.reserve((size_t)b * sizeof(uint32_t));
+  const AdaptiveSpec as{ad ? ad->nprobe_min : 0u, ad ? ad->min_allowed : 0u, want_np ? W->flt_np.as<uint32_t>() : (uint32_t*)nullptr};
   if (!rc)
-    rc = probed ? filtered_dev_locked(h, io.q_dev, h->d, b, top_k, nprobe_or_metric, W->flt_bits.as<uint64_t>(), n_bits, io.ids_dev, io.dist_dev, io.cnt_dev, W->io_stream)
+    rc = probed ? filtered_dev_locked(h, io.q_dev, h->d, b, top_k, nprobe_or_metric, W->flt_bits.as<uint64_t>(), n_bits, io.ids_dev, io.dist_dev, io.cnt_dev, W->io_stream,
+                                      nullptr, ad ? &as : nullptr)
                 : exhaustive_filtered_dev_locked(h, io.q_dev, h->d, b, top_k, nprobe_or_metric, W->flt_bits.as<uint64_t>(), n_bits, io.ids_dev, io.dist_dev, io.cnt_dev,
                                                  W->io_stream);
   if (rc) {  // (the caller's bitmap may still be read by the staging copy)
@@ -1567,12 +1633,21 @@ static int32_t filtered_host_common(vers_ivf_t* h, const char* who, const float*
     return rc;
   }
   rc = host_io_end(h, io, b, top_k, out_ids, out_dist, out_count);
+  if (!rc && want_np) VERS_HIP_TRY(hipMemcpy(ad->out_nprobe, W->flt_np.p, (size_t)b * sizeof(uint32_t), hipMemcpyDeviceToHost));  // (the stream has been waited for)
   return rc == kRetrySpill ? VERS_ERR_INVALID : rc;
 }
 
 int32_t vers_ivf_search_filtered(vers_ivf_t* h, const float* queries, uint64_t q_stride_bytes, uint32_t b, uint32_t top_k, uint32_t nprobe,
                                  const uint64_t* allowed_bits, uint64_t n_bits, uint64_t* out_ids, float* out_dist, uint32_t* out_count) {
   return filtered_host_common(h, "vers_ivf_search_filtered", queries, q_stride_bytes, b, top_k, true, nprobe, allowed_bits, n_bits, out_ids, out_dist, out_count);
+}
+
+int32_t vers_ivf_search_filtered_adaptive(vers_ivf_t* h, const float* queries, uint64_t q_stride_bytes, uint32_t b, uint32_t top_k, uint32_t nprobe_min,
+                                          uint32_t nprobe_max, uint32_t min_allowed, const uint64_t* allowed_bits, uint64_t n_bits, uint64_t* out_ids, float* out_dist,
+                                          uint32_t* out_count, uint32_t* out_nprobe) {
+  const AdaptiveArgs ad{nprobe_min, min_allowed, out_nprobe};
+  return filtered_host_common(h, "vers_ivf_search_filtered_adaptive", queries, q_stride_bytes, b, top_k, true, nprobe_max, allowed_bits, n_bits, out_ids, out_dist,
+                              out_count, &ad);
 }
 
 int32_t vers_ivf_search_exhaustive_filtered(vers_ivf_t* h, const float* queries, uint64_t q_stride_bytes, uint32_t b, uint32_t top_k, uint32_t metric,
@@ -1595,11 +1670,13 @@ static int32_t filter_multi_check(vers_ivf* h, const char* who, bool probed, uin
 
 static int32_t filtered_multi_dev_common(vers_ivf_t* h, const char* who, bool probed, const float* queries_dev, uint64_t ldq_floats, uint32_t b, uint32_t top_k,
                                          uint32_t nprobe_or_metric, const uint64_t* filters_dev, uint64_t stride_words, uint32_t n_filters, uint64_t n_bits,
-                                         const uint32_t* filter_of_dev, uint64_t* out_ids_dev, float* out_dist_dev, uint32_t* out_count_dev, void* stream) {
+                                         const uint32_t* filter_of_dev, uint64_t* out_ids_dev, float* out_dist_dev, uint32_t* out_count_dev, void* stream,
+                                         const AdaptiveArgs* ad = nullptr) {
   if (!h) return fail(VERS_ERR_INVALID, "null handle");
   if (!probed && nprobe_or_metric > VERS_METRIC_COSDIST) return fail(VERS_ERR_INVALID, "unknown metric");
   if (b && (!queries_dev || ldq_floats < h->d || !out_count_dev || (top_k && (!out_ids_dev || !out_dist_dev))))
     return fail(VERS_ERR_INVALID, std::string(who) + ": bad arguments");
+  if (int32_t rc = adaptive_check(who, ad, nprobe_or_metric)) return rc;
   std::shared_lock<std::shared_mutex> lk(h->index);
   if (int32_t rc = filter_multi_check(h, who, probed, probed ? nprobe_or_metric : 1u, b, filters_dev, stride_words, n_filters, n_bits, filter_of_dev)) return rc;
   if (b == 0) return VERS_OK;
@@ -1608,8 +1685,9 @@ static int32_t filtered_multi_dev_common(vers_ivf_t* h, const char* who, bool pr
   if (lease.rc) return lease.rc;
   if (int32_t rc = lease.order_on((hipStream_t)stream)) return rc;
   const FilterMultiSpec ms{stride_words, n_filters, filter_of_dev};
+  const AdaptiveSpec as{ad ? ad->nprobe_min : 0u, ad ? ad->min_allowed : 0u, ad ? ad->out_nprobe : (uint32_t*)nullptr};
   return probed ? filtered_dev_locked(h, queries_dev, ldq_floats, b, top_k, nprobe_or_metric, filters_dev, n_bits, out_ids_dev, out_dist_dev, out_count_dev,
-                                      (hipStream_t)stream, &ms)
+                                      (hipStream_t)stream, &ms, ad ? &as : nullptr)
                 : exhaustive_filtered_dev_locked(h, queries_dev, ldq_floats, b, top_k, nprobe_or_metric, filters_dev, n_bits, out_ids_dev, out_dist_dev, out_count_dev,
                                                  (hipStream_t)stream, &ms);
 }
@@ -1619,6 +1697,15 @@ int32_t vers_ivf_search_filtered_multi_dev(vers_ivf_t* h, const float* queries_d
                                            const uint32_t* filter_of_dev, uint64_t* out_ids_dev, float* out_dist_dev, uint32_t* out_count_dev, void* stream) {
   return filtered_multi_dev_common(h, "vers_ivf_search_filtered_multi_dev", true, queries_dev, ldq_floats, b, top_k, nprobe, filters_dev, filter_stride_words, n_filters,
                                    n_bits, filter_of_dev, out_ids_dev, out_dist_dev, out_count_dev, stream);
+}
+
+int32_t vers_ivf_search_filtered_multi_adaptive_dev(vers_ivf_t* h, const float* queries_dev, uint64_t ldq_floats, uint32_t b, uint32_t top_k, uint32_t nprobe_min,
+                                                    uint32_t nprobe_max, uint32_t min_allowed, const uint64_t* filters_dev, uint64_t filter_stride_words,
+                                                    uint32_t n_filters, uint64_t n_bits, const uint32_t* filter_of_dev, uint64_t* out_ids_dev, float* out_dist_dev,
+                                                    uint32_t* out_count_dev, uint32_t* out_nprobe_dev, void* stream) {
+  const AdaptiveArgs ad{nprobe_min, min_allowed, out_nprobe_dev};
+  return filtered_multi_dev_common(h, "vers_ivf_search_filtered_multi_adaptive_dev", true, queries_dev, ldq_floats, b, top_k, nprobe_max, filters_dev,
+                                   filter_stride_words, n_filters, n_bits, filter_of_dev, out_ids_dev, out_dist_dev, out_count_dev, stream, &ad);
 }
 
 int32_t vers_ivf_search_exhaustive_filtered_multi_dev(vers_ivf_t* h, const float* queries_dev, uint64_t ldq_floats, uint32_t b, uint32_t top_k, uint32_t metric,
@@ -1633,11 +1720,12 @@ int32_t vers_ivf_search_exhaustive_filtered_multi_dev(vers_ivf_t* h, const float
 // entry of filter_of at or beyond n_filters is refused here, where it can be read.
 static int32_t filtered_multi_host_common(vers_ivf_t* h, const char* who, const float* queries, uint64_t q_stride_bytes, uint32_t b, uint32_t top_k, bool probed,
                                           uint32_t nprobe_or_metric, const uint64_t* filters, uint64_t stride_words, uint32_t n_filters, uint64_t n_bits,
-                                          const uint32_t* filter_of, uint64_t* out_ids, float* out_dist, uint32_t* out_count) {
+                                          const uint32_t* filter_of, uint64_t* out_ids, float* out_dist, uint32_t* out_count, const AdaptiveArgs* ad = nullptr) {
   if (!h) return fail(VERS_ERR_INVALID, "null handle");
   if (!probed && nprobe_or_metric > VERS_METRIC_COSDIST) return fail(VERS_ERR_INVALID, "unknown metric");
   if (b && (!queries || q_stride_bytes < (uint64_t)h->d * 4 || q_stride_bytes % 4 || !out_count || (top_k && (!out_ids || !out_dist))))
     return fail(VERS_ERR_INVALID, std::string(who) + ": bad arguments");
+  if (int32_t rc = adaptive_check(who, ad, nprobe_or_metric)) return rc;
   std::shared_lock<std::shared_mutex> lk(h->index);
   if (int32_t rc = filter_multi_check(h, who, probed, probed ? nprobe_or_metric : 1u, b, filters, stride_words, n_filters, n_bits, filter_of)) return rc;
   for (uint32_t q = 0; q < b; ++q)
@@ -1659,9 +1747,13 @@ static int32_t filtered_multi_host_common(vers_ivf_t* h, const char* who, const 
   if (!rc && hipMemcpyAsync(W->flt_of.p, filter_of, (size_t)b * sizeof(uint32_t), hipMemcpyHostToDevice, W->io_stream) != hipSuccess)
     rc = fail(VERS_ERR_HIP, std::string(who) + ": staging filter_of failed");
   if (!rc && hipMemsetAsync(W->io_out.p, 0, io.out_bytes, W->io_stream) != hipSuccess) rc = fail(VERS_ERR_HIP, std::string(who) + ": hipMemsetAsync failed");  // entries past a query's count come back as zeros
+  const bool want_np = ad && ad->out_nprobe;
+  if (!rc && want_np) rc = W->flt_np.reserve((size_t)b * sizeof(uint32_t));
   if (!rc) {
     const FilterMultiSpec ms{(uint64_t)words, n_filters, W->flt_of.as<uint32_t>()};
-    rc = probed ? filtered_dev_locked(h, io.q_dev, h->d, b, top_k, nprobe_or_metric, W->flt_bits.as<uint64_t>(), n_bits, io.ids_dev, io.dist_dev, io.cnt_dev, W->io_stream, &ms)
+    const AdaptiveSpec as{ad ? ad->nprobe_min : 0u, ad ? ad->min_allowed : 0u, want_np ? W->flt_np.as<uint32_t>() : (uint32_t*)nullptr};
+    rc = probed ? filtered_dev_locked(h, io.q_dev, h->d, b, top_k, nprobe_or_metric, W->flt_bits.as<uint64_t>(), n_bits, io.ids_dev, io.dist_dev, io.cnt_dev, W->io_stream, &ms,
+                                      ad ? &as : nullptr)
                 : exhaustive_filtered_dev_locked(h, io.q_dev, h->d, b, top_k, nprobe_or_metric, W->flt_bits.as<uint64_t>(), n_bits, io.ids_dev, io.dist_dev, io.cnt_dev,
                                                  W->io_stream, &ms);
   }
@@ -1670,6 +1762,7 @@ static int32_t filtered_multi_host_common(vers_ivf_t* h, const char* who, const 
     return rc;
   }
   rc = host_io_end(h, io, b, top_k, out_ids, out_dist, out_count);
+  if (!rc && want_np) VERS_HIP_TRY(hipMemcpy(ad->out_nprobe, W->flt_np.p, (size_t)b * sizeof(uint32_t), hipMemcpyDeviceToHost));  // (the stream has been waited for)
   return rc == kRetrySpill ? VERS_ERR_INVALID : rc;
 }
 
@@ -1678,6 +1771,15 @@ int32_t vers_ivf_search_filtered_multi(vers_ivf_t* h, const float* queries, uint
                                        uint64_t* out_ids, float* out_dist, uint32_t* out_count) {
   return filtered_multi_host_common(h, "vers_ivf_search_filtered_multi", queries, q_stride_bytes, b, top_k, true, nprobe, filters, filter_stride_words, n_filters, n_bits,
                                     filter_of, out_ids, out_dist, out_count);
+}
+
+int32_t vers_ivf_search_filtered_multi_adaptive(vers_ivf_t* h, const float* queries, uint64_t q_stride_bytes, uint32_t b, uint32_t top_k, uint32_t nprobe_min,
+                                                uint32_t nprobe_max, uint32_t min_allowed, const uint64_t* filters, uint64_t filter_stride_words, uint32_t n_filters,
+                                                uint64_t n_bits, const uint32_t* filter_of, uint64_t* out_ids, float* out_dist, uint32_t* out_count,
+                                                uint32_t* out_nprobe) {
+  const AdaptiveArgs ad{nprobe_min, min_allowed, out_nprobe};
+  return filtered_multi_host_common(h, "vers_ivf_search_filtered_multi_adaptive", queries, q_stride_bytes, b, top_k, true, nprobe_max, filters, filter_stride_words,
+                                    n_filters, n_bits, filter_of, out_ids, out_dist, out_count, &ad);
 }
 
 int32_t vers_ivf_search_exhaustive_filtered_multi(vers_ivf_t* h, const float* queries, uint64_t q_stride_bytes, uint32_t b, uint32_t top_k, uint32_t metric,

@@ -205,6 +205,23 @@ class IVFFlatIndex {
     return out;
   }
 
+  // Filtered search to an adaptive depth (extension, vers_ivf_search_filtered_adaptive): search_filtered(query, top_k, P, allowed) with P the
+  // smallest depth in [min(nprobe_min, k), min(nprobe_max, k)] whose lists hold min_allowed allowed rows, or the upper end when none does;
+  // *depth (nullable) receives P.
+  std::vector<std::pair<size_t, float>> search_filtered_adaptive(const Vector<N>& query, size_t top_k, size_t nprobe_min, size_t nprobe_max, size_t min_allowed,
+                                                                 const std::vector<bool>& allowed, size_t* depth = nullptr) const {
+    const std::vector<uint64_t> bits = allowed_bitmap(allowed);
+    std::vector<uint64_t> oi(top_k ? top_k : 1);
+    std::vector<float> od(top_k ? top_k : 1);
+    uint32_t cnt = 0, np = 0;
+    check(vers_ivf_search_filtered_adaptive(handle(), query.v, sizeof(Vector<N>), 1, (uint32_t)top_k, (uint32_t)nprobe_min, (uint32_t)nprobe_max,
+                                            (uint32_t)min_allowed, bits.data(), allowed.size(), oi.data(), od.data(), &cnt, &np));
+    if (depth) *depth = np;
+    std::vector<std::pair<size_t, float>> out;
+    for (uint32_t i = 0; i < cnt; ++i) out.emplace_back((size_t)oi[i], od[i]);
+    return out;
+  }
+
   // Exhaustive filtered search (extension, vers_ivf_search_exhaustive_filtered): the top_k nearest among the allowed rows that are in a list
   // now, under `metric`, ascending by (distance, vec id).
   std::vector<std::pair<size_t, float>> search_exhaustive_filtered(const Vector<N>& query, size_t top_k, const std::vector<bool>& allowed,

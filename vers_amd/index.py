@@ -282,6 +282,55 @@ class IVFFlatIndex:
                                                                   stride_words, n_filters, n_bits, _vp(filter_of_ptr) if filter_of_ptr else None,
                                                                   _vp(ids_ptr), _vp(dist_ptr), _vp(cnt_ptr), _vp(stream)))
 
+    # -- adaptive depth: every query probes until min_allowed allowed rows are in reach, between nprobe_min and nprobe_max lists -----
+    def search_filtered_adaptive(self, queries, top_k: int, nprobe_min: int, nprobe_max: int, min_allowed: int, allowed, n_bits=None):
+        """vers_ivf_search_filtered_adaptive: row q is row q of search_filtered(queries, top_k, P_q, allowed), bit for bit, with P_q the
+        smallest depth in [min(nprobe_min, k), min(nprobe_max, k)] whose lists hold min_allowed allowed rows (or the upper end).
+        -> (ids [b, top_k] u64, dist [b, top_k] f32, count [b] u32, nprobe [b] u32 = P_q)."""
+        q = np.ascontiguousarray(np.atleast_2d(queries), dtype=np.float32)
+        b = q.shape[0]
+        words, nb = self._filter_words(allowed, n_bits)
+        ids = np.zeros((b, max(top_k, 1)), dtype=np.uint64)
+        dist = np.zeros((b, max(top_k, 1)), dtype=np.float32)
+        cnt = np.zeros(b, dtype=np.uint32)
+        npr = np.zeros(b, dtype=np.uint32)
+        check(lib().vers_ivf_search_filtered_adaptive(self._h, _ptr(q), 4 * self.d, b, top_k, nprobe_min, nprobe_max, min_allowed, _ptr(words), nb,
+                                                      _ptr(ids), _ptr(dist), _ptr(cnt), _ptr(npr)))
+        return ids[:, :top_k], dist[:, :top_k], cnt, npr
+
+    def search_filtered_adaptive_dev(self, q_ptr: int, ldq: int, b: int, top_k: int, nprobe_min: int, nprobe_max: int, min_allowed: int, bits_ptr: int,
+                                     n_bits: int, ids_ptr: int, dist_ptr: int, cnt_ptr: int, nprobe_ptr: int, stream: int = 0):
+        """vers_ivf_search_filtered_adaptive_dev on raw device pointers (nprobe_ptr: u32 [b] or 0); queued on `stream`, not synchronised."""
+        check(lib().vers_ivf_search_filtered_adaptive_dev(self._h, _vp(q_ptr), ldq, b, top_k, nprobe_min, nprobe_max, min_allowed,
+                                                          _vp(bits_ptr) if bits_ptr else None, n_bits, _vp(ids_ptr), _vp(dist_ptr), _vp(cnt_ptr),
+                                                          _vp(nprobe_ptr) if nprobe_ptr else None, _vp(stream)))
+
+    def search_filtered_multi_adaptive(self, queries, top_k: int, nprobe_min: int, nprobe_max: int, min_allowed: int, filters, filter_of, n_bits=None):
+        """vers_ivf_search_filtered_multi_adaptive: row q is row q of search_filtered_adaptive with bitmap filters[filter_of[q]].
+        -> (ids, dist, count, nprobe)."""
+        q = np.ascontiguousarray(np.atleast_2d(queries), dtype=np.float32)
+        b = q.shape[0]
+        words, nb = self._filters_words(filters, n_bits)
+        fo = np.ascontiguousarray(np.broadcast_to(np.asarray(filter_of, dtype=np.uint32).reshape(-1), (b,)))
+        ids = np.zeros((b, max(top_k, 1)), dtype=np.uint64)
+        dist = np.zeros((b, max(top_k, 1)), dtype=np.float32)
+        cnt = np.zeros(b, dtype=np.uint32)
+        npr = np.zeros(b, dtype=np.uint32)
+        check(lib().vers_ivf_search_filtered_multi_adaptive(self._h, _ptr(q), 4 * self.d, b, top_k, nprobe_min, nprobe_max, min_allowed, _ptr(words),
+                                                            words.shape[1] if words.size else 0, words.shape[0], nb, _ptr(fo), _ptr(ids), _ptr(dist),
+                                                            _ptr(cnt), _ptr(npr)))
+        return ids[:, :top_k], dist[:, :top_k], cnt, npr
+
+    def search_filtered_multi_adaptive_dev(self, q_ptr: int, ldq: int, b: int, top_k: int, nprobe_min: int, nprobe_max: int, min_allowed: int,
+                                           filters_ptr: int, stride_words: int, n_filters: int, n_bits: int, filter_of_ptr: int, ids_ptr: int,
+                                           dist_ptr: int, cnt_ptr: int, nprobe_ptr: int, stream: int = 0):
+        """vers_ivf_search_filtered_multi_adaptive_dev on raw device pointers; a filter_of entry at or beyond n_filters selects the empty filter
+        (depth min(nprobe_max, k), count 0)."""
+        check(lib().vers_ivf_search_filtered_multi_adaptive_dev(self._h, _vp(q_ptr), ldq, b, top_k, nprobe_min, nprobe_max, min_allowed,
+                                                                _vp(filters_ptr) if filters_ptr else None, stride_words, n_filters, n_bits,
+                                                                _vp(filter_of_ptr) if filter_of_ptr else None, _vp(ids_ptr), _vp(dist_ptr), _vp(cnt_ptr),
+                                                                _vp(nprobe_ptr) if nprobe_ptr else None, _vp(stream)))
+
     def filter_stats(self):
         """vers_ivf_filter_stats: of the most recent filtered call and over the handle's life -- 64-row tile visits the plan implied, tile
         visits actually loaded, work items skipped before their first load, allowed storage rows."""
