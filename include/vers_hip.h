@@ -493,7 +493,8 @@ int32_t vers_ivf_range_search_exhaustive_dev(vers_ivf_t* h, const float* queries
  *   errors   : VERS_ERR_INVALID n_bits > 0 with a NULL bitmap; nprobe == 0 on the probed call (the reference's spill walk depends on the
  *              filtered list lengths: OUT OF SCOPE); metric > VERS_METRIC_COSDIST on the exhaustive call; a handle sharded by cluster
  *              (world > 1: OUT OF SCOPE).  VERS_ERR_INSUFFICIENT no centroids on the probed call, as in vers_ivf_search.
- *   out of scope: nprobe == 0, sharded handles, the flat corpus handle, a prepared (reusable) filter object.  (A filter per query: the _multi
+ *   out of scope: nprobe == 0, the flat corpus handle, a prepared (reusable) filter object.  (Handles sharded by cluster: refused HERE;
+ *              vers_ivf_search_filtered_sharded_dev / _partial_dev and their exhaustive twins, further below.  A filter per query: the _multi
  *              calls below.  A depth per query, for filters that leave nprobe lists short of top_k rows: the _adaptive calls below.)
  * vers_ivf_filter_stats (measurement hook; functions of the data and the plan alone): out4 = the most recent filtered call of the handle,
  * out4_total = over the handle's life; either may be NULL.  [0] tile visits the plan implied (64-row tiles of every work item, counted once
@@ -537,9 +538,10 @@ int32_t vers_ivf_search_exhaustive_filtered_dev(vers_ivf_t* h, const float* quer
  *   stats    : vers_ivf_filter_stats covers these calls: [0..2] as above (a tile counts as loaded when some live query of the work item is
  *              allowed a row of it); [3] = allowed (bitmap, storage row) pairs, summed over the call's n_filters bitmaps.  The scan-timing
  *              ring gets the mask kernel's record, then one per scan pass.
- *   out of scope (refused, not approximated): sharded handles and partials, the flat corpus handle, nprobe == 0, more than VERS_FILTER_MAX
+ *   out of scope (refused, not approximated): the flat corpus handle, nprobe == 0, more than VERS_FILTER_MAX
  *              bitmaps per call, a prepared (reusable) mask, re-grouping a list's queries by filter in the plan, any fp16 / matrix-core
- *              pre-filter.  (A filter per query on the range calls: the vers_ivf_range_search_*filtered_multi calls below.  A depth per
+ *              pre-filter.  (Sharded handles and partials: refused HERE; the _filtered_sharded_dev / _filtered_partial_dev calls further
+ *              below, with a non-NULL filter_of_dev.  A filter per query on the range calls: the vers_ivf_range_search_*filtered_multi calls below.  A depth per
  *              query: vers_ivf_search_filtered_multi_adaptive below.) */
 #define VERS_FILTER_MAX 64
 int32_t vers_ivf_search_filtered_multi(vers_ivf_t* h, const float* queries, uint64_t q_stride_bytes, uint32_t b, uint32_t top_k, uint32_t nprobe,
@@ -581,8 +583,9 @@ int32_t vers_ivf_filter_stats(vers_ivf_t* h, uint64_t* out4, uint64_t* out4_tota
  *              of the plain call at nprobe = nprobe_max; the SCAN visits each query's P_q lists only.
  *   stats    : vers_ivf_filter_stats covers these calls as it covers the plain ones.  The scan-timing ring gets the mask kernel's record,
  *              then the allowed-count kernel's, then one per scan pass.
- *   out of scope (refused or absent, not approximated): sharded handles and partials, the range calls (no top_k to aim for), the exhaustive
- *              calls (nothing to adapt), nprobe == 0. */
+ *   out of scope (refused or absent, not approximated): the range calls (no top_k to aim for), the exhaustive calls (nothing to adapt),
+ *              nprobe == 0.  (Sharded handles and partials: refused HERE; vers_ivf_search_filtered_sharded_dev / _partial_dev with a
+ *              vers_adaptive_t, further below.) */
 int32_t vers_ivf_search_filtered_adaptive(vers_ivf_t* h, const float* queries, uint64_t q_stride_bytes, uint32_t b, uint32_t top_k,
                                           uint32_t nprobe_min, uint32_t nprobe_max, uint32_t min_allowed, const uint64_t* allowed_bits,
                                           uint64_t n_bits, uint64_t* out_ids, float* out_dist, uint32_t* out_count, uint32_t* out_nprobe);
@@ -628,8 +631,9 @@ int32_t vers_ivf_search_filtered_multi_adaptive_dev(vers_ivf_t* h, const float* 
  *              VERS_ERR_INSUFFICIENT no centroids on the probed call (a streamed upload in progress is seen as an empty index); the
  *              exhaustive call on such a handle: VERS_OK, total 0, every limit 0.  VERS_ERR_NAN as above.  VERS_ERR_HIP scratch for the
  *              result staging did not fit, outputs untouched.
- *   out of scope (refused, not approximated): sharded handles and partials, the flat corpus handle, a prepared (reusable) filter object,
- *              any fp16 / matrix-core pre-filter.  (A filter per query: the _multi calls below.)
+ *   out of scope (refused, not approximated): the flat corpus handle, a prepared (reusable) filter object, any fp16 / matrix-core
+ *              pre-filter.  (Sharded handles and partials: refused HERE; vers_ivf_range_search_filtered_sharded_dev / _partial_dev and
+ *              their exhaustive twins, further below.  A filter per query: the _multi calls below.)
  * vers_ivf_filter_stats covers these calls: [3] comes from the mask kernel; [0..2] -- planned tile visits, loaded tile visits, items skipped
  * before their first load -- are counted in the COUNT pass only, so they do not depend on the radius: what the fill pass skips for lack of
  * hits is range search's own saving, not the filter's.  vers_range_phases counts these calls; its slot [3] then also covers the mask kernel.
@@ -677,9 +681,10 @@ int32_t vers_ivf_range_search_exhaustive_filtered_dev(vers_ivf_t* h, const float
  *              work item is allowed a row of it), [3] = allowed (bitmap, storage row) pairs from the mask kernel.  vers_range_phases counts
  *              these calls, its slot [3] covering the mask kernel; the scan-timing ring gets the mask kernel's record and none for the range
  *              passes.
- *   out of scope (refused, not approximated): sharded handles and partials, the flat corpus handle, nprobe == 0, more than VERS_FILTER_MAX
+ *   out of scope (refused, not approximated): the flat corpus handle, nprobe == 0, more than VERS_FILTER_MAX
  *              bitmaps per call, a prepared (reusable) mask, re-grouping a list's queries by filter in the plan, any fp16 / matrix-core
- *              pre-filter. */
+ *              pre-filter.  (Sharded handles and partials: refused HERE; the range _filtered_sharded_dev / _filtered_partial_dev calls
+ *              further below, with a non-NULL filter_of_dev.) */
 int32_t vers_ivf_range_search_filtered_multi(vers_ivf_t* h, const float* queries, uint64_t q_stride_bytes, uint32_t b, const float* radius /* [b] */,
                                              uint32_t nprobe, uint32_t flags, const uint64_t* filters, uint64_t filter_stride_words,
                                              uint32_t n_filters, uint64_t n_bits, const uint32_t* filter_of /* [b] */,
@@ -872,6 +877,96 @@ int32_t vers_ivf_search_exhaustive_sharded_dev(vers_ivf_t* h, const vers_gather_
                                                uint64_t ldq_floats, uint32_t b, uint32_t top_k, uint32_t metric,
                                                uint64_t* out_ids_dev, float* out_dist_dev, uint32_t* out_count_dev,
                                                void* stream);
+
+/* ---- FILTERED search on handles SHARDED BY CLUSTER: partials, the merges' input, and the calls end to end ---------------------------
+ * The filtered calls above refuse a sharded handle (world > 1); these nine take one.
+ *   semantics: none of their own.  Call R the result of the matching existing filtered call on the UNSHARDED index -- the same data, lists,
+ *              queries and bitmaps.  Every rank's partial, laid out as the all-gather lays it out and fed UNCHANGED into vers_topk_merge_dev
+ *              (any nprobe >= 1) / vers_range_merge_dev, gives R bit for bit: ids, order, distance bits, counts, limits.  The _sharded_dev
+ *              calls do that end to end and every rank gets R; with `adaptive`, out_nprobe is the unsharded adaptive call's on every rank.
+ *   filters  : always in the _multi form -- filters_dev, filter_stride_words, n_filters, n_bits with the meaning they have above, indexed by
+ *              GLOBAL vec id; every rank passes the same bits.  filter_of_dev == NULL: ONE bitmap for the whole batch, n_filters must be 1,
+ *              the per-call kernels run and the rules are those of vers_ivf_search_filtered / vers_ivf_range_search_filtered, to the
+ *              letter.  filter_of_dev != NULL: a bitmap per query, the per-query kernels, the rules of the _multi calls (an entry at or
+ *              beyond n_filters selects the empty filter).
+ *   partials : top-k: out_keys_dev / out_ids_dev [b * top_k], kKeyMax (all ones) padded, with the keys of vers_ivf_search_partial_dev
+ *              (probed: order bits of the distance << 32 | the row's sequence number in the query's probe order over the GLOBAL list
+ *              lengths) and vers_ivf_search_exhaustive_partial_dev (order bits << 32 | vec id); top_k >= 1; stream-ordered, nothing
+ *              synchronises.  Range: CSR of (key, id) with the keys, the walk-order rule and the cap protocol (on the LOCAL count) of
+ *              vers_ivf_range_search_*partial_dev; synchronous.  Handles sharded or not: at world 1 the partial is the whole result as keys.
+ *   adaptive : NULL = plain depth; else `nprobe` is nprobe_max.  A query's depth depends on the allowed rows of EVERY list and a rank can
+ *              count only the lists it stores.  vers_ivf_filter_allowed_len_dev: the mask pass + the count, out_len_dev[f * k + L] = the
+ *              rows of list L bitmap f allows if this rank stores L, else 0 -- on an unsharded handle the true counts; every list has one
+ *              owner, so the ranks' arrays ADD UP to the global counts.  A partial call takes those global counts (allowed_len_dev, required
+ *              [n_filters][k]; filter_of_dev == NULL: [k]); a _sharded_dev call takes NULL and exchanges them itself.  Depth, sequence
+ *              numbers and out_nprobe come from the global lengths and counts: identical on every rank.
+ *   exchanges: the top-k _sharded_dev calls follow vers_ivf_search_sharded_dev: stream-ordered through g->all_gather_async, never
+ *              synchronising, one gather per call, a rank that fails locally joining it with a poisoned partial (peers latch VERS_ERR_COMM
+ *              at vers_ivf_poll).  An ADAPTIVE call gathers TWICE on the stream: n_filters * k u32 of local allowed counts (summed over the
+ *              ranks on the device, then the plan), then the partials; a rank that fails locally joins both -- zeros in the first, the
+ *              poisoned partial in the second.  The range _sharded_dev calls follow vers_ivf_range_search_sharded_dev: its agreement round
+ *              (a local failure -- option "test_fail_sharded" injects one -- is every rank's status, outputs untouched), the same cap on
+ *              every rank, synchronous comm->all_gather, 2 callbacks per call, 1 for the size query / a total beyond cap / a batch without
+ *              a hit, 0 for a call refused from its arguments.  g / comm == NULL on an unsharded handle: the existing filtered call.
+ *   errors   : the union of the filtered and the sharded calls'.  VERS_ERR_INVALID nprobe == 0 (OUT OF SCOPE); n_filters == 0 with b > 0;
+ *              n_filters > VERS_FILTER_MAX; a NULL filter_of_dev with n_filters != 1; filter_stride_words < ceil(n_bits / 64); n_bits > 0
+ *              with NULL filters; top_k == 0 (top-k calls); VERS_RANGE_WALK_ORDER on an exhaustive range partial or sharded call; a g /
+ *              comm whose rank or world disagree with the handle; adaptive with nprobe_min == 0 or nprobe < nprobe_min; a NULL
+ *              allowed_len_dev on an adaptive partial, a non-NULL one on a sharded call.  VERS_ERR_INSUFFICIENT no centroids on the probed
+ *              calls.  VERS_ERR_NAN only for a (query, row) pair that is allowed, scanned and stored on THIS rank.
+ *   stats    : vers_ivf_filter_stats covers the local part of every one of these calls.  An adaptive partial leaves no allowed-count record in
+ *              the scan-timing ring (it counts nothing).
+ *   out of scope: nprobe == 0, the flat corpus handle, a prepared (reusable) mask, a walk order of the exhaustive range search across ranks. */
+typedef struct vers_adaptive { /* NULL = plain depth */
+  uint32_t nprobe_min, min_allowed;
+  const uint32_t* allowed_len_dev; /* partial call: GLOBAL counts [n_filters][k], required; sharded call: must be NULL */
+  uint32_t* out_nprobe_dev;        /* nullable, [b] */
+} vers_adaptive_t;
+int32_t vers_ivf_filter_allowed_len_dev(vers_ivf_t* h, const uint64_t* filters_dev, uint64_t filter_stride_words, uint32_t n_filters,
+                                        uint64_t n_bits, uint32_t* out_len_dev /* [n_filters][k] */, void* stream);
+int32_t vers_ivf_search_filtered_partial_dev(vers_ivf_t* h, const float* queries_dev, uint64_t ldq_floats, uint32_t b, uint32_t top_k,
+                                             uint32_t nprobe /* nprobe_max if adaptive */, const uint64_t* filters_dev,
+                                             uint64_t filter_stride_words, uint32_t n_filters, uint64_t n_bits, const uint32_t* filter_of_dev,
+                                             const vers_adaptive_t* adaptive, uint64_t* out_keys_dev, uint64_t* out_ids_dev, void* stream);
+int32_t vers_ivf_search_exhaustive_filtered_partial_dev(vers_ivf_t* h, const float* queries_dev, uint64_t ldq_floats, uint32_t b,
+                                                        uint32_t top_k, uint32_t metric, const uint64_t* filters_dev,
+                                                        uint64_t filter_stride_words, uint32_t n_filters, uint64_t n_bits,
+                                                        const uint32_t* filter_of_dev, uint64_t* out_keys_dev, uint64_t* out_ids_dev,
+                                                        void* stream);
+int32_t vers_ivf_search_filtered_sharded_dev(vers_ivf_t* h, const vers_gather_t* g /* NULL = world 1 */, const float* queries_dev,
+                                             uint64_t ldq_floats, uint32_t b, uint32_t top_k, uint32_t nprobe, const uint64_t* filters_dev,
+                                             uint64_t filter_stride_words, uint32_t n_filters, uint64_t n_bits, const uint32_t* filter_of_dev,
+                                             const vers_adaptive_t* adaptive, uint64_t* out_ids_dev, float* out_dist_dev,
+                                             uint32_t* out_count_dev, void* stream);
+int32_t vers_ivf_search_exhaustive_filtered_sharded_dev(vers_ivf_t* h, const vers_gather_t* g /* NULL = world 1 */, const float* queries_dev,
+                                                        uint64_t ldq_floats, uint32_t b, uint32_t top_k, uint32_t metric,
+                                                        const uint64_t* filters_dev, uint64_t filter_stride_words, uint32_t n_filters,
+                                                        uint64_t n_bits, const uint32_t* filter_of_dev, uint64_t* out_ids_dev,
+                                                        float* out_dist_dev, uint32_t* out_count_dev, void* stream);
+int32_t vers_ivf_range_search_filtered_partial_dev(vers_ivf_t* h, const float* queries_dev, uint64_t ldq_floats, uint32_t b,
+                                                   const float* radius_dev, uint32_t nprobe, uint32_t flags, const uint64_t* filters_dev,
+                                                   uint64_t filter_stride_words, uint32_t n_filters, uint64_t n_bits,
+                                                   const uint32_t* filter_of_dev, uint64_t* out_lims_dev /* [b+1] */, uint64_t* out_keys_dev,
+                                                   uint64_t* out_ids_dev, uint64_t cap, uint64_t* out_total /* host */, void* stream);
+int32_t vers_ivf_range_search_exhaustive_filtered_partial_dev(vers_ivf_t* h, const float* queries_dev, uint64_t ldq_floats, uint32_t b,
+                                                              const float* radius_dev, uint32_t metric, uint32_t flags,
+                                                              const uint64_t* filters_dev, uint64_t filter_stride_words, uint32_t n_filters,
+                                                              uint64_t n_bits, const uint32_t* filter_of_dev, uint64_t* out_lims_dev,
+                                                              uint64_t* out_keys_dev, uint64_t* out_ids_dev, uint64_t cap,
+                                                              uint64_t* out_total /* host */, void* stream);
+int32_t vers_ivf_range_search_filtered_sharded_dev(vers_ivf_t* h, const vers_comm_t* comm /* NULL = world 1 */, const float* queries_dev,
+                                                   uint64_t ldq_floats, uint32_t b, const float* radius_dev, uint32_t nprobe, uint32_t flags,
+                                                   const uint64_t* filters_dev, uint64_t filter_stride_words, uint32_t n_filters,
+                                                   uint64_t n_bits, const uint32_t* filter_of_dev, uint64_t* out_lims_dev,
+                                                   uint64_t* out_ids_dev, float* out_dist_dev, uint64_t cap, uint64_t* out_total /* host */,
+                                                   void* stream);
+int32_t vers_ivf_range_search_exhaustive_filtered_sharded_dev(vers_ivf_t* h, const vers_comm_t* comm /* NULL = world 1 */,
+                                                              const float* queries_dev, uint64_t ldq_floats, uint32_t b,
+                                                              const float* radius_dev, uint32_t metric, uint32_t flags,
+                                                              const uint64_t* filters_dev, uint64_t filter_stride_words, uint32_t n_filters,
+                                                              uint64_t n_bits, const uint32_t* filter_of_dev, uint64_t* out_lims_dev,
+                                                              uint64_t* out_ids_dev, float* out_dist_dev, uint64_t cap,
+                                                              uint64_t* out_total /* host */, void* stream);
 
 /* Measurement hook: durations (HIP events on the search's stream) of the two kernels of the most recent batched
  * coarse quantiser -- the queries x centroids contraction on the f32 matrix cores (2*b*k*d flop) and the selection /

@@ -23,6 +23,7 @@ Prints ONE JSON line.
     python scripts/bench_filtered.py --multi        # a filter per query against one per-call search per tenant: multi_main below
     python scripts/bench_filtered.py --range --multi   # the same for the RANGE search: range_multi_main below
     python scripts/bench_filtered.py --adaptive     # a depth per query against one nprobe for the batch: adaptive_main below
+    python scripts/bench_filtered.py --shards 8     # the index sharded over 8 ranks, emulated on one GPU: shards_main below
 """
 from __future__ import annotations
 
@@ -546,6 +547,145 @@ def adaptive_main(args):
     return 0
 
 
+def shards_main(args):
+    """--shards W: filtered search on an index sharded by cluster over W ranks, EMULATED on one GPU the way scripts/emulate_shard.py does it: W
+    handles, each keeping the lists LPT deals to its rank (vers_ivf_set_shard + vers_ivf_upload_dev from the device-resident fields of one
+    build), their partials timed one rank at a time.  No exchange is timed: the all-gather's bytes are 16 * b * top_k per rank.
+    Batches of 64 and 1024; filters: `all` (one bitmap of ones), `random_0.01` (one random 1 % bitmap), `tenants8` (F = 8 contiguous id
+    ranges, query q in tenant q % 8, the per-query kernels).  Per combination, over --reps repeats ALTERNATING between the kinds, ms as median
+    [min, max] over the repeats (each repeat: device events around one call):
+      partial    the SLOWEST rank's vers_ivf_search_filtered_partial_dev
+      merge      vers_topk_merge_dev over the W partials laid out as the all-gather lays them out
+      sharded    partial + merge: what a rank waits for, less the exchange
+      unsharded  the existing filtered call of the same batch on the unsharded handle (vers_ivf_search_filtered_dev / _multi_dev)
+      discard    what a sharded deployment has without these calls: the slowest rank's UNFILTERED vers_ivf_search_partial_dev + merge at
+                 top_k' = min(1024, ceil(top_k / selectivity)) -- enough results that about top_k survive --, the result copied to the host and
+                 the rows outside the query's bitmap dropped there (numpy), wall clock around all of it
+    Before timing the merged partials are checked equal to the unsharded call's rows.  Prints ONE JSON line."""
+    import torch
+    from tests import datagen as dg
+    from vers_amd import capi
+    from vers_amd.index import IVFFlatIndex
+
+    torch.cuda.set_device(0)
+    W = args.shards
+    n, d, nlist, nprobe, top_k = args.rows, args.d, args.nlist, args.nprobe, args.top_k
+    ld = (d + 3) // 4 * 4
+    n_modes = max(1, args.modes_per_list * nlist)
+    sigma = float(dg.default_sigma(d))
+    SEED_X, SEED_C = 0x5EED0001, 0x5EEDC0DE   # bench.py's corpus
+    X = torch.empty(n, ld, dtype=torch.float32, device="cuda")
+    capi.gen_rows_dev(X.data_ptr(), n, d, ld, 1, SEED_X, SEED_C, n_modes, sigma)
+    init = (dg.mix64(np.uint64(0xB01D) + np.arange(nlist, dtype=np.uint64)) % np.uint64(n)).astype(np.uint64)
+    whole = IVFFlatIndex(d)
+    t0 = time.perf_counter()
+    assert whole.build_dev(X.data_ptr(), n, nlist, 1, args.kmeans_iters, init, want_fields=True)
+    t_build = time.perf_counter() - t0
+    Cd = torch.from_numpy(np.ascontiguousarray(whole.centroids)).cuda()
+    Ad = torch.from_numpy(whole.assignments.astype(np.int64)).cuda()
+    shards = []
+    for r in range(W):
+        ix = IVFFlatIndex(d)
+        if W > 1:
+            ix.set_shard(r, W)
+        ix.upload_dev(X.data_ptr(), n, ld, Cd.data_ptr(), nlist, d, Ad.data_ptr())
+        shards.append(ix)
+    torch.cuda.synchronize()
+    log(f"[bench_filtered --shards {W}] index built in {t_build:.2f} s, {W} shards uploaded")
+
+    rng = np.random.default_rng(0xF117E5)
+    tenant = (np.arange(n, dtype=np.int64) * 8) // n
+    sets = {"all": ([np.ones(n, dtype=bool)], None, 1.0), "random_0.01": ([rng.random(n) < 0.01], None, 0.01),
+            "tenants8": ([tenant == f for f in range(8)], 8, 0.125)}
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+
+    def timed(fn, polls):
+        torch.cuda.synchronize()
+        e0.record(); fn(); e1.record()
+        for ix in polls:
+            ix.poll()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1)
+
+    out = {}
+    for b in (int(x) for x in args.multi_batches.split(",")):
+        Q = torch.empty(b, ld, dtype=torch.float32, device="cuda")
+        capi.gen_rows_dev(Q.data_ptr(), b, d, ld, 1, SEED_X + 1, SEED_C, n_modes, sigma)
+        res = {}
+        for name, (masks, F, sel) in sets.items():
+            words_h = capi.allowed_bitmaps(masks, n)
+            words = torch.from_numpy(words_h.view(np.int64)).cuda()
+            fo_h = (np.arange(b) % F).astype(np.int32) if F else None
+            fo = torch.from_numpy(fo_h).cuda() if F else None
+            filt = (words.data_ptr(), words_h.shape[1], len(masks), n, fo.data_ptr() if F else 0)
+            k_unf = min(1024, int(np.ceil(top_k / sel)))
+            buf = torch.zeros(W, 2, b, top_k, dtype=torch.int64, device="cuda")
+            ubuf = torch.zeros(W, 2, b, k_unf, dtype=torch.int64, device="cuda")
+            oi = torch.zeros(b, top_k, dtype=torch.int64, device="cuda"); od = torch.zeros(b, top_k, device="cuda"); oc = torch.zeros(b, dtype=torch.int32, device="cuda")
+            wi = torch.zeros(b, top_k, dtype=torch.int64, device="cuda"); wd = torch.zeros(b, top_k, device="cuda"); wc = torch.zeros(b, dtype=torch.int32, device="cuda")
+            ui = torch.zeros(b, k_unf, dtype=torch.int64, device="cuda"); ud = torch.zeros(b, k_unf, device="cuda"); uc = torch.zeros(b, dtype=torch.int32, device="cuda")
+
+            def partial(r):
+                shards[r].search_filtered_partial_dev(Q.data_ptr(), ld, b, top_k, nprobe, filt, buf[r, 0].data_ptr(), buf[r, 1].data_ptr())
+
+            def merge():
+                IVFFlatIndex.merge_partials_dev(buf.data_ptr(), buf[0, 1].data_ptr(), 2 * b * top_k, W, b, top_k, nprobe, oi.data_ptr(), od.data_ptr(), oc.data_ptr())
+
+            def unsharded():
+                if F:
+                    whole.search_filtered_multi_dev(Q.data_ptr(), ld, b, top_k, nprobe, words.data_ptr(), words_h.shape[1], F, n, fo.data_ptr(), wi.data_ptr(), wd.data_ptr(),
+                                                    wc.data_ptr())
+                else:
+                    whole.search_filtered_dev(Q.data_ptr(), ld, b, top_k, nprobe, words.data_ptr(), n, wi.data_ptr(), wd.data_ptr(), wc.data_ptr())
+
+            def upartial(r):
+                shards[r].search_partial_dev(Q.data_ptr(), ld, b, k_unf, nprobe, ubuf[r, 0].data_ptr(), ubuf[r, 1].data_ptr())
+
+            def discard_tail():
+                """merge at top_k', the result to the host, the rows outside each query's bitmap dropped there -> wall ms"""
+                torch.cuda.synchronize()
+                t = time.perf_counter()
+                IVFFlatIndex.merge_partials_dev(ubuf.data_ptr(), ubuf[0, 1].data_ptr(), 2 * b * k_unf, W, b, k_unf, nprobe, ui.data_ptr(), ud.data_ptr(), uc.data_ptr())
+                ids = ui.cpu().numpy(); cnt = uc.cpu().numpy()
+                live = np.arange(k_unf)[None, :] < cnt[:, None]
+                m = np.stack(masks)[(fo_h if F else np.zeros(b, dtype=np.int32))[:, None], np.where(live, ids, 0)] & live
+                kept = [ids[q][m[q]][:top_k] for q in range(b)]
+                return (time.perf_counter() - t) * 1e3, float(np.mean([len(x) for x in kept]))
+
+            # warm-up of every shape; the merged partials are the unsharded call's rows
+            for r in range(W):
+                partial(r); upartial(r)
+            merge(); unsharded(); discard_tail()
+            for ix in shards + [whole]:
+                ix.poll()
+            torch.cuda.synchronize()
+            assert torch.equal(oc, wc), "counts of the merged partials and of the unsharded call differ"
+            live = torch.arange(top_k, device="cuda")[None, :] < oc[:, None]
+            assert bool(((oi == wi) | ~live).all()) and bool(((od.view(torch.int32) == wd.view(torch.int32)) | ~live).all()), "rows differ"
+            runs = {k: [] for k in ("partial", "merge", "sharded", "unsharded", "discard")}
+            kept_mean = 0.0
+            for _ in range(args.reps):
+                p = max(timed(lambda r=r: partial(r), [shards[r]]) for r in range(W))
+                mg = timed(merge, [])
+                runs["partial"].append(p); runs["merge"].append(mg); runs["sharded"].append(p + mg)
+                runs["unsharded"].append(timed(unsharded, [whole]))
+                up = max(timed(lambda r=r: upartial(r), [shards[r]]) for r in range(W))
+                tail, kept_mean = discard_tail()
+                runs["discard"].append(up + tail)
+            res[name] = {**{k: mms(v) for k, v in runs.items()}, "discard_top_k": k_unf, "discard_mean_kept": round(kept_mean, 2),
+                         "mean_count": round(float(oc.float().mean()), 2),
+                         "sharded_over_unsharded": round(float(np.median(runs["sharded"]) / np.median(runs["unsharded"])), 3),
+                         "discard_over_sharded": round(float(np.median(runs["discard"]) / np.median(runs["sharded"])), 2)}
+            log(f"[bench_filtered --shards {W}] batch {b} {name}: {json.dumps(res[name])}")
+        out[f"batch{b}"] = res
+    line = {"metric": f"vers_ivf_search_filtered_partial_dev + vers_topk_merge_dev in ms, {W} ranks emulated on one GPU, IVFFlat (N={n} d={d} nlist={nlist}) "
+                      f"nprobe={nprobe} top_k={top_k}", "build_s": round(t_build, 2), "reps": args.reps, **out}
+    for ix in shards + [whole]:
+        ix.close()
+    print(json.dumps(line), flush=True)
+    return 0
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", type=int, default=1_000_000)
@@ -563,8 +703,11 @@ def main():
     ap.add_argument("--nprobe-max", type=int, default=0, help="--adaptive: nprobe_max (0: nlist)")
     ap.add_argument("--multi-batches", default="64,1024", help="--multi: the batch sizes (multiples of 64); with --range too")
     ap.add_argument("--inner", type=int, default=8, help="--multi: back-to-back calls per timed window")
+    ap.add_argument("--shards", type=int, default=0, help="filtered search on an index sharded over this many ranks, emulated on one GPU (partials + merge): see shards_main")
     args = ap.parse_args()
     assert args.reps >= 5, "at least 5 alternating repeats per point"
+    if args.shards:
+        return shards_main(args)
     if args.adaptive:
         return adaptive_main(args)
     if args.range and args.multi:

@@ -167,10 +167,33 @@ SIGNATURES = {
     "vers_ivf_range_search_exhaustive_filtered_multi_dev": (C.c_int32, [_vp, _vp, C.c_uint64, C.c_uint32, _vp, C.c_uint32, C.c_uint32, _vp, C.c_uint64,
                                                                         C.c_uint32, C.c_uint64, _vp, _vp, _vp, _vp, C.c_uint64, C.POINTER(C.c_uint64),
                                                                         _vp]),
+    # filtered search on sharded handles: the filters always as (filters_dev, stride_words, n_filters, n_bits, filter_of_dev); vers_adaptive_t* as a pointer
+    "vers_ivf_filter_allowed_len_dev": (C.c_int32, [_vp, _vp, C.c_uint64, C.c_uint32, C.c_uint64, _vp, _vp]),
+    "vers_ivf_search_filtered_partial_dev": (C.c_int32, [_vp, _vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, _vp, C.c_uint64, C.c_uint32, C.c_uint64, _vp,
+                                                         _vp, _vp, _vp, _vp]),
+    "vers_ivf_search_exhaustive_filtered_partial_dev": (C.c_int32, [_vp, _vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, _vp, C.c_uint64, C.c_uint32,
+                                                                    C.c_uint64, _vp, _vp, _vp, _vp]),
+    "vers_ivf_search_filtered_sharded_dev": (C.c_int32, [_vp, _vp, _vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, _vp, C.c_uint64, C.c_uint32, C.c_uint64,
+                                                         _vp, _vp, _vp, _vp, _vp, _vp]),
+    "vers_ivf_search_exhaustive_filtered_sharded_dev": (C.c_int32, [_vp, _vp, _vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, _vp, C.c_uint64, C.c_uint32,
+                                                                    C.c_uint64, _vp, _vp, _vp, _vp, _vp]),
+    "vers_ivf_range_search_filtered_partial_dev": (C.c_int32, [_vp, _vp, C.c_uint64, C.c_uint32, _vp, C.c_uint32, C.c_uint32, _vp, C.c_uint64, C.c_uint32,
+                                                               C.c_uint64, _vp, _vp, _vp, _vp, C.c_uint64, C.POINTER(C.c_uint64), _vp]),
+    "vers_ivf_range_search_exhaustive_filtered_partial_dev": (C.c_int32, [_vp, _vp, C.c_uint64, C.c_uint32, _vp, C.c_uint32, C.c_uint32, _vp, C.c_uint64,
+                                                                          C.c_uint32, C.c_uint64, _vp, _vp, _vp, _vp, C.c_uint64, C.POINTER(C.c_uint64), _vp]),
+    "vers_ivf_range_search_filtered_sharded_dev": (C.c_int32, [_vp, _vp, _vp, C.c_uint64, C.c_uint32, _vp, C.c_uint32, C.c_uint32, _vp, C.c_uint64, C.c_uint32,
+                                                               C.c_uint64, _vp, _vp, _vp, _vp, C.c_uint64, C.POINTER(C.c_uint64), _vp]),
+    "vers_ivf_range_search_exhaustive_filtered_sharded_dev": (C.c_int32, [_vp, _vp, _vp, C.c_uint64, C.c_uint32, _vp, C.c_uint32, C.c_uint32, _vp, C.c_uint64,
+                                                                          C.c_uint32, C.c_uint64, _vp, _vp, _vp, _vp, C.c_uint64, C.POINTER(C.c_uint64), _vp]),
     "vers_kmeans_update": (C.c_int32, [C.c_int32, _vp, C.c_uint64, C.c_uint64, _vp, C.c_uint64, C.c_uint32, _vp]),
     "vers_kmeans_cost": (C.c_int32, [C.c_int32, _vp, C.c_uint64, C.c_uint64, _vp, C.c_uint64, C.c_uint64, _vp, C.c_uint32,
                                      C.POINTER(C.c_float)]),
 }
+
+
+class Adaptive(C.Structure):
+    """vers_adaptive_t: the adaptive depth of the filtered calls on sharded handles (a NULL pointer = plain depth)."""
+    _fields_ = [("nprobe_min", C.c_uint32), ("min_allowed", C.c_uint32), ("allowed_len_dev", C.c_void_p), ("out_nprobe_dev", C.c_void_p)]
 
 
 def _preload_hip_runtime():

@@ -9,6 +9,8 @@
 //                                    tile boundaries, a removal closes the gaps inside a list, slack and freed rows have mask bits 0)
 //   filter_multi_allowed_len_kernel  the same per bitmap, allowed_len[f * k + L], from the row_sets words: a wave per list, lane f keeps bitmap
 //                                    f's count, a tile costs one ballot per bitmap that has a row in it (tile_sets says which)
+//   allowed_len_rank_sum_kernel      a sharded handle: the ranks' counts (each rank counts the lists it stores, the others read 0) summed into
+//                                    the global ones, between the gather of the counts and the plan
 //   plan_queries_adaptive_kernel     plan_queries_kernel with a second running sum: next to the row count of the unfiltered walk (pj_pref: the
 //                                    sequence bases must stay those of the plain call) the allowed rows before each rank.  A rank the rule
 //                                    does not visit is written as kNoList and adds nothing to cnt; np[q] = P_q.
@@ -33,11 +35,17 @@ struct AdaptiveQ {
 
 constexpr int kAdpThreads = 256;  // four waves: a list (the count kernels) or a query (the plan) each
 
+// owner (nullable) / rank: a handle sharded by cluster counts the lists it stores; a list of another rank's is written as 0 and neither its
+// list_off (which means nothing here) nor a mask word is read.  Every list has one owner: the ranks' counts add up to the global ones.
 static __global__ __launch_bounds__(kAdpThreads) void filter_allowed_len_kernel(const uint64_t* tile_mask, const uint32_t* list_off, const uint32_t* list_len,
-                                                                               uint32_t k_lists, uint32_t* allowed_len) {
+                                                                               uint32_t k_lists, uint32_t* allowed_len, const uint8_t* owner, uint32_t rank) {
   const uint32_t L = blockIdx.x * (kAdpThreads / kWave) + (threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
   if (L >= k_lists) return;  // (whole waves)
+  if (owner != nullptr && (uint32_t)owner[L] != rank) {  // (wave-uniform)
+    if (lane == 0) allowed_len[L] = 0u;
+    return;
+  }
   const uint32_t n_tiles = (list_len[L] + kWave - 1) / kWave;
   const uint64_t* words = tile_mask + (n_tiles ? (list_off[L] >> 6) : 0u);
   uint32_t n = 0;
@@ -48,10 +56,14 @@ static __global__ __launch_bounds__(kAdpThreads) void filter_allowed_len_kernel(
 
 static __global__ __launch_bounds__(kAdpThreads) void filter_multi_allowed_len_kernel(const uint64_t* row_sets, const uint64_t* tile_sets, const uint32_t* list_off,
                                                                                      const uint32_t* list_len, uint32_t k_lists, uint32_t n_filters,
-                                                                                     uint32_t* allowed_len) {
+                                                                                     uint32_t* allowed_len, const uint8_t* owner, uint32_t rank) {
   const uint32_t L = blockIdx.x * (kAdpThreads / kWave) + (threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
   if (L >= k_lists) return;  // (whole waves)
+  if (owner != nullptr && (uint32_t)owner[L] != rank) {  // (wave-uniform; filter_allowed_len_kernel's guard)
+    if ((uint32_t)lane < n_filters) allowed_len[(uint64_t)lane * k_lists + L] = 0u;
+    return;
+  }
   const uint32_t n_tiles = (list_len[L] + kWave - 1) / kWave;
   const uint64_t t0 = n_tiles ? (uint64_t)(list_off[L] >> 6) : 0ull;
   uint32_t mine = 0;  // lane f: bitmap f's rows in the list
@@ -77,6 +89,16 @@ static __global__ __launch_bounds__(kAdpThreads) void filter_multi_allowed_len_k
   if ((uint32_t)lane < n_filters) allowed_len[(uint64_t)lane * k_lists + L] = mine;
 }
 
+// The allowed counts of a sharded handle's ranks, gathered as [world][n] (n = n_filters x k_lists), summed into the global ones: every list
+// has exactly one owner and the others wrote 0 for it, so the sum is that owner's count.
+static __global__ __launch_bounds__(kAdpThreads) void allowed_len_rank_sum_kernel(const uint32_t* gathered, uint32_t world, uint64_t n, uint32_t* out) {
+  const uint64_t i = (uint64_t)blockIdx.x * kAdpThreads + threadIdx.x;
+  if (i >= n) return;
+  uint32_t sum = 0;
+  for (uint32_t r = 0; r < world; ++r) sum += gathered[(uint64_t)r * n + i];
+  out[i] = sum;
+}
+
 // One chunk (64 probe ranks) of a query's adaptive plan: plan_query_chunk in nprobe mode with the depth rule in place of "every ranked list".
 // `carry` links the row counts of the chunks, `acarry` the allowed-row counts.
 __device__ __forceinline__ void plan_adaptive_chunk(const PlanQ& a, const AdaptiveQ& ad, const uint32_t* alen, uint32_t q, int lane, uint32_t c0, uint64_t key,
@@ -86,6 +108,7 @@ __device__ __forceinline__ void plan_adaptive_chunk(const PlanQ& a, const Adapti
   const uint32_t len = L != kNoList ? a.list_len[L] : 0u;
   const uint32_t slot = L != kNoList ? a.list_slot[L] : kNoList;
   const uint32_t al = (L != kNoList && alen != nullptr) ? alen[L] : 0u;
+  const uint32_t own = (a.owner != nullptr && L != kNoList) ? (uint32_t)a.owner[L] : a.rank;  // (plan_query_chunk's: with the lengths)
   const uint32_t inc = wave_incl_u32(len);
   const uint32_t pref = carry + inc - len;
   carry += (uint32_t)__builtin_amdgcn_readlane((int)inc, kWave - 1);
@@ -93,7 +116,9 @@ __device__ __forceinline__ void plan_adaptive_chunk(const PlanQ& a, const Adapti
   const uint32_t abefore = acarry + ainc - al;
   acarry += (uint32_t)__builtin_amdgcn_readlane((int)ainc, kWave - 1);
   const bool visited = L != kNoList && adaptive_rank_visited(j, abefore, ad.p_min, a.P, ad.min_allowed);
-  const bool scan = visited && len > 0 && a.top_k > 0;  // (lists the filter empties are scanned as the plain call scans them: the kernel skips their tiles)
+  // (lists the filter empties are scanned as the plain call scans them: the kernel skips their tiles.  Depth, pj_pref and np come from the
+  // GLOBAL lengths and allowed counts -- the same on every rank of a sharded handle --, the scan and cnt cover the lists this rank stores)
+  const bool scan = visited && len > 0 && a.top_k > 0 && own == a.rank;
   if (j < a.P) {
     a.pj_list[(uint64_t)q * a.P + j] = scan ? slot : kNoList;
     a.pj_pref[(uint64_t)q * a.P + j] = pref;

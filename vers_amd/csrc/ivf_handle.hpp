@@ -56,6 +56,7 @@ struct SearchWs {
   bool no_ahead = false;  // the plan of a filtered call neither consumes a look-ahead slot nor touches a pending request (plan_search)
   DevBuf rg_rlims;  // sharded range search: every rank's CSR limits [world][b + 1] (range_merge.hip.h); the gather itself goes through g_send / g_recv
   DevBuf g_send, g_recv;  // sharded search without the host in the loop: this rank's [2][b][top_k] partial | the world's
+  DevBuf g_cnt;  // an adaptive filtered call on a sharded handle: this rank's allowed counts [n] | the world's [world][n] | their sum [n], u32
   bool g_poisoned = false;  // g_send holds the poison mark of a locally failed batch (cleared before the next partial is written)
   static constexpr uint32_t kEvRing = 64;  // scan-launch timing ring (measurement hook)
   hipEvent_t ev0[kEvRing] = {}, ev1[kEvRing] = {};

@@ -573,10 +573,34 @@ struct FilterMultiSpec {
 };
 
 // An adaptive call's own arguments (filter_adaptive.hip.h): the call's nprobe is nprobe_max; out_nprobe is on the device, nullable.
+// On a handle sharded by cluster a rank counts the allowed rows of the lists it stores only, and the depth needs every list's:
+//   allowed_len  a partial call: the GLOBAL counts [n_filters or 1][k], the caller's (vers_ivf_filter_allowed_len_dev on every rank, summed);
+//                the count kernel is not run
+//   reduce       a sharded call: told this rank's counts (n words, on `st`), it exchanges them and names the global ones
 struct AdaptiveSpec {
   uint32_t nprobe_min, min_allowed;
   uint32_t* out_nprobe;
+  const uint32_t* allowed_len = nullptr;
+  std::function<int32_t(const uint32_t* local, size_t n, const uint32_t*& global, hipStream_t st)> reduce;
 };
+
+// allowed_len[f * k + L] of the call's mask(s) into `out` ([n_sets][k]): a record of the scan-timing ring of its own.  On a sharded handle the
+// lists this rank stores, 0 for the others (filter_adaptive.hip.h).
+static int32_t filter_count_allowed(vers_ivf* h, const FilterParams* f, const FilterMultiParams* fm, uint32_t n_sets, uint32_t* out, hipStream_t st) {
+  return timed_scan(st, [&]() -> int32_t {
+    if (h->k == 0) return VERS_OK;
+    const uint32_t blocks = (h->k + kAdpThreads / kWave - 1) / (kAdpThreads / kWave);
+    const uint8_t* owner = h->world > 1 ? h->owner.as<uint8_t>() : (const uint8_t*)nullptr;
+    if (fm)
+      hipLaunchKernelGGL(filter_multi_allowed_len_kernel, dim3(blocks), dim3(kAdpThreads), 0, st, fm->row_sets, fm->tile_sets, (const uint32_t*)h->list_off.as<uint32_t>(),
+                         (const uint32_t*)h->list_len.as<uint32_t>(), h->k, n_sets, out, owner, h->rank);
+    else
+      hipLaunchKernelGGL(filter_allowed_len_kernel, dim3(blocks), dim3(kAdpThreads), 0, st, f->tile_mask, (const uint32_t*)h->list_off.as<uint32_t>(),
+                         (const uint32_t*)h->list_len.as<uint32_t>(), h->k, out, owner, h->rank);
+    VERS_HIP_TRY(hipGetLastError());
+    return VERS_OK;
+  });
+}
 
 // filter_begin's twin for a filter per query: row_sets (8 bytes per storage row, whole tiles) and tile_sets (in the per-call mask's buffer)
 // over `n_rows` storage rows + the zeroed counters; the mask kernel inside the same bracket of the scan-timing ring.
@@ -682,7 +706,9 @@ int32_t exhaustive_dev_locked(vers_ivf* h, const float* q_dev, uint64_t ldq_in, 
 // per list are counted (a record of the scan-timing ring of its own, between the mask's and the passes'), and the plan is the adaptive one.
 int32_t filtered_dev_locked(vers_ivf* h, const float* q_dev, uint64_t ldq_in, uint32_t b, uint32_t top_k, uint32_t nprobe, const uint64_t* bits_dev,
                             uint64_t n_bits, uint64_t* out_ids, float* out_dist, uint32_t* out_count, hipStream_t st, const FilterMultiSpec* multi = nullptr,
-                            const AdaptiveSpec* adaptive = nullptr) {
+                            const AdaptiveSpec* adaptive = nullptr, uint64_t* out_keys = nullptr) {
+  // out_keys: a rank's PARTIAL (search_dev_locked's: the merge stores the keys beside the ids, kKeyMax padded); top_k >= 1 then.  The handle
+  // may be sharded by cluster: the plan scans the lists this rank stores, sequence numbers run over the global lengths.
   if (b == 0) return VERS_OK;
   if (top_k == 0) {
     VERS_HIP_TRY(hipMemsetAsync(out_count, 0, sizeof(uint32_t) * b, st));
@@ -696,20 +722,15 @@ int32_t filtered_dev_locked(vers_ivf* h, const float* q_dev, uint64_t ldq_in, ui
   AdaptiveQ aq;
   if (adaptive) {
     const uint32_t n_sets = multi ? multi->n_filters : 1u;
-    if (int32_t rc = W->flt_alen.reserve((size_t)n_sets * h->k * sizeof(uint32_t))) return rc;
-    aq.p_min = std::min<uint32_t>(adaptive->nprobe_min, h->k); aq.min_allowed = adaptive->min_allowed; aq.allowed_len = W->flt_alen.as<uint32_t>();
+    aq.p_min = std::min<uint32_t>(adaptive->nprobe_min, h->k); aq.min_allowed = adaptive->min_allowed; aq.allowed_len = adaptive->allowed_len;
     aq.filter_of = multi ? multi->filter_of : (const uint32_t*)nullptr; aq.n_filters = n_sets; aq.out_nprobe = adaptive->out_nprobe;
-    if (int32_t rc = timed_scan(st, [&]() -> int32_t {
-          const uint32_t blocks = (h->k + kAdpThreads / kWave - 1) / (kAdpThreads / kWave);
-          if (multi)
-            hipLaunchKernelGGL(filter_multi_allowed_len_kernel, dim3(blocks), dim3(kAdpThreads), 0, st, fm.row_sets, fm.tile_sets, (const uint32_t*)h->list_off.as<uint32_t>(),
-                               (const uint32_t*)h->list_len.as<uint32_t>(), h->k, n_sets, W->flt_alen.as<uint32_t>());
-          else
-            hipLaunchKernelGGL(filter_allowed_len_kernel, dim3(blocks), dim3(kAdpThreads), 0, st, f.tile_mask, (const uint32_t*)h->list_off.as<uint32_t>(),
-                               (const uint32_t*)h->list_len.as<uint32_t>(), h->k, W->flt_alen.as<uint32_t>());
-          VERS_HIP_TRY(hipGetLastError());
-          return VERS_OK;
-        })) return rc;
+    if (aq.allowed_len == nullptr) {  // (a partial call brings the global counts: nothing to count)
+      if (int32_t rc = W->flt_alen.reserve((size_t)n_sets * h->k * sizeof(uint32_t))) return rc;
+      if (int32_t rc = filter_count_allowed(h, multi ? nullptr : &f, multi ? &fm : nullptr, n_sets, W->flt_alen.as<uint32_t>(), st)) return rc;
+      aq.allowed_len = W->flt_alen.as<uint32_t>();
+      if (adaptive->reduce)
+        if (int32_t rc = adaptive->reduce(W->flt_alen.as<uint32_t>(), (size_t)n_sets * h->k, aq.allowed_len, st)) return rc;
+    }
   }
   SearchPlan s;
   W->no_ahead = true;
@@ -718,7 +739,7 @@ int32_t filtered_dev_locked(vers_ivf* h, const float* q_dev, uint64_t ldq_in, ui
   if (prc) return prc;
   { const int ev = scan_events_ref().load(); W->ev_on = ev == 1 || ev == 2; }  // (the plan set it for an unfiltered call)
   W->tot_valid = true;
-  if (int32_t rc = run_chain_passes(h, s, b, top_k, out_ids, out_dist, out_count, nullptr, /*unfiltered=*/false, st, [&](const uint64_t* lower) -> int32_t {
+  if (int32_t rc = run_chain_passes(h, s, b, top_k, out_ids, out_dist, out_count, out_keys, /*unfiltered=*/false, st, [&](const uint64_t* lower) -> int32_t {
         return with_qg<1, 8, 16>(s.QG, [&](auto qg) -> int32_t {
           return launch_ivf_scan(h, make_ivf_src<decltype(qg)::value>(h, s, 0u), (uint32_t)s.items_bound, st, lower, flt);
         });
@@ -730,7 +751,10 @@ int32_t filtered_dev_locked(vers_ivf* h, const float* q_dev, uint64_t ldq_in, ui
 // the segment length here as it does for the chains.  An index without centroids (a streamed upload in progress included) is scanned as zero
 // rows: counts 0.
 int32_t exhaustive_filtered_dev_locked(vers_ivf* h, const float* q_dev, uint64_t ldq_in, uint32_t b, uint32_t top_k, uint32_t metric, const uint64_t* bits_dev,
-                                       uint64_t n_bits, uint64_t* out_ids, float* out_dist, uint32_t* out_count, hipStream_t st, const FilterMultiSpec* multi = nullptr) {
+                                       uint64_t n_bits, uint64_t* out_ids, float* out_dist, uint32_t* out_count, hipStream_t st, const FilterMultiSpec* multi = nullptr,
+                                       uint64_t* out_keys = nullptr, uint64_t* out_key_ids = nullptr) {
+  // out_keys / out_key_ids: a rank's PARTIAL as well -- (distance bits << 32) | vec id beside the ids, kKeyMax padded, packed from the local
+  // result (out_ids / out_dist / out_count are then the caller's scratch); top_k >= 1 then
   if (b == 0) return VERS_OK;
   if (top_k == 0) {
     VERS_HIP_TRY(hipMemsetAsync(out_count, 0, sizeof(uint32_t) * b, st));
@@ -742,6 +766,12 @@ int32_t exhaustive_filtered_dev_locked(vers_ivf* h, const float* q_dev, uint64_t
   if (int32_t rc = multi ? filter_multi_begin(h, bits_dev, n_bits, *multi, n_rows, st, fm) : filter_begin(h, bits_dev, n_bits, n_rows, st, f)) return rc;
   const FilterChoice flt{multi ? nullptr : &f, multi ? &fm : nullptr};
   if (int32_t rc = run_exhaustive_passes(h, q_dev, ldq_in, b, top_k, metric, n_rows, knobs().seg_rows, flt, out_ids, out_dist, out_count, st)) return rc;
+  if (out_keys != nullptr) {
+    const size_t part = (size_t)b * top_k;
+    hipLaunchKernelGGL(pack_exhaustive_keys_kernel, dim3((unsigned)((part + 255) / 256)), dim3(256), 0, st, (const uint64_t*)out_ids, (const float*)out_dist,
+                       (const uint32_t*)out_count, b, top_k, out_keys, out_key_ids);
+    VERS_HIP_TRY(hipGetLastError());
+  }
   return filter_end(h, st);
 }
 
@@ -750,7 +780,7 @@ static int32_t filter_check(vers_ivf* h, const char* who, bool probed, uint32_t 
   if (n_bits != 0 && bits == nullptr) return fail(VERS_ERR_INVALID, std::string(who) + ": n_bits > 0 with a NULL bitmap");
   if (probed && nprobe == 0)
     return fail(VERS_ERR_INVALID, std::string(who) + ": nprobe must be at least 1 (the reference's spill walk depends on the filtered list lengths: out of scope)");
-  if (h->world > 1) return fail(VERS_ERR_INVALID, std::string(who) + ": the handle is sharded by cluster; filtered search on a sharded handle is out of scope");
+  if (h->world > 1) return fail(VERS_ERR_INVALID, std::string(who) + ": the handle is sharded by cluster; filtered search on a sharded handle is out of scope for this call (use vers_ivf_search_filtered_sharded_dev / vers_ivf_search_exhaustive_filtered_sharded_dev, or the _filtered_partial_dev calls + vers_topk_merge_dev)");
   if (probed && h->k == 0) return fail(VERS_ERR_INSUFFICIENT, "search on an index without centroids (reference: index out of bounds, ivfflat.rs:169)");
   return VERS_OK;
 }
@@ -998,7 +1028,7 @@ static int32_t launch_filter_range_pass(vers_ivf* h, int metric, const Src& src,
 // ProbedRangeSource behind a filter: the mask kernel (with its record in the scan-timing ring) opens the first phase, the plan is the
 // unfiltered one (the lists are ranked as without a filter) but neither consumes nor starts a look-ahead, both passes run the filtered kernel.
 struct FilteredProbedRangeSource : ProbedRangeSource {
-  static constexpr bool kPartials = false;
+  static constexpr bool kPartials = true;  // (a rank's partial of the _filtered_partial / _filtered_sharded calls)
   const char* who = "vers_ivf_range_search_filtered";
   const uint64_t* bits_dev; uint64_t n_bits;
   FilterParams f{};
@@ -1024,7 +1054,7 @@ struct FilteredProbedRangeSource : ProbedRangeSource {
 
 // StoredRangeSource behind a filter: the mask covers the rows the scan covers (none on an index without centroids).
 struct FilteredStoredRangeSource : StoredRangeSource {
-  static constexpr bool kPartials = false;
+  static constexpr bool kPartials = true;  // (a rank's partial of the _filtered_partial / _filtered_sharded calls)
   const char* who = "vers_ivf_range_search_exhaustive_filtered";
   const uint64_t* bits_dev; uint64_t n_bits;
   FilterParams f{};
@@ -1047,17 +1077,20 @@ struct FilteredStoredRangeSource : StoredRangeSource {
 };
 
 // A filtered range search on the index, on `st`: mask kernel + counters, the range protocol, the counters folded.  A call that fails leaves
-// vers_ivf_filter_stats where it was.
+// vers_ivf_filter_stats where it was.  part: a rank's partial ((key, id) pairs, range_search_run); who: the entry point's name when it is not
+// the source's own.
 int32_t range_filtered_dev_locked(vers_ivf* h, bool probed, const float* q_dev, uint64_t ldq_in, uint32_t b, const float* radius_dev, uint32_t nprobe_or_metric,
                                   uint32_t flags, const uint64_t* bits_dev, uint64_t n_bits, uint64_t* lims_dev, uint64_t* ids_dev, float* dist_dev, uint64_t cap,
-                                  bool own_out, uint64_t* out_total, hipStream_t st) {
+                                  bool own_out, uint64_t* out_total, hipStream_t st, RangePartial* part = nullptr, const char* who = nullptr) {
   if (probed) {
     FilteredProbedRangeSource src(h, q_dev, ldq_in, b, nprobe_or_metric, bits_dev, n_bits);
-    if (int32_t rc = range_search_run(src, W->rg, b, radius_dev, flags, lims_dev, ids_dev, dist_dev, cap, own_out, out_total, st)) return rc;
+    if (who) src.who = who;
+    if (int32_t rc = range_search_run(src, W->rg, b, radius_dev, flags, lims_dev, ids_dev, dist_dev, cap, own_out, out_total, st, part)) return rc;
     return filter_end(h, st);
   }
   FilteredStoredRangeSource src(h, q_dev, ldq_in, b, nprobe_or_metric, bits_dev, n_bits);
-  if (int32_t rc = range_search_run(src, W->rg, b, radius_dev, flags, lims_dev, ids_dev, dist_dev, cap, own_out, out_total, st)) return rc;
+  if (who) src.who = who;
+  if (int32_t rc = range_search_run(src, W->rg, b, radius_dev, flags, lims_dev, ids_dev, dist_dev, cap, own_out, out_total, st, part)) return rc;
   return filter_end(h, st);
 }
 
@@ -1073,7 +1106,7 @@ static int32_t launch_filter_range_multi_pass(vers_ivf* h, int metric, const Src
 
 // FilteredProbedRangeSource with a filter per query: filter_multi_begin's mask kernel opens the first phase, both passes run the per-query kernel.
 struct FilteredMultiProbedRangeSource : ProbedRangeSource {
-  static constexpr bool kPartials = false;
+  static constexpr bool kPartials = true;  // (a rank's partial of the _filtered_partial / _filtered_sharded calls)
   const char* who = "vers_ivf_range_search_filtered_multi";
   const uint64_t* bits_dev; uint64_t n_bits;
   FilterMultiSpec ms;
@@ -1100,7 +1133,7 @@ struct FilteredMultiProbedRangeSource : ProbedRangeSource {
 
 // FilteredStoredRangeSource with a filter per query: the sets cover the rows the scan covers (none on an index without centroids).
 struct FilteredMultiStoredRangeSource : StoredRangeSource {
-  static constexpr bool kPartials = false;
+  static constexpr bool kPartials = true;  // (a rank's partial of the _filtered_partial / _filtered_sharded calls)
   const char* who = "vers_ivf_range_search_exhaustive_filtered_multi";
   const uint64_t* bits_dev; uint64_t n_bits;
   FilterMultiSpec ms;
@@ -1127,14 +1160,17 @@ struct FilteredMultiStoredRangeSource : StoredRangeSource {
 // where it was.
 int32_t range_filtered_multi_dev_locked(vers_ivf* h, bool probed, const float* q_dev, uint64_t ldq_in, uint32_t b, const float* radius_dev, uint32_t nprobe_or_metric,
                                         uint32_t flags, const uint64_t* bits_dev, uint64_t n_bits, const FilterMultiSpec& ms, uint64_t* lims_dev, uint64_t* ids_dev,
-                                        float* dist_dev, uint64_t cap, bool own_out, uint64_t* out_total, hipStream_t st) {
+                                        float* dist_dev, uint64_t cap, bool own_out, uint64_t* out_total, hipStream_t st, RangePartial* part = nullptr,
+                                        const char* who = nullptr) {
   if (probed) {
     FilteredMultiProbedRangeSource src(h, q_dev, ldq_in, b, nprobe_or_metric, bits_dev, n_bits, ms);
-    if (int32_t rc = range_search_run(src, W->rg, b, radius_dev, flags, lims_dev, ids_dev, dist_dev, cap, own_out, out_total, st)) return rc;
+    if (who) src.who = who;
+    if (int32_t rc = range_search_run(src, W->rg, b, radius_dev, flags, lims_dev, ids_dev, dist_dev, cap, own_out, out_total, st, part)) return rc;
     return filter_end(h, st);
   }
   FilteredMultiStoredRangeSource src(h, q_dev, ldq_in, b, nprobe_or_metric, bits_dev, n_bits, ms);
-  if (int32_t rc = range_search_run(src, W->rg, b, radius_dev, flags, lims_dev, ids_dev, dist_dev, cap, own_out, out_total, st)) return rc;
+  if (who) src.who = who;
+  if (int32_t rc = range_search_run(src, W->rg, b, radius_dev, flags, lims_dev, ids_dev, dist_dev, cap, own_out, out_total, st, part)) return rc;
   return filter_end(h, st);
 }
 
@@ -1143,7 +1179,7 @@ static int32_t range_filter_check(vers_ivf* h, const char* who, bool probed, uin
   if (flags & ~VERS_RANGE_WALK_ORDER) return fail(VERS_ERR_INVALID, std::string(who) + ": unknown flag bits");
   if (n_bits != 0 && bits == nullptr) return fail(VERS_ERR_INVALID, std::string(who) + ": n_bits > 0 with a NULL bitmap");
   if (probed && nprobe == 0) return fail(VERS_ERR_INVALID, std::string(who) + ": nprobe must be at least 1 (the reference's spill walk is defined by top_k: it has no range meaning)");
-  if (h->world > 1) return fail(VERS_ERR_INVALID, std::string(who) + ": the handle is sharded by cluster; filtered range search on a sharded handle is out of scope");
+  if (h->world > 1) return fail(VERS_ERR_INVALID, std::string(who) + ": the handle is sharded by cluster; filtered range search on a sharded handle is out of scope for this call (use vers_ivf_range_search_filtered_sharded_dev / vers_ivf_range_search_exhaustive_filtered_sharded_dev, or the _filtered_partial_dev calls + vers_range_merge_dev)");
   if (probed && h->k == 0) return fail(VERS_ERR_INSUFFICIENT, "range search on an index without centroids (reference: index out of bounds, ivfflat.rs:169)");
   return VERS_OK;
 }
@@ -1316,21 +1352,29 @@ int32_t vers_ivf_search_partial_dev(vers_ivf_t* h, const float* queries_dev, uin
                            out_keys_dev, (hipStream_t)stream);
 }
 
-// partial search / partial exhaustive scan -> the one exchange -> merge, all on `stream` (vers_hip.h: vers_gather_t)
-static int32_t sharded_common(vers_ivf_t* h, const vers_gather_t* g, const float* queries_dev, uint64_t ldq_floats, uint32_t b, uint32_t top_k,
-                              uint32_t nprobe, int exhaustive_metric, uint64_t* out_ids_dev, float* out_dist_dev, uint32_t* out_count_dev, void* stream) {
-  const char* who = exhaustive_metric >= 0 ? "vers_ivf_search_exhaustive_sharded_dev" : "vers_ivf_search_sharded_dev";
+// A sharded top-k call, all on `stream` (vers_hip.h: vers_gather_t): the local part -> the one exchange -> merge.  What differs between the
+// calls is theirs to say:
+//   check    under the handle's shared lock, before anything is reserved or exchanged: what the call refuses from its arguments and the handle
+//   local    this rank's partial -- keys | ids, [b * top_k] each, kKeyMax padded -- written on `st` by whatever search the call is
+//   count_words != 0: an ADAPTIVE filtered call, which exchanges twice.  Its local part hands `reduce` this rank's allowed counts (count_words
+//            u32, on the device) between its count kernel and its plan: they are all-gathered on the stream, summed over the ranks on the device
+//            and the global counts named.  A rank that fails locally before that point still joins the first gather, with zeros.
+using ShardReduce = std::function<int32_t(const uint32_t* local, size_t n, const uint32_t*& global, hipStream_t st)>;
+extern "C++" {  // (a template has no C linkage)
+template <class Check, class Local>
+static int32_t sharded_topk_run(vers_ivf_t* h, const char* who, const vers_gather_t* g, const float* queries_dev, uint64_t ldq_floats, uint32_t b, uint32_t top_k, int ref_mode,
+                                const size_t& count_words /* read behind check(), which may set it from the locked handle */, uint64_t* out_ids_dev, float* out_dist_dev, uint32_t* out_count_dev, void* stream, Check&& check, Local&& local) {
   if (!h) return fail(VERS_ERR_INVALID, "null handle");
   if (top_k == 0) return fail(VERS_ERR_INVALID, std::string(who) + ": top_k must be at least 1");
   if (b && (!queries_dev || ldq_floats < h->d || !out_ids_dev || !out_dist_dev || !out_count_dev))
     return fail(VERS_ERR_INVALID, std::string(who) + ": bad arguments");
-  if (exhaustive_metric > (int)VERS_METRIC_COSDIST) return fail(VERS_ERR_INVALID, "unknown metric");
   const uint32_t world = g ? g->world : 1u;
   if (g && (g->world == 0 || g->rank >= g->world || (g->world > 1 && !g->all_gather_async))) return fail(VERS_ERR_INVALID, std::string(who) + ": incomplete vers_gather_t");
   if (b == 0) return VERS_OK;
   std::shared_lock<std::shared_mutex> lk(h->index);
   if (world != h->world || (g && world > 1 && g->rank != h->rank))
     return fail(VERS_ERR_INVALID, std::string(who) + ": the handle is sharded as rank " + std::to_string(h->rank) + " of " + std::to_string(h->world) + ", the exchange says otherwise");
+  if (int32_t rc = check()) return rc;
   DeviceGuard gd(h->device);
   hipStream_t st = (hipStream_t)stream;
   WsLease lease(h, true, st);
@@ -1344,6 +1388,7 @@ static int32_t sharded_common(vers_ivf_t* h, const vers_gather_t* g, const float
   {
     int32_t rc = W->g_send.reserve(2 * part * sizeof(uint64_t));
     if (!rc) rc = W->g_recv.reserve((size_t)world * 2 * part * sizeof(uint64_t));
+    if (!rc && count_words) rc = W->g_cnt.reserve(((size_t)world + 2) * count_words * sizeof(uint32_t));  // this rank's | the world's | their sum
     if (rc) {
       if (exchange && world > 1)
         fail(rc, std::string(who) + ": the exchange buffers could not be reserved -- this rank cannot join the batch's all-gather; abort the communicator (" + vers_last_error() + ")");
@@ -1353,7 +1398,28 @@ static int32_t sharded_common(vers_ivf_t* h, const vers_gather_t* g, const float
   // (no exchange -- g == nullptr, a single process: the partial is the gathered buffer.  A one-rank communicator still gathers:
   // the call is the same code path as with peers, which is how the RCCL leg is tested on a one-GPU box)
   uint64_t* mine = exchange ? W->g_send.as<uint64_t>() : W->g_recv.as<uint64_t>();
-  // From here on a LOCAL failure (scratch reservation, a failed launch) must not skip the batch's ONLY collective: the peers have
+  // The adaptive call's first exchange: exactly once per call, on every way through it.
+  bool counted = false;
+  int32_t gather_rc = VERS_OK;  // a callback that failed: nothing more is exchanged
+  ShardReduce reduce = [&](const uint32_t* counts, size_t n, const uint32_t*& global, hipStream_t) -> int32_t {
+    counted = true;
+    uint32_t* send = W->g_cnt.as<uint32_t>();
+    uint32_t* recv = send + count_words;
+    uint32_t* sum = recv + (size_t)world * count_words;
+    if (counts != nullptr && n == count_words) VERS_HIP_TRY(hipMemcpyAsync(exchange ? send : recv, counts, n * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
+    else VERS_HIP_TRY(hipMemsetAsync(exchange ? send : recv, 0, count_words * sizeof(uint32_t), st));  // (a rank that failed: it adds nothing)
+    if (exchange)
+      if (int32_t rc = g->all_gather_async(g->ctx, send, recv, count_words * sizeof(uint32_t), stream)) {
+        gather_rc = rc;
+        return fail(VERS_ERR_COMM, "vers_gather_t::all_gather_async reported failure (status " + std::to_string(rc) + ")");
+      }
+    hipLaunchKernelGGL(allowed_len_rank_sum_kernel, dim3((unsigned)((count_words + kAdpThreads - 1) / kAdpThreads)), dim3(kAdpThreads), 0, st, (const uint32_t*)recv, world,
+                       (uint64_t)count_words, sum);
+    VERS_HIP_TRY(hipGetLastError());
+    global = sum;
+    return VERS_OK;
+  };
+  // From here on a LOCAL failure (scratch reservation, a failed launch) must not skip the batch's collectives: the peers have
   // already queued their ncclAllGather and would block forever, and every later collective on the communicator would be
   // mismatched.  The rank answers with a POISONED partial instead -- every key kKeyMax (it contributes nothing), first id word
   // kPoisonId -- so that the gather completes everywhere; every rank's merge sees the mark and latches kStPeerFailed in its
@@ -1364,18 +1430,15 @@ static int32_t sharded_common(vers_ivf_t* h, const vers_gather_t* g, const float
     W->g_poisoned = false;
   }
   if (test_fail_sharded_ref().load() > 0 && test_fail_sharded_ref().fetch_sub(1) > 0) local_rc = fail(VERS_ERR_HIP, std::string(who) + ": injected local failure (test hook)");
-  if (!local_rc) local_rc = [&]() -> int32_t {
-    if (int32_t rc = ensure_out(h, part, b)) return rc;
-    if (exhaustive_metric >= 0) {
-      if (int32_t rc = exhaustive_dev_locked(h, queries_dev, ldq_floats, b, top_k, (uint32_t)exhaustive_metric, W->o_ids.as<uint64_t>(), W->o_dist.as<float>(),
-                                             W->o_cnt.as<uint32_t>(), st)) return rc;
-      hipLaunchKernelGGL(pack_exhaustive_keys_kernel, dim3((unsigned)((part + 255) / 256)), dim3(256), 0, st, (const uint64_t*)W->o_ids.as<uint64_t>(),
-                         (const float*)W->o_dist.as<float>(), (const uint32_t*)W->o_cnt.as<uint32_t>(), b, top_k, mine, mine + part);
-      VERS_HIP_TRY(hipGetLastError());
-      return VERS_OK;
-    }
-    return search_dev_locked(h, queries_dev, ldq_floats, b, top_k, nprobe, mine + part, W->o_dist.as<float>(), W->o_cnt.as<uint32_t>(), mine, st);
-  }();
+  if (!local_rc) local_rc = local(mine, mine + part, reduce, st);
+  if (count_words && !counted && exchange) {  // the local part did not get as far as its counts: zeros, so that the peers' first gather completes
+    const std::string why = local_rc ? std::string(vers_last_error()) : std::string();
+    const uint32_t* unused = nullptr;
+    const int32_t crc = reduce(nullptr, 0, unused, st);
+    if (local_rc) fail(local_rc, why);
+    else local_rc = crc;
+  }
+  if (gather_rc) return local_rc;
   if (local_rc && !exchange) return local_rc;
   if (local_rc) {  // (stream order: behind whatever the failed search had already queued into `mine`)
     const std::string why = vers_last_error();
@@ -1391,11 +1454,37 @@ static int32_t sharded_common(vers_ivf_t* h, const vers_gather_t* g, const float
       return local_rc ? local_rc : fail(VERS_ERR_COMM, "vers_gather_t::all_gather_async reported failure (status " + std::to_string(rc) + ")");
   }
   hipLaunchKernelGGL(rank_merge_kernel, dim3(b), dim3(kWave), 0, st, (const uint64_t*)W->g_recv.as<uint64_t>(), (const uint64_t*)W->g_recv.as<uint64_t>() + part,
-                     (uint64_t)(2 * part), world, b, top_k, (exhaustive_metric < 0 && nprobe == 0) ? 1 : 0, out_ids_dev, out_dist_dev, out_count_dev,
+                     (uint64_t)(2 * part), world, b, top_k, ref_mode, out_ids_dev, out_dist_dev, out_count_dev,
                      exchange ? W->st_word() : (uint32_t*)nullptr);
   if (local_rc) { (void)hipGetLastError(); return local_rc; }
   VERS_HIP_TRY(hipGetLastError());
   return VERS_OK;
+}
+
+}  // extern "C++"
+
+// the two unfiltered sharded calls: the local part is the partial search / the partial exhaustive scan
+static int32_t sharded_common(vers_ivf_t* h, const vers_gather_t* g, const float* queries_dev, uint64_t ldq_floats, uint32_t b, uint32_t top_k,
+                              uint32_t nprobe, int exhaustive_metric, uint64_t* out_ids_dev, float* out_dist_dev, uint32_t* out_count_dev, void* stream) {
+  const char* who = exhaustive_metric >= 0 ? "vers_ivf_search_exhaustive_sharded_dev" : "vers_ivf_search_sharded_dev";
+  if (exhaustive_metric > (int)VERS_METRIC_COSDIST) return fail(VERS_ERR_INVALID, "unknown metric");
+  const size_t part = (size_t)b * top_k;
+  const size_t no_counts = 0;
+  return sharded_topk_run(
+      h, who, g, queries_dev, ldq_floats, b, top_k, (exhaustive_metric < 0 && nprobe == 0) ? 1 : 0, no_counts, out_ids_dev, out_dist_dev, out_count_dev, stream,
+      []() -> int32_t { return VERS_OK; },
+      [&](uint64_t* keys, uint64_t* ids, const ShardReduce&, hipStream_t st) -> int32_t {
+        if (int32_t rc = ensure_out(h, part, b)) return rc;
+        if (exhaustive_metric >= 0) {
+          if (int32_t rc = exhaustive_dev_locked(h, queries_dev, ldq_floats, b, top_k, (uint32_t)exhaustive_metric, W->o_ids.as<uint64_t>(), W->o_dist.as<float>(),
+                                                 W->o_cnt.as<uint32_t>(), st)) return rc;
+          hipLaunchKernelGGL(pack_exhaustive_keys_kernel, dim3((unsigned)((part + 255) / 256)), dim3(256), 0, st, (const uint64_t*)W->o_ids.as<uint64_t>(),
+                             (const float*)W->o_dist.as<float>(), (const uint32_t*)W->o_cnt.as<uint32_t>(), b, top_k, keys, ids);
+          VERS_HIP_TRY(hipGetLastError());
+          return VERS_OK;
+        }
+        return search_dev_locked(h, queries_dev, ldq_floats, b, top_k, nprobe, ids, W->o_dist.as<float>(), W->o_cnt.as<uint32_t>(), keys, st);
+      });
 }
 
 int32_t vers_ivf_search_sharded_dev(vers_ivf_t* h, const vers_gather_t* g, const float* queries_dev, uint64_t ldq_floats, uint32_t b, uint32_t top_k,
@@ -2148,15 +2237,19 @@ int32_t vers_range_merge_dev(const uint64_t* keys_dev, const uint64_t* ids_dev, 
 }
 
 // local count -> exchange 1 (counts + status: the agreement round) -> local fill into the send buffer -> exchange 2 (keys | ids, padded to
-// the largest rank) -> merge.  exhaustive_metric < 0: the probed lists.
-static int32_t range_sharded_common(vers_ivf_t* h, const vers_comm_t* comm, const float* queries_dev, uint64_t ldq_floats, uint32_t b, const float* radius_dev,
-                                    uint32_t nprobe, int exhaustive_metric, uint32_t flags, uint64_t* out_lims_dev, uint64_t* out_ids_dev, float* out_dist_dev,
-                                    uint64_t cap, uint64_t* out_total, void* stream) {
-  const std::string who = exhaustive_metric >= 0 ? "vers_ivf_range_search_exhaustive_sharded_dev" : "vers_ivf_range_search_sharded_dev";
+// the largest rank) -> merge.  What differs between the sharded range calls is theirs to say:
+//   key_ids  the sort key's low word is the vec id (the exhaustive calls: keys alone are sorted) -- sizes the sort's scratch
+//   check    under the handle's shared lock, before any exchange: what the call refuses from its arguments and the handle
+//   local    the rank's partial range call (range_search_run with `part`): count pass, part->decide, fill pass, on `st`
+extern "C++" {  // (a template has no C linkage)
+template <class Check, class Local>
+static int32_t range_sharded_run(vers_ivf_t* h, const char* who_c, const vers_comm_t* comm, const float* queries_dev, uint64_t ldq_floats, uint32_t b, const float* radius_dev,
+                                 bool key_ids, uint32_t flags, uint64_t* out_lims_dev, uint64_t* out_ids_dev, float* out_dist_dev, uint64_t cap, uint64_t* out_total,
+                                 void* stream, Check&& check, Local&& local) {
+  const std::string who = who_c;
   if (!h) return fail(VERS_ERR_INVALID, "null handle");
   if (!out_total) return fail(VERS_ERR_INVALID, who + ": out_total is required");
   *out_total = 0;
-  if (exhaustive_metric > (int)VERS_METRIC_COSDIST) return fail(VERS_ERR_INVALID, "unknown metric");
   if (b && (!queries_dev || ldq_floats < h->d || !radius_dev || !out_lims_dev || (cap && (!out_ids_dev || !out_dist_dev)))) return fail(VERS_ERR_INVALID, who + ": bad arguments");
   if (comm && (comm->world == 0 || comm->rank >= comm->world || comm->world > 65535u || !comm->all_gather)) return fail(VERS_ERR_INVALID, who + ": incomplete vers_comm_t");
   if (b == 0) return VERS_OK;
@@ -2164,7 +2257,7 @@ static int32_t range_sharded_common(vers_ivf_t* h, const vers_comm_t* comm, cons
   const uint32_t world = comm ? comm->world : 1u;
   if (world != h->world || (comm && world > 1 && comm->rank != h->rank))
     return fail(VERS_ERR_INVALID, who + ": the handle is sharded as rank " + std::to_string(h->rank) + " of " + std::to_string(h->world) + ", the communicator says otherwise");
-  if (int32_t rc = exhaustive_metric >= 0 ? range_exhaustive_check(h, who.c_str(), flags, true) : range_check(h, who.c_str(), nprobe, flags, true)) return rc;
+  if (int32_t rc = check()) return rc;
   DeviceGuard gd(h->device);
   hipStream_t st = (hipStream_t)stream;
   WsLease lease(h, true, st);
@@ -2233,7 +2326,7 @@ static int32_t range_sharded_common(vers_ivf_t* h, const vers_comm_t* comm, cons
     if (total != 0 && total <= cap) {  // the fill's staging BEFORE the agreement: scratch that does not fit is a status the peers learn
       lrc = W->rg.stage.reserve(2 * (size_t)total * sizeof(uint64_t));
       if (!lrc && !(flags & VERS_RANGE_WALK_ORDER))
-        lrc = W->rg.tmp.reserve(exhaustive_metric >= 0 ? range_sort_keys_temp_bytes((uint32_t)total, b) : range_sort_temp_bytes((uint32_t)total, b));
+        lrc = W->rg.tmp.reserve(key_ids ? range_sort_keys_temp_bytes((uint32_t)total, b) : range_sort_temp_bytes((uint32_t)total, b));
     }
     if (int32_t rc = exchange1(lrc, true)) return rc;
     go = false;
@@ -2253,9 +2346,7 @@ static int32_t range_sharded_common(vers_ivf_t* h, const vers_comm_t* comm, cons
   if (test_fail_sharded_ref().load() > 0 && test_fail_sharded_ref().fetch_sub(1) > 0) rc = fail(VERS_ERR_HIP, who + ": injected local failure (test hook)");
   if (!rc) {
     rc = W->rg_lims.reserve(nw * sizeof(uint64_t));
-    if (!rc)
-      rc = range_dev_locked(h, exhaustive_metric < 0, queries_dev, ldq_floats, b, radius_dev, exhaustive_metric >= 0 ? (uint32_t)exhaustive_metric : nprobe, flags,
-                            W->rg_lims.as<uint64_t>(), nullptr, nullptr, cap, false, &local_total, st, &part);
+    if (!rc) rc = local(W->rg_lims.as<uint64_t>(), &local_total, st, &part);
   }
   if (!agreed) {  // the local count did not get as far as the agreement: enter it with the failure
     const int32_t arc = exchange1(rc ? rc : fail(VERS_ERR_HIP, who + ": the local count ended without a verdict"), false);
@@ -2279,6 +2370,23 @@ static int32_t range_sharded_common(vers_ivf_t* h, const vers_comm_t* comm, cons
   return VERS_OK;
 }
 
+}  // extern "C++"
+
+// the two unfiltered sharded range calls: the local part is the partial range call.  exhaustive_metric < 0: the probed lists.
+static int32_t range_sharded_common(vers_ivf_t* h, const vers_comm_t* comm, const float* queries_dev, uint64_t ldq_floats, uint32_t b, const float* radius_dev,
+                                    uint32_t nprobe, int exhaustive_metric, uint32_t flags, uint64_t* out_lims_dev, uint64_t* out_ids_dev, float* out_dist_dev,
+                                    uint64_t cap, uint64_t* out_total, void* stream) {
+  const char* who = exhaustive_metric >= 0 ? "vers_ivf_range_search_exhaustive_sharded_dev" : "vers_ivf_range_search_sharded_dev";
+  if (h && out_total && exhaustive_metric > (int)VERS_METRIC_COSDIST) { *out_total = 0; return fail(VERS_ERR_INVALID, "unknown metric"); }
+  return range_sharded_run(
+      h, who, comm, queries_dev, ldq_floats, b, radius_dev, exhaustive_metric >= 0, flags, out_lims_dev, out_ids_dev, out_dist_dev, cap, out_total, stream,
+      [&]() -> int32_t { return exhaustive_metric >= 0 ? range_exhaustive_check(h, who, flags, true) : range_check(h, who, nprobe, flags, true); },
+      [&](uint64_t* lims, uint64_t* local_total, hipStream_t st, RangePartial* part) -> int32_t {
+        return range_dev_locked(h, exhaustive_metric < 0, queries_dev, ldq_floats, b, radius_dev, exhaustive_metric >= 0 ? (uint32_t)exhaustive_metric : nprobe, flags, lims,
+                                nullptr, nullptr, cap, false, local_total, st, part);
+      });
+}
+
 int32_t vers_ivf_range_search_sharded_dev(vers_ivf_t* h, const vers_comm_t* comm, const float* queries_dev, uint64_t ldq_floats, uint32_t b, const float* radius_dev,
                                           uint32_t nprobe, uint32_t flags, uint64_t* out_lims_dev, uint64_t* out_ids_dev, float* out_dist_dev, uint64_t cap,
                                           uint64_t* out_total, void* stream) {
@@ -2290,6 +2398,240 @@ int32_t vers_ivf_range_search_exhaustive_sharded_dev(vers_ivf_t* h, const vers_c
                                                      float* out_dist_dev, uint64_t cap, uint64_t* out_total, void* stream) {
   if (metric > VERS_METRIC_COSDIST) return fail(VERS_ERR_INVALID, "unknown metric");
   return range_sharded_common(h, comm, queries_dev, ldq_floats, b, radius_dev, 1, (int)metric, flags, out_lims_dev, out_ids_dev, out_dist_dev, cap, out_total, stream);
+}
+
+// ---- filtered search on handles sharded by cluster (vers_hip.h): a rank's partial of every filtered call, and the calls end to end ----
+// The filters of these calls, always in the _multi form.  filter_of == NULL: ONE bitmap for the batch, the per-call kernels (filter.hip.h,
+// filter_range.hip.h); else the per-query kernels (filter_multi.hip.h, filter_range_multi.hip.h).
+namespace {
+struct ShardFilter {
+  const uint64_t* filters; uint64_t stride_words; uint32_t n_filters; uint64_t n_bits; const uint32_t* filter_of;
+  bool multi() const { return filter_of != nullptr; }
+  uint32_t n_sets() const { return multi() ? n_filters : 1u; }
+  FilterMultiSpec spec() const { return FilterMultiSpec{stride_words, n_filters, filter_of}; }
+};
+enum class ShardKind { kPartial, kSharded };
+
+// what these calls refuse before they touch the device: the per-call and _multi calls' checks, less the refusal of a sharded handle
+int32_t shard_filter_check(vers_ivf* h, const std::string& who, bool probed, bool range, uint32_t nprobe, uint32_t b, const ShardFilter& f) {
+  if (b != 0 && f.n_filters == 0) return fail(VERS_ERR_INVALID, who + ": n_filters == 0");
+  if (f.n_filters > VERS_FILTER_MAX) return fail(VERS_ERR_INVALID, who + ": more than VERS_FILTER_MAX bitmaps in one call; split the batch by allowed set");
+  if (b != 0 && f.filter_of == nullptr && f.n_filters != 1) return fail(VERS_ERR_INVALID, who + ": a NULL filter_of means one bitmap for the batch: n_filters must be 1");
+  if (f.n_bits != 0 && f.stride_words < (f.n_bits + 63) / 64) return fail(VERS_ERR_INVALID, who + ": filter_stride_words is smaller than ceil(n_bits / 64)");
+  if (f.n_bits != 0 && f.filters == nullptr) return fail(VERS_ERR_INVALID, who + ": n_bits > 0 with NULL filters");
+  if (probed && nprobe == 0)
+    return fail(VERS_ERR_INVALID, who + (range ? ": nprobe must be at least 1 (the reference's spill walk is defined by top_k: it has no range meaning)"
+                                               : ": nprobe must be at least 1 (the reference's spill walk depends on the filtered list lengths: out of scope)"));
+  if (probed && h->k == 0)
+    return fail(VERS_ERR_INSUFFICIENT, range ? "range search on an index without centroids (reference: index out of bounds, ivfflat.rs:169)"
+                                             : "search on an index without centroids (reference: index out of bounds, ivfflat.rs:169)");
+  return VERS_OK;
+}
+
+int32_t shard_adaptive_check(const std::string& who, const vers_adaptive_t* ad, uint32_t nprobe_max, ShardKind kind) {
+  if (ad == nullptr) return VERS_OK;
+  if (ad->nprobe_min == 0) return fail(VERS_ERR_INVALID, who + ": nprobe_min must be at least 1");
+  if (nprobe_max < ad->nprobe_min) return fail(VERS_ERR_INVALID, who + ": nprobe (the adaptive call's nprobe_max) is below nprobe_min");
+  if (kind == ShardKind::kPartial && ad->allowed_len_dev == nullptr)
+    return fail(VERS_ERR_INVALID, who + ": an adaptive partial needs the GLOBAL allowed counts (vers_ivf_filter_allowed_len_dev on every rank, summed)");
+  if (kind == ShardKind::kSharded && ad->allowed_len_dev != nullptr) return fail(VERS_ERR_INVALID, who + ": allowed_len_dev must be NULL (the call exchanges the counts itself)");
+  return VERS_OK;
+}
+
+// the local part of the four top-k calls: this rank's partial into keys / ids.  The workspace's o_* buffers take what a partial has no use for.
+int32_t shard_filtered_local(vers_ivf* h, bool probed, const float* q_dev, uint64_t ldq, uint32_t b, uint32_t top_k, uint32_t nprobe_or_metric, const ShardFilter& f,
+                             const AdaptiveSpec* as, uint64_t* keys, uint64_t* ids, hipStream_t st) {
+  if (int32_t rc = ensure_out(h, (size_t)b * top_k, b)) return rc;
+  const FilterMultiSpec ms = f.spec();
+  if (probed)
+    return filtered_dev_locked(h, q_dev, ldq, b, top_k, nprobe_or_metric, f.filters, f.n_bits, ids, W->o_dist.as<float>(), W->o_cnt.as<uint32_t>(), st, f.multi() ? &ms : nullptr, as, keys);
+  return exhaustive_filtered_dev_locked(h, q_dev, ldq, b, top_k, nprobe_or_metric, f.filters, f.n_bits, W->o_ids.as<uint64_t>(), W->o_dist.as<float>(), W->o_cnt.as<uint32_t>(), st,
+                                        f.multi() ? &ms : nullptr, keys, ids);
+}
+
+int32_t filtered_partial_common(vers_ivf_t* h, const char* who, bool probed, const float* queries_dev, uint64_t ldq_floats, uint32_t b, uint32_t top_k, uint32_t nprobe_or_metric,
+                                const ShardFilter& f, const vers_adaptive_t* ad, uint64_t* out_keys_dev, uint64_t* out_ids_dev, void* stream) {
+  if (!h) return fail(VERS_ERR_INVALID, "null handle");
+  if (top_k == 0) return fail(VERS_ERR_INVALID, std::string(who) + ": top_k must be at least 1");
+  if (!probed && nprobe_or_metric > VERS_METRIC_COSDIST) return fail(VERS_ERR_INVALID, "unknown metric");
+  if (b && (!queries_dev || ldq_floats < h->d || !out_keys_dev || !out_ids_dev)) return fail(VERS_ERR_INVALID, std::string(who) + ": bad arguments");
+  if (int32_t rc = shard_adaptive_check(who, ad, nprobe_or_metric, ShardKind::kPartial)) return rc;
+  std::shared_lock<std::shared_mutex> lk(h->index);
+  if (int32_t rc = shard_filter_check(h, who, probed, false, probed ? nprobe_or_metric : 1u, b, f)) return rc;
+  if (b == 0) return VERS_OK;
+  DeviceGuard g(h->device);
+  WsLease lease(h, true, (hipStream_t)stream);
+  if (lease.rc) return lease.rc;
+  if (int32_t rc = lease.order_on((hipStream_t)stream)) return rc;
+  AdaptiveSpec as{ad ? ad->nprobe_min : 0u, ad ? ad->min_allowed : 0u, ad ? ad->out_nprobe_dev : (uint32_t*)nullptr};
+  if (ad) as.allowed_len = ad->allowed_len_dev;
+  return shard_filtered_local(h, probed, queries_dev, ldq_floats, b, top_k, nprobe_or_metric, f, ad ? &as : nullptr, out_keys_dev, out_ids_dev, (hipStream_t)stream);
+}
+
+int32_t filtered_sharded_common(vers_ivf_t* h, const char* who, bool probed, const vers_gather_t* g, const float* queries_dev, uint64_t ldq_floats, uint32_t b, uint32_t top_k,
+                                uint32_t nprobe_or_metric, const ShardFilter& f, const vers_adaptive_t* ad, uint64_t* out_ids_dev, float* out_dist_dev, uint32_t* out_count_dev,
+                                void* stream) {
+  if (h && !probed && nprobe_or_metric > VERS_METRIC_COSDIST) return fail(VERS_ERR_INVALID, "unknown metric");
+  if (h)
+    if (int32_t rc = shard_adaptive_check(who, ad, nprobe_or_metric, ShardKind::kSharded)) return rc;
+  size_t count_words = 0;
+  return sharded_topk_run(
+      h, who, g, queries_dev, ldq_floats, b, top_k, 0, count_words, out_ids_dev, out_dist_dev, out_count_dev, stream,
+      [&]() -> int32_t {
+        if (int32_t rc = shard_filter_check(h, who, probed, false, probed ? nprobe_or_metric : 1u, b, f)) return rc;
+        if (ad) count_words = (size_t)f.n_sets() * h->k;
+        return VERS_OK;
+      },
+      [&](uint64_t* keys, uint64_t* ids, const ShardReduce& reduce, hipStream_t st) -> int32_t {
+        AdaptiveSpec as{ad ? ad->nprobe_min : 0u, ad ? ad->min_allowed : 0u, ad ? ad->out_nprobe_dev : (uint32_t*)nullptr};
+        if (ad) as.reduce = reduce;
+        return shard_filtered_local(h, probed, queries_dev, ldq_floats, b, top_k, nprobe_or_metric, f, ad ? &as : nullptr, keys, ids, st);
+      });
+}
+
+// what the four range calls refuse before they touch the device or exchange anything
+int32_t shard_range_filter_check(vers_ivf* h, const std::string& who, bool probed, uint32_t nprobe, uint32_t flags, uint32_t b, const ShardFilter& f) {
+  if (flags & ~VERS_RANGE_WALK_ORDER) return fail(VERS_ERR_INVALID, who + ": unknown flag bits");
+  if (!probed && (flags & VERS_RANGE_WALK_ORDER))
+    return fail(VERS_ERR_INVALID, who + ": no walk order across ranks (storage order has no key the ranks share); use the default order");
+  return shard_filter_check(h, who, probed, true, nprobe, b, f);
+}
+
+// a rank's partial filtered range call on `st` (the caller holds the index shared, a leased workspace and status word 1)
+int32_t shard_range_filtered_local(vers_ivf* h, const char* who, bool probed, const float* q_dev, uint64_t ldq, uint32_t b, const float* radius_dev, uint32_t nprobe_or_metric,
+                                   uint32_t flags, const ShardFilter& f, uint64_t* lims_dev, uint64_t* ids_dev, uint64_t cap, uint64_t* out_total, hipStream_t st,
+                                   RangePartial* part) {
+  if (f.multi())
+    return range_filtered_multi_dev_locked(h, probed, q_dev, ldq, b, radius_dev, nprobe_or_metric, flags, f.filters, f.n_bits, f.spec(), lims_dev, ids_dev, nullptr, cap, false,
+                                           out_total, st, part, who);
+  return range_filtered_dev_locked(h, probed, q_dev, ldq, b, radius_dev, nprobe_or_metric, flags, f.filters, f.n_bits, lims_dev, ids_dev, nullptr, cap, false, out_total, st, part,
+                                   who);
+}
+
+int32_t range_filtered_partial_common(vers_ivf_t* h, const char* who, bool probed, const float* queries_dev, uint64_t ldq_floats, uint32_t b, const float* radius_dev,
+                                      uint32_t nprobe_or_metric, uint32_t flags, const ShardFilter& f, uint64_t* out_lims_dev, uint64_t* out_keys_dev, uint64_t* out_ids_dev,
+                                      uint64_t cap, uint64_t* out_total, void* stream) {
+  if (!h) return fail(VERS_ERR_INVALID, "null handle");
+  if (!out_total) return fail(VERS_ERR_INVALID, std::string(who) + ": out_total is required");
+  *out_total = 0;
+  if (!probed && nprobe_or_metric > VERS_METRIC_COSDIST) return fail(VERS_ERR_INVALID, "unknown metric");
+  if (b && (!queries_dev || ldq_floats < h->d || !radius_dev || !out_lims_dev || (cap && (!out_ids_dev || !out_keys_dev))))
+    return fail(VERS_ERR_INVALID, std::string(who) + ": bad arguments");
+  if (b == 0) return VERS_OK;
+  std::shared_lock<std::shared_mutex> lk(h->index);
+  if (int32_t rc = shard_range_filter_check(h, who, probed, probed ? nprobe_or_metric : 1u, flags, b, f)) return rc;
+  DeviceGuard g(h->device);
+  WsLease lease(h, true, (hipStream_t)stream);
+  if (lease.rc) return lease.rc;
+  if (int32_t rc = lease.order_on((hipStream_t)stream)) return rc;
+  HostStatusSlot slot(h);
+  RangePartial part;
+  part.keys = out_keys_dev;
+  return shard_range_filtered_local(h, who, probed, queries_dev, ldq_floats, b, radius_dev, nprobe_or_metric, flags, f, out_lims_dev, out_ids_dev, cap, out_total,
+                                    (hipStream_t)stream, &part);
+}
+
+int32_t range_filtered_sharded_common(vers_ivf_t* h, const char* who, bool probed, const vers_comm_t* comm, const float* queries_dev, uint64_t ldq_floats, uint32_t b,
+                                      const float* radius_dev, uint32_t nprobe_or_metric, uint32_t flags, const ShardFilter& f, uint64_t* out_lims_dev, uint64_t* out_ids_dev,
+                                      float* out_dist_dev, uint64_t cap, uint64_t* out_total, void* stream) {
+  if (h && out_total && !probed && nprobe_or_metric > VERS_METRIC_COSDIST) { *out_total = 0; return fail(VERS_ERR_INVALID, "unknown metric"); }
+  return range_sharded_run(
+      h, who, comm, queries_dev, ldq_floats, b, radius_dev, !probed, flags, out_lims_dev, out_ids_dev, out_dist_dev, cap, out_total, stream,
+      [&]() -> int32_t { return shard_range_filter_check(h, who, probed, probed ? nprobe_or_metric : 1u, flags, b, f); },
+      [&](uint64_t* lims, uint64_t* local_total, hipStream_t st, RangePartial* part) -> int32_t {
+        return shard_range_filtered_local(h, who, probed, queries_dev, ldq_floats, b, radius_dev, nprobe_or_metric, flags, f, lims, nullptr, cap, local_total, st, part);
+      });
+}
+}  // namespace
+
+int32_t vers_ivf_filter_allowed_len_dev(vers_ivf_t* h, const uint64_t* filters_dev, uint64_t filter_stride_words, uint32_t n_filters, uint64_t n_bits, uint32_t* out_len_dev,
+                                        void* stream) {
+  const char* who = "vers_ivf_filter_allowed_len_dev";
+  if (!h) return fail(VERS_ERR_INVALID, "null handle");
+  if (n_filters == 0) return fail(VERS_ERR_INVALID, std::string(who) + ": n_filters == 0");
+  if (n_filters > VERS_FILTER_MAX) return fail(VERS_ERR_INVALID, std::string(who) + ": more than VERS_FILTER_MAX bitmaps in one call");
+  if (n_bits != 0 && filter_stride_words < (n_bits + 63) / 64) return fail(VERS_ERR_INVALID, std::string(who) + ": filter_stride_words is smaller than ceil(n_bits / 64)");
+  if (n_bits != 0 && filters_dev == nullptr) return fail(VERS_ERR_INVALID, std::string(who) + ": n_bits > 0 with NULL filters");
+  std::shared_lock<std::shared_mutex> lk(h->index);
+  if (h->k == 0) return VERS_OK;  // (no list: nothing to write)
+  if (!out_len_dev) return fail(VERS_ERR_INVALID, std::string(who) + ": NULL out_len_dev");
+  DeviceGuard g(h->device);
+  hipStream_t st = (hipStream_t)stream;
+  WsLease lease(h, true, st);
+  if (lease.rc) return lease.rc;
+  if (int32_t rc = lease.order_on(st)) return rc;
+  FilterParams f;
+  FilterMultiParams fm;
+  const bool multi = n_filters > 1;
+  const FilterMultiSpec ms{filter_stride_words, n_filters, nullptr};
+  if (int32_t rc = multi ? filter_multi_begin(h, filters_dev, n_bits, ms, h->cap_rows, st, fm) : filter_begin(h, filters_dev, n_bits, h->cap_rows, st, f)) return rc;
+  if (int32_t rc = filter_count_allowed(h, multi ? nullptr : &f, multi ? &fm : nullptr, n_filters, out_len_dev, st)) return rc;
+  return filter_end(h, st);
+}
+
+int32_t vers_ivf_search_filtered_partial_dev(vers_ivf_t* h, const float* queries_dev, uint64_t ldq_floats, uint32_t b, uint32_t top_k, uint32_t nprobe,
+                                             const uint64_t* filters_dev, uint64_t filter_stride_words, uint32_t n_filters, uint64_t n_bits, const uint32_t* filter_of_dev,
+                                             const vers_adaptive_t* adaptive, uint64_t* out_keys_dev, uint64_t* out_ids_dev, void* stream) {
+  return filtered_partial_common(h, "vers_ivf_search_filtered_partial_dev", true, queries_dev, ldq_floats, b, top_k, nprobe,
+                                 ShardFilter{filters_dev, filter_stride_words, n_filters, n_bits, filter_of_dev}, adaptive, out_keys_dev, out_ids_dev, stream);
+}
+
+int32_t vers_ivf_search_exhaustive_filtered_partial_dev(vers_ivf_t* h, const float* queries_dev, uint64_t ldq_floats, uint32_t b, uint32_t top_k, uint32_t metric,
+                                                        const uint64_t* filters_dev, uint64_t filter_stride_words, uint32_t n_filters, uint64_t n_bits,
+                                                        const uint32_t* filter_of_dev, uint64_t* out_keys_dev, uint64_t* out_ids_dev, void* stream) {
+  return filtered_partial_common(h, "vers_ivf_search_exhaustive_filtered_partial_dev", false, queries_dev, ldq_floats, b, top_k, metric,
+                                 ShardFilter{filters_dev, filter_stride_words, n_filters, n_bits, filter_of_dev}, nullptr, out_keys_dev, out_ids_dev, stream);
+}
+
+int32_t vers_ivf_search_filtered_sharded_dev(vers_ivf_t* h, const vers_gather_t* g, const float* queries_dev, uint64_t ldq_floats, uint32_t b, uint32_t top_k, uint32_t nprobe,
+                                             const uint64_t* filters_dev, uint64_t filter_stride_words, uint32_t n_filters, uint64_t n_bits, const uint32_t* filter_of_dev,
+                                             const vers_adaptive_t* adaptive, uint64_t* out_ids_dev, float* out_dist_dev, uint32_t* out_count_dev, void* stream) {
+  return filtered_sharded_common(h, "vers_ivf_search_filtered_sharded_dev", true, g, queries_dev, ldq_floats, b, top_k, nprobe,
+                                 ShardFilter{filters_dev, filter_stride_words, n_filters, n_bits, filter_of_dev}, adaptive, out_ids_dev, out_dist_dev, out_count_dev, stream);
+}
+
+int32_t vers_ivf_search_exhaustive_filtered_sharded_dev(vers_ivf_t* h, const vers_gather_t* g, const float* queries_dev, uint64_t ldq_floats, uint32_t b, uint32_t top_k,
+                                                        uint32_t metric, const uint64_t* filters_dev, uint64_t filter_stride_words, uint32_t n_filters, uint64_t n_bits,
+                                                        const uint32_t* filter_of_dev, uint64_t* out_ids_dev, float* out_dist_dev, uint32_t* out_count_dev, void* stream) {
+  return filtered_sharded_common(h, "vers_ivf_search_exhaustive_filtered_sharded_dev", false, g, queries_dev, ldq_floats, b, top_k, metric,
+                                 ShardFilter{filters_dev, filter_stride_words, n_filters, n_bits, filter_of_dev}, nullptr, out_ids_dev, out_dist_dev, out_count_dev, stream);
+}
+
+int32_t vers_ivf_range_search_filtered_partial_dev(vers_ivf_t* h, const float* queries_dev, uint64_t ldq_floats, uint32_t b, const float* radius_dev, uint32_t nprobe,
+                                                   uint32_t flags, const uint64_t* filters_dev, uint64_t filter_stride_words, uint32_t n_filters, uint64_t n_bits,
+                                                   const uint32_t* filter_of_dev, uint64_t* out_lims_dev, uint64_t* out_keys_dev, uint64_t* out_ids_dev, uint64_t cap,
+                                                   uint64_t* out_total, void* stream) {
+  return range_filtered_partial_common(h, "vers_ivf_range_search_filtered_partial_dev", true, queries_dev, ldq_floats, b, radius_dev, nprobe, flags,
+                                       ShardFilter{filters_dev, filter_stride_words, n_filters, n_bits, filter_of_dev}, out_lims_dev, out_keys_dev, out_ids_dev, cap, out_total,
+                                       stream);
+}
+
+int32_t vers_ivf_range_search_exhaustive_filtered_partial_dev(vers_ivf_t* h, const float* queries_dev, uint64_t ldq_floats, uint32_t b, const float* radius_dev, uint32_t metric,
+                                                              uint32_t flags, const uint64_t* filters_dev, uint64_t filter_stride_words, uint32_t n_filters, uint64_t n_bits,
+                                                              const uint32_t* filter_of_dev, uint64_t* out_lims_dev, uint64_t* out_keys_dev, uint64_t* out_ids_dev,
+                                                              uint64_t cap, uint64_t* out_total, void* stream) {
+  return range_filtered_partial_common(h, "vers_ivf_range_search_exhaustive_filtered_partial_dev", false, queries_dev, ldq_floats, b, radius_dev, metric, flags,
+                                       ShardFilter{filters_dev, filter_stride_words, n_filters, n_bits, filter_of_dev}, out_lims_dev, out_keys_dev, out_ids_dev, cap, out_total,
+                                       stream);
+}
+
+int32_t vers_ivf_range_search_filtered_sharded_dev(vers_ivf_t* h, const vers_comm_t* comm, const float* queries_dev, uint64_t ldq_floats, uint32_t b, const float* radius_dev,
+                                                   uint32_t nprobe, uint32_t flags, const uint64_t* filters_dev, uint64_t filter_stride_words, uint32_t n_filters,
+                                                   uint64_t n_bits, const uint32_t* filter_of_dev, uint64_t* out_lims_dev, uint64_t* out_ids_dev, float* out_dist_dev,
+                                                   uint64_t cap, uint64_t* out_total, void* stream) {
+  return range_filtered_sharded_common(h, "vers_ivf_range_search_filtered_sharded_dev", true, comm, queries_dev, ldq_floats, b, radius_dev, nprobe, flags,
+                                       ShardFilter{filters_dev, filter_stride_words, n_filters, n_bits, filter_of_dev}, out_lims_dev, out_ids_dev, out_dist_dev, cap, out_total,
+                                       stream);
+}
+
+int32_t vers_ivf_range_search_exhaustive_filtered_sharded_dev(vers_ivf_t* h, const vers_comm_t* comm, const float* queries_dev, uint64_t ldq_floats, uint32_t b,
+                                                              const float* radius_dev, uint32_t metric, uint32_t flags, const uint64_t* filters_dev,
+                                                              uint64_t filter_stride_words, uint32_t n_filters, uint64_t n_bits, const uint32_t* filter_of_dev,
+                                                              uint64_t* out_lims_dev, uint64_t* out_ids_dev, float* out_dist_dev, uint64_t cap, uint64_t* out_total,
+                                                              void* stream) {
+  return range_filtered_sharded_common(h, "vers_ivf_range_search_exhaustive_filtered_sharded_dev", false, comm, queries_dev, ldq_floats, b, radius_dev, metric, flags,
+                                       ShardFilter{filters_dev, filter_stride_words, n_filters, n_bits, filter_of_dev}, out_lims_dev, out_ids_dev, out_dist_dev, cap, out_total,
+                                       stream);
 }
 
 int32_t vers_range_phases(double* out8, int32_t reset) {

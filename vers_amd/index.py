@@ -770,6 +770,83 @@ class IVFFlatIndex:
                                                                  C.byref(total), _vp(stream)))
         return int(total.value)
 
+    # -- filtered search on handles sharded by cluster (vers_hip.h: partials, vers_adaptive_t, the _filtered_sharded_dev calls) -----------
+    # filt = (filters_ptr, stride_words, n_filters, n_bits, filter_of_ptr): the _multi form; filter_of_ptr 0 = one bitmap for the batch.
+    # adaptive = None (plain depth) or (nprobe_min, min_allowed, allowed_len_ptr, out_nprobe_ptr) with `nprobe` the call's nprobe_max.
+    @staticmethod
+    def _filt(filt):
+        fp, stride, nf, n_bits, fo = filt
+        return (_vp(fp) if fp else None, stride, nf, n_bits, _vp(fo) if fo else None)
+
+    @staticmethod
+    def _adaptive(adaptive):
+        if adaptive is None:
+            return None, None
+        nprobe_min, min_allowed, alen_ptr, np_ptr = adaptive
+        ad = capi.Adaptive(nprobe_min, min_allowed, alen_ptr if alen_ptr else None, np_ptr if np_ptr else None)
+        return ad, C.byref(ad)
+
+    def filter_allowed_len_dev(self, filters_ptr: int, stride_words: int, n_filters: int, n_bits: int, out_len_ptr: int, stream: int = 0):
+        """u32 [n_filters][k] on the device: the rows of every list THIS handle stores that each bitmap allows, 0 for lists of other ranks
+        (vers_ivf_filter_allowed_len_dev); the ranks' arrays add up to the global counts an adaptive partial takes."""
+        check(lib().vers_ivf_filter_allowed_len_dev(self._h, _vp(filters_ptr) if filters_ptr else None, stride_words, n_filters, n_bits,
+                                                    _vp(out_len_ptr), _vp(stream)))
+
+    def search_filtered_partial_dev(self, q_ptr: int, ldq: int, b: int, top_k: int, nprobe: int, filt, keys_ptr: int, ids_ptr: int,
+                                    adaptive=None, stream: int = 0):
+        """This rank's part of a probed filtered search as (key, vec id) pairs for merge_partials_dev (vers_ivf_search_filtered_partial_dev)."""
+        ad, adp = self._adaptive(adaptive)
+        check(lib().vers_ivf_search_filtered_partial_dev(self._h, _vp(q_ptr), ldq, b, top_k, nprobe, *self._filt(filt), adp, _vp(keys_ptr), _vp(ids_ptr),
+                                                         _vp(stream)))
+
+    def search_exhaustive_filtered_partial_dev(self, q_ptr: int, ldq: int, b: int, top_k: int, metric: int, filt, keys_ptr: int, ids_ptr: int,
+                                               stream: int = 0):
+        check(lib().vers_ivf_search_exhaustive_filtered_partial_dev(self._h, _vp(q_ptr), ldq, b, top_k, metric, *self._filt(filt), _vp(keys_ptr),
+                                                                    _vp(ids_ptr), _vp(stream)))
+
+    def search_filtered_sharded_dev(self, gather_ptr, q_ptr: int, ldq: int, b: int, top_k: int, nprobe: int, filt, ids_ptr: int, dist_ptr: int,
+                                    cnt_ptr: int, adaptive=None, stream: int = 0):
+        """Probed filtered search over lists sharded by cluster, end to end on `stream` (vers_ivf_search_filtered_sharded_dev); gather_ptr as
+        search_sharded_dev's (None on an unsharded handle).  adaptive: two gathers, allowed_len_ptr must be 0."""
+        ad, adp = self._adaptive(adaptive)
+        check(lib().vers_ivf_search_filtered_sharded_dev(self._h, gather_ptr, _vp(q_ptr), ldq, b, top_k, nprobe, *self._filt(filt), adp, _vp(ids_ptr),
+                                                         _vp(dist_ptr), _vp(cnt_ptr), _vp(stream)))
+
+    def search_exhaustive_filtered_sharded_dev(self, gather_ptr, q_ptr: int, ldq: int, b: int, top_k: int, metric: int, filt, ids_ptr: int,
+                                               dist_ptr: int, cnt_ptr: int, stream: int = 0):
+        check(lib().vers_ivf_search_exhaustive_filtered_sharded_dev(self._h, gather_ptr, _vp(q_ptr), ldq, b, top_k, metric, *self._filt(filt),
+                                                                    _vp(ids_ptr), _vp(dist_ptr), _vp(cnt_ptr), _vp(stream)))
+
+    def range_search_filtered_partial_dev(self, q_ptr: int, ldq: int, b: int, radius_ptr: int, nprobe: int, flags: int, filt, lims_ptr: int,
+                                          keys_ptr: int, ids_ptr: int, cap: int, stream: int = 0, exhaustive_metric=None) -> int:
+        """range_search_partial_dev behind a filter (vers_ivf_range_search_filtered_partial_dev / _exhaustive_filtered_partial_dev).  Returns
+        the LOCAL total: keys / ids were written only when it is <= cap."""
+        total = C.c_uint64(0)
+        fn = lib().vers_ivf_range_search_filtered_partial_dev if exhaustive_metric is None else lib().vers_ivf_range_search_exhaustive_filtered_partial_dev
+        check(fn(self._h, _vp(q_ptr), ldq, b, _vp(radius_ptr), nprobe if exhaustive_metric is None else exhaustive_metric, flags, *self._filt(filt),
+                 _vp(lims_ptr), _vp(keys_ptr) if keys_ptr else None, _vp(ids_ptr) if ids_ptr else None, cap, C.byref(total), _vp(stream)))
+        return int(total.value)
+
+    def range_search_filtered_sharded_dev(self, comm, q_ptr: int, ldq: int, b: int, radius_ptr: int, nprobe: int, flags: int, filt, lims_ptr: int,
+                                          ids_ptr: int, dist_ptr: int, cap: int, stream: int = 0, exhaustive_metric=None) -> int:
+        """range_search_sharded_dev behind a filter (vers_ivf_range_search_filtered_sharded_dev / _exhaustive_filtered_sharded_dev): every rank
+        calls with the same arguments, bitmaps and cap.  Returns the GLOBAL total."""
+        total = C.c_uint64(0)
+        fn = lib().vers_ivf_range_search_filtered_sharded_dev if exhaustive_metric is None else lib().vers_ivf_range_search_exhaustive_filtered_sharded_dev
+        check(fn(self._h, comm.ptr() if comm is not None else None, _vp(q_ptr), ldq, b, _vp(radius_ptr),
+                 nprobe if exhaustive_metric is None else exhaustive_metric, flags, *self._filt(filt), _vp(lims_ptr), _vp(ids_ptr) if ids_ptr else None,
+                 _vp(dist_ptr) if dist_ptr else None, cap, C.byref(total), _vp(stream)))
+        return int(total.value)
+
+    def range_search_exhaustive_filtered_partial_dev(self, q_ptr: int, ldq: int, b: int, radius_ptr: int, metric: int, flags: int, filt, lims_ptr: int,
+                                                     keys_ptr: int, ids_ptr: int, cap: int, stream: int = 0) -> int:
+        return self.range_search_filtered_partial_dev(q_ptr, ldq, b, radius_ptr, 0, flags, filt, lims_ptr, keys_ptr, ids_ptr, cap, stream, exhaustive_metric=metric)
+
+    def range_search_exhaustive_filtered_sharded_dev(self, comm, q_ptr: int, ldq: int, b: int, radius_ptr: int, metric: int, flags: int, filt, lims_ptr: int,
+                                                     ids_ptr: int, dist_ptr: int, cap: int, stream: int = 0) -> int:
+        return self.range_search_filtered_sharded_dev(comm, q_ptr, ldq, b, radius_ptr, 0, flags, filt, lims_ptr, ids_ptr, dist_ptr, cap, stream,
+                                                      exhaustive_metric=metric)
+
     def poll(self, stream: int = 0):
         check(lib().vers_ivf_poll(self._h, _vp(stream)))
 
