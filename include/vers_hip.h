@@ -493,7 +493,8 @@ int32_t vers_ivf_range_search_exhaustive_dev(vers_ivf_t* h, const float* queries
  *   errors   : VERS_ERR_INVALID n_bits > 0 with a NULL bitmap; nprobe == 0 on the probed call (the reference's spill walk depends on the
  *              filtered list lengths: OUT OF SCOPE); metric > VERS_METRIC_COSDIST on the exhaustive call; a handle sharded by cluster
  *              (world > 1: OUT OF SCOPE).  VERS_ERR_INSUFFICIENT no centroids on the probed call, as in vers_ivf_search.
- *   out of scope: nprobe == 0, the flat corpus handle, a prepared (reusable) filter object.  (Handles sharded by cluster: refused HERE;
+ *   out of scope: nprobe == 0, the flat corpus handle.  (A prepared, reusable filter object: DONE, vers_ivf_filter_prepare and
+ *              vers_ivf_search_prepared_dev / _exhaustive_prepared_dev, further below.)  (Handles sharded by cluster: refused HERE;
  *              vers_ivf_search_filtered_sharded_dev / _partial_dev and their exhaustive twins, further below.  A filter per query: the _multi
  *              calls below.  A depth per query, for filters that leave nprobe lists short of top_k rows: the _adaptive calls below.)
  * vers_ivf_filter_stats (measurement hook; functions of the data and the plan alone): out4 = the most recent filtered call of the handle,
@@ -539,7 +540,7 @@ int32_t vers_ivf_search_exhaustive_filtered_dev(vers_ivf_t* h, const float* quer
  *              allowed a row of it); [3] = allowed (bitmap, storage row) pairs, summed over the call's n_filters bitmaps.  The scan-timing
  *              ring gets the mask kernel's record, then one per scan pass.
  *   out of scope (refused, not approximated): the flat corpus handle, nprobe == 0, more than VERS_FILTER_MAX
- *              bitmaps per call, a prepared (reusable) mask, re-grouping a list's queries by filter in the plan, any fp16 / matrix-core
+ *              bitmaps per call, a prepared (reusable) mask (DONE: vers_ivf_filter_prepare and the _prepared_dev calls, further below), re-grouping a list's queries by filter in the plan, any fp16 / matrix-core
  *              pre-filter.  (Sharded handles and partials: refused HERE; the _filtered_sharded_dev / _filtered_partial_dev calls further
  *              below, with a non-NULL filter_of_dev.  A filter per query on the range calls: the vers_ivf_range_search_*filtered_multi calls below.  A depth per
  *              query: vers_ivf_search_filtered_multi_adaptive below.) */
@@ -631,7 +632,7 @@ int32_t vers_ivf_search_filtered_multi_adaptive_dev(vers_ivf_t* h, const float* 
  *              VERS_ERR_INSUFFICIENT no centroids on the probed call (a streamed upload in progress is seen as an empty index); the
  *              exhaustive call on such a handle: VERS_OK, total 0, every limit 0.  VERS_ERR_NAN as above.  VERS_ERR_HIP scratch for the
  *              result staging did not fit, outputs untouched.
- *   out of scope (refused, not approximated): the flat corpus handle, a prepared (reusable) filter object, any fp16 / matrix-core
+ *   out of scope (refused, not approximated): the flat corpus handle, a prepared (reusable) filter object (DONE: vers_ivf_filter_prepare and the _prepared_dev calls, further below), any fp16 / matrix-core
  *              pre-filter.  (Sharded handles and partials: refused HERE; vers_ivf_range_search_filtered_sharded_dev / _partial_dev and
  *              their exhaustive twins, further below.  A filter per query: the _multi calls below.)
  * vers_ivf_filter_stats covers these calls: [3] comes from the mask kernel; [0..2] -- planned tile visits, loaded tile visits, items skipped
@@ -682,7 +683,7 @@ int32_t vers_ivf_range_search_exhaustive_filtered_dev(vers_ivf_t* h, const float
  *              these calls, its slot [3] covering the mask kernel; the scan-timing ring gets the mask kernel's record and none for the range
  *              passes.
  *   out of scope (refused, not approximated): the flat corpus handle, nprobe == 0, more than VERS_FILTER_MAX
- *              bitmaps per call, a prepared (reusable) mask, re-grouping a list's queries by filter in the plan, any fp16 / matrix-core
+ *              bitmaps per call, a prepared (reusable) mask (DONE: vers_ivf_filter_prepare and the _prepared_dev calls, further below), re-grouping a list's queries by filter in the plan, any fp16 / matrix-core
  *              pre-filter.  (Sharded handles and partials: refused HERE; the range _filtered_sharded_dev / _filtered_partial_dev calls
  *              further below, with a non-NULL filter_of_dev.) */
 int32_t vers_ivf_range_search_filtered_multi(vers_ivf_t* h, const float* queries, uint64_t q_stride_bytes, uint32_t b, const float* radius /* [b] */,
@@ -916,7 +917,7 @@ int32_t vers_ivf_search_exhaustive_sharded_dev(vers_ivf_t* h, const vers_gather_
  *              calls.  VERS_ERR_NAN only for a (query, row) pair that is allowed, scanned and stored on THIS rank.
  *   stats    : vers_ivf_filter_stats covers the local part of every one of these calls.  An adaptive partial leaves no allowed-count record in
  *              the scan-timing ring (it counts nothing).
- *   out of scope: nprobe == 0, the flat corpus handle, a prepared (reusable) mask, a walk order of the exhaustive range search across ranks. */
+ *   out of scope: nprobe == 0, the flat corpus handle, a prepared (reusable) mask (DONE: vers_ivf_filter_prepare and the _prepared_dev calls, further below), a walk order of the exhaustive range search across ranks. */
 typedef struct vers_adaptive { /* NULL = plain depth */
   uint32_t nprobe_min, min_allowed;
   const uint32_t* allowed_len_dev; /* partial call: GLOBAL counts [n_filters][k], required; sharded call: must be NULL */
@@ -967,6 +968,68 @@ int32_t vers_ivf_range_search_exhaustive_filtered_sharded_dev(vers_ivf_t* h, con
                                                               uint64_t n_bits, const uint32_t* filter_of_dev, uint64_t* out_lims_dev,
                                                               uint64_t* out_ids_dev, float* out_dist_dev, uint64_t cap,
                                                               uint64_t* out_total /* host */, void* stream);
+
+/* ---- PREPARED filters: masks kept across calls, refreshed when rows move ------------------------------------------------------------
+ * Every filtered call above rebuilds its masks from the bitmaps: a pass over every storage row, per call.  A tenant or an access-control
+ * set stays the same over thousands of queries; a vers_filter_t keeps its masks in an object the index handle owns.
+ *   object   : vers_ivf_filter_prepare(_dev) COPIES the bitmaps -- the _multi form and meaning: n_filters <= VERS_FILTER_MAX bitmaps
+ *              filter_stride_words apart, one n_bits for all, ids at or beyond n_bits not allowed -- and builds the masks for the index as it
+ *              stands, synchronously, holding the handle shared like a search.  The caller's array may be freed or changed afterwards.  On a
+ *              handle without an index (no centroids, or a streamed upload in progress) the masks are empty.  No update call: to change the
+ *              bits, destroy the object and prepare a new one.  The handle keeps a registry: vers_ivf_destroy frees the objects still alive;
+ *              an object of another handle is VERS_ERR_INVALID everywhere.  Its device bytes count in vers_mem_stats.
+ *   holds    : what the per-call path leaves in its workspace, with the same content -- the per-call tile mask (needed when a search passes no
+ *              filter_of), the per-query row / tile sets (needed when it passes one), allowed_len[n_filters][k] and the allowed total that
+ *              feeds vers_ivf_filter_stats.  Each mask form is built at first need and then kept (prepare builds the per-call form of a
+ *              one-bitmap object, the per-query form otherwise).
+ *   searches : the four _prepared_dev calls are the _filtered_sharded_dev calls without g / comm and with `f` in the bitmaps' place.  No
+ *              semantics of their own: each returns, bit for bit, what the matching vers_ivf_*_filtered_sharded_dev call with g / comm = NULL
+ *              returns on the same handle in its current state, given the bitmaps f was prepared from -- ids, order, distance bits, counts /
+ *              limits / total, out_nprobe, the latched status, the capacity protocol, all four slots of vers_ivf_filter_stats.
+ *              (tiles_loaded / items_skipped of a PROBED batch with a filter per query are not reproducible between two runs of the same
+ *              call, prepared or not: the plan deals a list's queries into work items in the order of an atomic counter, and an item's
+ *              union of filters decides which tiles it loads.  tiles_planned, rows_allowed and every result are reproducible.)
+ *              filter_of_dev == NULL needs an object of ONE bitmap (the per-call kernels); else the per-query kernels and the _multi rules
+ *              (an entry at or beyond n_filters selects the empty filter).  adaptive->allowed_len_dev must be NULL: the object has the counts.
+ *   staleness: at the start of a prepared search, or of vers_ivf_filter_refresh (on `stream`), the object is compared with the handle.  Rows
+ *              MOVED since (build, upload, set_shard, a remove_batch that removed something, compact, an add / add_batch that re-laid-out
+ *              storage): a full rebuild on the call's stream.  Rows only APPENDED in place (an add / add_batch into list slack): a tail
+ *              refresh over the appended rows alone -- and nothing at all when every id handed out since is at or beyond n_bits.  Neither:
+ *              nothing; the call launches no mask and no count kernel and leaves no mask record in vers_ivf_scan_times (a call that rebuilds
+ *              or tail-refreshes leaves one).  A rebuild queued on one stream is waited for ON THE DEVICE by searches on other streams; no host
+ *              synchronisation is added to the query path.
+ *   threads  : prepared searches on one object may run from several threads and streams.  vers_ivf_filter_destroy (and vers_ivf_destroy)
+ *              must NOT run while another thread is inside a call that uses the object: the caller orders them, as for the handle itself.
+ *              A one-bitmap object that builds its second mask form after in-place adds it has not yet seen rebuilds and recounts in full.
+ *   info     : out8 = n_filters | n_bits | device bytes held | full builds so far (prepare's and every form's first build included) | tail
+ *              refreshes | searches served with no mask work at all | 1 if fresh against the handle now, else 0 | 0.
+ *   errors   : those of the _filtered_sharded_dev calls, and VERS_ERR_INVALID for a NULL f, an f of another handle (or destroyed), a handle
+ *              sharded by cluster (world > 1: OUT OF SCOPE), n_filters == 0 or > VERS_FILTER_MAX or a too small filter_stride_words at prepare.
+ *   out of scope: handles sharded by cluster, nprobe == 0, the flat corpus handle, updating an object's bits in place, an incremental refresh
+ *              after remove_batch / compact (a removal compacts every touched list from its first removed row on), host-pointer searches. */
+typedef struct vers_filter vers_filter_t;
+int32_t vers_ivf_filter_prepare(vers_ivf_t* h, const uint64_t* filters, uint64_t filter_stride_words, uint32_t n_filters, uint64_t n_bits,
+                                vers_filter_t** out);
+int32_t vers_ivf_filter_prepare_dev(vers_ivf_t* h, const uint64_t* filters_dev, uint64_t filter_stride_words, uint32_t n_filters,
+                                    uint64_t n_bits, vers_filter_t** out);
+int32_t vers_ivf_filter_refresh(vers_ivf_t* h, vers_filter_t* f, void* stream);
+int32_t vers_ivf_filter_info(vers_ivf_t* h, const vers_filter_t* f, uint64_t* out8);
+int32_t vers_ivf_filter_destroy(vers_ivf_t* h, vers_filter_t* f);
+int32_t vers_ivf_search_prepared_dev(vers_ivf_t* h, const float* queries_dev, uint64_t ldq_floats, uint32_t b, uint32_t top_k,
+                                     uint32_t nprobe /* nprobe_max if adaptive */, const vers_filter_t* f, const uint32_t* filter_of_dev,
+                                     const vers_adaptive_t* adaptive, uint64_t* out_ids_dev, float* out_dist_dev, uint32_t* out_count_dev,
+                                     void* stream);
+int32_t vers_ivf_search_exhaustive_prepared_dev(vers_ivf_t* h, const float* queries_dev, uint64_t ldq_floats, uint32_t b, uint32_t top_k,
+                                                uint32_t metric, const vers_filter_t* f, const uint32_t* filter_of_dev, uint64_t* out_ids_dev,
+                                                float* out_dist_dev, uint32_t* out_count_dev, void* stream);
+int32_t vers_ivf_range_search_prepared_dev(vers_ivf_t* h, const float* queries_dev, uint64_t ldq_floats, uint32_t b, const float* radius_dev,
+                                           uint32_t nprobe, uint32_t flags, const vers_filter_t* f, const uint32_t* filter_of_dev,
+                                           uint64_t* out_lims_dev /* [b+1] */, uint64_t* out_ids_dev, float* out_dist_dev, uint64_t cap,
+                                           uint64_t* out_total /* host */, void* stream);
+int32_t vers_ivf_range_search_exhaustive_prepared_dev(vers_ivf_t* h, const float* queries_dev, uint64_t ldq_floats, uint32_t b,
+                                                      const float* radius_dev, uint32_t metric, uint32_t flags, const vers_filter_t* f,
+                                                      const uint32_t* filter_of_dev, uint64_t* out_lims_dev, uint64_t* out_ids_dev,
+                                                      float* out_dist_dev, uint64_t cap, uint64_t* out_total /* host */, void* stream);
 
 /* Measurement hook: durations (HIP events on the search's stream) of the two kernels of the most recent batched
  * coarse quantiser -- the queries x centroids contraction on the f32 matrix cores (2*b*k*d flop) and the selection /

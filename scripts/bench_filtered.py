@@ -24,6 +24,7 @@ Prints ONE JSON line.
     python scripts/bench_filtered.py --range --multi   # the same for the RANGE search: range_multi_main below
     python scripts/bench_filtered.py --adaptive     # a depth per query against one nprobe for the batch: adaptive_main below
     python scripts/bench_filtered.py --shards 8     # the index sharded over 8 ranks, emulated on one GPU: shards_main below
+    python scripts/bench_filtered.py --prepared     # masks kept across calls against the per-call entry points: prepared_main below
 """
 from __future__ import annotations
 
@@ -686,6 +687,212 @@ def shards_main(args):
     return 0
 
 
+def prepared_main(args):
+    """--prepared: a prepared filter (vers_ivf_filter_prepare + vers_ivf_search_prepared_dev) against the per-call entry point it replaces, on the
+    same handle in the same run.  Batches of --batches queries; F = 1, 8, 64 bitmaps (F = 1: one bitmap for the batch, the per-call kernels and
+    vers_ivf_search_filtered_dev as yardstick; else query q uses bitmap q % F and the yardstick is vers_ivf_search_filtered_multi_dev); the
+    script's selectivities, drawn per bitmap.  Per point, over --reps repeats ALTERNATING between the variants, whole-call ms (device events
+    around the call) as median [min, max]:
+      per_call   the existing entry point (unchanged code = the parent commit's), with the mask record it leaves in the scan-timing ring
+      fresh      (a) the prepared call on a fresh object
+      tail       (b) the first prepared call after an in-place add_batch of 64 rows whose ids the bitmaps cover (a take whose add re-laid-out
+                 storage is a rebuild, not a tail refresh: it is dropped and counted in `tail_dropped`)
+      rebuild    (c) the first prepared call after a remove_batch of one row
+    and, at b = 64, selectivity 0.01, F = 1 and 8: the adaptive call (nprobe_min = --nprobe, nprobe_max = nlist, min_allowed = top_k) and one
+    range shape (radius: each query's 10th allowed probed distance; wall clock around the synchronous call).  Every take goes to --out.
+    Prints ONE JSON line."""
+    import torch
+    from tests import datagen as dg
+    from vers_amd import capi
+    from vers_amd.index import IVFFlatIndex
+
+    torch.cuda.set_device(0)
+    n, d, nlist, nprobe, top_k = args.rows, args.d, args.nlist, args.nprobe, args.top_k
+    ld = (d + 3) // 4 * 4
+    n_modes = max(1, args.modes_per_list * nlist)
+    sigma = float(dg.default_sigma(d))
+    SEED_X, SEED_C = 0x5EED0001, 0x5EEDC0DE   # bench.py's corpus
+    X = torch.empty(n, ld, dtype=torch.float32, device="cuda")
+    capi.gen_rows_dev(X.data_ptr(), n, d, ld, 1, SEED_X, SEED_C, n_modes, sigma)
+    init = (dg.mix64(np.uint64(0xB01D) + np.arange(nlist, dtype=np.uint64)) % np.uint64(n)).astype(np.uint64)
+    index = IVFFlatIndex(d)
+    t0 = time.perf_counter()
+    assert index.build_dev(X.data_ptr(), n, nlist, 1, args.kmeans_iters, init)
+    t_build = time.perf_counter() - t0
+    log(f"[bench_filtered --prepared] index built in {t_build:.2f} s")
+    del X
+
+    room = 1 << 18                      # vec ids beyond n the bitmaps cover: the rows the tail takes add
+    n_bits = n + room
+    stride = (n_bits + 63) // 64
+    fresh_rows = torch.empty(64, ld, dtype=torch.float32, device="cuda")
+    state = {"added": 0, "removed": 0}
+    takes = open(args.out, "w")
+    takes.write(f"# scripts/bench_filtered.py --prepared: N={n} d={d} nlist={nlist} nprobe={nprobe} top_k={top_k} reps={args.reps}; every take, ms\n")
+
+    made = {}
+
+    def bitmaps(sel, F, seed):
+        if (sel, F) not in made:
+            made[(sel, F)] = make_bitmaps(sel, F, seed)
+        return made[(sel, F)]
+
+    def make_bitmaps(sel, F, seed):
+        rng = np.random.default_rng(seed)
+        out = np.zeros((F, stride), dtype=np.uint64)
+        for f in range(F):
+            if sel == "contiguous_0.01":
+                a = np.zeros(stride * 64, dtype=bool)
+                lo = (n // 3 + f * (n // max(F, 1))) % n
+                a[lo:lo + n // 100] = True
+                a[n:n_bits] = True      # (the rows added later are allowed: the tail refresh has bits to set)
+            else:
+                a = np.ones(stride * 64, dtype=bool) if sel >= 1 else rng.random(stride * 64) < sel
+                a[n_bits:] = False
+            out[f] = np.packbits(a, bitorder="little").view(np.uint64)
+        return out
+
+    def append_in_place():
+        capi.gen_rows_dev(fresh_rows.data_ptr(), 64, d, ld, 1, SEED_X + 7 + state["added"], SEED_C, n_modes, sigma)
+        first, added = index.add_batch_dev(fresh_rows.data_ptr(), 64, ld)
+        assert added == 64 and first + 64 <= n_bits
+        state["added"] += 1
+
+    one_id = torch.zeros(1, dtype=torch.int64, device="cuda")
+
+    def remove_one():
+        one_id[0] = 17 + 31 * state["removed"]      # a row of the build, still there
+        assert index.remove_batch_dev(one_id.data_ptr(), 1) == 1
+        state["removed"] += 1
+
+    found = capi.env_option("scan_events", 2)
+    sels = (1, 0.5, 0.1, 0.01, 0.001, "contiguous_0.01")
+    out = {}
+    try:
+        capi.set_option("scan_events", 1)
+        for b in (int(x) for x in args.batches.split(",")):
+            Q = torch.empty(b, ld, dtype=torch.float32, device="cuda")
+            capi.gen_rows_dev(Q.data_ptr(), b, d, ld, 1, SEED_X + 1, SEED_C, n_modes, sigma)
+            oi = torch.zeros(b, top_k, dtype=torch.int64, device="cuda"); od = torch.zeros(b, top_k, device="cuda")
+            oc = torch.zeros(b, dtype=torch.int32, device="cuda"); on = torch.zeros(b, dtype=torch.int32, device="cuda")
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            res = {}
+
+            def timed(fn):
+                index.scan_times(reset=True)
+                torch.cuda.synchronize()
+                e0.record(); fn(); e1.record()
+                index.poll(); torch.cuda.synchronize()
+                return e0.elapsed_time(e1), index.scan_times(reset=True)
+
+            for F in (1, 8, 64):
+                fo = torch.from_numpy((np.arange(b) % F).astype(np.int32)).cuda()
+                for sel in sels:
+                    name = f"F{F}/" + (sel if isinstance(sel, str) else f"random_{sel:g}")
+                    w = torch.from_numpy(bitmaps(sel, F, 0xF117E2 + F).view(np.int64)).cuda()
+                    pf = index.prepare_filter_dev(w.data_ptr(), stride, F, n_bits)
+                    fop = fo.data_ptr() if F > 1 else 0
+                    out_p = (oi.data_ptr(), od.data_ptr(), oc.data_ptr())
+
+                    def per_call(adaptive=False):
+                        if F == 1 and adaptive:
+                            index.search_filtered_adaptive_dev(Q.data_ptr(), ld, b, top_k, nprobe, nlist, top_k, w.data_ptr(), n_bits, *out_p, on.data_ptr())
+                        elif F == 1:
+                            index.search_filtered_dev(Q.data_ptr(), ld, b, top_k, nprobe, w.data_ptr(), n_bits, *out_p)
+                        elif adaptive:
+                            index.search_filtered_multi_adaptive_dev(Q.data_ptr(), ld, b, top_k, nprobe, nlist, top_k, w.data_ptr(), stride, F, n_bits, fop, *out_p, on.data_ptr())
+                        else:
+                            index.search_filtered_multi_dev(Q.data_ptr(), ld, b, top_k, nprobe, w.data_ptr(), stride, F, n_bits, fop, *out_p)
+
+                    def prepared(adaptive=False):
+                        index.search_prepared_dev(Q.data_ptr(), ld, b, top_k, nlist if adaptive else nprobe, pf, fop, *out_p,
+                                                  adaptive=(nprobe, top_k, 0, on.data_ptr()) if adaptive else None)
+
+                    def take(kind, adaptive=False):
+                        i0 = pf.info()
+                        if kind == "tail":
+                            append_in_place()
+                        elif kind == "rebuild":
+                            remove_one()
+                        ms, ring = timed((lambda: per_call(adaptive)) if kind == "per_call" else (lambda: prepared(adaptive)))
+                        i1 = pf.info()
+                        r = {"call_ms": ms}
+                        if kind == "per_call":
+                            r["mask_ms"] = float(ring[0])
+                            if adaptive:
+                                r["count_ms"] = float(ring[1])
+                        else:   # what the object did is part of the take
+                            did = (i1["builds"] - i0["builds"], i1["tail_refreshes"] - i0["tail_refreshes"], i1["hits"] - i0["hits"])
+                            want = {"fresh": (0, 0, 1), "tail": (0, 1, 0), "rebuild": (1, 0, 0)}[kind]
+                            if kind == "tail" and did == (1, 0, 0):
+                                return None   # the add re-laid-out storage
+                            assert did == want, (name, kind, did)
+                            if kind != "fresh":
+                                r["refresh_ms"] = float(ring[0])
+                        takes.write(f"b={b} {name} {'adaptive ' if adaptive else ''}{kind} " + " ".join(f"{k}={v:.4f}" for k, v in r.items()) + "\n")
+                        return r
+
+                    def point(adaptive=False):
+                        kinds = ("per_call", "fresh", "tail", "rebuild")
+                        for k in ("per_call", "fresh"):
+                            take(k, adaptive)   # warm-up of both shapes
+                        runs = {k: [] for k in kinds}
+                        for _ in range(args.reps):
+                            for k in kinds:
+                                r = take(k, adaptive)
+                                if r is not None:
+                                    runs[k].append(r)
+                        p = {k: {f: mms([r[f] for r in v]) for f in v[0]} for k, v in runs.items() if v}
+                        p["tail_dropped"] = args.reps - len(runs["tail"])
+                        med = lambda k: p[k]["call_ms"]["median"]
+                        p["per_call_minus_fresh_ms"] = round(med("per_call") - med("fresh"), 4)
+                        p["rebuild_minus_per_call_ms"] = round(med("rebuild") - med("per_call"), 4)
+                        return p
+
+                    res[name] = point()
+                    if b == 64 and sel == 0.01 and F in (1, 8):
+                        res[name + "/adaptive"] = point(adaptive=True)
+                        # one range shape: each query's 10th allowed probed distance
+                        per_call(); index.poll(); torch.cuda.synchronize()
+                        odh, och = od.cpu().numpy(), oc.cpu().numpy().astype(np.int64)
+                        rad = torch.from_numpy(np.where(och > 0, odh[np.arange(b), np.clip(och - 1, 0, top_k - 1)], np.float32(0)).astype(np.float32)).cuda()
+                        lims = torch.zeros(b + 1, dtype=torch.int64, device="cuda")
+                        filt = (w.data_ptr(), stride, F, n_bits, fop)
+                        cap = max(1, index.range_search_filtered_sharded_dev(None, Q.data_ptr(), ld, b, rad.data_ptr(), nprobe, 0, filt, lims.data_ptr(), 0, 0, 0))
+                        ids = torch.zeros(cap, dtype=torch.int64, device="cuda"); dist = torch.zeros(cap, device="cuda")
+
+                        def wall(fn):
+                            torch.cuda.synchronize()
+                            t = time.perf_counter(); fn()
+                            return (time.perf_counter() - t) * 1e3
+
+                        rng_calls = {"per_call": lambda: index.range_search_filtered_sharded_dev(None, Q.data_ptr(), ld, b, rad.data_ptr(), nprobe, 0, filt, lims.data_ptr(),
+                                                                                                 ids.data_ptr(), dist.data_ptr(), cap),
+                                     "fresh": lambda: index.range_search_prepared_dev(Q.data_ptr(), ld, b, rad.data_ptr(), nprobe, 0, pf, fop, lims.data_ptr(), ids.data_ptr(),
+                                                                                      dist.data_ptr(), cap)}
+                        for fn in rng_calls.values():
+                            fn()
+                        rr = {k: [] for k in rng_calls}
+                        for _ in range(args.reps):
+                            for k, fn in rng_calls.items():
+                                rr[k].append(wall(fn))
+                                takes.write(f"b={b} {name} range {k} wall_ms={rr[k][-1]:.4f}\n")
+                        res[name + "/range"] = {**{k: {"wall_ms": mms(v)} for k, v in rr.items()}, "total": cap,
+                                                "per_call_minus_fresh_ms": round(float(np.median(rr["per_call"]) - np.median(rr["fresh"])), 4)}
+                    log(f"[bench_filtered --prepared] batch {b} {name}: {json.dumps({k: v for k, v in res.items() if k.startswith(name)})}")
+                    pf.close()
+                    del w
+            out[f"batch{b}"] = res
+    finally:
+        capi.set_option("scan_events", found)
+        takes.close()
+    line = {"metric": f"vers_ivf_search_prepared_dev against the per-call filtered entry points in ms, IVFFlat (N={n} d={d} nlist={nlist}) nprobe={nprobe} top_k={top_k}",
+            "build_s": round(t_build, 2), "reps": args.reps, "rows_added": 64 * state["added"], "rows_removed": state["removed"], **out}
+    index.close()
+    print(json.dumps(line), flush=True)
+    return 0
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", type=int, default=1_000_000)
@@ -703,11 +910,15 @@ def main():
     ap.add_argument("--nprobe-max", type=int, default=0, help="--adaptive: nprobe_max (0: nlist)")
     ap.add_argument("--multi-batches", default="64,1024", help="--multi: the batch sizes (multiples of 64); with --range too")
     ap.add_argument("--inner", type=int, default=8, help="--multi: back-to-back calls per timed window")
+    ap.add_argument("--prepared", action="store_true", help="a prepared filter (vers_ivf_filter_prepare + the _prepared_dev calls) against the per-call entry points: see prepared_main")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r18_filtered_prepared.txt"), help="--prepared: the file every take is written to")
     ap.add_argument("--shards", type=int, default=0, help="filtered search on an index sharded over this many ranks, emulated on one GPU (partials + merge): see shards_main")
     args = ap.parse_args()
     assert args.reps >= 5, "at least 5 alternating repeats per point"
     if args.shards:
         return shards_main(args)
+    if args.prepared:
+        return prepared_main(args)
     if args.adaptive:
         return adaptive_main(args)
     if args.range and args.multi:

@@ -185,6 +185,18 @@ SIGNATURES = {
                                                                C.c_uint64, _vp, _vp, _vp, _vp, C.c_uint64, C.POINTER(C.c_uint64), _vp]),
     "vers_ivf_range_search_exhaustive_filtered_sharded_dev": (C.c_int32, [_vp, _vp, _vp, C.c_uint64, C.c_uint32, _vp, C.c_uint32, C.c_uint32, _vp, C.c_uint64,
                                                                           C.c_uint32, C.c_uint64, _vp, _vp, _vp, _vp, C.c_uint64, C.POINTER(C.c_uint64), _vp]),
+    # prepared filters: the object (a vers_filter_t* travels as a void pointer) and the four searches that take it
+    "vers_ivf_filter_prepare": (C.c_int32, [_vp, _vp, C.c_uint64, C.c_uint32, C.c_uint64, C.POINTER(_vp)]),
+    "vers_ivf_filter_prepare_dev": (C.c_int32, [_vp, _vp, C.c_uint64, C.c_uint32, C.c_uint64, C.POINTER(_vp)]),
+    "vers_ivf_filter_refresh": (C.c_int32, [_vp, _vp, _vp]),
+    "vers_ivf_filter_info": (C.c_int32, [_vp, _vp, _vp]),
+    "vers_ivf_filter_destroy": (C.c_int32, [_vp, _vp]),
+    "vers_ivf_search_prepared_dev": (C.c_int32, [_vp, _vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "vers_ivf_search_exhaustive_prepared_dev": (C.c_int32, [_vp, _vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "vers_ivf_range_search_prepared_dev": (C.c_int32, [_vp, _vp, C.c_uint64, C.c_uint32, _vp, C.c_uint32, C.c_uint32, _vp, _vp, _vp, _vp, _vp, C.c_uint64,
+                                                       C.POINTER(C.c_uint64), _vp]),
+    "vers_ivf_range_search_exhaustive_prepared_dev": (C.c_int32, [_vp, _vp, C.c_uint64, C.c_uint32, _vp, C.c_uint32, C.c_uint32, _vp, _vp, _vp, _vp, _vp,
+                                                                  C.c_uint64, C.POINTER(C.c_uint64), _vp]),
     "vers_kmeans_update": (C.c_int32, [C.c_int32, _vp, C.c_uint64, C.c_uint64, _vp, C.c_uint64, C.c_uint32, _vp]),
     "vers_kmeans_cost": (C.c_int32, [C.c_int32, _vp, C.c_uint64, C.c_uint64, _vp, C.c_uint64, C.c_uint64, _vp, C.c_uint32,
                                      C.POINTER(C.c_float)]),

@@ -1389,6 +1389,7 @@ int32_t build_common(vers_ivf* h, const float* X, uint32_t ldx, uint64_t n, cons
 // Every owned list moves to a new storage plan with room for lens[c] rows plus head-room (the rows it holds now, h_len[c], are copied):
 // relayout() plans for the current lengths, add_batch for the lengths after the chunk -- one re-layout per chunk however many lists overflow.
 static int32_t relayout_for(vers_ivf* h, const uint32_t* lens) {
+  h->flt_moved += 1;  // (prepared filters: every storage row moves)
   const uint32_t k = h->k;
   std::vector<uint32_t> noff(k), ncap(k);
   uint64_t off = 0;
@@ -2206,6 +2207,19 @@ int32_t compact_locked(vers_ivf* h, uint64_t* out_before, uint64_t* out_after) {
 }  // namespace ivf
 }  // namespace vers
 
+namespace {
+// What an add / add_batch means to the prepared filters (vers_ivf::flt_moved / flt_appended), noted when the call leaves: rows written into
+// list slack in place are an append; a re-layout has counted itself (relayout_for).
+struct AppendNote {
+  vers_ivf* h;
+  uint64_t moved0, n0;
+  explicit AppendNote(vers_ivf* hh) : h(hh), moved0(hh->flt_moved), n0(hh->n_total) {}
+  ~AppendNote() {
+    if (h->n_total != n0 && h->flt_moved == moved0) h->flt_appended += 1;
+  }
+};
+}  // namespace
+
 extern "C" {
 
 int32_t vers_ivf_build(vers_ivf_t* h, const float* rows, uint64_t n, uint64_t row_stride_bytes, uint64_t num_clusters,
@@ -2217,6 +2231,7 @@ int32_t vers_ivf_build(vers_ivf_t* h, const float* rows, uint64_t n, uint64_t ro
       (out_centroids && num_clusters && c_stride_bytes < (uint64_t)h->d * 4))
     return fail(VERS_ERR_INVALID, "vers_ivf_build: bad arguments");
   std::unique_lock<std::shared_mutex> lk(h->index);
+  h->flt_moved += 1;
   DeviceGuard g(h->device);
   DevBuf X;
   if (int32_t rc = X.reserve((n ? n : 1) * (size_t)h->ldx * sizeof(float))) return rc;
@@ -2239,6 +2254,7 @@ int32_t vers_ivf_build_dev(vers_ivf_t* h, const float* rows_dev, uint64_t n, uin
       (out_centroids && num_clusters && c_stride_bytes < (uint64_t)h->d * 4))
     return fail(VERS_ERR_INVALID, "vers_ivf_build_dev: bad arguments (ld_floats must be >= d and a multiple of 4)");
   std::unique_lock<std::shared_mutex> lk(h->index);
+  h->flt_moved += 1;
   DeviceGuard g(h->device);
   BuildShard one;
   one.n_total = n;
@@ -2258,6 +2274,7 @@ int32_t vers_ivf_build_sharded_dev(vers_ivf_t* h, const float* rows_dev, uint64_
       (comm->world > 1 && (!comm->all_gather || !comm->send || !comm->recv || !comm->broadcast || !comm->all_to_all_v)))
     return fail(VERS_ERR_INVALID, "vers_ivf_build_sharded_dev: incomplete vers_comm_t");
   std::unique_lock<std::shared_mutex> lk(h->index);
+  h->flt_moved += 1;
   DeviceGuard g(h->device);
   BuildShard sh;
   sh.comm = comm->world > 1 ? comm : nullptr;
@@ -2280,6 +2297,7 @@ int32_t vers_ivf_upload(vers_ivf_t* h, const float* rows, uint64_t n, uint64_t r
     lens[assignments[i]] += 1;
   }
   std::unique_lock<std::shared_mutex> lk(h->index);
+  h->flt_moved += 1;
   DeviceGuard g(h->device);
   if (int32_t rc = upload_begin_locked(h, centroids, k, c_stride_bytes, lens.data(), n)) return rc;
   if (int32_t rc = upload_chunk_host_locked(h, rows, row_stride_bytes, assignments, 0, n)) return rc;
@@ -2292,6 +2310,7 @@ int32_t vers_ivf_upload_begin(vers_ivf_t* h, const float* centroids, uint64_t k,
       (k == 0 && n_total != 0))
     return fail(VERS_ERR_INVALID, "vers_ivf_upload_begin: bad arguments");
   std::unique_lock<std::shared_mutex> lk(h->index);
+  h->flt_moved += 1;
   DeviceGuard g(h->device);
   return upload_begin_locked(h, centroids, k, c_stride_bytes, list_lengths, n_total);
 }
@@ -2301,6 +2320,7 @@ int32_t vers_ivf_upload_chunk(vers_ivf_t* h, const float* rows, uint64_t row_str
   if (!h || (n && (!rows || !assignments)) || row_stride_bytes < (uint64_t)(h ? h->d : 0) * 4)
     return fail(VERS_ERR_INVALID, "vers_ivf_upload_chunk: bad arguments");
   std::unique_lock<std::shared_mutex> lk(h->index);
+  h->flt_moved += 1;
   DeviceGuard g(h->device);
   return upload_chunk_host_locked(h, rows, row_stride_bytes, assignments, first_vec_id, n);
 }
@@ -2310,6 +2330,7 @@ int32_t vers_ivf_upload_chunk_dev(vers_ivf_t* h, const float* rows_dev, uint64_t
   if (!h || (n && (!rows_dev || !assignments_dev)) || ld_floats < (uint64_t)(h ? h->d : 0) || ld_floats % 4 || ld_floats > 0x3FFFFFFFull)
     return fail(VERS_ERR_INVALID, "vers_ivf_upload_chunk_dev: bad arguments (ld_floats must be >= d and a multiple of 4)");
   std::unique_lock<std::shared_mutex> lk(h->index);
+  h->flt_moved += 1;
   DeviceGuard g(h->device);
   return upload_chunk_dev_locked(h, rows_dev, ld_floats, assignments_dev, first_vec_id, n);
 }
@@ -2317,6 +2338,7 @@ int32_t vers_ivf_upload_chunk_dev(vers_ivf_t* h, const float* rows_dev, uint64_t
 int32_t vers_ivf_upload_end(vers_ivf_t* h) {
   if (!h) return fail(VERS_ERR_INVALID, "vers_ivf_upload_end: null handle");
   std::unique_lock<std::shared_mutex> lk(h->index);
+  h->flt_moved += 1;
   DeviceGuard g(h->device);
   return upload_end_locked(h);
 }
@@ -2327,6 +2349,7 @@ int32_t vers_ivf_upload_dev(vers_ivf_t* h, const float* rows_dev, uint64_t n, ui
       ld_floats > 0x3FFFFFFFull || (k && c_ld_floats < (uint64_t)h->d) || n > 0xFFFFFFFFull || k > 0xFFFFFFFFull)
     return fail(VERS_ERR_INVALID, "vers_ivf_upload_dev: bad arguments (ld_floats must be >= d and a multiple of 4)");
   std::unique_lock<std::shared_mutex> lk(h->index);
+  h->flt_moved += 1;
   DeviceGuard g(h->device);
   upload_abandon(h);
   DevBuf A, bad;
@@ -2353,6 +2376,7 @@ int32_t vers_ivf_upload_dev(vers_ivf_t* h, const float* rows_dev, uint64_t n, ui
 int32_t vers_ivf_add(vers_ivf_t* h, const float* row, uint64_t* out_cluster, uint64_t* out_vec_id) {
   if (!h || !row) return fail(VERS_ERR_INVALID, "vers_ivf_add: bad arguments");
   std::unique_lock<std::shared_mutex> lk(h->index);
+  AppendNote note(h);
   DeviceGuard g(h->device);
   VERS_HIP_TRY(hipDeviceSynchronize());  // searches still in flight on any stream read the rows and tables this call changes
   WsLease lease(h);
@@ -2409,6 +2433,7 @@ int32_t vers_ivf_add_batch(vers_ivf_t* h, const float* rows, uint64_t n, uint64_
   if (!h || (n && !rows) || row_stride_bytes < (uint64_t)(h ? h->d : 0) * 4 || row_stride_bytes % 4)
     return fail(VERS_ERR_INVALID, "vers_ivf_add_batch: bad arguments (row_stride_bytes must be >= 4 d and a multiple of 4)");
   std::unique_lock<std::shared_mutex> lk(h->index);
+  AppendNote note(h);
   DeviceGuard g(h->device);
   return add_batch_locked(h, rows, row_stride_bytes, nullptr, 0, n, out_clusters, nullptr, out_first_vec_id, out_added);
 }
@@ -2418,6 +2443,7 @@ int32_t vers_ivf_add_batch_dev(vers_ivf_t* h, const float* rows_dev, uint64_t n,
   if (!h || (n && !rows_dev) || ld_floats < (uint64_t)(h ? h->d : 0) || ld_floats % 4 || ld_floats > 0x3FFFFFFFull)
     return fail(VERS_ERR_INVALID, "vers_ivf_add_batch_dev: bad arguments (ld_floats must be >= d and a multiple of 4)");
   std::unique_lock<std::shared_mutex> lk(h->index);
+  AppendNote note(h);
   DeviceGuard g(h->device);
   return add_batch_locked(h, nullptr, 0, rows_dev, ld_floats, n, nullptr, out_clusters_dev, out_first_vec_id, out_added);
 }
@@ -2426,14 +2452,22 @@ int32_t vers_ivf_remove_batch(vers_ivf_t* h, const uint64_t* vec_ids, uint64_t n
   if (!h || (n_ids && !vec_ids)) return fail(VERS_ERR_INVALID, "vers_ivf_remove_batch: bad arguments");
   std::unique_lock<std::shared_mutex> lk(h->index);
   DeviceGuard g(h->device);
-  return remove_batch_locked(h, vec_ids, nullptr, n_ids, nullptr, out_removed);
+  uint64_t removed = 0;
+  const int32_t rc = remove_batch_locked(h, vec_ids, nullptr, n_ids, nullptr, &removed);
+  if (rc || removed) h->flt_moved += 1;  // (prepared filters: a removal compacts every touched list from its first removed row on)
+  if (out_removed) *out_removed = removed;
+  return rc;
 }
 
 int32_t vers_ivf_remove_batch_dev(vers_ivf_t* h, const uint64_t* vec_ids_dev, uint64_t n_ids, const vers_comm_t* comm, uint64_t* out_removed) {
   if (!h || (n_ids && !vec_ids_dev)) return fail(VERS_ERR_INVALID, "vers_ivf_remove_batch_dev: bad arguments");
   std::unique_lock<std::shared_mutex> lk(h->index);
   DeviceGuard g(h->device);
-  return remove_batch_locked(h, nullptr, vec_ids_dev, n_ids, comm, out_removed);
+  uint64_t removed = 0;
+  const int32_t rc = remove_batch_locked(h, nullptr, vec_ids_dev, n_ids, comm, &removed);
+  if (rc || removed) h->flt_moved += 1;  // (prepared filters: a removal compacts every touched list from its first removed row on)
+  if (out_removed) *out_removed = removed;
+  return rc;
 }
 
 int32_t vers_ivf_live_count(vers_ivf_t* h, uint64_t* out_live) {
@@ -2448,6 +2482,7 @@ int32_t vers_ivf_live_count(vers_ivf_t* h, uint64_t* out_live) {
 int32_t vers_ivf_compact(vers_ivf_t* h, uint64_t* out_rows_before, uint64_t* out_rows_after) {
   if (!h) return fail(VERS_ERR_INVALID, "vers_ivf_compact: null handle");
   std::unique_lock<std::shared_mutex> lk(h->index);
+  h->flt_moved += 1;
   DeviceGuard g(h->device);
   return compact_locked(h, out_rows_before, out_rows_after);
 }

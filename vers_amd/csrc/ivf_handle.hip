@@ -163,6 +163,7 @@ int32_t vers_ivf_destroy(vers_ivf_t* h) {
   h->up.close();
   h->ab.free_pin();
   h->rm.free_pin();
+  for (vers_filter* f : h->filters) delete f;  // (prepared filters still alive: the handle owns them)
   delete h;
   return VERS_OK;
 }
@@ -198,6 +199,7 @@ int32_t vers_ivf_set_shard(vers_ivf_t* h, uint32_t rank, uint32_t world) {
   if (h->k != 0 || h->up.open) return fail(VERS_ERR_INVALID, "vers_ivf_set_shard: call before build / upload");
   h->rank = rank;
   h->world = world;
+  h->flt_moved += 1;
   return VERS_OK;
 }
 

@@ -31,6 +31,36 @@ constexpr int32_t kRetrySpill = 1001;  // internal: reference-mode spill ran pas
 
 using namespace vers;
 
+// A prepared filter (vers_ivf_filter_prepare): the bitmaps, copied, and the arrays the per-call path leaves in the leased workspace -- kept
+// across calls and brought up to date against the handle's `flt_moved` / `flt_appended` counters at the start of a prepared search or of
+// vers_ivf_filter_refresh (ivf_search.hip: prepared_sync).  Everything below `mu` is read and written under it; the device arrays are written
+// in place by a rebuild or a tail refresh, which is ordered against searches on other streams by `ready`.
+struct vers_filter {
+  struct vers_ivf* owner = nullptr;
+  uint32_t n_filters = 0;
+  uint64_t n_bits = 0, words = 1;  // words: the pitch of `bits`, max(1, ceil(n_bits / 64))
+  DevBuf bits;                     // [n_filters][words]
+  std::mutex mu;
+  DevBuf tile_mask;                // the per-call form (filter_tile_mask_kernel's output): held once a search without filter_of asked for it
+  DevBuf row_sets, tile_sets;      // the per-query form (filter_multi_mask_kernel's output): held once a search with filter_of asked for it
+  DevBuf alen;                     // allowed_len [n_filters][k] (filter_count_allowed's output)
+  DevBuf stats;                    // u64 [kFltStats]: [kFltRowsAllowed] = the allowed (bitmap, row) pairs | u64 [kFltStats]: the sink of a form built beside a fresh one
+  DevBuf work;                     // the tail refresh's work list
+  bool have_one = false, have_multi = false;
+  bool built = false;              // the held forms, alen and the total describe the index as of (seen_moved, snap_len)
+  uint64_t seen_moved = 0, seen_appended = 0;
+  uint64_t snap_n_total = 0;       // the next vec id add would have handed out at the snapshot
+  std::vector<uint32_t> snap_len;  // h_len at the last build or refresh
+  hipEvent_t ready = nullptr;      // recorded behind the last rebuild / tail refresh, on ready_stream
+  hipStream_t ready_stream = nullptr;
+  bool pending = false;            // `ready` may still be unsignalled
+  uint64_t builds = 0, tails = 0, hits = 0;
+  uint64_t device_bytes() const { return bits.cap + tile_mask.cap + row_sets.cap + tile_sets.cap + alen.cap + stats.cap + work.cap; }
+  ~vers_filter() {
+    if (ready) (void)hipEventDestroy(ready);
+  }
+};
+
 // =================================================================================================
 // Everything a search call MUTATES lives in a workspace, not in the handle: scratch buffers, status words, the timing
 // ring, the host-pointer staging, the look-ahead slots.  Search_approximate(&self) is legal from many threads in the
@@ -54,6 +84,7 @@ struct SearchWs {
   DevBuf flt_rows, flt_of;  // a filter per query (filter_multi.hip.h): the row_sets words; the staged filter_of of a host-pointer call
   DevBuf flt_alen, flt_np;  // adaptive depth (filter_adaptive.hip.h): allowed rows per (bitmap, list); the staged out_nprobe of a host-pointer call
   bool no_ahead = false;  // the plan of a filtered call neither consumes a look-ahead slot nor touches a pending request (plan_search)
+  vers_filter* prep = nullptr;  // a prepared call (vers_ivf_*_prepared_dev): filter_begin / filter_multi_begin point at this object's masks instead of building the call's
   DevBuf rg_rlims;  // sharded range search: every rank's CSR limits [world][b + 1] (range_merge.hip.h); the gather itself goes through g_send / g_recv
   DevBuf g_send, g_recv;  // sharded search without the host in the loop: this rank's [2][b][top_k] partial | the world's
   DevBuf g_cnt;  // an adaptive filtered call on a sharded handle: this rank's allowed counts [n] | the world's [world][n] | their sum [n], u32
@@ -223,6 +254,13 @@ struct vers_ivf {
   DevBuf flt_total;  // u64 [4] vers_ivf_filter_stats over the handle's life (filter_stats_fold_kernel adds every call's counters); allocated under flt_mu
   std::mutex flt_mu;
   SearchWs* flt_last = nullptr;  // the workspace of the most recent filtered call (guarded by pool_mu)
+  // Prepared filters (vers_ivf_filter_prepare): the objects still alive (guarded by flt_mu; vers_ivf_destroy frees them) and the two counters
+  // their staleness protocol reads.  Both are written only while a mutator holds `index` exclusively -- when no search is in flight:
+  //   flt_moved     anything after which a storage row may hold another vector or the tables changed: build, upload, set_shard, a
+  //                 remove_batch that removed something, compact, an add / add_batch that re-laid-out storage
+  //   flt_appended  an add / add_batch that wrote its rows into list slack in place: cap_rows, list_off and every existing row unchanged
+  std::vector<vers_filter*> filters;
+  uint64_t flt_moved = 0, flt_appended = 0;
   DevBuf prune_ctr;  // u64 [3] steps executed | steps without math | tiles abandoned by the list scan's early abandon, over the handle's life
   // fp16 shadow of the rows for the matrix-core pre-selection (+50 % corpus memory; VERS_SHADOW=0 or a failed
   // allocation: the f32 rows feed it).  The wider certificate window makes it sensitive to data with many near-ties:

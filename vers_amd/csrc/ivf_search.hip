@@ -21,6 +21,7 @@
 #include "filter_adaptive.hip.h"
 #include "filter_range.hip.h"
 #include "filter_range_multi.hip.h"
+#include "filter_prepared.hip.h"
 
 namespace vers {
 
@@ -544,10 +545,159 @@ static int32_t filter_counters_begin(vers_ivf* h, hipStream_t st, unsigned long 
   return VERS_OK;
 }
 
+// ---- prepared filters (filter_prepared.hip.h): whose arrays a filtered call reads ----
+// A full build of the forms asked for into the object's arrays, on `st`: the mask kernels and the count kernel of the per-call path.  recount:
+// allowed_len and the total are rebuilt with them (a stale object); else a form is built BESIDE a fresh one (a one-bitmap object's second
+// form), whose counts hold already -- the mask kernel's count then goes to the spare counters, so that a search on another stream never
+// reads a total in the making.
+static int32_t prepared_build(vers_ivf* h, vers_filter* o, bool one, bool multi, bool recount, uint64_t n_rows, hipStream_t st) {
+  const uint64_t n_tiles = (n_rows + kWave - 1) / kWave;
+  const size_t tile_bytes = std::max<size_t>(1, n_tiles) * sizeof(uint64_t), row_bytes = tile_bytes * kWave;
+  if (one)
+    if (int32_t rc = o->tile_mask.reserve(tile_bytes)) return rc;
+  if (multi) {
+    if (int32_t rc = o->tile_sets.reserve(tile_bytes)) return rc;
+    if (int32_t rc = o->row_sets.reserve(row_bytes)) return rc;
+  }
+  if (int32_t rc = o->stats.reserve(2 * kFltStats * sizeof(unsigned long long))) return rc;
+  if (recount)
+    if (int32_t rc = o->alen.reserve(std::max<size_t>(1, (size_t)o->n_filters * h->k) * sizeof(uint32_t))) return rc;
+  unsigned long long* const sink = o->stats.as<unsigned long long>() + (recount ? 0 : kFltStats);
+  const bool empty = o->n_bits == 0 || n_tiles == 0;  // nothing is allowed
+  const uint64_t blocks = std::min<uint64_t>((uint64_t)h->n_cu, (n_tiles + kFltMaskThreads / kWave - 1) / (kFltMaskThreads / kWave));
+  if (one) {
+    VERS_HIP_TRY(hipMemsetAsync(sink, 0, kFltStats * sizeof(unsigned long long), st));
+    if (empty) VERS_HIP_TRY(hipMemsetAsync(o->tile_mask.p, 0, tile_bytes, st));
+    else
+      hipLaunchKernelGGL(filter_tile_mask_kernel, dim3((unsigned)blocks), dim3(kFltMaskThreads), 0, st, (const uint32_t*)h->row_ids.as<uint32_t>(), n_rows,
+                         (const uint64_t*)o->bits.as<uint64_t>(), o->n_bits, o->tile_mask.as<uint64_t>(), sink);
+    VERS_HIP_TRY(hipGetLastError());
+  }
+  if (multi) {
+    VERS_HIP_TRY(hipMemsetAsync(sink, 0, kFltStats * sizeof(unsigned long long), st));  // (both forms of one bitmap count the same rows)
+    if (empty) {
+      VERS_HIP_TRY(hipMemsetAsync(o->tile_sets.p, 0, tile_bytes, st));
+      VERS_HIP_TRY(hipMemsetAsync(o->row_sets.p, 0, row_bytes, st));
+    } else {
+      hipLaunchKernelGGL(filter_multi_mask_kernel, dim3((unsigned)blocks), dim3(kFltMaskThreads), 0, st, (const uint32_t*)h->row_ids.as<uint32_t>(), n_rows,
+                         (const uint64_t*)o->bits.as<uint64_t>(), o->words, o->n_filters, o->n_bits, o->row_sets.as<uint64_t>(), o->tile_sets.as<uint64_t>(), sink);
+      VERS_HIP_TRY(hipGetLastError());
+    }
+  }
+  if (recount && h->k != 0) {
+    const uint32_t cblocks = (h->k + kAdpThreads / kWave - 1) / (kAdpThreads / kWave);
+    const uint8_t* owner = h->world > 1 ? h->owner.as<uint8_t>() : (const uint8_t*)nullptr;
+    if (multi)
+      hipLaunchKernelGGL(filter_multi_allowed_len_kernel, dim3(cblocks), dim3(kAdpThreads), 0, st, (const uint64_t*)o->row_sets.as<uint64_t>(),
+                         (const uint64_t*)o->tile_sets.as<uint64_t>(), (const uint32_t*)h->list_off.as<uint32_t>(), (const uint32_t*)h->list_len.as<uint32_t>(), h->k,
+                         o->n_filters, o->alen.as<uint32_t>(), owner, h->rank);
+    else
+      hipLaunchKernelGGL(filter_allowed_len_kernel, dim3(cblocks), dim3(kAdpThreads), 0, st, (const uint64_t*)o->tile_mask.as<uint64_t>(),
+                         (const uint32_t*)h->list_off.as<uint32_t>(), (const uint32_t*)h->list_len.as<uint32_t>(), h->k, o->alen.as<uint32_t>(), owner, h->rank);
+    VERS_HIP_TRY(hipGetLastError());
+  }
+  return VERS_OK;
+}
+
+// The object brought up to date against the handle on `st`, under the handle's shared lock (the caller's) and the object's mutex (taken here):
+// "check, enqueue, record the event" is one critical section.  want: 0 the per-call form, 1 the per-query form, -1 whatever the object holds
+// (vers_ivf_filter_refresh).  A rebuild or a tail refresh leaves ONE record in the scan-timing ring of the leased workspace; a call served
+// from fresh masks leaves none, and is counted as a hit when it is a search's.
+static int32_t prepared_sync(vers_ivf* h, vers_filter* o, int want, bool search, hipStream_t st) {
+  std::lock_guard<std::mutex> lk(o->mu);
+  const uint64_t n_rows = (h->k == 0 || h->up.open) ? 0 : h->cap_rows;
+  // Work queued for the object on ANOTHER stream (a rebuild, a tail refresh, a form's first build) may still be running: whatever this call
+  // reads or writes of the object comes behind it, on the device.  Before anything below records `ready` anew.
+  if (o->pending && o->ready_stream != st) {
+    const hipError_t q = hipEventQuery(o->ready);
+    if (q == hipSuccess) o->pending = false;
+    else {
+      if (q == hipErrorNotReady) (void)hipGetLastError();  // (no error: the query's answer)
+      VERS_HIP_TRY(hipStreamWaitEvent(st, o->ready, 0));
+    }
+  }
+  bool stale = !o->built || o->seen_moved != h->flt_moved;
+  // A form's first build beside held ones, after in-place appends the object has not seen: the new form would hold the appended rows'
+  // bits while allowed_len and the total do not count them yet, and the tail refresh takes its corrections from the words that were there.
+  // Rare (a one-bitmap object's second form): everything is rebuilt and recounted, as if rows had moved.
+  if (!stale && o->seen_appended != h->flt_appended && ((want == 0 && !o->have_one) || (want == 1 && !o->have_multi))) stale = true;
+  const bool one = want == 0 ? (stale || !o->have_one) : (stale && o->have_one);
+  const bool multi = want == 1 ? (stale || !o->have_multi) : (stale && o->have_multi);
+  auto snapshot = [&]() {
+    o->seen_moved = h->flt_moved; o->seen_appended = h->flt_appended; o->snap_n_total = h->n_total;
+    o->snap_len.assign(h->h_len.begin(), h->h_len.begin() + std::min<size_t>(h->h_len.size(), h->k));
+  };
+  auto record = [&]() -> int32_t {
+    VERS_HIP_TRY(hipEventRecord(o->ready, st));
+    o->ready_stream = st;
+    o->pending = true;
+    return VERS_OK;
+  };
+  if (one || multi) {
+    if (stale) o->built = false;
+    if (int32_t rc = timed_scan(st, [&]() -> int32_t { return prepared_build(h, o, one, multi, stale, n_rows, st); })) {
+      if (one) o->have_one = false;
+      if (multi) o->have_multi = false;
+      return rc;
+    }
+    o->have_one = o->have_one || one; o->have_multi = o->have_multi || multi;
+    if (stale) { snapshot(); o->built = true; }
+    o->builds += 1;
+    return record();
+  }
+  if (stale) { snapshot(); o->built = true; }  // (an object that holds no form yet: nothing to rebuild)
+  if (o->seen_appended != h->flt_appended) {
+    std::vector<TailItem> items;
+    if (o->have_one || o->have_multi)
+      (void)filter_tail_plan(o->snap_len.data(), h->h_len.data(), h->world > 1 ? h->h_owner.data() : (const uint8_t*)nullptr, h->rank, h->k, o->snap_n_total, o->n_bits, items);
+    if (!items.empty()) {
+      if (int32_t rc = o->work.reserve(items.size() * sizeof(TailItem))) return rc;
+      VERS_HIP_TRY(hipMemcpyAsync(o->work.p, items.data(), items.size() * sizeof(TailItem), hipMemcpyHostToDevice, st));  // (pageable source: copied before the call returns)
+      TailArgs a;
+      a.items = o->work.as<TailItem>(); a.n_items = (uint32_t)items.size();
+      a.row_ids = h->row_ids.as<uint32_t>(); a.list_off = h->list_off.as<uint32_t>(); a.cap_rows = n_rows;
+      a.bits = o->bits.as<uint64_t>(); a.stride_words = o->words; a.n_bits = o->n_bits; a.n_filters = o->n_filters;
+      a.tile_mask = o->have_one ? o->tile_mask.as<uint64_t>() : (uint64_t*)nullptr;
+      a.row_sets = o->have_multi ? o->row_sets.as<uint64_t>() : (uint64_t*)nullptr;
+      a.tile_sets = o->have_multi ? o->tile_sets.as<uint64_t>() : (uint64_t*)nullptr;
+      a.allowed_len = o->alen.as<uint32_t>(); a.k_lists = h->k;
+      a.total = o->stats.as<unsigned long long>() + kFltRowsAllowed;
+      if (int32_t rc = timed_scan(st, [&]() -> int32_t {
+            hipLaunchKernelGGL(filter_tail_refresh_kernel, dim3((a.n_items + kTailThreads / kWave - 1) / (kTailThreads / kWave)), dim3(kTailThreads), 0, st, a);
+            VERS_HIP_TRY(hipGetLastError());
+            return VERS_OK;
+          })) {
+        o->built = false;  // (what the kernel did is not known: the next call rebuilds)
+        return rc;
+      }
+      snapshot();
+      o->tails += 1;
+      return record();
+    }
+    snapshot();  // no new row can be allowed, and a slack row's bits were 0 already
+  }
+  if (search) o->hits += 1;
+  return VERS_OK;
+}
+
+// filter_begin / filter_multi_begin of a prepared call: the object's arrays in the workspace's place, the allowed total from the object
+static int32_t prepared_begin(vers_ivf* h, bool multi, hipStream_t st, unsigned long long* stats) {
+  vers_filter* const o = W->prep;
+  if (int32_t rc = prepared_sync(h, o, multi ? 1 : 0, true, st)) return rc;
+  VERS_HIP_TRY(hipMemcpyAsync(stats + kFltRowsAllowed, o->stats.as<unsigned long long>() + kFltRowsAllowed, sizeof(unsigned long long), hipMemcpyDeviceToDevice, st));
+  return VERS_OK;
+}
+
 // The tile mask of the call over `n_rows` storage rows + its zeroed counters.  The mask kernel is bracketed by a record of the scan-timing
 // ring (vers_ivf_scan_times: a filtered call leaves the mask kernel's record, then one per scan pass).
 static int32_t filter_begin(vers_ivf* h, const uint64_t* bits_dev, uint64_t n_bits, uint64_t n_rows, hipStream_t st, FilterParams& f) {
   const uint64_t n_tiles = (n_rows + kWave - 1) / kWave;
+  if (W->prep) {  // a prepared call: no mask kernel, the object's mask
+    if (int32_t rc = filter_counters_begin(h, st, f.stats, f.wave_slots)) return rc;
+    if (int32_t rc = prepared_begin(h, false, st, f.stats)) return rc;
+    f.tile_mask = W->prep->tile_mask.as<uint64_t>();
+    return VERS_OK;
+  }
   if (int32_t rc = W->flt_mask.reserve(std::max<size_t>(1, n_tiles) * sizeof(uint64_t))) return rc;
   if (int32_t rc = filter_counters_begin(h, st, f.stats, f.wave_slots)) return rc;
   f.tile_mask = W->flt_mask.as<uint64_t>();
@@ -608,6 +758,15 @@ static int32_t filter_multi_begin(vers_ivf* h, const uint64_t* filters_dev, uint
                                   FilterMultiParams& f) {
   const uint64_t n_tiles = (n_rows + kWave - 1) / kWave;
   const size_t tile_bytes = std::max<size_t>(1, n_tiles) * sizeof(uint64_t), row_bytes = tile_bytes * kWave;
+  if (W->prep) {  // a prepared call: no mask kernel, the object's sets
+    if (int32_t rc = filter_counters_begin(h, st, f.stats, f.wave_slots)) return rc;
+    if (int32_t rc = prepared_begin(h, true, st, f.stats)) return rc;
+    f.tile_sets = W->prep->tile_sets.as<uint64_t>();
+    f.row_sets = W->prep->row_sets.as<uint64_t>();
+    f.filter_of = ms.filter_of;
+    f.n_filters = ms.n_filters;
+    return VERS_OK;
+  }
   if (int32_t rc = W->flt_mask.reserve(tile_bytes)) return rc;
   if (int32_t rc = W->flt_rows.reserve(row_bytes)) return rc;
   if (int32_t rc = filter_counters_begin(h, st, f.stats, f.wave_slots)) return rc;
@@ -725,11 +884,15 @@ int32_t filtered_dev_locked(vers_ivf* h, const float* q_dev, uint64_t ldq_in, ui
     aq.p_min = std::min<uint32_t>(adaptive->nprobe_min, h->k); aq.min_allowed = adaptive->min_allowed; aq.allowed_len = adaptive->allowed_len;
     aq.filter_of = multi ? multi->filter_of : (const uint32_t*)nullptr; aq.n_filters = n_sets; aq.out_nprobe = adaptive->out_nprobe;
     if (aq.allowed_len == nullptr) {  // (a partial call brings the global counts: nothing to count)
-      if (int32_t rc = W->flt_alen.reserve((size_t)n_sets * h->k * sizeof(uint32_t))) return rc;
-      if (int32_t rc = filter_count_allowed(h, multi ? nullptr : &f, multi ? &fm : nullptr, n_sets, W->flt_alen.as<uint32_t>(), st)) return rc;
-      aq.allowed_len = W->flt_alen.as<uint32_t>();
+      const uint32_t* counts = W->prep ? W->prep->alen.as<uint32_t>() : (const uint32_t*)nullptr;  // (a prepared call: the object has them, kept with its masks)
+      if (counts == nullptr) {
+        if (int32_t rc = W->flt_alen.reserve((size_t)n_sets * h->k * sizeof(uint32_t))) return rc;
+        if (int32_t rc = filter_count_allowed(h, multi ? nullptr : &f, multi ? &fm : nullptr, n_sets, W->flt_alen.as<uint32_t>(), st)) return rc;
+        counts = W->flt_alen.as<uint32_t>();
+      }
+      aq.allowed_len = counts;
       if (adaptive->reduce)
-        if (int32_t rc = adaptive->reduce(W->flt_alen.as<uint32_t>(), (size_t)n_sets * h->k, aq.allowed_len, st)) return rc;
+        if (int32_t rc = adaptive->reduce(counts, (size_t)n_sets * h->k, aq.allowed_len, st)) return rc;
     }
   }
   SearchPlan s;
@@ -2406,11 +2569,18 @@ int32_t vers_ivf_range_search_exhaustive_sharded_dev(vers_ivf_t* h, const vers_c
 namespace {
 struct ShardFilter {
   const uint64_t* filters; uint64_t stride_words; uint32_t n_filters; uint64_t n_bits; const uint32_t* filter_of;
+  vers_filter* prep = nullptr;  // a prepared call: the object the bitmaps above are (its masks serve the call, filter_begin / filter_multi_begin)
   bool multi() const { return filter_of != nullptr; }
   uint32_t n_sets() const { return multi() ? n_filters : 1u; }
   FilterMultiSpec spec() const { return FilterMultiSpec{stride_words, n_filters, filter_of}; }
 };
 enum class ShardKind { kPartial, kSharded };
+// the leased workspace told whose masks the call reads, for as long as the local part runs
+struct PreparedScope {
+  SearchWs* w;
+  explicit PreparedScope(vers_filter* o) : w(W) { w->prep = o; }
+  ~PreparedScope() { w->prep = nullptr; }
+};
 
 // what these calls refuse before they touch the device: the per-call and _multi calls' checks, less the refusal of a sharded handle
 int32_t shard_filter_check(vers_ivf* h, const std::string& who, bool probed, bool range, uint32_t nprobe, uint32_t b, const ShardFilter& f) {
@@ -2443,6 +2613,7 @@ int32_t shard_filtered_local(vers_ivf* h, bool probed, const float* q_dev, uint6
                              const AdaptiveSpec* as, uint64_t* keys, uint64_t* ids, hipStream_t st) {
   if (int32_t rc = ensure_out(h, (size_t)b * top_k, b)) return rc;
   const FilterMultiSpec ms = f.spec();
+  const PreparedScope scope(f.prep);
   if (probed)
     return filtered_dev_locked(h, q_dev, ldq, b, top_k, nprobe_or_metric, f.filters, f.n_bits, ids, W->o_dist.as<float>(), W->o_cnt.as<uint32_t>(), st, f.multi() ? &ms : nullptr, as, keys);
   return exhaustive_filtered_dev_locked(h, q_dev, ldq, b, top_k, nprobe_or_metric, f.filters, f.n_bits, W->o_ids.as<uint64_t>(), W->o_dist.as<float>(), W->o_cnt.as<uint32_t>(), st,
@@ -2501,6 +2672,7 @@ int32_t shard_range_filter_check(vers_ivf* h, const std::string& who, bool probe
 int32_t shard_range_filtered_local(vers_ivf* h, const char* who, bool probed, const float* q_dev, uint64_t ldq, uint32_t b, const float* radius_dev, uint32_t nprobe_or_metric,
                                    uint32_t flags, const ShardFilter& f, uint64_t* lims_dev, uint64_t* ids_dev, uint64_t cap, uint64_t* out_total, hipStream_t st,
                                    RangePartial* part) {
+  const PreparedScope scope(f.prep);
   if (f.multi())
     return range_filtered_multi_dev_locked(h, probed, q_dev, ldq, b, radius_dev, nprobe_or_metric, flags, f.filters, f.n_bits, f.spec(), lims_dev, ids_dev, nullptr, cap, false,
                                            out_total, st, part, who);
@@ -2632,6 +2804,163 @@ int32_t vers_ivf_range_search_exhaustive_filtered_sharded_dev(vers_ivf_t* h, con
   return range_filtered_sharded_common(h, "vers_ivf_range_search_exhaustive_filtered_sharded_dev", false, comm, queries_dev, ldq_floats, b, radius_dev, metric, flags,
                                        ShardFilter{filters_dev, filter_stride_words, n_filters, n_bits, filter_of_dev}, out_lims_dev, out_ids_dev, out_dist_dev, cap, out_total,
                                        stream);
+}
+
+// ---- prepared filters (vers_hip.h): the object's lifecycle, and the four searches that take it ----
+namespace {
+// is `f` one of h's live objects?  (an object of another handle, or one destroyed already, is not in the registry)
+bool filter_is_ours(vers_ivf* h, const vers_filter* f) {
+  std::lock_guard<std::mutex> lk(h->flt_mu);
+  return std::find(h->filters.begin(), h->filters.end(), f) != h->filters.end();
+}
+
+int32_t filter_prepare_common(vers_ivf_t* h, const char* who_c, const uint64_t* filters, bool on_device, uint64_t stride_words, uint32_t n_filters, uint64_t n_bits,
+                              vers_filter_t** out) {
+  const std::string who = who_c;
+  if (!h) return fail(VERS_ERR_INVALID, "null handle");
+  if (!out) return fail(VERS_ERR_INVALID, who + ": NULL out");
+  *out = nullptr;
+  if (n_filters == 0) return fail(VERS_ERR_INVALID, who + ": n_filters == 0");
+  if (n_filters > VERS_FILTER_MAX) return fail(VERS_ERR_INVALID, who + ": more than VERS_FILTER_MAX bitmaps in one object; split by allowed set");
+  if (n_bits != 0 && stride_words < (n_bits + 63) / 64) return fail(VERS_ERR_INVALID, who + ": filter_stride_words is smaller than ceil(n_bits / 64)");
+  if (n_bits != 0 && filters == nullptr) return fail(VERS_ERR_INVALID, who + ": n_bits > 0 with NULL filters");
+  std::shared_lock<std::shared_mutex> lk(h->index);
+  DeviceGuard g(h->device);
+  std::unique_ptr<vers_filter> o(new (std::nothrow) vers_filter());
+  if (!o) return fail(VERS_ERR_INVALID, "out of host memory");
+  o->owner = h;
+  o->n_filters = n_filters;
+  o->n_bits = n_bits;
+  o->words = std::max<uint64_t>(1, (n_bits + 63) / 64);
+  VERS_HIP_TRY(hipEventCreateWithFlags(&o->ready, hipEventDisableTiming));
+  if (int32_t rc = o->bits.reserve((size_t)n_filters * o->words * sizeof(uint64_t))) return rc;
+  if (n_bits == 0) VERS_HIP_TRY(hipMemset(o->bits.p, 0, (size_t)n_filters * o->words * sizeof(uint64_t)));
+  else  // the object's own copy, packed: the caller's array may change or go
+    VERS_HIP_TRY(hipMemcpy2D(o->bits.p, o->words * sizeof(uint64_t), filters, stride_words * sizeof(uint64_t), o->words * sizeof(uint64_t), n_filters,
+                             on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
+  WsLease lease(h, true, nullptr);
+  if (lease.rc) return lease.rc;
+  if (int32_t rc = lease.order_on(nullptr)) return rc;
+  W->ev_on = false;  // (no search: nothing for the scan-timing ring)
+  // the masks for the index as it stands, in the form the object's first search can ask for without a second pass being likelier
+  if (int32_t rc = prepared_sync(h, o.get(), n_filters == 1 ? 0 : 1, false, nullptr)) return rc;
+  VERS_HIP_TRY(hipStreamSynchronize(nullptr));
+  o->pending = false;
+  {
+    std::lock_guard<std::mutex> rk(h->flt_mu);
+    h->filters.push_back(o.get());
+  }
+  *out = o.release();
+  return VERS_OK;
+}
+
+// what the four prepared searches refuse on top of the _filtered_sharded_dev calls' checks
+int32_t prepared_check(vers_ivf_t* h, const char* who, const vers_filter_t* f) {
+  if (!h) return fail(VERS_ERR_INVALID, "null handle");
+  if (!f) return fail(VERS_ERR_INVALID, std::string(who) + ": NULL filter object");
+  if (!filter_is_ours(h, f)) return fail(VERS_ERR_INVALID, std::string(who) + ": the filter object was not prepared on this handle (or is destroyed)");
+  {
+    std::shared_lock<std::shared_mutex> lk(h->index);
+    if (h->world > 1)
+      return fail(VERS_ERR_INVALID, std::string(who) + ": the handle is sharded by cluster; prepared filters on a sharded handle are out of scope (use the _filtered_sharded_dev calls)");
+  }
+  return VERS_OK;
+}
+void prepared_filter(const vers_filter_t* f, const uint32_t* filter_of_dev, ShardFilter& sf) {
+  sf = ShardFilter{f->bits.as<uint64_t>(), f->words, f->n_filters, f->n_bits, filter_of_dev};
+  sf.prep = const_cast<vers_filter_t*>(f);
+}
+}  // namespace
+
+int32_t vers_ivf_filter_prepare(vers_ivf_t* h, const uint64_t* filters, uint64_t filter_stride_words, uint32_t n_filters, uint64_t n_bits, vers_filter_t** out) {
+  return filter_prepare_common(h, "vers_ivf_filter_prepare", filters, false, filter_stride_words, n_filters, n_bits, out);
+}
+
+int32_t vers_ivf_filter_prepare_dev(vers_ivf_t* h, const uint64_t* filters_dev, uint64_t filter_stride_words, uint32_t n_filters, uint64_t n_bits, vers_filter_t** out) {
+  return filter_prepare_common(h, "vers_ivf_filter_prepare_dev", filters_dev, true, filter_stride_words, n_filters, n_bits, out);
+}
+
+int32_t vers_ivf_filter_refresh(vers_ivf_t* h, vers_filter_t* f, void* stream) {
+  if (!h) return fail(VERS_ERR_INVALID, "null handle");
+  if (!f || !filter_is_ours(h, f)) return fail(VERS_ERR_INVALID, "vers_ivf_filter_refresh: not a filter object of this handle");
+  std::shared_lock<std::shared_mutex> lk(h->index);
+  DeviceGuard g(h->device);
+  WsLease lease(h, true, (hipStream_t)stream);
+  if (lease.rc) return lease.rc;
+  if (int32_t rc = lease.order_on((hipStream_t)stream)) return rc;
+  W->ev_on = false;  // (no search: nothing for the scan-timing ring)
+  return prepared_sync(h, f, -1, false, (hipStream_t)stream);
+}
+
+int32_t vers_ivf_filter_info(vers_ivf_t* h, const vers_filter_t* f, uint64_t* out8) {
+  if (!h) return fail(VERS_ERR_INVALID, "null handle");
+  if (!f || !out8 || !filter_is_ours(h, f)) return fail(VERS_ERR_INVALID, "vers_ivf_filter_info: not a filter object of this handle, or NULL out8");
+  std::shared_lock<std::shared_mutex> lk(h->index);
+  vers_filter_t* o = const_cast<vers_filter_t*>(f);
+  std::lock_guard<std::mutex> ok(o->mu);
+  out8[0] = o->n_filters; out8[1] = o->n_bits; out8[2] = o->device_bytes(); out8[3] = o->builds; out8[4] = o->tails; out8[5] = o->hits;
+  out8[6] = (o->built && o->seen_moved == h->flt_moved && o->seen_appended == h->flt_appended) ? 1 : 0;
+  out8[7] = 0;
+  return VERS_OK;
+}
+
+int32_t vers_ivf_filter_destroy(vers_ivf_t* h, vers_filter_t* f) {
+  if (!h) return fail(VERS_ERR_INVALID, "null handle");
+  if (!f) return VERS_OK;
+  {
+    std::lock_guard<std::mutex> lk(h->flt_mu);
+    auto it = std::find(h->filters.begin(), h->filters.end(), f);
+    if (it == h->filters.end()) return fail(VERS_ERR_INVALID, "vers_ivf_filter_destroy: not a filter object of this handle");
+    h->filters.erase(it);
+  }
+  DeviceGuard g(h->device);
+  (void)hipDeviceSynchronize();  // searches in flight on any stream may still read the object's arrays
+  delete f;
+  return VERS_OK;
+}
+
+int32_t vers_ivf_search_prepared_dev(vers_ivf_t* h, const float* queries_dev, uint64_t ldq_floats, uint32_t b, uint32_t top_k, uint32_t nprobe, const vers_filter_t* f,
+                                     const uint32_t* filter_of_dev, const vers_adaptive_t* adaptive, uint64_t* out_ids_dev, float* out_dist_dev, uint32_t* out_count_dev,
+                                     void* stream) {
+  const char* who = "vers_ivf_search_prepared_dev";
+  if (int32_t rc = prepared_check(h, who, f)) return rc;
+  ShardFilter sf;
+  prepared_filter(f, filter_of_dev, sf);
+  return filtered_sharded_common(h, who, true, nullptr, queries_dev, ldq_floats, b, top_k, nprobe, sf, adaptive, out_ids_dev, out_dist_dev,
+                                 out_count_dev, stream);
+}
+
+int32_t vers_ivf_search_exhaustive_prepared_dev(vers_ivf_t* h, const float* queries_dev, uint64_t ldq_floats, uint32_t b, uint32_t top_k, uint32_t metric,
+                                                const vers_filter_t* f, const uint32_t* filter_of_dev, uint64_t* out_ids_dev, float* out_dist_dev,
+                                                uint32_t* out_count_dev, void* stream) {
+  const char* who = "vers_ivf_search_exhaustive_prepared_dev";
+  if (int32_t rc = prepared_check(h, who, f)) return rc;
+  ShardFilter sf;
+  prepared_filter(f, filter_of_dev, sf);
+  return filtered_sharded_common(h, who, false, nullptr, queries_dev, ldq_floats, b, top_k, metric, sf, nullptr, out_ids_dev, out_dist_dev,
+                                 out_count_dev, stream);
+}
+
+int32_t vers_ivf_range_search_prepared_dev(vers_ivf_t* h, const float* queries_dev, uint64_t ldq_floats, uint32_t b, const float* radius_dev, uint32_t nprobe,
+                                           uint32_t flags, const vers_filter_t* f, const uint32_t* filter_of_dev, uint64_t* out_lims_dev, uint64_t* out_ids_dev,
+                                           float* out_dist_dev, uint64_t cap, uint64_t* out_total, void* stream) {
+  const char* who = "vers_ivf_range_search_prepared_dev";
+  if (int32_t rc = prepared_check(h, who, f)) return rc;
+  ShardFilter sf;
+  prepared_filter(f, filter_of_dev, sf);
+  return range_filtered_sharded_common(h, who, true, nullptr, queries_dev, ldq_floats, b, radius_dev, nprobe, flags, sf, out_lims_dev,
+                                       out_ids_dev, out_dist_dev, cap, out_total, stream);
+}
+
+int32_t vers_ivf_range_search_exhaustive_prepared_dev(vers_ivf_t* h, const float* queries_dev, uint64_t ldq_floats, uint32_t b, const float* radius_dev,
+                                                      uint32_t metric, uint32_t flags, const vers_filter_t* f, const uint32_t* filter_of_dev, uint64_t* out_lims_dev,
+                                                      uint64_t* out_ids_dev, float* out_dist_dev, uint64_t cap, uint64_t* out_total, void* stream) {
+  const char* who = "vers_ivf_range_search_exhaustive_prepared_dev";
+  if (int32_t rc = prepared_check(h, who, f)) return rc;
+  ShardFilter sf;
+  prepared_filter(f, filter_of_dev, sf);
+  return range_filtered_sharded_common(h, who, false, nullptr, queries_dev, ldq_floats, b, radius_dev, metric, flags, sf, out_lims_dev,
+                                       out_ids_dev, out_dist_dev, cap, out_total, stream);
 }
 
 int32_t vers_range_phases(double* out8, int32_t reset) {

@@ -847,6 +847,53 @@ class IVFFlatIndex:
         return self.range_search_filtered_sharded_dev(comm, q_ptr, ldq, b, radius_ptr, 0, flags, filt, lims_ptr, ids_ptr, dist_ptr, cap, stream,
                                                       exhaustive_metric=metric)
 
+    # -- prepared filters (vers_hip.h): masks kept across calls, refreshed when rows move ------------------------------------------------
+    def prepare_filter(self, filters, n_bits: int) -> "PreparedFilter":
+        """A PreparedFilter from host bitmaps: u64 [n_filters][stride_words] (one row per bitmap; a 1-d array is one bitmap), copied by the
+        library (vers_ivf_filter_prepare)."""
+        f = np.ascontiguousarray(np.atleast_2d(np.asarray(filters, dtype=np.uint64)))
+        out = _vp(None)
+        check(lib().vers_ivf_filter_prepare(self._h, _ptr(f) if f.size else None, f.shape[1], f.shape[0], n_bits, C.byref(out)))
+        return PreparedFilter(self, out.value)
+
+    def prepare_filter_dev(self, filters_ptr: int, stride_words: int, n_filters: int, n_bits: int) -> "PreparedFilter":
+        """The same from bitmaps on the device (vers_ivf_filter_prepare_dev)."""
+        out = _vp(None)
+        check(lib().vers_ivf_filter_prepare_dev(self._h, _vp(filters_ptr) if filters_ptr else None, stride_words, n_filters, n_bits, C.byref(out)))
+        return PreparedFilter(self, out.value)
+
+    @staticmethod
+    def _pf(pf):
+        return _vp(pf.ptr if isinstance(pf, PreparedFilter) else pf)
+
+    def search_prepared_dev(self, q_ptr: int, ldq: int, b: int, top_k: int, nprobe: int, pf, filter_of_ptr: int, ids_ptr: int, dist_ptr: int,
+                            cnt_ptr: int, adaptive=None, stream: int = 0):
+        """search_filtered_sharded_dev (no exchange) with a PreparedFilter in the bitmaps' place (vers_ivf_search_prepared_dev)."""
+        ad, adp = self._adaptive(adaptive)
+        check(lib().vers_ivf_search_prepared_dev(self._h, _vp(q_ptr), ldq, b, top_k, nprobe, self._pf(pf), _vp(filter_of_ptr) if filter_of_ptr else None, adp,
+                                                 _vp(ids_ptr), _vp(dist_ptr), _vp(cnt_ptr), _vp(stream)))
+
+    def search_exhaustive_prepared_dev(self, q_ptr: int, ldq: int, b: int, top_k: int, metric: int, pf, filter_of_ptr: int, ids_ptr: int,
+                                       dist_ptr: int, cnt_ptr: int, stream: int = 0):
+        check(lib().vers_ivf_search_exhaustive_prepared_dev(self._h, _vp(q_ptr), ldq, b, top_k, metric, self._pf(pf),
+                                                            _vp(filter_of_ptr) if filter_of_ptr else None, _vp(ids_ptr), _vp(dist_ptr), _vp(cnt_ptr), _vp(stream)))
+
+    def range_search_prepared_dev(self, q_ptr: int, ldq: int, b: int, radius_ptr: int, nprobe: int, flags: int, pf, filter_of_ptr: int,
+                                  lims_ptr: int, ids_ptr: int, dist_ptr: int, cap: int, stream: int = 0, exhaustive_metric=None) -> int:
+        """range_search_filtered_sharded_dev (no exchange) with a PreparedFilter (vers_ivf_range_search_prepared_dev / _exhaustive_prepared_dev).
+        Returns the total."""
+        total = C.c_uint64(0)
+        fn = lib().vers_ivf_range_search_prepared_dev if exhaustive_metric is None else lib().vers_ivf_range_search_exhaustive_prepared_dev
+        check(fn(self._h, _vp(q_ptr), ldq, b, _vp(radius_ptr), nprobe if exhaustive_metric is None else exhaustive_metric, flags, self._pf(pf),
+                 _vp(filter_of_ptr) if filter_of_ptr else None, _vp(lims_ptr), _vp(ids_ptr) if ids_ptr else None, _vp(dist_ptr) if dist_ptr else None, cap,
+                 C.byref(total), _vp(stream)))
+        return int(total.value)
+
+    def range_search_exhaustive_prepared_dev(self, q_ptr: int, ldq: int, b: int, radius_ptr: int, metric: int, flags: int, pf, filter_of_ptr: int,
+                                             lims_ptr: int, ids_ptr: int, dist_ptr: int, cap: int, stream: int = 0) -> int:
+        return self.range_search_prepared_dev(q_ptr, ldq, b, radius_ptr, 0, flags, pf, filter_of_ptr, lims_ptr, ids_ptr, dist_ptr, cap, stream,
+                                              exhaustive_metric=metric)
+
     def poll(self, stream: int = 0):
         check(lib().vers_ivf_poll(self._h, _vp(stream)))
 
@@ -874,6 +921,29 @@ class IVFFlatIndex:
             check(lib().vers_ivf_remove_batch(self._h, _ptr(gone), gone.size, C.byref(removed)))
             assert removed.value == gone.size, (removed.value, gone.size)
         return self
+
+
+class PreparedFilter:
+    """A vers_filter_t of one IVFFlatIndex: bitmaps the library copied and the masks it keeps for them.  Close it before (or let it go with)
+    the index; the index frees the objects still alive when it is closed."""
+    INFO = ("n_filters", "n_bits", "device_bytes", "builds", "tail_refreshes", "hits", "fresh", "reserved")
+
+    def __init__(self, index: IVFFlatIndex, ptr: int):
+        self.index, self.ptr = index, ptr
+
+    def refresh(self, stream: int = 0):
+        """Brings the masks up to date now, on `stream`, so that the next search finds them fresh (vers_ivf_filter_refresh)."""
+        check(lib().vers_ivf_filter_refresh(self.index._h, _vp(self.ptr), _vp(stream)))
+
+    def info(self) -> dict:
+        out = np.zeros(8, dtype=np.uint64)
+        check(lib().vers_ivf_filter_info(self.index._h, _vp(self.ptr), _ptr(out)))
+        return dict(zip(self.INFO, map(int, out)))
+
+    def close(self):
+        if self.ptr and self.index._h:
+            check(lib().vers_ivf_filter_destroy(self.index._h, _vp(self.ptr)))
+        self.ptr = 0
 
 
 # The index file of Index::save_index (base.rs:31-43): bincode 1.3.3 with default options over the five fields of
