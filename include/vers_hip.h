@@ -370,6 +370,45 @@ int32_t vers_ivf_live_count(vers_ivf_t* h, uint64_t* out_live);
  * pass over row_ids, a sharded handle's exchange), [5] compaction, [6] length tables, [7] derived arrays (|x|^2, shadow, row-major
  * copy of the touched tiles).  reset != 0 zeroes them. */
 int32_t vers_remove_phases(double* out8, int32_t reset);
+/* Update (extension: the reference cannot change a stored vector; defined on its five fields, like the removal).  For every i of the call,
+ * with v = vec_ids[i] and x = rows[i]:
+ *     if v is in no list (removed earlier)   -> skipped, nothing changes for v
+ *     else values[v] = x;  c = first-minimum centroid of x in the index's metric (ivfflat.rs:201-207, the rule of add)
+ *          if c != assignments[v] { ids[assignments[v]].retain(|&y| y != v); assignments[v] = c;
+ *                                   ids[c].insert(ids[c].partition_point(|&y| y < v), v) }       -- its SORTED place, not the end
+ * A row that keeps its cluster keeps its position in the list; a row that changes cluster enters the new list at its sorted place by vec
+ * id, so every list stays ascending in vec id -- what vers_ivf_upload ("ids[c] is implied"), load_index and the streamed upload rely on.
+ * In one sentence: AFTER AN UPDATE THE HANDLE IS, BIT FOR BIT IN EVERYTHING OBSERVABLE, A HANDLE THAT RECEIVED
+ * vers_ivf_upload(values', centroids, assignments') FOLLOWED BY vers_ivf_remove_batch OF THE IDS THAT ARE IN NO LIST.  The vec ids are kept
+ * (bitmap filters and prepared vers_filter_t stay valid), centroids do not move, n of vers_ivf_info, the id the next add hands out and the
+ * live count do not change; ties in the (distance, probe rank, list position) order break as on that fresh handle.
+ *   out_status   : [n] nullable; 0 = overwritten in place (cluster kept), 1 = moved to another list, 2 = skipped (the id is in no list).
+ *   out_clusters : [n] nullable; the first-minimum centroid of rows[i] for EVERY i, skipped ones included (the host mirrors assignments).
+ *   out_counts   : [4] nullable, host memory in both calls; stayed | moved | skipped | re-layouts of the storage (0 or 1).
+ *   rows         : as vers_ivf_add_batch: pitch >= 4 d bytes (a multiple of 4), resp. ld_floats >= d and a multiple of 4; padding columns
+ *                  are never read.
+ *   ALL OR NOTHING -- every check happens before the first byte of the index is written: any id >= n -> VERS_ERR_INVALID; the same id
+ *                  twice in one call -> VERS_ERR_INVALID (a loop of single updates would let the last one win; refusing keeps the batch
+ *                  order-free); a NaN distance on any row with k >= 2 -> VERS_ERR_NAN (k == 1: a NaN row is accepted, as in add); no
+ *                  centroids, or a streamed upload in progress -> VERS_ERR_EMPTY; a handle sharded by cluster (world > 1) ->
+ *                  VERS_ERR_INVALID (not supported yet).  On any of these the index is unchanged and searchable and the outputs are
+ *                  untouched.  THIS DIFFERS FROM vers_ivf_add_batch ON PURPOSE, which keeps the rows in front of a NaN.  A call of more
+ *                  than one staging chunk (option "add_batch_rows") stages its rows twice for it: once to assign and check, once to place.
+ *                  n == 0: no-op.  A NULL handle: VERS_ERR_INVALID before anything else is looked at.
+ *   _dev         : vec_ids_dev, rows_dev, out_clusters_dev and out_status_dev are device memory.
+ * Synchronous; holds the handle exclusively and waits for searches in flight, like vers_ivf_add_batch / vers_ivf_remove_batch.  The maxima
+ * the search certificates charge only grow (an overwritten larger row still counts), as after a removal; vers_ivf_compact re-tightens
+ * them.  Prepared filters: an update that moved a row (or re-laid-out storage) makes them rebuild at their next use; an update in which
+ * every row stayed leaves them valid as they are. */
+int32_t vers_ivf_update_batch(vers_ivf_t* h, const uint64_t* vec_ids, const float* rows, uint64_t n, uint64_t row_stride_bytes,
+                              uint64_t* out_clusters, uint8_t* out_status, uint64_t* out_counts);
+int32_t vers_ivf_update_batch_dev(vers_ivf_t* h, const uint64_t* vec_ids_dev, const float* rows_dev, uint64_t n, uint64_t ld_floats,
+                                  uint64_t* out_clusters_dev, uint8_t* out_status_dev, uint64_t* out_counts);
+/* The update calls of this process by PHASE (host wall clock in ms, the stream synchronised at each phase's end).  out[10]: [0] calls,
+ * [1] rows passed, [2] rows that stayed, [3] rows that moved, [4] staging of the rows, [5] assign, [6] mark + locate (id table, range and
+ * duplicate check, the pass over row_ids), [7] overwrite in place (and the movers into their stage), [8] compaction + merge (the movers'
+ * sort and a re-layout, if any, included), [9] tables + derived arrays.  reset != 0 zeroes them. */
+int32_t vers_update_phases(double* out10, int32_t reset);
 /* Compaction (extension; in the reference's terms: nothing -- ids[c].shrink_to_fit()).  Nothing observable through the reference's five
  * fields changes: n of vers_ivf_info, the vec id the next add hands out, centroids, live count, every list's rows, ids and order, and every
  * search result in every mode and on every path, bit for bit.  What changes is the storage behind them:

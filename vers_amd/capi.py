@@ -62,6 +62,8 @@ SIGNATURES = {
     "vers_ivf_remove_batch": (C.c_int32, [_vp, _vp, C.c_uint64, C.POINTER(C.c_uint64)]),
     "vers_ivf_remove_batch_dev": (C.c_int32, [_vp, _vp, C.c_uint64, _vp, C.POINTER(C.c_uint64)]),
     "vers_ivf_live_count": (C.c_int32, [_vp, C.POINTER(C.c_uint64)]),
+    "vers_ivf_update_batch": (C.c_int32, [_vp, _vp, _vp, C.c_uint64, C.c_uint64, _vp, _vp, C.POINTER(C.c_uint64)]),
+    "vers_ivf_update_batch_dev": (C.c_int32, [_vp, _vp, _vp, C.c_uint64, C.c_uint64, _vp, _vp, C.POINTER(C.c_uint64)]),
     "vers_ivf_search": (C.c_int32, [_vp, _vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, _vp, _vp, _vp]),
     "vers_ivf_search_dev": (C.c_int32, [_vp, _vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, _vp, _vp, _vp, _vp]),
     "vers_ivf_poll": (C.c_int32, [_vp, _vp]),
@@ -104,6 +106,7 @@ SIGNATURES = {
     "vers_build_phases": (C.c_int32, [C.POINTER(C.c_double), C.c_int32]),
     "vers_add_batch_phases": (C.c_int32, [C.POINTER(C.c_double), C.c_int32]),
     "vers_remove_phases": (C.c_int32, [C.POINTER(C.c_double), C.c_int32]),
+    "vers_update_phases": (C.c_int32, [C.POINTER(C.c_double), C.c_int32]),
     "vers_ivf_compact": (C.c_int32, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "vers_compact_phases": (C.c_int32, [C.POINTER(C.c_double), C.c_int32]),
     "vers_ivf_range_search": (C.c_int32, [_vp, _vp, C.c_uint64, C.c_uint32, _vp, C.c_uint32, C.c_uint32, _vp, _vp, _vp, C.c_uint64,
@@ -493,6 +496,14 @@ def remove_phases(reset=False) -> dict:
     v = (C.c_double * 8)()
     check(lib().vers_remove_phases(v, 1 if reset else 0))
     keys = ("calls", "ids", "removed", "stage_ms", "mark_ms", "compact_ms", "tables_ms", "derive_ms")
+    return dict(zip(keys, (float(x) for x in v)))
+
+
+def update_phases(reset=False) -> dict:
+    """The update_batch calls of this process by phase, host wall clock in ms (vers_update_phases)."""
+    v = (C.c_double * 10)()
+    check(lib().vers_update_phases(v, 1 if reset else 0))
+    keys = ("calls", "rows", "stayed", "moved", "stage_ms", "assign_ms", "locate_ms", "overwrite_ms", "merge_ms", "derive_ms")
     return dict(zip(keys, (float(x) for x in v)))
 
 

@@ -15,6 +15,7 @@
 #include "ivf_handle.hpp"
 #include "prescan.hip.h"
 #include "head_filter.hip.h"
+#include "update_plan.hpp"
 
 namespace vers {
 
@@ -532,6 +533,142 @@ __global__ __launch_bounds__(kRmWaves * 64) void remove_compact_kernel(const Rem
       for (uint32_t u = 0; u < kRmCols4; ++u) {
         v[u] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
         if (src != 0xFFFFFFFFu && cb + u < ld4) v[u] = sp[(uint64_t)(cb + u) * 64u];
+      }
+      __builtin_amdgcn_wave_barrier();  // every load of the pieces above is issued before the first store below
+#pragma unroll
+      for (uint32_t u = 0; u < kRmCols4; ++u)
+        if (cb + u < ld4) dp[(uint64_t)(cb + u) * 64u] = v[u];
+    }
+    __syncthreads();  // the map of this tile is read by every wave until here
+  }
+}
+
+// ---- vers_ivf_update_batch: mark, locate, overwrite in place, backward merge of the lists that gain rows (update_plan.hpp) ---------------
+// slot[v] = index of the update of vec id v in the call (upd::kNone: none).  *bad |= 1: an id >= n_total; |= 2: an id twice (the exchange
+// found the slot taken).  Nothing of the index has been written by then.
+__global__ void update_mark_kernel(const uint64_t* ids, uint64_t m, uint64_t n_total, uint32_t* slot, uint32_t* bad) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= m) return;
+  const uint64_t v = ids[i];
+  if (v >= n_total) { atomicOr(bad, 1u); return; }
+  if (atomicExch(&slot[v], (uint32_t)i) != upd::kNone) atomicOr(bad, 2u);
+}
+
+// One pass over row_ids, as remove_scan_rows_kernel: a stored row whose vec id has update i either stays (its list is a32[i]: rel[i] = its
+// position in the list) or moves: its bit in the removal bitmap, one more row leaving its list (and the list's first tile, list-relative,
+// that loses one -- what remove_compact_kernel consumes), one more entering list a32[i], and the pair ((new list, vec id), i) appended for
+// the sort.  Updates never met keep status 2 (the id is in no list).  Positions are list-relative: a re-layout may follow.
+__global__ void update_locate_kernel(const uint32_t* row_ids, uint64_t cap_rows, const uint32_t* slot, uint64_t n_total, const uint32_t* list_off, uint32_t k,
+                                     const uint32_t* a32, uint8_t* status, uint32_t* rel, uint32_t* bitmap, uint32_t* out_cnt, uint32_t* first_tile,
+                                     uint32_t* in_cnt, uint32_t* n_mv, uint32_t mv_cap, uint64_t* mv_key, uint64_t* mv_val) {
+  for (uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; r < cap_rows; r += (uint64_t)gridDim.x * blockDim.x) {
+    const uint32_t id = row_ids[r];
+    if (id == upd::kNone || id >= n_total) continue;
+    const uint32_t i = slot[id];
+    if (i == upd::kNone) continue;
+    const uint32_t c = upd::list_of_row(list_off, k, r), a = a32[i];
+    const uint32_t p = (uint32_t)(r - list_off[c]);
+    const uint8_t s = upd::classify(c, a);
+    status[i] = s;
+    if (s == upd::kStayed) { rel[i] = p; continue; }
+    atomicOr(&bitmap[id >> 5], 1u << (id & 31));
+    atomicAdd(&out_cnt[c], 1u);
+    atomicMin(&first_tile[c], p >> 6);
+    atomicAdd(&in_cnt[a], 1u);
+    const uint32_t j = atomicAdd(n_mv, 1u);
+    if (j >= mv_cap) continue;  // (a vec id stored twice: the host sees the count and refuses)
+    mv_key[j] = ((uint64_t)a << 32) | id;
+    mv_val[j] = i;
+  }
+}
+
+// mv_row[i] = the place of update i among the movers sorted by (new list, vec id)
+__global__ void update_mover_rows_kernel(const uint64_t* vals_sorted, uint32_t n_mv, uint32_t* mv_row) {
+  const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
+  if (q < n_mv) mv_row[(uint32_t)vals_sorted[q]] = q;
+}
+
+// The staged chunk X [m][ldx] (zero-padded; updates i0 .. i0 + m of the call): a row that stays goes over its storage row, 16-byte piece by
+// piece (tile[c4 * 64 + r]: nothing else of the tile is read or written); a row that moves is copied to its place in the movers' stage
+// S [n_mv][ldx], where the merge finds the rows of a list side by side in ascending vec id.
+__global__ void update_place_kernel(const float* X, uint32_t ldx, uint32_t ld, uint64_t i0, uint32_t m, const uint8_t* status, const uint32_t* a32,
+                                    const uint32_t* rel, const uint32_t* mv_row, const uint32_t* list_off, float* rows, float* S) {
+  const uint32_t ld4 = ld / 4, ldx4 = ldx / 4;
+  const uint64_t total = (uint64_t)m * ld4;
+  for (uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (uint64_t)gridDim.x * blockDim.x) {
+    const uint64_t il = t / ld4, i = i0 + il;
+    const uint32_t c4 = (uint32_t)(t % ld4);
+    const uint8_t s = status[i];
+    if (s == upd::kSkipped) continue;
+    f32x4 v = {0.0f, 0.0f, 0.0f, 0.0f};
+    if (c4 < ldx4) v = reinterpret_cast<const f32x4*>(X + il * ldx)[c4];
+    if (s == upd::kStayed) {
+      const uint64_t r = (uint64_t)list_off[a32[i]] + rel[i];
+      *reinterpret_cast<f32x4*>(rows + blocked_index(r, c4 * 4, ld)) = v;
+    } else if (c4 < ldx4) {
+      reinterpret_cast<f32x4*>(S + (uint64_t)mv_row[i] * ldx)[c4] = v;
+    }
+  }
+}
+
+// pos[q] = #ids of the mover's new list (after the movers that leave it are gone: mid_len) below its vec id
+__global__ void update_positions_kernel(const uint64_t* keys_sorted, uint32_t n_mv, const uint32_t* list_off, const uint32_t* mid_len, const uint32_t* row_ids,
+                                        uint32_t* pos) {
+  const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
+  if (q >= n_mv) return;
+  const uint32_t c = (uint32_t)(keys_sorted[q] >> 32), v = (uint32_t)keys_sorted[q];
+  pos[q] = upd::insertion_point(row_ids + list_off[c], mid_len[c], v);
+}
+
+// One list that gains rows: its first storage row, its length after the movers left, the rows entering and where they start in the sorted order.
+struct MergeJob {
+  uint32_t off, len, n_in, in0;
+};
+
+// One BLOCK per job walks the list's destination tiles in DESCENDING order, from the last tile of the merged list down to the tile of the
+// first insertion point; tiles in front of it are not touched.  Destination row j takes upd::merge_source(j): an old row s <= j of the list
+// or a new row of S.  Every destination is >= its source, so the sources of a tile lie in that tile or in front of it, where nothing has
+// been written yet, and the move is safe IN PLACE with remove_compact_kernel's discipline --
+//   map  : wave 0 computes the tile's 64 sources and reads their vec ids into LDS; row_ids of the tile are written after the barrier behind
+//          those reads (the tiles still to come read only rows in front of this tile).
+//   rows : a float4 COLUMN of a tile is its own 1 KiB piece and rows move within their column only.  Each wave owns its columns: it reads
+//          the 64 sources of a destination piece into registers and then writes the whole piece -- all loads of a piece precede its stores in
+//          the one wave that touches that column.
+// Rows behind the merged list in its last tile are slack: row_ids 0xFFFFFFFF and zeros.
+__global__ __launch_bounds__(kRmWaves * 64) void update_merge_kernel(const MergeJob* jobs, const uint32_t* pos_all, const uint64_t* keys_sorted, const float* S,
+                                                                     uint32_t ldx, uint32_t ld, float* rows, uint32_t* row_ids) {
+  __shared__ uint32_t s_src[kWave], s_id[kWave];
+  const MergeJob jb = jobs[blockIdx.x];
+  const uint32_t tid = threadIdx.x, lane = tid & 63u, wv = tid >> 6;
+  const uint32_t ld4 = ld / 4, ldx4 = ldx / 4;
+  f32x4* const base4 = reinterpret_cast<f32x4*>(rows) + (uint64_t)jb.off * ld4;
+  const f32x4* const S4 = reinterpret_cast<const f32x4*>(S) + (uint64_t)jb.in0 * ldx4;
+  uint32_t* const ids = row_ids + jb.off;
+  const uint32_t* const pos = pos_all + jb.in0;
+  const uint32_t t_first = upd::merge_first_tile(pos), t_last = upd::merge_last_tile(jb.len, jb.n_in);
+  for (uint32_t T = t_last + 1u; T-- > t_first;) {
+    if (tid < 64u) {
+      const uint32_t src = upd::merge_source(pos, jb.n_in, jb.len, T * 64u + tid);
+      uint32_t id = upd::kNone;
+      if (src != upd::kNone) id = (src & upd::kNewBit) ? (uint32_t)keys_sorted[jb.in0 + (src & ~upd::kNewBit)] : ids[src];
+      s_src[tid] = src;
+      s_id[tid] = id;
+    }
+    __syncthreads();
+    if (tid < 64u) ids[T * 64u + tid] = s_id[tid];  // (T * 64 + 63 < round_up(len + n_in, 64) <= the list's capacity)
+    const uint32_t src = s_src[lane];
+    const bool is_new = src != upd::kNone && (src & upd::kNewBit) != 0u, is_old = src != upd::kNone && !is_new;
+    const uint32_t s0 = is_old ? src : 0u, t0 = is_new ? (src & ~upd::kNewBit) : 0u;
+    const f32x4* const sp = base4 + (uint64_t)(s0 >> 6) * 64u * ld4 + (s0 & 63u);
+    const f32x4* const np = S4 + (uint64_t)t0 * ldx4;
+    f32x4* const dp = base4 + (uint64_t)T * 64u * ld4 + lane;
+    for (uint32_t cb = wv * kRmCols4; cb < ld4; cb += kRmWaves * kRmCols4) {
+      f32x4 v[kRmCols4];
+#pragma unroll
+      for (uint32_t u = 0; u < kRmCols4; ++u) {
+        v[u] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+        if (is_old && cb + u < ld4) v[u] = sp[(uint64_t)(cb + u) * 64u];
+        if (is_new && cb + u < ldx4) v[u] = np[cb + u];  // (the stage's padding is zero; columns >= ldx of a stored row are zero)
       }
       __builtin_amdgcn_wave_barrier();  // every load of the pieces above is issued before the first store below
 #pragma unroll
@@ -2054,6 +2191,307 @@ int32_t remove_batch_locked(vers_ivf* h, const uint64_t* ids_host, const uint64_
   return VERS_OK;
 }
 
+// ---- update_batch: values[v] = x for many v, each row to the list of its first-minimum centroid (see vers_hip.h) -------------------------
+constexpr int kUpdatePhases = 10;
+static double g_up[kUpdatePhases] = {};  // vers_update_phases: calls, rows, stayed, moved, stage, assign, mark + locate, overwrite, compact + merge, tables + derive (ms)
+
+// rows [s0, s0 + m) of the call -> ab.stage [m][ldx], zero-padded (add_batch_locked's staging: through the pinned buffer, or from rows_dev)
+static int32_t update_stage_chunk(vers_ivf* h, const float* rows_host, uint64_t row_stride_bytes, const float* rows_dev, uint64_t ld_floats, uint64_t s0,
+                                  uint32_t m) {
+  const uint32_t ldx = h->ldx, d = h->d;
+  auto& ab = h->ab;
+  if (rows_host) {
+    float* pin = (float*)ab.pin;
+    for (uint64_t i = 0; i < m; ++i) {
+      float* dst = pin + i * ldx;
+      std::memcpy(dst, (const char*)rows_host + (s0 + i) * row_stride_bytes, (size_t)d * 4);
+      for (uint32_t j = d; j < ldx; ++j) dst[j] = 0.0f;
+    }
+    VERS_HIP_TRY(hipMemcpyAsync(ab.stage.p, pin, (size_t)m * ldx * 4, hipMemcpyHostToDevice, nullptr));
+  } else {
+    const uint64_t blocks = std::min<uint64_t>((uint64_t)h->n_cu * 8, ((uint64_t)m * (ldx / 4) + 255) / 256);
+    hipLaunchKernelGGL(add_stage_rows_kernel, dim3((unsigned)blocks), dim3(256), 0, nullptr, rows_dev + s0 * ld_floats, ld_floats, d, ldx, (uint64_t)m,
+                       ab.stage.as<float>());
+    VERS_HIP_TRY(hipGetLastError());
+  }
+  return VERS_OK;
+}
+
+// ALL OR NOTHING: the range and duplicate checks (mark), the assignment of every row (NaN) and the plan (locate, lengths, at most one
+// re-layout, which moves rows but changes nothing observable) come before the first stored row is written.  A call of more than one staging
+// chunk (option "add_batch_rows") therefore stages its rows TWICE: once to assign and check, once to place -- the second pass over the
+// caller's rows is the price of refusing a NaN in the last chunk with the index untouched.  dev: the outputs but out_counts are device memory.
+int32_t update_batch_locked(vers_ivf* h, const uint64_t* ids_host, const uint64_t* ids_dev, const float* rows_host, uint64_t row_stride_bytes,
+                            const float* rows_dev, uint64_t ld_floats, uint64_t n, bool dev, uint64_t* out_clusters, uint8_t* out_status, uint64_t* out_counts) {
+  VERS_HIP_TRY(hipDeviceSynchronize());  // searches still in flight on any stream read the rows and tables this call changes
+  if (h->world > 1)
+    return fail(VERS_ERR_INVALID, "vers_ivf_update_batch: a handle sharded by cluster is not supported (the old and the new owner of a row differ)");
+  if (n == 0) {
+    if (out_counts) std::fill(out_counts, out_counts + 4, 0ull);
+    return VERS_OK;
+  }
+  if (h->k == 0) {
+    if (h->up.open) return fail(VERS_ERR_EMPTY, "update_batch while a streamed upload is in progress: the handle holds no index until vers_ivf_upload_end");
+    return fail(VERS_ERR_EMPTY, "update_batch on an index without centroids");
+  }
+  const uint32_t k = h->k, ldx = h->ldx;
+  const uint64_t nt_ids = h->n_total;
+  if (n > nt_ids) return fail(VERS_ERR_INVALID, "vers_ivf_update_batch: more ids than the index ever held (one is out of range or repeated): nothing updated");
+  const hipStream_t st = nullptr;
+  auto& ud = h->ud;
+  auto& ab = h->ab;
+  const size_t words = (size_t)((nt_ids + 31) / 32);
+  const uint64_t chunk = std::min<uint64_t>(n, (uint64_t)std::max<int64_t>(1, opt_get("add_batch_rows", 131072)));
+  if (int32_t rc = ud.slot.reserve(nt_ids * sizeof(uint32_t))) return rc;
+  if (int32_t rc = ud.a32.reserve(n * sizeof(uint32_t))) return rc;
+  if (int32_t rc = ud.status.reserve(n)) return rc;
+  if (int32_t rc = ud.rel.reserve(n * sizeof(uint32_t))) return rc;
+  if (int32_t rc = ud.mv_row.reserve(n * sizeof(uint32_t))) return rc;
+  if (int32_t rc = ud.cnt.reserve((4 * (size_t)k + 2) * sizeof(uint32_t))) return rc;
+  if (int32_t rc = ud.keys.reserve(2 * n * sizeof(uint64_t))) return rc;
+  if (int32_t rc = ud.vals.reserve(2 * n * sizeof(uint64_t) + 2 * sizeof(uint64_t))) return rc;
+  if (int32_t rc = h->rm.bitmap.reserve((words ? words : 1) * sizeof(uint32_t))) return rc;
+  if (int32_t rc = ab.stage.reserve(chunk * ldx * sizeof(float))) return rc;
+  if (int32_t rc = h->km.counts.reserve((2 * (size_t)k + 2) * sizeof(uint32_t))) return rc;
+  if (int32_t rc = h->pre_misc.reserve(64)) return rc;
+  if (rows_host && ab.pin_cap < chunk * ldx * sizeof(float)) {
+    ab.free_pin();
+    VERS_HIP_TRY(hipHostMalloc(&ab.pin, chunk * ldx * sizeof(float), hipHostMallocDefault));
+    ab.pin_cap = chunk * ldx * sizeof(float);
+  }
+  uint32_t* const a32 = ud.a32.as<uint32_t>();
+  uint32_t* const out_cnt = ud.cnt.as<uint32_t>();
+  uint32_t* const first_tile = out_cnt + k;
+  uint32_t* const in_cnt = out_cnt + 2 * (size_t)k;
+  uint32_t* const mid_len = out_cnt + 3 * (size_t)k;
+  uint32_t* const n_mv_dev = out_cnt + 4 * (size_t)k;
+  uint32_t* const bad = n_mv_dev + 1;
+  const uint64_t* ids = ids_dev;
+  ab_count(0, 1.0, g_up);
+  ab_count(1, (double)n, g_up);
+  // 1. the ids: one table entry per vec id, range- and duplicate-checked
+  {
+    AbClock clk(6, g_up);
+    if (ids_host) {
+      if (int32_t rc = ud.ids.reserve(n * sizeof(uint64_t))) return rc;
+      VERS_HIP_TRY(hipMemcpy(ud.ids.p, ids_host, n * sizeof(uint64_t), hipMemcpyHostToDevice));
+      ids = ud.ids.as<uint64_t>();
+    }
+    VERS_HIP_TRY(hipMemsetAsync(ud.slot.p, 0xFF, nt_ids * sizeof(uint32_t), st));
+    VERS_HIP_TRY(hipMemsetAsync(bad, 0, sizeof(uint32_t), st));
+    hipLaunchKernelGGL(update_mark_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, ids, n, nt_ids, ud.slot.as<uint32_t>(), bad);
+    VERS_HIP_TRY(hipGetLastError());
+    uint32_t any_bad = 0;
+    VERS_HIP_TRY(hipMemcpy(&any_bad, bad, sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (int32_t rc = clk.done()) return rc;
+    if (any_bad & 1u) return fail(VERS_ERR_INVALID, "vers_ivf_update_batch: vec id >= n (assignments.len() = " + std::to_string(nt_ids) + "): nothing updated");
+    if (any_bad & 2u) return fail(VERS_ERR_INVALID, "vers_ivf_update_batch: the same vec id twice in one call: nothing updated");
+  }
+  // 2. first-minimum centroid of every row of the call (ivfflat.rs:201-207), chunk by chunk
+  const bool one_chunk = chunk >= n;
+  for (uint64_t s0 = 0; s0 < n; s0 += chunk) {
+    const uint32_t m = (uint32_t)std::min<uint64_t>(chunk, n - s0);
+    {
+      AbClock clk(4, g_up);
+      if (int32_t rc = update_stage_chunk(h, rows_host, row_stride_bytes, rows_dev, ld_floats, s0, m)) return rc;
+      if (int32_t rc = clk.done()) return rc;
+    }
+    AbClock clk(5, g_up);
+    if (k == 1) {  // one centroid: every row stays there, a NaN one included (nothing is compared)
+      VERS_HIP_TRY(hipMemsetAsync(a32 + s0, 0, (size_t)m * sizeof(uint32_t), st));
+    } else {
+      if (int32_t rc = h->km.status.reserve(16)) return rc;
+      VERS_HIP_TRY(hipMemsetAsync(h->km.status.p, 0, 16, st));
+      if (int32_t rc = (km_use_mfma(m, k, h->d) ? km_assign_mfma : km_assign)(ab.stage.as<float>(), ldx, m, h->centroids.as<float>(), ldx, k, h->d, a32 + s0,
+                                                                              nullptr, h->km, h->n_cu, st, h->metric))
+        return rc;
+      uint32_t stw = 0;
+      VERS_HIP_TRY(hipMemcpy(&stw, h->km.status.p, 4, hipMemcpyDeviceToHost));
+      if (stw & 1u) {
+        VERS_HIP_TRY(hipMemsetAsync(h->km.status.p, 0, 16, st));
+        VERS_HIP_TRY(hipStreamSynchronize(st));
+        return fail(VERS_ERR_NAN, "NaN distance in update_batch (rows " + std::to_string(s0) + " .. " + std::to_string(s0 + m) + "): nothing updated");
+      }
+    }
+    if (int32_t rc = clk.done()) return rc;
+  }
+  // 3. locate: who stays where, who leaves which list for which
+  std::vector<uint32_t> cnt(3 * (size_t)k);
+  std::vector<uint8_t> status(n);
+  std::vector<uint32_t> a_host(n), rel;
+  uint32_t n_mv = 0;
+  uint64_t* const keys_in = ud.keys.as<uint64_t>();
+  uint64_t* const keys_out = keys_in + n;
+  uint64_t* const vals_in = ud.vals.as<uint64_t>();
+  uint64_t* const vals_out = vals_in + n;
+  uint64_t* const lims = vals_out + n;
+  {
+    AbClock clk(6, g_up);
+    VERS_HIP_TRY(hipMemsetAsync(bad, 0, sizeof(uint32_t), st));
+    hipLaunchKernelGGL(add_check_assign_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a32, (uint32_t)n, k, bad);
+    VERS_HIP_TRY(hipMemsetAsync(ud.status.p, upd::kSkipped, n, st));
+    VERS_HIP_TRY(hipMemsetAsync(h->rm.bitmap.p, 0, (words ? words : 1) * sizeof(uint32_t), st));
+    VERS_HIP_TRY(hipMemsetAsync(out_cnt, 0, (size_t)k * sizeof(uint32_t), st));
+    VERS_HIP_TRY(hipMemsetAsync(first_tile, 0xFF, (size_t)k * sizeof(uint32_t), st));
+    VERS_HIP_TRY(hipMemsetAsync(in_cnt, 0, (size_t)k * sizeof(uint32_t), st));
+    VERS_HIP_TRY(hipMemsetAsync(n_mv_dev, 0, sizeof(uint32_t), st));
+    if (h->cap_rows) {
+      const uint64_t blocks = std::min<uint64_t>((uint64_t)h->n_cu * 8, (h->cap_rows + 255) / 256);
+      hipLaunchKernelGGL(update_locate_kernel, dim3((unsigned)blocks), dim3(256), 0, st, (const uint32_t*)h->row_ids.as<uint32_t>(), h->cap_rows,
+                         (const uint32_t*)ud.slot.as<uint32_t>(), nt_ids, (const uint32_t*)h->list_off.as<uint32_t>(), k, (const uint32_t*)a32,
+                         ud.status.as<uint8_t>(), ud.rel.as<uint32_t>(), h->rm.bitmap.as<uint32_t>(), out_cnt, first_tile, in_cnt, n_mv_dev, (uint32_t)n, keys_in, vals_in);
+    }
+    VERS_HIP_TRY(hipGetLastError());
+    uint32_t tail[2] = {0, 0};
+    VERS_HIP_TRY(hipMemcpy(cnt.data(), out_cnt, cnt.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    VERS_HIP_TRY(hipMemcpy(tail, n_mv_dev, sizeof(tail), hipMemcpyDeviceToHost));
+    VERS_HIP_TRY(hipMemcpy(status.data(), ud.status.p, n, hipMemcpyDeviceToHost));
+    VERS_HIP_TRY(hipMemcpy(a_host.data(), a32, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (tail[1]) return fail(VERS_ERR_HIP, "vers_ivf_update_batch: the assign pass returned a cluster index out of range");
+    n_mv = tail[0];
+    if (int32_t rc = clk.done()) return rc;
+  }
+  uint64_t stayed = 0, moved = 0, skipped = 0;
+  for (uint64_t i = 0; i < n; ++i) (status[i] == upd::kStayed ? stayed : status[i] == upd::kMoved ? moved : skipped) += 1;
+  if (moved != n_mv) return fail(VERS_ERR_HIP, "vers_ivf_update_batch: a vec id is stored twice (inconsistent index)");
+  // 4. the plan: lengths in between and afterwards, the jobs of both kernels (list-relative: a re-layout may follow)
+  const uint32_t* const c_out = cnt.data();
+  const uint32_t* const c_ft = cnt.data() + k;
+  const uint32_t* const c_in = cnt.data() + 2 * (size_t)k;
+  for (uint32_t c = 0; c < k; ++c)
+    if (c_out[c] > h->h_len[c] || (c_out[c] && (uint64_t)c_ft[c] * 64 >= h->h_len[c]))
+      return fail(VERS_ERR_HIP, "vers_ivf_update_batch: a located row lies outside its list (inconsistent index)");
+  std::vector<uint32_t> mid(k), nl(k);
+  const bool grow = moved != 0 && upd::plan_lengths(h->h_len.data(), c_out, c_in, h->h_cap.data(), k, mid.data(), nl.data());
+  if (moved == 0) { mid = h->h_len; nl = h->h_len; }
+  uint64_t relayouts = 0;
+  if (grow) {
+    AbClock clk(8, g_up);
+    if (int32_t rc = relayout_for(h, nl.data())) return rc;
+    relayouts = 1;
+    if (int32_t rc = clk.done()) return rc;
+  }
+  // 5. the movers in (new list, vec id) order; every update's place among them
+  if (n_mv) {
+    AbClock clk(8, g_up);
+    const uint64_t lim_host[2] = {0, n_mv};
+    const size_t tmp_b = range_sort_temp_bytes(n_mv, 1);
+    if (int32_t rc = ud.tmp.reserve(tmp_b)) return rc;
+    if (int32_t rc = ud.pos.reserve((size_t)n_mv * sizeof(uint32_t))) return rc;
+    if (int32_t rc = ud.mstage.reserve((size_t)n_mv * ldx * sizeof(float))) return rc;
+    VERS_HIP_TRY(hipMemcpy(lims, lim_host, sizeof(lim_host), hipMemcpyHostToDevice));
+    if (int32_t rc = range_sort_segments(keys_in, keys_out, vals_in, vals_out, n_mv, 1, lims, ud.tmp.p, tmp_b, st)) return rc;
+    hipLaunchKernelGGL(update_mover_rows_kernel, dim3((n_mv + 255) / 256), dim3(256), 0, st, (const uint64_t*)vals_out, n_mv, ud.mv_row.as<uint32_t>());
+    VERS_HIP_TRY(hipGetLastError());
+    if (int32_t rc = clk.done()) return rc;
+  }
+  // 6. placement of the staged rows: stays over their storage rows, movers into their stage.  THE FIRST WRITE to a stored row.
+  if (moved) h->flt_moved += 1;  // (prepared filters: storage rows change their vec ids from here on)
+  for (uint64_t s0 = 0; s0 < n; s0 += chunk) {
+    const uint32_t m = (uint32_t)std::min<uint64_t>(chunk, n - s0);
+    if (!one_chunk) {
+      AbClock clk(4, g_up);
+      if (int32_t rc = update_stage_chunk(h, rows_host, row_stride_bytes, rows_dev, ld_floats, s0, m)) return rc;
+      if (int32_t rc = clk.done()) return rc;
+    }
+    AbClock clk(7, g_up);
+    const uint64_t blocks = std::min<uint64_t>((uint64_t)h->n_cu * 8, ((uint64_t)m * (h->ld / 4) + 255) / 256);
+    hipLaunchKernelGGL(update_place_kernel, dim3((unsigned)blocks), dim3(256), 0, st, (const float*)ab.stage.as<float>(), ldx, h->ld, s0, m,
+                       (const uint8_t*)ud.status.as<uint8_t>(), (const uint32_t*)a32, (const uint32_t*)ud.rel.as<uint32_t>(),
+                       (const uint32_t*)ud.mv_row.as<uint32_t>(), (const uint32_t*)h->list_off.as<uint32_t>(), h->rows.as<float>(), ud.mstage.as<float>());
+    VERS_HIP_TRY(hipGetLastError());
+    if (int32_t rc = clk.done()) return rc;
+  }
+  // 7. the touched tiles: of the stays, of the lists that lose rows (from their first loss on), of the lists that gain rows (from their
+  // first insertion point on -- known once the positions are computed, below)
+  std::vector<uint32_t> tiles;
+  if (stayed) {
+    rel.resize(n);
+    VERS_HIP_TRY(hipMemcpy(rel.data(), ud.rel.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    for (uint64_t i = 0; i < n; ++i)
+      if (status[i] == upd::kStayed) tiles.push_back((uint32_t)(((uint64_t)h->h_off[a_host[i]] + rel[i]) / 64));
+  }
+  if (moved) {
+    AbClock clk(8, g_up);
+    std::vector<RemoveJob> rjobs;
+    std::vector<MergeJob> mjobs;
+    uint32_t run = 0;
+    for (uint32_t c = 0; c < k; ++c) {
+      if (c_out[c]) {
+        rjobs.push_back(RemoveJob{h->h_off[c], h->h_len[c], c_ft[c]});
+        for (uint32_t t = c_ft[c]; (uint64_t)t * 64 < h->h_len[c]; ++t) tiles.push_back(h->h_off[c] / 64u + t);
+      }
+      if (c_in[c]) mjobs.push_back(MergeJob{h->h_off[c], mid[c], c_in[c], run});
+      run += c_in[c];
+    }
+    const size_t rj_b = rjobs.size() * sizeof(RemoveJob), mj_b = mjobs.size() * sizeof(MergeJob);
+    if (int32_t rc = ud.jobs.reserve(rj_b + mj_b + 16)) return rc;
+    if (rj_b) VERS_HIP_TRY(hipMemcpy(ud.jobs.p, rjobs.data(), rj_b, hipMemcpyHostToDevice));
+    VERS_HIP_TRY(hipMemcpy(ud.jobs.as<char>() + rj_b, mjobs.data(), mj_b, hipMemcpyHostToDevice));
+    VERS_HIP_TRY(hipMemcpy(mid_len, mid.data(), (size_t)k * sizeof(uint32_t), hipMemcpyHostToDevice));
+    // movers out: remove_batch's compaction with the bitmap the locate pass wrote
+    hipLaunchKernelGGL(remove_compact_kernel, dim3((unsigned)rjobs.size()), dim3(kRmWaves * 64), 0, st, (const RemoveJob*)ud.jobs.p,
+                       (const uint32_t*)h->rm.bitmap.as<uint32_t>(), nt_ids, h->ld, h->rows.as<float>(), h->row_ids.as<uint32_t>());
+    // movers in: insertion points against the compacted lists, then the backward merge
+    hipLaunchKernelGGL(update_positions_kernel, dim3((n_mv + 255) / 256), dim3(256), 0, st, (const uint64_t*)keys_out, n_mv, (const uint32_t*)h->list_off.as<uint32_t>(),
+                       (const uint32_t*)mid_len, (const uint32_t*)h->row_ids.as<uint32_t>(), ud.pos.as<uint32_t>());
+    hipLaunchKernelGGL(update_merge_kernel, dim3((unsigned)mjobs.size()), dim3(kRmWaves * 64), 0, st, (const MergeJob*)(ud.jobs.as<char>() + rj_b),
+                       (const uint32_t*)ud.pos.as<uint32_t>(), (const uint64_t*)keys_out, (const float*)ud.mstage.as<float>(), ldx, h->ld, h->rows.as<float>(),
+                       h->row_ids.as<uint32_t>());
+    VERS_HIP_TRY(hipGetLastError());
+    std::vector<uint32_t> pos(n_mv);
+    VERS_HIP_TRY(hipMemcpy(pos.data(), ud.pos.p, (size_t)n_mv * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    for (const MergeJob& jb : mjobs)
+      for (uint32_t t = upd::merge_first_tile(pos.data() + jb.in0); t <= upd::merge_last_tile(jb.len, jb.n_in); ++t) tiles.push_back(jb.off / 64u + t);
+    if (int32_t rc = clk.done()) return rc;
+  }
+  {
+    // 8. tables (as remove_batch) and the derived arrays of the touched tiles; the maxima in pre_misc only grow, as after a removal
+    AbClock clk(9, g_up);
+    if (moved) {
+      std::vector<uint32_t> sl(k);
+      for (uint32_t c = 0; c < k; ++c) sl[h->h_slot[c]] = nl[c];
+      VERS_HIP_TRY(hipMemcpy(h->list_len.p, nl.data(), (size_t)k * sizeof(uint32_t), hipMemcpyHostToDevice));
+      VERS_HIP_TRY(hipMemcpy(h->slot_len.p, sl.data(), (size_t)k * sizeof(uint32_t), hipMemcpyHostToDevice));
+      h->h_len = nl;
+      h->max_len = 0;
+      for (uint32_t c = 0; c < k; ++c) h->max_len = std::max(h->max_len, nl[c]);
+      h->set_len_asc_prefix();
+    }
+    {  // the union, each tile once, ascending (a mark per storage tile: a sort of one entry per updated row cost more than the kernels)
+      std::vector<uint8_t> hit((size_t)(h->cap_rows / 64) + 1, 0);
+      for (uint32_t t : tiles) hit[t] = 1;
+      tiles.clear();
+      for (size_t t = 0; t < hit.size(); ++t)
+        if (hit[t]) tiles.push_back((uint32_t)t);
+    }
+    const uint32_t n_tiles = (uint32_t)tiles.size();
+    if (n_tiles) {
+      if (int32_t rc = ud.jobs.reserve((size_t)n_tiles * sizeof(uint32_t))) return rc;
+      VERS_HIP_TRY(hipMemcpy(ud.jobs.p, tiles.data(), (size_t)n_tiles * sizeof(uint32_t), hipMemcpyHostToDevice));
+      if (int32_t rc = refresh_tiles(h, (const uint32_t*)ud.jobs.p, n_tiles, st)) return rc;
+    }
+    if (int32_t rc = clk.done()) return rc;
+  }
+  ab_count(2, (double)stayed, g_up);
+  ab_count(3, (double)moved, g_up);
+  // 9. the outputs, only now
+  if (dev) {
+    if (out_clusters) {
+      hipLaunchKernelGGL(u32_to_u64_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const uint32_t*)a32, n, out_clusters);
+      VERS_HIP_TRY(hipGetLastError());
+    }
+    if (out_status) VERS_HIP_TRY(hipMemcpyAsync(out_status, ud.status.p, n, hipMemcpyDeviceToDevice, st));
+    VERS_HIP_TRY(hipStreamSynchronize(st));
+  } else {
+    if (out_clusters)
+      for (uint64_t i = 0; i < n; ++i) out_clusters[i] = a_host[i];
+    if (out_status) std::memcpy(out_status, status.data(), n);
+  }
+  if (out_counts) { out_counts[0] = stayed; out_counts[1] = moved; out_counts[2] = skipped; out_counts[3] = relayouts; }
+  return VERS_OK;
+}
+
 // ---- compact: back to plan_storage's capacities for the CURRENT lengths (see vers_hip.h) ------------------------------------------------
 constexpr int kCompactPhases = 8;
 static double g_cp[kCompactPhases] = {};  // vers_compact_phases: calls, storage rows before, after, plan + allocation, move, derive (unfused), tables (ms), reserved
@@ -2468,6 +2906,35 @@ int32_t vers_ivf_remove_batch_dev(vers_ivf_t* h, const uint64_t* vec_ids_dev, ui
   if (rc || removed) h->flt_moved += 1;  // (prepared filters: a removal compacts every touched list from its first removed row on)
   if (out_removed) *out_removed = removed;
   return rc;
+}
+
+int32_t vers_ivf_update_batch(vers_ivf_t* h, const uint64_t* vec_ids, const float* rows, uint64_t n, uint64_t row_stride_bytes, uint64_t* out_clusters,
+                              uint8_t* out_status, uint64_t* out_counts) {
+  if (!h) return fail(VERS_ERR_INVALID, "vers_ivf_update_batch: null handle");
+  if ((n && (!vec_ids || !rows)) || row_stride_bytes < (uint64_t)h->d * 4 || row_stride_bytes % 4)
+    return fail(VERS_ERR_INVALID, "vers_ivf_update_batch: bad arguments (row_stride_bytes must be >= 4 d and a multiple of 4)");
+  std::unique_lock<std::shared_mutex> lk(h->index);
+  DeviceGuard g(h->device);
+  return update_batch_locked(h, vec_ids, nullptr, rows, row_stride_bytes, nullptr, 0, n, false, out_clusters, out_status, out_counts);
+}
+
+int32_t vers_ivf_update_batch_dev(vers_ivf_t* h, const uint64_t* vec_ids_dev, const float* rows_dev, uint64_t n, uint64_t ld_floats, uint64_t* out_clusters_dev,
+                                  uint8_t* out_status_dev, uint64_t* out_counts) {
+  if (!h) return fail(VERS_ERR_INVALID, "vers_ivf_update_batch_dev: null handle");
+  if ((n && (!vec_ids_dev || !rows_dev)) || ld_floats < (uint64_t)h->d || ld_floats % 4 || ld_floats > 0x3FFFFFFFull)
+    return fail(VERS_ERR_INVALID, "vers_ivf_update_batch_dev: bad arguments (ld_floats must be >= d and a multiple of 4)");
+  std::unique_lock<std::shared_mutex> lk(h->index);
+  DeviceGuard g(h->device);
+  return update_batch_locked(h, nullptr, vec_ids_dev, nullptr, 0, rows_dev, ld_floats, n, true, out_clusters_dev, out_status_dev, out_counts);
+}
+
+int32_t vers_update_phases(double* out, int32_t reset) {
+  std::lock_guard<std::mutex> lk(g_ab_mu);
+  if (out)
+    for (int i = 0; i < kUpdatePhases; ++i) out[i] = g_up[i];
+  if (reset)
+    for (double& v : g_up) v = 0.0;
+  return VERS_OK;
 }
 
 int32_t vers_ivf_live_count(vers_ivf_t* h, uint64_t* out_live) {

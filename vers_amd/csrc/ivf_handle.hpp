@@ -249,6 +249,15 @@ struct vers_ivf {
       pin = nullptr; pin_cap = 0;
     }
   } rm;
+  // vers_ivf_update_batch / _update_batch_dev (ivf_build.hip): scratch kept between calls (the callers hold the handle exclusively); the
+  // staged chunk, its pinned buffer and the removal bitmap are add_batch's and remove_batch's (ab.stage, ab.pin, rm.bitmap).
+  // ids: the call's vec ids (host call) | slot: u32 per vec id, the update's index | a32 / status / rel / mv_row: per update, its cluster,
+  // its status, its position in the list it stays in, its place among the sorted movers | cnt: u32 [k] rows leaving, [k] first tile that
+  // loses one, [k] rows entering, [k] lengths in between, [1] movers, [1] check flags | keys / vals (in | out halves): the movers as
+  // ((new list, vec id), update) pairs | pos: insertion points | mstage: the movers' rows [n_mv][ldx] | jobs: both kernels' jobs + tiles.
+  struct UpdateState {
+    DevBuf ids, slot, a32, status, rel, mv_row, cnt, keys, vals, pos, mstage, jobs, tmp;
+  } ud;
   // matrix-core list scan (prescan.hip.h): |x|^2 per storage row, [0] max |x|^2 bits, [1] certificate failures (running)
   DevBuf xnorm, pre_misc;
   DevBuf flt_total;  // u64 [4] vers_ivf_filter_stats over the handle's life (filter_stats_fold_kernel adds every call's counters); allocated under flt_mu
@@ -257,8 +266,11 @@ struct vers_ivf {
   // Prepared filters (vers_ivf_filter_prepare): the objects still alive (guarded by flt_mu; vers_ivf_destroy frees them) and the two counters
   // their staleness protocol reads.  Both are written only while a mutator holds `index` exclusively -- when no search is in flight:
   //   flt_moved     anything after which a storage row may hold another vector or the tables changed: build, upload, set_shard, a
-  //                 remove_batch that removed something, compact, an add / add_batch that re-laid-out storage
+  //                 remove_batch that removed something, compact, an add / add_batch that re-laid-out storage, an update_batch that moved
+  //                 at least one row to another list (or re-laid-out storage)
   //   flt_appended  an add / add_batch that wrote its rows into list slack in place: cap_rows, list_off and every existing row unchanged
+  // An update_batch in which every row stayed in its list bumps NEITHER: values changed, but no storage row changed its vec id and no table
+  // moved, so the masks and allowed_len of a prepared filter are still right.
   std::vector<vers_filter*> filters;
   uint64_t flt_moved = 0, flt_appended = 0;
   DevBuf prune_ctr;  // u64 [3] steps executed | steps without math | tiles abandoned by the list scan's early abandon, over the handle's life

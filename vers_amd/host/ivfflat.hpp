@@ -8,6 +8,7 @@
 //   Index::save_index / load_index base.rs:31-58   (bincode 1.3 layout, see vers_amd/index.py)
 // A reference panic becomes a thrown vers::Panic.  The five fields stay host-owned (serde); the handle is a cache.
 #pragma once
+#include <algorithm>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -132,6 +133,36 @@ class IVFFlatIndex {
     }
     if (gone != removed) throw Panic(VERS_ERR_INVALID, "remove_batch: the device removed another number of rows than the host lists hold");
     return gone;
+  }
+
+  // Update (extension, vers_ivf_update_batch): values[v] = embeddings[i] for v = vec_ids[i], under the id the vector already has.  A row
+  // whose first-minimum centroid is still its list keeps its position; one that changes cluster leaves its list and enters the new one at
+  // its sorted place by vec id (every list stays ascending); an id that is in no list is skipped.  All or nothing: an id >=
+  // assignments.size(), an id twice in the call or a NaN distance throws and nothing changes.  Returns the status per update
+  // (0 stayed, 1 moved, 2 skipped).
+  std::vector<uint8_t> update_batch(const std::vector<size_t>& vec_ids, const std::vector<Vector<N>>& embeddings) {
+    if (vec_ids.size() != embeddings.size()) throw Panic(VERS_ERR_INVALID, "update_batch: one embedding per vec id");
+    const size_t n = vec_ids.size();
+    std::vector<uint64_t> v(vec_ids.begin(), vec_ids.end()), cl(n ? n : 1);
+    std::vector<uint8_t> st(n ? n : 1);
+    check(vers_ivf_update_batch(handle(), v.data(), n ? embeddings[0].v : nullptr, n, sizeof(Vector<N>), cl.data(), st.data(), nullptr));
+    st.resize(n);
+    for (size_t i = 0; i < n; ++i) {
+      const size_t id = vec_ids[i], old = assignments[id], c = (size_t)cl[i];
+      auto& from = ids[old];
+      const auto at = std::lower_bound(from.begin(), from.end(), id);
+      const bool listed = at != from.end() && *at == id;
+      const uint8_t want = !listed ? 2 : c == old ? 0 : 1;
+      if (st[i] != want) throw Panic(VERS_ERR_INVALID, "update_batch: the device's status differs from the host lists'");
+      if (!listed) continue;
+      values[id] = embeddings[i];
+      if (c == old) continue;
+      from.erase(at);
+      assignments[id] = c;
+      auto& to = ids[c];
+      to.insert(std::lower_bound(to.begin(), to.end(), id), id);
+    }
+    return st;
   }
 
   // Compaction (extension, vers_ivf_compact): the device storage goes back to the capacities a fresh upload of the current lists plans and

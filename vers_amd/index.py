@@ -147,6 +147,52 @@ class IVFFlatIndex:
                                               C.byref(removed)))
         return int(removed.value)
 
+    # -- update (extension; the reference has none): values[v] = x, the row to the list of its first-minimum centroid ----
+    def update_batch(self, vec_ids, embeddings):
+        """Replaces the vectors stored under `vec_ids` by the rows of `embeddings` (vers_ivf_update_batch); the vec ids are kept.  A row
+        whose first-minimum centroid is still its list is overwritten in place; one that changes cluster leaves its list and enters the
+        new one at its sorted place by vec id (bisect.insort); an id that is in no list is skipped.  All or nothing: an id >=
+        len(assignments), an id twice in the call or a NaN distance raises and changes nothing.  The host mirror follows and the device's
+        clusters and status are asserted against it.  Returns (clusters, status): u64 [n], u8 [n] (0 stayed, 1 moved, 2 skipped)."""
+        import bisect
+        v = np.ascontiguousarray(np.asarray(vec_ids, dtype=np.uint64).reshape(-1))
+        e = np.ascontiguousarray(embeddings, dtype=np.float32).reshape(-1, self.d)
+        n = v.size
+        assert e.shape[0] == n
+        cl = np.zeros(max(n, 1), dtype=np.uint64)
+        st = np.zeros(max(n, 1), dtype=np.uint8)
+        counts = np.zeros(4, dtype=np.uint64)
+        check(lib().vers_ivf_update_batch(self._h, _ptr(v) if n else None, _ptr(e) if n else None, n, 4 * self.d, _ptr(cl), _ptr(st), counts.ctypes.data_as(C.POINTER(C.c_uint64))))
+        cl, st = cl[:n], st[:n]
+        self.values = self.values.copy()
+        self.assignments = self.assignments.copy()
+        want = np.zeros(n, dtype=np.uint8)
+        for i, (vid, c) in enumerate(zip(v.tolist(), cl.tolist())):
+            old = int(self.assignments[vid])
+            lst = self.ids[old]
+            j = bisect.bisect_left(lst, vid)
+            if j == len(lst) or lst[j] != vid:
+                want[i] = 2
+                continue
+            self.values[vid] = e[i]
+            if c != old:
+                want[i] = 1
+                del lst[j]
+                self.assignments[vid] = c
+                bisect.insort(self.ids[c], vid)
+        assert np.array_equal(st, want), (st, want)
+        assert counts[:3].tolist() == [int((want == s).sum()) for s in (0, 1, 2)], counts
+        self.last_update_counts = tuple(int(x) for x in counts)
+        return cl, st
+
+    def update_batch_dev(self, ids_ptr: int, rows_ptr: int, n: int, ld: int, clusters_ptr: int = 0, status_ptr: int = 0):
+        """vers_ivf_update_batch_dev on device arrays: u64 vec ids, rows [n][ld] f32; clusters (u64) / status (u8) to device memory when
+        given.  The host fields are NOT mirrored.  Returns (stayed, moved, skipped, relayouts)."""
+        counts = np.zeros(4, dtype=np.uint64)
+        check(lib().vers_ivf_update_batch_dev(self._h, _vp(ids_ptr) if n else None, _vp(rows_ptr) if n else None, n, ld,
+                                              _vp(clusters_ptr) if clusters_ptr else None, _vp(status_ptr) if status_ptr else None, counts.ctypes.data_as(C.POINTER(C.c_uint64))))
+        return tuple(int(x) for x in counts)
+
     def compact(self):
         """vers_ivf_compact: every list back to the capacity a fresh upload of the current lengths plans, the certificate maxima
         recomputed over the rows the lists hold.  Nothing of the five fields changes (the host mirror is left as it is).  Returns
