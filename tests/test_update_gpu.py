@@ -18,7 +18,7 @@ import pytest
 from oracle import c_oracle as co
 from tests.golden import make_golden as mg
 from tests.test_certificate_gpu import corpus, d_ref
-from tests.test_certificate_mutation_gpu import fresh_handle, row_r2, row_x2, same_vals
+from tests.test_certificate_mutation_gpu import fresh_handle, r2_ref, row_r2, row_x2, same_vals, xmax2_ref
 from tests.test_remove_gpu import bits, check, check_search, check_state, live_ids, make, queries
 from vers_amd import capi, testhooks
 from vers_amd.index import IVFFlatIndex
@@ -412,11 +412,12 @@ def test_prepared_filters_stay_valid_when_every_row_stays_and_rebuild_after_a_mo
 
 
 # ---- derived state: |x|^2, the fp16 shadow, the two maxima -- the search oracle cannot see a wrong one, a fallback hides it ---------------
-def audit(ix, Q, top_k, nprobe, qs, ever, label):
+def audit(ix, Q, top_k, nprobe, qs, ever, label, tight_live=False):
     """One batched search on the matrix-core list scan with the shadow on, then for every query of `qs` what the scan dumped: every val
     inside its bound, only live rows of the probed lists, each once; the maxima between the restatement over the live rows' CURRENT values
     and the restatement over every value EVER stored (`ever`: the mirror's values plus the overwritten ones, which the mirror no longer
-    holds); the results against the oracle.  -> the dict tests/test_certificate_mutation_gpu.same_vals compares"""
+    holds); the results against the oracle.  tight_live (straight after compact): both maxima EQUAL the restatement over the live rows.
+    -> the dict tests/test_certificate_mutation_gpu.same_vals compares"""
     metric = ix.metric
     n_ever = ix.values.shape[0]
     live = live_ids(ix)
@@ -445,6 +446,8 @@ def audit(ix, Q, top_k, nprobe, qs, ever, label):
             out["n_vals"] += 1
         assert x_lo <= info["xmax2"] <= x_hi, (label, qi, x_lo, info["xmax2"], x_hi)
         assert r_lo <= info["r2"] <= r_hi, (label, qi, r_lo, info["r2"], r_hi)
+        if tight_live:
+            assert info["xmax2"] == xmax2_ref(ix.values[live]) and info["r2"] == r2_ref(ix.values[live]), (label, qi, info["xmax2"], x_lo, info["r2"], r_lo)
         oi, od = co.search_nprobe(ix.values, ix.centroids, ix.ids, Q[qi], top_k, nprobe, metric)
         assert cnt[qi] == len(oi) and np.array_equal(ids[qi, :len(oi)], oi) and np.array_equal(bits(dist[qi, :len(oi)]), bits(od)), (label, qi)
         out["dumps"][qi] = (v, bits(vals).copy())
@@ -502,4 +505,74 @@ def test_derived_state_after_updates(tmp_path, metric):
     r = audit(ix, Q, top_k, nprobe, qs, np.concatenate(ever), "stays and moves")
     twin("stays and moves", r)
     check_search(ix, Q[:40], nprobes=(1, 5), top_ks=(10,))
+    ix.close()
+
+
+# ---- the adversarial rows of the add and compact suites, delivered by update_batch ----------------------------------------------------------
+@pytest.mark.parametrize("metric", [capi.METRIC_L2SQ, capi.METRIC_COSDIST])
+def test_adversarial_rows_delivered_as_stays(tmp_path, metric):
+    """A row of 100 x the corpus norm and a row with an element of 7e4 (beyond fp16: its shadow residual is inf) overwrite two rows in
+    place.  What the handle then does with its shadow -- retire it, or re-scan every query exactly -- is what a handle does that received
+    the same two rows through add_batch; results stay the oracle's; the maxima are upper bounds until compact re-tightens them."""
+    from tests.test_compact_gpu import fallbacks_of
+    n, d, k, b = 3000, 96, 12, 64
+    X = corpus("dist_c", n, d, 0x19E0 + metric)
+    Q = corpus("dist_c", b, d, 0x19E8 + metric)
+    init = mg.init_draws(0x19E, 1, k, n)
+    ix = IVFFlatIndex.build_index(k, 1, 3, X, init_indices=init, metric=metric)
+    by_add = IVFFlatIndex.build_index(k, 1, 3, X, init_indices=init, metric=metric)
+    assert ix.shadow_state()["active"]
+    _, batches, _ = fallbacks_of(ix, Q)
+    assert batches == 1
+    info = testhooks.last_vals(ix, 0, cap=32768)[3]
+    x_fresh, r_fresh = info["xmax2"], info["r2"]
+    assert x_fresh == xmax2_ref(ix.values) and r_fresh == r2_ref(ix.values)
+
+    def stays(v, x):
+        return co.add_cluster(ix.centroids, x, metric) == int(ix.assignments[v])
+
+    def overflowing(x):
+        x = x.copy(); x[3] = np.float32(7.0e4)
+        return x
+
+    home = [v for v in range(n) if stays(v, X[v])]          # (rows that can be told to stay with their ordinary value again)
+    vb = next(v for v in home if stays(v, X[v] * np.float32(100.0)))
+    vo = next(v for v in home if v != vb and stays(v, overflowing(X[v])))
+    rows = np.stack([X[vb] * np.float32(100.0), overflowing(X[vo])]).astype(np.float32)
+    targets = [int(ix.assignments[vb]), int(ix.assignments[vo])]
+    update(ix, [vb, vo], rows, targets, STAYED)
+    by_add.add_batch(rows)
+    for _ in range(6):   # (256 queries: a shadow whose certificates fail retires itself for the handle)
+        _, _, fa = fallbacks_of(ix, Q)
+        _, _, ft = fallbacks_of(by_add, Q)
+    assert ix.shadow_state()["active"] == by_add.shadow_state()["active"], (ix.shadow_state(), by_add.shadow_state())
+    if ix.shadow_state()["active"]:
+        assert fa == ft == b, (fa, ft)                       # every query re-scanned exactly
+    print(f"metric {metric}: shadow active after the adversarial stays {ix.shadow_state()['active']}, re-scanned {fa} (through add: {ft}) of {b}")
+    by_add.close()
+    check_state(ix)
+    check_search(ix, Q[:40], nprobes=(1, 5), top_ks=(10,))
+    # back to ordinary values: the maxima do not come down (upper bounds)
+    update(ix, [vb, vo], X[[vb, vo]], targets, STAYED)
+    assert np.array_equal(bits(ix.values), bits(X))
+    ix.search_batch(Q, 10, 5)
+    info = testhooks.last_vals(ix, 0, cap=32768)[3]
+    assert info["xmax2"] >= xmax2_ref(rows) > x_fresh, (info, x_fresh)
+    if info["shadow"] != 0:   # (a scan on the f32 rows charges no residual: the hook reports 0 for it)
+        assert info["r2"] >= r2_ref(rows) > r_fresh, (info, r_fresh)
+    else:                     # the residual maximum stayed inf: ordinary values in every row again cure nothing, the shadow stays retired
+        assert not ix.shadow_state()["active"]
+    check_search(ix, Q[:40], nprobes=(5,), top_ks=(10,), exhaustive=False)
+    # compact: both maxima equal the live rows', the shadow is active again, and a batch re-scans as many queries as on a fresh handle
+    ix.compact()
+    assert ix.shadow_state()["active"]
+    _, batches, fb = fallbacks_of(ix, Q)
+    info = testhooks.last_vals(ix, 0, cap=32768)[3]
+    assert batches == 1 and info["shadow"] != 0
+    assert info["xmax2"] == xmax2_ref(ix.values) == x_fresh and info["r2"] == r2_ref(ix.values) == r_fresh, (info, x_fresh, r_fresh)
+    t = fresh_handle(ix, tmp_path, False)
+    _, batches_t, fb_t = fallbacks_of(t, Q)
+    assert (batches_t, fb_t) == (1, fb), (fb, fb_t)
+    t.close()
+    check(ix, Q[:40], nprobes=(1, 5), top_ks=(10,))
     ix.close()

@@ -2367,7 +2367,12 @@ int32_t update_batch_locked(vers_ivf* h, const uint64_t* ids_host, const uint64_
   uint64_t relayouts = 0;
   if (grow) {
     AbClock clk(8, g_up);
-    if (int32_t rc = relayout_for(h, nl.data())) return rc;
+    // relayout_for copies the rows a list holds NOW (h_len) into the room planned for the length it is given: a list that shrinks in this
+    // call (its movers leave after the re-layout, below) keeps room for its old length -- planned for the new one, its tiles would be
+    // copied, and then compacted, over the storage of the lists behind it
+    std::vector<uint32_t> room(k);
+    for (uint32_t c = 0; c < k; ++c) room[c] = std::max(h->h_len[c], nl[c]);
+    if (int32_t rc = relayout_for(h, room.data())) return rc;
     relayouts = 1;
     if (int32_t rc = clk.done()) return rc;
   }
