@@ -84,7 +84,6 @@ struct SearchWs {
   DevBuf flt_rows, flt_of;  // a filter per query (filter_multi.hip.h): the row_sets words; the staged filter_of of a host-pointer call
   DevBuf flt_alen, flt_np;  // adaptive depth (filter_adaptive.hip.h): allowed rows per (bitmap, list); the staged out_nprobe of a host-pointer call
   bool no_ahead = false;  // the plan of a filtered call neither consumes a look-ahead slot nor touches a pending request (plan_search)
-  vers_filter* prep = nullptr;  // a prepared call (vers_ivf_*_prepared_dev): filter_begin / filter_multi_begin point at this object's masks instead of building the call's
   DevBuf rg_rlims;  // sharded range search: every rank's CSR limits [world][b + 1] (range_merge.hip.h); the gather itself goes through g_send / g_recv
   DevBuf g_send, g_recv;  // sharded search without the host in the loop: this rank's [2][b][top_k] partial | the world's
   DevBuf g_cnt;  // an adaptive filtered call on a sharded handle: this rank's allowed counts [n] | the world's [world][n] | their sum [n], u32

@@ -6,6 +6,7 @@
 #include <cstring>
 #include <functional>
 #include <limits>
+#include <optional>
 #include <vector>
 
 #include "finish.hip.h"
@@ -197,8 +198,9 @@ namespace ivf {
 
 static size_t filter_wave_slots(const vers_ivf* h) { return (size_t)h->n_cu * 3 * kWavesPerBlock; }  // (filter_scan_kernel: at most 3 blocks per CU)
 
-// The filtered kernel a scan launches: none, the per-call mask's (filter.hip.h) or the per-query sets' (filter_multi.hip.h).  The drivers pass
-// the choice down; nothing else about a pass differs between the two.
+// The filtered kernel a pass launches: none, the per-call mask's (filter.hip.h, filter_range.hip.h) or the per-query sets' (filter_multi.hip.h,
+// filter_range_multi.hip.h).  A call's FilterMasks (below) hands it out once filter_begin has filled them; the top-k drivers and the range source
+// pass it down, and nothing else about a pass differs between the two.
 struct FilterChoice {
   const FilterParams* one = nullptr;
   const FilterMultiParams* multi = nullptr;
@@ -680,9 +682,34 @@ static int32_t prepared_sync(vers_ivf* h, vers_filter* o, int want, bool search,
   return VERS_OK;
 }
 
-// filter_begin / filter_multi_begin of a prepared call: the object's arrays in the workspace's place, the allowed total from the object
-static int32_t prepared_begin(vers_ivf* h, bool multi, hipStream_t st, unsigned long long* stats) {
-  vers_filter* const o = W->prep;
+// The filter of a call, on the device -- what every filtered *_dev_locked function takes: n_filters bitmaps `stride_words` apart, one n_bits for
+// all.  filter_of == NULL: ONE bitmap for the batch and the per-call kernels (filter.hip.h, filter_range.hip.h); else the batch's filter_of and
+// the per-query kernels (filter_multi.hip.h, filter_range_multi.hip.h).  prep: a prepared call -- the object the bitmaps above are; its masks
+// serve the call and no mask kernel runs.
+struct FilterArg {
+  const uint64_t* filters; uint64_t stride_words; uint32_t n_filters; uint64_t n_bits; const uint32_t* filter_of;
+  vers_filter* prep = nullptr;
+  // (several bitmaps without a filter_of: vers_ivf_filter_allowed_len_dev, which counts every bitmap and has no batch; the searches refuse that)
+  bool multi() const { return filter_of != nullptr || n_filters > 1; }
+  uint32_t n_sets() const { return multi() ? n_filters : 1u; }
+};
+// the per-call entry points' filter: one bitmap of n_bits bits
+static FilterArg per_call_filter(const uint64_t* bits, uint64_t n_bits) { return FilterArg{bits, (n_bits + 63) / 64, 1u, n_bits, nullptr}; }
+// the prepared calls' filter: the object's own packed copy of the bitmaps, and the object
+static FilterArg prepared_filter(const vers_filter* f, const uint32_t* filter_of_dev) {
+  return FilterArg{f->bits.as<uint64_t>(), f->words, f->n_filters, f->n_bits, filter_of_dev, const_cast<vers_filter*>(f)};
+}
+
+// What filter_begin fills for the kernels of the call: the per-call mask's parameters or the per-query sets', and which of the two.
+struct FilterMasks {
+  FilterParams one;
+  FilterMultiParams multi;
+  bool per_query = false;
+  FilterChoice choice() const { return per_query ? FilterChoice{nullptr, &multi} : FilterChoice{&one, nullptr}; }
+};
+
+// the begin of a prepared call: the object's arrays in the workspace's place, the allowed total from the object
+static int32_t prepared_begin(vers_ivf* h, vers_filter* o, bool multi, hipStream_t st, unsigned long long* stats) {
   if (int32_t rc = prepared_sync(h, o, multi ? 1 : 0, true, st)) return rc;
   VERS_HIP_TRY(hipMemcpyAsync(stats + kFltRowsAllowed, o->stats.as<unsigned long long>() + kFltRowsAllowed, sizeof(unsigned long long), hipMemcpyDeviceToDevice, st));
   return VERS_OK;
@@ -690,12 +717,14 @@ static int32_t prepared_begin(vers_ivf* h, bool multi, hipStream_t st, unsigned 
 
 // The tile mask of the call over `n_rows` storage rows + its zeroed counters.  The mask kernel is bracketed by a record of the scan-timing
 // ring (vers_ivf_scan_times: a filtered call leaves the mask kernel's record, then one per scan pass).
-static int32_t filter_begin(vers_ivf* h, const uint64_t* bits_dev, uint64_t n_bits, uint64_t n_rows, hipStream_t st, FilterParams& f) {
+static int32_t filter_one_begin(vers_ivf* h, const FilterArg& a, uint64_t n_rows, hipStream_t st, FilterParams& f) {
+  const uint64_t* const bits_dev = a.filters;
+  const uint64_t n_bits = a.n_bits;
   const uint64_t n_tiles = (n_rows + kWave - 1) / kWave;
-  if (W->prep) {  // a prepared call: no mask kernel, the object's mask
+  if (a.prep) {  // a prepared call: no mask kernel, the object's mask
     if (int32_t rc = filter_counters_begin(h, st, f.stats, f.wave_slots)) return rc;
-    if (int32_t rc = prepared_begin(h, false, st, f.stats)) return rc;
-    f.tile_mask = W->prep->tile_mask.as<uint64_t>();
+    if (int32_t rc = prepared_begin(h, a.prep, false, st, f.stats)) return rc;
+    f.tile_mask = a.prep->tile_mask.as<uint64_t>();
     return VERS_OK;
   }
   if (int32_t rc = W->flt_mask.reserve(std::max<size_t>(1, n_tiles) * sizeof(uint64_t))) return rc;
@@ -714,55 +743,58 @@ static int32_t filter_begin(vers_ivf* h, const uint64_t* bits_dev, uint64_t n_bi
   });
 }
 
-// The bitmaps of a call with a filter per query (filter_multi.hip.h): n_filters bitmaps `stride_words` apart, one n_bits for all, and the
-// batch's filter_of, all on the device.
-struct FilterMultiSpec {
-  uint64_t stride_words;
-  uint32_t n_filters;
-  const uint32_t* filter_of;
-};
-
-// An adaptive call's own arguments (filter_adaptive.hip.h): the call's nprobe is nprobe_max; out_nprobe is on the device, nullable.
+// An adaptive call's own arguments (filter_adaptive.hip.h), `on` for the calls that are: the call's nprobe is nprobe_max; out_nprobe is where
+// the call's other outputs are (host or device), nullable.
 // On a handle sharded by cluster a rank counts the allowed rows of the lists it stores only, and the depth needs every list's:
 //   allowed_len  a partial call: the GLOBAL counts [n_filters or 1][k], the caller's (vers_ivf_filter_allowed_len_dev on every rank, summed);
 //                the count kernel is not run
 //   reduce       a sharded call: told this rank's counts (n words, on `st`), it exchanges them and names the global ones
 struct AdaptiveSpec {
-  uint32_t nprobe_min, min_allowed;
-  uint32_t* out_nprobe;
+  bool on = false;
+  uint32_t nprobe_min = 0, min_allowed = 0;
+  uint32_t* out_nprobe = nullptr;
   const uint32_t* allowed_len = nullptr;
   std::function<int32_t(const uint32_t* local, size_t n, const uint32_t*& global, hipStream_t st)> reduce;
 };
+static AdaptiveSpec adaptive_spec(uint32_t nprobe_min, uint32_t min_allowed, uint32_t* out_nprobe, const uint32_t* allowed_len = nullptr) {
+  AdaptiveSpec as;
+  as.on = true; as.nprobe_min = nprobe_min; as.min_allowed = min_allowed; as.out_nprobe = out_nprobe; as.allowed_len = allowed_len;
+  return as;
+}
+static AdaptiveSpec adaptive_spec(const vers_adaptive_t* ad) {  // (NULL: plain depth)
+  return ad ? adaptive_spec(ad->nprobe_min, ad->min_allowed, ad->out_nprobe_dev, ad->allowed_len_dev) : AdaptiveSpec{};
+}
 
 // allowed_len[f * k + L] of the call's mask(s) into `out` ([n_sets][k]): a record of the scan-timing ring of its own.  On a sharded handle the
 // lists this rank stores, 0 for the others (filter_adaptive.hip.h).
-static int32_t filter_count_allowed(vers_ivf* h, const FilterParams* f, const FilterMultiParams* fm, uint32_t n_sets, uint32_t* out, hipStream_t st) {
+static int32_t filter_count_allowed(vers_ivf* h, const FilterMasks& m, uint32_t n_sets, uint32_t* out, hipStream_t st) {
   return timed_scan(st, [&]() -> int32_t {
     if (h->k == 0) return VERS_OK;
     const uint32_t blocks = (h->k + kAdpThreads / kWave - 1) / (kAdpThreads / kWave);
     const uint8_t* owner = h->world > 1 ? h->owner.as<uint8_t>() : (const uint8_t*)nullptr;
-    if (fm)
-      hipLaunchKernelGGL(filter_multi_allowed_len_kernel, dim3(blocks), dim3(kAdpThreads), 0, st, fm->row_sets, fm->tile_sets, (const uint32_t*)h->list_off.as<uint32_t>(),
+    if (m.per_query)
+      hipLaunchKernelGGL(filter_multi_allowed_len_kernel, dim3(blocks), dim3(kAdpThreads), 0, st, m.multi.row_sets, m.multi.tile_sets, (const uint32_t*)h->list_off.as<uint32_t>(),
                          (const uint32_t*)h->list_len.as<uint32_t>(), h->k, n_sets, out, owner, h->rank);
     else
-      hipLaunchKernelGGL(filter_allowed_len_kernel, dim3(blocks), dim3(kAdpThreads), 0, st, f->tile_mask, (const uint32_t*)h->list_off.as<uint32_t>(),
+      hipLaunchKernelGGL(filter_allowed_len_kernel, dim3(blocks), dim3(kAdpThreads), 0, st, m.one.tile_mask, (const uint32_t*)h->list_off.as<uint32_t>(),
                          (const uint32_t*)h->list_len.as<uint32_t>(), h->k, out, owner, h->rank);
     VERS_HIP_TRY(hipGetLastError());
     return VERS_OK;
   });
 }
 
-// filter_begin's twin for a filter per query: row_sets (8 bytes per storage row, whole tiles) and tile_sets (in the per-call mask's buffer)
+// filter_one_begin's twin for a filter per query: row_sets (8 bytes per storage row, whole tiles) and tile_sets (in the per-call mask's buffer)
 // over `n_rows` storage rows + the zeroed counters; the mask kernel inside the same bracket of the scan-timing ring.
-static int32_t filter_multi_begin(vers_ivf* h, const uint64_t* filters_dev, uint64_t n_bits, const FilterMultiSpec& ms, uint64_t n_rows, hipStream_t st,
-                                  FilterMultiParams& f) {
+static int32_t filter_multi_begin(vers_ivf* h, const FilterArg& ms, uint64_t n_rows, hipStream_t st, FilterMultiParams& f) {
+  const uint64_t* const filters_dev = ms.filters;
+  const uint64_t n_bits = ms.n_bits;
   const uint64_t n_tiles = (n_rows + kWave - 1) / kWave;
   const size_t tile_bytes = std::max<size_t>(1, n_tiles) * sizeof(uint64_t), row_bytes = tile_bytes * kWave;
-  if (W->prep) {  // a prepared call: no mask kernel, the object's sets
+  if (ms.prep) {  // a prepared call: no mask kernel, the object's sets
     if (int32_t rc = filter_counters_begin(h, st, f.stats, f.wave_slots)) return rc;
-    if (int32_t rc = prepared_begin(h, true, st, f.stats)) return rc;
-    f.tile_sets = W->prep->tile_sets.as<uint64_t>();
-    f.row_sets = W->prep->row_sets.as<uint64_t>();
+    if (int32_t rc = prepared_begin(h, ms.prep, true, st, f.stats)) return rc;
+    f.tile_sets = ms.prep->tile_sets.as<uint64_t>();
+    f.row_sets = ms.prep->row_sets.as<uint64_t>();
     f.filter_of = ms.filter_of;
     f.n_filters = ms.n_filters;
     return VERS_OK;
@@ -787,6 +819,14 @@ static int32_t filter_multi_begin(vers_ivf* h, const uint64_t* filters_dev, uint
     return VERS_OK;
   });
 }
+
+// the masks of the call's filter over `n_rows` storage rows, in the form the filter asks for
+static int32_t filter_begin(vers_ivf* h, const FilterArg& a, uint64_t n_rows, hipStream_t st, FilterMasks& m) {
+  m.per_query = a.multi();
+  return m.per_query ? filter_multi_begin(h, a, n_rows, st, m.multi) : filter_one_begin(h, a, n_rows, st, m.one);
+}
+// the rows an exhaustive filtered scan covers: none on an index without centroids (a streamed upload in progress included)
+static uint64_t stored_rows(const vers_ivf* h) { return (h->k == 0 || h->up.open) ? 0 : h->cap_rows; }
 
 // the call's counters into the handle's totals, and the workspace noted for vers_ivf_filter_stats
 static int32_t filter_end(vers_ivf* h, hipStream_t st) {
@@ -859,52 +899,48 @@ int32_t exhaustive_dev_locked(vers_ivf* h, const float* q_dev, uint64_t ldq_in, 
 
 // Filtered search over the min(nprobe, k) nearest lists, nprobe >= 1: mask kernel, the plan of the ordered-chain scan (the lists are ranked as
 // without a filter: the centroids do not depend on it), per pass the filtered scan, ivf_merge_kernel as it is.  The caller has checked nprobe,
-// the handle's sharding and its centroids.  multi: bits_dev holds the bitmaps of a call with a filter per query; the mask kernel and the scan
-// kernel are then filter_multi.hip.h's, everything else is the same.
+// the handle's sharding and its centroids.  flt says which mask kernel and which scan kernel (FilterArg); everything else is the same.
 // adaptive: nprobe is nprobe_max and every query probes to its own depth (filter_adaptive.hip.h) -- behind the mask kernel the allowed rows
 // per list are counted (a record of the scan-timing ring of its own, between the mask's and the passes'), and the plan is the adaptive one.
-int32_t filtered_dev_locked(vers_ivf* h, const float* q_dev, uint64_t ldq_in, uint32_t b, uint32_t top_k, uint32_t nprobe, const uint64_t* bits_dev,
-                            uint64_t n_bits, uint64_t* out_ids, float* out_dist, uint32_t* out_count, hipStream_t st, const FilterMultiSpec* multi = nullptr,
-                            const AdaptiveSpec* adaptive = nullptr, uint64_t* out_keys = nullptr) {
+int32_t filtered_dev_locked(vers_ivf* h, const float* q_dev, uint64_t ldq_in, uint32_t b, uint32_t top_k, uint32_t nprobe, const FilterArg& flt, const AdaptiveSpec& adaptive,
+                            uint64_t* out_ids, float* out_dist, uint32_t* out_count, hipStream_t st, uint64_t* out_keys = nullptr) {
   // out_keys: a rank's PARTIAL (search_dev_locked's: the merge stores the keys beside the ids, kKeyMax padded); top_k >= 1 then.  The handle
   // may be sharded by cluster: the plan scans the lists this rank stores, sequence numbers run over the global lengths.
   if (b == 0) return VERS_OK;
   if (top_k == 0) {
     VERS_HIP_TRY(hipMemsetAsync(out_count, 0, sizeof(uint32_t) * b, st));
-    if (adaptive && adaptive->out_nprobe) VERS_HIP_TRY(hipMemsetAsync(adaptive->out_nprobe, 0, sizeof(uint32_t) * b, st));  // (nothing is probed)
+    if (adaptive.on && adaptive.out_nprobe) VERS_HIP_TRY(hipMemsetAsync(adaptive.out_nprobe, 0, sizeof(uint32_t) * b, st));  // (nothing is probed)
     return VERS_OK;
   }
-  FilterParams f;
-  FilterMultiParams fm;
-  if (int32_t rc = multi ? filter_multi_begin(h, bits_dev, n_bits, *multi, h->cap_rows, st, fm) : filter_begin(h, bits_dev, n_bits, h->cap_rows, st, f)) return rc;
-  const FilterChoice flt{multi ? nullptr : &f, multi ? &fm : nullptr};
+  FilterMasks masks;
+  if (int32_t rc = filter_begin(h, flt, h->cap_rows, st, masks)) return rc;
   AdaptiveQ aq;
-  if (adaptive) {
-    const uint32_t n_sets = multi ? multi->n_filters : 1u;
-    aq.p_min = std::min<uint32_t>(adaptive->nprobe_min, h->k); aq.min_allowed = adaptive->min_allowed; aq.allowed_len = adaptive->allowed_len;
-    aq.filter_of = multi ? multi->filter_of : (const uint32_t*)nullptr; aq.n_filters = n_sets; aq.out_nprobe = adaptive->out_nprobe;
+  if (adaptive.on) {
+    const uint32_t n_sets = flt.n_sets();
+    aq.p_min = std::min<uint32_t>(adaptive.nprobe_min, h->k); aq.min_allowed = adaptive.min_allowed; aq.allowed_len = adaptive.allowed_len;
+    aq.filter_of = flt.filter_of; aq.n_filters = n_sets; aq.out_nprobe = adaptive.out_nprobe;
     if (aq.allowed_len == nullptr) {  // (a partial call brings the global counts: nothing to count)
-      const uint32_t* counts = W->prep ? W->prep->alen.as<uint32_t>() : (const uint32_t*)nullptr;  // (a prepared call: the object has them, kept with its masks)
+      const uint32_t* counts = flt.prep ? flt.prep->alen.as<uint32_t>() : (const uint32_t*)nullptr;  // (a prepared call: the object has them, kept with its masks)
       if (counts == nullptr) {
         if (int32_t rc = W->flt_alen.reserve((size_t)n_sets * h->k * sizeof(uint32_t))) return rc;
-        if (int32_t rc = filter_count_allowed(h, multi ? nullptr : &f, multi ? &fm : nullptr, n_sets, W->flt_alen.as<uint32_t>(), st)) return rc;
+        if (int32_t rc = filter_count_allowed(h, masks, n_sets, W->flt_alen.as<uint32_t>(), st)) return rc;
         counts = W->flt_alen.as<uint32_t>();
       }
       aq.allowed_len = counts;
-      if (adaptive->reduce)
-        if (int32_t rc = adaptive->reduce(counts, (size_t)n_sets * h->k, aq.allowed_len, st)) return rc;
+      if (adaptive.reduce)
+        if (int32_t rc = adaptive.reduce(counts, (size_t)n_sets * h->k, aq.allowed_len, st)) return rc;
     }
   }
   SearchPlan s;
   W->no_ahead = true;
-  const int32_t prc = plan_search(h, q_dev, ldq_in, b, top_k, nprobe, st, s, true, adaptive ? &aq : nullptr);
+  const int32_t prc = plan_search(h, q_dev, ldq_in, b, top_k, nprobe, st, s, true, adaptive.on ? &aq : nullptr);
   W->no_ahead = false;
   if (prc) return prc;
   { const int ev = scan_events_ref().load(); W->ev_on = ev == 1 || ev == 2; }  // (the plan set it for an unfiltered call)
   W->tot_valid = true;
   if (int32_t rc = run_chain_passes(h, s, b, top_k, out_ids, out_dist, out_count, out_keys, /*unfiltered=*/false, st, [&](const uint64_t* lower) -> int32_t {
         return with_qg<1, 8, 16>(s.QG, [&](auto qg) -> int32_t {
-          return launch_ivf_scan(h, make_ivf_src<decltype(qg)::value>(h, s, 0u), (uint32_t)s.items_bound, st, lower, flt);
+          return launch_ivf_scan(h, make_ivf_src<decltype(qg)::value>(h, s, 0u), (uint32_t)s.items_bound, st, lower, masks.choice());
         });
       })) return rc;
   return filter_end(h, st);
@@ -913,9 +949,8 @@ int32_t filtered_dev_locked(vers_ivf* h, const float* q_dev, uint64_t ldq_in, ui
 // The exhaustive scan with the filtered kernel: every allowed row that is in a list now, ascending (distance, vec id).  Option "seg_rows" fixes
 // the segment length here as it does for the chains.  An index without centroids (a streamed upload in progress included) is scanned as zero
 // rows: counts 0.
-int32_t exhaustive_filtered_dev_locked(vers_ivf* h, const float* q_dev, uint64_t ldq_in, uint32_t b, uint32_t top_k, uint32_t metric, const uint64_t* bits_dev,
-                                       uint64_t n_bits, uint64_t* out_ids, float* out_dist, uint32_t* out_count, hipStream_t st, const FilterMultiSpec* multi = nullptr,
-                                       uint64_t* out_keys = nullptr, uint64_t* out_key_ids = nullptr) {
+int32_t exhaustive_filtered_dev_locked(vers_ivf* h, const float* q_dev, uint64_t ldq_in, uint32_t b, uint32_t top_k, uint32_t metric, const FilterArg& flt, uint64_t* out_ids,
+                                       float* out_dist, uint32_t* out_count, hipStream_t st, uint64_t* out_keys = nullptr, uint64_t* out_key_ids = nullptr) {
   // out_keys / out_key_ids: a rank's PARTIAL as well -- (distance bits << 32) | vec id beside the ids, kKeyMax padded, packed from the local
   // result (out_ids / out_dist / out_count are then the caller's scratch); top_k >= 1 then
   if (b == 0) return VERS_OK;
@@ -923,12 +958,10 @@ int32_t exhaustive_filtered_dev_locked(vers_ivf* h, const float* q_dev, uint64_t
     VERS_HIP_TRY(hipMemsetAsync(out_count, 0, sizeof(uint32_t) * b, st));
     return VERS_OK;
   }
-  const uint64_t n_rows = (h->k == 0 || h->up.open) ? 0 : h->cap_rows;
-  FilterParams f;
-  FilterMultiParams fm;
-  if (int32_t rc = multi ? filter_multi_begin(h, bits_dev, n_bits, *multi, n_rows, st, fm) : filter_begin(h, bits_dev, n_bits, n_rows, st, f)) return rc;
-  const FilterChoice flt{multi ? nullptr : &f, multi ? &fm : nullptr};
-  if (int32_t rc = run_exhaustive_passes(h, q_dev, ldq_in, b, top_k, metric, n_rows, knobs().seg_rows, flt, out_ids, out_dist, out_count, st)) return rc;
+  const uint64_t n_rows = stored_rows(h);
+  FilterMasks masks;
+  if (int32_t rc = filter_begin(h, flt, n_rows, st, masks)) return rc;
+  if (int32_t rc = run_exhaustive_passes(h, q_dev, ldq_in, b, top_k, metric, n_rows, knobs().seg_rows, masks.choice(), out_ids, out_dist, out_count, st)) return rc;
   if (out_keys != nullptr) {
     const size_t part = (size_t)b * top_k;
     hipLaunchKernelGGL(pack_exhaustive_keys_kernel, dim3((unsigned)((part + 255) / 256)), dim3(256), 0, st, (const uint64_t*)out_ids, (const float*)out_dist,
@@ -938,25 +971,74 @@ int32_t exhaustive_filtered_dev_locked(vers_ivf* h, const float* q_dev, uint64_t
   return filter_end(h, st);
 }
 
-// what the four filtered entry points refuse before they touch the device
-static int32_t filter_check(vers_ivf* h, const char* who, bool probed, uint32_t nprobe, const uint64_t* bits, uint64_t n_bits) {
-  if (n_bits != 0 && bits == nullptr) return fail(VERS_ERR_INVALID, std::string(who) + ": n_bits > 0 with a NULL bitmap");
-  if (probed && nprobe == 0)
-    return fail(VERS_ERR_INVALID, std::string(who) + ": nprobe must be at least 1 (the reference's spill walk depends on the filtered list lengths: out of scope)");
-  if (h->world > 1) return fail(VERS_ERR_INVALID, std::string(who) + ": the handle is sharded by cluster; filtered search on a sharded handle is out of scope for this call (use vers_ivf_search_filtered_sharded_dev / vers_ivf_search_exhaustive_filtered_sharded_dev, or the _filtered_partial_dev calls + vers_topk_merge_dev)");
-  if (probed && h->k == 0) return fail(VERS_ERR_INSUFFICIENT, "search on an index without centroids (reference: index out of bounds, ivfflat.rs:169)");
+// The local part of a whole (not a rank's partial) filtered top-k call: the probed lists, or every stored row under the metric given in place of nprobe.
+static int32_t filtered_topk_locked(vers_ivf* h, bool probed, const float* q_dev, uint64_t ldq_in, uint32_t b, uint32_t top_k, uint32_t nprobe_or_metric, const FilterArg& flt,
+                                    const AdaptiveSpec& adaptive, uint64_t* out_ids, float* out_dist, uint32_t* out_count, hipStream_t st) {
+  if (probed) return filtered_dev_locked(h, q_dev, ldq_in, b, top_k, nprobe_or_metric, flt, adaptive, out_ids, out_dist, out_count, st);
+  return exhaustive_filtered_dev_locked(h, q_dev, ldq_in, b, top_k, nprobe_or_metric, flt, out_ids, out_dist, out_count, st);
+}
+
+// ---- what the filtered calls refuse before they touch the device: ONE check, told what differs between them ----
+//   form         how the call takes its filter: one bitmap (kPerCall); the _multi form, where a NULL filter_of is an error (kMulti); the _multi
+//                form of the shard and prepared calls, where a NULL filter_of means one bitmap for the batch and needs n_filters == 1 (kEither)
+//   sharded_use  the sentence that names the calls to use on a handle sharded by cluster, which this call then refuses; NULL: the call serves a
+//                rank (the _partial, _sharded and _prepared calls).  Such a call has no walk order on stored rows: storage order has no key
+//                the ranks share.
+// Where several refusals apply the first in this order is reported: flags (and walk order), n_filters == 0, VERS_FILTER_MAX, filter_of,
+// stride, NULL bitmap, nprobe, sharded handle, no centroids -- except that the _multi range calls test the flags behind their own four.
+// b == 0 passes without bitmaps or filter_of: the top-k calls check before they return for an empty batch.
+enum class FilterForm { kPerCall, kMulti, kEither };
+struct FilterCheck {
+  bool probed, range;
+  FilterForm form;
+  const char* sharded_use;
+};
+static const char* const kUseShardedTopk = ": the handle is sharded by cluster; filtered search on a sharded handle is out of scope for this call (use vers_ivf_search_filtered_sharded_dev / vers_ivf_search_exhaustive_filtered_sharded_dev, or the _filtered_partial_dev calls + vers_topk_merge_dev)";
+static const char* const kUseShardedRange = ": the handle is sharded by cluster; filtered range search on a sharded handle is out of scope for this call (use vers_ivf_range_search_filtered_sharded_dev / vers_ivf_range_search_exhaustive_filtered_sharded_dev, or the _filtered_partial_dev calls + vers_range_merge_dev)";
+static int32_t filtered_check(vers_ivf* h, const char* who, const FilterCheck& c, uint32_t nprobe, uint32_t flags, uint32_t b, const FilterArg& f) {
+  auto bad = [&](const char* what) -> int32_t { return fail(VERS_ERR_INVALID, std::string(who) + what); };
+  auto flags_ok = [&]() -> int32_t {
+    if (flags & ~VERS_RANGE_WALK_ORDER) return bad(": unknown flag bits");
+    if (c.sharded_use == nullptr && !c.probed && (flags & VERS_RANGE_WALK_ORDER))
+      return bad(": no walk order across ranks (storage order has no key the ranks share); use the default order");
+    return VERS_OK;
+  };
+  const bool flags_late = c.form == FilterForm::kMulti;
+  if (c.range && !flags_late)
+    if (int32_t rc = flags_ok()) return rc;
+  if (c.form != FilterForm::kPerCall) {
+    if (b != 0 && f.n_filters == 0) return bad(": n_filters == 0");
+    if (f.n_filters > VERS_FILTER_MAX) return bad(": more than VERS_FILTER_MAX bitmaps in one call; split the batch by allowed set");
+    if (b != 0 && f.filter_of == nullptr) {
+      if (c.form == FilterForm::kMulti) return bad(": NULL filter_of");
+      if (f.n_filters != 1) return bad(": a NULL filter_of means one bitmap for the batch: n_filters must be 1");
+    }
+    if (f.n_bits != 0 && f.stride_words < (f.n_bits + 63) / 64) return bad(": filter_stride_words is smaller than ceil(n_bits / 64)");
+  }
+  if (c.range && flags_late)
+    if (int32_t rc = flags_ok()) return rc;
+  if (f.n_bits != 0 && f.filters == nullptr) return bad(c.form == FilterForm::kEither ? ": n_bits > 0 with NULL filters" : ": n_bits > 0 with a NULL bitmap");
+  if (c.probed && nprobe == 0)
+    return bad(c.range ? ": nprobe must be at least 1 (the reference's spill walk is defined by top_k: it has no range meaning)"
+                       : ": nprobe must be at least 1 (the reference's spill walk depends on the filtered list lengths: out of scope)");
+  if (h->world > 1 && c.sharded_use != nullptr) return bad(c.sharded_use);
+  if (c.probed && h->k == 0)
+    return fail(VERS_ERR_INSUFFICIENT, c.range ? "range search on an index without centroids (reference: index out of bounds, ivfflat.rs:169)"
+                                               : "search on an index without centroids (reference: index out of bounds, ivfflat.rs:169)");
   return VERS_OK;
 }
 
-// what the four adaptive entry points refuse on top of that (filter_adaptive.hip.h); nullptr: not an adaptive call
-struct AdaptiveArgs {
-  uint32_t nprobe_min, min_allowed;
-  uint32_t* out_nprobe;  // host or device as the call's other outputs, nullable
-};
-static int32_t adaptive_check(const char* who, const AdaptiveArgs* ad, uint32_t nprobe_max) {
-  if (ad == nullptr) return VERS_OK;
-  if (ad->nprobe_min == 0) return fail(VERS_ERR_INVALID, std::string(who) + ": nprobe_min must be at least 1");
-  if (nprobe_max < ad->nprobe_min) return fail(VERS_ERR_INVALID, std::string(who) + ": nprobe_max is below nprobe_min");
+// What the adaptive calls refuse on top of that (filter_adaptive.hip.h), before the handle is locked.  On a handle sharded by cluster the depth
+// needs every rank's counts: a partial must bring them, a sharded (or prepared) call exchanges them itself.
+enum class AdaptiveKind { kCall, kPartial, kSharded };
+static int32_t adaptive_check(const char* who, const AdaptiveSpec& ad, uint32_t nprobe_max, AdaptiveKind kind) {
+  if (!ad.on) return VERS_OK;
+  auto bad = [&](const char* what) -> int32_t { return fail(VERS_ERR_INVALID, std::string(who) + what); };
+  if (ad.nprobe_min == 0) return bad(": nprobe_min must be at least 1");
+  if (nprobe_max < ad.nprobe_min) return bad(kind == AdaptiveKind::kCall ? ": nprobe_max is below nprobe_min" : ": nprobe (the adaptive call's nprobe_max) is below nprobe_min");
+  if (kind == AdaptiveKind::kPartial && ad.allowed_len == nullptr)
+    return bad(": an adaptive partial needs the GLOBAL allowed counts (vers_ivf_filter_allowed_len_dev on every rank, summed)");
+  if (kind == AdaptiveKind::kSharded && ad.allowed_len != nullptr) return bad(": allowed_len_dev must be NULL (the call exchanges the counts itself)");
   return VERS_OK;
 }
 
@@ -1100,11 +1182,11 @@ struct IvfRangeSource {
 // keeps walk order when asked to: ascending sequence number (a sharded rank walks its probes in rank order).
 struct ProbedRangeSource : IvfRangeSource {
   static constexpr bool kKeyIds = false, kPartials = true;
-  const char* who = "vers_ivf_range_search";
+  const char* who;
   const float* q_dev; uint64_t ldq_in; uint32_t b, nprobe;
   SearchPlan s;
   bool planned = false;
-  ProbedRangeSource(vers_ivf* hh, const float* q, uint64_t ldq, uint32_t bb, uint32_t np) : IvfRangeSource{hh}, q_dev(q), ldq_in(ldq), b(bb), nprobe(np) {}
+  ProbedRangeSource(vers_ivf* hh, const char* w, const float* q, uint64_t ldq, uint32_t bb, uint32_t np) : IvfRangeSource{hh}, who(w), q_dev(q), ldq_in(ldq), b(bb), nprobe(np) {}
   hipStream_t st_ = nullptr;
   ~ProbedRangeSource() {  // a look-ahead slot the plan consumed is free again behind whatever the call queued, on EVERY way out
     if (planned && s.took && hipEventRecord(s.took->freed, st_) == hipSuccess) s.took->freed_rec = true;
@@ -1118,13 +1200,21 @@ struct ProbedRangeSource : IvfRangeSource {
     return VERS_OK;
   }
   bool walk_order(uint32_t flags, bool) const { return (flags & VERS_RANGE_WALK_ORDER) != 0; }
-  template <class Fill>
-  int32_t launch(Fill, RangeParams p, hipStream_t st) const {  // hand-out counter as launch_ivf_scan's; no pruning: every row within the radius counts
+  // one pass: pass(query-group tag, metric, the items, how many) launches it over the plan's items.  Hand-out counter as launch_ivf_scan's; no
+  // pruning: every row within the radius counts
+  template <class Pass>
+  int32_t with_items(RangeParams& p, hipStream_t st, Pass&& pass) const {
     return with_qg<1, 8, 16>(s.QG, [&](auto qg) -> int32_t {
       constexpr int QG = decltype(qg)::value;
       if (QG != 1)
         if (int32_t rc = fresh_quad_counter(st, &p.next_quad)) return rc;
-      return launch_range_pass<QG, Fill::value>(h->n_cu, h->ld, h->metric, make_ivf_src<QG>(h, s, 0u), (uint32_t)s.items_bound, p, st);
+      return pass(qg, h->metric, make_ivf_src<QG>(h, s, 0u), (uint32_t)s.items_bound);
+    });
+  }
+  template <class Fill>
+  int32_t launch(Fill, RangeParams p, hipStream_t st) const {
+    return with_items(p, st, [&](auto qg, int metric, const auto& src, uint32_t items) -> int32_t {
+      return launch_range_pass<decltype(qg)::value, Fill::value>(h->n_cu, h->ld, metric, src, items, p, st);
     });
   }
 };
@@ -1135,13 +1225,13 @@ struct ProbedRangeSource : IvfRangeSource {
 // points refuse the flag).
 struct StoredRangeSource : IvfRangeSource {
   static constexpr bool kKeyIds = true, kPartials = true;
-  const char* who = "vers_ivf_range_search_exhaustive";
+  const char* who;
   const float* q_dev; uint64_t ldq_in; uint32_t b, metric;
   uint64_t n_rows = 0;
   SegPlan sp{};
-  StoredRangeSource(vers_ivf* hh, const float* q, uint64_t ldq, uint32_t bb, uint32_t m) : IvfRangeSource{hh}, q_dev(q), ldq_in(ldq), b(bb), metric(m) {}
+  StoredRangeSource(vers_ivf* hh, const char* w, const float* q, uint64_t ldq, uint32_t bb, uint32_t m) : IvfRangeSource{hh}, who(w), q_dev(q), ldq_in(ldq), b(bb), metric(m) {}
   int32_t prepare(hipStream_t st, uint64_t& slots_per_query) {
-    n_rows = (h->k == 0 || h->up.open) ? 0 : h->cap_rows;
+    n_rows = stored_rows(h);
     sp = seg_plan(n_rows, b, h->ld, h->n_cu, knobs().seg_rows);
     if (int32_t rc = W->qil.reserve((size_t)sp.n_qg * h->ldq * sp.QG * sizeof(float))) return rc;
     if (int32_t rc = launch_stage_queries(q_dev, ldq_in, h->d, W->qil.as<float>(), h->ldq, b, sp.QG, st)) return rc;
@@ -1153,198 +1243,84 @@ struct StoredRangeSource : IvfRangeSource {
   void launch_key_ids(const uint64_t* keys, uint64_t n, uint64_t* ids, hipStream_t st) const {
     hipLaunchKernelGGL(range_key_ids_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, keys, n, ids);
   }
-  template <class Fill>
-  int32_t launch(Fill, const RangeParams& p, hipStream_t st) const {
+  template <class Pass>
+  int32_t with_items(RangeParams&, hipStream_t, Pass&& pass) const {  // (ProbedRangeSource::with_items over the segment items)
     return with_qg<1, 8>(sp.QG, [&](auto qg) -> int32_t {
-      constexpr int QG = decltype(qg)::value;
-      using Src = SegSrc<QG, true>;
-      return launch_range_pass<QG, Fill::value>(h->n_cu, h->ld, (int)metric,
-                                                make_seg_src<Src>(h->rows.as<float>(), n_rows, h->ld, sp, W->qil.as<float>(), h->ldq, b, nullptr, 0, h->row_ids.as<uint32_t>()),
-                                                sp.n_items, p, st);
+      using Src = SegSrc<decltype(qg)::value, true>;
+      return pass(qg, (int)metric, make_seg_src<Src>(h->rows.as<float>(), n_rows, h->ld, sp, W->qil.as<float>(), h->ldq, b, nullptr, 0, h->row_ids.as<uint32_t>()), sp.n_items);
+    });
+  }
+  template <class Fill>
+  int32_t launch(Fill, RangeParams p, hipStream_t st) const {
+    return with_items(p, st, [&](auto qg, int metric, const auto& src, uint32_t items) -> int32_t {
+      return launch_range_pass<decltype(qg)::value, Fill::value>(h->n_cu, h->ld, metric, src, items, p, st);
     });
   }
 };
 
 // A range search on the index, on `st`: over the probed lists, or (probed = false) over every stored row under the metric given in place of
-// nprobe.  own_out / part: range_search_run.
-int32_t range_dev_locked(vers_ivf* h, bool probed, const float* q_dev, uint64_t ldq_in, uint32_t b, const float* radius_dev, uint32_t nprobe_or_metric, uint32_t flags,
-                         uint64_t* lims_dev, uint64_t* ids_dev, float* dist_dev, uint64_t cap, bool own_out, uint64_t* out_total, hipStream_t st,
+// nprobe.  own_out / part: range_search_run.  who: the name the source reports under (the unfiltered calls all report as the host-pointer call).
+int32_t range_dev_locked(vers_ivf* h, const char* who, bool probed, const float* q_dev, uint64_t ldq_in, uint32_t b, const float* radius_dev, uint32_t nprobe_or_metric,
+                         uint32_t flags, uint64_t* lims_dev, uint64_t* ids_dev, float* dist_dev, uint64_t cap, bool own_out, uint64_t* out_total, hipStream_t st,
                          RangePartial* part = nullptr) {
   if (probed) {
-    ProbedRangeSource src(h, q_dev, ldq_in, b, nprobe_or_metric);
+    ProbedRangeSource src(h, who, q_dev, ldq_in, b, nprobe_or_metric);
     return range_search_run(src, W->rg, b, radius_dev, flags, lims_dev, ids_dev, dist_dev, cap, own_out, out_total, st, part);
   }
-  StoredRangeSource src(h, q_dev, ldq_in, b, nprobe_or_metric);
+  StoredRangeSource src(h, who, q_dev, ldq_in, b, nprobe_or_metric);
   return range_search_run(src, W->rg, b, radius_dev, flags, lims_dev, ids_dev, dist_dev, cap, own_out, out_total, st, part);
 }
+static const char* range_name(bool probed) { return probed ? "vers_ivf_range_search" : "vers_ivf_range_search_exhaustive"; }
 
-// ---- filtered range search (filter_range.hip.h): the range protocol over the allowed rows of a per-call bitmap -----------------------
-// one pass of the filtered range walk; not timed by the scan-timing ring (no range pass is), and no more waves than counter slots (filter_begin)
+// ---- filtered range search (filter_range.hip.h, filter_range_multi.hip.h): the range protocol over the allowed rows ---------------------------
+// one pass of the filtered range walk, with the kernel of the call's masks; not timed by the scan-timing ring (no range pass is), and no more
+// waves than counter slots (filter_begin)
 template <int QG, bool FILL, class Src>
-static int32_t launch_filter_range_pass(vers_ivf* h, int metric, const Src& src, uint32_t items, const RangeParams& p, const FilterParams& f, hipStream_t st) {
+static int32_t launch_filter_range_pass(vers_ivf* h, int metric, const Src& src, uint32_t items, const RangeParams& p, FilterChoice f, hipStream_t st) {
   const uint32_t blocks = scan_grid(h->n_cu, QG, h->ld, items, (uint32_t)(filter_wave_slots(h) / kWavesPerBlock));
   return with_metric(metric, [&](auto m) -> int32_t {
-    return launch_scan(filter_range_scan_kernel<QG, decltype(m)::value, FILL, Src>, blocks, kWavesPerBlock, scan_lds_bytes(QG, h->ld), st, src, p, f);
+    if (f.multi) return launch_scan(filter_range_multi_scan_kernel<QG, decltype(m)::value, FILL, Src>, blocks, kWavesPerBlock, scan_lds_bytes(QG, h->ld), st, src, p, *f.multi);
+    return launch_scan(filter_range_scan_kernel<QG, decltype(m)::value, FILL, Src>, blocks, kWavesPerBlock, scan_lds_bytes(QG, h->ld), st, src, p, *f.one);
   });
 }
 
-// ProbedRangeSource behind a filter: the mask kernel (with its record in the scan-timing ring) opens the first phase, the plan is the
-// unfiltered one (the lists are ranked as without a filter) but neither consumes nor starts a look-ahead, both passes run the filtered kernel.
-struct FilteredProbedRangeSource : ProbedRangeSource {
-  static constexpr bool kPartials = true;  // (a rank's partial of the _filtered_partial / _filtered_sharded calls)
-  const char* who = "vers_ivf_range_search_filtered";
-  const uint64_t* bits_dev; uint64_t n_bits;
-  FilterParams f{};
-  FilteredProbedRangeSource(vers_ivf* hh, const float* q, uint64_t ldq, uint32_t bb, uint32_t np, const uint64_t* bits, uint64_t nb)
-      : ProbedRangeSource(hh, q, ldq, bb, np), bits_dev(bits), n_bits(nb) {}
+// A range source behind a filter, Base one of ProbedRangeSource and StoredRangeSource: the mask kernel (with its record in the scan-timing ring)
+// opens the first phase, over the rows the scan covers (none on an index without centroids for the stored rows); both passes run the filtered
+// kernel over the base's items.  The probed plan is the unfiltered one (the lists are ranked as without a filter) but neither consumes nor
+// starts a look-ahead.  Serves a rank's partial of the _filtered_partial / _filtered_sharded calls too.
+template <class Base>
+struct Filtered : Base {
+  static constexpr bool kProbed = std::is_same<Base, ProbedRangeSource>::value;
+  FilterArg flt;
+  FilterMasks masks{};
+  Filtered(vers_ivf* hh, const char* w, const float* q, uint64_t ldq, uint32_t bb, uint32_t nprobe_or_metric, const FilterArg& f) : Base(hh, w, q, ldq, bb, nprobe_or_metric), flt(f) {}
   int32_t prepare(hipStream_t st, uint64_t& slots_per_query) {
-    if (int32_t rc = filter_begin(h, bits_dev, n_bits, h->cap_rows, st, f)) return rc;
-    W->no_ahead = true;
-    const int32_t rc = ProbedRangeSource::prepare(st, slots_per_query);
-    W->no_ahead = false;
+    vers_ivf* const h = this->h;
+    if (int32_t rc = filter_begin(h, flt, kProbed ? h->cap_rows : stored_rows(h), st, masks)) return rc;
+    if (kProbed) W->no_ahead = true;
+    const int32_t rc = Base::prepare(st, slots_per_query);
+    if (kProbed) W->no_ahead = false;
     return rc;
   }
   template <class Fill>
   int32_t launch(Fill, RangeParams p, hipStream_t st) const {
-    return with_qg<1, 8, 16>(s.QG, [&](auto qg) -> int32_t {
-      constexpr int QG = decltype(qg)::value;
-      if (QG != 1)
-        if (int32_t rc = fresh_quad_counter(st, &p.next_quad)) return rc;
-      return launch_filter_range_pass<QG, Fill::value>(h, h->metric, make_ivf_src<QG>(h, s, 0u), (uint32_t)s.items_bound, p, f, st);
-    });
-  }
-};
-
-// StoredRangeSource behind a filter: the mask covers the rows the scan covers (none on an index without centroids).
-struct FilteredStoredRangeSource : StoredRangeSource {
-  static constexpr bool kPartials = true;  // (a rank's partial of the _filtered_partial / _filtered_sharded calls)
-  const char* who = "vers_ivf_range_search_exhaustive_filtered";
-  const uint64_t* bits_dev; uint64_t n_bits;
-  FilterParams f{};
-  FilteredStoredRangeSource(vers_ivf* hh, const float* q, uint64_t ldq, uint32_t bb, uint32_t m, const uint64_t* bits, uint64_t nb)
-      : StoredRangeSource(hh, q, ldq, bb, m), bits_dev(bits), n_bits(nb) {}
-  int32_t prepare(hipStream_t st, uint64_t& slots_per_query) {
-    if (int32_t rc = filter_begin(h, bits_dev, n_bits, (h->k == 0 || h->up.open) ? 0 : h->cap_rows, st, f)) return rc;
-    return StoredRangeSource::prepare(st, slots_per_query);
-  }
-  template <class Fill>
-  int32_t launch(Fill, const RangeParams& p, hipStream_t st) const {
-    return with_qg<1, 8>(sp.QG, [&](auto qg) -> int32_t {
-      constexpr int QG = decltype(qg)::value;
-      using Src = SegSrc<QG, true>;
-      return launch_filter_range_pass<QG, Fill::value>(h, (int)metric,
-                                                       make_seg_src<Src>(h->rows.as<float>(), n_rows, h->ld, sp, W->qil.as<float>(), h->ldq, b, nullptr, 0, h->row_ids.as<uint32_t>()),
-                                                       sp.n_items, p, f, st);
+    return this->with_items(p, st, [&](auto qg, int metric, const auto& src, uint32_t items) -> int32_t {
+      return launch_filter_range_pass<decltype(qg)::value, Fill::value>(this->h, metric, src, items, p, masks.choice(), st);
     });
   }
 };
 
 // A filtered range search on the index, on `st`: mask kernel + counters, the range protocol, the counters folded.  A call that fails leaves
-// vers_ivf_filter_stats where it was.  part: a rank's partial ((key, id) pairs, range_search_run); who: the entry point's name when it is not
-// the source's own.
-int32_t range_filtered_dev_locked(vers_ivf* h, bool probed, const float* q_dev, uint64_t ldq_in, uint32_t b, const float* radius_dev, uint32_t nprobe_or_metric,
-                                  uint32_t flags, const uint64_t* bits_dev, uint64_t n_bits, uint64_t* lims_dev, uint64_t* ids_dev, float* dist_dev, uint64_t cap,
-                                  bool own_out, uint64_t* out_total, hipStream_t st, RangePartial* part = nullptr, const char* who = nullptr) {
-  if (probed) {
-    FilteredProbedRangeSource src(h, q_dev, ldq_in, b, nprobe_or_metric, bits_dev, n_bits);
-    if (who) src.who = who;
+// vers_ivf_filter_stats where it was.  part: a rank's partial ((key, id) pairs, range_search_run); who: the name the source reports under.
+int32_t range_filtered_dev_locked(vers_ivf* h, const char* who, bool probed, const float* q_dev, uint64_t ldq_in, uint32_t b, const float* radius_dev, uint32_t nprobe_or_metric,
+                                  uint32_t flags, const FilterArg& flt, uint64_t* lims_dev, uint64_t* ids_dev, float* dist_dev, uint64_t cap, bool own_out, uint64_t* out_total,
+                                  hipStream_t st, RangePartial* part = nullptr) {
+  auto run = [&](auto&& src) -> int32_t {
     if (int32_t rc = range_search_run(src, W->rg, b, radius_dev, flags, lims_dev, ids_dev, dist_dev, cap, own_out, out_total, st, part)) return rc;
     return filter_end(h, st);
-  }
-  FilteredStoredRangeSource src(h, q_dev, ldq_in, b, nprobe_or_metric, bits_dev, n_bits);
-  if (who) src.who = who;
-  if (int32_t rc = range_search_run(src, W->rg, b, radius_dev, flags, lims_dev, ids_dev, dist_dev, cap, own_out, out_total, st, part)) return rc;
-  return filter_end(h, st);
-}
-
-// ---- filtered range search with a filter per query (filter_range_multi.hip.h) ----
-// launch_filter_range_pass's twin for the per-query sets
-template <int QG, bool FILL, class Src>
-static int32_t launch_filter_range_multi_pass(vers_ivf* h, int metric, const Src& src, uint32_t items, const RangeParams& p, const FilterMultiParams& f, hipStream_t st) {
-  const uint32_t blocks = scan_grid(h->n_cu, QG, h->ld, items, (uint32_t)(filter_wave_slots(h) / kWavesPerBlock));
-  return with_metric(metric, [&](auto m) -> int32_t {
-    return launch_scan(filter_range_multi_scan_kernel<QG, decltype(m)::value, FILL, Src>, blocks, kWavesPerBlock, scan_lds_bytes(QG, h->ld), st, src, p, f);
-  });
-}
-
-// FilteredProbedRangeSource with a filter per query: filter_multi_begin's mask kernel opens the first phase, both passes run the per-query kernel.
-struct FilteredMultiProbedRangeSource : ProbedRangeSource {
-  static constexpr bool kPartials = true;  // (a rank's partial of the _filtered_partial / _filtered_sharded calls)
-  const char* who = "vers_ivf_range_search_filtered_multi";
-  const uint64_t* bits_dev; uint64_t n_bits;
-  FilterMultiSpec ms;
-  FilterMultiParams f{};
-  FilteredMultiProbedRangeSource(vers_ivf* hh, const float* q, uint64_t ldq, uint32_t bb, uint32_t np, const uint64_t* bits, uint64_t nb, const FilterMultiSpec& m)
-      : ProbedRangeSource(hh, q, ldq, bb, np), bits_dev(bits), n_bits(nb), ms(m) {}
-  int32_t prepare(hipStream_t st, uint64_t& slots_per_query) {
-    if (int32_t rc = filter_multi_begin(h, bits_dev, n_bits, ms, h->cap_rows, st, f)) return rc;
-    W->no_ahead = true;
-    const int32_t rc = ProbedRangeSource::prepare(st, slots_per_query);
-    W->no_ahead = false;
-    return rc;
-  }
-  template <class Fill>
-  int32_t launch(Fill, RangeParams p, hipStream_t st) const {
-    return with_qg<1, 8, 16>(s.QG, [&](auto qg) -> int32_t {
-      constexpr int QG = decltype(qg)::value;
-      if (QG != 1)
-        if (int32_t rc = fresh_quad_counter(st, &p.next_quad)) return rc;
-      return launch_filter_range_multi_pass<QG, Fill::value>(h, h->metric, make_ivf_src<QG>(h, s, 0u), (uint32_t)s.items_bound, p, f, st);
-    });
-  }
-};
-
-// FilteredStoredRangeSource with a filter per query: the sets cover the rows the scan covers (none on an index without centroids).
-struct FilteredMultiStoredRangeSource : StoredRangeSource {
-  static constexpr bool kPartials = true;  // (a rank's partial of the _filtered_partial / _filtered_sharded calls)
-  const char* who = "vers_ivf_range_search_exhaustive_filtered_multi";
-  const uint64_t* bits_dev; uint64_t n_bits;
-  FilterMultiSpec ms;
-  FilterMultiParams f{};
-  FilteredMultiStoredRangeSource(vers_ivf* hh, const float* q, uint64_t ldq, uint32_t bb, uint32_t m, const uint64_t* bits, uint64_t nb, const FilterMultiSpec& mm)
-      : StoredRangeSource(hh, q, ldq, bb, m), bits_dev(bits), n_bits(nb), ms(mm) {}
-  int32_t prepare(hipStream_t st, uint64_t& slots_per_query) {
-    if (int32_t rc = filter_multi_begin(h, bits_dev, n_bits, ms, (h->k == 0 || h->up.open) ? 0 : h->cap_rows, st, f)) return rc;
-    return StoredRangeSource::prepare(st, slots_per_query);
-  }
-  template <class Fill>
-  int32_t launch(Fill, const RangeParams& p, hipStream_t st) const {
-    return with_qg<1, 8>(sp.QG, [&](auto qg) -> int32_t {
-      constexpr int QG = decltype(qg)::value;
-      using Src = SegSrc<QG, true>;
-      return launch_filter_range_multi_pass<QG, Fill::value>(h, (int)metric,
-                                                             make_seg_src<Src>(h->rows.as<float>(), n_rows, h->ld, sp, W->qil.as<float>(), h->ldq, b, nullptr, 0, h->row_ids.as<uint32_t>()),
-                                                             sp.n_items, p, f, st);
-    });
-  }
-};
-
-// range_filtered_dev_locked with a filter per query: bits_dev holds the bitmaps `ms` describes.  A call that fails leaves vers_ivf_filter_stats
-// where it was.
-int32_t range_filtered_multi_dev_locked(vers_ivf* h, bool probed, const float* q_dev, uint64_t ldq_in, uint32_t b, const float* radius_dev, uint32_t nprobe_or_metric,
-                                        uint32_t flags, const uint64_t* bits_dev, uint64_t n_bits, const FilterMultiSpec& ms, uint64_t* lims_dev, uint64_t* ids_dev,
-                                        float* dist_dev, uint64_t cap, bool own_out, uint64_t* out_total, hipStream_t st, RangePartial* part = nullptr,
-                                        const char* who = nullptr) {
-  if (probed) {
-    FilteredMultiProbedRangeSource src(h, q_dev, ldq_in, b, nprobe_or_metric, bits_dev, n_bits, ms);
-    if (who) src.who = who;
-    if (int32_t rc = range_search_run(src, W->rg, b, radius_dev, flags, lims_dev, ids_dev, dist_dev, cap, own_out, out_total, st, part)) return rc;
-    return filter_end(h, st);
-  }
-  FilteredMultiStoredRangeSource src(h, q_dev, ldq_in, b, nprobe_or_metric, bits_dev, n_bits, ms);
-  if (who) src.who = who;
-  if (int32_t rc = range_search_run(src, W->rg, b, radius_dev, flags, lims_dev, ids_dev, dist_dev, cap, own_out, out_total, st, part)) return rc;
-  return filter_end(h, st);
-}
-
-// what the four filtered range entry points refuse before they touch the device: the union of the two parents' checks
-static int32_t range_filter_check(vers_ivf* h, const char* who, bool probed, uint32_t nprobe, uint32_t flags, const uint64_t* bits, uint64_t n_bits) {
-  if (flags & ~VERS_RANGE_WALK_ORDER) return fail(VERS_ERR_INVALID, std::string(who) + ": unknown flag bits");
-  if (n_bits != 0 && bits == nullptr) return fail(VERS_ERR_INVALID, std::string(who) + ": n_bits > 0 with a NULL bitmap");
-  if (probed && nprobe == 0) return fail(VERS_ERR_INVALID, std::string(who) + ": nprobe must be at least 1 (the reference's spill walk is defined by top_k: it has no range meaning)");
-  if (h->world > 1) return fail(VERS_ERR_INVALID, std::string(who) + ": the handle is sharded by cluster; filtered range search on a sharded handle is out of scope for this call (use vers_ivf_range_search_filtered_sharded_dev / vers_ivf_range_search_exhaustive_filtered_sharded_dev, or the _filtered_partial_dev calls + vers_range_merge_dev)");
-  if (probed && h->k == 0) return fail(VERS_ERR_INSUFFICIENT, "range search on an index without centroids (reference: index out of bounds, ivfflat.rs:169)");
-  return VERS_OK;
+  };
+  if (probed) return run(Filtered<ProbedRangeSource>(h, who, q_dev, ldq_in, b, nprobe_or_metric, flt));
+  return run(Filtered<StoredRangeSource>(h, who, q_dev, ldq_in, b, nprobe_or_metric, flt));
 }
 
 // what both exhaustive entry points refuse before they touch the device
@@ -1364,6 +1340,90 @@ static int32_t range_check(vers_ivf* h, const char* who, uint32_t nprobe, uint32
   if (h->world > 1 && !partial)
     return fail(VERS_ERR_INVALID, std::string(who) + ": the handle is sharded by cluster; use vers_ivf_range_search_sharded_dev (or the partial call + vers_range_merge_dev)");
   if (h->k == 0) return fail(VERS_ERR_INSUFFICIENT, "range search on an index without centroids (reference: index out of bounds, ivfflat.rs:169)");
+  return VERS_OK;
+}
+
+// ---- the entry scaffolds of the filtered calls and of the range calls: what follows a call's own argument tests --------------------------------
+// A device-pointer call: the handle locked shared, check() (what the call refuses from its arguments and the locked handle), nothing more for
+// an empty batch, then a workspace leased for `stream` and ordered on it, and body(st).  status_slot: the call synchronises and consumes its
+// status itself (the range calls: HostStatusSlot).  A call that returns for b == 0 BEFORE its checks (the range calls) does so itself.
+template <class Check, class Body>
+static int32_t dev_call(vers_ivf* h, uint32_t b, bool status_slot, void* stream, Check&& check, Body&& body) {
+  std::shared_lock<std::shared_mutex> lk(h->index);
+  if (int32_t rc = check()) return rc;
+  if (b == 0) return VERS_OK;
+  DeviceGuard g(h->device);
+  hipStream_t st = (hipStream_t)stream;
+  WsLease lease(h, true, st);
+  if (lease.rc) return lease.rc;
+  if (int32_t rc = lease.order_on(st)) return rc;
+  std::optional<HostStatusSlot> slot;
+  if (status_slot) slot.emplace(h);
+  return body(st);
+}
+
+// A host-pointer call: the same, with the queries through the pinned staging of every host-pointer call onto the workspace's own stream, and
+// body(io).  A body that fails may have queued staging copies that still read the caller's memory: the stream is waited for before the error
+// goes back.
+template <class Check, class Body>
+static int32_t host_call(vers_ivf* h, const float* queries, uint64_t q_stride_bytes, uint32_t b, uint32_t top_k, Check&& check, Body&& body) {
+  std::shared_lock<std::shared_mutex> lk(h->index);
+  if (int32_t rc = check()) return rc;
+  if (b == 0) return VERS_OK;
+  DeviceGuard g(h->device);
+  WsLease lease(h);
+  if (lease.rc) return lease.rc;
+  HostStatusSlot slot(h);
+  HostIo io;
+  if (int32_t rc = host_io_begin(h, queries, q_stride_bytes, b, top_k, io)) return rc;
+  lease.st = W->io_stream;
+  const int32_t rc = body(io);
+  if (rc) (void)hipStreamSynchronize(W->io_stream);
+  return rc;
+}
+
+// A host call's filter onto the device, on the workspace's stream: the bitmaps packed to ceil(n_bits / 64) words each in W->flt_bits -- one
+// bitmap a plain copy, the _multi form a pitched one -- and filter_of beside them in W->flt_of.  An entry of filter_of at or beyond n_filters is
+// refused here, where it can be read.  dev: the filter as the device sees it.
+static int32_t stage_filter(vers_ivf* h, const char* who, const FilterArg& host, uint32_t b, FilterArg& dev) {
+  for (uint32_t q = 0; host.filter_of != nullptr && q < b; ++q)
+    if (host.filter_of[q] >= host.n_filters) return fail(VERS_ERR_INVALID, std::string(who) + ": filter_of[" + std::to_string(q) + "] is not below n_filters");
+  const size_t words = (size_t)((host.n_bits + 63) / 64), bit_bytes = words * sizeof(uint64_t);
+  if (int32_t rc = W->flt_bits.reserve(std::max<size_t>(8, bit_bytes * host.n_filters))) return rc;
+  if (host.filter_of != nullptr)
+    if (int32_t rc = W->flt_of.reserve((size_t)b * sizeof(uint32_t))) return rc;
+  if (bit_bytes && host.filter_of == nullptr && hipMemcpyAsync(W->flt_bits.p, host.filters, bit_bytes, hipMemcpyHostToDevice, W->io_stream) != hipSuccess)
+    return fail(VERS_ERR_HIP, std::string(who) + ": staging the bitmap failed");
+  if (bit_bytes && host.filter_of != nullptr &&
+      hipMemcpy2DAsync(W->flt_bits.p, bit_bytes, host.filters, (size_t)host.stride_words * sizeof(uint64_t), bit_bytes, host.n_filters, hipMemcpyHostToDevice, W->io_stream) != hipSuccess)
+    return fail(VERS_ERR_HIP, std::string(who) + ": staging the bitmaps failed");
+  if (host.filter_of != nullptr && hipMemcpyAsync(W->flt_of.p, host.filter_of, (size_t)b * sizeof(uint32_t), hipMemcpyHostToDevice, W->io_stream) != hipSuccess)
+    return fail(VERS_ERR_HIP, std::string(who) + ": staging filter_of failed");
+  dev = FilterArg{W->flt_bits.as<uint64_t>(), (uint64_t)words, host.n_filters, host.n_bits, host.filter_of != nullptr ? W->flt_of.as<uint32_t>() : (const uint32_t*)nullptr};
+  return VERS_OK;
+}
+
+// A host range call's radii: a NaN among them is refused before the handle is locked ...
+static int32_t radii_check(const char* who, const float* radius, uint32_t b) {
+  for (uint32_t i = 0; i < b; ++i)
+    if (radius[i] != radius[i]) return fail(VERS_ERR_INVALID, std::string(who) + ": NaN radius");
+  return VERS_OK;
+}
+// ... and they go to W->rg_rad on the workspace's stream, with W->rg_lims reserved for the limits
+static int32_t stage_radii(vers_ivf* h, const float* radius, uint32_t b) {
+  if (int32_t rc = W->rg_rad.reserve((size_t)b * sizeof(float))) return rc;
+  if (int32_t rc = W->rg_lims.reserve(((size_t)b + 1) * sizeof(uint64_t))) return rc;
+  VERS_HIP_TRY(hipMemcpyAsync(W->rg_rad.p, radius, (size_t)b * sizeof(float), hipMemcpyHostToDevice, W->io_stream));
+  return VERS_OK;
+}
+
+// a host range call's result out of the workspace (the call has synchronised): the limits and the total always, ids and distances when they fit
+static int32_t range_download(vers_ivf* h, uint32_t b, uint64_t total, uint64_t cap, uint64_t* out_lims, uint64_t* out_ids, float* out_dist, uint64_t* out_total) {
+  VERS_HIP_TRY(hipMemcpy(out_lims, W->rg_lims.p, ((size_t)b + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost));
+  *out_total = total;
+  if (total == 0 || total > cap) return VERS_OK;
+  VERS_HIP_TRY(hipMemcpy(out_ids, W->o_ids.p, (size_t)total * sizeof(uint64_t), hipMemcpyDeviceToHost));
+  VERS_HIP_TRY(hipMemcpy(out_dist, W->o_dist.p, (size_t)total * sizeof(float), hipMemcpyDeviceToHost));
   return VERS_OK;
 }
 
@@ -1794,251 +1854,138 @@ int32_t vers_ivf_search_exhaustive(vers_ivf_t* h, const float* queries, uint64_t
   return rc == kRetrySpill ? VERS_ERR_INVALID : rc;
 }
 
-// ---- filtered top-k search (filter.hip.h) ----
-// (ad: the adaptive call's arguments, nprobe then being nprobe_max)
-static int32_t filtered_dev_common(vers_ivf_t* h, const char* who, const float* queries_dev, uint64_t ldq_floats, uint32_t b, uint32_t top_k, uint32_t nprobe,
-                                   const uint64_t* allowed_bits_dev, uint64_t n_bits, uint64_t* out_ids_dev, float* out_dist_dev, uint32_t* out_count_dev,
-                                   void* stream, const AdaptiveArgs* ad = nullptr) {
+// ---- filtered top-k search (filter.hip.h, filter_multi.hip.h, filter_adaptive.hip.h) ----
+// The device-pointer calls: the probed lists or (probed = false) every stored row under the metric given in place of nprobe; one bitmap or the
+// _multi form (form); ad: the adaptive call's arguments, nprobe then being nprobe_max.
+static int32_t filtered_dev_common(vers_ivf_t* h, const char* who, bool probed, FilterForm form, const float* queries_dev, uint64_t ldq_floats, uint32_t b, uint32_t top_k,
+                                   uint32_t nprobe_or_metric, const FilterArg& flt, uint64_t* out_ids_dev, float* out_dist_dev, uint32_t* out_count_dev, void* stream,
+                                   const AdaptiveSpec& ad = {}) {
   if (!h) return fail(VERS_ERR_INVALID, "null handle");
+  if (!probed && nprobe_or_metric > VERS_METRIC_COSDIST) return fail(VERS_ERR_INVALID, "unknown metric");
   if (b && (!queries_dev || ldq_floats < h->d || !out_count_dev || (top_k && (!out_ids_dev || !out_dist_dev))))
     return fail(VERS_ERR_INVALID, std::string(who) + ": bad arguments");
-  if (int32_t rc = adaptive_check(who, ad, nprobe)) return rc;
-  std::shared_lock<std::shared_mutex> lk(h->index);
-  if (int32_t rc = filter_check(h, who, true, nprobe, allowed_bits_dev, n_bits)) return rc;
-  if (b == 0) return VERS_OK;
-  DeviceGuard g(h->device);
-  WsLease lease(h, true, (hipStream_t)stream);
-  if (lease.rc) return lease.rc;
-  if (int32_t rc = lease.order_on((hipStream_t)stream)) return rc;
-  const AdaptiveSpec as{ad ? ad->nprobe_min : 0u, ad ? ad->min_allowed : 0u, ad ? ad->out_nprobe : (uint32_t*)nullptr};
-  return filtered_dev_locked(h, queries_dev, ldq_floats, b, top_k, nprobe, allowed_bits_dev, n_bits, out_ids_dev, out_dist_dev, out_count_dev, (hipStream_t)stream,
-                             nullptr, ad ? &as : nullptr);
+  if (int32_t rc = adaptive_check(who, ad, nprobe_or_metric, AdaptiveKind::kCall)) return rc;
+  return dev_call(
+      h, b, false, stream, [&]() -> int32_t { return filtered_check(h, who, FilterCheck{probed, false, form, kUseShardedTopk}, nprobe_or_metric, 0, b, flt); },
+      [&](hipStream_t st) -> int32_t {
+        return filtered_topk_locked(h, probed, queries_dev, ldq_floats, b, top_k, nprobe_or_metric, flt, ad, out_ids_dev, out_dist_dev, out_count_dev, st);
+      });
+}
+
+// The host-pointer calls: the filter through the workspace (stage_filter), one synchronisation.  ad.out_nprobe is the caller's host array.
+static int32_t filtered_host_common(vers_ivf_t* h, const char* who, bool probed, FilterForm form, const float* queries, uint64_t q_stride_bytes, uint32_t b, uint32_t top_k,
+                                    uint32_t nprobe_or_metric, const FilterArg& flt, uint64_t* out_ids, float* out_dist, uint32_t* out_count, const AdaptiveSpec& ad = {}) {
+  if (!h) return fail(VERS_ERR_INVALID, "null handle");
+  if (!probed && nprobe_or_metric > VERS_METRIC_COSDIST) return fail(VERS_ERR_INVALID, "unknown metric");
+  if (b && (!queries || q_stride_bytes < (uint64_t)h->d * 4 || q_stride_bytes % 4 || !out_count || (top_k && (!out_ids || !out_dist))))
+    return fail(VERS_ERR_INVALID, std::string(who) + ": bad arguments");
+  if (int32_t rc = adaptive_check(who, ad, nprobe_or_metric, AdaptiveKind::kCall)) return rc;
+  return host_call(
+      h, queries, q_stride_bytes, b, top_k,
+      [&]() -> int32_t { return filtered_check(h, who, FilterCheck{probed, false, form, kUseShardedTopk}, nprobe_or_metric, 0, b, flt); },
+      [&](const HostIo& io) -> int32_t {
+        FilterArg flt_dev;
+        if (int32_t rc = stage_filter(h, who, flt, b, flt_dev)) return rc;
+        if (hipMemsetAsync(W->io_out.p, 0, io.out_bytes, W->io_stream) != hipSuccess) return fail(VERS_ERR_HIP, std::string(who) + ": hipMemsetAsync failed");  // entries past a query's count come back as zeros
+        AdaptiveSpec ad_dev = ad;
+        const bool want_np = ad.on && ad.out_nprobe;
+        if (want_np) {
+          if (int32_t rc = W->flt_np.reserve((size_t)b * sizeof(uint32_t))) return rc;
+          ad_dev.out_nprobe = W->flt_np.as<uint32_t>();
+        }
+        if (int32_t rc = filtered_topk_locked(h, probed, io.q_dev, h->d, b, top_k, nprobe_or_metric, flt_dev, ad_dev, io.ids_dev, io.dist_dev, io.cnt_dev, W->io_stream)) return rc;
+        const int32_t rc = host_io_end(h, io, b, top_k, out_ids, out_dist, out_count);
+        if (!rc && want_np) VERS_HIP_TRY(hipMemcpy(ad.out_nprobe, W->flt_np.p, (size_t)b * sizeof(uint32_t), hipMemcpyDeviceToHost));  // (the stream has been waited for)
+        return rc == kRetrySpill ? VERS_ERR_INVALID : rc;
+      });
 }
 
 int32_t vers_ivf_search_filtered_dev(vers_ivf_t* h, const float* queries_dev, uint64_t ldq_floats, uint32_t b, uint32_t top_k, uint32_t nprobe,
                                      const uint64_t* allowed_bits_dev, uint64_t n_bits, uint64_t* out_ids_dev, float* out_dist_dev, uint32_t* out_count_dev,
                                      void* stream) {
-  return filtered_dev_common(h, "vers_ivf_search_filtered_dev", queries_dev, ldq_floats, b, top_k, nprobe, allowed_bits_dev, n_bits, out_ids_dev, out_dist_dev,
-                             out_count_dev, stream);
+  return filtered_dev_common(h, "vers_ivf_search_filtered_dev", true, FilterForm::kPerCall, queries_dev, ldq_floats, b, top_k, nprobe, per_call_filter(allowed_bits_dev, n_bits),
+                             out_ids_dev, out_dist_dev, out_count_dev, stream);
 }
 
 int32_t vers_ivf_search_filtered_adaptive_dev(vers_ivf_t* h, const float* queries_dev, uint64_t ldq_floats, uint32_t b, uint32_t top_k, uint32_t nprobe_min,
                                               uint32_t nprobe_max, uint32_t min_allowed, const uint64_t* allowed_bits_dev, uint64_t n_bits, uint64_t* out_ids_dev,
                                               float* out_dist_dev, uint32_t* out_count_dev, uint32_t* out_nprobe_dev, void* stream) {
-  const AdaptiveArgs ad{nprobe_min, min_allowed, out_nprobe_dev};
-  return filtered_dev_common(h, "vers_ivf_search_filtered_adaptive_dev", queries_dev, ldq_floats, b, top_k, nprobe_max, allowed_bits_dev, n_bits, out_ids_dev,
-                             out_dist_dev, out_count_dev, stream, &ad);
+  return filtered_dev_common(h, "vers_ivf_search_filtered_adaptive_dev", true, FilterForm::kPerCall, queries_dev, ldq_floats, b, top_k, nprobe_max,
+                             per_call_filter(allowed_bits_dev, n_bits), out_ids_dev, out_dist_dev, out_count_dev, stream, adaptive_spec(nprobe_min, min_allowed, out_nprobe_dev));
 }
 
 int32_t vers_ivf_search_exhaustive_filtered_dev(vers_ivf_t* h, const float* queries_dev, uint64_t ldq_floats, uint32_t b, uint32_t top_k, uint32_t metric,
                                                 const uint64_t* allowed_bits_dev, uint64_t n_bits, uint64_t* out_ids_dev, float* out_dist_dev,
                                                 uint32_t* out_count_dev, void* stream) {
-  if (!h) return fail(VERS_ERR_INVALID, "null handle");
-  if (metric > VERS_METRIC_COSDIST) return fail(VERS_ERR_INVALID, "unknown metric");
-  if (b && (!queries_dev || ldq_floats < h->d || !out_count_dev || (top_k && (!out_ids_dev || !out_dist_dev))))
-    return fail(VERS_ERR_INVALID, "vers_ivf_search_exhaustive_filtered_dev: bad arguments");
-  std::shared_lock<std::shared_mutex> lk(h->index);
-  if (int32_t rc = filter_check(h, "vers_ivf_search_exhaustive_filtered_dev", false, 1, allowed_bits_dev, n_bits)) return rc;
-  if (b == 0) return VERS_OK;
-  DeviceGuard g(h->device);
-  WsLease lease(h, true, (hipStream_t)stream);
-  if (lease.rc) return lease.rc;
-  if (int32_t rc = lease.order_on((hipStream_t)stream)) return rc;
-  return exhaustive_filtered_dev_locked(h, queries_dev, ldq_floats, b, top_k, metric, allowed_bits_dev, n_bits, out_ids_dev, out_dist_dev, out_count_dev,
-                                        (hipStream_t)stream);
-}
-
-// host-pointer calls: queries through the pinned staging of every host-pointer call, the bitmap through the workspace, one synchronisation
-static int32_t filtered_host_common(vers_ivf_t* h, const char* who, const float* queries, uint64_t q_stride_bytes, uint32_t b, uint32_t top_k, bool probed,
-                                    uint32_t nprobe_or_metric, const uint64_t* allowed_bits, uint64_t n_bits, uint64_t* out_ids, float* out_dist, uint32_t* out_count,
-                                    const AdaptiveArgs* ad = nullptr) {
-  if (!h) return fail(VERS_ERR_INVALID, "null handle");
-  if (!probed && nprobe_or_metric > VERS_METRIC_COSDIST) return fail(VERS_ERR_INVALID, "unknown metric");
-  if (b && (!queries || q_stride_bytes < (uint64_t)h->d * 4 || q_stride_bytes % 4 || !out_count || (top_k && (!out_ids || !out_dist))))
-    return fail(VERS_ERR_INVALID, std::string(who) + ": bad arguments");
-  if (int32_t rc = adaptive_check(who, ad, nprobe_or_metric)) return rc;
-  std::shared_lock<std::shared_mutex> lk(h->index);
-  if (int32_t rc = filter_check(h, who, probed, probed ? nprobe_or_metric : 1u, allowed_bits, n_bits)) return rc;
-  if (b == 0) return VERS_OK;
-  DeviceGuard g(h->device);
-  WsLease lease(h);
-  if (lease.rc) return lease.rc;
-  HostStatusSlot slot(h);
-  HostIo io;
-  if (int32_t rc = host_io_begin(h, queries, q_stride_bytes, b, top_k, io)) return rc;
-  lease.st = W->io_stream;
-  const size_t bit_bytes = (size_t)((n_bits + 63) / 64) * sizeof(uint64_t);
-  int32_t rc = W->flt_bits.reserve(std::max<size_t>(8, bit_bytes));
-  if (!rc && bit_bytes && hipMemcpyAsync(W->flt_bits.p, allowed_bits, bit_bytes, hipMemcpyHostToDevice, W->io_stream) != hipSuccess)
-    rc = fail(VERS_ERR_HIP, std::string(who) + ": staging the bitmap failed");
-  if (!rc && hipMemsetAsync(W->io_out.p, 0, io.out_bytes, W->io_stream) != hipSuccess) rc = fail(VERS_ERR_HIP, std::string(who) + ": hipMemsetAsync failed");  // entries past a query's count come back as zeros
-  const bool want_np = ad && ad->out_nprobe;
-  if (!rc && want_np) rc = W->flt_np.reserve((size_t)b * sizeof(uint32_t));
-  const AdaptiveSpec as{ad ? ad->nprobe_min : 0u, ad ? ad->min_allowed : 0u, want_np ? W->flt_np.as<uint32_t>() : (uint32_t*)nullptr};
-  if (!rc)
-    rc = probed ? filtered_dev_locked(h, io.q_dev, h->d, b, top_k, nprobe_or_metric, W->flt_bits.as<uint64_t>(), n_bits, io.ids_dev, io.dist_dev, io.cnt_dev, W->io_stream,
-                                      nullptr, ad ? &as : nullptr)
-                : exhaustive_filtered_dev_locked(h, io.q_dev, h->d, b, top_k, nprobe_or_metric, W->flt_bits.as<uint64_t>(), n_bits, io.ids_dev, io.dist_dev, io.cnt_dev,
-                                                 W->io_stream);
-  if (rc) {  // (the caller's bitmap may still be read by the staging copy)
-    (void)hipStreamSynchronize(W->io_stream);
-    return rc;
-  }
-  rc = host_io_end(h, io, b, top_k, out_ids, out_dist, out_count);
-  if (!rc && want_np) VERS_HIP_TRY(hipMemcpy(ad->out_nprobe, W->flt_np.p, (size_t)b * sizeof(uint32_t), hipMemcpyDeviceToHost));  // (the stream has been waited for)
-  return rc == kRetrySpill ? VERS_ERR_INVALID : rc;
+  return filtered_dev_common(h, "vers_ivf_search_exhaustive_filtered_dev", false, FilterForm::kPerCall, queries_dev, ldq_floats, b, top_k, metric,
+                             per_call_filter(allowed_bits_dev, n_bits), out_ids_dev, out_dist_dev, out_count_dev, stream);
 }
 
 int32_t vers_ivf_search_filtered(vers_ivf_t* h, const float* queries, uint64_t q_stride_bytes, uint32_t b, uint32_t top_k, uint32_t nprobe,
                                  const uint64_t* allowed_bits, uint64_t n_bits, uint64_t* out_ids, float* out_dist, uint32_t* out_count) {
-  return filtered_host_common(h, "vers_ivf_search_filtered", queries, q_stride_bytes, b, top_k, true, nprobe, allowed_bits, n_bits, out_ids, out_dist, out_count);
+  return filtered_host_common(h, "vers_ivf_search_filtered", true, FilterForm::kPerCall, queries, q_stride_bytes, b, top_k, nprobe, per_call_filter(allowed_bits, n_bits), out_ids,
+                              out_dist, out_count);
 }
 
 int32_t vers_ivf_search_filtered_adaptive(vers_ivf_t* h, const float* queries, uint64_t q_stride_bytes, uint32_t b, uint32_t top_k, uint32_t nprobe_min,
                                           uint32_t nprobe_max, uint32_t min_allowed, const uint64_t* allowed_bits, uint64_t n_bits, uint64_t* out_ids, float* out_dist,
                                           uint32_t* out_count, uint32_t* out_nprobe) {
-  const AdaptiveArgs ad{nprobe_min, min_allowed, out_nprobe};
-  return filtered_host_common(h, "vers_ivf_search_filtered_adaptive", queries, q_stride_bytes, b, top_k, true, nprobe_max, allowed_bits, n_bits, out_ids, out_dist,
-                              out_count, &ad);
+  return filtered_host_common(h, "vers_ivf_search_filtered_adaptive", true, FilterForm::kPerCall, queries, q_stride_bytes, b, top_k, nprobe_max,
+                              per_call_filter(allowed_bits, n_bits), out_ids, out_dist, out_count, adaptive_spec(nprobe_min, min_allowed, out_nprobe));
 }
 
 int32_t vers_ivf_search_exhaustive_filtered(vers_ivf_t* h, const float* queries, uint64_t q_stride_bytes, uint32_t b, uint32_t top_k, uint32_t metric,
                                             const uint64_t* allowed_bits, uint64_t n_bits, uint64_t* out_ids, float* out_dist, uint32_t* out_count) {
-  return filtered_host_common(h, "vers_ivf_search_exhaustive_filtered", queries, q_stride_bytes, b, top_k, false, metric, allowed_bits, n_bits, out_ids, out_dist,
-                              out_count);
+  return filtered_host_common(h, "vers_ivf_search_exhaustive_filtered", false, FilterForm::kPerCall, queries, q_stride_bytes, b, top_k, metric,
+                              per_call_filter(allowed_bits, n_bits), out_ids, out_dist, out_count);
 }
 
-// ---- filtered top-k search with a filter per query (filter_multi.hip.h) ----
-// what the four entry points refuse before they touch the device: their own arguments, then the per-call checks
-static int32_t filter_multi_check(vers_ivf* h, const char* who, bool probed, uint32_t nprobe, uint32_t b, const uint64_t* filters, uint64_t stride_words,
-                                  uint32_t n_filters, uint64_t n_bits, const uint32_t* filter_of) {
-  if (b != 0 && n_filters == 0) return fail(VERS_ERR_INVALID, std::string(who) + ": n_filters == 0");
-  if (n_filters > VERS_FILTER_MAX)
-    return fail(VERS_ERR_INVALID, std::string(who) + ": more than VERS_FILTER_MAX bitmaps in one call; split the batch by allowed set");
-  if (b != 0 && filter_of == nullptr) return fail(VERS_ERR_INVALID, std::string(who) + ": NULL filter_of");
-  if (n_bits != 0 && stride_words < (n_bits + 63) / 64) return fail(VERS_ERR_INVALID, std::string(who) + ": filter_stride_words is smaller than ceil(n_bits / 64)");
-  return filter_check(h, who, probed, nprobe, filters, n_bits);
-}
-
-static int32_t filtered_multi_dev_common(vers_ivf_t* h, const char* who, bool probed, const float* queries_dev, uint64_t ldq_floats, uint32_t b, uint32_t top_k,
-                                         uint32_t nprobe_or_metric, const uint64_t* filters_dev, uint64_t stride_words, uint32_t n_filters, uint64_t n_bits,
-                                         const uint32_t* filter_of_dev, uint64_t* out_ids_dev, float* out_dist_dev, uint32_t* out_count_dev, void* stream,
-                                         const AdaptiveArgs* ad = nullptr) {
-  if (!h) return fail(VERS_ERR_INVALID, "null handle");
-  if (!probed && nprobe_or_metric > VERS_METRIC_COSDIST) return fail(VERS_ERR_INVALID, "unknown metric");
-  if (b && (!queries_dev || ldq_floats < h->d || !out_count_dev || (top_k && (!out_ids_dev || !out_dist_dev))))
-    return fail(VERS_ERR_INVALID, std::string(who) + ": bad arguments");
-  if (int32_t rc = adaptive_check(who, ad, nprobe_or_metric)) return rc;
-  std::shared_lock<std::shared_mutex> lk(h->index);
-  if (int32_t rc = filter_multi_check(h, who, probed, probed ? nprobe_or_metric : 1u, b, filters_dev, stride_words, n_filters, n_bits, filter_of_dev)) return rc;
-  if (b == 0) return VERS_OK;
-  DeviceGuard g(h->device);
-  WsLease lease(h, true, (hipStream_t)stream);
-  if (lease.rc) return lease.rc;
-  if (int32_t rc = lease.order_on((hipStream_t)stream)) return rc;
-  const FilterMultiSpec ms{stride_words, n_filters, filter_of_dev};
-  const AdaptiveSpec as{ad ? ad->nprobe_min : 0u, ad ? ad->min_allowed : 0u, ad ? ad->out_nprobe : (uint32_t*)nullptr};
-  return probed ? filtered_dev_locked(h, queries_dev, ldq_floats, b, top_k, nprobe_or_metric, filters_dev, n_bits, out_ids_dev, out_dist_dev, out_count_dev,
-                                      (hipStream_t)stream, &ms, ad ? &as : nullptr)
-                : exhaustive_filtered_dev_locked(h, queries_dev, ldq_floats, b, top_k, nprobe_or_metric, filters_dev, n_bits, out_ids_dev, out_dist_dev, out_count_dev,
-                                                 (hipStream_t)stream, &ms);
-}
-
+// ---- with a filter per query: the same two paths, the filter in the _multi form ----
 int32_t vers_ivf_search_filtered_multi_dev(vers_ivf_t* h, const float* queries_dev, uint64_t ldq_floats, uint32_t b, uint32_t top_k, uint32_t nprobe,
                                            const uint64_t* filters_dev, uint64_t filter_stride_words, uint32_t n_filters, uint64_t n_bits,
                                            const uint32_t* filter_of_dev, uint64_t* out_ids_dev, float* out_dist_dev, uint32_t* out_count_dev, void* stream) {
-  return filtered_multi_dev_common(h, "vers_ivf_search_filtered_multi_dev", true, queries_dev, ldq_floats, b, top_k, nprobe, filters_dev, filter_stride_words, n_filters,
-                                   n_bits, filter_of_dev, out_ids_dev, out_dist_dev, out_count_dev, stream);
+  return filtered_dev_common(h, "vers_ivf_search_filtered_multi_dev", true, FilterForm::kMulti, queries_dev, ldq_floats, b, top_k, nprobe,
+                             FilterArg{filters_dev, filter_stride_words, n_filters, n_bits, filter_of_dev}, out_ids_dev, out_dist_dev, out_count_dev, stream);
 }
 
 int32_t vers_ivf_search_filtered_multi_adaptive_dev(vers_ivf_t* h, const float* queries_dev, uint64_t ldq_floats, uint32_t b, uint32_t top_k, uint32_t nprobe_min,
                                                     uint32_t nprobe_max, uint32_t min_allowed, const uint64_t* filters_dev, uint64_t filter_stride_words,
                                                     uint32_t n_filters, uint64_t n_bits, const uint32_t* filter_of_dev, uint64_t* out_ids_dev, float* out_dist_dev,
                                                     uint32_t* out_count_dev, uint32_t* out_nprobe_dev, void* stream) {
-  const AdaptiveArgs ad{nprobe_min, min_allowed, out_nprobe_dev};
-  return filtered_multi_dev_common(h, "vers_ivf_search_filtered_multi_adaptive_dev", true, queries_dev, ldq_floats, b, top_k, nprobe_max, filters_dev,
-                                   filter_stride_words, n_filters, n_bits, filter_of_dev, out_ids_dev, out_dist_dev, out_count_dev, stream, &ad);
+  return filtered_dev_common(h, "vers_ivf_search_filtered_multi_adaptive_dev", true, FilterForm::kMulti, queries_dev, ldq_floats, b, top_k, nprobe_max,
+                             FilterArg{filters_dev, filter_stride_words, n_filters, n_bits, filter_of_dev}, out_ids_dev, out_dist_dev, out_count_dev, stream,
+                             adaptive_spec(nprobe_min, min_allowed, out_nprobe_dev));
 }
 
 int32_t vers_ivf_search_exhaustive_filtered_multi_dev(vers_ivf_t* h, const float* queries_dev, uint64_t ldq_floats, uint32_t b, uint32_t top_k, uint32_t metric,
                                                       const uint64_t* filters_dev, uint64_t filter_stride_words, uint32_t n_filters, uint64_t n_bits,
                                                       const uint32_t* filter_of_dev, uint64_t* out_ids_dev, float* out_dist_dev, uint32_t* out_count_dev,
                                                       void* stream) {
-  return filtered_multi_dev_common(h, "vers_ivf_search_exhaustive_filtered_multi_dev", false, queries_dev, ldq_floats, b, top_k, metric, filters_dev,
-                                   filter_stride_words, n_filters, n_bits, filter_of_dev, out_ids_dev, out_dist_dev, out_count_dev, stream);
-}
-
-// host-pointer calls: filtered_host_common's staging, with the bitmaps packed to ceil(n_bits / 64) words each and filter_of beside them.  An
-// entry of filter_of at or beyond n_filters is refused here, where it can be read.
-static int32_t filtered_multi_host_common(vers_ivf_t* h, const char* who, const float* queries, uint64_t q_stride_bytes, uint32_t b, uint32_t top_k, bool probed,
-                                          uint32_t nprobe_or_metric, const uint64_t* filters, uint64_t stride_words, uint32_t n_filters, uint64_t n_bits,
-                                          const uint32_t* filter_of, uint64_t* out_ids, float* out_dist, uint32_t* out_count, const AdaptiveArgs* ad = nullptr) {
-  if (!h) return fail(VERS_ERR_INVALID, "null handle");
-  if (!probed && nprobe_or_metric > VERS_METRIC_COSDIST) return fail(VERS_ERR_INVALID, "unknown metric");
-  if (b && (!queries || q_stride_bytes < (uint64_t)h->d * 4 || q_stride_bytes % 4 || !out_count || (top_k && (!out_ids || !out_dist))))
-    return fail(VERS_ERR_INVALID, std::string(who) + ": bad arguments");
-  if (int32_t rc = adaptive_check(who, ad, nprobe_or_metric)) return rc;
-  std::shared_lock<std::shared_mutex> lk(h->index);
-  if (int32_t rc = filter_multi_check(h, who, probed, probed ? nprobe_or_metric : 1u, b, filters, stride_words, n_filters, n_bits, filter_of)) return rc;
-  for (uint32_t q = 0; q < b; ++q)
-    if (filter_of[q] >= n_filters) return fail(VERS_ERR_INVALID, std::string(who) + ": filter_of[" + std::to_string(q) + "] is not below n_filters");
-  if (b == 0) return VERS_OK;
-  DeviceGuard g(h->device);
-  WsLease lease(h);
-  if (lease.rc) return lease.rc;
-  HostStatusSlot slot(h);
-  HostIo io;
-  if (int32_t rc = host_io_begin(h, queries, q_stride_bytes, b, top_k, io)) return rc;
-  lease.st = W->io_stream;
-  const size_t words = (size_t)((n_bits + 63) / 64), bit_bytes = words * sizeof(uint64_t);
-  int32_t rc = W->flt_bits.reserve(std::max<size_t>(8, bit_bytes * n_filters));
-  if (!rc) rc = W->flt_of.reserve((size_t)b * sizeof(uint32_t));
-  if (!rc && bit_bytes &&
-      hipMemcpy2DAsync(W->flt_bits.p, bit_bytes, filters, (size_t)stride_words * sizeof(uint64_t), bit_bytes, n_filters, hipMemcpyHostToDevice, W->io_stream) != hipSuccess)
-    rc = fail(VERS_ERR_HIP, std::string(who) + ": staging the bitmaps failed");
-  if (!rc && hipMemcpyAsync(W->flt_of.p, filter_of, (size_t)b * sizeof(uint32_t), hipMemcpyHostToDevice, W->io_stream) != hipSuccess)
-    rc = fail(VERS_ERR_HIP, std::string(who) + ": staging filter_of failed");
-  if (!rc && hipMemsetAsync(W->io_out.p, 0, io.out_bytes, W->io_stream) != hipSuccess) rc = fail(VERS_ERR_HIP, std::string(who) + ": hipMemsetAsync failed");  // entries past a query's count come back as zeros
-  const bool want_np = ad && ad->out_nprobe;
-  if (!rc && want_np) rc = W->flt_np.reserve((size_t)b * sizeof(uint32_t));
-  if (!rc) {
-    const FilterMultiSpec ms{(uint64_t)words, n_filters, W->flt_of.as<uint32_t>()};
-    const AdaptiveSpec as{ad ? ad->nprobe_min : 0u, ad ? ad->min_allowed : 0u, want_np ? W->flt_np.as<uint32_t>() : (uint32_t*)nullptr};
-    rc = probed ? filtered_dev_locked(h, io.q_dev, h->d, b, top_k, nprobe_or_metric, W->flt_bits.as<uint64_t>(), n_bits, io.ids_dev, io.dist_dev, io.cnt_dev, W->io_stream, &ms,
-                                      ad ? &as : nullptr)
-                : exhaustive_filtered_dev_locked(h, io.q_dev, h->d, b, top_k, nprobe_or_metric, W->flt_bits.as<uint64_t>(), n_bits, io.ids_dev, io.dist_dev, io.cnt_dev,
-                                                 W->io_stream, &ms);
-  }
-  if (rc) {  // (the caller's bitmaps may still be read by the staging copies)
-    (void)hipStreamSynchronize(W->io_stream);
-    return rc;
-  }
-  rc = host_io_end(h, io, b, top_k, out_ids, out_dist, out_count);
-  if (!rc && want_np) VERS_HIP_TRY(hipMemcpy(ad->out_nprobe, W->flt_np.p, (size_t)b * sizeof(uint32_t), hipMemcpyDeviceToHost));  // (the stream has been waited for)
-  return rc == kRetrySpill ? VERS_ERR_INVALID : rc;
+  return filtered_dev_common(h, "vers_ivf_search_exhaustive_filtered_multi_dev", false, FilterForm::kMulti, queries_dev, ldq_floats, b, top_k, metric,
+                             FilterArg{filters_dev, filter_stride_words, n_filters, n_bits, filter_of_dev}, out_ids_dev, out_dist_dev, out_count_dev, stream);
 }
 
 int32_t vers_ivf_search_filtered_multi(vers_ivf_t* h, const float* queries, uint64_t q_stride_bytes, uint32_t b, uint32_t top_k, uint32_t nprobe,
                                        const uint64_t* filters, uint64_t filter_stride_words, uint32_t n_filters, uint64_t n_bits, const uint32_t* filter_of,
                                        uint64_t* out_ids, float* out_dist, uint32_t* out_count) {
-  return filtered_multi_host_common(h, "vers_ivf_search_filtered_multi", queries, q_stride_bytes, b, top_k, true, nprobe, filters, filter_stride_words, n_filters, n_bits,
-                                    filter_of, out_ids, out_dist, out_count);
+  return filtered_host_common(h, "vers_ivf_search_filtered_multi", true, FilterForm::kMulti, queries, q_stride_bytes, b, top_k, nprobe,
+                              FilterArg{filters, filter_stride_words, n_filters, n_bits, filter_of}, out_ids, out_dist, out_count);
 }
 
 int32_t vers_ivf_search_filtered_multi_adaptive(vers_ivf_t* h, const float* queries, uint64_t q_stride_bytes, uint32_t b, uint32_t top_k, uint32_t nprobe_min,
                                                 uint32_t nprobe_max, uint32_t min_allowed, const uint64_t* filters, uint64_t filter_stride_words, uint32_t n_filters,
                                                 uint64_t n_bits, const uint32_t* filter_of, uint64_t* out_ids, float* out_dist, uint32_t* out_count,
                                                 uint32_t* out_nprobe) {
-  const AdaptiveArgs ad{nprobe_min, min_allowed, out_nprobe};
-  return filtered_multi_host_common(h, "vers_ivf_search_filtered_multi_adaptive", queries, q_stride_bytes, b, top_k, true, nprobe_max, filters, filter_stride_words,
-                                    n_filters, n_bits, filter_of, out_ids, out_dist, out_count, &ad);
+  return filtered_host_common(h, "vers_ivf_search_filtered_multi_adaptive", true, FilterForm::kMulti, queries, q_stride_bytes, b, top_k, nprobe_max,
+                              FilterArg{filters, filter_stride_words, n_filters, n_bits, filter_of}, out_ids, out_dist, out_count,
+                              adaptive_spec(nprobe_min, min_allowed, out_nprobe));
 }
 
 int32_t vers_ivf_search_exhaustive_filtered_multi(vers_ivf_t* h, const float* queries, uint64_t q_stride_bytes, uint32_t b, uint32_t top_k, uint32_t metric,
                                                   const uint64_t* filters, uint64_t filter_stride_words, uint32_t n_filters, uint64_t n_bits,
                                                   const uint32_t* filter_of, uint64_t* out_ids, float* out_dist, uint32_t* out_count) {
-  return filtered_multi_host_common(h, "vers_ivf_search_exhaustive_filtered_multi", queries, q_stride_bytes, b, top_k, false, metric, filters, filter_stride_words,
-                                    n_filters, n_bits, filter_of, out_ids, out_dist, out_count);
+  return filtered_host_common(h, "vers_ivf_search_exhaustive_filtered_multi", false, FilterForm::kMulti, queries, q_stride_bytes, b, top_k, metric,
+                              FilterArg{filters, filter_stride_words, n_filters, n_bits, filter_of}, out_ids, out_dist, out_count);
 }
 
 int32_t vers_ivf_filter_stats(vers_ivf_t* h, uint64_t* out4, uint64_t* out4_total) {
@@ -2077,17 +2024,14 @@ static int32_t range_dev_common(vers_ivf_t* h, const char* who, bool probed, boo
   if (b && (!queries_dev || ldq_floats < h->d || !radius_dev || !out_lims_dev || (cap && (!out_ids_dev || (partial ? !out_keys_dev : !out_dist_dev)))))
     return fail(VERS_ERR_INVALID, std::string(who) + ": bad arguments");
   if (b == 0) return VERS_OK;
-  std::shared_lock<std::shared_mutex> lk(h->index);
-  if (int32_t rc = probed ? range_check(h, who, nprobe_or_metric, flags, partial) : range_exhaustive_check(h, who, flags, partial)) return rc;
-  DeviceGuard g(h->device);
-  WsLease lease(h, true, (hipStream_t)stream);
-  if (lease.rc) return lease.rc;
-  if (int32_t rc = lease.order_on((hipStream_t)stream)) return rc;
-  HostStatusSlot slot(h);
-  RangePartial part;
-  part.keys = out_keys_dev;
-  return range_dev_locked(h, probed, queries_dev, ldq_floats, b, radius_dev, nprobe_or_metric, flags, out_lims_dev, out_ids_dev, out_dist_dev, cap, false, out_total,
-                          (hipStream_t)stream, partial ? &part : nullptr);
+  return dev_call(
+      h, b, true, stream, [&]() -> int32_t { return probed ? range_check(h, who, nprobe_or_metric, flags, partial) : range_exhaustive_check(h, who, flags, partial); },
+      [&](hipStream_t st) -> int32_t {
+        RangePartial part;
+        part.keys = out_keys_dev;
+        return range_dev_locked(h, range_name(probed), probed, queries_dev, ldq_floats, b, radius_dev, nprobe_or_metric, flags, out_lims_dev, out_ids_dev, out_dist_dev, cap, false,
+                                out_total, st, partial ? &part : nullptr);
+      });
 }
 
 int32_t vers_ivf_range_search_dev(vers_ivf_t* h, const float* queries_dev, uint64_t ldq_floats, uint32_t b, const float* radius_dev, uint32_t nprobe,
@@ -2129,8 +2073,7 @@ static int32_t range_host_common(vers_ivf_t* h, const char* who, bool probed, co
   if (b && (!queries || q_stride_bytes < (uint64_t)h->d * 4 || q_stride_bytes % 4 || !radius || !out_lims || (cap && (!out_ids || !out_dist))))
     return fail(VERS_ERR_INVALID, std::string(who) + ": bad arguments");
   if (b == 0) return VERS_OK;
-  for (uint32_t i = 0; i < b; ++i)
-    if (radius[i] != radius[i]) return fail(VERS_ERR_INVALID, std::string(who) + ": NaN radius");
+  if (int32_t rc = radii_check(who, radius, b)) return rc;
   std::shared_lock<std::shared_mutex> lk(h->index);
   if (int32_t rc = probed ? range_check(h, who, nprobe_or_metric, flags) : range_exhaustive_check(h, who, flags)) return rc;
   DeviceGuard g(h->device);
@@ -2140,18 +2083,11 @@ static int32_t range_host_common(vers_ivf_t* h, const char* who, bool probed, co
   HostIo io;
   if (int32_t rc = host_io_begin(h, queries, q_stride_bytes, b, 0, io)) return rc;  // (the pinned query staging of every host-pointer call)
   lease.st = W->io_stream;
-  if (int32_t rc = W->rg_rad.reserve((size_t)b * sizeof(float))) return rc;
-  if (int32_t rc = W->rg_lims.reserve(((size_t)b + 1) * sizeof(uint64_t))) return rc;
-  VERS_HIP_TRY(hipMemcpyAsync(W->rg_rad.p, radius, (size_t)b * sizeof(float), hipMemcpyHostToDevice, W->io_stream));
+  if (int32_t rc = stage_radii(h, radius, b)) return rc;
   uint64_t total = 0;
-  if (int32_t rc = range_dev_locked(h, probed, io.q_dev, h->d, b, W->rg_rad.as<float>(), nprobe_or_metric, flags, W->rg_lims.as<uint64_t>(), nullptr, nullptr, cap, true,
+  if (int32_t rc = range_dev_locked(h, who, probed, io.q_dev, h->d, b, W->rg_rad.as<float>(), nprobe_or_metric, flags, W->rg_lims.as<uint64_t>(), nullptr, nullptr, cap, true,
                                     &total, W->io_stream)) return rc;
-  VERS_HIP_TRY(hipMemcpy(out_lims, W->rg_lims.p, ((size_t)b + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost));
-  *out_total = total;
-  if (total == 0 || total > cap) return VERS_OK;
-  VERS_HIP_TRY(hipMemcpy(out_ids, W->o_ids.p, (size_t)total * sizeof(uint64_t), hipMemcpyDeviceToHost));
-  VERS_HIP_TRY(hipMemcpy(out_dist, W->o_dist.p, (size_t)total * sizeof(float), hipMemcpyDeviceToHost));
-  return VERS_OK;
+  return range_download(h, b, total, cap, out_lims, out_ids, out_dist, out_total);
 }
 
 int32_t vers_ivf_range_search(vers_ivf_t* h, const float* queries, uint64_t q_stride_bytes, uint32_t b, const float* radius, uint32_t nprobe, uint32_t flags,
@@ -2164,46 +2100,34 @@ int32_t vers_ivf_range_search_exhaustive(vers_ivf_t* h, const float* queries, ui
   return range_host_common(h, "vers_ivf_range_search_exhaustive", false, queries, q_stride_bytes, b, radius, metric, flags, out_lims, out_ids, out_dist, cap, out_total);
 }
 
-// ---- filtered range search (filter_range.hip.h): the probed lists or (probed = false) every stored row under the metric given in place of nprobe ----
-static int32_t range_filtered_dev_common(vers_ivf_t* h, const char* who, bool probed, const float* queries_dev, uint64_t ldq_floats, uint32_t b, const float* radius_dev,
-                                         uint32_t nprobe_or_metric, uint32_t flags, const uint64_t* allowed_bits_dev, uint64_t n_bits, uint64_t* out_lims_dev,
-                                         uint64_t* out_ids_dev, float* out_dist_dev, uint64_t cap, uint64_t* out_total, void* stream) {
+// ---- filtered range search (filter_range.hip.h, filter_range_multi.hip.h): the probed lists or (probed = false) every stored row under the metric
+// given in place of nprobe; one bitmap, the _multi form, or (a rank's partial: out_keys_dev in place of out_dist_dev) either ----
+// The device-pointer calls.  who: the entry point; src_who: the name its range source reports under (the host-pointer call's for the whole calls).
+static int32_t range_filtered_dev_common(vers_ivf_t* h, const char* who, const char* src_who, bool probed, FilterForm form, const float* queries_dev, uint64_t ldq_floats,
+                                         uint32_t b, const float* radius_dev, uint32_t nprobe_or_metric, uint32_t flags, const FilterArg& flt, uint64_t* out_lims_dev,
+                                         uint64_t* out_keys_dev, uint64_t* out_ids_dev, float* out_dist_dev, uint64_t cap, uint64_t* out_total, void* stream) {
+  const bool partial = form == FilterForm::kEither;
   if (!h) return fail(VERS_ERR_INVALID, "null handle");
   if (!out_total) return fail(VERS_ERR_INVALID, std::string(who) + ": out_total is required");
   *out_total = 0;
   if (!probed && nprobe_or_metric > VERS_METRIC_COSDIST) return fail(VERS_ERR_INVALID, "unknown metric");
-  if (b && (!queries_dev || ldq_floats < h->d || !radius_dev || !out_lims_dev || (cap && (!out_ids_dev || !out_dist_dev))))
+  if (b && (!queries_dev || ldq_floats < h->d || !radius_dev || !out_lims_dev || (cap && (!out_ids_dev || (partial ? !out_keys_dev : !out_dist_dev)))))
     return fail(VERS_ERR_INVALID, std::string(who) + ": bad arguments");
   if (b == 0) return VERS_OK;
-  std::shared_lock<std::shared_mutex> lk(h->index);
-  if (int32_t rc = range_filter_check(h, who, probed, probed ? nprobe_or_metric : 1u, flags, allowed_bits_dev, n_bits)) return rc;
-  DeviceGuard g(h->device);
-  WsLease lease(h, true, (hipStream_t)stream);
-  if (lease.rc) return lease.rc;
-  if (int32_t rc = lease.order_on((hipStream_t)stream)) return rc;
-  HostStatusSlot slot(h);
-  return range_filtered_dev_locked(h, probed, queries_dev, ldq_floats, b, radius_dev, nprobe_or_metric, flags, allowed_bits_dev, n_bits, out_lims_dev, out_ids_dev,
-                                   out_dist_dev, cap, false, out_total, (hipStream_t)stream);
+  return dev_call(
+      h, b, true, stream,
+      [&]() -> int32_t { return filtered_check(h, who, FilterCheck{probed, true, form, partial ? nullptr : kUseShardedRange}, nprobe_or_metric, flags, b, flt); },
+      [&](hipStream_t st) -> int32_t {
+        RangePartial part;
+        part.keys = out_keys_dev;
+        return range_filtered_dev_locked(h, src_who, probed, queries_dev, ldq_floats, b, radius_dev, nprobe_or_metric, flags, flt, out_lims_dev, out_ids_dev, out_dist_dev, cap,
+                                         false, out_total, st, partial ? &part : nullptr);
+      });
 }
 
-int32_t vers_ivf_range_search_filtered_dev(vers_ivf_t* h, const float* queries_dev, uint64_t ldq_floats, uint32_t b, const float* radius_dev, uint32_t nprobe,
-                                           uint32_t flags, const uint64_t* allowed_bits_dev, uint64_t n_bits, uint64_t* out_lims_dev, uint64_t* out_ids_dev,
-                                           float* out_dist_dev, uint64_t cap, uint64_t* out_total, void* stream) {
-  return range_filtered_dev_common(h, "vers_ivf_range_search_filtered_dev", true, queries_dev, ldq_floats, b, radius_dev, nprobe, flags, allowed_bits_dev, n_bits,
-                                   out_lims_dev, out_ids_dev, out_dist_dev, cap, out_total, stream);
-}
-
-int32_t vers_ivf_range_search_exhaustive_filtered_dev(vers_ivf_t* h, const float* queries_dev, uint64_t ldq_floats, uint32_t b, const float* radius_dev,
-                                                      uint32_t metric, uint32_t flags, const uint64_t* allowed_bits_dev, uint64_t n_bits, uint64_t* out_lims_dev,
-                                                      uint64_t* out_ids_dev, float* out_dist_dev, uint64_t cap, uint64_t* out_total, void* stream) {
-  return range_filtered_dev_common(h, "vers_ivf_range_search_exhaustive_filtered_dev", false, queries_dev, ldq_floats, b, radius_dev, metric, flags, allowed_bits_dev,
-                                   n_bits, out_lims_dev, out_ids_dev, out_dist_dev, cap, out_total, stream);
-}
-
-// host-pointer calls: range_host_common's staging (queries pinned, radii and limits through the workspace) + filtered_host_common's (the bitmap
-// through the workspace)
-static int32_t range_filtered_host_common(vers_ivf_t* h, const char* who, bool probed, const float* queries, uint64_t q_stride_bytes, uint32_t b, const float* radius,
-                                          uint32_t nprobe_or_metric, uint32_t flags, const uint64_t* allowed_bits, uint64_t n_bits, uint64_t* out_lims, uint64_t* out_ids,
+// The host-pointer calls: radii and limits through the workspace (stage_radii), the filter beside them (stage_filter).
+static int32_t range_filtered_host_common(vers_ivf_t* h, const char* who, bool probed, FilterForm form, const float* queries, uint64_t q_stride_bytes, uint32_t b,
+                                          const float* radius, uint32_t nprobe_or_metric, uint32_t flags, const FilterArg& flt, uint64_t* out_lims, uint64_t* out_ids,
                                           float* out_dist, uint64_t cap, uint64_t* out_total) {
   if (!h) return fail(VERS_ERR_INVALID, "null handle");
   if (!out_total) return fail(VERS_ERR_INVALID, std::string(who) + ": out_total is required");
@@ -2212,178 +2136,81 @@ static int32_t range_filtered_host_common(vers_ivf_t* h, const char* who, bool p
   if (b && (!queries || q_stride_bytes < (uint64_t)h->d * 4 || q_stride_bytes % 4 || !radius || !out_lims || (cap && (!out_ids || !out_dist))))
     return fail(VERS_ERR_INVALID, std::string(who) + ": bad arguments");
   if (b == 0) return VERS_OK;
-  for (uint32_t i = 0; i < b; ++i)
-    if (radius[i] != radius[i]) return fail(VERS_ERR_INVALID, std::string(who) + ": NaN radius");
-  std::shared_lock<std::shared_mutex> lk(h->index);
-  if (int32_t rc = range_filter_check(h, who, probed, probed ? nprobe_or_metric : 1u, flags, allowed_bits, n_bits)) return rc;
-  DeviceGuard g(h->device);
-  WsLease lease(h);
-  if (lease.rc) return lease.rc;
-  HostStatusSlot slot(h);
-  HostIo io;
-  if (int32_t rc = host_io_begin(h, queries, q_stride_bytes, b, 0, io)) return rc;  // (the pinned query staging of every host-pointer call)
-  lease.st = W->io_stream;
-  if (int32_t rc = W->rg_rad.reserve((size_t)b * sizeof(float))) return rc;
-  if (int32_t rc = W->rg_lims.reserve(((size_t)b + 1) * sizeof(uint64_t))) return rc;
-  const size_t bit_bytes = (size_t)((n_bits + 63) / 64) * sizeof(uint64_t);
-  if (int32_t rc = W->flt_bits.reserve(std::max<size_t>(8, bit_bytes))) return rc;
-  VERS_HIP_TRY(hipMemcpyAsync(W->rg_rad.p, radius, (size_t)b * sizeof(float), hipMemcpyHostToDevice, W->io_stream));
-  uint64_t total = 0;
-  int32_t rc = VERS_OK;
-  if (bit_bytes && hipMemcpyAsync(W->flt_bits.p, allowed_bits, bit_bytes, hipMemcpyHostToDevice, W->io_stream) != hipSuccess)
-    rc = fail(VERS_ERR_HIP, std::string(who) + ": staging the bitmap failed");
-  if (!rc)
-    rc = range_filtered_dev_locked(h, probed, io.q_dev, h->d, b, W->rg_rad.as<float>(), nprobe_or_metric, flags, W->flt_bits.as<uint64_t>(), n_bits,
-                                   W->rg_lims.as<uint64_t>(), nullptr, nullptr, cap, true, &total, W->io_stream);
-  if (rc) {  // (the caller's bitmap and radii may still be read by the staging copies)
-    (void)hipStreamSynchronize(W->io_stream);
-    return rc;
-  }
-  VERS_HIP_TRY(hipMemcpy(out_lims, W->rg_lims.p, ((size_t)b + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost));
-  *out_total = total;
-  if (total == 0 || total > cap) return VERS_OK;
-  VERS_HIP_TRY(hipMemcpy(out_ids, W->o_ids.p, (size_t)total * sizeof(uint64_t), hipMemcpyDeviceToHost));
-  VERS_HIP_TRY(hipMemcpy(out_dist, W->o_dist.p, (size_t)total * sizeof(float), hipMemcpyDeviceToHost));
-  return VERS_OK;
+  if (int32_t rc = radii_check(who, radius, b)) return rc;
+  return host_call(
+      h, queries, q_stride_bytes, b, 0,
+      [&]() -> int32_t { return filtered_check(h, who, FilterCheck{probed, true, form, kUseShardedRange}, nprobe_or_metric, flags, b, flt); },
+      [&](const HostIo& io) -> int32_t {
+        FilterArg flt_dev;
+        if (int32_t rc = stage_radii(h, radius, b)) return rc;
+        if (int32_t rc = stage_filter(h, who, flt, b, flt_dev)) return rc;
+        uint64_t total = 0;
+        if (int32_t rc = range_filtered_dev_locked(h, who, probed, io.q_dev, h->d, b, W->rg_rad.as<float>(), nprobe_or_metric, flags, flt_dev, W->rg_lims.as<uint64_t>(), nullptr,
+                                                   nullptr, cap, true, &total, W->io_stream)) return rc;
+        return range_download(h, b, total, cap, out_lims, out_ids, out_dist, out_total);
+      });
+}
+
+int32_t vers_ivf_range_search_filtered_dev(vers_ivf_t* h, const float* queries_dev, uint64_t ldq_floats, uint32_t b, const float* radius_dev, uint32_t nprobe,
+                                           uint32_t flags, const uint64_t* allowed_bits_dev, uint64_t n_bits, uint64_t* out_lims_dev, uint64_t* out_ids_dev,
+                                           float* out_dist_dev, uint64_t cap, uint64_t* out_total, void* stream) {
+  return range_filtered_dev_common(h, "vers_ivf_range_search_filtered_dev", "vers_ivf_range_search_filtered", true, FilterForm::kPerCall, queries_dev, ldq_floats, b, radius_dev,
+                                   nprobe, flags, per_call_filter(allowed_bits_dev, n_bits), out_lims_dev, nullptr, out_ids_dev, out_dist_dev, cap, out_total, stream);
+}
+
+int32_t vers_ivf_range_search_exhaustive_filtered_dev(vers_ivf_t* h, const float* queries_dev, uint64_t ldq_floats, uint32_t b, const float* radius_dev,
+                                                      uint32_t metric, uint32_t flags, const uint64_t* allowed_bits_dev, uint64_t n_bits, uint64_t* out_lims_dev,
+                                                      uint64_t* out_ids_dev, float* out_dist_dev, uint64_t cap, uint64_t* out_total, void* stream) {
+  return range_filtered_dev_common(h, "vers_ivf_range_search_exhaustive_filtered_dev", "vers_ivf_range_search_exhaustive_filtered", false, FilterForm::kPerCall, queries_dev,
+                                   ldq_floats, b, radius_dev, metric, flags, per_call_filter(allowed_bits_dev, n_bits), out_lims_dev, nullptr, out_ids_dev, out_dist_dev, cap,
+                                   out_total, stream);
 }
 
 int32_t vers_ivf_range_search_filtered(vers_ivf_t* h, const float* queries, uint64_t q_stride_bytes, uint32_t b, const float* radius, uint32_t nprobe, uint32_t flags,
                                        const uint64_t* allowed_bits, uint64_t n_bits, uint64_t* out_lims, uint64_t* out_ids, float* out_dist, uint64_t cap,
                                        uint64_t* out_total) {
-  return range_filtered_host_common(h, "vers_ivf_range_search_filtered", true, queries, q_stride_bytes, b, radius, nprobe, flags, allowed_bits, n_bits, out_lims, out_ids,
-                                    out_dist, cap, out_total);
+  return range_filtered_host_common(h, "vers_ivf_range_search_filtered", true, FilterForm::kPerCall, queries, q_stride_bytes, b, radius, nprobe, flags,
+                                    per_call_filter(allowed_bits, n_bits), out_lims, out_ids, out_dist, cap, out_total);
 }
 
 int32_t vers_ivf_range_search_exhaustive_filtered(vers_ivf_t* h, const float* queries, uint64_t q_stride_bytes, uint32_t b, const float* radius, uint32_t metric,
                                                   uint32_t flags, const uint64_t* allowed_bits, uint64_t n_bits, uint64_t* out_lims, uint64_t* out_ids, float* out_dist,
                                                   uint64_t cap, uint64_t* out_total) {
-  return range_filtered_host_common(h, "vers_ivf_range_search_exhaustive_filtered", false, queries, q_stride_bytes, b, radius, metric, flags, allowed_bits, n_bits,
-                                    out_lims, out_ids, out_dist, cap, out_total);
-}
-
-// ---- filtered range search with a filter per query (filter_range_multi.hip.h) ----
-// what the four entry points refuse before they touch the device: the _multi calls' own arguments, then the filtered range checks
-static int32_t range_filter_multi_check(vers_ivf* h, const char* who, bool probed, uint32_t nprobe, uint32_t flags, uint32_t b, const uint64_t* filters,
-                                        uint64_t stride_words, uint32_t n_filters, uint64_t n_bits, const uint32_t* filter_of) {
-  if (b != 0 && n_filters == 0) return fail(VERS_ERR_INVALID, std::string(who) + ": n_filters == 0");
-  if (n_filters > VERS_FILTER_MAX)
-    return fail(VERS_ERR_INVALID, std::string(who) + ": more than VERS_FILTER_MAX bitmaps in one call; split the batch by allowed set");
-  if (b != 0 && filter_of == nullptr) return fail(VERS_ERR_INVALID, std::string(who) + ": NULL filter_of");
-  if (n_bits != 0 && stride_words < (n_bits + 63) / 64) return fail(VERS_ERR_INVALID, std::string(who) + ": filter_stride_words is smaller than ceil(n_bits / 64)");
-  return range_filter_check(h, who, probed, nprobe, flags, filters, n_bits);
-}
-
-static int32_t range_filtered_multi_dev_common(vers_ivf_t* h, const char* who, bool probed, const float* queries_dev, uint64_t ldq_floats, uint32_t b,
-                                               const float* radius_dev, uint32_t nprobe_or_metric, uint32_t flags, const uint64_t* filters_dev, uint64_t stride_words,
-                                               uint32_t n_filters, uint64_t n_bits, const uint32_t* filter_of_dev, uint64_t* out_lims_dev, uint64_t* out_ids_dev,
-                                               float* out_dist_dev, uint64_t cap, uint64_t* out_total, void* stream) {
-  if (!h) return fail(VERS_ERR_INVALID, "null handle");
-  if (!out_total) return fail(VERS_ERR_INVALID, std::string(who) + ": out_total is required");
-  *out_total = 0;
-  if (!probed && nprobe_or_metric > VERS_METRIC_COSDIST) return fail(VERS_ERR_INVALID, "unknown metric");
-  if (b && (!queries_dev || ldq_floats < h->d || !radius_dev || !out_lims_dev || (cap && (!out_ids_dev || !out_dist_dev))))
-    return fail(VERS_ERR_INVALID, std::string(who) + ": bad arguments");
-  if (b == 0) return VERS_OK;
-  std::shared_lock<std::shared_mutex> lk(h->index);
-  if (int32_t rc = range_filter_multi_check(h, who, probed, probed ? nprobe_or_metric : 1u, flags, b, filters_dev, stride_words, n_filters, n_bits, filter_of_dev))
-    return rc;
-  DeviceGuard g(h->device);
-  WsLease lease(h, true, (hipStream_t)stream);
-  if (lease.rc) return lease.rc;
-  if (int32_t rc = lease.order_on((hipStream_t)stream)) return rc;
-  HostStatusSlot slot(h);
-  const FilterMultiSpec ms{stride_words, n_filters, filter_of_dev};
-  return range_filtered_multi_dev_locked(h, probed, queries_dev, ldq_floats, b, radius_dev, nprobe_or_metric, flags, filters_dev, n_bits, ms, out_lims_dev, out_ids_dev,
-                                         out_dist_dev, cap, false, out_total, (hipStream_t)stream);
+  return range_filtered_host_common(h, "vers_ivf_range_search_exhaustive_filtered", false, FilterForm::kPerCall, queries, q_stride_bytes, b, radius, metric, flags,
+                                    per_call_filter(allowed_bits, n_bits), out_lims, out_ids, out_dist, cap, out_total);
 }
 
 int32_t vers_ivf_range_search_filtered_multi_dev(vers_ivf_t* h, const float* queries_dev, uint64_t ldq_floats, uint32_t b, const float* radius_dev, uint32_t nprobe,
                                                  uint32_t flags, const uint64_t* filters_dev, uint64_t filter_stride_words, uint32_t n_filters, uint64_t n_bits,
                                                  const uint32_t* filter_of_dev, uint64_t* out_lims_dev, uint64_t* out_ids_dev, float* out_dist_dev, uint64_t cap,
                                                  uint64_t* out_total, void* stream) {
-  return range_filtered_multi_dev_common(h, "vers_ivf_range_search_filtered_multi_dev", true, queries_dev, ldq_floats, b, radius_dev, nprobe, flags, filters_dev,
-                                         filter_stride_words, n_filters, n_bits, filter_of_dev, out_lims_dev, out_ids_dev, out_dist_dev, cap, out_total, stream);
+  return range_filtered_dev_common(h, "vers_ivf_range_search_filtered_multi_dev", "vers_ivf_range_search_filtered_multi", true, FilterForm::kMulti, queries_dev, ldq_floats, b,
+                                   radius_dev, nprobe, flags, FilterArg{filters_dev, filter_stride_words, n_filters, n_bits, filter_of_dev}, out_lims_dev, nullptr, out_ids_dev,
+                                   out_dist_dev, cap, out_total, stream);
 }
 
 int32_t vers_ivf_range_search_exhaustive_filtered_multi_dev(vers_ivf_t* h, const float* queries_dev, uint64_t ldq_floats, uint32_t b, const float* radius_dev,
                                                             uint32_t metric, uint32_t flags, const uint64_t* filters_dev, uint64_t filter_stride_words,
                                                             uint32_t n_filters, uint64_t n_bits, const uint32_t* filter_of_dev, uint64_t* out_lims_dev,
                                                             uint64_t* out_ids_dev, float* out_dist_dev, uint64_t cap, uint64_t* out_total, void* stream) {
-  return range_filtered_multi_dev_common(h, "vers_ivf_range_search_exhaustive_filtered_multi_dev", false, queries_dev, ldq_floats, b, radius_dev, metric, flags,
-                                         filters_dev, filter_stride_words, n_filters, n_bits, filter_of_dev, out_lims_dev, out_ids_dev, out_dist_dev, cap, out_total,
-                                         stream);
-}
-
-// host-pointer calls: range_filtered_host_common's staging (queries pinned, radii and limits through the workspace) + filtered_multi_host_common's
-// (the bitmaps packed to ceil(n_bits / 64) words each and filter_of beside them).  An entry of filter_of at or beyond n_filters is refused here,
-// where it can be read.
-static int32_t range_filtered_multi_host_common(vers_ivf_t* h, const char* who, bool probed, const float* queries, uint64_t q_stride_bytes, uint32_t b,
-                                                const float* radius, uint32_t nprobe_or_metric, uint32_t flags, const uint64_t* filters, uint64_t stride_words,
-                                                uint32_t n_filters, uint64_t n_bits, const uint32_t* filter_of, uint64_t* out_lims, uint64_t* out_ids, float* out_dist,
-                                                uint64_t cap, uint64_t* out_total) {
-  if (!h) return fail(VERS_ERR_INVALID, "null handle");
-  if (!out_total) return fail(VERS_ERR_INVALID, std::string(who) + ": out_total is required");
-  *out_total = 0;
-  if (!probed && nprobe_or_metric > VERS_METRIC_COSDIST) return fail(VERS_ERR_INVALID, "unknown metric");
-  if (b && (!queries || q_stride_bytes < (uint64_t)h->d * 4 || q_stride_bytes % 4 || !radius || !out_lims || (cap && (!out_ids || !out_dist))))
-    return fail(VERS_ERR_INVALID, std::string(who) + ": bad arguments");
-  if (b == 0) return VERS_OK;
-  for (uint32_t i = 0; i < b; ++i)
-    if (radius[i] != radius[i]) return fail(VERS_ERR_INVALID, std::string(who) + ": NaN radius");
-  std::shared_lock<std::shared_mutex> lk(h->index);
-  if (int32_t rc = range_filter_multi_check(h, who, probed, probed ? nprobe_or_metric : 1u, flags, b, filters, stride_words, n_filters, n_bits, filter_of)) return rc;
-  for (uint32_t q = 0; q < b; ++q)
-    if (filter_of[q] >= n_filters) return fail(VERS_ERR_INVALID, std::string(who) + ": filter_of[" + std::to_string(q) + "] is not below n_filters");
-  DeviceGuard g(h->device);
-  WsLease lease(h);
-  if (lease.rc) return lease.rc;
-  HostStatusSlot slot(h);
-  HostIo io;
-  if (int32_t rc = host_io_begin(h, queries, q_stride_bytes, b, 0, io)) return rc;  // (the pinned query staging of every host-pointer call)
-  lease.st = W->io_stream;
-  if (int32_t rc = W->rg_rad.reserve((size_t)b * sizeof(float))) return rc;
-  if (int32_t rc = W->rg_lims.reserve(((size_t)b + 1) * sizeof(uint64_t))) return rc;
-  const size_t words = (size_t)((n_bits + 63) / 64), bit_bytes = words * sizeof(uint64_t);
-  if (int32_t rc = W->flt_bits.reserve(std::max<size_t>(8, bit_bytes * n_filters))) return rc;
-  if (int32_t rc = W->flt_of.reserve((size_t)b * sizeof(uint32_t))) return rc;
-  VERS_HIP_TRY(hipMemcpyAsync(W->rg_rad.p, radius, (size_t)b * sizeof(float), hipMemcpyHostToDevice, W->io_stream));
-  uint64_t total = 0;
-  int32_t rc = VERS_OK;
-  if (bit_bytes &&
-      hipMemcpy2DAsync(W->flt_bits.p, bit_bytes, filters, (size_t)stride_words * sizeof(uint64_t), bit_bytes, n_filters, hipMemcpyHostToDevice, W->io_stream) != hipSuccess)
-    rc = fail(VERS_ERR_HIP, std::string(who) + ": staging the bitmaps failed");
-  if (!rc && hipMemcpyAsync(W->flt_of.p, filter_of, (size_t)b * sizeof(uint32_t), hipMemcpyHostToDevice, W->io_stream) != hipSuccess)
-    rc = fail(VERS_ERR_HIP, std::string(who) + ": staging filter_of failed");
-  if (!rc) {
-    const FilterMultiSpec ms{(uint64_t)words, n_filters, W->flt_of.as<uint32_t>()};
-    rc = range_filtered_multi_dev_locked(h, probed, io.q_dev, h->d, b, W->rg_rad.as<float>(), nprobe_or_metric, flags, W->flt_bits.as<uint64_t>(), n_bits, ms,
-                                         W->rg_lims.as<uint64_t>(), nullptr, nullptr, cap, true, &total, W->io_stream);
-  }
-  if (rc) {  // (the caller's bitmaps, filter_of and radii may still be read by the staging copies)
-    (void)hipStreamSynchronize(W->io_stream);
-    return rc;
-  }
-  VERS_HIP_TRY(hipMemcpy(out_lims, W->rg_lims.p, ((size_t)b + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost));
-  *out_total = total;
-  if (total == 0 || total > cap) return VERS_OK;
-  VERS_HIP_TRY(hipMemcpy(out_ids, W->o_ids.p, (size_t)total * sizeof(uint64_t), hipMemcpyDeviceToHost));
-  VERS_HIP_TRY(hipMemcpy(out_dist, W->o_dist.p, (size_t)total * sizeof(float), hipMemcpyDeviceToHost));
-  return VERS_OK;
+  return range_filtered_dev_common(h, "vers_ivf_range_search_exhaustive_filtered_multi_dev", "vers_ivf_range_search_exhaustive_filtered_multi", false, FilterForm::kMulti,
+                                   queries_dev, ldq_floats, b, radius_dev, metric, flags, FilterArg{filters_dev, filter_stride_words, n_filters, n_bits, filter_of_dev},
+                                   out_lims_dev, nullptr, out_ids_dev, out_dist_dev, cap, out_total, stream);
 }
 
 int32_t vers_ivf_range_search_filtered_multi(vers_ivf_t* h, const float* queries, uint64_t q_stride_bytes, uint32_t b, const float* radius, uint32_t nprobe,
                                              uint32_t flags, const uint64_t* filters, uint64_t filter_stride_words, uint32_t n_filters, uint64_t n_bits,
                                              const uint32_t* filter_of, uint64_t* out_lims, uint64_t* out_ids, float* out_dist, uint64_t cap, uint64_t* out_total) {
-  return range_filtered_multi_host_common(h, "vers_ivf_range_search_filtered_multi", true, queries, q_stride_bytes, b, radius, nprobe, flags, filters,
-                                          filter_stride_words, n_filters, n_bits, filter_of, out_lims, out_ids, out_dist, cap, out_total);
+  return range_filtered_host_common(h, "vers_ivf_range_search_filtered_multi", true, FilterForm::kMulti, queries, q_stride_bytes, b, radius, nprobe, flags,
+                                    FilterArg{filters, filter_stride_words, n_filters, n_bits, filter_of}, out_lims, out_ids, out_dist, cap, out_total);
 }
 
 int32_t vers_ivf_range_search_exhaustive_filtered_multi(vers_ivf_t* h, const float* queries, uint64_t q_stride_bytes, uint32_t b, const float* radius, uint32_t metric,
                                                         uint32_t flags, const uint64_t* filters, uint64_t filter_stride_words, uint32_t n_filters, uint64_t n_bits,
                                                         const uint32_t* filter_of, uint64_t* out_lims, uint64_t* out_ids, float* out_dist, uint64_t cap,
                                                         uint64_t* out_total) {
-  return range_filtered_multi_host_common(h, "vers_ivf_range_search_exhaustive_filtered_multi", false, queries, q_stride_bytes, b, radius, metric, flags, filters,
-                                          filter_stride_words, n_filters, n_bits, filter_of, out_lims, out_ids, out_dist, cap, out_total);
+  return range_filtered_host_common(h, "vers_ivf_range_search_exhaustive_filtered_multi", false, FilterForm::kMulti, queries, q_stride_bytes, b, radius, metric, flags,
+                                    FilterArg{filters, filter_stride_words, n_filters, n_bits, filter_of}, out_lims, out_ids, out_dist, cap, out_total);
 }
 
 int32_t vers_range_merge_dev(const uint64_t* keys_dev, const uint64_t* ids_dev, uint64_t rank_stride, const uint64_t* rank_lims_dev, uint32_t world, uint32_t b,
@@ -2545,8 +2372,8 @@ static int32_t range_sharded_common(vers_ivf_t* h, const vers_comm_t* comm, cons
       h, who, comm, queries_dev, ldq_floats, b, radius_dev, exhaustive_metric >= 0, flags, out_lims_dev, out_ids_dev, out_dist_dev, cap, out_total, stream,
       [&]() -> int32_t { return exhaustive_metric >= 0 ? range_exhaustive_check(h, who, flags, true) : range_check(h, who, nprobe, flags, true); },
       [&](uint64_t* lims, uint64_t* local_total, hipStream_t st, RangePartial* part) -> int32_t {
-        return range_dev_locked(h, exhaustive_metric < 0, queries_dev, ldq_floats, b, radius_dev, exhaustive_metric >= 0 ? (uint32_t)exhaustive_metric : nprobe, flags, lims,
-                                nullptr, nullptr, cap, false, local_total, st, part);
+        return range_dev_locked(h, range_name(exhaustive_metric < 0), exhaustive_metric < 0, queries_dev, ldq_floats, b, radius_dev,
+                                exhaustive_metric >= 0 ? (uint32_t)exhaustive_metric : nprobe, flags, lims, nullptr, nullptr, cap, false, local_total, st, part);
       });
 }
 
@@ -2564,154 +2391,59 @@ int32_t vers_ivf_range_search_exhaustive_sharded_dev(vers_ivf_t* h, const vers_c
 }
 
 // ---- filtered search on handles sharded by cluster (vers_hip.h): a rank's partial of every filtered call, and the calls end to end ----
-// The filters of these calls, always in the _multi form.  filter_of == NULL: ONE bitmap for the batch, the per-call kernels (filter.hip.h,
-// filter_range.hip.h); else the per-query kernels (filter_multi.hip.h, filter_range_multi.hip.h).
+// The filters of these calls come in the _multi form, a NULL filter_of meaning one bitmap for the batch (FilterForm::kEither).
 namespace {
-struct ShardFilter {
-  const uint64_t* filters; uint64_t stride_words; uint32_t n_filters; uint64_t n_bits; const uint32_t* filter_of;
-  vers_filter* prep = nullptr;  // a prepared call: the object the bitmaps above are (its masks serve the call, filter_begin / filter_multi_begin)
-  bool multi() const { return filter_of != nullptr; }
-  uint32_t n_sets() const { return multi() ? n_filters : 1u; }
-  FilterMultiSpec spec() const { return FilterMultiSpec{stride_words, n_filters, filter_of}; }
-};
-enum class ShardKind { kPartial, kSharded };
-// the leased workspace told whose masks the call reads, for as long as the local part runs
-struct PreparedScope {
-  SearchWs* w;
-  explicit PreparedScope(vers_filter* o) : w(W) { w->prep = o; }
-  ~PreparedScope() { w->prep = nullptr; }
-};
-
-// what these calls refuse before they touch the device: the per-call and _multi calls' checks, less the refusal of a sharded handle
-int32_t shard_filter_check(vers_ivf* h, const std::string& who, bool probed, bool range, uint32_t nprobe, uint32_t b, const ShardFilter& f) {
-  if (b != 0 && f.n_filters == 0) return fail(VERS_ERR_INVALID, who + ": n_filters == 0");
-  if (f.n_filters > VERS_FILTER_MAX) return fail(VERS_ERR_INVALID, who + ": more than VERS_FILTER_MAX bitmaps in one call; split the batch by allowed set");
-  if (b != 0 && f.filter_of == nullptr && f.n_filters != 1) return fail(VERS_ERR_INVALID, who + ": a NULL filter_of means one bitmap for the batch: n_filters must be 1");
-  if (f.n_bits != 0 && f.stride_words < (f.n_bits + 63) / 64) return fail(VERS_ERR_INVALID, who + ": filter_stride_words is smaller than ceil(n_bits / 64)");
-  if (f.n_bits != 0 && f.filters == nullptr) return fail(VERS_ERR_INVALID, who + ": n_bits > 0 with NULL filters");
-  if (probed && nprobe == 0)
-    return fail(VERS_ERR_INVALID, who + (range ? ": nprobe must be at least 1 (the reference's spill walk is defined by top_k: it has no range meaning)"
-                                               : ": nprobe must be at least 1 (the reference's spill walk depends on the filtered list lengths: out of scope)"));
-  if (probed && h->k == 0)
-    return fail(VERS_ERR_INSUFFICIENT, range ? "range search on an index without centroids (reference: index out of bounds, ivfflat.rs:169)"
-                                             : "search on an index without centroids (reference: index out of bounds, ivfflat.rs:169)");
-  return VERS_OK;
-}
-
-int32_t shard_adaptive_check(const std::string& who, const vers_adaptive_t* ad, uint32_t nprobe_max, ShardKind kind) {
-  if (ad == nullptr) return VERS_OK;
-  if (ad->nprobe_min == 0) return fail(VERS_ERR_INVALID, who + ": nprobe_min must be at least 1");
-  if (nprobe_max < ad->nprobe_min) return fail(VERS_ERR_INVALID, who + ": nprobe (the adaptive call's nprobe_max) is below nprobe_min");
-  if (kind == ShardKind::kPartial && ad->allowed_len_dev == nullptr)
-    return fail(VERS_ERR_INVALID, who + ": an adaptive partial needs the GLOBAL allowed counts (vers_ivf_filter_allowed_len_dev on every rank, summed)");
-  if (kind == ShardKind::kSharded && ad->allowed_len_dev != nullptr) return fail(VERS_ERR_INVALID, who + ": allowed_len_dev must be NULL (the call exchanges the counts itself)");
-  return VERS_OK;
-}
-
-// the local part of the four top-k calls: this rank's partial into keys / ids.  The workspace's o_* buffers take what a partial has no use for.
-int32_t shard_filtered_local(vers_ivf* h, bool probed, const float* q_dev, uint64_t ldq, uint32_t b, uint32_t top_k, uint32_t nprobe_or_metric, const ShardFilter& f,
-                             const AdaptiveSpec* as, uint64_t* keys, uint64_t* ids, hipStream_t st) {
+// the local part of the top-k partial, sharded and prepared calls: this rank's partial into keys / ids.  The workspace's o_* buffers take what a partial has no use for.
+int32_t shard_filtered_local(vers_ivf* h, bool probed, const float* q_dev, uint64_t ldq, uint32_t b, uint32_t top_k, uint32_t nprobe_or_metric, const FilterArg& f,
+                             const AdaptiveSpec& as, uint64_t* keys, uint64_t* ids, hipStream_t st) {
   if (int32_t rc = ensure_out(h, (size_t)b * top_k, b)) return rc;
-  const FilterMultiSpec ms = f.spec();
-  const PreparedScope scope(f.prep);
-  if (probed)
-    return filtered_dev_locked(h, q_dev, ldq, b, top_k, nprobe_or_metric, f.filters, f.n_bits, ids, W->o_dist.as<float>(), W->o_cnt.as<uint32_t>(), st, f.multi() ? &ms : nullptr, as, keys);
-  return exhaustive_filtered_dev_locked(h, q_dev, ldq, b, top_k, nprobe_or_metric, f.filters, f.n_bits, W->o_ids.as<uint64_t>(), W->o_dist.as<float>(), W->o_cnt.as<uint32_t>(), st,
-                                        f.multi() ? &ms : nullptr, keys, ids);
+  if (probed) return filtered_dev_locked(h, q_dev, ldq, b, top_k, nprobe_or_metric, f, as, ids, W->o_dist.as<float>(), W->o_cnt.as<uint32_t>(), st, keys);
+  return exhaustive_filtered_dev_locked(h, q_dev, ldq, b, top_k, nprobe_or_metric, f, W->o_ids.as<uint64_t>(), W->o_dist.as<float>(), W->o_cnt.as<uint32_t>(), st, keys, ids);
 }
 
 int32_t filtered_partial_common(vers_ivf_t* h, const char* who, bool probed, const float* queries_dev, uint64_t ldq_floats, uint32_t b, uint32_t top_k, uint32_t nprobe_or_metric,
-                                const ShardFilter& f, const vers_adaptive_t* ad, uint64_t* out_keys_dev, uint64_t* out_ids_dev, void* stream) {
+                                const FilterArg& f, const vers_adaptive_t* adaptive, uint64_t* out_keys_dev, uint64_t* out_ids_dev, void* stream) {
   if (!h) return fail(VERS_ERR_INVALID, "null handle");
   if (top_k == 0) return fail(VERS_ERR_INVALID, std::string(who) + ": top_k must be at least 1");
   if (!probed && nprobe_or_metric > VERS_METRIC_COSDIST) return fail(VERS_ERR_INVALID, "unknown metric");
   if (b && (!queries_dev || ldq_floats < h->d || !out_keys_dev || !out_ids_dev)) return fail(VERS_ERR_INVALID, std::string(who) + ": bad arguments");
-  if (int32_t rc = shard_adaptive_check(who, ad, nprobe_or_metric, ShardKind::kPartial)) return rc;
-  std::shared_lock<std::shared_mutex> lk(h->index);
-  if (int32_t rc = shard_filter_check(h, who, probed, false, probed ? nprobe_or_metric : 1u, b, f)) return rc;
-  if (b == 0) return VERS_OK;
-  DeviceGuard g(h->device);
-  WsLease lease(h, true, (hipStream_t)stream);
-  if (lease.rc) return lease.rc;
-  if (int32_t rc = lease.order_on((hipStream_t)stream)) return rc;
-  AdaptiveSpec as{ad ? ad->nprobe_min : 0u, ad ? ad->min_allowed : 0u, ad ? ad->out_nprobe_dev : (uint32_t*)nullptr};
-  if (ad) as.allowed_len = ad->allowed_len_dev;
-  return shard_filtered_local(h, probed, queries_dev, ldq_floats, b, top_k, nprobe_or_metric, f, ad ? &as : nullptr, out_keys_dev, out_ids_dev, (hipStream_t)stream);
+  const AdaptiveSpec as = adaptive_spec(adaptive);
+  if (int32_t rc = adaptive_check(who, as, nprobe_or_metric, AdaptiveKind::kPartial)) return rc;
+  return dev_call(
+      h, b, false, stream, [&]() -> int32_t { return filtered_check(h, who, FilterCheck{probed, false, FilterForm::kEither, nullptr}, nprobe_or_metric, 0, b, f); },
+      [&](hipStream_t st) -> int32_t { return shard_filtered_local(h, probed, queries_dev, ldq_floats, b, top_k, nprobe_or_metric, f, as, out_keys_dev, out_ids_dev, st); });
 }
 
 int32_t filtered_sharded_common(vers_ivf_t* h, const char* who, bool probed, const vers_gather_t* g, const float* queries_dev, uint64_t ldq_floats, uint32_t b, uint32_t top_k,
-                                uint32_t nprobe_or_metric, const ShardFilter& f, const vers_adaptive_t* ad, uint64_t* out_ids_dev, float* out_dist_dev, uint32_t* out_count_dev,
+                                uint32_t nprobe_or_metric, const FilterArg& f, const vers_adaptive_t* adaptive, uint64_t* out_ids_dev, float* out_dist_dev, uint32_t* out_count_dev,
                                 void* stream) {
   if (h && !probed && nprobe_or_metric > VERS_METRIC_COSDIST) return fail(VERS_ERR_INVALID, "unknown metric");
+  AdaptiveSpec as = adaptive_spec(adaptive);
   if (h)
-    if (int32_t rc = shard_adaptive_check(who, ad, nprobe_or_metric, ShardKind::kSharded)) return rc;
+    if (int32_t rc = adaptive_check(who, as, nprobe_or_metric, AdaptiveKind::kSharded)) return rc;
   size_t count_words = 0;
   return sharded_topk_run(
       h, who, g, queries_dev, ldq_floats, b, top_k, 0, count_words, out_ids_dev, out_dist_dev, out_count_dev, stream,
       [&]() -> int32_t {
-        if (int32_t rc = shard_filter_check(h, who, probed, false, probed ? nprobe_or_metric : 1u, b, f)) return rc;
-        if (ad) count_words = (size_t)f.n_sets() * h->k;
+        if (int32_t rc = filtered_check(h, who, FilterCheck{probed, false, FilterForm::kEither, nullptr}, nprobe_or_metric, 0, b, f)) return rc;
+        if (as.on) count_words = (size_t)f.n_sets() * h->k;
         return VERS_OK;
       },
       [&](uint64_t* keys, uint64_t* ids, const ShardReduce& reduce, hipStream_t st) -> int32_t {
-        AdaptiveSpec as{ad ? ad->nprobe_min : 0u, ad ? ad->min_allowed : 0u, ad ? ad->out_nprobe_dev : (uint32_t*)nullptr};
-        if (ad) as.reduce = reduce;
-        return shard_filtered_local(h, probed, queries_dev, ldq_floats, b, top_k, nprobe_or_metric, f, ad ? &as : nullptr, keys, ids, st);
+        if (as.on) as.reduce = reduce;
+        return shard_filtered_local(h, probed, queries_dev, ldq_floats, b, top_k, nprobe_or_metric, f, as, keys, ids, st);
       });
 }
 
-// what the four range calls refuse before they touch the device or exchange anything
-int32_t shard_range_filter_check(vers_ivf* h, const std::string& who, bool probed, uint32_t nprobe, uint32_t flags, uint32_t b, const ShardFilter& f) {
-  if (flags & ~VERS_RANGE_WALK_ORDER) return fail(VERS_ERR_INVALID, who + ": unknown flag bits");
-  if (!probed && (flags & VERS_RANGE_WALK_ORDER))
-    return fail(VERS_ERR_INVALID, who + ": no walk order across ranks (storage order has no key the ranks share); use the default order");
-  return shard_filter_check(h, who, probed, true, nprobe, b, f);
-}
-
-// a rank's partial filtered range call on `st` (the caller holds the index shared, a leased workspace and status word 1)
-int32_t shard_range_filtered_local(vers_ivf* h, const char* who, bool probed, const float* q_dev, uint64_t ldq, uint32_t b, const float* radius_dev, uint32_t nprobe_or_metric,
-                                   uint32_t flags, const ShardFilter& f, uint64_t* lims_dev, uint64_t* ids_dev, uint64_t cap, uint64_t* out_total, hipStream_t st,
-                                   RangePartial* part) {
-  const PreparedScope scope(f.prep);
-  if (f.multi())
-    return range_filtered_multi_dev_locked(h, probed, q_dev, ldq, b, radius_dev, nprobe_or_metric, flags, f.filters, f.n_bits, f.spec(), lims_dev, ids_dev, nullptr, cap, false,
-                                           out_total, st, part, who);
-  return range_filtered_dev_locked(h, probed, q_dev, ldq, b, radius_dev, nprobe_or_metric, flags, f.filters, f.n_bits, lims_dev, ids_dev, nullptr, cap, false, out_total, st, part,
-                                   who);
-}
-
-int32_t range_filtered_partial_common(vers_ivf_t* h, const char* who, bool probed, const float* queries_dev, uint64_t ldq_floats, uint32_t b, const float* radius_dev,
-                                      uint32_t nprobe_or_metric, uint32_t flags, const ShardFilter& f, uint64_t* out_lims_dev, uint64_t* out_keys_dev, uint64_t* out_ids_dev,
-                                      uint64_t cap, uint64_t* out_total, void* stream) {
-  if (!h) return fail(VERS_ERR_INVALID, "null handle");
-  if (!out_total) return fail(VERS_ERR_INVALID, std::string(who) + ": out_total is required");
-  *out_total = 0;
-  if (!probed && nprobe_or_metric > VERS_METRIC_COSDIST) return fail(VERS_ERR_INVALID, "unknown metric");
-  if (b && (!queries_dev || ldq_floats < h->d || !radius_dev || !out_lims_dev || (cap && (!out_ids_dev || !out_keys_dev))))
-    return fail(VERS_ERR_INVALID, std::string(who) + ": bad arguments");
-  if (b == 0) return VERS_OK;
-  std::shared_lock<std::shared_mutex> lk(h->index);
-  if (int32_t rc = shard_range_filter_check(h, who, probed, probed ? nprobe_or_metric : 1u, flags, b, f)) return rc;
-  DeviceGuard g(h->device);
-  WsLease lease(h, true, (hipStream_t)stream);
-  if (lease.rc) return lease.rc;
-  if (int32_t rc = lease.order_on((hipStream_t)stream)) return rc;
-  HostStatusSlot slot(h);
-  RangePartial part;
-  part.keys = out_keys_dev;
-  return shard_range_filtered_local(h, who, probed, queries_dev, ldq_floats, b, radius_dev, nprobe_or_metric, flags, f, out_lims_dev, out_ids_dev, cap, out_total,
-                                    (hipStream_t)stream, &part);
-}
-
 int32_t range_filtered_sharded_common(vers_ivf_t* h, const char* who, bool probed, const vers_comm_t* comm, const float* queries_dev, uint64_t ldq_floats, uint32_t b,
-                                      const float* radius_dev, uint32_t nprobe_or_metric, uint32_t flags, const ShardFilter& f, uint64_t* out_lims_dev, uint64_t* out_ids_dev,
+                                      const float* radius_dev, uint32_t nprobe_or_metric, uint32_t flags, const FilterArg& f, uint64_t* out_lims_dev, uint64_t* out_ids_dev,
                                       float* out_dist_dev, uint64_t cap, uint64_t* out_total, void* stream) {
   if (h && out_total && !probed && nprobe_or_metric > VERS_METRIC_COSDIST) { *out_total = 0; return fail(VERS_ERR_INVALID, "unknown metric"); }
   return range_sharded_run(
       h, who, comm, queries_dev, ldq_floats, b, radius_dev, !probed, flags, out_lims_dev, out_ids_dev, out_dist_dev, cap, out_total, stream,
-      [&]() -> int32_t { return shard_range_filter_check(h, who, probed, probed ? nprobe_or_metric : 1u, flags, b, f); },
+      [&]() -> int32_t { return filtered_check(h, who, FilterCheck{probed, true, FilterForm::kEither, nullptr}, nprobe_or_metric, flags, b, f); },
       [&](uint64_t* lims, uint64_t* local_total, hipStream_t st, RangePartial* part) -> int32_t {
-        return shard_range_filtered_local(h, who, probed, queries_dev, ldq_floats, b, radius_dev, nprobe_or_metric, flags, f, lims, nullptr, cap, local_total, st, part);
+        return range_filtered_dev_locked(h, who, probed, queries_dev, ldq_floats, b, radius_dev, nprobe_or_metric, flags, f, lims, nullptr, nullptr, cap, false, local_total, st, part);
       });
 }
 }  // namespace
@@ -2732,12 +2464,9 @@ int32_t vers_ivf_filter_allowed_len_dev(vers_ivf_t* h, const uint64_t* filters_d
   WsLease lease(h, true, st);
   if (lease.rc) return lease.rc;
   if (int32_t rc = lease.order_on(st)) return rc;
-  FilterParams f;
-  FilterMultiParams fm;
-  const bool multi = n_filters > 1;
-  const FilterMultiSpec ms{filter_stride_words, n_filters, nullptr};
-  if (int32_t rc = multi ? filter_multi_begin(h, filters_dev, n_bits, ms, h->cap_rows, st, fm) : filter_begin(h, filters_dev, n_bits, h->cap_rows, st, f)) return rc;
-  if (int32_t rc = filter_count_allowed(h, multi ? nullptr : &f, multi ? &fm : nullptr, n_filters, out_len_dev, st)) return rc;
+  FilterMasks masks;  // (one bitmap: the per-call mask; several: the per-query sets, every bitmap counted)
+  if (int32_t rc = filter_begin(h, FilterArg{filters_dev, filter_stride_words, n_filters, n_bits, nullptr}, h->cap_rows, st, masks)) return rc;
+  if (int32_t rc = filter_count_allowed(h, masks, n_filters, out_len_dev, st)) return rc;
   return filter_end(h, st);
 }
 
@@ -2745,46 +2474,48 @@ int32_t vers_ivf_search_filtered_partial_dev(vers_ivf_t* h, const float* queries
                                              const uint64_t* filters_dev, uint64_t filter_stride_words, uint32_t n_filters, uint64_t n_bits, const uint32_t* filter_of_dev,
                                              const vers_adaptive_t* adaptive, uint64_t* out_keys_dev, uint64_t* out_ids_dev, void* stream) {
   return filtered_partial_common(h, "vers_ivf_search_filtered_partial_dev", true, queries_dev, ldq_floats, b, top_k, nprobe,
-                                 ShardFilter{filters_dev, filter_stride_words, n_filters, n_bits, filter_of_dev}, adaptive, out_keys_dev, out_ids_dev, stream);
+                                 FilterArg{filters_dev, filter_stride_words, n_filters, n_bits, filter_of_dev}, adaptive, out_keys_dev, out_ids_dev, stream);
 }
 
 int32_t vers_ivf_search_exhaustive_filtered_partial_dev(vers_ivf_t* h, const float* queries_dev, uint64_t ldq_floats, uint32_t b, uint32_t top_k, uint32_t metric,
                                                         const uint64_t* filters_dev, uint64_t filter_stride_words, uint32_t n_filters, uint64_t n_bits,
                                                         const uint32_t* filter_of_dev, uint64_t* out_keys_dev, uint64_t* out_ids_dev, void* stream) {
   return filtered_partial_common(h, "vers_ivf_search_exhaustive_filtered_partial_dev", false, queries_dev, ldq_floats, b, top_k, metric,
-                                 ShardFilter{filters_dev, filter_stride_words, n_filters, n_bits, filter_of_dev}, nullptr, out_keys_dev, out_ids_dev, stream);
+                                 FilterArg{filters_dev, filter_stride_words, n_filters, n_bits, filter_of_dev}, nullptr, out_keys_dev, out_ids_dev, stream);
 }
 
 int32_t vers_ivf_search_filtered_sharded_dev(vers_ivf_t* h, const vers_gather_t* g, const float* queries_dev, uint64_t ldq_floats, uint32_t b, uint32_t top_k, uint32_t nprobe,
                                              const uint64_t* filters_dev, uint64_t filter_stride_words, uint32_t n_filters, uint64_t n_bits, const uint32_t* filter_of_dev,
                                              const vers_adaptive_t* adaptive, uint64_t* out_ids_dev, float* out_dist_dev, uint32_t* out_count_dev, void* stream) {
   return filtered_sharded_common(h, "vers_ivf_search_filtered_sharded_dev", true, g, queries_dev, ldq_floats, b, top_k, nprobe,
-                                 ShardFilter{filters_dev, filter_stride_words, n_filters, n_bits, filter_of_dev}, adaptive, out_ids_dev, out_dist_dev, out_count_dev, stream);
+                                 FilterArg{filters_dev, filter_stride_words, n_filters, n_bits, filter_of_dev}, adaptive, out_ids_dev, out_dist_dev, out_count_dev, stream);
 }
 
 int32_t vers_ivf_search_exhaustive_filtered_sharded_dev(vers_ivf_t* h, const vers_gather_t* g, const float* queries_dev, uint64_t ldq_floats, uint32_t b, uint32_t top_k,
                                                         uint32_t metric, const uint64_t* filters_dev, uint64_t filter_stride_words, uint32_t n_filters, uint64_t n_bits,
                                                         const uint32_t* filter_of_dev, uint64_t* out_ids_dev, float* out_dist_dev, uint32_t* out_count_dev, void* stream) {
   return filtered_sharded_common(h, "vers_ivf_search_exhaustive_filtered_sharded_dev", false, g, queries_dev, ldq_floats, b, top_k, metric,
-                                 ShardFilter{filters_dev, filter_stride_words, n_filters, n_bits, filter_of_dev}, nullptr, out_ids_dev, out_dist_dev, out_count_dev, stream);
+                                 FilterArg{filters_dev, filter_stride_words, n_filters, n_bits, filter_of_dev}, nullptr, out_ids_dev, out_dist_dev, out_count_dev, stream);
 }
 
 int32_t vers_ivf_range_search_filtered_partial_dev(vers_ivf_t* h, const float* queries_dev, uint64_t ldq_floats, uint32_t b, const float* radius_dev, uint32_t nprobe,
                                                    uint32_t flags, const uint64_t* filters_dev, uint64_t filter_stride_words, uint32_t n_filters, uint64_t n_bits,
                                                    const uint32_t* filter_of_dev, uint64_t* out_lims_dev, uint64_t* out_keys_dev, uint64_t* out_ids_dev, uint64_t cap,
                                                    uint64_t* out_total, void* stream) {
-  return range_filtered_partial_common(h, "vers_ivf_range_search_filtered_partial_dev", true, queries_dev, ldq_floats, b, radius_dev, nprobe, flags,
-                                       ShardFilter{filters_dev, filter_stride_words, n_filters, n_bits, filter_of_dev}, out_lims_dev, out_keys_dev, out_ids_dev, cap, out_total,
-                                       stream);
+  const char* who = "vers_ivf_range_search_filtered_partial_dev";
+  return range_filtered_dev_common(h, who, who, true, FilterForm::kEither, queries_dev, ldq_floats, b, radius_dev, nprobe, flags,
+                                   FilterArg{filters_dev, filter_stride_words, n_filters, n_bits, filter_of_dev}, out_lims_dev, out_keys_dev, out_ids_dev, nullptr, cap, out_total,
+                                   stream);
 }
 
 int32_t vers_ivf_range_search_exhaustive_filtered_partial_dev(vers_ivf_t* h, const float* queries_dev, uint64_t ldq_floats, uint32_t b, const float* radius_dev, uint32_t metric,
                                                               uint32_t flags, const uint64_t* filters_dev, uint64_t filter_stride_words, uint32_t n_filters, uint64_t n_bits,
                                                               const uint32_t* filter_of_dev, uint64_t* out_lims_dev, uint64_t* out_keys_dev, uint64_t* out_ids_dev,
                                                               uint64_t cap, uint64_t* out_total, void* stream) {
-  return range_filtered_partial_common(h, "vers_ivf_range_search_exhaustive_filtered_partial_dev", false, queries_dev, ldq_floats, b, radius_dev, metric, flags,
-                                       ShardFilter{filters_dev, filter_stride_words, n_filters, n_bits, filter_of_dev}, out_lims_dev, out_keys_dev, out_ids_dev, cap, out_total,
-                                       stream);
+  const char* who = "vers_ivf_range_search_exhaustive_filtered_partial_dev";
+  return range_filtered_dev_common(h, who, who, false, FilterForm::kEither, queries_dev, ldq_floats, b, radius_dev, metric, flags,
+                                   FilterArg{filters_dev, filter_stride_words, n_filters, n_bits, filter_of_dev}, out_lims_dev, out_keys_dev, out_ids_dev, nullptr, cap, out_total,
+                                   stream);
 }
 
 int32_t vers_ivf_range_search_filtered_sharded_dev(vers_ivf_t* h, const vers_comm_t* comm, const float* queries_dev, uint64_t ldq_floats, uint32_t b, const float* radius_dev,
@@ -2792,7 +2523,7 @@ int32_t vers_ivf_range_search_filtered_sharded_dev(vers_ivf_t* h, const vers_com
                                                    uint64_t n_bits, const uint32_t* filter_of_dev, uint64_t* out_lims_dev, uint64_t* out_ids_dev, float* out_dist_dev,
                                                    uint64_t cap, uint64_t* out_total, void* stream) {
   return range_filtered_sharded_common(h, "vers_ivf_range_search_filtered_sharded_dev", true, comm, queries_dev, ldq_floats, b, radius_dev, nprobe, flags,
-                                       ShardFilter{filters_dev, filter_stride_words, n_filters, n_bits, filter_of_dev}, out_lims_dev, out_ids_dev, out_dist_dev, cap, out_total,
+                                       FilterArg{filters_dev, filter_stride_words, n_filters, n_bits, filter_of_dev}, out_lims_dev, out_ids_dev, out_dist_dev, cap, out_total,
                                        stream);
 }
 
@@ -2802,7 +2533,7 @@ int32_t vers_ivf_range_search_exhaustive_filtered_sharded_dev(vers_ivf_t* h, con
                                                               uint64_t* out_lims_dev, uint64_t* out_ids_dev, float* out_dist_dev, uint64_t cap, uint64_t* out_total,
                                                               void* stream) {
   return range_filtered_sharded_common(h, "vers_ivf_range_search_exhaustive_filtered_sharded_dev", false, comm, queries_dev, ldq_floats, b, radius_dev, metric, flags,
-                                       ShardFilter{filters_dev, filter_stride_words, n_filters, n_bits, filter_of_dev}, out_lims_dev, out_ids_dev, out_dist_dev, cap, out_total,
+                                       FilterArg{filters_dev, filter_stride_words, n_filters, n_bits, filter_of_dev}, out_lims_dev, out_ids_dev, out_dist_dev, cap, out_total,
                                        stream);
 }
 
@@ -2866,10 +2597,6 @@ int32_t prepared_check(vers_ivf_t* h, const char* who, const vers_filter_t* f) {
   }
   return VERS_OK;
 }
-void prepared_filter(const vers_filter_t* f, const uint32_t* filter_of_dev, ShardFilter& sf) {
-  sf = ShardFilter{f->bits.as<uint64_t>(), f->words, f->n_filters, f->n_bits, filter_of_dev};
-  sf.prep = const_cast<vers_filter_t*>(f);
-}
 }  // namespace
 
 int32_t vers_ivf_filter_prepare(vers_ivf_t* h, const uint64_t* filters, uint64_t filter_stride_words, uint32_t n_filters, uint64_t n_bits, vers_filter_t** out) {
@@ -2924,8 +2651,7 @@ int32_t vers_ivf_search_prepared_dev(vers_ivf_t* h, const float* queries_dev, ui
                                      void* stream) {
   const char* who = "vers_ivf_search_prepared_dev";
   if (int32_t rc = prepared_check(h, who, f)) return rc;
-  ShardFilter sf;
-  prepared_filter(f, filter_of_dev, sf);
+  const FilterArg sf = prepared_filter(f, filter_of_dev);
   return filtered_sharded_common(h, who, true, nullptr, queries_dev, ldq_floats, b, top_k, nprobe, sf, adaptive, out_ids_dev, out_dist_dev,
                                  out_count_dev, stream);
 }
@@ -2935,8 +2661,7 @@ int32_t vers_ivf_search_exhaustive_prepared_dev(vers_ivf_t* h, const float* quer
                                                 uint32_t* out_count_dev, void* stream) {
   const char* who = "vers_ivf_search_exhaustive_prepared_dev";
   if (int32_t rc = prepared_check(h, who, f)) return rc;
-  ShardFilter sf;
-  prepared_filter(f, filter_of_dev, sf);
+  const FilterArg sf = prepared_filter(f, filter_of_dev);
   return filtered_sharded_common(h, who, false, nullptr, queries_dev, ldq_floats, b, top_k, metric, sf, nullptr, out_ids_dev, out_dist_dev,
                                  out_count_dev, stream);
 }
@@ -2946,8 +2671,7 @@ int32_t vers_ivf_range_search_prepared_dev(vers_ivf_t* h, const float* queries_d
                                            float* out_dist_dev, uint64_t cap, uint64_t* out_total, void* stream) {
   const char* who = "vers_ivf_range_search_prepared_dev";
   if (int32_t rc = prepared_check(h, who, f)) return rc;
-  ShardFilter sf;
-  prepared_filter(f, filter_of_dev, sf);
+  const FilterArg sf = prepared_filter(f, filter_of_dev);
   return range_filtered_sharded_common(h, who, true, nullptr, queries_dev, ldq_floats, b, radius_dev, nprobe, flags, sf, out_lims_dev,
                                        out_ids_dev, out_dist_dev, cap, out_total, stream);
 }
@@ -2957,8 +2681,7 @@ int32_t vers_ivf_range_search_exhaustive_prepared_dev(vers_ivf_t* h, const float
                                                       uint64_t* out_ids_dev, float* out_dist_dev, uint64_t cap, uint64_t* out_total, void* stream) {
   const char* who = "vers_ivf_range_search_exhaustive_prepared_dev";
   if (int32_t rc = prepared_check(h, who, f)) return rc;
-  ShardFilter sf;
-  prepared_filter(f, filter_of_dev, sf);
+  const FilterArg sf = prepared_filter(f, filter_of_dev);
   return range_filtered_sharded_common(h, who, false, nullptr, queries_dev, ldq_floats, b, radius_dev, metric, flags, sf, out_lims_dev,
                                        out_ids_dev, out_dist_dev, cap, out_total, stream);
 }
