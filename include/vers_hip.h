@@ -434,6 +434,49 @@ int32_t vers_ivf_compact(vers_ivf_t* h, uint64_t* out_rows_before, uint64_t* out
  * [1] storage rows before, [2] storage rows after (summed over the calls), [3] planning + allocation, [4] the move (fused: with every
  * derived array), [5] derived arrays on the unfused path, [6] tables, [7] reserved.  reset != 0 zeroes them. */
 int32_t vers_compact_phases(double* out8, int32_t reset);
+/* Recluster (extension: the reference re-trains by building a new index, which renumbers every vector; defined on its five fields, like the
+ * removal and the update).  With L = the ascending sequence of the vec ids that are in some list, m = |L| and X'[j] = values[L[j]]:
+ *     (centroids', a') = IVFFlatIndex::build_index(num_clusters, num_attempts, max_iterations, &X')     -- ivfflat.rs:102-136, the handle's metric,
+ *                        the draws of initialize_centroids injected as init_indices [num_attempts * num_clusters]: POSITIONS in L, 0 .. m-1,
+ *                        exactly what gen_range(0..X'.len()) would draw
+ *     if an attempt was kept { centroids = centroids';  for j: assignments[L[j]] = a'[j];  ids[c] = [ L[j] : a'[j] == c ], ascending }
+ * values, assignments.len() (n of vers_ivf_info and the id the next add hands out) and the live count do not change; an id that is not in L
+ * stays in no list and is never reused.  In one sentence: AFTER A RECLUSTER THE HANDLE IS, BIT FOR BIT IN EVERYTHING OBSERVABLE, A HANDLE
+ * THAT RECEIVED vers_ivf_upload(values, centroids', assignments') FOLLOWED BY vers_ivf_remove_batch OF THE IDS THAT ARE IN NO LIST
+ * (assignments' of such an id is 0; nothing observable depends on it).  The vec ids are kept: bitmap filters, the host's id mapping and
+ * whatever an update call addresses stay valid.
+ *   arithmetic   : the k-means is the build's own -- update_centroids sums a cluster's members in ascending position of X' (ascending vec
+ *                  id), the cost fold runs in that order, the first best attempt wins: centroids, assignments, cost and iteration counts
+ *                  are the bits vers_ivf_build gives on the rows values[L].
+ *   num_clusters : may differ from the current k, larger or smaller; an empty cluster gets the zero centroid, as in the build.
+ *   storage      : the plan of a fresh upload of the new lengths (len + max(8, len / 16) rounded up to 64 rows, lists ascending on tile
+ *                  boundaries), whatever slack the old lists carried.
+ *   derived      : both certificate maxima and the fp16 shadow's self-retirement state are recomputed over the rows the lists hold, as
+ *                  after vers_ivf_compact; the int8 head, the shadow and the row-major copy follow the options as a build reads them.
+ *   filters      : a prepared vers_filter_t stays a valid object (ids are kept) and rebuilds in full at its next use, also when k changed.
+ *   outputs      : host memory, all nullable except out_kept.  out_centroids: num_clusters rows of pitch c_stride_bytes (>= 4 d);
+ *                  out_assignments: [n] indexed by VEC ID, 0 for an id in no list; out_cost; out_iterations [num_attempts].
+ *   ALL OR NOTHING -- every refusal leaves the index unchanged and searchable and the outputs untouched: a handle sharded by cluster
+ *                  (world > 1: the build's exchanges are not wired in yet) -> VERS_ERR_INVALID; no centroids, no live row,
+ *                  num_clusters == 0 or a streamed upload in progress -> VERS_ERR_EMPTY; an init index >= m -> VERS_ERR_INVALID; a NaN
+ *                  distance with num_clusters >= 2 -> VERS_ERR_NAN (the k-means runs beside the index, not in it).  A NULL handle:
+ *                  VERS_ERR_INVALID before anything else is looked at.
+ *   nothing kept : num_attempts == 0, or no attempt's cost below +inf: VERS_OK, *out_kept = 0 (cost +inf, the iteration counts written),
+ *                  the index UNCHANGED.  THIS DIFFERS FROM vers_ivf_build ON PURPOSE, which leaves an empty index: a maintenance call
+ *                  does not destroy what it was asked to improve.
+ *   memory       : beside the index the call holds X' (m rows at the row-major pitch) for the length of the k-means, and the new tiles
+ *                  until they replace the old ones; the old shadow, head and row-major copy are released before the new tiles are
+ *                  reserved.  When X' or the new tiles do not fit: VERS_ERR_HIP, the OLD index stays intact and searchable (the rule of
+ *                  vers_ivf_compact).
+ * Synchronous; holds the handle exclusively and waits for searches in flight, like vers_ivf_add_batch / vers_ivf_remove_batch /
+ * vers_ivf_compact. */
+int32_t vers_ivf_recluster(vers_ivf_t* h, uint64_t num_clusters, uint64_t num_attempts, uint64_t max_iterations, const uint64_t* init_indices,
+                           float* out_centroids, uint64_t c_stride_bytes, uint64_t* out_assignments, float* out_cost, int32_t* out_kept,
+                           uint64_t* out_iterations);
+/* The recluster calls of this process by PHASE (host wall clock in ms, the stream synchronised at each phase's end; a refused call counts
+ * nowhere).  out[8]: [0] calls, [1] live rows gathered, [2] the gather (rank table plus rows), [3] k-means, all attempts, [4] install
+ * (grouping, reservation, placement, id relabel), [5] derived arrays, [6] tables (the storage plan), [7] reserved.  reset != 0 zeroes them. */
+int32_t vers_recluster_phases(double* out8, int32_t reset);
 /* Range search (extension; the reference has search_approximate only).  In the reference's terms: for query q, rank the lists as
  * search_approximate does (ivfflat.rs:155-161: first minimum, stable), take the P = min(nprobe, k) nearest, and return EVERY row of
  * `ids[c]` of those lists whose distance D(q, values[id]) -- the index's metric, the reference's bits: sequential f32, multiply and add

@@ -109,6 +109,9 @@ SIGNATURES = {
     "vers_update_phases": (C.c_int32, [C.POINTER(C.c_double), C.c_int32]),
     "vers_ivf_compact": (C.c_int32, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "vers_compact_phases": (C.c_int32, [C.POINTER(C.c_double), C.c_int32]),
+    "vers_ivf_recluster": (C.c_int32, [_vp, C.c_uint64, C.c_uint64, C.c_uint64, _vp, _vp, C.c_uint64, _vp, C.POINTER(C.c_float), C.POINTER(C.c_int32),
+                                       _vp]),
+    "vers_recluster_phases": (C.c_int32, [C.POINTER(C.c_double), C.c_int32]),
     "vers_ivf_range_search": (C.c_int32, [_vp, _vp, C.c_uint64, C.c_uint32, _vp, C.c_uint32, C.c_uint32, _vp, _vp, _vp, C.c_uint64,
                                           C.POINTER(C.c_uint64)]),
     "vers_ivf_range_search_dev": (C.c_int32, [_vp, _vp, C.c_uint64, C.c_uint32, _vp, C.c_uint32, C.c_uint32, _vp, _vp, _vp, C.c_uint64,
@@ -512,6 +515,14 @@ def compact_phases(reset=False) -> dict:
     v = (C.c_double * 8)()
     check(lib().vers_compact_phases(v, 1 if reset else 0))
     keys = ("calls", "rows_before", "rows_after", "plan_ms", "move_ms", "derive_ms", "tables_ms", "reserved")
+    return dict(zip(keys, (float(x) for x in v)))
+
+
+def recluster_phases(reset=False) -> dict:
+    """The recluster calls of this process by phase, host wall clock in ms (vers_recluster_phases)."""
+    v = (C.c_double * 8)()
+    check(lib().vers_recluster_phases(v, 1 if reset else 0))
+    keys = ("calls", "rows", "gather_ms", "kmeans_ms", "install_ms", "derive_ms", "tables_ms", "reserved")
     return dict(zip(keys, (float(x) for x in v)))
 
 

@@ -350,6 +350,89 @@ __global__ __launch_bounds__(256) void tiles_to_rowmajor_kernel(const float* in,
   }
 }
 
+// ---- vers_ivf_recluster: the tiled list storage back to the live rows in ascending vec id ------------------------------------------------
+// [recluster gather kernel: begin] (tests/test_recluster_kernel_host.py runs the text between the two markers on the host)
+// One job per OCCUPIED tile, made on the host from the lists' offsets and lengths (vers_ivf::tile_list is not used: a re-layout leaves it
+// stale): the tile and how many of its rows lie below its list's length.
+struct GatherJob {
+  uint32_t tile, n_valid;  // storage row / 64 | 1 .. 64
+};
+// One BLOCK per occupied tile (jobs[blockIdx.x]), tiles_to_rowmajor_kernel with a destination per ROW: the tile's 1 KiB pieces are read as
+// they lie, turned through LDS kGatherCols4 float4 columns at a time, and every live row r of the tile -- r < n_valid: below its list's
+// length -- leaves as one contiguous run to row rank[row_ids[r]] of X' (pitch floats a row, a multiple of 4, <= ld).  Columns d .. pitch - 1
+// are written as zeros whatever the tile holds there; a row past the list's length is written nowhere, so what slack holds (NaN, anything)
+// reaches nothing.  Only the f32 tiles are read.  The destinations of the tile's 64 rows sit behind the [64][kGatherCols4 + 1] float4s of
+// the dynamic LDS.
+__global__ __launch_bounds__(256) void tiles_to_live_rows_kernel(const float* in, uint32_t ld, uint32_t d, uint32_t pitch, const GatherJob* jobs,
+                                                                 const uint32_t* row_ids, const uint64_t* rank, uint64_t n_total, uint64_t m,
+                                                                 float* out) {
+  extern __shared__ __attribute__((aligned(16))) f32x4 tl[];  // [64][kGatherCols4 + 1] | u32 [64]
+  constexpr uint32_t kPitch = kGatherCols4 + 1;
+  uint32_t* s_dst = reinterpret_cast<uint32_t*>(tl + 64u * kPitch);
+  const uint64_t t = jobs[blockIdx.x].tile;
+  const uint32_t n_valid = jobs[blockIdx.x].n_valid;
+  if (threadIdx.x < 64u) {
+    uint32_t dst = 0xFFFFFFFFu;
+    if (threadIdx.x < n_valid) {
+      const uint32_t v = row_ids[t * 64ull + threadIdx.x];
+      if (v < n_total && rank[v] < m) dst = (uint32_t)rank[v];
+    }
+    s_dst[threadIdx.x] = dst;
+  }
+  const uint32_t p4 = pitch / 4;
+  const f32x4* tile = reinterpret_cast<const f32x4*>(in + t * 64ull * ld);
+  f32x4* xo = reinterpret_cast<f32x4*>(out);
+  for (uint32_t c0 = 0; c0 < p4; c0 += kGatherCols4) {
+    const uint32_t nc = p4 - c0 < kGatherCols4 ? p4 - c0 : kGatherCols4;
+    for (uint32_t i = threadIdx.x; i < 64u * nc; i += 256u) {  // a piece's 64 rows by consecutive threads: 1 KiB contiguous
+      const uint32_t j = i / 64u, r = i % 64u;
+      tl[r * kPitch + j] = tile[(uint64_t)(c0 + j) * 64 + r];
+    }
+    lds_barrier();  // (the first pass: s_dst too)
+    for (uint32_t i = threadIdx.x; i < 64u * kGatherCols4; i += 256u) {  // a row's float4s by consecutive threads
+      const uint32_t r = i / kGatherCols4, j = i % kGatherCols4;
+      const uint32_t dst = s_dst[r];
+      if (j < nc && dst != 0xFFFFFFFFu) {
+        f32x4 v = tl[r * kPitch + j];
+        const uint32_t col = (c0 + j) * 4u;
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+          if (col + u >= d) v[u] = 0.0f;
+        xo[(uint64_t)dst * p4 + c0 + j] = v;
+      }
+    }
+    lds_barrier();
+  }
+}
+// [recluster gather kernel: end]
+// One bit's worth (a u32 the device scan sums) per vec id that is in some list: a row counts when it lies below its list's length -- what a
+// slack row's row_ids entry happens to hold is never looked at.  One thread per (job, row).
+__global__ void recluster_live_kernel(const GatherJob* jobs, uint32_t n_jobs, const uint32_t* row_ids, uint64_t n_total, uint32_t* live) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (uint64_t)n_jobs * 64u) return;
+  const GatherJob jb = jobs[i >> 6];
+  if ((uint32_t)(i & 63u) >= jb.n_valid) return;
+  const uint32_t v = row_ids[(uint64_t)jb.tile * 64u + (i & 63u)];
+  if (v < n_total) live[v] = 1u;
+}
+// L[rank[v]] = v for every live vec id (rank = the exclusive prefix over `live`)
+__global__ void recluster_order_kernel(const uint32_t* live, const uint64_t* rank, uint64_t n_total, uint64_t m, uint32_t* L) {
+  const uint64_t v = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (v < n_total && live[v] && rank[v] < m) L[rank[v]] = (uint32_t)v;
+}
+// install_index on X' wrote row_ids as positions in X': every entry that holds a vector becomes its vec id
+__global__ void recluster_relabel_kernel(uint32_t* row_ids, uint64_t cap_rows, const uint32_t* L, uint64_t m) {
+  const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= cap_rows) return;
+  const uint32_t p = row_ids[r];
+  if (p != 0xFFFFFFFFu) row_ids[r] = p < m ? L[p] : 0xFFFFFFFFu;
+}
+// out_assignments of the call, indexed by vec id: the cluster of position rank[v] of X' for a live id, 0 for an id in no list
+__global__ void recluster_assign_out_kernel(const uint32_t* live, const uint64_t* rank, const uint32_t* a, uint64_t n_total, uint64_t m, uint64_t* out) {
+  const uint64_t v = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (v < n_total) out[v] = live[v] && rank[v] < m ? a[rank[v]] : 0ull;
+}
+
 // ---- vers_ivf_compact: whole tiles move to a tighter storage plan, every derived array written from the one read -------------------------
 // Lists start on tile boundaries and a removal has already closed the gaps inside a list, so the ceil(len / 64) tiles of an owned list
 // move as they lie: one job = one tile, from the old storage to the new one.
@@ -902,14 +985,16 @@ struct Agreement {
 // device tables, zeroed row ids.
 // The storage rule, shared by plan_storage and vers_ivf_compact: offsets and capacities of the lists this rank owns (h_owner / rank),
 // lists in ascending order, each starting on a tile boundary; another rank's list gets no storage.  *total = storage rows.
+// (all_mine: the plan of k lists this rank owns every one of, whatever h_owner says of the CURRENT lists -- vers_ivf_recluster sizes the
+// storage of its new lists before the handle learns of them)
 static int32_t plan_capacities(const vers_ivf* h, const uint32_t* lens, uint32_t k, std::vector<uint32_t>& offs, std::vector<uint32_t>& caps,
-                               uint64_t* total) {
+                               uint64_t* total, bool all_mine = false) {
   offs.assign(k, 0);
   caps.assign(k, 0);
   uint64_t off = 0;
   for (uint32_t c = 0; c < k; ++c) {
     const uint32_t len = lens[c];
-    const bool mine = h->h_owner[c] == h->rank;
+    const bool mine = all_mine || h->h_owner[c] == h->rank;
     // slack for `add` behind the list: 1/16 of its length, at least 8 rows, then up to the tile boundary the next list starts on.
     // (Rounds 1-5 kept at least 64: at k = 65536 over 6.25M rows -- lists of ~95 rows -- that alone doubled the storage; a list
     // that outgrows its slack is re-laid-out with 1/8 of head-room, relayout().)
@@ -1026,20 +1111,22 @@ int32_t finish_index(vers_ivf* h, uint32_t k, uint64_t n_total, hipStream_t st) 
   return VERS_OK;
 }
 
-// index from (X in vec_id order -- ALL rows in this process --, centroids already in h->centroids, device assignments);
-// with vers_ivf_set_shard only the owned lists are stored.
-int32_t install_index(vers_ivf* h, const float* X, uint32_t ldx, uint64_t n, const uint32_t* d_assign, uint32_t k,
-                      hipStream_t st) {
-  DevBuf sorted;
+// install_index's steps around plan_storage, before finish_index.  group_for_install: the cluster-sorted order of the rows (sorted [n], counts |
+// starts in h->km.counts) and the list lengths on the host; nothing of the index is touched.  place_rows: the rows into the tiles of the plan
+// plan_storage has just made of those lengths, row_ids = the rows' positions in X.
+static int32_t group_for_install(vers_ivf* h, uint64_t n, const uint32_t* d_assign, uint32_t k, DevBuf& sorted, std::vector<uint32_t>& lens, hipStream_t st) {
   if (int32_t rc = sorted.reserve((n ? n : 1) * sizeof(uint32_t))) return rc;
   if (int32_t rc = h->km.counts.reserve((2 * (size_t)k + 2) * sizeof(uint32_t))) return rc;
   uint32_t* counts = h->km.counts.as<uint32_t>();
-  uint32_t* starts = counts + k;
-  if (int32_t rc = km_group(d_assign, (uint32_t)n, k, sorted.as<uint32_t>(), counts, starts, h->km, st)) return rc;
-  std::vector<uint32_t> lens(k ? k : 1, 0);
+  if (int32_t rc = km_group(d_assign, (uint32_t)n, k, sorted.as<uint32_t>(), counts, counts + k, h->km, st)) return rc;
+  lens.assign(k ? k : 1, 0);
   if (k) VERS_HIP_TRY(hipMemcpyAsync(lens.data(), counts, (size_t)k * 4, hipMemcpyDeviceToHost, st));
   VERS_HIP_TRY(hipStreamSynchronize(st));
-  if (int32_t rc = plan_storage(h, lens.data(), k, st)) return rc;
+  return VERS_OK;
+}
+static int32_t place_rows(vers_ivf* h, const float* X, uint32_t ldx, uint64_t n, const uint32_t* d_assign, uint32_t k, const DevBuf& sorted,
+                          hipStream_t st) {
+  const uint32_t* starts = h->km.counts.as<uint32_t>() + k;
   if (n) {
     if (h->cap_rows >= 64) {  // whole destination tiles through LDS; (the float4-wise placement of round 1 is kept for indexes of less than one tile)
       const size_t lds = 64 * (size_t)(kGatherCols4 + 1) * sizeof(f32x4);
@@ -1053,6 +1140,17 @@ int32_t install_index(vers_ivf* h, const float* X, uint32_t ldx, uint64_t n, con
                        h->rows.as<float>(), h->row_ids.as<uint32_t>());
     VERS_HIP_TRY(hipGetLastError());
   }
+  return VERS_OK;
+}
+// index from (X in vec_id order -- ALL rows in this process --, centroids already in h->centroids, device assignments);
+// with vers_ivf_set_shard only the owned lists are stored.
+int32_t install_index(vers_ivf* h, const float* X, uint32_t ldx, uint64_t n, const uint32_t* d_assign, uint32_t k,
+                      hipStream_t st) {
+  DevBuf sorted;
+  std::vector<uint32_t> lens;
+  if (int32_t rc = group_for_install(h, n, d_assign, k, sorted, lens, st)) return rc;
+  if (int32_t rc = plan_storage(h, lens.data(), k, st)) return rc;
+  if (int32_t rc = place_rows(h, X, ldx, n, d_assign, k, sorted, st)) return rc;
   return finish_index(h, k, n, st);
 }
 
@@ -1257,11 +1355,11 @@ int32_t install_index_sharded(vers_ivf* h, const float* X, uint32_t ldx, uint64_
 }
 
 // build_kmeans + best-of-attempts (ivfflat.rs:73-121) on device-resident rows -- ALL of them (sh.comm == nullptr) or
-// this process's contiguous range of a row-sharded corpus; leaves the winning centroids in h->centroids and the
-// assignments of the LOCAL rows in best_assign.  Same arithmetic order either way (see vers_hip.h).
+// this process's contiguous range of a row-sharded corpus; leaves the winning centroids in h->centroids (or in
+// *dst_centroids when one is given) and the assignments of the LOCAL rows in best_assign.  Same arithmetic order either way (see vers_hip.h).
 int32_t run_build(vers_ivf* h, const float* X, uint32_t ldx, uint64_t n, const BuildShard& sh, uint32_t k, uint64_t num_attempts,
                   uint64_t max_iterations, const uint64_t* init_indices, DevBuf& best_assign, float* out_cost, int32_t* out_kept,
-                  uint64_t* out_iterations, hipStream_t st) {
+                  uint64_t* out_iterations, hipStream_t st, DevBuf* dst_centroids = nullptr) {
   const uint32_t ld = h->ldx;  // centroids live row-major with pitch ldx during k-means
   const vers_comm_t* cm = sh.comm;
   const uint32_t W = sh.world, me = sh.rank;
@@ -1458,8 +1556,9 @@ int32_t run_build(vers_ivf* h, const float* X, uint32_t ldx, uint64_t n, const B
   km_timers_collect();
   *out_cost = best;
   if (*out_kept) {
-    if (int32_t rc = h->centroids.reserve(cbytes)) return rc;
-    VERS_HIP_TRY(hipMemcpyAsync(h->centroids.p, bestC.p, cbytes, hipMemcpyDeviceToDevice, st));
+    DevBuf& dst = dst_centroids ? *dst_centroids : h->centroids;  // (vers_ivf_recluster: the handle's centroids stay until its commit point)
+    if (int32_t rc = dst.reserve(cbytes)) return rc;
+    VERS_HIP_TRY(hipMemcpyAsync(dst.p, bestC.p, cbytes, hipMemcpyDeviceToDevice, st));
   }
   VERS_HIP_TRY(hipStreamSynchronize(st));
   return VERS_OK;
@@ -2647,6 +2746,161 @@ int32_t compact_locked(vers_ivf* h, uint64_t* out_before, uint64_t* out_after) {
   if (out_after) *out_after = total;
   return VERS_OK;
 }
+
+// ---- recluster: build_index over the live rows in ascending vec id, the ids kept (see vers_hip.h) ----------------------------------------
+constexpr int kReclusterPhases = 8;
+static double g_rc[kReclusterPhases] = {};  // vers_recluster_phases: calls, live rows, gather, k-means, install, derived arrays, tables (ms), reserved
+
+// Nothing of the handle changes before the COMMIT POINT below: the live rows are gathered into X' beside the index, run_build leaves its
+// centroids in a buffer of the call's, and the new tiles are reserved while the old ones still stand (vers_ivf_compact's order).  A refusal,
+// a NaN distance, a failed allocation and a call that keeps no attempt all return from above that point.
+int32_t recluster_locked(vers_ivf* h, uint64_t num_clusters, uint64_t num_attempts, uint64_t max_iterations, const uint64_t* init_indices,
+                         float* out_centroids, uint64_t c_stride_bytes, uint64_t* out_assignments, float* out_cost, int32_t* out_kept,
+                         uint64_t* out_iterations) {
+  VERS_HIP_TRY(hipDeviceSynchronize());  // searches still in flight on any stream read the storage this call replaces
+  if (h->world > 1) return fail(VERS_ERR_INVALID, "vers_ivf_recluster: the handle is sharded by cluster (the build's exchanges are not wired into this call)");
+  if (h->up.open) return fail(VERS_ERR_EMPTY, "recluster while a streamed upload is in progress: the handle holds no index until vers_ivf_upload_end");
+  if (h->k == 0) return fail(VERS_ERR_EMPTY, "vers_ivf_recluster: the handle holds no centroids");
+  uint64_t m = 0;
+  for (uint32_t c = 0; c < h->k; ++c) m += h->h_len[c];
+  if (m == 0) return fail(VERS_ERR_EMPTY, "vers_ivf_recluster: no live row");
+  if (num_clusters == 0) return fail(VERS_ERR_EMPTY, "vers_ivf_recluster with zero clusters: min_by over no centroids (reference panics)");
+  for (uint64_t i = 0; i < num_attempts * num_clusters; ++i)
+    if (init_indices[i] >= m) return fail(VERS_ERR_INVALID, "vers_ivf_recluster: init index out of range (positions among the live rows, 0 .. m-1)");
+  const uint32_t k_old = h->k, k = (uint32_t)num_clusters, ld = h->ld, ldx = h->ldx;
+  const uint64_t n_total = h->n_total;
+  const hipStream_t st = nullptr;
+  double ph[kReclusterPhases] = {};  // this call's clocks: added to the totals where the call succeeds (a refused call counts nowhere)
+  auto count_call = [&]() {
+    ab_count(0, 1.0, g_rc);
+    ab_count(1, (double)m, g_rc);
+    for (int i = 2; i < kReclusterPhases; ++i) ab_count(i, ph[i], g_rc);
+  };
+  auto no_room = [&](const char* what) -> int32_t {
+    (void)hipGetLastError();
+    return fail(VERS_ERR_HIP, std::string("vers_ivf_recluster: ") + what + " do not fit beside the index; the index is unchanged");
+  };
+  DevBuf live, rank, L, X, dtiles, tmp;
+  {
+    AbClock clk(2, ph);
+    std::vector<GatherJob> tiles;
+    for (uint32_t c = 0; c < k_old; ++c) {
+      if (!h->h_len[c]) continue;
+      const uint32_t nt = (h->h_len[c] + 63u) / 64u;
+      if (h->h_off[c] % 64u || (uint64_t)nt * 64 > h->h_cap[c] || (uint64_t)h->h_off[c] + h->h_cap[c] > h->cap_rows)
+        return fail(VERS_ERR_HIP, "vers_ivf_recluster: a list lies outside its storage (inconsistent index)");
+      for (uint32_t t = 0; t < nt; ++t) tiles.push_back(GatherJob{h->h_off[c] / 64u + t, std::min<uint32_t>(64u, h->h_len[c] - t * 64u)});
+    }
+    const size_t scan_tmp = range_scan_temp_bytes((size_t)n_total + 1);
+    const size_t lds = 64 * (size_t)(kGatherCols4 + 1) * sizeof(f32x4) + 64 * sizeof(uint32_t);
+    if (int32_t rc = scan_prepare_launch(tiles_to_live_rows_kernel, lds)) return rc;
+    if (live.reserve(((size_t)n_total + 1) * sizeof(uint32_t)) != VERS_OK || rank.reserve(((size_t)n_total + 1) * sizeof(uint64_t)) != VERS_OK ||
+        L.reserve((size_t)m * sizeof(uint32_t)) != VERS_OK || tmp.reserve(scan_tmp) != VERS_OK || dtiles.reserve(tiles.size() * sizeof(GatherJob)) != VERS_OK ||
+        X.reserve((size_t)m * ldx * sizeof(float)) != VERS_OK)
+      return no_room("the live rows");
+    // the rank table: a count per vec id (+ one zero: the prefix's last entry is the number of live ids), its exclusive prefix, L
+    VERS_HIP_TRY(hipMemsetAsync(live.p, 0, ((size_t)n_total + 1) * sizeof(uint32_t), st));
+    VERS_HIP_TRY(hipMemcpyAsync(dtiles.p, tiles.data(), tiles.size() * sizeof(GatherJob), hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(recluster_live_kernel, dim3((unsigned)((tiles.size() * 64 + 255) / 256)), dim3(256), 0, st, (const GatherJob*)dtiles.as<GatherJob>(),
+                       (uint32_t)tiles.size(), (const uint32_t*)h->row_ids.as<uint32_t>(), n_total, live.as<uint32_t>());
+    VERS_HIP_TRY(hipGetLastError());
+    if (int32_t rc = range_scan_counts(live.as<uint32_t>(), rank.as<uint64_t>(), (size_t)n_total + 1, tmp.p, scan_tmp, st)) return rc;
+    uint64_t counted = 0;
+    VERS_HIP_TRY(hipMemcpyAsync(&counted, rank.as<uint64_t>() + n_total, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    VERS_HIP_TRY(hipStreamSynchronize(st));
+    if (counted != m) return fail(VERS_ERR_HIP, "vers_ivf_recluster: the lists do not hold as many distinct vec ids as their lengths say (inconsistent index)");
+    hipLaunchKernelGGL(recluster_order_kernel, dim3((unsigned)((n_total + 255) / 256)), dim3(256), 0, st, (const uint32_t*)live.as<uint32_t>(),
+                       (const uint64_t*)rank.as<uint64_t>(), n_total, m, L.as<uint32_t>());
+    hipLaunchKernelGGL(tiles_to_live_rows_kernel, dim3((unsigned)tiles.size()), dim3(256), lds, st, (const float*)h->rows.as<float>(), ld, h->d, ldx,
+                       (const GatherJob*)dtiles.as<GatherJob>(), (const uint32_t*)h->row_ids.as<uint32_t>(), (const uint64_t*)rank.as<uint64_t>(), n_total, m,
+                       X.as<float>());
+    VERS_HIP_TRY(hipGetLastError());
+    if (int32_t rc = clk.done()) return rc;  // (tiles: read by the copy above, finished here)
+  }
+  DevBuf best_assign, newC;
+  float cost = INFINITY;
+  int32_t kept = 0;
+  std::vector<uint64_t> iters(num_attempts ? num_attempts : 1, 0);
+  {
+    AbClock clk(3, ph);
+    BuildShard one;
+    one.n_total = m;
+    if (int32_t rc = run_build(h, X.as<float>(), ldx, m, one, k, num_attempts, max_iterations, init_indices, best_assign, &cost, &kept, iters.data(), st, &newC))
+      return rc;
+    if (int32_t rc = clk.done()) return rc;
+  }
+  auto small_outputs = [&]() {
+    if (out_cost) *out_cost = cost;
+    *out_kept = kept;
+    if (out_iterations)
+      for (uint64_t a = 0; a < num_attempts; ++a) out_iterations[a] = iters[a];
+  };
+  if (!kept) {  // a maintenance call does not destroy what it was asked to improve: the index stays as it is (vers_ivf_build leaves an empty one)
+    small_outputs();
+    count_call();
+    return VERS_OK;
+  }
+  DevBuf sorted, nrows, nids, a64;
+  std::vector<uint32_t> lens, noff, ncap;
+  uint64_t total = 0;
+  {
+    AbClock clk(4, ph);
+    if (int32_t rc = group_for_install(h, m, best_assign.as<uint32_t>(), k, sorted, lens, st)) return rc;
+    if (int32_t rc = plan_capacities(h, lens.data(), k, noff, ncap, &total, true)) return rc;
+    // the old shadow, head and row-major copy go first: they are derived, the new tiles take their room
+    h->shadow_valid = false;
+    h->head_valid = false;
+    h->rows_bf.release();
+    h->rows_h8.release();
+    h->rows_rm.release();
+    if (nrows.reserve((size_t)(total ? total : 1) * ld * sizeof(float)) != VERS_OK || nids.reserve((size_t)(total ? total : 1) * sizeof(uint32_t)) != VERS_OK ||
+        (out_assignments && a64.reserve((size_t)(n_total ? n_total : 1) * 8) != VERS_OK)) {
+      (void)hipGetLastError();
+      nrows.release(); nids.release(); a64.release();
+      if (int32_t rc = refresh_norms(h, 0, h->cap_rows, st)) return rc;  // the old index stays, with its derived arrays back
+      VERS_HIP_TRY(hipStreamSynchronize(st));
+      return no_room("the new tiles");
+    }
+    if (int32_t rc = clk.done()) return rc;
+  }
+  // ---- COMMIT POINT: from here on the handle becomes the new index ----
+  h->flt_moved += 1;  // (prepared filters: every storage row holds another vector, the tables have another k)
+  std::swap(h->rows.p, nrows.p); std::swap(h->rows.cap, nrows.cap);
+  std::swap(h->row_ids.p, nids.p); std::swap(h->row_ids.cap, nids.cap);
+  nrows.release(); nids.release();
+  std::swap(h->centroids.p, newC.p); std::swap(h->centroids.cap, newC.cap);
+  newC.release();
+  {
+    AbClock clk(6, ph);
+    if (int32_t rc = plan_storage(h, lens.data(), k, st)) return rc;  // (rows and row_ids: exactly the bytes reserved above, nothing is allocated)
+    if (int32_t rc = clk.done()) return rc;
+  }
+  {
+    AbClock clk(4, ph);
+    if (int32_t rc = place_rows(h, X.as<float>(), ldx, m, best_assign.as<uint32_t>(), k, sorted, st)) return rc;
+    hipLaunchKernelGGL(recluster_relabel_kernel, dim3((unsigned)((h->cap_rows + 255) / 256)), dim3(256), 0, st, h->row_ids.as<uint32_t>(), h->cap_rows,
+                       (const uint32_t*)L.as<uint32_t>(), m);
+    VERS_HIP_TRY(hipGetLastError());
+    if (int32_t rc = clk.done()) return rc;
+    X.release(); sorted.release(); L.release();  // (before the shadow and the row-major copy are allocated)
+  }
+  {
+    AbClock clk(5, ph);
+    if (int32_t rc = finish_index(h, k, n_total, st)) return rc;  // n_total: assignments.len() does not change
+    if (int32_t rc = clk.done()) return rc;
+  }
+  if (out_centroids)
+    VERS_HIP_TRY(hipMemcpy2D(out_centroids, (size_t)c_stride_bytes, h->centroids.p, (size_t)ldx * 4, (size_t)h->d * 4, k, hipMemcpyDeviceToHost));
+  if (out_assignments && n_total) {
+    hipLaunchKernelGGL(recluster_assign_out_kernel, dim3((unsigned)((n_total + 255) / 256)), dim3(256), 0, st, (const uint32_t*)live.as<uint32_t>(),
+                       (const uint64_t*)rank.as<uint64_t>(), (const uint32_t*)best_assign.as<uint32_t>(), n_total, m, a64.as<uint64_t>());
+    VERS_HIP_TRY(hipGetLastError());
+    VERS_HIP_TRY(hipMemcpy(out_assignments, a64.p, n_total * 8, hipMemcpyDeviceToHost));
+  }
+  small_outputs();
+  count_call();
+  return VERS_OK;
+}
 }  // namespace ivf
 }  // namespace vers
 
@@ -2957,6 +3211,28 @@ int32_t vers_ivf_compact(vers_ivf_t* h, uint64_t* out_rows_before, uint64_t* out
   h->flt_moved += 1;
   DeviceGuard g(h->device);
   return compact_locked(h, out_rows_before, out_rows_after);
+}
+
+int32_t vers_ivf_recluster(vers_ivf_t* h, uint64_t num_clusters, uint64_t num_attempts, uint64_t max_iterations, const uint64_t* init_indices,
+                           float* out_centroids, uint64_t c_stride_bytes, uint64_t* out_assignments, float* out_cost, int32_t* out_kept,
+                           uint64_t* out_iterations) {
+  if (!h) return fail(VERS_ERR_INVALID, "vers_ivf_recluster: null handle");
+  if (!out_kept || (num_attempts && num_clusters && !init_indices) || num_clusters > 0xFFFFFFFFull ||
+      (num_clusters && num_attempts > 0xFFFFFFFFFFFFFFFFull / num_clusters) || (out_centroids && num_clusters && c_stride_bytes < (uint64_t)h->d * 4))
+    return fail(VERS_ERR_INVALID, "vers_ivf_recluster: bad arguments (out_kept is not nullable; c_stride_bytes must be >= 4 d)");
+  std::unique_lock<std::shared_mutex> lk(h->index);
+  DeviceGuard g(h->device);
+  return recluster_locked(h, num_clusters, num_attempts, max_iterations, init_indices, out_centroids, c_stride_bytes, out_assignments, out_cost, out_kept,
+                          out_iterations);
+}
+
+int32_t vers_recluster_phases(double* out, int32_t reset) {
+  std::lock_guard<std::mutex> lk(g_ab_mu);
+  if (out)
+    for (int i = 0; i < kReclusterPhases; ++i) out[i] = g_rc[i];
+  if (reset)
+    for (double& v : g_rc) v = 0.0;
+  return VERS_OK;
 }
 
 int32_t vers_compact_phases(double* out, int32_t reset) {

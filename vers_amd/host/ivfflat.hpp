@@ -173,6 +173,38 @@ class IVFFlatIndex {
     return {before, after};
   }
 
+  // Recluster (extension, vers_ivf_recluster): build_index over the vectors that are in some list, taken in ascending vec id (L), the vec ids
+  // kept.  `init_indices` (optional) are POSITIONS in L, num_attempts * num_clusters of them; without it they are drawn as build_index draws
+  // them.  When an attempt is kept, centroids, assignments (0 for an id in no list), ids and num_centroids follow the call's outputs; values,
+  // assignments.size() and the live count do not change.  When none is kept nothing changes; a refusal throws and nothing changes.
+  // Returns {cost, an attempt was kept}.
+  std::pair<float, bool> recluster(size_t num_clusters, size_t num_attempts, size_t max_iterations, const std::vector<uint64_t>* init_indices = nullptr) {
+    std::vector<size_t> live;
+    for (const auto& l : ids) live.insert(live.end(), l.begin(), l.end());
+    std::sort(live.begin(), live.end());
+    std::vector<uint64_t> draws;
+    if (init_indices) draws = *init_indices;
+    else {
+      std::random_device rd;
+      std::mt19937_64 rng(rd());
+      draws.resize(num_attempts * num_clusters);
+      for (auto& x : draws) x = live.empty() ? 0 : rng() % live.size();
+    }
+    std::vector<Vector<N>> cent(num_clusters);
+    std::vector<uint64_t> asg(assignments.size() ? assignments.size() : 1);
+    float cost = 0; int32_t kept = 0;
+    check(vers_ivf_recluster(handle(), num_clusters, num_attempts, max_iterations, draws.empty() ? nullptr : draws.data(), cent.empty() ? nullptr : cent[0].v,
+                             sizeof(Vector<N>), asg.data(), &cost, &kept, nullptr));
+    if (kept) {
+      num_centroids = num_clusters;
+      centroids = std::move(cent);
+      assignments.assign(asg.begin(), asg.begin() + assignments.size());
+      ids.assign(num_clusters, {});
+      for (size_t v : live) ids[assignments[v]].push_back(v);  // ascending vec id: every list ascending
+    }
+    return {cost, kept != 0};
+  }
+
   // vectors currently in the lists (vers_ivf_live_count)
   size_t live_count() const {
     uint64_t live = 0;

@@ -201,6 +201,40 @@ class IVFFlatIndex:
         check(lib().vers_ivf_compact(self._h, C.byref(before), C.byref(after)))
         return int(before.value), int(after.value)
 
+    # -- recluster (extension): build_index over the live rows in ascending vec id, the vec ids kept -----------------
+    def recluster(self, num_clusters: int, num_attempts: int, max_iterations: int, init_indices=None, rng=None):
+        """vers_ivf_recluster: k-means again over the rows that are in some list, taken in ascending vec id (L); `init_indices`
+        [num_attempts * num_clusters] are POSITIONS in L (drawn as build_index draws them when None).  When an attempt is kept,
+        `centroids`, `assignments` (0 for an id in no list), `ids` and `num_centroids` follow the call's outputs; `values`,
+        len(assignments) and the live count do not change.  When none is kept (num_attempts == 0, no finite cost) nothing changes.
+        A refusal raises and changes nothing.  Returns (cost, kept, iterations)."""
+        n = len(self.assignments)
+        live = np.sort(np.fromiter((v for lst in self.ids for v in lst), dtype=np.int64))
+        if init_indices is None:
+            rng = rng or np.random.default_rng()
+            init_indices = rng.integers(0, max(live.size, 1), size=num_attempts * num_clusters)
+        init = np.ascontiguousarray(np.asarray(init_indices).reshape(-1), dtype=np.uint64)
+        assert init.size == num_attempts * num_clusters
+        cent = np.zeros((max(num_clusters, 1), self.d), dtype=np.float32)
+        asg = np.zeros(max(n, 1), dtype=np.uint64)
+        cost = C.c_float(np.inf); kept = C.c_int32(0)
+        iters = np.zeros(max(num_attempts, 1), dtype=np.uint64)
+        check(lib().vers_ivf_recluster(self._h, num_clusters, num_attempts, max_iterations, _ptr(init) if init.size else None, _ptr(cent), 4 * self.d,
+                                       _ptr(asg), C.byref(cost), C.byref(kept), _ptr(iters)))
+        if kept.value:
+            asg = asg[:n]
+            dead = np.ones(n, dtype=bool)
+            dead[live] = False
+            assert not asg[dead].any()
+            self.num_centroids = int(num_clusters)
+            self.centroids, self.assignments = cent[:num_clusters], asg
+            self.ids = [[] for _ in range(num_clusters)]
+            for v in live.tolist():  # ascending vec id: every list ascending
+                self.ids[int(asg[v])].append(v)
+            self.cost = np.float32(cost.value)
+            self.iterations = iters[:num_attempts]
+        return np.float32(cost.value), int(kept.value), iters[:num_attempts]
+
     def live_count(self):
         live = C.c_uint64(0)
         check(lib().vers_ivf_live_count(self._h, C.byref(live)))
