@@ -477,6 +477,62 @@ int32_t vers_ivf_recluster(vers_ivf_t* h, uint64_t num_clusters, uint64_t num_at
  * nowhere).  out[8]: [0] calls, [1] live rows gathered, [2] the gather (rank table plus rows), [3] k-means, all attempts, [4] install
  * (grouping, reservation, placement, id relabel), [5] derived arrays, [6] tables (the storage plan), [7] reserved.  reset != 0 zeroes them. */
 int32_t vers_recluster_phases(double* out8, int32_t reset);
+/* Fetch (extension: the read side of the five fields -- the reference's callers read `values` and `assignments` directly).  For every i of
+ * the call, with v = vec_ids[i]:
+ *     if v is in some list                 -> out_rows[i] = values[v] (the stored bits, d floats);  out_clusters[i] = assignments[v];  out_status[i] = 0
+ *     if v < n is in no list (removed)     -> the d floats of out_rows[i] = +0.0;  out_clusters[i] = UINT64_MAX;  out_status[i] = 2
+ *                                             (2 is vers_ivf_update_batch's code for the same fact)
+ * This is the call that makes the `values'` of the mutators' specifications observable: after any sequence of add_batch, remove_batch,
+ * update_batch, compact and recluster, a fetch of every id returns the fields of the handle those sentences describe.
+ *   vec_ids      : any order; repeats are allowed (the call is read-only) and every occurrence is answered.
+ *   out_rows     : [n] rows, nullable; pitch as vers_ivf_add_batch: row_stride_bytes >= 4 d (a multiple of 4), resp. ld_floats >= d and a
+ *                  multiple of 4.  Columns d .. pitch - 1 of an output row are NEVER written.
+ *   out_clusters : [n] nullable.    out_status : [n] nullable (0 found, 2 in no list).    A call without rows is the membership query.
+ *   out_counts   : [2] nullable, host memory in both calls: found | in no list.
+ *   ALL OR NOTHING -- every id is checked before the first store: any id >= n of vers_ivf_info -> VERS_ERR_INVALID and no output byte is
+ *                  written; no centroids, or a streamed upload in progress -> VERS_ERR_EMPTY; a handle sharded by cluster (world > 1) ->
+ *                  VERS_ERR_INVALID (whether an id is live is known to its owner alone; not supported yet); more than 2^32 - 1 ids in one
+ *                  _dev call -> VERS_ERR_INVALID.  n == 0: no-op, counts 0.  A NULL handle: VERS_ERR_INVALID before anything else is looked at.
+ *   handle       : taken the way searches take it -- shared with searches and other fetches, excluded by the mutators.
+ *   _dev         : vec_ids_dev and the three outputs are device memory.  The call queues on `stream` and WAITS for it, like
+ *                  vers_ivf_range_search_dev: the host must learn the check's verdict before anything may be written.
+ *   host call    : ids and rows are staged through bounded pinned buffers in chunks of option "add_batch_rows" ids (without out_rows:
+ *                  "remove_batch_ids"); n rows are never held on the device.
+ *   sources      : the row-major copy where the handle has one (a wave per row, whole sectors); otherwise the f32 tiles alone, the requests
+ *                  ordered by storage row, one job per touched tile (option "fetch_lds_min": requests per tile from which the tile is
+ *                  turned through LDS instead of read piece by piece).  Same bits either way.
+ *   memory       : the first fetch allocates a vec id -> storage row map of 4 bytes per vec id on the handle (freed by vers_ivf_destroy).  It
+ *                  is read-side state like a prepared filter: rebuilt after anything that moved rows, extended after an add into list slack,
+ *                  valid as it is otherwise.  Optional memory: when it does not fit (or option "fetch_map" = 0) every call builds a
+ *                  table of its own requests instead, with the same results. */
+int32_t vers_ivf_fetch(vers_ivf_t* h, const uint64_t* vec_ids, uint64_t n, float* out_rows, uint64_t row_stride_bytes, uint64_t* out_clusters,
+                       uint8_t* out_status, uint64_t* out_counts);
+int32_t vers_ivf_fetch_dev(vers_ivf_t* h, const uint64_t* vec_ids_dev, uint64_t n, float* out_rows_dev, uint64_t ld_floats, uint64_t* out_clusters_dev,
+                           uint8_t* out_status_dev, uint64_t* out_counts, void* stream);
+/* The fetch calls of this process by PHASE (host wall clock in ms, the call's stream synchronised at each phase's end; a refused call counts
+ * nowhere).  out[8]: [0] calls, [1] ids passed, [2] ids found, [3] staging of the ids, [4] map build or refresh (0 when the cached map was
+ * valid), [5] check + gather, [6] copy out, [7] reserved.  reset != 0 zeroes them. */
+int32_t vers_fetch_phases(double* out8, int32_t reset);
+/* Search by stored id ("more like this"; extension).  flags == 0: row q is, bit for bit, row q of vers_ivf_search[_dev] with
+ * queries[q] = values[vec_ids[q]] at the same top_k and nprobe, the reference's mode nprobe == 0 included.  The queries never leave the
+ * device: they are fetched into the call's workspace at the query pitch.
+ *   VERS_BYID_EXCLUDE_SELF : row q is, bit for bit, that search on an index from which vec_ids[q] ALONE was removed.  In the order of
+ *                  nprobe >= 1 -- one global stable order -- that is EXACTLY: SEARCH top_k + 1, DROP THE ENTRY WHOSE ID IS vec_ids[q] IF IT
+ *                  IS THERE AND THE LAST ENTRY OTHERWISE, out_count[q] = min(count, top_k) of what is left.  It holds wherever the row's
+ *                  own list ranks (after vers_ivf_upload with assignments of the caller's choice that need not be rank 0, nor within the
+ *                  probe at all).  With nprobe == 0 the flag is refused: the reference's spill walk over per-list remainders has no such
+ *                  identity.
+ *   refusals     : all decided before anything is written -- VERS_ERR_INVALID for unknown flag bits, the flag with nprobe == 0, any
+ *                  id >= n, any id that is in no list (vers_ivf_fetch tells which), a handle sharded by cluster; the search's own
+ *                  refusals unchanged (no centroids: VERS_ERR_INSUFFICIENT).  A NULL handle: VERS_ERR_INVALID before anything else.
+ *   _dev         : after the id check -- one status word read back, for which the call waits on `stream` -- the protocol of
+ *                  vers_ivf_search_dev exactly: results after the stream's work, status through vers_ivf_poll.
+ *   host call    : the ids go up, the results come down; reference mode retries deeper as vers_ivf_search does. */
+#define VERS_BYID_EXCLUDE_SELF 1u
+int32_t vers_ivf_search_by_id(vers_ivf_t* h, const uint64_t* vec_ids, uint32_t b, uint32_t top_k, uint32_t nprobe, uint32_t flags, uint64_t* out_ids,
+                              float* out_dist, uint32_t* out_count);
+int32_t vers_ivf_search_by_id_dev(vers_ivf_t* h, const uint64_t* vec_ids_dev, uint32_t b, uint32_t top_k, uint32_t nprobe, uint32_t flags,
+                                  uint64_t* out_ids_dev, float* out_dist_dev, uint32_t* out_count_dev, void* stream);
 /* Range search (extension; the reference has search_approximate only).  In the reference's terms: for query q, rank the lists as
  * search_approximate does (ivfflat.rs:155-161: first minimum, stable), take the P = min(nprobe, k) nearest, and return EVERY row of
  * `ids[c]` of those lists whose distance D(q, values[id]) -- the index's metric, the reference's bits: sequential f32, multiply and add
@@ -907,6 +963,9 @@ int32_t vers_ivf_range_search_exhaustive_sharded_dev(vers_ivf_t* h, const vers_c
  *                       DESIGN.md section 5.  "seg_rows", when non-zero, also fixes the row-segment length of the two exhaustive range
  *                       scans (vers_flat_range_search, vers_ivf_range_search_exhaustive), rounded up to 64 and capped at what one buffer
  *                       descriptor addresses; vers_flat_search and vers_ivf_search_exhaustive keep their own sizing.
+ *   "fetch_lds_min" (64; never for rows of more than 256 columns) requests for one 64-row tile from which vers_ivf_fetch's tile gather
+ *                       turns the whole tile through LDS instead of reading the wanted rows' 16-byte pieces directly (1 = always, above 64 = never).  "fetch_map" (1): 0 = no vec id ->
+ *                       storage row map on the handle, every fetch builds a table of its own requests (what a failed allocation does).
  *   "scan_debug" (0), "poison_alloc" (-1), "poison_slack_bits" (-1), "test_fail_sharded" (0)   diagnosis: phase stamps / skipped
  *                       phases, new device buffers filled with a byte, slack rows filled with an f32 bit pattern, the next n sharded
  *                       searches fail locally. */

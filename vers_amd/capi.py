@@ -13,6 +13,9 @@ LIB_PATH = os.environ.get("VERS_LIB_PATH") or os.path.join(_HERE, "lib", "libver
 
 OK, ERR_INVALID, ERR_NAN, ERR_INSUFFICIENT, ERR_HIP, ERR_EMPTY, ERR_COMM = 0, 1, 2, 3, 4, 5, 6
 RANGE_WALK_ORDER = 1
+BYID_EXCLUDE_SELF = 1  # VERS_BYID_EXCLUDE_SELF
+FETCH_FOUND, FETCH_IN_NO_LIST = 0, 2  # out_status of vers_ivf_fetch (2: vers_ivf_update_batch's code for the same fact)
+NO_CLUSTER = 0xFFFFFFFFFFFFFFFF  # out_clusters of an id in no list
 METRIC_L2SQ, METRIC_COSDIST = 0, 1
 MAX_TOPK = 64
 
@@ -112,6 +115,11 @@ SIGNATURES = {
     "vers_ivf_recluster": (C.c_int32, [_vp, C.c_uint64, C.c_uint64, C.c_uint64, _vp, _vp, C.c_uint64, _vp, C.POINTER(C.c_float), C.POINTER(C.c_int32),
                                        _vp]),
     "vers_recluster_phases": (C.c_int32, [C.POINTER(C.c_double), C.c_int32]),
+    "vers_ivf_fetch": (C.c_int32, [_vp, _vp, C.c_uint64, _vp, C.c_uint64, _vp, _vp, C.POINTER(C.c_uint64)]),
+    "vers_ivf_fetch_dev": (C.c_int32, [_vp, _vp, C.c_uint64, _vp, C.c_uint64, _vp, _vp, C.POINTER(C.c_uint64), _vp]),
+    "vers_fetch_phases": (C.c_int32, [C.POINTER(C.c_double), C.c_int32]),
+    "vers_ivf_search_by_id": (C.c_int32, [_vp, _vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _vp, _vp, _vp]),
+    "vers_ivf_search_by_id_dev": (C.c_int32, [_vp, _vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _vp, _vp, _vp, _vp]),
     "vers_ivf_range_search": (C.c_int32, [_vp, _vp, C.c_uint64, C.c_uint32, _vp, C.c_uint32, C.c_uint32, _vp, _vp, _vp, C.c_uint64,
                                           C.POINTER(C.c_uint64)]),
     "vers_ivf_range_search_dev": (C.c_int32, [_vp, _vp, C.c_uint64, C.c_uint32, _vp, C.c_uint32, C.c_uint32, _vp, _vp, _vp, C.c_uint64,
@@ -523,6 +531,14 @@ def recluster_phases(reset=False) -> dict:
     v = (C.c_double * 8)()
     check(lib().vers_recluster_phases(v, 1 if reset else 0))
     keys = ("calls", "rows", "gather_ms", "kmeans_ms", "install_ms", "derive_ms", "tables_ms", "reserved")
+    return dict(zip(keys, (float(x) for x in v)))
+
+
+def fetch_phases(reset=False) -> dict:
+    """The fetch calls of this process by phase, host wall clock in ms (vers_fetch_phases); map_ms is 0 when the cached map was valid."""
+    v = (C.c_double * 8)()
+    check(lib().vers_fetch_phases(v, 1 if reset else 0))
+    keys = ("calls", "ids", "found", "stage_ms", "map_ms", "gather_ms", "copy_ms", "reserved")
     return dict(zip(keys, (float(x) for x in v)))
 
 

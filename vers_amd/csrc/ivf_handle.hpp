@@ -86,6 +86,10 @@ struct SearchWs {
   bool no_ahead = false;  // the plan of a filtered call neither consumes a look-ahead slot nor touches a pending request (plan_search)
   DevBuf rg_rlims;  // sharded range search: every rank's CSR limits [world][b + 1] (range_merge.hip.h); the gather itself goes through g_send / g_recv
   DevBuf g_send, g_recv;  // sharded search without the host in the loop: this rank's [2][b][top_k] partial | the world's
+  // vers_ivf_fetch / vers_ivf_search_by_id (ivf_fetch.hip): the call's storage row per request | its (storage row, request) pairs before and
+  // after the sort | the tile jobs' heads, their prefix and first requests | the call's counters | rocPRIM's temp | the staged chunk of a
+  // host-pointer call (ids, rows, clusters, status) | the fetched queries [b][ldq] and the top_k + 1 results of a search by id
+  DevBuf ft_src, ft_pairs, ft_heads, ft_base, ft_jobs, ft_misc, ft_tmp, ft_stage, ft_q, ft_res;
   DevBuf g_cnt;  // an adaptive filtered call on a sharded handle: this rank's allowed counts [n] | the world's [world][n] | their sum [n], u32
   bool g_poisoned = false;  // g_send holds the poison mark of a locally failed batch (cleared before the next partial is written)
   static constexpr uint32_t kEvRing = 64;  // scan-launch timing ring (measurement hook)
@@ -272,6 +276,20 @@ struct vers_ivf {
   // moved, so the masks and allowed_len of a prepared filter are still right.
   std::vector<vers_filter*> filters;
   uint64_t flt_moved = 0, flt_appended = 0;
+  // vers_ivf_fetch (ivf_fetch.hip): the vec id -> storage row map, READ-SIDE state like the prepared filters': made at the first fetch, brought
+  // up to date against flt_moved / flt_appended at the start of a fetch (fetch_plan.hpp decides how), freed with the handle.  Everything
+  // below `mu` is read and written under it; a refresh has finished on the device before `mu` is released.  No mutator touches it.
+  struct FetchMap {
+    std::mutex mu;
+    DevBuf row_of;     // u32 [cap_ids]: the storage row of a vec id, 0xFFFFFFFF = in no list
+    uint64_t cap_ids = 0;
+    bool built = false;
+    uint64_t seen_moved = 0, seen_appended = 0;
+    uint64_t snap_n_total = 0;       // the next vec id add would have handed out when the map was last brought up to date
+    std::vector<uint32_t> snap_len;  // h_len then
+    DevBuf jobs;                     // the refresh's tile jobs
+    uint64_t builds = 0, tails = 0, hits = 0;
+  } fm;
   DevBuf prune_ctr;  // u64 [3] steps executed | steps without math | tiles abandoned by the list scan's early abandon, over the handle's life
   // fp16 shadow of the rows for the matrix-core pre-selection (+50 % corpus memory; VERS_SHADOW=0 or a failed
   // allocation: the f32 rows feed it).  The wider certificate window makes it sensitive to data with many near-ties:

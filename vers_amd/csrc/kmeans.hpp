@@ -20,6 +20,10 @@ int32_t range_sort_segments(const uint64_t* keys_in, uint64_t* keys_out, const u
 size_t range_sort_keys_temp_bytes(uint32_t n, uint32_t segments);  // keys alone
 int32_t range_sort_segment_keys(const uint64_t* keys_in, uint64_t* keys_out, uint32_t n, uint32_t segments, const uint64_t* lims, void* temp,
                                 size_t temp_bytes, hipStream_t st);
+// vers_ivf_fetch: ascending stable sort of (u32 key, u32 value) pairs over the keys' low `bits` bits
+size_t fetch_sort_temp_bytes(size_t n);
+int32_t fetch_sort_pairs(const uint32_t* keys_in, uint32_t* keys_out, const uint32_t* vals_in, uint32_t* vals_out, size_t n, void* temp, size_t temp_bytes,
+                         hipStream_t st);
 
 // ---- kmeans.hip ---------------------------------------------------------------------
 // Simple owning device buffer (grow-only).

@@ -85,4 +85,18 @@ int32_t range_sort_segment_keys(const uint64_t* keys_in, uint64_t* keys_out, uin
   return VERS_OK;
 }
 
+// ---- vers_ivf_fetch: the requests ordered by storage row (or, without the id map, by vec id) -----------------------------------------
+size_t fetch_sort_temp_bytes(size_t n) {
+  size_t bytes = 0;
+  (void)rocprim::radix_sort_pairs(nullptr, bytes, (const uint32_t*)nullptr, (uint32_t*)nullptr, (const uint32_t*)nullptr, (uint32_t*)nullptr, n, 0u, 32u,
+                                  (hipStream_t) nullptr);
+  return bytes + 256;
+}
+int32_t fetch_sort_pairs(const uint32_t* keys_in, uint32_t* keys_out, const uint32_t* vals_in, uint32_t* vals_out, size_t n, void* temp, size_t temp_bytes,
+                         hipStream_t st) {
+  if (n == 0) return VERS_OK;
+  VERS_HIP_TRY(rocprim::radix_sort_pairs(temp, temp_bytes, keys_in, keys_out, vals_in, vals_out, n, 0u, 32u, st));
+  return VERS_OK;
+}
+
 }  // namespace vers

@@ -205,6 +205,44 @@ class IVFFlatIndex {
     return {cost, kept != 0};
   }
 
+  // Fetch (extension, vers_ivf_fetch): what the DEVICE holds under each listed vec id -- the stored vector, its cluster and a status (0 found,
+  // 2 in no list: the vector is zeros, the cluster SIZE_MAX).  Any order, repeats allowed.  An id >= assignments.size() throws and nothing
+  // is written.  The rows arrive with the pitch of Vec<Vector<N>>; the padding behind N floats is left as it is.
+  struct Fetched {
+    std::vector<Vector<N>> rows;
+    std::vector<size_t> clusters;
+    std::vector<uint8_t> status;
+    size_t found = 0, in_no_list = 0;
+  };
+  Fetched fetch(const std::vector<size_t>& vec_ids) const {
+    const size_t n = vec_ids.size();
+    std::vector<uint64_t> v(vec_ids.begin(), vec_ids.end()), cl(n ? n : 1);
+    Fetched f;
+    f.rows.resize(n);
+    f.status.resize(n ? n : 1);
+    uint64_t counts[2] = {0, 0};
+    check(vers_ivf_fetch(handle(), v.data(), n, n ? f.rows[0].v : nullptr, sizeof(Vector<N>), cl.data(), f.status.data(), counts));
+    f.status.resize(n);
+    f.clusters.assign(cl.begin(), cl.begin() + n);
+    f.found = (size_t)counts[0];
+    f.in_no_list = (size_t)counts[1];
+    return f;
+  }
+
+  // Search by stored id (extension, vers_ivf_search_by_id): search with values[vec_id] as the query, which never leaves the device.
+  // nprobe == 0: search_approximate's own semantics; exclude_self (nprobe >= 1): the result on the index without vec_id itself.  An id that
+  // is in no list throws.
+  std::vector<std::pair<size_t, float>> search_by_id(size_t vec_id, size_t top_k, size_t nprobe = 0, bool exclude_self = false) const {
+    std::vector<uint64_t> oi(top_k ? top_k : 1);
+    std::vector<float> od(top_k ? top_k : 1);
+    uint32_t cnt = 0;
+    const uint64_t v = vec_id;
+    check(vers_ivf_search_by_id(handle(), &v, 1, (uint32_t)top_k, (uint32_t)nprobe, exclude_self ? VERS_BYID_EXCLUDE_SELF : 0u, oi.data(), od.data(), &cnt));
+    std::vector<std::pair<size_t, float>> out;
+    for (uint32_t i = 0; i < cnt; ++i) out.emplace_back((size_t)oi[i], od[i]);
+    return out;
+  }
+
   // vectors currently in the lists (vers_ivf_live_count)
   size_t live_count() const {
     uint64_t live = 0;

@@ -240,6 +240,77 @@ class IVFFlatIndex:
         check(lib().vers_ivf_live_count(self._h, C.byref(live)))
         return int(live.value)
 
+    # -- fetch (extension): the stored vector, its list and whether it is still there, by vec id --------------------
+    def fetch(self, vec_ids, want_rows: bool = True, row_stride_floats=None, fill=None):
+        """vers_ivf_fetch: for every v of `vec_ids` (any order, repeats allowed) the stored vector, its cluster and a status -- 0 found,
+        2 in no list (then the row is zeros and the cluster capi.NO_CLUSTER).  An id >= len(assignments) raises and writes nothing.
+        row_stride_floats / fill: the rows come back in a [n, stride] array prefilled with `fill` (columns >= d are never written).
+        -> (rows [n, d or stride] f32 or None, clusters [n] u64, status [n] u8); the counts are left in last_fetch_counts."""
+        v = np.ascontiguousarray(np.asarray(vec_ids, dtype=np.uint64).reshape(-1))
+        n = v.size
+        stride = self.d if row_stride_floats is None else int(row_stride_floats)
+        rows = np.full((max(n, 1), stride), 0.0 if fill is None else fill, dtype=np.float32) if want_rows else None
+        cl = np.zeros(max(n, 1), dtype=np.uint64)
+        st = np.zeros(max(n, 1), dtype=np.uint8)
+        counts = np.zeros(2, dtype=np.uint64)
+        check(lib().vers_ivf_fetch(self._h, _ptr(v) if n else None, n, _ptr(rows) if want_rows else None, 4 * stride, _ptr(cl), _ptr(st),
+                                   counts.ctypes.data_as(C.POINTER(C.c_uint64))))
+        self.last_fetch_counts = (int(counts[0]), int(counts[1]))
+        return (rows[:n] if want_rows else None), cl[:n], st[:n]
+
+    def fetch_dev(self, ids_ptr: int, n: int, rows_ptr: int = 0, ld: int = 0, clusters_ptr: int = 0, status_ptr: int = 0, stream: int = 0):
+        """vers_ivf_fetch_dev on device arrays: u64 vec ids in; rows [n][ld] f32, clusters (u64), status (u8) out, each optional.  Queued on
+        `stream` and waited for.  Returns (found, in no list)."""
+        counts = np.zeros(2, dtype=np.uint64)
+        check(lib().vers_ivf_fetch_dev(self._h, _vp(ids_ptr) if n else None, n, _vp(rows_ptr) if rows_ptr else None, ld, _vp(clusters_ptr) if clusters_ptr else None,
+                                       _vp(status_ptr) if status_ptr else None, counts.ctypes.data_as(C.POINTER(C.c_uint64)), _vp(stream)))
+        return int(counts[0]), int(counts[1])
+
+    def search_by_id(self, vec_ids, top_k: int, nprobe: int = 0, exclude_self: bool = False):
+        """search_batch(values[vec_ids], top_k, nprobe) without the queries leaving the device (vers_ivf_search_by_id).  exclude_self
+        (nprobe >= 1): each row as on an index from which its own id alone was removed.  An id that is in no list raises."""
+        v = np.ascontiguousarray(np.asarray(vec_ids, dtype=np.uint64).reshape(-1))
+        b = v.size
+        ids = np.zeros((b, max(top_k, 1)), dtype=np.uint64)
+        dist = np.zeros((b, max(top_k, 1)), dtype=np.float32)
+        cnt = np.zeros(max(b, 1), dtype=np.uint32)
+        check(lib().vers_ivf_search_by_id(self._h, _ptr(v) if b else None, b, top_k, nprobe, capi.BYID_EXCLUDE_SELF if exclude_self else 0, _ptr(ids), _ptr(dist),
+                                          _ptr(cnt)))
+        return ids[:, :top_k], dist[:, :top_k], cnt[:b]
+
+    def search_by_id_dev(self, ids_in_ptr: int, b: int, top_k: int, nprobe: int, ids_ptr: int, dist_ptr: int, cnt_ptr: int, exclude_self: bool = False,
+                         stream: int = 0, flags=None):
+        """vers_ivf_search_by_id_dev on raw device pointers; after the id check it is search_dev's protocol: poll() reports."""
+        f = (capi.BYID_EXCLUDE_SELF if exclude_self else 0) if flags is None else int(flags)
+        check(lib().vers_ivf_search_by_id_dev(self._h, _vp(ids_in_ptr) if b else None, b, top_k, nprobe, f, _vp(ids_ptr), _vp(dist_ptr), _vp(cnt_ptr), _vp(stream)))
+
+    def sync_from_device(self, chunk: int = 1 << 16):
+        """Rebuilds the host fields from the handle -- what a process that used the _dev mutators (which do not mirror) needs before
+        save_index.  Ids 0 .. n-1 are fetched in chunks: `values[v]` and `assignments[v]` are replaced for every id that is in a list;
+        entries of ids in no list keep what the mirror held (nothing observable depends on them), zeros / 0 beyond the mirror's length;
+        `ids[c]` = the ascending found ids of cluster c; `centroids` through vers_ivf_get_centroids.  Returns (found, in no list)."""
+        n, k, _ = self.info()
+        values = np.zeros((n, self.d), dtype=np.float32)
+        assignments = np.zeros(n, dtype=np.uint64)
+        keep = min(n, len(self.assignments), len(self.values))
+        values[:keep] = self.values[:keep]
+        assignments[:keep] = self.assignments[:keep]
+        found_mask = np.zeros(n, dtype=bool)
+        for v0 in range(0, n, max(1, int(chunk))):
+            v1 = min(n, v0 + max(1, int(chunk)))
+            rows, cl, st = self.fetch(np.arange(v0, v1, dtype=np.uint64))
+            ok = st == capi.FETCH_FOUND
+            values[v0:v1][ok] = rows[ok]
+            assignments[v0:v1][ok] = cl[ok]
+            found_mask[v0:v1] = ok
+        self.values, self.assignments = values, assignments
+        self.num_centroids = int(k)
+        self.centroids = self.get_centroids()
+        self.ids = [[] for _ in range(int(k))]
+        for v in np.flatnonzero(found_mask).tolist():  # ascending vec id: every list ascending
+            self.ids[int(assignments[v])].append(v)
+        return int(found_mask.sum()), int(n - found_mask.sum())
+
     # -- Index::search_approximate (ivfflat.rs:153-198) ---------------------------------------------
     def search_approximate(self, query, top_k: int):
         ids, dist, cnt = self.search_batch(np.asarray(query, dtype=np.float32).reshape(1, self.d), top_k, nprobe=0)
