@@ -511,7 +511,7 @@ int32_t vers_ivf_fetch_dev(vers_ivf_t* h, const uint64_t* vec_ids_dev, uint64_t 
                            uint8_t* out_status_dev, uint64_t* out_counts, void* stream);
 /* The fetch calls of this process by PHASE (host wall clock in ms, the call's stream synchronised at each phase's end; a refused call counts
  * nowhere).  out[8]: [0] calls, [1] ids passed, [2] ids found, [3] staging of the ids, [4] map build or refresh (0 when the cached map was
- * valid), [5] check + gather, [6] copy out, [7] reserved.  reset != 0 zeroes them. */
+ * valid), [5] check + gather, [6] copy out, [7] time inside the callbacks of vers_ivf_fetch_sharded_dev.  reset != 0 zeroes them. */
 int32_t vers_fetch_phases(double* out8, int32_t reset);
 /* Search by stored id ("more like this"; extension).  flags == 0: row q is, bit for bit, row q of vers_ivf_search[_dev] with
  * queries[q] = values[vec_ids[q]] at the same top_k and nprobe, the reference's mode nprobe == 0 included.  The queries never leave the
@@ -1019,6 +1019,58 @@ int32_t vers_ivf_search_exhaustive_sharded_dev(vers_ivf_t* h, const vers_gather_
                                                uint64_t ldq_floats, uint32_t b, uint32_t top_k, uint32_t metric,
                                                uint64_t* out_ids_dev, float* out_dist_dev, uint32_t* out_count_dev,
                                                void* stream);
+
+/* ---- UPDATE, FETCH and SEARCH BY ID on handles SHARDED BY CLUSTER ---------------------------------------------------------------------
+ * vers_ivf_update_batch[_dev], vers_ivf_fetch[_dev] and vers_ivf_search_by_id[_dev] refuse a sharded handle (world > 1); these three take
+ * one.  They have no semantics of their own: EVERY rank calls with the same ids (and, for the update, the same rows), exactly as the sharded
+ * vers_ivf_add_batch and vers_ivf_remove_batch_dev are called, and every rank receives, bit for bit, what the matching _dev call returns on
+ * the UNSHARDED index holding the same five fields -- but out_counts[3] of the update: storage re-layouts are this rank's own, 0 or 1.
+ * comm == NULL (and g == NULL) on an unsharded handle: the call IS the existing _dev call.
+ *   the "where" round : whether an id is live, and in which list, is known to the list's owner alone.  ONE comm->all_gather of 4 * (n + 1)
+ *              bytes per rank, shared by the three calls: word i = the cluster (< k) of vec_ids[i] if this rank stores it in a list, else
+ *              0xFFFFFFFF; word n = this rank's local status (0, or the VERS_ERR_* of a local failure such as scratch that did not fit;
+ *              option "test_fail_sharded" injects one).  It is the agreement round, as in vers_ivf_range_search_sharded_dev: if any rank's
+ *              status word is non-zero every rank returns the first failing rank's status, nothing written, no further exchange.  An id
+ *              claimed by two ranks, or by a rank that does not own the claimed list: VERS_ERR_HIP (inconsistent index), nothing written.
+ *   before any exchange, the same on every rank, 0 callbacks, outputs and index untouched: every refusal of the unsharded call that
+ *              follows from the arguments, the centroids or n (an id >= n, a duplicate id or a NaN distance of the update, no centroids, a
+ *              streamed upload in progress, unknown flags, VERS_BYID_EXCLUDE_SELF with nprobe == 0), a comm / g whose rank or world
+ *              disagree with the handle, world > 1 with a NULL comm.
+ *   fetch    : after the where round every rank knows each request's cluster, status and owner; a call without out_rows_dev ends there
+ *              (1 callback).  Rows travel in chunks of option "add_batch_rows" requests: for chunk j every rank sends the rows it found
+ *              among requests [jR, (j+1)R), packed in request order at a pitch of exactly d floats and padded to the largest rank's count
+ *              of that chunk -- ONE all_gather per chunk, a chunk in which no rank found anything is skipped: 1 + (non-empty chunks)
+ *              callbacks per call.  A device kernel places the rows; a request in no list gets d zeros; columns d .. ld_floats - 1 are
+ *              never written.  Synchronous like vers_ivf_fetch_dev; takes the handle shared.  vers_fetch_phases [7] = time in callbacks.
+ *              A failure of this rank AFTER the where round (scratch for a chunk that does not fit) has no round left to be told in:
+ *              the peers are inside their callback and the host aborts the group, as for the sharded mutators.
+ *   update   : mark, assign, the local pass over the stored rows, the where round, then a resolve pass over the gathered table, from
+ *              which every rank derives the same status per row (stayed: old cluster == new; moved; skipped: no claimer) and the same
+ *              per-list out / in counts, hence the same new GLOBAL lengths.  The owner of a row that stays overwrites it in place; the
+ *              owner of a list that loses rows compacts it; the owner of a list that gains rows merges the movers in from the CALL's
+ *              rows at their sorted places (every rank is handed the rows anyway: no row crosses ranks) and, when an owned list outgrows
+ *              its capacity, re-lays out its own storage.  Afterwards every handle is what vers_ivf_set_shard + vers_ivf_upload of the
+ *              updated fields + removal of the ids in no list would hold.  The first byte of the index is written after the agreement:
+ *              ONE callback per call.  A failure after it has no round left to be told in: the host aborts the group, as for the other
+ *              sharded mutators.  Synchronous; holds the handle exclusively.  The exchange is counted in vers_update_phases [6].  Prepared
+ *              filters and fetch maps refresh on EVERY rank when anything moved anywhere.
+ *   search by id : the where round over the b ids (an id in no list on any rank: VERS_ERR_INVALID on every rank after that one callback,
+ *              nothing written), one row round that puts the query block into the call's workspace on every rank, then
+ *              vers_ivf_search_sharded_dev unchanged (for VERS_BYID_EXCLUDE_SELF at top_k + 1, the own id dropped behind it): from there
+ *              on results after the stream's work, status through vers_ivf_poll.  The call gives the handle back between the row round
+ *              and the search: a mutator that was waiting runs in that gap, and the search then sees the index AFTER it (with the flag, a
+ *              query id removed in the gap is no longer there and the last entry goes in its place).  Ranks issue their calls in one
+ *              order, so every rank sees the same; a host that needs the search on the index the rows were read from does not mutate
+ *              concurrently. */
+int32_t vers_ivf_fetch_sharded_dev(vers_ivf_t* h, const vers_comm_t* comm /* NULL = world 1 */, const uint64_t* vec_ids_dev, uint64_t n,
+                                   float* out_rows_dev, uint64_t ld_floats, uint64_t* out_clusters_dev, uint8_t* out_status_dev,
+                                   uint64_t* out_counts /* host [2] */, void* stream);
+int32_t vers_ivf_update_batch_sharded_dev(vers_ivf_t* h, const vers_comm_t* comm /* NULL = world 1 */, const uint64_t* vec_ids_dev,
+                                          const float* rows_dev, uint64_t n, uint64_t ld_floats, uint64_t* out_clusters_dev,
+                                          uint8_t* out_status_dev, uint64_t* out_counts /* host [4] */);
+int32_t vers_ivf_search_by_id_sharded_dev(vers_ivf_t* h, const vers_comm_t* comm, const vers_gather_t* g /* both NULL = world 1 */,
+                                          const uint64_t* vec_ids_dev, uint32_t b, uint32_t top_k, uint32_t nprobe, uint32_t flags,
+                                          uint64_t* out_ids_dev, float* out_dist_dev, uint32_t* out_count_dev, void* stream);
 
 /* ---- FILTERED search on handles SHARDED BY CLUSTER: partials, the merges' input, and the calls end to end ---------------------------
  * The filtered calls above refuse a sharded handle (world > 1); these nine take one.

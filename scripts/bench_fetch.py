@@ -21,6 +21,7 @@ Default index: N = 1M, d = 128, nlist = 1024; `--rows 10000000 --d 768 --nlist 4
     python scripts/bench_fetch.py
     python scripts/bench_fetch.py --sweep --rows 200000 --d 768 --nlist 256
     python scripts/bench_fetch.py --yardsticks --root /path/to/parent/checkout
+    python scripts/bench_fetch.py --shards 4      (vers_ivf_fetch_sharded_dev, the ranks emulated on this GPU; the exchange is not measured)
 """
 from __future__ import annotations
 
@@ -46,6 +47,7 @@ def main():
     ap.add_argument("--kmeans-iters", type=int, default=2)
     ap.add_argument("--takes", type=int, default=3)
     ap.add_argument("--sweep", action="store_true", help="the crossover of the tile gather's two forms only")
+    ap.add_argument("--shards", type=int, default=0, help="W ranks emulated on this GPU: vers_ivf_fetch_sharded_dev, time outside the (answered) callbacks")
     ap.add_argument("--yardsticks", action="store_true", help="the calls that existed before fetch, only")
     ap.add_argument("--root", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))), help="the checkout to import vers_amd and tests from")
     args = ap.parse_args()
@@ -163,6 +165,97 @@ def main():
         wins = [w for w, r in table.items() if r["lds_ms"] < r["direct_ms"]]
         line["sweep"] = table
         line["T_smallest_count_where_lds_wins"] = min(wins) if wins else None
+        ix.close()
+        print(json.dumps(line), flush=True)
+        return 0
+
+    if args.shards:
+        # W ranks EMULATED on this one GPU: W handles, each keeping its own lists of the same index; every rank's all_gather is answered from
+        # tables made on the device from the unsharded index (where words from its clusters / status and owners(), row chunks from its rows).
+        # Reported: the slowest rank's time OUTSIDE callbacks, the bytes each exchange would carry, the unsharded call in the same run.  The
+        # exchange itself, and any run on more than one physical GPU, is NOT measured.
+        from vers_amd.dist import _AG, VersComm, _Mem
+
+        class _Ptr:   # what IVFFlatIndex.fetch_sharded_dev takes: something with ptr()
+            def __init__(self, p):
+                self.p = p
+
+            def ptr(self):
+                return self.p
+        W_ = args.shards
+        ix = build()
+        every = torch.arange(n, dtype=torch.int64, device="cuda")
+        cl = torch.zeros(n, dtype=torch.int64, device="cuda"); st = torch.zeros(n, dtype=torch.uint8, device="cuda")
+        rows = torch.empty(n, ld, dtype=torch.float32, device="cuda")
+        ix.fetch_dev(every.data_ptr(), n, rows.data_ptr(), ld, cl.data_ptr(), st.data_ptr())
+        assert bool((st == 0).all())   # (a fresh build: every id is in a list)
+        cent = torch.zeros(nlist, ld, dtype=torch.float32, device="cuda")
+        cent[:, :d] = torch.from_numpy(np.ascontiguousarray(ix.get_centroids())).cuda()
+        shards = []
+        for r in range(W_):
+            sx = IVFFlatIndex(d)
+            sx.set_shard(r, W_)
+            sx.upload_dev(rows.data_ptr(), n, ld, cent.data_ptr(), nlist, ld, cl.data_ptr())
+            shards.append(sx)
+        owners = torch.from_numpy(shards[0].owners().astype(np.int64)).cuda()
+        R = 131072
+
+        def answers(ids_dev):
+            m = ids_dev.numel()
+            c, who = cl[ids_dev], owners[cl[ids_dev]]
+            where = torch.full((W_, m + 1), -1, dtype=torch.int32, device="cuda")
+            where[:, m] = 0
+            where[who, torch.arange(m, device="cuda")] = c.to(torch.int32)
+            out_t = [where.view(torch.uint8).reshape(-1)]
+            for i0 in range(0, m, R):
+                sl = slice(i0, min(m, i0 + R))
+                per = [ids_dev[sl][who[sl] == r] for r in range(W_)]
+                pad = max(int(p.numel()) for p in per)
+                buf = torch.zeros((W_, pad, d), dtype=torch.float32, device="cuda")
+                for r in range(W_):
+                    buf[r, :per[r].numel()] = rows[per[r], :d]
+                out_t.append(buf.view(torch.uint8).reshape(-1))
+            return out_t
+
+        res = {"shards": W_, "note": "ranks emulated on one GPU, callbacks answered from the unsharded index; the exchange itself is not measured"}
+        out = torch.empty(n, ld, dtype=torch.float32, device="cuda")
+        for name, ids in (("all_ids", np.arange(n, dtype=np.int64)), ("random_1pct", rng.choice(n, n // 100, replace=False).astype(np.int64))):
+            ids_dev = torch.from_numpy(ids).cuda()
+            ans = answers(ids_dev)
+            state = {"i": 0, "s": 0.0}
+
+            def all_gather(_ctx, send_ptr, recv_ptr, nbytes):
+                try:
+                    t0 = time.perf_counter()
+                    a = ans[state["i"]]
+                    state["i"] += 1
+                    if a.numel() != nbytes * W_:
+                        return 1
+                    torch.as_tensor(_Mem(recv_ptr, nbytes * W_), device="cuda").copy_(a)
+                    torch.cuda.synchronize()
+                    state["s"] += time.perf_counter() - t0
+                    return 0
+                except Exception:   # never unwind through the C frame
+                    return 1
+
+            cb = _AG(all_gather)
+            worst = None
+            for r, sx in enumerate(shards):
+                comm = VersComm(None, r, W_, cb)
+                best = None
+                for _ in range(args.takes + 1):   # (the first take builds the rank's map)
+                    state["i"], state["s"] = 0, 0.0
+                    ms, counts = timed(lambda: sx.fetch_sharded_dev(_Ptr(C.byref(comm)), ids_dev.data_ptr(), len(ids), out.data_ptr(), ld))
+                    outside = ms - state["s"] * 1e3
+                    best = outside if best is None else min(best, outside)
+                worst = best if worst is None else max(worst, best)
+            un = report(f"unsharded {name}", ix, ids, out, args.takes)
+            res[name] = {"ids": len(ids), "slowest_rank_ms_outside_callbacks": round(worst, 4), "unsharded_ms": un["ms"],
+                         "where_bytes_per_rank": 4 * (len(ids) + 1), "row_chunk_bytes_per_rank": [int(a.numel() // W_) for a in ans[1:]]}
+            log(f"[bench_fetch] shards={W_} {name}: {res[name]}")
+        line["sharded"] = res
+        for sx in shards:
+            sx.close()
         ix.close()
         print(json.dumps(line), flush=True)
         return 0

@@ -44,6 +44,7 @@ def main():
     ap.add_argument("--takes", type=int, default=2)
     ap.add_argument("--check-lists", type=int, default=12)
     ap.add_argument("--no-reupload", action="store_true")
+    ap.add_argument("--shards", type=int, default=0, help="W ranks emulated on this GPU: vers_ivf_update_batch_sharded_dev, time outside the (answered) callback")
     args = ap.parse_args()
 
     import torch
@@ -114,6 +115,81 @@ def main():
     res, stay_ids = {}, {}
     keys = ("stage_ms", "assign_ms", "locate_ms", "overwrite_ms", "merge_ms", "derive_ms")
     call(perm[-64:], src[perm[-64:]])   # warm-up: first launches and the scratch
+    if args.shards:
+        # W ranks EMULATED on this one GPU: W handles over the settled index (vers_ivf_set_shard + vers_ivf_upload_dev), the one all_gather of a
+        # call answered from the where table the unsharded index implies.  Reported per size (10 % movers): the slowest rank's time OUTSIDE
+        # the callback, the bytes the exchange would carry, and the unsharded call on the same index in the same run.  The exchange itself,
+        # and any run on more than one physical GPU, is NOT measured.
+        from vers_amd.dist import _AG, VersComm, _Mem
+        W_ = args.shards
+        cent = torch.zeros(nlist, ld, dtype=torch.float32, device="cuda")
+        cent[:, :d] = torch.from_numpy(np.ascontiguousarray(index.get_centroids())).cuda()
+        own_d = torch.from_numpy(own.astype(np.int64)).cuda()
+        shards = []
+        for r in range(W_):
+            sx = IVFFlatIndex(d)
+            sx.set_shard(r, W_)
+            sx.upload_dev(X.data_ptr(), n, ld, cent.data_ptr(), nlist, ld, own_d.data_ptr())
+            shards.append(sx)
+        owners = shards[0].owners().astype(np.int64)
+        sharded = {}
+        for m in sizes:
+            ids = perm[taken:taken + m].copy()
+            taken += m
+            now = own[src[ids]]
+            move = rng.random(m) < 0.10
+            shift = 1 + rng.integers(0, max(1, full.size - 1), m)
+            target = np.where(move, full[(np.searchsorted(full, now) + shift) % full.size], now)
+            move &= target != now
+            new_src = donor_in(target)
+            table = np.full((W_, m + 1), 0xFFFFFFFF, dtype=np.uint32)
+            table[:, m] = 0
+            table[owners[now], np.arange(m)] = now
+            ans = torch.from_numpy(table.reshape(-1).view(np.uint8).copy()).cuda()
+            spent = [0.0]
+
+            def all_gather(_ctx, send_ptr, recv_ptr, nbytes):
+                try:
+                    t0 = time.perf_counter()
+                    if ans.numel() != nbytes * W_:
+                        return 1
+                    torch.as_tensor(_Mem(recv_ptr, nbytes * W_), device="cuda").copy_(ans)
+                    torch.cuda.synchronize()
+                    spent[0] += time.perf_counter() - t0
+                    return 0
+                except Exception:   # never unwind through the C frame
+                    return 1
+
+            cb = _AG(all_gather)
+            ids_d = torch.from_numpy(ids.astype(np.int64)).cuda()
+            rows_d = X[torch.from_numpy(new_src.astype(np.int64)).cuda()].contiguous()
+            worst, ok = 0.0, True
+            for r, sx in enumerate(shards):
+                comm = VersComm(None, r, W_, cb)
+                cl_d = torch.zeros(m, dtype=torch.int64, device="cuda"); st_d = torch.zeros(m, dtype=torch.uint8, device="cuda")
+                counts4 = np.zeros(4, dtype=np.uint64)
+                spent[0] = 0.0
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                capi.check(capi.lib().vers_ivf_update_batch_sharded_dev(sx._h, C.byref(comm), capi._vp(ids_d.data_ptr()), capi._vp(rows_d.data_ptr()), m, ld,
+                                                                        capi._vp(cl_d.data_ptr()), capi._vp(st_d.data_ptr()), counts4.ctypes.data_as(C.POINTER(C.c_uint64))))
+                worst = max(worst, (time.perf_counter() - t0 - spent[0]) * 1e3)
+                ok &= np.array_equal(cl_d.cpu().numpy(), target) and np.array_equal(st_d.cpu().numpy(), move.astype(np.uint8))
+            ms, cl, st, counts = call(ids, new_src)   # the unsharded call on the same index, the same rows
+            ok &= np.array_equal(cl, target) and np.array_equal(st, move.astype(np.uint8))
+            src[ids] = new_src
+            for sx in shards:
+                ok &= np.array_equal(sx.list_lengths(), index.list_lengths())
+            all_ok &= bool(ok)
+            sharded[str(m)] = {"slowest_rank_ms_outside_callback": round(worst, 3), "unsharded_ms": round(ms, 3), "moved": int(move.sum()),
+                               "where_bytes_per_rank": 4 * (m + 1), "same_as_unsharded": bool(ok)}
+            log(f"[bench_update] shards={W_} mix_{m}: {sharded[str(m)]}")
+        for sx in shards:
+            sx.close()
+        index.close()
+        print(json.dumps({"metric": f"update_batch_sharded_dev, {W_} ranks emulated on one GPU, IVFFlat N={n} d={d} nlist={nlist}", "sizes": sharded,
+                          "note": "callbacks answered from the unsharded index; the exchange itself is not measured", "same_as_unsharded": bool(all_ok)}), flush=True)
+        return 0 if all_ok else 1
     for m in sizes:
         for way in ways:
             for take in range(args.takes):

@@ -120,6 +120,9 @@ SIGNATURES = {
     "vers_fetch_phases": (C.c_int32, [C.POINTER(C.c_double), C.c_int32]),
     "vers_ivf_search_by_id": (C.c_int32, [_vp, _vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _vp, _vp, _vp]),
     "vers_ivf_search_by_id_dev": (C.c_int32, [_vp, _vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _vp, _vp, _vp, _vp]),
+    "vers_ivf_fetch_sharded_dev": (C.c_int32, [_vp, _vp, _vp, C.c_uint64, _vp, C.c_uint64, _vp, _vp, C.POINTER(C.c_uint64), _vp]),
+    "vers_ivf_update_batch_sharded_dev": (C.c_int32, [_vp, _vp, _vp, _vp, C.c_uint64, C.c_uint64, _vp, _vp, C.POINTER(C.c_uint64)]),
+    "vers_ivf_search_by_id_sharded_dev": (C.c_int32, [_vp, _vp, _vp, _vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _vp, _vp, _vp, _vp]),
     "vers_ivf_range_search": (C.c_int32, [_vp, _vp, C.c_uint64, C.c_uint32, _vp, C.c_uint32, C.c_uint32, _vp, _vp, _vp, C.c_uint64,
                                           C.POINTER(C.c_uint64)]),
     "vers_ivf_range_search_dev": (C.c_int32, [_vp, _vp, C.c_uint64, C.c_uint32, _vp, C.c_uint32, C.c_uint32, _vp, _vp, _vp, C.c_uint64,
@@ -538,7 +541,7 @@ def fetch_phases(reset=False) -> dict:
     """The fetch calls of this process by phase, host wall clock in ms (vers_fetch_phases); map_ms is 0 when the cached map was valid."""
     v = (C.c_double * 8)()
     check(lib().vers_fetch_phases(v, 1 if reset else 0))
-    keys = ("calls", "ids", "found", "stage_ms", "map_ms", "gather_ms", "copy_ms", "reserved")
+    keys = ("calls", "ids", "found", "stage_ms", "map_ms", "gather_ms", "copy_ms", "callback_ms")
     return dict(zip(keys, (float(x) for x in v)))
 
 

@@ -11,6 +11,8 @@
 //   fetch_rows_rm_kernel  the gather from the row-major copy: a wave per requested row, whole sectors in, contiguous stores out
 //   fetch_tiles_kernel    the gather from the f32 tiles: the requests ordered by storage row, a block per touched tile
 //   byid_drop_self_kernel VERS_BYID_EXCLUDE_SELF: the search's top_k + 1 rows without the query's own id
+//   shard_*_kernel        handles sharded by cluster: the rank's words of the where round, the source list of a packed chunk, clusters and
+//                         status from the resolved table, and the rows of a gathered chunk to their requests (a wave per row)
 //
 // The two rules of DESIGN section 2 decide the gathers: from the tiles a row is d / 4 separate 16-byte pieces, each in its own 64-byte
 // sector (4x the useful bytes); from the row-major copy it is whole sectors.  A tile of which at least `lds_min` rows are wanted is read as
@@ -19,6 +21,7 @@
 #pragma once
 #include "scan.hip.h"  // f32x4, lds_barrier
 #include "fetch_plan.hpp"
+#include "shard_where.hpp"
 #include "update_plan.hpp"
 
 namespace vers {
@@ -212,6 +215,54 @@ __global__ __launch_bounds__(256) void fetch_tiles_kernel(const float* in, uint3
   }
 }
 // [fetch gather kernel: end]
+
+// ---- handles sharded by cluster: the "where" round and the row round (shard_where.hpp) ---------------------------------------------------
+// words[i] = the list of storage row src[i] (by the CURRENT list_off, as fetch_meta_kernel), shw::kNoWord for an id this rank stores in no
+// list: what the rank sends in the where round.  Only the call's exchange buffer is written.
+__global__ void shard_where_kernel(const uint32_t* src, uint64_t n, const uint32_t* list_off, uint32_t k, uint32_t* words) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t r = src[i];
+  words[i] = r == kFetchNone ? shw::kNoWord : upd::list_of_row(list_off, k, r);
+}
+// csrc[p] = src[req[p]]: the storage rows of the requests this rank found in one chunk, in request order -- the source list that drives the
+// existing gathers (fetch_rows_rm_kernel / fetch_tiles_kernel) into the packed send buffer
+__global__ void shard_pack_src_kernel(const uint32_t* src, const uint32_t* req, uint64_t m, uint32_t* csrc) {
+  const uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (p < m) csrc[p] = src[req[p]];
+}
+// out_clusters / out_status (each nullable) from the resolved table: cluster[i] = the list of request i on its owner, shw::kNoWord = in no list
+__global__ void shard_meta_kernel(const uint32_t* cluster, uint64_t n, uint64_t* out_clusters, uint8_t* out_status) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t c = cluster[i];
+  if (out_clusters) out_clusters[i] = c == shw::kNoWord ? 0xFFFFFFFFFFFFFFFFull : (uint64_t)c;
+  if (out_status) out_status[i] = c == shw::kNoWord ? upd::kSkipped : (uint8_t)0;
+}
+// One WAVE per request of a chunk (four to a block), as fetch_rows_rm_kernel: request i0 + i takes row slot[i0 + i] of the gathered chunk
+// (recv: [world][pad] rows at a pitch of exactly d floats) to out row i0 + i (pitch floats); a request in no list leaves as d zeros.  Whole
+// 16-byte pieces when both sides allow it (vec: d, pitch and out are multiples of 16 bytes; recv is); otherwise a float per lane.  Columns
+// d .. pitch - 1 are never written.
+__global__ __launch_bounds__(256) void shard_place_rows_kernel(const float* recv, uint32_t d, const uint32_t* slot, uint64_t i0, uint64_t m, float* out, uint64_t pitch,
+                                                               int vec) {
+  const uint64_t il = (uint64_t)blockIdx.x * 4u + (threadIdx.x >> 6);
+  const uint32_t lane = threadIdx.x & 63u;
+  if (il >= m) return;
+  const uint64_t i = i0 + il;
+  const uint32_t s = slot[i];
+  const bool have = s != shw::kNoWord;
+  const float* in = recv + (uint64_t)(have ? s : 0u) * d;
+  float* o = out + i * pitch;
+  if (vec) {
+    for (uint32_t j = lane; j < d / 4u; j += 64u) {
+      f32x4 v = {0.0f, 0.0f, 0.0f, 0.0f};
+      if (have) v = reinterpret_cast<const f32x4*>(in)[j];
+      reinterpret_cast<f32x4*>(o)[j] = v;
+    }
+  } else {
+    for (uint32_t c = lane; c < d; c += 64u) o[c] = have ? in[c] : 0.0f;
+  }
+}
 
 // ---- search by stored id: VERS_BYID_EXCLUDE_SELF -----------------------------------------------------------------------------------------
 // Row q of the search at top_k + 1 (ids / dist [b][top_k + 1], cnt [b]) without the entry whose id is self[q] -- or without its last entry

@@ -643,7 +643,7 @@ __global__ void update_mark_kernel(const uint64_t* ids, uint64_t m, uint64_t n_t
 // the sort.  Updates never met keep status 2 (the id is in no list).  Positions are list-relative: a re-layout may follow.
 __global__ void update_locate_kernel(const uint32_t* row_ids, uint64_t cap_rows, const uint32_t* slot, uint64_t n_total, const uint32_t* list_off, uint32_t k,
                                      const uint32_t* a32, uint8_t* status, uint32_t* rel, uint32_t* bitmap, uint32_t* out_cnt, uint32_t* first_tile,
-                                     uint32_t* in_cnt, uint32_t* n_mv, uint32_t mv_cap, uint64_t* mv_key, uint64_t* mv_val) {
+                                     uint32_t* in_cnt, uint32_t* n_mv, uint32_t mv_cap, uint64_t* mv_key, uint64_t* mv_val, uint32_t* old_of) {
   for (uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; r < cap_rows; r += (uint64_t)gridDim.x * blockDim.x) {
     const uint32_t id = row_ids[r];
     if (id == upd::kNone || id >= n_total) continue;
@@ -653,6 +653,7 @@ __global__ void update_locate_kernel(const uint32_t* row_ids, uint64_t cap_rows,
     const uint32_t p = (uint32_t)(r - list_off[c]);
     const uint8_t s = upd::classify(c, a);
     status[i] = s;
+    if (old_of) old_of[i] = c;  // (a handle sharded by cluster: this rank's word of the where round)
     if (s == upd::kStayed) { rel[i] = p; continue; }
     atomicOr(&bitmap[id >> 5], 1u << (id & 31));
     atomicAdd(&out_cnt[c], 1u);
@@ -663,6 +664,50 @@ __global__ void update_locate_kernel(const uint32_t* row_ids, uint64_t cap_rows,
     mv_key[j] = ((uint64_t)a << 32) | id;
     mv_val[j] = i;
   }
+}
+
+// A handle sharded by cluster, after the where round: table [world][n + 1] holds, per rank, the list every vec id of the call lies in THERE
+// (0xFFFFFFFF: in no list of that rank).  Every rank derives the same from it --
+//   gstatus[i]  stayed (the claimed list is a32[i]) / moved / skipped (no claimer): the call's out_status
+//   g_out / g_in  rows leaving / entering every list, whoever owns it: the new GLOBAL lengths
+// and its own part: lstatus[i] = stayed only where THIS rank is the claimer (rel[i] is valid: update_locate_kernel met the row), moved only
+// where this rank owns the new list -- then the pair ((new list, vec id), i) is appended for the sort, the row comes from the CALL's rows,
+// wherever the old one lay -- and skipped otherwise.  *bad |= 1: an id claimed twice; |= 2: a claim by a rank that does not own the list.
+__global__ void update_resolve_kernel(const uint32_t* table, uint32_t world, uint32_t me, const uint64_t* ids, uint32_t n, const uint8_t* owner, uint32_t k,
+                                      const uint32_t* a32, uint8_t* gstatus, uint8_t* lstatus, uint32_t* g_out, uint32_t* g_in, uint32_t* n_mv, uint64_t* mv_key,
+                                      uint64_t* mv_val, uint32_t* bad) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  uint32_t who = upd::kNone, old = upd::kNone;
+  for (uint32_t r = 0; r < world; ++r) {
+    const uint32_t w = table[(uint64_t)r * ((uint64_t)n + 1u) + i];
+    if (w == upd::kNone) continue;
+    if (who != upd::kNone) { atomicOr(bad, 1u); continue; }
+    if (w >= k || (uint32_t)owner[w] != r) { atomicOr(bad, 2u); continue; }
+    who = r;
+    old = w;
+  }
+  const uint32_t a = a32[i];
+  uint8_t g = upd::kSkipped, l = upd::kSkipped;
+  if (who != upd::kNone && a < k) {
+    g = upd::classify(old, a);
+    if (g == upd::kStayed) {
+      if (who == me) l = upd::kStayed;
+    } else {
+      atomicAdd(&g_out[old], 1u);
+      atomicAdd(&g_in[a], 1u);
+      if ((uint32_t)owner[a] == me) {
+        l = upd::kMoved;
+        const uint32_t j = atomicAdd(n_mv, 1u);
+        if (j < n) {
+          mv_key[j] = ((uint64_t)a << 32) | (uint32_t)ids[i];
+          mv_val[j] = i;
+        }
+      }
+    }
+  }
+  gstatus[i] = g;
+  lstatus[i] = l;
 }
 
 // mv_row[i] = the place of update i among the movers sorted by (new list, vec id)
@@ -2321,9 +2366,13 @@ static int32_t update_stage_chunk(vers_ivf* h, const float* rows_host, uint64_t 
 // chunk (option "add_batch_rows") therefore stages its rows TWICE: once to assign and check, once to place -- the second pass over the
 // caller's rows is the price of refusing a NaN in the last chunk with the index untouched.  dev: the outputs but out_counts are device memory.
 int32_t update_batch_locked(vers_ivf* h, const uint64_t* ids_host, const uint64_t* ids_dev, const float* rows_host, uint64_t row_stride_bytes,
-                            const float* rows_dev, uint64_t ld_floats, uint64_t n, bool dev, uint64_t* out_clusters, uint8_t* out_status, uint64_t* out_counts) {
+                            const float* rows_dev, uint64_t ld_floats, uint64_t n, bool dev, uint64_t* out_clusters, uint8_t* out_status, uint64_t* out_counts,
+                            const vers_comm_t* comm = nullptr) {
+  // comm != nullptr: vers_ivf_update_batch_sharded_dev -- the handle is sharded by cluster (or a one-rank communicator stands in for that):
+  // every rank runs the same call; what differs is marked `sh` below.  The where round (shard_where.hpp) sits between locate and the plan.
+  const bool sh = comm != nullptr;
   VERS_HIP_TRY(hipDeviceSynchronize());  // searches still in flight on any stream read the rows and tables this call changes
-  if (h->world > 1)
+  if (h->world > 1 && !sh)
     return fail(VERS_ERR_INVALID, "vers_ivf_update_batch: a handle sharded by cluster is not supported (the old and the new owner of a row differ)");
   if (n == 0) {
     if (out_counts) std::fill(out_counts, out_counts + 4, 0ull);
@@ -2353,6 +2402,11 @@ int32_t update_batch_locked(vers_ivf* h, const uint64_t* ids_host, const uint64_
   if (int32_t rc = ab.stage.reserve(chunk * ldx * sizeof(float))) return rc;
   if (int32_t rc = h->km.counts.reserve((2 * (size_t)k + 2) * sizeof(uint32_t))) return rc;
   if (int32_t rc = h->pre_misc.reserve(64)) return rc;
+  if (sh) {  // (before any exchange: a rank without these cannot join the where round at all -- the host aborts the group)
+    if (int32_t rc = ud.where.reserve((n + 1) * sizeof(uint32_t))) return rc;
+    if (int32_t rc = ud.gstat.reserve(n)) return rc;
+    if (int32_t rc = h->rm.gath.reserve((size_t)h->world * (n + 1) * sizeof(uint32_t))) return rc;
+  }
   if (rows_host && ab.pin_cap < chunk * ldx * sizeof(float)) {
     ab.free_pin();
     VERS_HIP_TRY(hipHostMalloc(&ab.pin, chunk * ldx * sizeof(float), hipHostMallocDefault));
@@ -2434,11 +2488,13 @@ int32_t update_batch_locked(vers_ivf* h, const uint64_t* ids_host, const uint64_
     VERS_HIP_TRY(hipMemsetAsync(first_tile, 0xFF, (size_t)k * sizeof(uint32_t), st));
     VERS_HIP_TRY(hipMemsetAsync(in_cnt, 0, (size_t)k * sizeof(uint32_t), st));
     VERS_HIP_TRY(hipMemsetAsync(n_mv_dev, 0, sizeof(uint32_t), st));
+    if (sh) VERS_HIP_TRY(hipMemsetAsync(ud.where.p, 0xFF, n * sizeof(uint32_t), st));  // (an id this rank stores in no list)
     if (h->cap_rows) {
       const uint64_t blocks = std::min<uint64_t>((uint64_t)h->n_cu * 8, (h->cap_rows + 255) / 256);
       hipLaunchKernelGGL(update_locate_kernel, dim3((unsigned)blocks), dim3(256), 0, st, (const uint32_t*)h->row_ids.as<uint32_t>(), h->cap_rows,
                          (const uint32_t*)ud.slot.as<uint32_t>(), nt_ids, (const uint32_t*)h->list_off.as<uint32_t>(), k, (const uint32_t*)a32,
-                         ud.status.as<uint8_t>(), ud.rel.as<uint32_t>(), h->rm.bitmap.as<uint32_t>(), out_cnt, first_tile, in_cnt, n_mv_dev, (uint32_t)n, keys_in, vals_in);
+                         ud.status.as<uint8_t>(), ud.rel.as<uint32_t>(), h->rm.bitmap.as<uint32_t>(), out_cnt, first_tile, in_cnt, n_mv_dev, (uint32_t)n, keys_in, vals_in,
+                         sh ? ud.where.as<uint32_t>() : (uint32_t*)nullptr);
     }
     VERS_HIP_TRY(hipGetLastError());
     uint32_t tail[2] = {0, 0};
@@ -2446,23 +2502,103 @@ int32_t update_batch_locked(vers_ivf* h, const uint64_t* ids_host, const uint64_
     VERS_HIP_TRY(hipMemcpy(tail, n_mv_dev, sizeof(tail), hipMemcpyDeviceToHost));
     VERS_HIP_TRY(hipMemcpy(status.data(), ud.status.p, n, hipMemcpyDeviceToHost));
     VERS_HIP_TRY(hipMemcpy(a_host.data(), a32, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    if (tail[1]) return fail(VERS_ERR_HIP, "vers_ivf_update_batch: the assign pass returned a cluster index out of range");
+    if (tail[1]) return fail(VERS_ERR_HIP, "vers_ivf_update_batch: the assign pass returned a cluster index out of range");  // (centroids are replicated: every rank alike)
     n_mv = tail[0];
     if (int32_t rc = clk.done()) return rc;
   }
   uint64_t stayed = 0, moved = 0, skipped = 0;
   for (uint64_t i = 0; i < n; ++i) (status[i] == upd::kStayed ? stayed : status[i] == upd::kMoved ? moved : skipped) += 1;
-  if (moved != n_mv) return fail(VERS_ERR_HIP, "vers_ivf_update_batch: a vec id is stored twice (inconsistent index)");
+  // On a sharded handle what this rank's own rows show wrong is a LOCAL failure: it travels in the status word of the where round.
+  int32_t local_rc = VERS_OK;
+  std::string local_why;
+  auto refuse = [&](const char* msg) -> int32_t {
+    const int32_t e = fail(VERS_ERR_HIP, msg);
+    if (sh && !local_rc) { local_rc = e; local_why = msg; }
+    return e;
+  };
+  if (moved != n_mv)
+    if (int32_t e = refuse("vers_ivf_update_batch: a vec id is stored twice (inconsistent index)"); !sh) return e;
   // 4. the plan: lengths in between and afterwards, the jobs of both kernels (list-relative: a re-layout may follow)
   const uint32_t* const c_out = cnt.data();
   const uint32_t* const c_ft = cnt.data() + k;
-  const uint32_t* const c_in = cnt.data() + 2 * (size_t)k;
+  const uint32_t* c_in = cnt.data() + 2 * (size_t)k;
   for (uint32_t c = 0; c < k; ++c)
-    if (c_out[c] > h->h_len[c] || (c_out[c] && (uint64_t)c_ft[c] * 64 >= h->h_len[c]))
-      return fail(VERS_ERR_HIP, "vers_ivf_update_batch: a located row lies outside its list (inconsistent index)");
-  std::vector<uint32_t> mid(k), nl(k);
-  const bool grow = moved != 0 && upd::plan_lengths(h->h_len.data(), c_out, c_in, h->h_cap.data(), k, mid.data(), nl.data());
-  if (moved == 0) { mid = h->h_len; nl = h->h_len; }
+    if (c_out[c] > h->h_len[c] || (c_out[c] && (uint64_t)c_ft[c] * 64 >= h->h_len[c]) || (sh && c_out[c] && h->h_owner.size() == k && h->h_owner[c] != h->rank)) {
+      if (int32_t e = refuse("vers_ivf_update_batch: a located row lies outside its list (inconsistent index)"); !sh) return e;
+      break;
+    }
+  std::vector<uint32_t> mid(k), nl(k), g_in;
+  bool own_io = moved != 0;  // this rank compacts or merges something
+  uint64_t moved_any = moved;  // rows that moved anywhere (prepared filters, fetch maps, tables)
+  bool grow = false;
+  if (sh) {
+    // 4a. the where round -- ONE all_gather of n + 1 words per rank -- and the resolve pass over the gathered table
+    AbClock clk(6, g_up);
+    const uint32_t world = h->world, me = h->rank;
+    const size_t nw = (size_t)n + 1;
+    if (!local_rc && test_fail_sharded_ref().load() > 0 && test_fail_sharded_ref().fetch_sub(1) > 0) (void)refuse("vers_ivf_update_batch_sharded_dev: injected local failure (test hook)");
+    uint32_t* const send = ud.where.as<uint32_t>();
+    if (local_rc) VERS_HIP_TRY(hipMemsetAsync(send, 0xFF, n * sizeof(uint32_t), st));
+    const uint32_t stw = (uint32_t)local_rc;
+    VERS_HIP_TRY(hipMemcpy(send + n, &stw, sizeof(stw), hipMemcpyHostToDevice));
+    VERS_HIP_TRY(hipDeviceSynchronize());
+    uint32_t* const table = h->rm.gath.as<uint32_t>();
+    if (int32_t crc = comm->all_gather(comm->ctx, send, table, (uint64_t)nw * sizeof(uint32_t)))
+      return local_rc ? fail(local_rc, local_why) : comm_rc(crc, "all_gather");
+    for (uint32_t r = 0; r < world; ++r) {  // the agreement: the first failing rank's status, in rank order
+      uint32_t s = 0;
+      VERS_HIP_TRY(hipMemcpy(&s, table + (size_t)r * nw + n, sizeof(s), hipMemcpyDeviceToHost));
+      if (s == 0) continue;
+      if (r == me && local_rc) return fail((int32_t)s, local_why);
+      return fail((int32_t)s, "vers_ivf_update_batch_sharded_dev: rank " + std::to_string(r) + " reported status " + std::to_string(s) + "; nothing updated");
+    }
+    // (mid_len's place holds the rows leaving every list until the host has read them)
+    VERS_HIP_TRY(hipMemsetAsync(in_cnt, 0, (size_t)k * sizeof(uint32_t), st));
+    VERS_HIP_TRY(hipMemsetAsync(mid_len, 0, (size_t)k * sizeof(uint32_t), st));
+    VERS_HIP_TRY(hipMemsetAsync(n_mv_dev, 0, 2 * sizeof(uint32_t), st));
+    DevBuf own_tmp;  // (a one-rank communicator on an unsharded handle: every list is this rank's)
+    const uint8_t* owner_dev = h->owner.as<uint8_t>();
+    if (h->h_owner.size() != k || owner_dev == nullptr) {
+      if (int32_t rc = own_tmp.reserve(k)) return rc;
+      VERS_HIP_TRY(hipMemsetAsync(own_tmp.p, 0, k, st));
+      owner_dev = own_tmp.as<uint8_t>();
+    }
+    hipLaunchKernelGGL(update_resolve_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const uint32_t*)table, world, me, ids, (uint32_t)n,
+                       owner_dev, k, (const uint32_t*)a32, ud.gstat.as<uint8_t>(), ud.status.as<uint8_t>(), mid_len, in_cnt, n_mv_dev, keys_in,
+                       vals_in, bad);
+    VERS_HIP_TRY(hipGetLastError());
+    std::vector<uint8_t> gstat(n);
+    std::vector<uint32_t> g_out(k);
+    g_in.resize(k);
+    uint32_t tail[2] = {0, 0};
+    VERS_HIP_TRY(hipMemcpy(tail, n_mv_dev, sizeof(tail), hipMemcpyDeviceToHost));
+    VERS_HIP_TRY(hipMemcpy(gstat.data(), ud.gstat.p, n, hipMemcpyDeviceToHost));
+    VERS_HIP_TRY(hipMemcpy(status.data(), ud.status.p, n, hipMemcpyDeviceToHost));  // from here on: this rank's part
+    VERS_HIP_TRY(hipMemcpy(g_out.data(), mid_len, (size_t)k * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    VERS_HIP_TRY(hipMemcpy(g_in.data(), in_cnt, (size_t)k * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (int32_t rc = clk.done()) return rc;
+    if (tail[1]) return fail(VERS_ERR_HIP, "vers_ivf_update_batch_sharded_dev: a vec id is claimed by two ranks, or by a rank that does not own its list (inconsistent index); nothing updated");
+    n_mv = tail[0];
+    stayed = moved = skipped = 0;
+    for (uint64_t i = 0; i < n; ++i) (gstat[i] == upd::kStayed ? stayed : gstat[i] == upd::kMoved ? moved : skipped) += 1;
+    moved_any = moved;
+    bool any_out = false;
+    for (uint32_t c = 0; c < k; ++c) {
+      const bool mine_c = h->h_owner.size() != k || h->h_owner[c] == me;
+      if (g_out[c] > h->h_len[c] || (mine_c && g_out[c] != c_out[c]))
+        return fail(VERS_ERR_HIP, "vers_ivf_update_batch_sharded_dev: the gathered table and this rank's lists disagree (inconsistent index); nothing updated");
+      mid[c] = h->h_len[c] - g_out[c];
+      nl[c] = mid[c] + g_in[c];
+      if (!mine_c) g_in[c] = 0;  // (the merge jobs: owned lists only)
+      else if (nl[c] > h->h_cap[c]) grow = true;
+      any_out = any_out || c_out[c] != 0;
+    }
+    c_in = g_in.data();
+    own_io = any_out || n_mv != 0;
+  } else {
+    grow = moved != 0 && upd::plan_lengths(h->h_len.data(), c_out, c_in, h->h_cap.data(), k, mid.data(), nl.data());
+    if (moved == 0) { mid = h->h_len; nl = h->h_len; }
+  }
   uint64_t relayouts = 0;
   if (grow) {
     AbClock clk(8, g_up);
@@ -2490,7 +2626,7 @@ int32_t update_batch_locked(vers_ivf* h, const uint64_t* ids_host, const uint64_
     if (int32_t rc = clk.done()) return rc;
   }
   // 6. placement of the staged rows: stays over their storage rows, movers into their stage.  THE FIRST WRITE to a stored row.
-  if (moved) h->flt_moved += 1;  // (prepared filters: storage rows change their vec ids from here on)
+  if (moved_any) h->flt_moved += 1;  // (prepared filters, fetch maps: storage rows change their vec ids from here on -- on a sharded handle on EVERY rank when anything moved anywhere)
   for (uint64_t s0 = 0; s0 < n; s0 += chunk) {
     const uint32_t m = (uint32_t)std::min<uint64_t>(chunk, n - s0);
     if (!one_chunk) {
@@ -2515,7 +2651,7 @@ int32_t update_batch_locked(vers_ivf* h, const uint64_t* ids_host, const uint64_
     for (uint64_t i = 0; i < n; ++i)
       if (status[i] == upd::kStayed) tiles.push_back((uint32_t)(((uint64_t)h->h_off[a_host[i]] + rel[i]) / 64));
   }
-  if (moved) {
+  if (own_io) {
     AbClock clk(8, g_up);
     std::vector<RemoveJob> rjobs;
     std::vector<MergeJob> mjobs;
@@ -2531,20 +2667,23 @@ int32_t update_batch_locked(vers_ivf* h, const uint64_t* ids_host, const uint64_
     const size_t rj_b = rjobs.size() * sizeof(RemoveJob), mj_b = mjobs.size() * sizeof(MergeJob);
     if (int32_t rc = ud.jobs.reserve(rj_b + mj_b + 16)) return rc;
     if (rj_b) VERS_HIP_TRY(hipMemcpy(ud.jobs.p, rjobs.data(), rj_b, hipMemcpyHostToDevice));
-    VERS_HIP_TRY(hipMemcpy(ud.jobs.as<char>() + rj_b, mjobs.data(), mj_b, hipMemcpyHostToDevice));
+    if (mj_b) VERS_HIP_TRY(hipMemcpy(ud.jobs.as<char>() + rj_b, mjobs.data(), mj_b, hipMemcpyHostToDevice));
     VERS_HIP_TRY(hipMemcpy(mid_len, mid.data(), (size_t)k * sizeof(uint32_t), hipMemcpyHostToDevice));
     // movers out: remove_batch's compaction with the bitmap the locate pass wrote
+    if (!rjobs.empty())  // (a sharded handle: a rank may only gain rows, or only lose some)
     hipLaunchKernelGGL(remove_compact_kernel, dim3((unsigned)rjobs.size()), dim3(kRmWaves * 64), 0, st, (const RemoveJob*)ud.jobs.p,
                        (const uint32_t*)h->rm.bitmap.as<uint32_t>(), nt_ids, h->ld, h->rows.as<float>(), h->row_ids.as<uint32_t>());
     // movers in: insertion points against the compacted lists, then the backward merge
+    if (n_mv)
     hipLaunchKernelGGL(update_positions_kernel, dim3((n_mv + 255) / 256), dim3(256), 0, st, (const uint64_t*)keys_out, n_mv, (const uint32_t*)h->list_off.as<uint32_t>(),
                        (const uint32_t*)mid_len, (const uint32_t*)h->row_ids.as<uint32_t>(), ud.pos.as<uint32_t>());
+    if (!mjobs.empty())
     hipLaunchKernelGGL(update_merge_kernel, dim3((unsigned)mjobs.size()), dim3(kRmWaves * 64), 0, st, (const MergeJob*)(ud.jobs.as<char>() + rj_b),
                        (const uint32_t*)ud.pos.as<uint32_t>(), (const uint64_t*)keys_out, (const float*)ud.mstage.as<float>(), ldx, h->ld, h->rows.as<float>(),
                        h->row_ids.as<uint32_t>());
     VERS_HIP_TRY(hipGetLastError());
     std::vector<uint32_t> pos(n_mv);
-    VERS_HIP_TRY(hipMemcpy(pos.data(), ud.pos.p, (size_t)n_mv * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (n_mv) VERS_HIP_TRY(hipMemcpy(pos.data(), ud.pos.p, (size_t)n_mv * sizeof(uint32_t), hipMemcpyDeviceToHost));
     for (const MergeJob& jb : mjobs)
       for (uint32_t t = upd::merge_first_tile(pos.data() + jb.in0); t <= upd::merge_last_tile(jb.len, jb.n_in); ++t) tiles.push_back(jb.off / 64u + t);
     if (int32_t rc = clk.done()) return rc;
@@ -2552,7 +2691,7 @@ int32_t update_batch_locked(vers_ivf* h, const uint64_t* ids_host, const uint64_
   {
     // 8. tables (as remove_batch) and the derived arrays of the touched tiles; the maxima in pre_misc only grow, as after a removal
     AbClock clk(9, g_up);
-    if (moved) {
+    if (moved_any) {
       std::vector<uint32_t> sl(k);
       for (uint32_t c = 0; c < k; ++c) sl[h->h_slot[c]] = nl[c];
       VERS_HIP_TRY(hipMemcpy(h->list_len.p, nl.data(), (size_t)k * sizeof(uint32_t), hipMemcpyHostToDevice));
@@ -2585,7 +2724,7 @@ int32_t update_batch_locked(vers_ivf* h, const uint64_t* ids_host, const uint64_
       hipLaunchKernelGGL(u32_to_u64_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const uint32_t*)a32, n, out_clusters);
       VERS_HIP_TRY(hipGetLastError());
     }
-    if (out_status) VERS_HIP_TRY(hipMemcpyAsync(out_status, ud.status.p, n, hipMemcpyDeviceToDevice, st));
+    if (out_status) VERS_HIP_TRY(hipMemcpyAsync(out_status, sh ? ud.gstat.p : ud.status.p, n, hipMemcpyDeviceToDevice, st));  // (sharded: the status every rank derived)
     VERS_HIP_TRY(hipStreamSynchronize(st));
   } else {
     if (out_clusters)
@@ -3185,6 +3324,22 @@ int32_t vers_ivf_update_batch_dev(vers_ivf_t* h, const uint64_t* vec_ids_dev, co
   std::unique_lock<std::shared_mutex> lk(h->index);
   DeviceGuard g(h->device);
   return update_batch_locked(h, nullptr, vec_ids_dev, nullptr, 0, rows_dev, ld_floats, n, true, out_clusters_dev, out_status_dev, out_counts);
+}
+
+int32_t vers_ivf_update_batch_sharded_dev(vers_ivf_t* h, const vers_comm_t* comm, const uint64_t* vec_ids_dev, const float* rows_dev, uint64_t n, uint64_t ld_floats,
+                                          uint64_t* out_clusters_dev, uint8_t* out_status_dev, uint64_t* out_counts) {
+  const std::string who = "vers_ivf_update_batch_sharded_dev";
+  if (!h) return fail(VERS_ERR_INVALID, who + ": null handle");
+  if ((n && (!vec_ids_dev || !rows_dev)) || ld_floats < (uint64_t)h->d || ld_floats % 4 || ld_floats > 0x3FFFFFFFull || n > 0xFFFFFFFEull)
+    return fail(VERS_ERR_INVALID, who + ": bad arguments (ld_floats must be >= d and a multiple of 4)");
+  if (comm && (comm->world == 0 || comm->rank >= comm->world || comm->world > 255u || !comm->all_gather)) return fail(VERS_ERR_INVALID, who + ": incomplete vers_comm_t");
+  std::unique_lock<std::shared_mutex> lk(h->index);
+  const uint32_t world = comm ? comm->world : 1u;
+  if (world != h->world || (comm && world > 1 && comm->rank != h->rank))
+    return fail(VERS_ERR_INVALID, who + ": the handle is sharded as rank " + std::to_string(h->rank) + " of " + std::to_string(h->world) + ", the communicator says otherwise");
+  DeviceGuard g(h->device);
+  // comm == NULL on an unsharded handle: the existing call
+  return update_batch_locked(h, nullptr, vec_ids_dev, nullptr, 0, rows_dev, ld_floats, n, true, out_clusters_dev, out_status_dev, out_counts, comm);
 }
 
 int32_t vers_update_phases(double* out, int32_t reset) {

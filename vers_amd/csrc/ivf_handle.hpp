@@ -260,6 +260,7 @@ struct vers_ivf {
   // ((new list, vec id), update) pairs | pos: insertion points | mstage: the movers' rows [n_mv][ldx] | jobs: both kernels' jobs + tiles.
   struct UpdateState {
     DevBuf ids, slot, a32, status, rel, mv_row, cnt, keys, vals, pos, mstage, jobs, tmp;
+    DevBuf where, gstat;  // a sharded handle (vers_ivf_update_batch_sharded_dev): this rank's n + 1 words of the where round | the global status per update
   } ud;
   // matrix-core list scan (prescan.hip.h): |x|^2 per storage row, [0] max |x|^2 bits, [1] certificate failures (running)
   DevBuf xnorm, pre_misc;

@@ -284,6 +284,38 @@ class IVFFlatIndex:
         f = (capi.BYID_EXCLUDE_SELF if exclude_self else 0) if flags is None else int(flags)
         check(lib().vers_ivf_search_by_id_dev(self._h, _vp(ids_in_ptr) if b else None, b, top_k, nprobe, f, _vp(ids_ptr), _vp(dist_ptr), _vp(cnt_ptr), _vp(stream)))
 
+    # -- the same on handles sharded by cluster: every rank calls with the same ids ------------------------------------
+    def fetch_sharded_dev(self, comm, ids_ptr: int, n: int, rows_ptr: int = 0, ld: int = 0, clusters_ptr: int = 0, status_ptr: int = 0, stream: int = 0):
+        """vers_ivf_fetch_sharded_dev: fetch_dev on a handle sharded by cluster.  comm: the vers_amd.dist.TorchComm of the handle (None on
+        an unsharded one: the call is fetch_dev).  One all_gather tells every rank where each id lives, one per non-empty chunk of
+        option "add_batch_rows" requests carries the rows; every rank receives what fetch_dev returns on the unsharded index.
+        Returns (found, in no list)."""
+        counts = np.zeros(2, dtype=np.uint64)
+        check(lib().vers_ivf_fetch_sharded_dev(self._h, comm.ptr() if comm is not None else None, _vp(ids_ptr) if n else None, n, _vp(rows_ptr) if rows_ptr else None, ld,
+                                               _vp(clusters_ptr) if clusters_ptr else None, _vp(status_ptr) if status_ptr else None,
+                                               counts.ctypes.data_as(C.POINTER(C.c_uint64)), _vp(stream)))
+        return int(counts[0]), int(counts[1])
+
+    def update_batch_sharded_dev(self, comm, ids_ptr: int, rows_ptr: int, n: int, ld: int, clusters_ptr: int = 0, status_ptr: int = 0):
+        """vers_ivf_update_batch_sharded_dev: update_batch_dev on a handle sharded by cluster.  EVERY rank calls with the same ids and rows
+        (comm: the vers_amd.dist.TorchComm of the handle; None on an unsharded one: the call is update_batch_dev); one all_gather tells
+        every rank where each id lives, no row crosses ranks.  The host fields are NOT mirrored.  Returns (stayed, moved, skipped,
+        this rank's relayouts)."""
+        counts = np.zeros(4, dtype=np.uint64)
+        check(lib().vers_ivf_update_batch_sharded_dev(self._h, comm.ptr() if comm is not None else None, _vp(ids_ptr) if n else None, _vp(rows_ptr) if n else None, n, ld,
+                                                      _vp(clusters_ptr) if clusters_ptr else None, _vp(status_ptr) if status_ptr else None,
+                                                      counts.ctypes.data_as(C.POINTER(C.c_uint64))))
+        return tuple(int(x) for x in counts)
+
+    def search_by_id_sharded_dev(self, comm, gather_ptr, ids_in_ptr: int, b: int, top_k: int, nprobe: int, ids_ptr: int, dist_ptr: int, cnt_ptr: int,
+                                 exclude_self: bool = False, stream: int = 0, flags=None):
+        """vers_ivf_search_by_id_sharded_dev: search_by_id_dev on a handle sharded by cluster.  comm (dist.TorchComm) carries the where
+        round and the row round that put the query block on every rank, gather_ptr (dist.TorchGather.ptr() or RcclComm.gather_ptr())
+        the sharded search behind them; both None on an unsharded handle.  After the id check it is search_sharded_dev's protocol."""
+        f = (capi.BYID_EXCLUDE_SELF if exclude_self else 0) if flags is None else int(flags)
+        check(lib().vers_ivf_search_by_id_sharded_dev(self._h, comm.ptr() if comm is not None else None, gather_ptr, _vp(ids_in_ptr) if b else None, b, top_k, nprobe, f,
+                                                      _vp(ids_ptr), _vp(dist_ptr), _vp(cnt_ptr), _vp(stream)))
+
     def sync_from_device(self, chunk: int = 1 << 16):
         """Rebuilds the host fields from the handle -- what a process that used the _dev mutators (which do not mirror) needs before
         save_index.  Ids 0 .. n-1 are fetched in chunks: `values[v]` and `assignments[v]` are replaced for every id that is in a list;
