@@ -943,6 +943,13 @@ int32_t vers_ivf_range_search_exhaustive_sharded_dev(vers_ivf_t* h, const vers_c
  *                       vers_ivf_compact (vers_ivf_head_state).  0 = no head, one launch.  "pre_head_backoff" (1): after a scan in which
  *                       fewer than 1/8 of the quads the filter tested were ruled out (rows without cluster contrast) the handle's
  *                       next 64 batches run as one launch, then the filter is tried again; 0 = never back off.
+ *   "pre_ball" (1)      sub-cluster balls per list, derived with the int8 head (up to 32 fp16 centres per list, a radius and the smallest
+ *                       |x|^2 each; at most 64 x the row length bytes per list): inside the three-launch scan a pass in front of the
+ *                       head's filter rules cold quads out from the centres alone, and the filter reads the heads of the quads that
+ *                       are left.  Results are bit-identical.  Read when the index is built / uploaded / compacted and per search;
+ *                       invalidated with the head (vers_ivf_ball_state).  "pre_ball_cut" (900): the farthest-point cut of the derive
+ *                       pass in thousandths of sqrt(max |x|^2); a list that needs more than 32 sub-clusters at the cut gets none.
+ *                       "pre_ball_min_quads" (0 = twice the compute units the scan uses): cold quads below which the pass stands aside.
  *   "scan_events" (2)   HIP event records around list-scan launches (vers_ivf_last_scan / vers_ivf_scan_times): 1 always, 0 never,
  *                       2 for batches only (the two records cost a single-query call 5.5-6 us).
  *  A/B and forced paths (tests, measurements):
@@ -1250,6 +1257,13 @@ int32_t vers_ivf_prune_stats(vers_ivf_t* h, uint64_t* out_last, uint64_t* out_to
  * ruled out | 64-column head steps (4 KiB each) read -- [3] of the most recent list scan (zeros when that scan was a single launch)
  * and [3] over the handle's life.  Any pointer may be NULL. */
 int32_t vers_ivf_head_state(vers_ivf_t* h, int32_t* out_valid, uint64_t* out_bytes, uint32_t* out_cols, uint64_t* out_last, uint64_t* out_total);
+/* The sub-cluster balls of the lists (option "pre_ball"): whether the handle holds VALID ones (derived and invalidated where the int8
+ * head is), their bytes, the lists that got balls and the sub-clusters over all lists, and the ball filter's counters -- units (list,
+ * query group) tested | units ruled out -- [2] of the most recent list scan (zeros when the pass was not launched or did not engage)
+ * and [2] over the handle's life.  The quads of a unit ruled out count in vers_ivf_head_state's quads tested | ruled out as well.
+ * Any pointer may be NULL. */
+int32_t vers_ivf_ball_state(vers_ivf_t* h, int32_t* out_valid, uint64_t* out_bytes, uint32_t* out_lists_with_balls, uint64_t* out_subclusters,
+                            uint64_t* out_last, uint64_t* out_total);
 /* An fp16 shadow copy of the stored rows (+50 % corpus memory) feeds the matrix-core pre-selection of batched searches:
  * half the HBM bytes per list scan, a ~2x wider certificate window, the same exact f32 finish -- results stay
  * bit-identical.  On by default (VERS_SHADOW=0 or vers_set_option("shadow", 0) before build / upload: f32 rows feed the

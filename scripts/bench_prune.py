@@ -39,5 +39,7 @@ out = {"dist": dist, "rows": n, "d": d, "nlist": nlist, "batch": B, "nprobe": np
        "list_scan_ms": round(float(np.mean(ix.scan_times())), 4), "queries_per_sec": round(B / dt, 1),
        "planned_gb": round(ls["streamed_rows"] * (2 * d + 4) / 1e9, 3), "rescanned_queries": int(ix.prescan_stats()["fallback_queries"]),
        "prune_last": ix.prune_stats()["last"] if hasattr(ix, "prune_stats") else None,
-       "head": ix.head_state() if hasattr(ix, "head_state") else None}
+       "head": ix.head_state() if hasattr(ix, "head_state") else None,
+       "balls": ix.ball_state() if hasattr(ix, "ball_state") else None,
+       "derive_ms": round(float(capi.build_phases()["derive_ms"]), 1) if hasattr(capi, "build_phases") else None}
 print(json.dumps(out))

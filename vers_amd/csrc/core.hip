@@ -31,6 +31,7 @@ OptEntry g_opts[] = {
     {"poison_alloc"}, {"poison_slack_bits"}, {"test_fail_sharded"}, {"memory"}, {"wide_k"}, {"assign_terms"}, {"assign_glds"},
     {"add_batch_rows"}, {"remove_batch_ids"}, {"compact_fused"}, {"pre_prune"}, {"pre_prune_first"}, {"pre_hot_single"},
     {"pre_head"}, {"pre_head_cols"}, {"pre_head_backoff"}, {"fetch_lds_min"}, {"fetch_map"},
+    {"pre_ball"}, {"pre_ball_cut"}, {"pre_ball_min_quads"},
 };
 OptEntry* opt_find(const char* name) {
   for (OptEntry& e : g_opts)

@@ -122,6 +122,10 @@ struct HeadParams {
   unsigned long long* prune_tot;
   uint32_t* done;           // blocks that have added their counters (zeroed with `last`)
   uint32_t* watch;          // pinned: <- 1 by the launch's last block when fewer than 1/8 of the tested quads died (vers_ivf::head_watch)
+  // the cold quads the ball filter left (ball_filter.hip.h), in any order, and how many; nullptr: every cold quad, hot_quads + i.  The quads
+  // that filter ruled out are in `last` / `tot` already (tested and dead): the back-off goes by the merged counts
+  const uint32_t* surv;
+  const uint32_t* n_surv;
 };
 constexpr uint32_t kHeadBackoff = 64;  // batches the split scan sits out after such a launch
 
@@ -160,6 +164,11 @@ __global__ __launch_bounds__(kWave * kHeadWaves) __attribute__((amdgpu_waves_per
   };
   // a segment's rows from its descriptor, by the source's own rule (Src::seg_span, storage_row); a quad beyond the launch's: no tiles
   auto item_of = [&](uint32_t bi) { return bi < n_quads ? src.items[4 * bi + (uint32_t)wid] : ItemDesc{0u, 0u, kNoSeg}; };
+  // the block's i-th quad: through the survivor list where there is one (one more indexed load, requested a quad ahead of its descriptor)
+  const uint32_t* const surv = hp.surv;
+  const uint32_t n_cold = surv != nullptr ? *hp.n_surv : n_quads - hot_quads;
+  auto quad_at = [&](uint32_t i) { return i < n_cold ? (surv != nullptr ? surv[i] : hot_quads + i) : 0xFFFFFFFFu; };
+  uint32_t q_cur = quad_at(blockIdx.x), q_nx = quad_at(blockIdx.x + gridDim.x);
   struct Seg { uint32_t nrows, row_s; };
   auto resolve = [&](const ItemDesc& d) {
     Seg sg;
@@ -176,11 +185,14 @@ __global__ __launch_bounds__(kWave * kHeadWaves) __attribute__((amdgpu_waves_per
       head_static_for<R>([&](auto r) { issue(r, (uint32_t)decltype(r)::value); });
     }
   };
-  enter(resolve(item_of(hot_quads + blockIdx.x)));
-  for (uint32_t bi = hot_quads + blockIdx.x; bi < n_quads; bi += gridDim.x) {
+  enter(resolve(item_of(q_cur)));
+  for (uint32_t i = blockIdx.x; i < n_cold; i += gridDim.x) {
+    const uint32_t bi = q_cur;
     // the next quad's segment: its descriptor is requested here, resolved behind the staging barriers and entered at the end of this
     // quad's tiles -- none of the three dependent loads stands between the last tile and the next segment's first loads
-    const ItemDesc d_next = item_of(bi + gridDim.x);
+    const ItemDesc d_next = item_of(q_nx);
+    q_cur = q_nx;
+    q_nx = quad_at(i + 2u * gridDim.x);
     __syncthreads();  // the previous quad's operands and verdict are done with
     const ItemDesc d0 = src.items[4 * bi];
     const uint32_t c0 = src.cnt[d0.list] - d0.group * (uint32_t)NQ;

@@ -14,6 +14,7 @@
 #include "gemm.hip.h"
 #include "ivf_handle.hpp"
 #include "prescan.hip.h"
+#include "ball_filter.hip.h"
 #include "head_filter.hip.h"
 #include "update_plan.hpp"
 
@@ -885,6 +886,81 @@ int32_t build_head(vers_ivf* h, hipStream_t st) {
   return VERS_OK;
 }
 
+// The lists' sub-cluster balls (ball_filter.hip.h) from the fp16 shadow and the stored |x|^2: a block per list slot.  Wanted where the
+// int8 head is wanted (squared L2, unsharded, a valid shadow) and option "pre_ball" is not 0; the cut of the farthest-point pass is option
+// "pre_ball_cut" in thousandths of sqrt(max |x|^2) (default 900).  Optional memory like the head: a failed allocation -- of any of
+// its buffers, the counters included -- leaves balls_valid false, silently.  The derive pass writes at the cap of 32 places per list into
+// scratch; what it kept is packed into [sum of k_c][ld] with ball_off / ball_cnt per slot and the scratch released.  When fewer than 1/8 of the non-empty lists got balls -- rows without cluster contrast -- everything is released:
+// such an index pays nothing per batch.  Synchronises st.
+int32_t build_balls(vers_ivf* h, hipStream_t st) {
+  h->balls_valid = false;
+  h->ball_lists = 0;
+  h->ball_sub = 0;
+  const uint32_t k = h->k;
+  const bool want = opt_get("pre_ball", kPreBallDefault) != 0 && opt_get("pre_head", kPreHeadDefault) != 0 && h->world == 1 && h->metric == 0 && shadow_mode() != 0 && h->shadow_valid &&
+                    h->rows_bf.p != nullptr && h->pre_misc.p != nullptr && h->xnorm.p != nullptr && h->cap_rows != 0 && k != 0 && h->ld >= 64u && h->ld <= kBallMaxLd &&
+                    h->slot_off.p != nullptr && h->slot_len.p != nullptr;
+  auto drop = [&]() {
+    (void)hipGetLastError();
+    h->ball_cent.release();
+    h->ball_f.release();
+    h->ball_cnt.release();
+    h->ball_off.release();
+    return VERS_OK;
+  };
+  if (!want) return drop();
+  // optional memory, every piece of it: whatever cannot be had leaves the handle without balls, silently
+  auto optional = [&](DevBuf& b, size_t need) {
+    if (need <= b.cap && b.p != nullptr) return true;
+    b.release();
+    size_t free_b = 0, total_b = 0;
+    (void)hipMemGetInfo(&free_b, &total_b);
+    void* p = nullptr;
+    if (need + (size_t(4) << 30) <= free_b && hipMalloc(&p, need) == hipSuccess) { b.p = p; b.cap = need; dev_mem_account((int64_t)need); return true; }
+    (void)hipGetLastError();
+    return false;
+  };
+  if (!h->ball_ctr.p) {
+    if (!optional(h->ball_ctr, 64)) return drop();
+    if (hipMemset(h->ball_ctr.p, 0, 64) != hipSuccess) { h->ball_ctr.release(); return drop(); }
+  }
+  // the derive pass writes at the cap, kBallMax places per list; what it kept is packed behind it and the cap-sized scratch released
+  DevBuf cent_cap, f_cap;
+  if (!optional(cent_cap, (size_t)k * kBallMax * h->ld * sizeof(uint16_t)) || !optional(f_cap, (size_t)k * kBallMax * 3 * sizeof(float)) ||
+      !optional(h->ball_cnt, (size_t)k * sizeof(uint32_t)) || !optional(h->ball_off, (size_t)k * sizeof(uint32_t)))
+    return drop();
+  const double cut = (double)std::max<int64_t>(1, std::min<int64_t>(opt_get("pre_ball_cut", 900), 4000)) / 1000.0;
+  const size_t lds = ball_derive_lds_bytes(h->ld);
+  VERS_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(ball_derive_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL(ball_derive_kernel, dim3(k), dim3(kBallDeriveThreads), lds, st, (const uint16_t*)h->rows_bf.as<uint16_t>(), h->ld, (const uint32_t*)h->slot_off.as<uint32_t>(),
+                     (const uint32_t*)h->slot_len.as<uint32_t>(), (const float*)h->xnorm.as<float>(), (const uint32_t*)h->pre_misc.as<uint32_t>(), (float)(cut * cut),
+                     cent_cap.as<uint16_t>(), f_cap.as<float>(), h->ball_cnt.as<uint32_t>());
+  VERS_HIP_TRY(hipGetLastError());
+  std::vector<uint32_t> cnt(k, 0u), len(k, 0u), boff(k, 0u);
+  VERS_HIP_TRY(hipMemcpyAsync(cnt.data(), h->ball_cnt.p, (size_t)k * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+  VERS_HIP_TRY(hipMemcpyAsync(len.data(), h->slot_len.p, (size_t)k * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+  VERS_HIP_TRY(hipStreamSynchronize(st));
+  uint32_t with = 0, non_empty = 0;
+  uint64_t sub = 0;
+  for (uint32_t c = 0; c < k; ++c) {
+    non_empty += len[c] != 0u ? 1u : 0u;
+    with += cnt[c] != 0u ? 1u : 0u;
+    boff[c] = (uint32_t)sub;
+    sub += std::min<uint32_t>(cnt[c], kBallMax);
+  }
+  if (with == 0u || 8ull * with < non_empty) return drop();
+  if (!optional(h->ball_cent, (size_t)sub * h->ld * sizeof(uint16_t)) || !optional(h->ball_f, (size_t)sub * 3 * sizeof(float))) return drop();
+  VERS_HIP_TRY(hipMemcpyAsync(h->ball_off.p, boff.data(), (size_t)k * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+  hipLaunchKernelGGL(ball_pack_kernel, dim3(k), dim3(256), 0, st, (const uint16_t*)cent_cap.as<uint16_t>(), (const float*)f_cap.as<float>(), (const uint32_t*)h->ball_cnt.as<uint32_t>(),
+                     (const uint32_t*)h->ball_off.as<uint32_t>(), h->ld, h->ball_cent.as<uint16_t>(), h->ball_f.as<float>());
+  VERS_HIP_TRY(hipGetLastError());
+  VERS_HIP_TRY(hipStreamSynchronize(st));  // (boff and the scratch go out of scope here)
+  h->ball_lists = with;
+  h->ball_sub = sub;
+  h->balls_valid = true;
+  return VERS_OK;
+}
+
 // |x|^2 of storage rows [r_begin, r_end) for the matrix-core list scan; a full refresh also resets the maximum
 int32_t refresh_norms(vers_ivf* h, uint64_t r_begin, uint64_t r_end, hipStream_t st) {
   if (int32_t rc = h->pre_misc.reserve(64)) return rc;
@@ -904,6 +980,7 @@ int32_t refresh_norms(vers_ivf* h, uint64_t r_begin, uint64_t r_end, hipStream_t
   const bool shadow = shadow_mode() != 0;
   if (full) h->shadow_valid = false;
   h->head_valid = false;  // rows change: a full refresh builds the int8 head again (below), a partial one leaves it invalid
+  h->balls_valid = false;  // (the lists' balls likewise)
   if (shadow) {
     if (full) {
       const size_t need = (h->cap_rows ? h->cap_rows : 1) * (size_t)h->ld * sizeof(uint16_t);
@@ -959,7 +1036,10 @@ int32_t refresh_norms(vers_ivf* h, uint64_t r_begin, uint64_t r_end, hipStream_t
                        h->row_ids.as<uint32_t>(), r_begin, r_end, h->xnorm.as<float>(), h->pre_misc.as<uint32_t>());
     VERS_HIP_TRY(hipGetLastError());
   }
-  if (full) return build_head(h, st);
+  if (full) {
+    if (int32_t rc = build_head(h, st)) return rc;
+    return build_balls(h, st);
+  }
   return VERS_OK;
 }
 
@@ -1959,6 +2039,7 @@ static void ab_count(int slot, double v, double* acc = g_ab) {
 static int32_t refresh_tiles(vers_ivf* h, const uint32_t* tiles, uint32_t nt, hipStream_t st) {
   if (nt == 0) return VERS_OK;
   h->head_valid = false;  // the int8 head does not follow tile lists: the list scan is one launch again until a compact or a full refresh
+  h->balls_valid = false;
   const uint64_t n_rows = (uint64_t)nt * 64;
   if (shadow_mode() != 0) {
     if (h->shadow_valid) {
@@ -2789,6 +2870,7 @@ int32_t compact_locked(vers_ivf* h, uint64_t* out_before, uint64_t* out_after) {
     // the old shadow and row-major copy go first: they are derived, the new ones take their room
     h->shadow_valid = false;
     h->head_valid = false;
+    h->balls_valid = false;
     h->rows_bf.release();
     h->rows_h8.release();
     h->rows_rm.release();
@@ -2879,6 +2961,7 @@ int32_t compact_locked(vers_ivf* h, uint64_t* out_before, uint64_t* out_after) {
     if (int32_t rc = clk.done()) return rc;
   } else {
     if (int32_t rc = build_head(h, st)) return rc;  // (the fused pass wrote every other derived array; the head is derived from the new tiles here)
+    if (int32_t rc = build_balls(h, st)) return rc;
   }
   VERS_HIP_TRY(hipDeviceSynchronize());
   if (out_before) *out_before = before;
@@ -2989,6 +3072,7 @@ int32_t recluster_locked(vers_ivf* h, uint64_t num_clusters, uint64_t num_attemp
     // the old shadow, head and row-major copy go first: they are derived, the new tiles take their room
     h->shadow_valid = false;
     h->head_valid = false;
+    h->balls_valid = false;
     h->rows_bf.release();
     h->rows_h8.release();
     h->rows_rm.release();

@@ -143,6 +143,8 @@ struct SearchWs {
   const uint32_t* prune_last = nullptr;  // device: the last matrix-core scan's step counters (nullptr: it ran with the early abandon off)
   DevBuf head_q8, head_q;                // the batch's int8 query rows [b][H] and { head_extra, s_n } [b][2] (prune_table_kernel; head_filter.hip.h)
   const uint32_t* head_last = nullptr;   // device: the last split scan's filter counters (nullptr: the scan was one launch)
+  DevBuf ball_qh, ball_q, ball_surv;     // the batch's q' rows [b][ld] fp16 and { ball_bracket, nq' } [b][2] (prune_table_kernel); the cold quads the balls left (ball_filter.hip.h)
+  const uint32_t* ball_last = nullptr;   // device: the last split scan's ball counters (nullptr: the ball pass was not launched)
   const GroupTotals* tot_dev = nullptr;  // device totals of the last planned search
   bool tot_valid = false;
   // lease bookkeeping
@@ -318,6 +320,14 @@ struct vers_ivf {
   // clears it and the handle's scans stay single launches for the next kHeadBackoff batches, then try again.
   uint32_t* head_watch = nullptr;
   std::atomic<uint32_t> head_backoff{0};
+  // Sub-cluster balls of the lists (ball_filter.hip.h): per list slot up to kBallMax centres (fp16 [ball_off[slot] + j][ld]), three
+  // floats per sub-cluster (radius | smallest stored |x|^2, NaN = open | |centre|), the first sub-cluster and the count per slot.  Derived and invalidated
+  // exactly where the int8 head is, optional memory like it; released when too few lists show cluster contrast (build_balls).
+  DevBuf ball_cent, ball_f, ball_cnt, ball_off;
+  bool balls_valid = false;  // (written under the exclusive lock, like head_valid)
+  uint32_t ball_lists = 0;   // lists with balls
+  uint64_t ball_sub = 0;     // sub-clusters over all lists
+  DevBuf ball_ctr;           // u64 [2] units (list, group) tested | dead by ball_filter_kernel, over the handle's life
   std::atomic<bool> shadow_off{false};
   bool shadow_valid = false;            // rows_bf mirrors every stored row of the CURRENT index (written under the exclusive lock)
   uint32_t* fail_watch = nullptr;       // pinned: cumulative certificate failures as of the last finished batch
@@ -610,6 +620,7 @@ int32_t upload_queries(const float* queries, uint64_t stride_bytes, uint32_t b, 
 
 // ---- ivf_build.hip -----------------------------------------------------------------------------------------------------
 int32_t refresh_norms(vers_ivf* h, uint64_t r_begin, uint64_t r_end, hipStream_t st);
+int32_t build_balls(vers_ivf* h, hipStream_t st);  // the lists' sub-cluster balls from the shadow (synchronises st); leaves balls_valid
 int32_t build_head(vers_ivf* h, hipStream_t st);  // the int8 head of the whole index from its rows (synchronises st); leaves head_valid
 int32_t poison_slack(vers_ivf* h, float value, hipStream_t st);  // test hook / option "poison_slack_bits": rows that hold no vector <- value
 

@@ -150,6 +150,32 @@ int32_t vers_ivf_head_state(vers_ivf_t* h, int32_t* out_valid, uint64_t* out_byt
   return VERS_OK;
 }
 
+int32_t vers_ivf_ball_state(vers_ivf_t* h, int32_t* out_valid, uint64_t* out_bytes, uint32_t* out_lists_with_balls, uint64_t* out_subclusters,
+                            uint64_t* out_last /* [2] */, uint64_t* out_total /* [2] */) {
+  if (!h) return fail(VERS_ERR_INVALID, "null handle");
+  DeviceGuard g(h->device);
+  unsigned long long tot[2] = {0, 0};
+  uint32_t last[2] = {0, 0};
+  {
+    UseLastWs use_ws(h);
+    if (use_ws.ok && W->ball_last != nullptr) {
+      if (W->used && W->done) VERS_HIP_TRY(hipEventSynchronize(W->done));
+      VERS_HIP_TRY(hipMemcpy(last, W->ball_last, sizeof(last), hipMemcpyDeviceToHost));
+    }
+  }
+  if (h->ball_ctr.p) VERS_HIP_TRY(hipMemcpy(tot, h->ball_ctr.p, sizeof(tot), hipMemcpyDeviceToHost));
+  const bool valid = h->balls_valid && h->ball_cent.p != nullptr;
+  if (out_valid) *out_valid = valid ? 1 : 0;
+  if (out_bytes) *out_bytes = (uint64_t)h->ball_cent.cap + h->ball_f.cap + h->ball_cnt.cap + h->ball_off.cap;
+  if (out_lists_with_balls) *out_lists_with_balls = valid ? h->ball_lists : 0u;
+  if (out_subclusters) *out_subclusters = valid ? h->ball_sub : 0u;
+  for (int i = 0; i < 2; ++i) {
+    if (out_last) out_last[i] = last[i];
+    if (out_total) out_total[i] = tot[i];
+  }
+  return VERS_OK;
+}
+
 int32_t vers_ivf_scan_times(vers_ivf_t* h, float* out_ms, uint32_t cap, uint32_t* out_n, int32_t reset) {
   if (!h || !out_n || (cap && !out_ms)) return fail(VERS_ERR_INVALID, "bad arguments");
   DeviceGuard g(h->device);

@@ -756,10 +756,11 @@ int32_t plan_search(vers_ivf* h, const float* q_dev, uint64_t ldq_in, uint32_t b
   // one zero-initialised zone per batch (ONE memset): cnt, fill, hot per list | quad hand-out counter | queue of
   // uncertified queries + its count | non-finite flags per (query, probe).  The counter's twelve words: hand-out | the early abandon's
   // three step counters | the cold launch's hand-out of a split scan | the head filter's three counters | its count of finished
-  // blocks | three spare (ivf_search.hip: launch_prescan)
+  // blocks | the ball filter's survivors, units tested, units dead (ivf_search.hip: launch_prescan)
   const size_t zero_words = 3 * (size_t)k_l + 12 + (use_pre ? (size_t)b + 4 + n_pj : 0);
   W->prune_last = nullptr;  // (points into the zone below: set again by the scan that counts into it)
   W->head_last = nullptr;
+  W->ball_last = nullptr;
   if (int32_t rc = W->lists.reserve((zero_words + 3 * (size_t)k_l) * sizeof(uint32_t) + sizeof(GroupTotals) + 64)) return rc;
   if (int32_t rc = W->pairs.reserve(n_pj * sizeof(uint32_t))) return rc;
   if (int32_t rc = W->items.reserve(one1 ? (items_bound + 4) * sizeof(Item1Rec) : std::max<uint64_t>(1, items_bound) * sizeof(ItemDesc))) return rc;

@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "finish.hip.h"
+#include "ball_filter.hip.h"
 #include "head_filter.hip.h"
 #include "flat_shadow.hpp"
 #include "ivf_src.hip.h"
@@ -291,6 +292,7 @@ int32_t launch_prescan(vers_ivf* h, const IvfSrc<NQ>& src, uint32_t items_bound,
   p.prune_tab = nullptr; p.prune_first = 0; p.prune_until = 0; p.prune_om = 0.0f; p.prune_last = nullptr; p.prune_tot = nullptr; p.hot_single = 0u;
   W->prune_last = nullptr;
   W->head_last = nullptr;
+  W->ball_last = nullptr;
   // The int8 head (head_filter.hip.h): where tiles are abandoned early and the handle holds a valid head, the scan is THREE launches -- the
   // hot quads, the head's filter over the cold ones, the cold quads the filter left.  option "pre_head" = 0, an invalid head, candidate
   // lists of more than one key per lane or a hand-out switched off for diagnosis: one launch, as ever.
@@ -307,14 +309,25 @@ int32_t launch_prescan(vers_ivf* h, const IvfSrc<NQ>& src, uint32_t items_bound,
   }
   const bool split = prune && !head_rest && opt_get("pre_head", kPreHeadDefault) != 0 && h->head_valid && h->rows_h8.p != nullptr && H >= kHeadMinCols && H <= kHeadMaxCols && H + 64u <= h->ld &&
                      kp <= kPreMaxKp && !(p.debug & 32u) && h->head_ctr.p != nullptr && h->head_watch != nullptr && opt_get("pre_hot_single", 1) != 0;
+  // The lists' balls (ball_filter.hip.h): inside a split scan, on a handle that holds valid ones, a fourth launch in front of the head's
+  // filter rules cold quads out from the sub-cluster centres alone; the head's filter then walks the quads that are left.  option
+  // "pre_ball" = 0 or invalid balls: the three launches as they were.
+  const bool balls = split && opt_get("pre_ball", kPreBallDefault) != 0 && h->balls_valid && h->ball_cent.p != nullptr && h->ball_f.p != nullptr && h->ball_cnt.p != nullptr && h->ball_off.p != nullptr &&
+                     h->ball_ctr.p != nullptr && h->ld <= kBallMaxLd;
   if (prune) {
     if (int32_t rc = W->prune_tab.reserve((size_t)b * n_steps * sizeof(float))) return rc;
     if (split) {
       if (int32_t rc = W->head_q8.reserve((size_t)b * H)) return rc;
       if (int32_t rc = W->head_q.reserve((size_t)b * 2 * sizeof(float))) return rc;
     }
+    if (balls) {
+      if (int32_t rc = W->ball_qh.reserve((size_t)b * h->ld * sizeof(uint16_t))) return rc;
+      if (int32_t rc = W->ball_q.reserve((size_t)b * 2 * sizeof(float))) return rc;
+      if (int32_t rc = W->ball_surv.reserve(((size_t)items_bound / 4 + 1) * sizeof(uint32_t))) return rc;
+    }
     hipLaunchKernelGGL(prune_table_kernel, dim3((b + 3) / 4), dim3(256), 0, st, src.qp, src.ldq, h->ld, b, (const uint32_t*)h->pre_misc.as<uint32_t>(),
-                       W->prune_tab.as<float>(), split ? H : 0u, split ? W->head_q8.as<int8_t>() : (int8_t*)nullptr, split ? W->head_q.as<float>() : (float*)nullptr);
+                       W->prune_tab.as<float>(), split ? H : 0u, split ? W->head_q8.as<int8_t>() : (int8_t*)nullptr, split ? W->head_q.as<float>() : (float*)nullptr,
+                       balls ? W->ball_qh.as<uint16_t>() : (uint16_t*)nullptr, balls ? W->ball_q.as<float>() : (float*)nullptr);
     VERS_HIP_TRY(hipGetLastError());
     p.prune_tab = W->prune_tab.as<float>();
     p.prune_first = (uint32_t)std::max<int64_t>(1, std::min<int64_t>(opt_get("pre_prune_first", 2), n_steps));
@@ -357,7 +370,27 @@ int32_t launch_prescan(vers_ivf* h, const IvfSrc<NQ>& src, uint32_t items_bound,
   hp.done = quad_ctr + 8;
   hp.prune_last = p.prune_last; hp.prune_tot = p.prune_tot;
   hp.watch = h->head_watch;
+  hp.surv = nullptr; hp.n_surv = nullptr;
   W->head_last = quad_ctr + 5;
+  const uint32_t fblocks = std::max<uint32_t>(1u, std::min<uint32_t>((items_bound + 3u) / 4u, ((uint32_t)h->n_cu - reserve) * 2u));  // (two blocks per compute unit: the kernel is compiled for two waves per SIMD)
+  BallParams bp;
+  if (balls) {
+    bp.cent = h->ball_cent.as<uint16_t>(); bp.ballf = h->ball_f.as<float>(); bp.ball_cnt = h->ball_cnt.as<uint32_t>(); bp.ball_off = h->ball_off.as<uint32_t>();
+    bp.qh16 = W->ball_qh.as<uint16_t>(); bp.qball = W->ball_q.as<float>(); bp.bounds32 = p.bounds32;
+    bp.ld = h->ld; bp.kp = kp; bp.n_steps = n_steps;
+    // the pass engages when the cold region has at least as many quads as the head's filter has blocks: below that the filter is a single
+    // round of blocks, its time one block's latency, which a launch in front of it cannot shorten.  option "pre_ball_min_quads" (> 0)
+    // replaces the figure (tests on small indexes).
+    const int64_t mq = opt_get("pre_ball_min_quads", 0);
+    bp.min_quads = mq > 0 ? (uint32_t)std::min<int64_t>(mq, 0x7FFFFFFF) : ((uint32_t)h->n_cu - reserve) * 2u;
+    bp.surv = W->ball_surv.as<uint32_t>();
+    bp.n_surv = quad_ctr + 9;  // (the three spare words, zeroed with the hand-out counters: survivors | units tested | units dead)
+    bp.last = quad_ctr + 10;
+    bp.tot = h->ball_ctr.as<unsigned long long>();
+    bp.head_last = hp.last; bp.head_tot = hp.tot; bp.prune_last = p.prune_last; bp.prune_tot = p.prune_tot;
+    hp.surv = bp.surv; hp.n_surv = bp.n_surv;
+    W->ball_last = quad_ctr + 10;
+  }
   if (int32_t rc = scan_prepare_launch(kern, lds)) return rc;
   return timed_scan(st, [&]() -> int32_t {
     PreParams ph = p, pc = p;
@@ -366,7 +399,10 @@ int32_t launch_prescan(vers_ivf* h, const IvfSrc<NQ>& src, uint32_t items_bound,
     pc.next_quad = quad_ctr + 4;  // the cold launch's own counter: starts at zero, counts from the first cold quad
     hipLaunchKernelGGL(kern, dim3(blocks), dim3(kWave * kPreWavesG), lds, st, src, ph);
     // a block per cold quad, striding; how many there are is on the device (GroupTotals): the grid is what the CUs hold at once
-    const uint32_t fblocks = std::max<uint32_t>(1u, std::min<uint32_t>((items_bound + 3u) / 4u, ((uint32_t)h->n_cu - reserve) * 2u));  // (two blocks per compute unit: the kernel is compiled for two waves per SIMD)
+    if (balls) {  // a block per cold quad, striding: four blocks per compute unit at most
+      const uint32_t bblocks = std::max<uint32_t>(1u, std::min<uint32_t>((items_bound + 3u) / 4u, ((uint32_t)h->n_cu - reserve) * 4u));
+      hipLaunchKernelGGL((ball_filter_kernel<NQ, IvfSrc<NQ>>), dim3(bblocks), dim3(kWave * kBallWaves), 0, st, src, bp);
+    }
     hipLaunchKernelGGL((head_filter_kernel<NQ, IvfSrc<NQ>>), dim3(fblocks), dim3(kWave * kHeadWaves), 0, st, src, hp);
     hipLaunchKernelGGL(kern, dim3(blocks), dim3(kWave * kPreWavesG), lds, st, src, pc);
     VERS_HIP_TRY(hipGetLastError());

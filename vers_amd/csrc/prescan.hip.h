@@ -60,6 +60,7 @@ constexpr uint32_t kPreColdOnly = 3u;  // the quads behind them, guided; next_qu
 // bit of ItemDesc::group in a quad's FIRST item: head_filter_kernel ruled the quad out, the cold launch skips it.  (Nothing behind the
 // scan reads the item descriptors: the exact finish and the fallback go by pairs and lists.)
 constexpr uint32_t kQuadDead = 0x80000000u;
+constexpr int64_t kPreBallDefault = 1;  // option "pre_ball": the lists' sub-cluster balls (ball_filter.hip.h) are derived with the head and used per search unless it says 0
 constexpr int64_t kPreHeadDefault = 1;  // option "pre_head": the head is built (at build / upload / compact time) and used (per search) unless it says 0
 
 struct PreParams {
@@ -1101,6 +1102,28 @@ __host__ __device__ inline double head_lower_dot(int32_t I_min, double norm_term
 __host__ __device__ inline double head_lower(int32_t I_min, uint32_t N_min, float s_x, float s_n, double Rh2, double om_eps, float bracket) {
   return head_lower_dot(I_min, head_norm_term(N_min, s_x, Rh2, om_eps), s_x, s_n, bracket);
 }
+
+// ---- sub-cluster balls: ruling a cold (list, group) out without reading a row (ball_filter.hip.h) -----------------------------------
+// A list is cut into <= kBallMax sub-clusters at derive time; sub-cluster j keeps a centre s_j (fp16), r_j >= |x~ - s_j| for every shadow
+// row assigned to it, m_j <= the stored |x|^2 (xn) of those rows and sn_j >= |s_j|.  With q' = fp16(-2 q) as stage() rounds it and
+// nq' >= |q'|, Cauchy-Schwarz gives <x~, q'> = <s_j, q'> + <x~ - s_j, q'> >= <s_j, q'> - r_j |q'|, so the val the scan completes for a row
+// of sub-cluster j -- xn + the products as the matrix cores sum them -- is at least
+//     m_j + D_j - E_dot - r_j nq' (1 + eps) - [ common + 16 u S ]
+// D_j = <s_j, q'> as COMPUTED (fp16 x fp16 products are exact in f32; an f32 sum in any order errs by at most (ld + 2) u |s_j| |q'|, a
+// percent more for the second-order terms), `common` of pre_bound as in prune_lower, S = |q|^2 + max |x|^2.  bracket = the term in square
+// brackets per query, rounded up (ball_bracket).  Evaluated in f64 (its own roundings: the 1e-12 factors).  Every comparison is false
+// on a NaN: m_j = NaN marks an OPEN sub-cluster (a row whose |x|^2 is not finite), which never rules anything out.
+__host__ __device__ inline float ball_bracket(double qn, double xmax2, double R2, double Rq2, uint32_t d_pad) {
+  const PreBound pb = pre_bound(qn, xmax2, R2, d_pad, 0, 2, Rq2);
+  return prune_round_up(pb.common + 16.0 * 5.9604644775390625e-08 * (pb.offset + xmax2));
+}
+__host__ __device__ inline double ball_lower(float m, float D, float r, float sn, float nq, float bracket, uint32_t d_pad) {
+  if (!(__builtin_fabsf(D) < __builtin_inff()) || !(r >= 0.0f) || !(sn >= 0.0f) || !(nq >= 0.0f)) return __builtin_nan("");
+  const double e_dot = 1.01 * ((double)d_pad + 2.0) * 5.9604644775390625e-08 * (double)sn * (double)nq;
+  const double ball = (double)r * (double)nq * (1.0 + prune_eps(d_pad));
+  const double lead = (double)m + (double)D;
+  return (lead - __builtin_fabs(lead) * 1e-12) - (e_dot + ball + (double)bracket) * (1.0 + 1e-12);
+}
 // --------------------------------------------------------------------------------------------------------------------------------------
 
 // The table of a batch: a wave per query.  tab[q][c], c = 1 .. ld / 64 - 1 (entry 0 is never read): prune_tail_entry of the columns
@@ -1109,18 +1132,24 @@ constexpr uint32_t kPruneMaxSteps = 128;
 // The int8 head's part (H != 0; head_filter.hip.h): the query's int8 row q8[q][H] and qhead[q] = { head_extra, s_n }.
 constexpr uint32_t kHeadMiscMax = 4, kHeadMiscRh2 = 5;  // words of pre_misc: max |x~| over the head columns of the stored rows | Rh2 (f32 bits)
 static __global__ __launch_bounds__(256) void prune_table_kernel(const float* qp, uint32_t ldq, uint32_t ld, uint32_t b, const uint32_t* misc, float* tab,
-                                                                 uint32_t H = 0, int8_t* q8 = nullptr, float* qhead = nullptr) {
+                                                                 uint32_t H = 0, int8_t* q8 = nullptr, float* qhead = nullptr,
+                                                                 uint16_t* qh16 = nullptr, float* qball = nullptr) {
   const uint32_t q = blockIdx.x * 4u + (threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
   if (q >= b) return;  // (whole waves)
   const float* qrow = qp + (uint64_t)q * ldq;
   const uint32_t nch = ld / 64u;
   float qn = 0.0f, rq = 0.0f, mine0 = 0.0f, mine1 = 0.0f;
+  double qp2 = 0.0;
   for (uint32_t s = 0; s < nch; ++s) {
     const float v = qrow[s * 64u + (uint32_t)lane];
     const float y = -2.0f * v, hi = (float)(_Float16)y, dl = y - hi, h = -0.5f * hi;
     qn = __fadd_rn(qn, __fmul_rn(v, v));
     rq = __fadd_rn(rq, __fmul_rn(dl, dl));
+    if (qh16 != nullptr) {  // (kernel-uniform) the ball filter's part: q' itself, fp16 [b][ld], and |q'|^2 in f64
+      qh16[(uint64_t)q * ld + s * 64u + (uint32_t)lane] = __builtin_bit_cast(uint16_t, (_Float16)y);
+      qp2 += (double)hi * (double)hi;
+    }
     float t = __fmul_rn(h, h);
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) t = __fadd_rn(t, __shfl_xor(t, off, kWave));
@@ -1138,6 +1167,14 @@ static __global__ __launch_bounds__(256) void prune_table_kernel(const float* qp
   const double xmax2 = (double)__uint_as_float(misc[0]), R2 = (double)__uint_as_float(misc[2]);
   if ((uint32_t)lane < nch) tab[(uint64_t)q * nch + lane] = prune_tail_entry(suf0, (double)qn, xmax2, R2, (double)rq, ld);
   if ((uint32_t)lane + 64u < nch) tab[(uint64_t)q * nch + lane + 64u] = prune_tail_entry(suf1, (double)qn, xmax2, R2, (double)rq, ld);
+  if (qball != nullptr) {  // (kernel-uniform) ball_lower's per-query figures: bracket | nq' >= |q'|
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) qp2 += __shfl_xor(qp2, off, kWave);
+    if (lane == 0) {
+      qball[2u * q] = ball_bracket((double)qn, xmax2, R2, (double)rq, ld);
+      qball[2u * q + 1u] = prune_round_up(__builtin_sqrt(qp2) * (1.0 + 1e-12));
+    }
+  }
   if (H != 0u) {  // (kernel-uniform)
     const uint32_t hs = H / 64u;
     float hmax = 0.0f;

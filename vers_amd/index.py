@@ -752,6 +752,16 @@ class IVFFlatIndex:
         return dict(valid=bool(v.value), bytes=int(nb.value), cols=int(cols.value), last=dict(zip(keys, (int(x) for x in last))),
                     total=dict(zip(keys, (int(x) for x in tot))))
 
+    def ball_state(self):
+        """The sub-cluster balls of the lists (option "pre_ball"): valid, bytes, lists with balls, sub-clusters, and the ball filter's
+        counters of the last list scan and over the handle's life."""
+        v = C.c_int32(0); nb = C.c_uint64(0); nl = C.c_uint32(0); ns = C.c_uint64(0)
+        last = (C.c_uint64 * 2)(); tot = (C.c_uint64 * 2)()
+        check(lib().vers_ivf_ball_state(self._h, C.byref(v), C.byref(nb), C.byref(nl), C.byref(ns), last, tot))
+        keys = ("units_tested", "units_dead")
+        return dict(valid=bool(v.value), bytes=int(nb.value), lists_with_balls=int(nl.value), subclusters=int(ns.value),
+                    last=dict(zip(keys, (int(x) for x in last))), total=dict(zip(keys, (int(x) for x in tot))))
+
     def last_finish_ms(self):
         ms = C.c_float(0)
         check(lib().vers_ivf_last_finish_ms(self._h, C.byref(ms)))
