@@ -950,6 +950,9 @@ int32_t vers_ivf_range_search_exhaustive_sharded_dev(vers_ivf_t* h, const vers_c
  *                       invalidated with the head (vers_ivf_ball_state).  "pre_ball_cut" (900): the farthest-point cut of the derive
  *                       pass in thousandths of sqrt(max |x|^2); a list that needs more than 32 sub-clusters at the cut gets none.
  *                       "pre_ball_min_quads" (0 = twice the compute units the scan uses): cold quads below which the pass stands aside.
+ *   "pre_live_list" (1) the three-launch scan's last launch draws its quads from the list of LIVE cold quads the head's filter leaves,
+ *                       guided over their count; 0 = it walks every cold quad and skips the dead ones by their mark.  Same results
+ *                       (vers_ivf_cold_state).
  *   "scan_events" (2)   HIP event records around list-scan launches (vers_ivf_last_scan / vers_ivf_scan_times): 1 always, 0 never,
  *                       2 for batches only (the two records cost a single-query call 5.5-6 us).
  *  A/B and forced paths (tests, measurements):
@@ -974,7 +977,7 @@ int32_t vers_ivf_range_search_exhaustive_sharded_dev(vers_ivf_t* h, const vers_c
  *                       turns the whole tile through LDS instead of reading the wanted rows' 16-byte pieces directly (1 = always, above 64 = never).  "fetch_map" (1): 0 = no vec id ->
  *                       storage row map on the handle, every fetch builds a table of its own requests (what a failed allocation does).
  *   "scan_debug" (0), "poison_alloc" (-1), "poison_slack_bits" (-1), "test_fail_sharded" (0)   diagnosis: phase stamps / skipped
- *                       phases, new device buffers filled with a byte, slack rows filled with an f32 bit pattern, the next n sharded
+ *                       phases ("scan_debug" & 256 with & 16: a split scan's stamps from its cold launch alone), new device buffers filled with a byte, slack rows filled with an f32 bit pattern, the next n sharded
  *                       searches fail locally. */
 int32_t vers_set_option(const char* name, int64_t value);
 /* Device memory the library holds in this process right now (rows, ids, scratch of every handle) and its high-water
@@ -1264,6 +1267,10 @@ int32_t vers_ivf_head_state(vers_ivf_t* h, int32_t* out_valid, uint64_t* out_byt
  * Any pointer may be NULL. */
 int32_t vers_ivf_ball_state(vers_ivf_t* h, int32_t* out_valid, uint64_t* out_bytes, uint32_t* out_lists_with_balls, uint64_t* out_subclusters,
                             uint64_t* out_last, uint64_t* out_total);
+/* The cold launch of a split list scan (options "pre_head", "pre_live_list"): cold quads the two filters left live, as the head's filter
+ * listed them | quads the cold launch scanned -- [2] of the most recent list scan (zeros when that scan was a single launch).  The two
+ * are equal whichever way the launch finds its quads; live + vers_ivf_head_state's quads ruled out = its quads tested. */
+int32_t vers_ivf_cold_state(vers_ivf_t* h, uint64_t* out_last);
 /* An fp16 shadow copy of the stored rows (+50 % corpus memory) feeds the matrix-core pre-selection of batched searches:
  * half the HBM bytes per list scan, a ~2x wider certificate window, the same exact f32 finish -- results stay
  * bit-identical.  On by default (VERS_SHADOW=0 or vers_set_option("shadow", 0) before build / upload: f32 rows feed the

@@ -41,5 +41,6 @@ out = {"dist": dist, "rows": n, "d": d, "nlist": nlist, "batch": B, "nprobe": np
        "prune_last": ix.prune_stats()["last"] if hasattr(ix, "prune_stats") else None,
        "head": ix.head_state() if hasattr(ix, "head_state") else None,
        "balls": ix.ball_state() if hasattr(ix, "ball_state") else None,
+       "cold": ix.cold_state()["last"] if hasattr(ix, "cold_state") else None,
        "derive_ms": round(float(capi.build_phases()["derive_ms"]), 1) if hasattr(capi, "build_phases") else None}
 print(json.dumps(out))

@@ -10,8 +10,9 @@
 // per segment.  From boundary 256 on, at every 64-column boundary, a wave tests head_lower (prescan.hip.h) for every live query column
 // against the query's threshold as the hot lists left it; a tile is dead at the first boundary where all columns pass, a tile that is not
 // dead by H makes the quad live and the block stops reading.  A quad whose tiles are all dead gets kKeyMax in its partial slots -- what
-// write_out leaves for the later quads of a run -- and the mark the cold launch skips it by (kQuadDead).  Dropping a dead quad drops only
-// rows whose val exceeds a threshold fold would have compared them with: the results stay bit-identical.
+// write_out leaves for the later quads of a run -- and the mark a cold launch that walks every quad skips it by (kQuadDead); a quad that
+// stays live is appended to the list the cold launch draws from (HeadParams::live).  Dropping a dead quad drops only rows whose val
+// exceeds a threshold fold would have compared them with: the results stay bit-identical.
 //
 // Nearly every tile is decided at the first boundary, so a wave treats the first 256 columns of its segment's tiles as ONE stream and keeps
 // a ring of kHeadRing 4 KiB steps of it in flight across tile ends and verdicts; its next segment's first loads go out before the barriers
@@ -126,6 +127,10 @@ struct HeadParams {
   // that filter ruled out are in `last` / `tot` already (tested and dead): the back-off goes by the merged counts
   const uint32_t* surv;
   const uint32_t* n_surv;
+  // the quads this filter leaves live, appended in any order, and how many (zeroed with `last`): every cold quad is either marked dead by
+  // one of the two filters or listed here, and the scan's cold launch draws from the list (PreParams::live)
+  uint32_t* live;
+  uint32_t* n_live;
 };
 constexpr uint32_t kHeadBackoff = 64;  // batches the split scan sits out after such a launch
 
@@ -336,6 +341,8 @@ __global__ __launch_bounds__(kWave * kHeadWaves) __attribute__((amdgpu_waves_per
         ctr_l[1] += 1u;
         ctr_l[3] += tiles_l;
       }
+    } else if (threadIdx.x == 0) {
+      hp.live[atomicAdd(hp.n_live, 1u)] = bi;
     }
     if (threadIdx.x == 0) ctr_l[0] += 1u;
   }

@@ -145,6 +145,8 @@ struct SearchWs {
   const uint32_t* head_last = nullptr;   // device: the last split scan's filter counters (nullptr: the scan was one launch)
   DevBuf ball_qh, ball_q, ball_surv;     // the batch's q' rows [b][ld] fp16 and { ball_bracket, nq' } [b][2] (prune_table_kernel); the cold quads the balls left (ball_filter.hip.h)
   const uint32_t* ball_last = nullptr;   // device: the last split scan's ball counters (nullptr: the ball pass was not launched)
+  DevBuf cold_live;                      // the cold quads the filters left live, as head_filter_kernel appends them: what the scan's cold launch draws from
+  const uint32_t* cold_last = nullptr;   // device: [2] live cold quads listed | quads the cold launch scanned, last split scan (nullptr: the scan was one launch)
   const GroupTotals* tot_dev = nullptr;  // device totals of the last planned search
   bool tot_valid = false;
   // lease bookkeeping

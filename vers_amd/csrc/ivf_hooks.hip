@@ -176,6 +176,22 @@ int32_t vers_ivf_ball_state(vers_ivf_t* h, int32_t* out_valid, uint64_t* out_byt
   return VERS_OK;
 }
 
+int32_t vers_ivf_cold_state(vers_ivf_t* h, uint64_t* out_last /* [2] */) {
+  if (!h || !out_last) return fail(VERS_ERR_INVALID, "bad arguments");
+  DeviceGuard g(h->device);
+  uint32_t last[2] = {0, 0};
+  {
+    UseLastWs use_ws(h);
+    if (use_ws.ok && W->cold_last != nullptr) {
+      if (W->used && W->done) VERS_HIP_TRY(hipEventSynchronize(W->done));
+      VERS_HIP_TRY(hipMemcpy(last, W->cold_last, sizeof(last), hipMemcpyDeviceToHost));
+    }
+  }
+  out_last[0] = last[0];
+  out_last[1] = last[1];
+  return VERS_OK;
+}
+
 int32_t vers_ivf_scan_times(vers_ivf_t* h, float* out_ms, uint32_t cap, uint32_t* out_n, int32_t reset) {
   if (!h || !out_n || (cap && !out_ms)) return fail(VERS_ERR_INVALID, "bad arguments");
   DeviceGuard g(h->device);

@@ -267,7 +267,7 @@ int32_t launch_prescan(vers_ivf* h, const IvfSrc<NQ>& src, uint32_t items_bound,
   p.ld = h->ld;
   p.n_chunks = h->ld / kChunk;
   p.kp = kp;
-  p.status = W->st_word();
+  p.live = nullptr;
   p.bounds32 = reinterpret_cast<uint32_t*>(W->partials.as<uint64_t>() + W->ivf_bounds_off);  // 0xFF-initialised with the slots
   p.qflags = qflags;
   p.xnorm = h->xnorm.as<float>();
@@ -293,6 +293,7 @@ int32_t launch_prescan(vers_ivf* h, const IvfSrc<NQ>& src, uint32_t items_bound,
   W->prune_last = nullptr;
   W->head_last = nullptr;
   W->ball_last = nullptr;
+  W->cold_last = nullptr;
   // The int8 head (head_filter.hip.h): where tiles are abandoned early and the handle holds a valid head, the scan is THREE launches -- the
   // hot quads, the head's filter over the cold ones, the cold quads the filter left.  option "pre_head" = 0, an invalid head, candidate
   // lists of more than one key per lane or a hand-out switched off for diagnosis: one launch, as ever.
@@ -319,6 +320,7 @@ int32_t launch_prescan(vers_ivf* h, const IvfSrc<NQ>& src, uint32_t items_bound,
     if (split) {
       if (int32_t rc = W->head_q8.reserve((size_t)b * H)) return rc;
       if (int32_t rc = W->head_q.reserve((size_t)b * 2 * sizeof(float))) return rc;
+      if (int32_t rc = W->cold_live.reserve(((size_t)items_bound / 4 + 1) * sizeof(uint32_t))) return rc;
     }
     if (balls) {
       if (int32_t rc = W->ball_qh.reserve((size_t)b * h->ld * sizeof(uint16_t))) return rc;
@@ -371,7 +373,9 @@ int32_t launch_prescan(vers_ivf* h, const IvfSrc<NQ>& src, uint32_t items_bound,
   hp.prune_last = p.prune_last; hp.prune_tot = p.prune_tot;
   hp.watch = h->head_watch;
   hp.surv = nullptr; hp.n_surv = nullptr;
+  hp.live = W->cold_live.as<uint32_t>(); hp.n_live = quad_ctr + kQuadCtrLive;
   W->head_last = quad_ctr + 5;
+  W->cold_last = quad_ctr + kQuadCtrLive;
   const uint32_t fblocks = std::max<uint32_t>(1u, std::min<uint32_t>((items_bound + 3u) / 4u, ((uint32_t)h->n_cu - reserve) * 2u));  // (two blocks per compute unit: the kernel is compiled for two waves per SIMD)
   BallParams bp;
   if (balls) {
@@ -396,7 +400,13 @@ int32_t launch_prescan(vers_ivf* h, const IvfSrc<NQ>& src, uint32_t items_bound,
     PreParams ph = p, pc = p;
     ph.hot_single = kPreHotOnly;
     pc.hot_single = kPreColdOnly;
-    pc.next_quad = quad_ctr + 4;  // the cold launch's own counter: starts at zero, counts from the first cold quad
+    pc.next_quad = quad_ctr + kQuadCtrCold;  // the cold launch's own counter: starts at zero, counts from the first cold quad ...
+    // ... or, by default, positions of the list of live quads the head's filter leaves.  option "pre_live_list" = 0: the walk over every
+    // cold quad, the dead ones skipped by their mark (A/B runs, the tests' reference)
+    if (opt_get("pre_live_list", 1) != 0) pc.live = hp.live;
+    // diagnosis, option "scan_debug" & 256 (with & 16): the phase stamps, which both launches add into the same words, are taken by the
+    // cold launch alone
+    if (p.debug & 256u) { ph.debug &= ~16u; ph.stamps = nullptr; }
     hipLaunchKernelGGL(kern, dim3(blocks), dim3(kWave * kPreWavesG), lds, st, src, ph);
     // a block per cold quad, striding; how many there are is on the device (GroupTotals): the grid is what the CUs hold at once
     if (balls) {  // a block per cold quad, striding: four blocks per compute unit at most

@@ -57,6 +57,11 @@ constexpr uint32_t kPreMaxP = 1024;  // most probed lists per query on the matri
 // hot_single of a SPLIT scan (ivf_search.hip: launch_prescan; the int8 head's filter, head_filter.hip.h, runs between the two launches)
 constexpr uint32_t kPreHotOnly = 2u;   // the quads of the hot lists alone, singly
 constexpr uint32_t kPreColdOnly = 3u;  // the quads behind them, guided; next_quad is a counter of this launch's own
+// words of the per-batch counter block (ivf_plan.hip: quad_ctr; zeroed with the planning tables) and, of a split scan's last two, where
+// they stand from the cold launch's hand-out counter -- the only pointer into the block that launch holds
+constexpr uint32_t kQuadCtrWords = 16;
+constexpr uint32_t kQuadCtrCold = 4, kQuadCtrLive = 12, kQuadCtrSeen = 13;  // the cold launch's hand-out | live cold quads listed | quads it scanned
+constexpr uint32_t kPreLiveCnt = kQuadCtrLive - kQuadCtrCold, kPreColdSeen = kQuadCtrSeen - kQuadCtrCold;
 // bit of ItemDesc::group in a quad's FIRST item: head_filter_kernel ruled the quad out, the cold launch skips it.  (Nothing behind the
 // scan reads the item descriptors: the exact finish and the fallback go by pairs and lists.)
 constexpr uint32_t kQuadDead = 0x80000000u;
@@ -66,7 +71,10 @@ constexpr int64_t kPreHeadDefault = 1;  // option "pre_head": the head is built 
 struct PreParams {
   uint32_t ld, n_chunks, kp;
   uint32_t hot_single;  // != 0: the quads of the hot lists are handed out singly (pre_run_len below; Src::hot_items() says how many there are); 2, 3: see above
-  uint32_t* status;
+  // the cold launch of a split scan (kPreColdOnly): the quads the filters left live, in any order -- head_filter_kernel appends them, their
+  // count is next_quad[kPreLiveCnt] -- and the launch hands out POSITIONS of this list; nullptr (option "pre_live_list" = 0): it walks every
+  // cold quad and skips the dead ones by their mark
+  const uint32_t* live;
   uint32_t* bounds32;   // per merge group: order bits of the smallest known kp-th val (0xFFFFFFFF = none yet)
   uint32_t* qflags;     // per merge group: != 0 -> a non-finite val was seen, the query must be re-done exactly
   uint32_t* next_quad;
@@ -781,7 +789,18 @@ __global__ __launch_bounds__(kWave * kPreWavesG) __attribute__((amdgpu_waves_per
         if constexpr (PR) {
           if (p.hot_single != 0u) hot_quads = src.hot_items() / 4u;
           if (p.hot_single == kPreHotOnly) upto = hot_quads < n_quads ? hot_quads : n_quads;
-          if (p.hot_single == kPreColdOnly) { base = hot_quads < n_quads ? hot_quads : n_quads; hot_quads = 0u; }
+          if (p.hot_single == kPreColdOnly) {
+            if (!WIDE && p.live != nullptr) {  // (a split scan keeps one key per lane: the wide-list kernels are never its cold launch)
+              // positions of the live list, not quad numbers: how many it holds is on the device, read like the hot count (the filters
+              // have finished).  Guided over the LIVE count: a hundred-odd live quads over twice as many blocks go out one per block, and
+              // an empty list sends every block home at its first draw.  (Never more than the launch's quads: the list's capacity.)
+              const uint32_t n_live = __hip_atomic_load(p.next_quad + kPreLiveCnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+              upto = n_live < n_quads ? n_live : n_quads;
+            } else {
+              base = hot_quads < n_quads ? hot_quads : n_quads;
+            }
+            hot_quads = 0u;
+          }
         }
         const uint32_t seen = base + __hip_atomic_load(p.next_quad, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         const uint32_t r = pre_run_len(seen, upto, hot_quads, n_res);
@@ -795,13 +814,28 @@ __global__ __launch_bounds__(kWave * kPreWavesG) __attribute__((amdgpu_waves_per
     }
     if (start >= lim) break;
     const uint32_t end = start + count < lim ? start + count : lim;
-    for (uint32_t bi = start; bi < end; ++bi) {
+    for (uint32_t at = start; at < end; ++at) {
+    uint32_t bi = at;
+    if constexpr (PR && !WIDE)
+      if (p.live != nullptr) {  // (kernel-uniform) the cold launch over the live list: `at` is a position, the quad is the list's entry
+        bi = (uint32_t)__builtin_amdgcn_readfirstlane((int)p.live[at]);
+        // (block-uniform) no address is formed from anything but a quad of this launch.  An entry below the hot region's end would pass:
+        // only head_filter_kernel writes the list, and it appends cold quads alone (its own walk starts at hot_quads)
+        if (bi >= n_quads) {
+          __syncthreads();
+          continue;
+        }
+      }
     const ItemDesc d0 = src.items[4 * bi];
-    if constexpr (PR)
-      if (d0.group & kQuadDead) {  // (block-uniform) the head filter ruled every tile of the quad out and filled its partial slots; a skipped quad also ends a run (`cont` below)
+    if constexpr (PR) {
+      // (block-uniform) the walk over every cold quad (no live list): a filter ruled every tile of the quad out and filled its partial
+      // slots; a skipped quad also ends a run (`cont` below).  The live list holds no such quad.
+      if (d0.group & kQuadDead) {
         __syncthreads();  // (a block that skips a whole run meets no other barrier before thread 0 rewrites the hand-out words)
         continue;
       }
+      if (!WIDE && p.hot_single == kPreColdOnly && threadIdx.x == 0) atomicAdd(p.next_quad + kPreColdSeen, 1u);  // quads the cold launch scanned
+    }
     // (block-uniform.  Only the quad right behind the run's last one: the slots written empty must be this block's own)
     const bool cont = run_first != 0xFFFFFFFFu && bi == run_last + 1 && d0.list == cur_list && d0.group == cur_group;
     const uint32_t it = bi * 4 + (wid & 3);

@@ -762,6 +762,12 @@ class IVFFlatIndex:
         return dict(valid=bool(v.value), bytes=int(nb.value), lists_with_balls=int(nl.value), subclusters=int(ns.value),
                     last=dict(zip(keys, (int(x) for x in last))), total=dict(zip(keys, (int(x) for x in tot))))
 
+    def cold_state(self):
+        """The cold launch of the last split list scan: cold quads the filters left live (as listed) and quads the launch scanned."""
+        last = (C.c_uint64 * 2)()
+        check(lib().vers_ivf_cold_state(self._h, last))
+        return dict(last=dict(quads_live=int(last[0]), quads_scanned=int(last[1])))
+
     def last_finish_ms(self):
         ms = C.c_float(0)
         check(lib().vers_ivf_last_finish_ms(self._h, C.byref(ms)))
