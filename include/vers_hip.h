@@ -567,6 +567,11 @@ int32_t vers_ivf_range_search_dev(vers_ivf_t* h, const float* queries_dev, uint6
  * coarse quantiser + plan (the exhaustive calls below: the query staging alone), [4] count pass, [5] prefix scan + read-back of the total,
  * [6] fill pass, [7] sort + decode (0 in walk order).  Calls that end in an error are not counted.  reset != 0 zeroes them. */
 int32_t vers_range_phases(double* out8, int32_t reset);
+/* The matrix-core pre-filter of the probed range search (option "range_prescan"), over the handle's life.  out4: [0] calls it served, [1]
+ * (query, row) pairs it tested -- the sum of the probed lists' lengths over the queries --, [2] candidates it left for the exact chains,
+ * [3] exact hits (the calls' totals).  A call that takes the chains (a single query, no shadow, option 0, the filtered / exhaustive / flat
+ * calls) moves none of them. */
+int32_t vers_ivf_range_stats(vers_ivf_t* h, uint64_t* out4);
 /* EXHAUSTIVE range search: the ground truth beside vers_ivf_range_search, as vers_flat_search / vers_ivf_search_exhaustive are beside the
  * approximate top-k search.  For query q: EVERY row whose distance D(q, row) -- `metric` as in vers_flat_search / vers_ivf_search_exhaustive,
  * the reference's bits: sequential f32, multiply and add rounded separately -- is <= radius[q], a plain f32 comparison (squared L2: a
@@ -953,6 +958,11 @@ int32_t vers_ivf_range_search_exhaustive_sharded_dev(vers_ivf_t* h, const vers_c
  *   "pre_live_list" (1) the three-launch scan's last launch draws its quads from the list of LIVE cold quads the head's filter leaves,
  *                       guided over their count; 0 = it walks every cold quad and skips the dead ones by their mark.  Same results
  *                       (vers_ivf_cold_state).
+ *   "range_prescan" (0) 1 = vers_ivf_range_search[_dev] and the partial / sharded probed range calls, batches of two or more queries in
+ *                       query groups on a handle with a valid fp16 shadow: a matrix-core pass over the shadow rules rows out that are
+ *                       provably beyond the radius and the ordered chains run for the rest alone (vers_ivf_range_stats).  Results are
+ *                       bit-identical.  0 = the ordered chains for every row, twice.  Off by default: measured faster only at about ten
+ *                       results per query.
  *   "scan_events" (2)   HIP event records around list-scan launches (vers_ivf_last_scan / vers_ivf_scan_times): 1 always, 0 never,
  *                       2 for batches only (the two records cost a single-query call 5.5-6 us).
  *  A/B and forced paths (tests, measurements):

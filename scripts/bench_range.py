@@ -120,6 +120,72 @@ def recall_mode(args, index, X, ld, n_modes, sigma, ranks, seed_x, seed_c):
                       f"nlist={args.nlist}), {nq} queries; phases in ms", "reps": args.reps, **out, "flat_yardstick": yard}
 
 
+def ab_prescan_mode(args, index, ld, n_modes, sigma, ranks, seed_x, seed_c):
+    """option "range_prescan" 0 (the ordered chains: the parent's code, the yardstick) against 1 (the matrix-core pre-filter + exact finish) in one
+    process, on the same index and radii: equal limits, ids and distance bits first, then the phases over alternating repeats."""
+    import torch
+    from vers_amd import capi
+
+    d, nprobe, top = args.d, args.nprobe, max(ranks)
+    found = capi.env_option("range_prescan", 1)
+    out = {}
+    try:
+        for b in (int(x) for x in args.batches.split(",")):
+            Q = torch.empty(b, ld, dtype=torch.float32, device="cuda")
+            capi.gen_rows_dev(Q.data_ptr(), b, d, ld, 1, seed_x + 1, seed_c, n_modes, sigma)
+            oi = torch.zeros(b, top, dtype=torch.int64, device="cuda"); od = torch.zeros(b, top, device="cuda")
+            oc = torch.zeros(b, dtype=torch.int32, device="cuda")
+            index.search_dev(Q.data_ptr(), ld, b, top, nprobe, oi.data_ptr(), od.data_ptr(), oc.data_ptr())
+            index.poll(); torch.cuda.synchronize()
+            assert int(oc.min()) == top, "fewer probed rows than the largest rank"
+            radii = {m: od[:, m - 1].contiguous() for m in ranks}
+            bufs = {}
+            for m in ranks:   # the results of both options, both orders: equal before anything is timed
+                for flags in (0, capi.RANGE_WALK_ORDER):
+                    got = []
+                    for opt in (0, 1):
+                        capi.set_option("range_prescan", opt)
+                        lims = torch.zeros(b + 1, dtype=torch.int64, device="cuda")
+                        total = index.range_search_dev(Q.data_ptr(), ld, b, radii[m].data_ptr(), nprobe, flags, lims.data_ptr(), 0, 0, 0)
+                        ids = torch.zeros(max(total, 1), dtype=torch.int64, device="cuda"); dist = torch.zeros(max(total, 1), device="cuda")
+                        assert index.range_search_dev(Q.data_ptr(), ld, b, radii[m].data_ptr(), nprobe, flags, lims.data_ptr(), ids.data_ptr(), dist.data_ptr(), total) == total
+                        got.append((lims, ids, dist, total))
+                    assert got[0][3] == got[1][3] and all(torch.equal(x.view(torch.int32) if x.dtype == torch.float32 else x, y.view(torch.int32) if y.dtype == torch.float32 else y)
+                                                         for x, y in zip(got[0][:3], got[1][:3])), (b, m, flags)
+                bufs[m] = got[1]
+
+            def one(m, opt):
+                capi.set_option("range_prescan", opt)
+                lims, ids, dist, total = bufs[m]
+                s0 = index.range_stats()
+                capi.range_phases(reset=True)
+                t0 = time.perf_counter()
+                assert index.range_search_dev(Q.data_ptr(), ld, b, radii[m].data_ptr(), nprobe, 0, lims.data_ptr(), ids.data_ptr(), dist.data_ptr(), total) == total
+                ph = capi.range_phases()
+                ph["call_ms"] = (time.perf_counter() - t0) * 1e3
+                s1 = index.range_stats()
+                ph["cand_frac"] = (s1["candidates"] - s0["candidates"]) / max(1, s1["pairs"] - s0["pairs"])
+                return ph
+
+            for m in ranks:
+                one(m, 0); one(m, 1)
+            runs = {(m, opt): [] for m in ranks for opt in (0, 1)}
+            for _ in range(args.reps):
+                for key in runs:
+                    runs[key].append(one(*key))
+            res = {}
+            for (m, opt), v in runs.items():
+                res[f"rank{m}_opt{opt}"] = {"results_per_query": round(bufs[m][3] / b, 1), "candidate_fraction": round(float(np.median([p["cand_frac"] for p in v])), 6),
+                                            "count_plus_fill_ms": mms([p["count_ms"] + p["fill_ms"] for p in v]),
+                                            **{k: mms([p[k] for p in v]) for k in ("call_ms", "plan_ms", "count_ms", "scan_ms", "fill_ms", "sort_ms")}}
+            out[f"batch{b}"] = res
+            log(f"[bench_range] batch {b}: {res}")
+    finally:
+        capi.set_option("range_prescan", found)
+    return {"metric": f"vers_ivf_range_search_dev, option range_prescan 0 / 1 alternating, sorted order, phases in ms, IVFFlat (N={args.rows} d={d} nlist={args.nlist}) "
+                      f"nprobe={nprobe}; results checked equal (limits, ids, distance bits, both orders) before timing", "reps": args.reps, **out}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", type=int, default=10_000_000)
@@ -133,6 +199,7 @@ def main():
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--recall", action="store_true", help="range recall against the exhaustive range search + its phases and yardstick")
     ap.add_argument("--recall-queries", type=int, default=64)
+    ap.add_argument("--ab-prescan", action="store_true", help='option "range_prescan" 0 and 1 alternating on the same index and radii, results checked equal first')
     args = ap.parse_args()
 
     import torch
@@ -156,8 +223,9 @@ def main():
     log(f"[bench_range] index built in {t_build:.2f} s")
     ranks = [int(x) for x in args.ranks.split(",")]
     top = max(ranks)
-    if args.recall:
-        line = recall_mode(args, index, X, ld, n_modes, sigma, ranks, SEED_X, SEED_C)
+    if args.recall or args.ab_prescan:
+        line = (recall_mode(args, index, X, ld, n_modes, sigma, ranks, SEED_X, SEED_C) if args.recall else
+                ab_prescan_mode(args, index, ld, n_modes, sigma, ranks, SEED_X, SEED_C))
         line["build_s"] = round(t_build, 2)
         index.close()
         print(json.dumps(line), flush=True)

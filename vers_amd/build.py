@@ -18,6 +18,8 @@ ARCH = "gfx950"
 # -ffp-contract=off: the reference rounds every product and sum separately (no FMA); see csrc/scan.hip.h
 CXXFLAGS = os.environ.get("VERS_EXTRA_CXXFLAGS", "").split() + ["-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", f"--offload-arch={ARCH}",
             "-Wall", "-Wno-unused-function"]
+# per-source additions: the range pre-filter's kernels are compiled without packed f32 VALU operations
+SRC_FLAGS = {"range_prescan.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 
 
 def _hipcc() -> str:
@@ -88,7 +90,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
         obj = os.path.join(OBJDIR, src[:-4] + ".o")
         objs.append(obj)
         if force or _stale(obj, [os.path.join(CSRC, src)] + headers):
-            cmd = [hipcc] + CXXFLAGS + ["-c", os.path.join(CSRC, src), "-o", obj]
+            cmd = [hipcc] + CXXFLAGS + SRC_FLAGS.get(src, []) + ["-c", os.path.join(CSRC, src), "-o", obj]
             if verbose:
                 print(" ".join(cmd))
             procs.append((src, subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)))

@@ -78,6 +78,9 @@ struct SearchWs {
   // range search (ivf_search.hip: range_dev_locked): the protocol's scratch | radii and CSR limits of a host-pointer call (its results: o_ids / o_dist)
   RangeScratch rg;
   DevBuf rg_rad, rg_lims;
+  // the probed range search's pre-filter (range_prescan.hip.h): one u64 per (pair, tile of the pair's list) | the pairs' tile counts and their
+  // exclusive scan (the mask's addressing) | candidates per slot | the cut per query | the scan's temporary | the waves' counter slots
+  DevBuf rp_mask, rp_tiles, rp_mbase, rp_cand, rp_cut, rp_tmp, rp_wave;
   // filtered search (filter.hip.h): one u64 per 64-row storage tile | the bitmap of a host-pointer call | the call's four counters, then a slot of four
   // words per wave a filtered scan can launch (summed into the counters by filter_stats_fold_kernel)
   DevBuf flt_mask, flt_bits, flt_stats;
@@ -270,6 +273,7 @@ struct vers_ivf {
   DevBuf xnorm, pre_misc;
   DevBuf flt_total;  // u64 [4] vers_ivf_filter_stats over the handle's life (filter_stats_fold_kernel adds every call's counters); allocated under flt_mu
   std::mutex flt_mu;
+  DevBuf rp_total;  // u64 [4] vers_ivf_range_stats over the handle's life (range_stats_fold_kernel adds every pre-filtered call's counters); allocated under flt_mu
   SearchWs* flt_last = nullptr;  // the workspace of the most recent filtered call (guarded by pool_mu)
   // Prepared filters (vers_ivf_filter_prepare): the objects still alive (guarded by flt_mu; vers_ivf_destroy frees them) and the two counters
   // their staleness protocol reads.  Both are written only while a mutator holds `index` exclusively -- when no search is in flight:

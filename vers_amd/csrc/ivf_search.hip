@@ -18,6 +18,7 @@
 #include "finish_wide.hip.h"
 #include "range_driver.hip.h"
 #include "range_merge.hip.h"
+#include "range_prescan.hip.h"
 #include "filter.hip.h"
 #include "filter_multi.hip.h"
 #include "filter_adaptive.hip.h"
@@ -1243,7 +1244,72 @@ struct ProbedRangeSource : IvfRangeSource {
     W->tot_valid = true;
     slots_per_query = (uint64_t)s.P * s.S_max;
     if ((uint64_t)b * slots_per_query >= 0xFFFFFFFFull) return fail(VERS_ERR_INVALID, "vers_ivf_range_search: batch too large (query x probe x segment slots); split the batch");
+    return prefilter_decide();
+  }
+  // The pre-filtered path (range_prescan.hip.h; option "range_prescan", default kRangePrescanDefault): a batch of two or more queries in query groups, on a handle
+  // whose shadow, |x|^2 and measured maxima are current, whose query block fits LDS and whose mask bound -- b x the tiles of the P longest
+  // lists x 8 B -- does not exceed the shadow's own bytes.  Everything else keeps the chains.
+  bool allow_prefilter = true, prefilter = false;
+  size_t mask_bytes = 0;
+  int32_t prefilter_decide() {
+    prefilter = false;
+    const size_t shadow_bytes = h->cap_rows * (size_t)h->ld * sizeof(uint16_t);
+    if (!allow_prefilter || opt_get("range_prescan", kRangePrescanDefault) == 0 || b < 2 || s.QG == 1 || shadow_mode() == 0 || h->shadow_off || !h->shadow_valid || !h->rows_bf.p ||
+        h->rows_bf.cap < shadow_bytes || !h->xnorm.p || !h->pre_misc.p || range_prefilter_lds_bytes(h->ld) > 160u * 1024u)
+      return VERS_OK;
+    std::vector<uint32_t> len(h->h_len);
+    const size_t top = std::min<size_t>(s.P, len.size());
+    std::partial_sort(len.begin(), len.begin() + (long)top, len.end(), std::greater<uint32_t>());
+    uint64_t tiles = 0;
+    for (size_t i = 0; i < top; ++i) tiles += (len[i] + (uint32_t)kWave - 1u) / (uint32_t)kWave;
+    mask_bytes = (size_t)b * tiles * sizeof(uint64_t);
+    if (mask_bytes > shadow_bytes) return VERS_OK;
+    {
+      std::lock_guard<std::mutex> lk(h->flt_mu);
+      if (!h->rp_total.p) {
+        if (int32_t rc = h->rp_total.reserve(4 * sizeof(unsigned long long))) return rc;
+        VERS_HIP_TRY(hipMemset(h->rp_total.p, 0, 4 * sizeof(unsigned long long)));
+      }
+    }
+    prefilter = true;
     return VERS_OK;
+  }
+  RangeExactParams exact_params() const {
+    RangeExactParams e;
+    e.rows = h->rows.as<float>(); e.ld = h->ld; e.ldq = h->ldq; e.qp = s.qp; e.pj_list = s.pj_list; e.pj_pref = s.pj_pref;
+    e.list_off = h->slot_off.as<uint32_t>(); e.list_len = h->slot_len.as<uint32_t>(); e.P = s.P; e.S_max = s.S_max; e.seg_rows = s.seg_rows;
+    e.seg_target = s.seg_target; e.n_slots = (uint64_t)b * s.P * s.S_max; e.mbase = W->rp_mbase.as<uint64_t>(); e.mask = W->rp_mask.as<uint64_t>();
+    e.cand = W->rp_cand.as<uint32_t>(); e.wave_slots = nullptr;
+    return e;
+  }
+  // the count tag of the pre-filtered path: cut per query, the mask's addressing, the pre-filter, the exact count, the counters' fold
+  int32_t launch_prefiltered_count(RangeParams p, hipStream_t st) const {
+    const uint64_t n_pairs = (uint64_t)b * s.P, n_slots = n_pairs * s.S_max;
+    const uint32_t pre_blocks = range_prefilter_grid(h->n_cu, h->ld, (uint32_t)s.items_bound), exact_blocks = range_exact_grid(h->n_cu, n_slots);
+    const uint32_t pre_waves = pre_blocks * kWavesPerBlock, exact_waves = exact_blocks * kWavesPerBlock;
+    const size_t scan_tmp = range_scan_temp_bytes((size_t)n_pairs + 1);
+    if (int32_t rc = W->rp_cut.reserve((size_t)b * sizeof(float))) return rc;
+    if (int32_t rc = W->rp_tiles.reserve(((size_t)n_pairs + 1) * sizeof(uint32_t))) return rc;
+    if (int32_t rc = W->rp_mbase.reserve(((size_t)n_pairs + 1) * sizeof(uint64_t))) return rc;
+    if (int32_t rc = W->rp_tmp.reserve(scan_tmp)) return rc;
+    if (int32_t rc = W->rp_mask.reserve(std::max<size_t>(mask_bytes, 8))) return rc;
+    if (int32_t rc = W->rp_cand.reserve((size_t)n_slots * sizeof(uint32_t))) return rc;
+    if (int32_t rc = W->rp_wave.reserve(((size_t)pre_waves * 2 + exact_waves) * sizeof(unsigned long long))) return rc;
+    if (int32_t rc = launch_range_cut(s.qp, h->ldq, h->ld, b, h->pre_misc.as<uint32_t>(), p.radius, h->metric, W->rp_cut.as<float>(), st)) return rc;
+    if (int32_t rc = launch_range_pair_tiles(s.pj_list, h->slot_len.as<uint32_t>(), n_pairs, W->rp_tiles.as<uint32_t>(), st)) return rc;
+    if (int32_t rc = range_scan_counts(W->rp_tiles.as<uint32_t>(), W->rp_mbase.as<uint64_t>(), (size_t)n_pairs + 1, W->rp_tmp.p, scan_tmp, st)) return rc;
+    VERS_HIP_TRY(hipMemsetAsync(W->rp_cand.p, 0, (size_t)n_slots * sizeof(uint32_t), st));
+    RangePreParams pp;
+    pp.ld = h->ld; pp.rows_h = h->rows_bf.as<uint16_t>(); pp.xnorm = h->xnorm.as<float>(); pp.cut = W->rp_cut.as<float>(); pp.mbase = W->rp_mbase.as<uint64_t>();
+    pp.mask = W->rp_mask.as<uint64_t>(); pp.cand = W->rp_cand.as<uint32_t>(); pp.wave_slots = W->rp_wave.as<unsigned long long>();
+    if (int32_t rc = fresh_quad_counter(st, &pp.next_quad)) return rc;
+    if (int32_t rc = s.QG == 8 ? launch_range_prefilter(h->metric, make_ivf_src<8>(h, s, 0u), pp, pre_blocks, st)
+                               : launch_range_prefilter(h->metric, make_ivf_src<16>(h, s, 0u), pp, pre_blocks, st))
+      return rc;
+    RangeExactParams e = exact_params();
+    e.wave_slots = pp.wave_slots + (size_t)pre_waves * 2;
+    if (int32_t rc = launch_range_exact(h->metric, false, e, p, exact_blocks, st)) return rc;
+    return launch_range_stats_fold(pp.wave_slots, pre_waves, e.wave_slots, exact_waves, h->rp_total.as<unsigned long long>(), st);
   }
   bool walk_order(uint32_t flags, bool) const { return (flags & VERS_RANGE_WALK_ORDER) != 0; }
   // one pass: pass(query-group tag, metric, the items, how many) launches it over the plan's items.  Hand-out counter as launch_ivf_scan's; no
@@ -1259,6 +1325,10 @@ struct ProbedRangeSource : IvfRangeSource {
   }
   template <class Fill>
   int32_t launch(Fill, RangeParams p, hipStream_t st) const {
+    if (prefilter) {
+      if (!Fill::value) return launch_prefiltered_count(p, st);
+      return launch_range_exact(h->metric, true, exact_params(), p, range_exact_grid(h->n_cu, (uint64_t)b * s.P * s.S_max), st);
+    }
     return with_items(p, st, [&](auto qg, int metric, const auto& src, uint32_t items) -> int32_t {
       return launch_range_pass<decltype(qg)::value, Fill::value>(h->n_cu, h->ld, metric, src, items, p, st);
     });
@@ -1339,7 +1409,9 @@ struct Filtered : Base {
   static constexpr bool kProbed = std::is_same<Base, ProbedRangeSource>::value;
   FilterArg flt;
   FilterMasks masks{};
-  Filtered(vers_ivf* hh, const char* w, const float* q, uint64_t ldq, uint32_t bb, uint32_t nprobe_or_metric, const FilterArg& f) : Base(hh, w, q, ldq, bb, nprobe_or_metric), flt(f) {}
+  Filtered(vers_ivf* hh, const char* w, const float* q, uint64_t ldq, uint32_t bb, uint32_t nprobe_or_metric, const FilterArg& f) : Base(hh, w, q, ldq, bb, nprobe_or_metric), flt(f) {
+    if constexpr (kProbed) this->allow_prefilter = false;  // (the filtered walks keep the chains)
+  }
   int32_t prepare(hipStream_t st, uint64_t& slots_per_query) {
     vers_ivf* const h = this->h;
     if (int32_t rc = filter_begin(h, flt, kProbed ? h->cap_rows : stored_rows(h), st, masks)) return rc;
@@ -2055,6 +2127,18 @@ int32_t vers_ivf_filter_stats(vers_ivf_t* h, uint64_t* out4, uint64_t* out4_tota
     if (out4) out4[i] = last[i];
     if (out4_total) out4_total[i] = tot[i];
   }
+  return VERS_OK;
+}
+
+int32_t vers_ivf_range_stats(vers_ivf_t* h, uint64_t* out4) {
+  if (!h || !out4) return fail(VERS_ERR_INVALID, "null handle or out4");
+  DeviceGuard g(h->device);
+  unsigned long long tot[4] = {};
+  {
+    std::lock_guard<std::mutex> lk(h->flt_mu);
+    if (h->rp_total.p) VERS_HIP_TRY(hipMemcpy(tot, h->rp_total.p, sizeof(tot), hipMemcpyDeviceToHost));
+  }
+  for (int i = 0; i < 4; ++i) out4[i] = tot[i];
   return VERS_OK;
 }
 

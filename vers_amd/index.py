@@ -523,6 +523,13 @@ class IVFFlatIndex:
         return dict(last=dict(zip(keys, (int(v) for v in last))), total=dict(zip(keys, (int(v) for v in tot))))
 
     # -- range search (extension; the reference has search_approximate only) ---------------------------
+    def range_stats(self):
+        """vers_ivf_range_stats: the probed range search's matrix-core pre-filter (option "range_prescan") over the handle's life -- calls
+        it served, (query, row) pairs tested, candidates left for the exact chains, exact hits."""
+        out = (C.c_uint64 * 4)()
+        check(lib().vers_ivf_range_stats(self._h, out))
+        return dict(zip(("calls", "pairs", "candidates", "hits"), (int(v) for v in out)))
+
     def range_search(self, queries, radius, nprobe: int, walk_order: bool = False):
         """Every row of the min(nprobe, k) nearest lists of each query with distance <= radius (vers_ivf_range_search).  radius: a
         scalar or one value per query.  -> (lims [b + 1] u64, ids u64, dist f32), CSR: query q owns [lims[q], lims[q + 1]).  Default
