@@ -704,6 +704,16 @@ int32_t vers_ivf_search_exhaustive_filtered_multi_dev(vers_ivf_t* h, const float
                                                       uint32_t n_filters, uint64_t n_bits, const uint32_t* filter_of_dev, uint64_t* out_ids_dev,
                                                       float* out_dist_dev, uint32_t* out_count_dev, void* stream);
 int32_t vers_ivf_filter_stats(vers_ivf_t* h, uint64_t* out4, uint64_t* out4_total);
+/* Option "filter_prescan" = 1 (default 0): vers_ivf_search_filtered[_dev] -- one bitmap per call, nprobe >= 1 -- scans the LIVE tiles of the
+ * probed lists on the matrix cores over the fp16 shadow, keeps per (query, work item) the top_k + slack smallest approximate keys of the
+ * ALLOWED rows and finishes exactly as the unfiltered batched search does (certificate, ordered chains for the survivors; queries whose
+ * certificate fails are re-scanned over their allowed rows by the ordered chain).  Ids, order, counts, distance bits and the latched status
+ * are the chain path's.  Taken when the batch is at least option "pre_min_batch", the plan groups queries (8 or 16 per list), top_k <= 48,
+ * min(nprobe, k) <= 64, the handle is unsharded and its shadow valid and in use, and option "prescan" is not 0; silently the ordered chains
+ * otherwise.  The _multi, _adaptive, prepared, partial / sharded, exhaustive and range forms keep the chains.  vers_ivf_filter_stats counts
+ * planned tiles, loaded tiles and skipped items on either path.
+ * vers_ivf_filter_prescan_stats, over the handle's life: out2[0] filtered calls served by that path, out2[1] queries sent to its fallback. */
+int32_t vers_ivf_filter_prescan_stats(vers_ivf_t* h, uint64_t* out2);
 /* ADAPTIVE DEPTH for the probed filtered calls: every query of the batch probes lists until enough allowed rows are in reach, instead of one
  * nprobe sized for the batch's worst query.  Under a selective filter out_count[q] of the plain calls is often below top_k; the depth a query
  * needs depends on its list ranking and on the allowed rows per list only, and the device knows both before the scan starts.
@@ -963,6 +973,9 @@ int32_t vers_ivf_range_search_exhaustive_sharded_dev(vers_ivf_t* h, const vers_c
  *                       provably beyond the radius and the ordered chains run for the rest alone (vers_ivf_range_stats).  Results are
  *                       bit-identical.  0 = the ordered chains for every row, twice.  Off by default: measured faster only at about ten
  *                       results per query.
+ *   "filter_prescan" (0) 1 = vers_ivf_search_filtered[_dev] on the matrix cores over the fp16 shadow with the exact finish, where the
+ *                       conditions stated at vers_ivf_filter_prescan_stats hold.  Results are bit-identical.  Off by default (DESIGN.md
+ *                       section 6).
  *   "scan_events" (2)   HIP event records around list-scan launches (vers_ivf_last_scan / vers_ivf_scan_times): 1 always, 0 never,
  *                       2 for batches only (the two records cost a single-query call 5.5-6 us).
  *  A/B and forced paths (tests, measurements):

@@ -893,6 +893,63 @@ def prepared_main(args):
     return 0
 
 
+def ab_prescan_mode(args, index, ld, n, n_modes, sigma, seed_x, seed_c, words):
+    """option "filter_prescan" 0 (the ordered chains: the parent's code, the yardstick) against 1 (the matrix-core scan of the allowed rows +
+    exact finish) in one process, on the same index, queries and bitmaps: equal ids, distance bits and counts first, then the whole call and
+    the list scan alone (the scan-timing ring's last record) over alternating repeats, with tiles loaded and fallback queries."""
+    import torch
+    from vers_amd import capi
+
+    d, nprobe, top_k = args.d, args.nprobe, args.top_k
+    found = {k: capi.env_option(k, v) for k, v in (("filter_prescan", 0), ("scan_events", 2))}
+    out = {}
+    try:
+        capi.set_option("scan_events", 1)
+        for b in (int(x) for x in args.batches.split(",")):
+            Q = torch.empty(b, ld, dtype=torch.float32, device="cuda")
+            capi.gen_rows_dev(Q.data_ptr(), b, d, ld, 1, seed_x + 1, seed_c, n_modes, sigma)
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+
+            def one(name, opt, bufs=None):
+                capi.set_option("filter_prescan", opt)
+                oi, od, oc = bufs or (torch.zeros(b, top_k, dtype=torch.int64, device="cuda"), torch.zeros(b, top_k, device="cuda"), torch.zeros(b, dtype=torch.int32, device="cuda"))
+                s0 = index.filter_prescan_stats()
+                index.scan_times(reset=True)
+                torch.cuda.synchronize()
+                e0.record()
+                index.search_filtered_dev(Q.data_ptr(), ld, b, top_k, nprobe, words[name].data_ptr(), n, oi.data_ptr(), od.data_ptr(), oc.data_ptr())
+                e1.record()
+                index.poll(); torch.cuda.synchronize()
+                ring = index.scan_times(reset=True)
+                s1 = index.filter_prescan_stats()
+                st = index.filter_stats()["last"]
+                return {"call_ms": e0.elapsed_time(e1), "scan_ms": float(ring[-1]), "tiles_loaded": st["tiles_loaded"], "tiles_planned": st["tiles_planned"],
+                        "served": s1["calls"] - s0["calls"], "fallback_queries": s1["fallback_queries"] - s0["fallback_queries"], "res": (oi, od, oc)}
+
+            for name in words:   # equal before anything is timed (and the warm-up of both paths)
+                r0, r1 = one(name, 0), one(name, 1)
+                c = r0["res"][2]
+                assert torch.equal(c, r1["res"][2]), (b, name, "counts")
+                live = torch.arange(top_k, device="cuda")[None, :] < c[:, None]
+                assert torch.equal(r0["res"][0][live], r1["res"][0][live]) and torch.equal(r0["res"][1].view(torch.int32)[live], r1["res"][1].view(torch.int32)[live]), (b, name)
+            runs = {(name, opt): [] for name in words for opt in (0, 1)}
+            for _ in range(args.reps):
+                for key in runs:
+                    runs[key].append(one(*key))
+            res = {}
+            for (name, opt), v in runs.items():
+                res[f"{name}_opt{opt}"] = {"call_ms": mms([r["call_ms"] for r in v]), "scan_ms": mms([r["scan_ms"] for r in v]), "tiles_loaded": v[0]["tiles_loaded"],
+                                          "tiles_planned": v[0]["tiles_planned"], "served_by_new_path": sum(r["served"] for r in v),
+                                          "fallback_queries": sum(r["fallback_queries"] for r in v)}
+            out[f"batch{b}"] = res
+            log(f"[bench_filtered] batch {b}: {json.dumps(res)}")
+    finally:
+        for k, v in found.items():
+            capi.set_option(k, v)
+    return {"metric": f"vers_ivf_search_filtered_dev, option filter_prescan 0 / 1 alternating, ms, IVFFlat (N={args.rows} d={d} nlist={args.nlist}) nprobe={nprobe} "
+                      f"top_k={top_k}; results checked equal (ids, distance bits, counts) before timing", "reps": args.reps, **out}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", type=int, default=1_000_000)
@@ -912,6 +969,7 @@ def main():
     ap.add_argument("--inner", type=int, default=8, help="--multi: back-to-back calls per timed window")
     ap.add_argument("--prepared", action="store_true", help="a prepared filter (vers_ivf_filter_prepare + the _prepared_dev calls) against the per-call entry points: see prepared_main")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r18_filtered_prepared.txt"), help="--prepared: the file every take is written to")
+    ap.add_argument("--ab-prescan", action="store_true", help='option "filter_prescan" 0 and 1 alternating on the same index, queries and bitmaps, results checked equal first')
     ap.add_argument("--shards", type=int, default=0, help="filtered search on an index sharded over this many ranks, emulated on one GPU (partials + merge): see shards_main")
     args = ap.parse_args()
     assert args.reps >= 5, "at least 5 alternating repeats per point"
@@ -955,6 +1013,13 @@ def main():
     contiguous = np.zeros(n, dtype=bool); contiguous[lo:lo + n // 100] = True
     filters["contiguous_0.01"] = contiguous
     words = {k: torch.from_numpy(capi.allowed_bitmap(v, n).view(np.int64)).cuda() for k, v in filters.items()}
+
+    if args.ab_prescan:
+        line = ab_prescan_mode(args, index, ld, n, n_modes, sigma, SEED_X, SEED_C, {k: words[k] for k in ("random_1", "random_0.1", "random_0.01", "contiguous_0.01")})
+        line["build_s"] = round(t_build, 2)
+        index.close()
+        print(json.dumps(line), flush=True)
+        return 0
 
     found = {k: capi.env_option(k, v) for k, v in (("prescan", 1), ("single_shadow", 1), ("scan_events", 2))}
     out = {}

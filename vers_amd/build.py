@@ -18,8 +18,9 @@ ARCH = "gfx950"
 # -ffp-contract=off: the reference rounds every product and sum separately (no FMA); see csrc/scan.hip.h
 CXXFLAGS = os.environ.get("VERS_EXTRA_CXXFLAGS", "").split() + ["-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", f"--offload-arch={ARCH}",
             "-Wall", "-Wno-unused-function"]
-# per-source additions: the range pre-filter's kernels are compiled without packed f32 VALU operations
-SRC_FLAGS = {"range_prescan.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
+# per-source additions: the range pre-filter's and the filtered matrix-core scan's kernels are compiled without packed f32 VALU operations
+_NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
+SRC_FLAGS = {"range_prescan.hip": _NO_PK_F32, "filter_prescan.hip": _NO_PK_F32}
 
 
 def _hipcc() -> str:

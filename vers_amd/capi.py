@@ -131,6 +131,7 @@ SIGNATURES = {
                                               C.POINTER(C.c_uint64), _vp]),
     "vers_range_phases": (C.c_int32, [C.POINTER(C.c_double), C.c_int32]),
     "vers_ivf_range_stats": (C.c_int32, [_vp, C.POINTER(C.c_uint64)]),
+    "vers_ivf_filter_prescan_stats": (C.c_int32, [_vp, C.POINTER(C.c_uint64)]),
     "vers_flat_range_search": (C.c_int32, [_vp, _vp, C.c_uint64, C.c_uint32, _vp, C.c_uint32, C.c_uint32, _vp, _vp, _vp, C.c_uint64,
                                            C.POINTER(C.c_uint64)]),
     "vers_flat_range_search_dev": (C.c_int32, [_vp, _vp, C.c_uint64, C.c_uint32, _vp, C.c_uint32, C.c_uint32, _vp, _vp, _vp, C.c_uint64,

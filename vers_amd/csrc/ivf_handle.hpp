@@ -273,6 +273,7 @@ struct vers_ivf {
   DevBuf xnorm, pre_misc;
   DevBuf flt_total;  // u64 [4] vers_ivf_filter_stats over the handle's life (filter_stats_fold_kernel adds every call's counters); allocated under flt_mu
   std::mutex flt_mu;
+  DevBuf fp_total;  // u64 [2] vers_ivf_filter_prescan_stats over the handle's life + the finish's u32 count of failed certificates on that path; allocated under flt_mu
   DevBuf rp_total;  // u64 [4] vers_ivf_range_stats over the handle's life (range_stats_fold_kernel adds every pre-filtered call's counters); allocated under flt_mu
   SearchWs* flt_last = nullptr;  // the workspace of the most recent filtered call (guarded by pool_mu)
   // Prepared filters (vers_ivf_filter_prepare): the objects still alive (guarded by flt_mu; vers_ivf_destroy frees them) and the two counters
@@ -601,6 +602,7 @@ struct SearchPlan {
   int pre_mode = 1;           // option "prescan"
   uint32_t kp = 0;            // candidate keys per partial list of the matrix-core scan (top_k + slack)
   uint32_t k_keep = 0;        // keys per partial slot
+  bool kp_slots = false;      // the ordered-chain plan with slots of kp keys and pj_nq / qflags / fail_list in place (plan_search: want_kp_slots)
   uint32_t n_pass = 1;        // 64 result ranks per pass (ordered-chain scans)
   uint32_t seg_rows = 0, seg_target = 0, S_max = 0;
   uint64_t items_bound = 0;
@@ -616,8 +618,12 @@ struct SearchPlan {
 // adaptive (nullable; with chains_only, nprobe >= 1 = nprobe_max): the lists are ranked WITHOUT the plan fused into the selection and
 // plan_queries_adaptive_kernel (filter_adaptive.hip.h) plans in plan_queries_kernel's place -- every query to its own depth; the tables are
 // sized by b x min(nprobe, k) all the same
+// want_kp_slots (with chains_only, no adaptive; filter_prescan.hip.h): where the plan groups queries (QG 8 / 16) and runs one pass, its items
+// are the chain path's but every (pair, segment) slot holds kp keys (k_keep = kp), segments are at least four tiles, and fail_list / qflags
+// sit in the zeroed zone as for the matrix-core scan; pj_nq is the caller's to fill (segments per pair).  s.kp_slots says whether it applied;
+// where it did not, the plan is the chains_only plan as it was.
 int32_t plan_search(vers_ivf* h, const float* q_dev, uint64_t ldq_in, uint32_t b, uint32_t top_k, uint32_t nprobe, hipStream_t st,
-                    SearchPlan& s, bool chains_only = false, const AdaptiveQ* adaptive = nullptr);
+                    SearchPlan& s, bool chains_only = false, const AdaptiveQ* adaptive = nullptr, bool want_kp_slots = false);
 
 // ---- ivf_search.hip ----------------------------------------------------------------------------------------------------
 int32_t search_dev_locked(vers_ivf* h, const float* q_dev, uint64_t ldq_in, uint32_t b, uint32_t top_k, uint32_t nprobe,

@@ -609,7 +609,7 @@ int32_t coarse(vers_ivf* h, const float* qp, uint32_t b, uint32_t P, hipStream_t
 // Geometry, staging, coarse quantiser and planning of one search call: everything up to the list scan's launch.  On return the
 // per-batch tables of the leased workspace are final (in stream order) and `s` says which scan the search runs.
 int32_t plan_search(vers_ivf* h, const float* q_dev, uint64_t ldq_in, uint32_t b, uint32_t top_k, uint32_t nprobe, hipStream_t st,
-                    SearchPlan& s, bool chains_only, const AdaptiveQ* adaptive) {
+                    SearchPlan& s, bool chains_only, const AdaptiveQ* adaptive, bool want_kp_slots) {
   const int ref_mode = nprobe == 0;
   { const int ev = scan_events_ref().load(); W->ev_on = ev == 1 || (ev == 2 && b > 1); }
   // reference mode ranks the 48 nearest lists (48 + 16 slack = one key per lane in the MFMA pre-selection);
@@ -714,7 +714,9 @@ int32_t plan_search(vers_ivf* h, const float* q_dev, uint64_t ldq_in, uint32_t b
   // -- one key per lane in the selection -- and runs exactly, 64 ranks per pass.  Rounds 1-5 sent nprobe > 64 to the ordered chains.)
   const bool use_pre = !chains_only && (one1_pre || (pre_batch && !ref_mode && pre_mode != 0 && (top_k + kPreMinSlack <= kPreMaxKp || wide_k) && P <= kPreMaxP && pre_nq != 0));
   if (use_pre && !one1_pre) QG = (int)pre_nq;
-  const uint32_t k_keep = use_pre ? kp : std::min<uint32_t>(top_k, kMaxTopK);
+  // the chain path's items with slots of kp keys for the exact finish (filter_prescan.hip.h): query groups, one pass
+  const bool kp_slots = want_kp_slots && chains_only && !adaptive && !ref_mode && QG != 1 && top_k + kPreMinSlack <= kPreMaxKp && use_shadow && pre_mode != 0;
+  const uint32_t k_keep = (use_pre || kp_slots) ? kp : std::min<uint32_t>(top_k, kMaxTopK);
   // 64 result ranks per pass; no pass beyond the rows the index holds (top_k = 100000 on 1000 rows: 16 passes, not 1563)
   const uint32_t n_pass = use_pre ? 1u : (uint32_t)((std::min<uint64_t>(top_k, std::max<uint64_t>(1, h->n_total)) + kMaxTopK - 1) / kMaxTopK);
   const uint64_t groups_bound = QG == 1 ? n_pj : (n_pj / QG + std::min<uint64_t>(h->k, n_pj));
@@ -738,6 +740,8 @@ int32_t plan_search(vers_ivf* h, const float* q_dev, uint64_t ldq_in, uint32_t b
   if (one1_pre) seg_rows = (uint32_t)std::min<uint64_t>(256, round_up64(std::max<uint64_t>(1, ((uint64_t)P * avg_len_all * 2) / (3 * (uint64_t)h->n_cu)), kWave));
   // (cutting the lists of a SHARDED scan into finer quads -- 2.7 whole-list quads per CU at 8 ranks -- was tried in rounds 3-4 and lost: a
   // short item pays its pipeline fill and its waves' waits for each other whatever the staging costs)
+  // (kp-wide slots: a wave keeps <= 16 lists of kp keys per item and fills them in the item's first tiles -- items of at least four tiles)
+  if (kp_slots) seg_rows = std::max<uint32_t>(seg_rows, 4u * kWave);
   if (knobs().seg_rows > 0) seg_rows = (uint32_t)round_up64(std::max(64l, knobs().seg_rows), kWave);  // tuning knob
   if (one1_pre && seg_rows > 256) seg_rows = 256;
   // matrix-core scan: per-list balanced segments of about seg_rows rows (list_seg_rows)
@@ -758,7 +762,7 @@ int32_t plan_search(vers_ivf* h, const float* q_dev, uint64_t ldq_in, uint32_t b
   // abandon's three step counters | the cold launch's hand-out of a split scan | the head filter's three counters | its count of finished
   // blocks | the ball filter's survivors, units tested, units dead | the live cold quads listed | the quads the cold launch scanned | two
   // spare (ivf_search.hip: launch_prescan; prescan.hip.h: kQuadCtr*)
-  const size_t zero_words = 3 * (size_t)k_l + kQuadCtrWords + (use_pre ? (size_t)b + 4 + n_pj : 0);
+  const size_t zero_words = 3 * (size_t)k_l + kQuadCtrWords + ((use_pre || kp_slots) ? (size_t)b + 4 + n_pj : 0);
   W->prune_last = nullptr;  // (points into the zone below: set again by the scan that counts into it)
   W->head_last = nullptr;
   W->ball_last = nullptr;
@@ -899,7 +903,7 @@ int32_t plan_search(vers_ivf* h, const float* q_dev, uint64_t ldq_in, uint32_t b
   }
   }  // batch planning
   s.P = P; s.ref_mode = ref_mode; s.one1 = one1; s.one1_pre = one1_pre; s.QG = QG; s.use_pre = use_pre; s.use_shadow = use_shadow; s.pre_hi_only = use_pre && pre_hi_only; s.pre_mode = pre_mode;
-  s.kp = kp; s.k_keep = k_keep; s.n_pass = n_pass; s.seg_rows = seg_rows; s.seg_target = seg_target; s.S_max = S_max;
+  s.kp = kp; s.k_keep = k_keep; s.kp_slots = kp_slots; s.n_pass = n_pass; s.seg_rows = seg_rows; s.seg_target = seg_target; s.S_max = S_max;
   s.items_bound = items_bound; s.part_bytes = part_bytes;
   s.pj_list = pj_list; s.pj_pref = pj_pref; s.pj_take = pj_take; s.np = np; s.pj_nq = pj_nq; s.cnt = cnt; s.pair_off = pair_off;
   s.group_off = group_off; s.quad_ctr = quad_ctr; s.fail_list = fail_list; s.qflags = qflags; s.tot = tot; s.qp = qp; s.took = took;

@@ -19,6 +19,7 @@
 #include "range_driver.hip.h"
 #include "range_merge.hip.h"
 #include "range_prescan.hip.h"
+#include "filter_prescan.hip.h"
 #include "filter.hip.h"
 #include "filter_multi.hip.h"
 #include "filter_adaptive.hip.h"
@@ -978,13 +979,60 @@ int32_t filtered_dev_locked(vers_ivf* h, const float* q_dev, uint64_t ldq_in, ui
         if (int32_t rc = adaptive.reduce(counts, (size_t)n_sets * h->k, aq.allowed_len, st)) return rc;
     }
   }
+  // The matrix-core scan of the allowed rows on the fp16 shadow + the unfiltered search's exact finish (filter_prescan.hip.h; option
+  // "filter_prescan", default kFilterPrescanDefault): one bitmap per call (prepared or not: the same mask), a whole result, a batch the
+  // matrix-core scan would take, one pass, an unsharded handle whose shadow is in use.  The plan adds: query groups.  Everything else -- and
+  // every other form of the call -- keeps the chains.
+  const bool want_pre = opt_get("filter_prescan", kFilterPrescanDefault) != 0 && !masks.per_query && flt.prep == nullptr && !adaptive.on && out_keys == nullptr && nprobe >= 1 &&
+                        b >= pre_min_batch_ref().load(std::memory_order_relaxed) && top_k + kPreMinSlack <= kPreMaxKp && std::min<uint32_t>(nprobe, h->k) <= (uint32_t)kWave &&
+                        shadow_mode() != 0 && !h->shadow_off && h->shadow_valid && h->rows_bf.p != nullptr && h->xnorm.p != nullptr && h->pre_misc.p != nullptr &&
+                        h->world == 1 && knobs().pre_mode != 0 && filter_prescan_lds_bytes(h->ld) <= 160u * 1024u;
   SearchPlan s;
   W->no_ahead = true;
-  const int32_t prc = plan_search(h, q_dev, ldq_in, b, top_k, nprobe, st, s, true, adaptive.on ? &aq : nullptr);
+  const int32_t prc = plan_search(h, q_dev, ldq_in, b, top_k, nprobe, st, s, true, adaptive.on ? &aq : nullptr, want_pre);
   W->no_ahead = false;
   if (prc) return prc;
   { const int ev = scan_events_ref().load(); W->ev_on = ev == 1 || ev == 2; }  // (the plan set it for an unfiltered call)
   W->tot_valid = true;
+  if (s.kp_slots) {
+    {
+      std::lock_guard<std::mutex> lk(h->flt_mu);
+      if (!h->fp_total.p) {
+        if (int32_t rc = h->fp_total.reserve((kFpStats + 1) * sizeof(unsigned long long))) return rc;
+        VERS_HIP_TRY(hipMemset(h->fp_total.p, 0, (kFpStats + 1) * sizeof(unsigned long long)));
+      }
+    }
+    unsigned long long* const fp_total = h->fp_total.as<unsigned long long>();
+    const uint64_t n_pairs = (uint64_t)b * s.P;
+    if (int32_t rc = launch_filter_pre_begin(s.pj_list, h->slot_len.as<uint32_t>(), n_pairs, s.seg_rows, s.pj_nq, fp_total, st)) return rc;
+    FilterPreParams fp;
+    fp.ld = h->ld; fp.kp = s.kp; fp.rows_h = h->rows_bf.as<uint16_t>(); fp.xnorm = h->xnorm.as<float>(); fp.tile_mask = masks.one.tile_mask;
+    fp.bounds32 = reinterpret_cast<uint32_t*>(W->partials.as<uint64_t>() + W->ivf_bounds_off);  // 0xFF-filled with the slots
+    fp.qflags = s.qflags; fp.wave_slots = masks.one.wave_slots;
+    if (int32_t rc = fresh_quad_counter(st, &fp.next_quad)) return rc;
+    const uint32_t blocks = filter_prescan_grid(h->n_cu, h->ld, (uint32_t)s.items_bound, (uint32_t)(filter_wave_slots(h) / kWavesPerBlock));
+    if (int32_t rc = s.QG == 8 ? launch_filter_prescan(h->metric, make_ivf_src<8>(h, s, 0u), fp, blocks, st)
+                               : launch_filter_prescan(h->metric, make_ivf_src<16>(h, s, 0u), fp, blocks, st))
+      return rc;
+    RescoreArgs a;
+    a.partials = W->partials.as<uint64_t>(); a.P = s.P; a.S_max = s.S_max; a.kp = s.kp; a.top_k = top_k; a.d_pad = h->ld;
+    a.pj_list = s.pj_list; a.pj_pref = s.pj_pref; a.pj_nq = s.pj_nq; a.list_off = h->slot_off.as<uint32_t>(); a.row_ids = h->row_ids.as<uint32_t>();
+    a.rows = h->rows.as<float>(); a.rows_rm = h->rows_rm.as<float>(); a.ld = h->ld; a.qp = s.qp; a.ldq = h->ldq; a.xmax2_bits = h->pre_misc.as<uint32_t>();
+    a.qflags = s.qflags; a.metric = h->metric; a.force_fail = s.pre_mode == 2; a.shadow = 1;  // (hi + lo query blocks into one accumulator: the audited model)
+    a.debug = 0; a.fail_list = s.fail_list; a.stats = reinterpret_cast<uint32_t*>(fp_total + kFpStats);
+    a.status = W->st_word(); a.out_ids = out_ids; a.out_dist = out_dist; a.out_count = out_count; a.out_keys = nullptr;
+    const int stage_rows = rescore_lds_bytes(h->ld, true, kRescoreWaves) <= 144u * 1024u ? 1 : 0;
+    const size_t rs_lds = rescore_lds_bytes(h->ld, stage_rows != 0, kRescoreWaves);
+    if (int32_t rc = scan_prepare_launch(ivf_rescore_kernel<kRescoreWaves>, rs_lds)) return rc;
+    hipLaunchKernelGGL(ivf_rescore_kernel<kRescoreWaves>, dim3(b), dim3(kWave * kRescoreWaves), rs_lds, st, a, stage_rows);
+    VERS_HIP_TRY(hipGetLastError());
+    FilterFbParams fb;
+    fb.rows = a.rows; fb.ld = h->ld; fb.ldq = h->ldq; fb.qp = s.qp; fb.pj_list = s.pj_list; fb.pj_pref = s.pj_pref; fb.list_off = a.list_off;
+    fb.list_len = h->slot_len.as<uint32_t>(); fb.row_ids = a.row_ids; fb.P = s.P; fb.top_k = top_k; fb.b = b; fb.tile_mask = fp.tile_mask;
+    fb.fail_list = s.fail_list; fb.status = W->st_word(); fb.out_ids = out_ids; fb.out_dist = out_dist; fb.out_count = out_count; fb.total = fp_total;
+    if (int32_t rc = launch_filter_fallback(h->metric, fb, std::min<uint32_t>(b, (uint32_t)h->n_cu * 2u), st)) return rc;
+    return filter_end(h, st);
+  }
   if (int32_t rc = run_chain_passes(h, s, b, top_k, out_ids, out_dist, out_count, out_keys, /*unfiltered=*/false, st, [&](const uint64_t* lower) -> int32_t {
         return with_qg<1, 8, 16>(s.QG, [&](auto qg) -> int32_t {
           return launch_ivf_scan(h, make_ivf_src<decltype(qg)::value>(h, s, 0u), (uint32_t)s.items_bound, st, lower, masks.choice());
@@ -2127,6 +2175,18 @@ int32_t vers_ivf_filter_stats(vers_ivf_t* h, uint64_t* out4, uint64_t* out4_tota
     if (out4) out4[i] = last[i];
     if (out4_total) out4_total[i] = tot[i];
   }
+  return VERS_OK;
+}
+
+int32_t vers_ivf_filter_prescan_stats(vers_ivf_t* h, uint64_t* out2) {
+  if (!h || !out2) return fail(VERS_ERR_INVALID, "null handle or out2");
+  DeviceGuard g(h->device);
+  unsigned long long tot[kFpStats] = {};
+  {
+    std::lock_guard<std::mutex> lk(h->flt_mu);
+    if (h->fp_total.p) VERS_HIP_TRY(hipMemcpy(tot, h->fp_total.p, sizeof(tot), hipMemcpyDeviceToHost));
+  }
+  for (int i = 0; i < kFpStats; ++i) out2[i] = tot[i];
   return VERS_OK;
 }
 

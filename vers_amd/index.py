@@ -522,6 +522,13 @@ class IVFFlatIndex:
         keys = ("tiles_planned", "tiles_loaded", "items_skipped", "rows_allowed")
         return dict(last=dict(zip(keys, (int(v) for v in last))), total=dict(zip(keys, (int(v) for v in tot))))
 
+    def filter_prescan_stats(self):
+        """vers_ivf_filter_prescan_stats: over the handle's life, the filtered top-k calls served by the matrix-core scan of the allowed rows
+        (option "filter_prescan") and the queries their exact finish sent to the filtered fallback."""
+        out = (C.c_uint64 * 2)()
+        check(lib().vers_ivf_filter_prescan_stats(self._h, out))
+        return dict(zip(("calls", "fallback_queries"), (int(v) for v in out)))
+
     # -- range search (extension; the reference has search_approximate only) ---------------------------
     def range_stats(self):
         """vers_ivf_range_stats: the probed range search's matrix-core pre-filter (option "range_prescan") over the handle's life -- calls
