@@ -275,15 +275,19 @@ def test_items_of_more_than_64_tiles():
         Q = queries(ix, 0xF181, 9)
         first = np.concatenate([l[:4096:7] for l in lists])    # live tiles in the first window only
         second = np.concatenate([l[4096:] for l in lists])     # ... in the second only
-        case = Case(ix, Q, [first, second], n, n)
+        partial = [l for l in lists if len(l) % 64]            # (12000 is no multiple of 64: not both lists end on a tile boundary)
+        assert partial
+        one_late = partial[0][-1:]                             # a single row, in the last (partial) tile of its list
+                                                               # (ix.ids[c] is in storage order: its last entry is the list's last row)
+        case = Case(ix, Q, [first, second, one_late], n, n)
         capi.set_option("seg_rows", 8192)
-        for fo in (np.arange(9) % 2, np.zeros(9, int), np.ones(9, int)):
+        for fo in (np.arange(9) % 2, np.zeros(9, int), np.ones(9, int), np.full(9, 2)):
             for nprobe in (1, 2):
                 check(case, fo, 10, nprobe)
             check(case, fo, 100, 2)
             check(case, fo, 10, L2, probed=False)
             check(case, fo, 100, L2, probed=False)
-        for f in (0, 1):
+        for f in (0, 1, 2):
             check(case, [f], 10, 2, qs=[0])
             check(case, [f], 10, L2, probed=False, qs=[0])
     finally:

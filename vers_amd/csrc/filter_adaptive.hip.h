@@ -1,7 +1,7 @@
 // filter_adaptive.hip.h -- adaptive depth for the probed filtered top-k search: every query of a batch probes lists until min_allowed rows its
 // bitmap allows are in reach, between nprobe_min and nprobe_max lists.
 //
-// Semantics: none of its own.  Row q of an adaptive call is, bit for bit, row q of the filtered search (filter.hip.h; filter_multi.hip.h with a
+// Semantics: none of its own.  Row q of an adaptive call is, bit for bit, row q of the filtered search (filter.hip.h, also with a
 // bitmap per query) made with nprobe = P_q, the depth adaptive_depth.hpp defines.  P_q depends on the query's list ranking and on the number of
 // allowed rows per list only, and the device has both before the scan starts: the mask pass has seen every storage row, the ranked keys are
 // in W->probe.  Two kernels between the mask pass and the plan's group step, and a twin of plan_queries_kernel:

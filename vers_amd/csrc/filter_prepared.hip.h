@@ -1,4 +1,4 @@
-// filter_prepared.hip.h -- prepared filters: the masks of filter.hip.h / filter_multi.hip.h and the counts of filter_adaptive.hip.h kept in an
+// filter_prepared.hip.h -- prepared filters: the masks of filter.hip.h (both layouts) and the counts of filter_adaptive.hip.h kept in an
 // object across calls (vers_ivf_filter_prepare), and the kernel that brings them up to date after an add that wrote its rows into list slack.
 //
 // A full build runs the existing mask and count kernels into the object's arrays.  What is new here is the TAIL REFRESH: after in-place
@@ -12,7 +12,7 @@
 // The two forms of a one-bitmap object agree bit for bit, and an object of several bitmaps holds the per-query form only: one allowed_len
 // and one total serve both.
 #pragma once
-#include "filter_multi.hip.h"
+#include "filter.hip.h"
 #include "filter_prepared.hpp"
 
 namespace vers {

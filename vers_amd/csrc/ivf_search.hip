@@ -21,10 +21,8 @@
 #include "range_prescan.hip.h"
 #include "filter_prescan.hip.h"
 #include "filter.hip.h"
-#include "filter_multi.hip.h"
 #include "filter_adaptive.hip.h"
 #include "filter_range.hip.h"
-#include "filter_range_multi.hip.h"
 #include "filter_prepared.hip.h"
 
 namespace vers {
@@ -201,19 +199,29 @@ namespace ivf {
 
 static size_t filter_wave_slots(const vers_ivf* h) { return (size_t)h->n_cu * 3 * kWavesPerBlock; }  // (filter_scan_kernel: at most 3 blocks per CU)
 
-// The filtered kernel a pass launches: none, the per-call mask's (filter.hip.h, filter_range.hip.h) or the per-query sets' (filter_multi.hip.h,
-// filter_range_multi.hip.h).  A call's FilterMasks (below) hands it out once filter_begin has filled them; the top-k drivers and the range source
-// pass it down, and nothing else about a pass differs between the two.
+// The filtered kernel a pass launches: none, the per-call mask's or the per-query sets' (filter_walk.hip.h: MaskPerCall, MaskPerQuery).  A
+// call's FilterMasks (below) hands it out once filter_begin has filled them; the top-k drivers and the range source pass it down, and
+// nothing else about a pass differs between the two.
 struct FilterChoice {
   const FilterParams* one = nullptr;
   const FilterMultiParams* multi = nullptr;
   explicit operator bool() const { return one != nullptr || multi != nullptr; }
 };
+// f(tag of the mask policy, its parameters) for the masks of a filtered pass: the caller names its kernel template once (with_metric,
+// scan_launch.hip.h).  The policies are device-side state: the host passes their type only.
+template <class Mask>
+struct MaskTag {
+  using type = Mask;
+};
+template <class F>
+static int32_t with_mask(const FilterChoice& c, F&& f) {
+  return c.multi ? f(MaskTag<MaskPerQuery>{}, *c.multi) : f(MaskTag<MaskPerCall>{}, *c.one);
+}
 
 // One pass of the ordered-chain list scan over the planned items, timed through the scan-timing ring.  Without a filter, option "scan_debug"
 // decides: bit 3 switches the pruning bounds off (A/B runs), bit 4 stamps phases, bit 5 switches the hand-out counter off.  flt: the filtered
 // kernel (filter.hip.h), which knows no diagnosis switches -- bounds and counter always on for QG != 1 -- and launches no more waves than it
-// has counter slots (filter_begin).  The per-query kernel (filter_multi.hip.h) is launched the same way.
+// has counter slots (filter_begin).
 template <int QG>
 int32_t launch_ivf_scan(vers_ivf* h, const IvfSrc<QG>& src, uint32_t items_bound, hipStream_t st, const uint64_t* lower, FilterChoice flt = {}) {
   ScanParams p = ivf_scan_params(h, src.k_keep, lower);
@@ -231,8 +239,10 @@ int32_t launch_ivf_scan(vers_ivf* h, const IvfSrc<QG>& src, uint32_t items_bound
   const uint32_t blocks = scan_grid(h->n_cu, QG, h->ld, items_bound, flt ? (uint32_t)(filter_wave_slots(h) / kWavesPerBlock) : 0xFFFFFFFFu);
   return with_metric(h->metric, [&](auto m) -> int32_t {
     constexpr int M = decltype(m)::value;
-    if (flt.multi) return launch_scan_timed(filter_multi_scan_kernel<QG, M, IvfSrc<QG>>, blocks, kWavesPerBlock, lds, st, src, p, *flt.multi);
-    if (flt.one) return launch_scan_timed(filter_scan_kernel<QG, M, IvfSrc<QG>>, blocks, kWavesPerBlock, lds, st, src, p, *flt.one);
+    if (flt)
+      return with_mask(flt, [&](auto mask, const auto& f) -> int32_t {
+        return launch_scan_timed(filter_scan_kernel<QG, M, IvfSrc<QG>, typename decltype(mask)::type>, blocks, kWavesPerBlock, lds, st, src, p, f);
+      });
     return launch_scan_timed(scan_kernel<QG, M, IvfSrc<QG>>, blocks, kWavesPerBlock, lds, st, src, p);
   });
 }
@@ -731,8 +741,8 @@ static int32_t prepared_sync(vers_ivf* h, vers_filter* o, int want, bool search,
 }
 
 // The filter of a call, on the device -- what every filtered *_dev_locked function takes: n_filters bitmaps `stride_words` apart, one n_bits for
-// all.  filter_of == NULL: ONE bitmap for the batch and the per-call kernels (filter.hip.h, filter_range.hip.h); else the batch's filter_of and
-// the per-query kernels (filter_multi.hip.h, filter_range_multi.hip.h).  prep: a prepared call -- the object the bitmaps above are; its masks
+// all.  filter_of == NULL: ONE bitmap for the batch and the per-call masks (filter_walk.hip.h: MaskPerCall); else the batch's filter_of and
+// the per-query masks (MaskPerQuery).  prep: a prepared call -- the object the bitmaps above are; its masks
 // serve the call and no mask kernel runs.
 struct FilterArg {
   const uint64_t* filters; uint64_t stride_words; uint32_t n_filters; uint64_t n_bits; const uint32_t* filter_of;
@@ -893,9 +903,9 @@ int32_t launch_filter_seg_scan(vers_ivf* h, const SegSrc<QG, true>& src, uint32_
   const ScanParams p = ivf_scan_params(h, src.k, lower);
   const uint32_t blocks = scan_grid(h->n_cu, QG, h->ld, n_items, (uint32_t)(filter_wave_slots(h) / kWavesPerBlock));
   return with_metric(metric, [&](auto m) -> int32_t {
-    if (f.multi)
-      return launch_scan_timed(filter_multi_scan_kernel<QG, decltype(m)::value, SegSrc<QG, true>>, blocks, kWavesPerBlock, scan_lds_bytes(QG, h->ld), st, src, p, *f.multi);
-    return launch_scan_timed(filter_scan_kernel<QG, decltype(m)::value, SegSrc<QG, true>>, blocks, kWavesPerBlock, scan_lds_bytes(QG, h->ld), st, src, p, *f.one);
+    return with_mask(f, [&](auto mask, const auto& fp) -> int32_t {
+      return launch_scan_timed(filter_scan_kernel<QG, decltype(m)::value, SegSrc<QG, true>, typename decltype(mask)::type>, blocks, kWavesPerBlock, scan_lds_bytes(QG, h->ld), st, src, p, fp);
+    });
   });
 }
 
@@ -1436,15 +1446,16 @@ int32_t range_dev_locked(vers_ivf* h, const char* who, bool probed, const float*
 }
 static const char* range_name(bool probed) { return probed ? "vers_ivf_range_search" : "vers_ivf_range_search_exhaustive"; }
 
-// ---- filtered range search (filter_range.hip.h, filter_range_multi.hip.h): the range protocol over the allowed rows ---------------------------
+// ---- filtered range search (filter_range.hip.h): the range protocol over the allowed rows ---------------------------
 // one pass of the filtered range walk, with the kernel of the call's masks; not timed by the scan-timing ring (no range pass is), and no more
 // waves than counter slots (filter_begin)
 template <int QG, bool FILL, class Src>
 static int32_t launch_filter_range_pass(vers_ivf* h, int metric, const Src& src, uint32_t items, const RangeParams& p, FilterChoice f, hipStream_t st) {
   const uint32_t blocks = scan_grid(h->n_cu, QG, h->ld, items, (uint32_t)(filter_wave_slots(h) / kWavesPerBlock));
   return with_metric(metric, [&](auto m) -> int32_t {
-    if (f.multi) return launch_scan(filter_range_multi_scan_kernel<QG, decltype(m)::value, FILL, Src>, blocks, kWavesPerBlock, scan_lds_bytes(QG, h->ld), st, src, p, *f.multi);
-    return launch_scan(filter_range_scan_kernel<QG, decltype(m)::value, FILL, Src>, blocks, kWavesPerBlock, scan_lds_bytes(QG, h->ld), st, src, p, *f.one);
+    return with_mask(f, [&](auto mask, const auto& fp) -> int32_t {
+      return launch_scan(filter_range_scan_kernel<QG, decltype(m)::value, FILL, Src, typename decltype(mask)::type>, blocks, kWavesPerBlock, scan_lds_bytes(QG, h->ld), st, src, p, fp);
+    });
   });
 }
 
@@ -2020,7 +2031,7 @@ int32_t vers_ivf_search_exhaustive(vers_ivf_t* h, const float* queries, uint64_t
   return rc == kRetrySpill ? VERS_ERR_INVALID : rc;
 }
 
-// ---- filtered top-k search (filter.hip.h, filter_multi.hip.h, filter_adaptive.hip.h) ----
+// ---- filtered top-k search (filter.hip.h, filter_adaptive.hip.h) ----
 // The device-pointer calls: the probed lists or (probed = false) every stored row under the metric given in place of nprobe; one bitmap or the
 // _multi form (form); ad: the adaptive call's arguments, nprobe then being nprobe_max.
 static int32_t filtered_dev_common(vers_ivf_t* h, const char* who, bool probed, FilterForm form, const float* queries_dev, uint64_t ldq_floats, uint32_t b, uint32_t top_k,
@@ -2290,7 +2301,7 @@ int32_t vers_ivf_range_search_exhaustive(vers_ivf_t* h, const float* queries, ui
   return range_host_common(h, "vers_ivf_range_search_exhaustive", false, queries, q_stride_bytes, b, radius, metric, flags, out_lims, out_ids, out_dist, cap, out_total);
 }
 
-// ---- filtered range search (filter_range.hip.h, filter_range_multi.hip.h): the probed lists or (probed = false) every stored row under the metric
+// ---- filtered range search (filter_range.hip.h): the probed lists or (probed = false) every stored row under the metric
 // given in place of nprobe; one bitmap, the _multi form, or (a rank's partial: out_keys_dev in place of out_dist_dev) either ----
 // The device-pointer calls.  who: the entry point; src_who: the name its range source reports under (the host-pointer call's for the whole calls).
 static int32_t range_filtered_dev_common(vers_ivf_t* h, const char* who, const char* src_who, bool probed, FilterForm form, const float* queries_dev, uint64_t ldq_floats,

@@ -32,7 +32,7 @@
 // On a handle sharded by cluster the same passes run over the lists (rows) the rank stores and end in (key, id) pairs; the cross-rank merge
 // is range_merge.hip.h.
 #pragma once
-#include "scan.hip.h"
+#include "item_loop.hip.h"
 
 #pragma clang fp contract(off)
 
@@ -186,57 +186,14 @@ __device__ __forceinline__ void range_item(const Src& src, const RangeParams& p,
 // FILL = false: the count pass; FILL = true: the fill pass.  Same grid, same items (scan_kernel's contract for Src).
 template <int QG, int METRIC, bool FILL, class Src>
 __global__ __launch_bounds__(kWave * kWavesPerBlock) void range_scan_kernel(Src src, RangeParams p) {
+  static_assert(QG == 1 || QG == 8 || Src::kRangeRows == kRangeRowsListed, "segment sources group 8 queries");
   const int lane = threadIdx.x & 63;
   const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const uint32_t n_items = src.n_items();
   bool nan_seen = false;
-  if constexpr (QG == 1) {
-    const uint32_t n_waves = gridDim.x * kWavesPerBlock;
-    for (uint32_t it = blockIdx.x * kWavesPerBlock + wid; it < n_items; it += n_waves) {
-      ItemView<QG> v;
-      src.get(it, v);
-      if (v.nrows == 0) continue;
-      range_item<1, 1, METRIC, FILL>(src, p, it, v, lane, nan_seen);
-    }
-  } else {
-    static_assert(QG == 8 || QG == 16, "query groups are 1, 8 or 16 wide");
-    static_assert(QG == 8 || Src::kRangeRows == kRangeRowsListed, "segment sources group 8 queries");
-    static_assert(kWavesPerBlock == 4, "items are padded to quads");
-    extern __shared__ __attribute__((aligned(16))) float qlds[];
-    const uint32_t n_quads = n_items / 4;
-    const uint32_t n4 = p.ld * (QG / 4);  // float4s of one query block
-    uint32_t* nq_lds = reinterpret_cast<uint32_t*>(qlds + (size_t)p.ld * QG);  // one word behind the query block
-    for (uint32_t b0 = blockIdx.x;; b0 += gridDim.x) {
-      uint32_t bi = b0;
-      if (p.next_quad != nullptr) {
-        if (threadIdx.x == 0) *nq_lds = atomicAdd(p.next_quad, 1u);
-        __syncthreads();
-        bi = *nq_lds;  // every wave reads it before the next write: two barriers follow below
-      }
-      if (bi >= n_quads) break;  // block-uniform
-      const uint32_t it = bi * 4 + wid;
-      ItemView<QG> v;
-      src.get(it, v);  // v.qb / v.nq are the same for the four items of the quad
-      __syncthreads();  // the previous quad's readers are done with the LDS block
-      const f32x4* g = reinterpret_cast<const f32x4*>(v.qb);
-      for (uint32_t i = threadIdx.x; i < n4; i += kWave * kWavesPerBlock) reinterpret_cast<f32x4*>(qlds)[i] = g[i];
-      __syncthreads();
-      v.qb = qlds;
-      if (v.nrows == 0) continue;  // padding item (wave-uniform; barriers are outside)
-      const uint32_t np = ((v.nq + 3) >> 2) << 1;  // live query pairs, in steps of two
-      if constexpr (QG == 8) {
-        if (np <= 2) range_item<8, 2, METRIC, FILL>(src, p, it, v, lane, nan_seen);
-        else range_item<8, 4, METRIC, FILL>(src, p, it, v, lane, nan_seen);
-      } else {
-        switch (np) {
-          case 2: range_item<16, 2, METRIC, FILL>(src, p, it, v, lane, nan_seen); break;
-          case 4: range_item<16, 4, METRIC, FILL>(src, p, it, v, lane, nan_seen); break;
-          case 6: range_item<16, 6, METRIC, FILL>(src, p, it, v, lane, nan_seen); break;
-          default: range_item<16, 8, METRIC, FILL>(src, p, it, v, lane, nan_seen); break;
-        }
-      }
-    }
-  }
+  for_each_item<QG>(src, p.ld, p.next_quad, wid, [&](uint32_t it, const ItemView<QG>& v) __attribute__((always_inline)) {
+    if constexpr (QG == 1) range_item<1, 1, METRIC, FILL>(src, p, it, v, lane, nan_seen);
+    else with_pairs_by_two<QG>(v.nq, [&](auto np) __attribute__((always_inline)) { range_item<QG, decltype(np)::value, METRIC, FILL>(src, p, it, v, lane, nan_seen); });
+  });
   if constexpr (!FILL) {
     if (__ballot(nan_seen) != 0 && lane == 0) atomicOr(p.status, 1u);
   }
