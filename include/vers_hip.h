@@ -86,6 +86,13 @@ int32_t vers_flat_poll(vers_flat_t* h, void* stream);
 /* Duration in ms of the most recent scan-kernel launch of this handle
  * (HIP events on the launch stream; synchronises on those events). */
 int32_t vers_flat_last_scan_ms(vers_flat_t* h, float* out_ms);
+/* Option "flat_prescan" = 1 (default 0): a BATCH (b >= 2, top_k <= 48) on a handle that keeps its fp16 shadow (see vers_flat_upload)
+ * contracts blocks of up to 64 queries against the shadow's row tiles on the matrix cores, keeps top_k + 16 candidates per query and
+ * is finished exactly -- certificate, ordered-chain re-score on the f32 rows, exact re-scan of the queries whose certificate fails.
+ * Ids, order, counts, distance bits and the latched NaN status are the ordered chains'.  Every other call takes the ordered chains as
+ * before; 2 = every certificate fails (tests the re-scan).  Over the handle's life (synchronises the device): out4[0] batched calls
+ * served by that path, out4[1] queries it served, out4[2] queries sent to the exact re-scan, out4[3] candidates re-scored. */
+int32_t vers_flat_prescan_stats(vers_flat_t* h, uint64_t* out4);
 
 /* ------------------------------------------------------------------------ *
  * k-means primitives on host arrays (unit-test / integration surface; the   *
@@ -937,7 +944,9 @@ int32_t vers_ivf_range_search_exhaustive_sharded_dev(vers_ivf_t* h, const vers_c
  *  Serving:
  *   "single_shadow" (1) a single query (b == 1, nprobe >= 1) streams the fp16 shadow and is finished exactly like a batch;
  *                       0 = the ordered-chain scan of the f32 rows.
- *   "host_spin" (1)     a host-pointer single-query call waits by spinning on the pinned status word (<= 2 ms); 0 = hipStreamSynchronize.
+ *   "flat_prescan" (0)  1 = vers_flat_search[_dev] batches (b >= 2, top_k <= 48) scan the flat handle's fp16 shadow on the matrix cores
+ *                       with the exact finish (vers_flat_prescan_stats); 2 = the same with every certificate failing.  Same results.
+ *   "host_spin" (1)    a host-pointer single-query call waits by spinning on the pinned status word (<= 2 ms); 0 = hipStreamSynchronize.
  *   "pre_min_batch" (4) the smallest batch whose list scan runs on the matrix cores when its lists are shared by fewer than two
  *                       queries on average; smaller batches run as consecutive single queries.
  *   "scan_reserve_cus" (-1 = auto: 64 while another batch of the handle is in flight on another stream, else 0) compute units the

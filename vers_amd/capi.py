@@ -45,6 +45,7 @@ SIGNATURES = {
     "vers_flat_search_dev": (C.c_int32, [_vp, _vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, _vp, _vp, _vp, _vp]),
     "vers_flat_poll": (C.c_int32, [_vp, _vp]),
     "vers_flat_last_scan_ms": (C.c_int32, [_vp, C.POINTER(C.c_float)]),
+    "vers_flat_prescan_stats": (C.c_int32, [_vp, C.POINTER(C.c_uint64)]),
     "vers_ivf_create": (C.c_int32, [C.c_int32, C.c_uint32, C.POINTER(_vp)]),
     "vers_ivf_destroy": (C.c_int32, [_vp]),
     "vers_ivf_set_metric": (C.c_int32, [_vp, C.c_uint32]),
@@ -414,6 +415,13 @@ class FlatCorpus:
         ms = C.c_float(0)
         check(lib().vers_flat_last_scan_ms(self._h, C.byref(ms)))
         return ms.value
+
+    def prescan_stats(self):
+        """vers_flat_prescan_stats, over the handle's life: (batched calls served by the matrix-core scan, queries it served, queries sent
+        to the exact re-scan, candidates re-scored)."""
+        out = (C.c_uint64 * 4)()
+        check(lib().vers_flat_prescan_stats(self._h, out))
+        return tuple(int(v) for v in out)
 
 
 # ---- k-means primitives (ivfflat.rs:29-71,138-149) -----------------------------------------

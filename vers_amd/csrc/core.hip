@@ -32,6 +32,7 @@ OptEntry g_opts[] = {
     {"add_batch_rows"}, {"remove_batch_ids"}, {"compact_fused"}, {"pre_prune"}, {"pre_prune_first"}, {"pre_hot_single"},
     {"pre_head"}, {"pre_head_cols"}, {"pre_head_backoff"}, {"fetch_lds_min"}, {"fetch_map"},
     {"pre_ball"}, {"pre_ball_cut"}, {"pre_ball_min_quads"}, {"pre_live_list"}, {"range_prescan"}, {"filter_prescan"},
+    {"flat_prescan"},
 };
 OptEntry* opt_find(const char* name) {
   for (OptEntry& e : g_opts)

@@ -42,6 +42,7 @@ struct RescoreArgs {
   // read once it is done with it, the fallback launch the count of queued queries it served (both nullable)
   uint32_t* reset_flag = nullptr;
   uint32_t* reset_count = nullptr;
+  uint32_t* surv_count = nullptr;  // nullable: += the survivors this launch re-scores (the flat batch's statistics)
   // host-pointer single-query call (vers_ivf_search, b == 1, on the shadow): the finish itself stores the stream's status word into the pinned
   // result block behind its results when the certificate held -- the host, spinning on that word, does not wait for the fallback launch that
   // follows and finds nothing to do (3.5-4 us); when the certificate failed the fallback launch publishes, after its re-scan
@@ -390,6 +391,7 @@ __global__ __launch_bounds__(kWave * NW) __attribute__((amdgpu_waves_per_eu(NW =
       s_failed = certified ? 0u : 1u;
       s_nsurv = n_surv;
       if (!certified) { a.fail_list[atomicAdd(a.fail_list + gridDim.x, 1u)] = q; atomicAdd(a.stats, 1u); }  // the fallback kernels redo it
+      else if (a.surv_count != nullptr) atomicAdd(a.surv_count, n_surv);
     }
   }
   __syncthreads();

@@ -114,6 +114,17 @@ int32_t flat_search_dev_locked(vers_flat* h, const float* q_dev, uint64_t ldq, u
     return VERS_OK;
   }
   const uint32_t ldq_pad = h->ld;
+  // A batch contracts blocks of up to 64 queries against the fp16 shadow on the matrix cores when option "flat_prescan" says so (default
+  // 0: DESIGN.md section 6): pre-selection, certificate, exact re-score and -- where the certificate fails; with 2: everywhere -- the
+  // exact re-scan; same results (flat_prescan.hip.h)
+  if (const int64_t fpm = opt_get("flat_prescan", 0); fpm != 0 && b >= 2 && flat_shadow_batch_usable(h->shadow, h->n, h->ld, b, top_k)) {
+    if (int32_t rc = grow(h->q_stage, h->q_stage_cap, (size_t)b * ldq_pad)) return rc;
+    if (int32_t rc = launch_stage_queries(q_dev, ldq, h->d, h->q_stage, ldq_pad, b, 1, st)) return rc;
+    if (int32_t rc = flat_shadow_search_batch(h->shadow, h->batch, h->rows, h->n, h->ld, h->n_cu, h->q_stage, b, top_k, metric, fpm == 2, h->status_dev,
+                                              out_ids, out_dist, out_count, st, h->ev0, h->ev1)) return rc;
+    h->ev_valid = true;
+    return VERS_OK;
+  }
   // one item per resident wave when possible (static balance), at least one 64-row tile each; option "seg_rows" is not honoured here
   const SegPlan sp = seg_plan(h->n, b, h->ld, h->n_cu, 0);
   const int QG = sp.QG;
@@ -272,6 +283,7 @@ int32_t vers_flat_destroy(vers_flat_t* h) {
   (void)hipDeviceSynchronize();
   if (h->rows) (void)hipFree(h->rows);
   h->shadow.release();
+  h->batch.release();
   for (void* p : {(void*)h->q_stage, (void*)h->q_up, (void*)h->zero_q, (void*)h->partials, (void*)h->lower, (void*)h->status_dev, (void*)h->o_ids,
                   (void*)h->o_dist, (void*)h->o_cnt})
     if (p) (void)hipFree(p);
@@ -426,6 +438,13 @@ int32_t vers_flat_range_search(vers_flat_t* h, const float* queries, uint64_t q_
   VERS_HIP_TRY(hipMemcpy(out_ids, h->o_ids, (size_t)total * sizeof(uint64_t), hipMemcpyDeviceToHost));
   VERS_HIP_TRY(hipMemcpy(out_dist, h->o_dist, (size_t)total * sizeof(float), hipMemcpyDeviceToHost));
   return VERS_OK;
+}
+
+int32_t vers_flat_prescan_stats(vers_flat_t* h, uint64_t* out4) {
+  if (!h || !out4) return fail(VERS_ERR_INVALID, "vers_flat_prescan_stats: bad arguments");
+  std::lock_guard<std::mutex> lk(h->mu);
+  DeviceGuard g(h->device);
+  return flat_shadow_batch_stats(h->batch, out4);
 }
 
 int32_t vers_flat_last_scan_ms(vers_flat_t* h, float* out_ms) {

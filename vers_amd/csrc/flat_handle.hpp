@@ -37,5 +37,6 @@ struct vers_flat {
   vers::RangeScratch rg;
   vers::DevBuf rg_q, rg_rad, rg_lims;
   vers::FlatShadow shadow;  // fp16 shadow of the rows + what a single query's exact finish needs (flat_shadow.hpp); empty when it did not fit
+  vers::FlatBatchWs batch;  // a batch on the shadow (option "flat_prescan"): tables, slots, vers_flat_prescan_stats' counters; survives uploads
   std::mutex mu;
 };

@@ -12,6 +12,7 @@
 #include "finish.hip.h"
 #include "ball_filter.hip.h"
 #include "head_filter.hip.h"
+#include "flat_prescan.hip.h"
 #include "flat_shadow.hpp"
 #include "ivf_src.hip.h"
 #include "single.hip.h"
@@ -1682,6 +1683,32 @@ bool flat_shadow_usable(const FlatShadow& s, uint64_t n, uint32_t ld, uint32_t t
          knobs().pre_mode != 0 && top_k >= 1 && top_k + kPreMinSlack <= kPreMaxKp && scan1h_lds_bytes(ld) <= 64u * 1024u;
 }
 
+// the exact finish of a scan of the shadow, one query or a batch: what the caller's scan left in a.partials -- [b][S_max][kp], the corpus being ONE
+// list (P = 1) -- is merged, certified and re-scored by ivf_rescore_kernel (a block of sixteen waves that reads a query's slots as one flat
+// array where there are many, of four where there are few), and what does not certify is re-scanned by fallback_kernel.  The caller fills
+// the slots, the tables, the policy (kp, top_k, metric, shadow, force_fail, counters, resets) and the outputs.
+static int32_t flat_shadow_finish(FlatShadow& s, RescoreArgs& a, const float* rows_blocked, uint32_t ld, const float* q_padded, uint32_t b,
+                                  const uint32_t* list_len, hipStream_t st) {
+  a.P = 1; a.d_pad = ld; a.row_ids = s.row_ids; a.rows = rows_blocked; a.rows_rm = nullptr; a.ld = ld; a.qp = q_padded; a.ldq = ld;
+  a.xmax2_bits = s.misc; a.debug = 0; a.out_keys = nullptr; a.stamps = nullptr;
+  if (b == 1 || a.S_max > 64u) {
+    const int stage_rows = rescore_lds_bytes(ld, true, kRescoreWaves1) <= 144u * 1024u ? 1 : 0;
+    const size_t rs_lds = rescore_lds_bytes(ld, stage_rows != 0, kRescoreWaves1);
+    if (int32_t rc = scan_prepare_launch(ivf_rescore_kernel<kRescoreWaves1>, rs_lds)) return rc;
+    hipLaunchKernelGGL(ivf_rescore_kernel<kRescoreWaves1>, dim3(b), dim3(kWave * kRescoreWaves1), rs_lds, st, a, stage_rows);
+  } else {
+    const int stage_rows = rescore_lds_bytes(ld, true, kRescoreWaves) <= 144u * 1024u ? 1 : 0;
+    const size_t rs_lds = rescore_lds_bytes(ld, stage_rows != 0, kRescoreWaves);
+    if (int32_t rc = scan_prepare_launch(ivf_rescore_kernel<kRescoreWaves>, rs_lds)) return rc;
+    hipLaunchKernelGGL(ivf_rescore_kernel<kRescoreWaves>, dim3(b), dim3(kWave * kRescoreWaves), rs_lds, st, a, stage_rows);
+  }
+  VERS_HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(fallback_kernel, dim3(kFallbackBlocks), dim3(kWave * kFbWaves), 0, st, a, list_len, (const uint32_t*)a.fail_list,
+                     (const uint32_t*)(a.fail_list + b), s.fb_part, s.fb_ctr, (uint32_t*)nullptr, (const uint32_t*)nullptr, (uint32_t*)nullptr);
+  VERS_HIP_TRY(hipGetLastError());
+  return VERS_OK;
+}
+
 int32_t flat_shadow_search1(FlatShadow& s, const float* rows_blocked, uint64_t n, uint32_t ld, int n_cu, const float* q_padded, uint32_t top_k,
                             uint32_t metric, uint32_t* status, uint64_t* out_ids, float* out_dist, uint32_t* out_count, hipStream_t st,
                             hipEvent_t ev0, hipEvent_t ev1) {
@@ -1700,20 +1727,75 @@ int32_t flat_shadow_search1(FlatShadow& s, const float* rows_blocked, uint64_t n
   VERS_HIP_TRY(hipGetLastError());
   if (ev1) VERS_HIP_TRY(hipEventRecord(ev1, st));
   RescoreArgs a;
-  a.partials = s.slots; a.P = 1; a.S_max = s.n_slots; a.kp = kp; a.top_k = top_k; a.d_pad = ld;
-  a.pj_list = tb + 0; a.pj_pref = tb + 1; a.pj_nq = tb + 2; a.list_off = tb + 3; a.row_ids = s.row_ids;
-  a.rows = rows_blocked; a.rows_rm = nullptr; a.ld = ld; a.qp = q_padded; a.ldq = ld; a.xmax2_bits = s.misc;
-  a.qflags = tb + 5; a.metric = (int)metric; a.force_fail = knobs().pre_mode == 2; a.shadow = 1; a.debug = 0; a.fail_list = tb + 6; a.stats = s.misc + 1;
-  a.status = status; a.out_ids = out_ids; a.out_dist = out_dist; a.out_count = out_count; a.out_keys = nullptr; a.stamps = nullptr;
+  a.partials = s.slots; a.S_max = s.n_slots; a.kp = kp; a.top_k = top_k;
+  a.pj_list = tb + 0; a.pj_pref = tb + 1; a.pj_nq = tb + 2; a.list_off = tb + 3;
+  a.qflags = tb + 5; a.metric = (int)metric; a.force_fail = knobs().pre_mode == 2; a.shadow = 1; a.fail_list = tb + 6; a.stats = s.misc + 1;
+  a.status = status; a.out_ids = out_ids; a.out_dist = out_dist; a.out_count = out_count;
   a.reset_flag = tb + 5; a.reset_count = tb + 7;
-  const int stage_rows = rescore_lds_bytes(ld, true, kRescoreWaves1) <= 144u * 1024u ? 1 : 0;
-  const size_t rs_lds = rescore_lds_bytes(ld, stage_rows != 0, kRescoreWaves1);
-  if (int32_t rc = scan_prepare_launch(ivf_rescore_kernel<kRescoreWaves1>, rs_lds)) return rc;
-  hipLaunchKernelGGL(ivf_rescore_kernel<kRescoreWaves1>, dim3(1), dim3(kWave * kRescoreWaves1), rs_lds, st, a, stage_rows);
-  VERS_HIP_TRY(hipGetLastError());
-  hipLaunchKernelGGL(fallback_kernel, dim3(kFallbackBlocks), dim3(kWave * kFbWaves), 0, st, a, (const uint32_t*)(tb + 4), (const uint32_t*)(tb + 6),
-                     (const uint32_t*)(tb + 7), s.fb_part, s.fb_ctr, (uint32_t*)nullptr, (const uint32_t*)nullptr, (uint32_t*)nullptr);
-  VERS_HIP_TRY(hipGetLastError());
+  return flat_shadow_finish(s, a, rows_blocked, ld, q_padded, 1, tb + 4, st);
+}
+
+// ---- a batch on the shadow: flat_prescan_kernel (flat_prescan.hip), then the same finish ---------------------------------------------
+void FlatBatchWs::release() {
+  for (void* p : {(void*)tab, (void*)fix, (void*)slots})
+    if (p) (void)hipFree(p);
+  *this = FlatBatchWs();
+}
+
+// kp of a batch: top_k + max(kPreMinSlack, top_k), one key per lane at most
+static uint32_t flat_batch_kp(uint32_t top_k) { return std::min<uint32_t>(kPreMaxKp, top_k + std::max<uint32_t>(kPreMinSlack, top_k)); }
+
+bool flat_shadow_batch_usable(const FlatShadow& s, uint64_t n, uint32_t ld, uint32_t b, uint32_t top_k) {
+  return s.rows_built == n && n != 0 && s.rows_h != nullptr && shadow_mode() != 0 && b >= 2 && top_k >= 1 && top_k + kPreMinSlack <= kPreMaxKp &&
+         flat_prescan_plan(n, b, ld, 1, flat_batch_kp(top_k)).ok;
+}
+
+int32_t flat_shadow_search_batch(FlatShadow& s, FlatBatchWs& w, const float* rows_blocked, uint64_t n, uint32_t ld, int n_cu, const float* q_padded,
+                                 uint32_t b, uint32_t top_k, uint32_t metric, bool force_fail, uint32_t* status, uint64_t* out_ids, float* out_dist,
+                                 uint32_t* out_count, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1) {
+  const uint32_t kp = flat_batch_kp(top_k);
+  const FlatPrePlan pl = flat_prescan_plan(n, b, ld, n_cu, kp);
+  if (!pl.ok) return fail(VERS_ERR_INVALID, "flat batch: no query block fits (flat_shadow_batch_usable was not asked)");
+  if (w.fix == nullptr) {
+    VERS_HIP_TRY(hipMalloc((void**)&w.fix, kFlpFixWords * sizeof(uint32_t)));
+    VERS_HIP_TRY(hipMemset(w.fix, 0, kFlpFixWords * sizeof(uint32_t)));
+  }
+  if ((size_t)b > w.tab_cap) {  // (six tables of tab_cap words, the last one a word longer)
+    size_t cap_words = w.tab_cap ? 6 * w.tab_cap + 1 : 0;
+    if (int32_t rc = grow(w.tab, cap_words, 6 * (size_t)b + 1)) { w.tab_cap = 0; return rc; }
+    w.tab_cap = b;
+  }
+  if (int32_t rc = grow(w.slots, w.slots_cap, (size_t)b * pl.n_segs * kp)) return rc;
+  FlatPreTables t;
+  t.pj_list = w.tab; t.pj_pref = w.tab + w.tab_cap; t.pj_nq = w.tab + 2 * w.tab_cap; t.qflags = w.tab + 3 * w.tab_cap;
+  t.bounds32 = w.tab + 4 * w.tab_cap; t.fail_list = w.tab + 5 * w.tab_cap; t.fix = w.fix;
+  if (ev0) VERS_HIP_TRY(hipEventRecord(ev0, st));
+  if (int32_t rc = launch_flat_pre_begin(t, b, pl.n_segs, (uint32_t)n, st)) return rc;
+  FlatPreArgs fa;
+  fa.rows_h = s.rows_h; fa.xnorm = s.xnorm; fa.qp = q_padded; fa.partials = w.slots; fa.bounds32 = t.bounds32; fa.qflags = t.qflags;
+  fa.ld = ld; fa.kp = kp; fa.metric = metric; fa.n_rows = (uint32_t)n; fa.b = b; fa.n_segs = pl.n_segs; fa.seg_tiles = pl.seg_tiles;
+  if (int32_t rc = launch_flat_prescan(fa, pl, st)) return rc;
+  RescoreArgs a;
+  a.partials = w.slots; a.S_max = pl.n_segs; a.kp = kp; a.top_k = top_k;
+  a.pj_list = t.pj_list; a.pj_pref = t.pj_pref; a.pj_nq = t.pj_nq; a.list_off = t.fix + 0;
+  a.qflags = t.qflags; a.metric = (int)metric; a.force_fail = force_fail; a.shadow = pl.lo ? 1 : 2; a.fail_list = t.fail_list; a.stats = t.fix + 2;
+  a.surv_count = t.fix + 3;
+  a.status = status; a.out_ids = out_ids; a.out_dist = out_dist; a.out_count = out_count;
+  if (int32_t rc = flat_shadow_finish(s, a, rows_blocked, ld, q_padded, b, t.fix + 1, st)) return rc;
+  if (ev1) VERS_HIP_TRY(hipEventRecord(ev1, st));
+  w.calls += 1; w.queries += b;
+  return VERS_OK;
+}
+
+int32_t flat_shadow_batch_stats(const FlatBatchWs& w, uint64_t* out4) {
+  out4[0] = w.calls; out4[1] = w.queries; out4[2] = out4[3] = 0;
+  if (w.fix == nullptr) return VERS_OK;
+  uint32_t fix[kFlpFixWords];
+  VERS_HIP_TRY(hipDeviceSynchronize());
+  VERS_HIP_TRY(hipMemcpy(fix, w.fix, sizeof(fix), hipMemcpyDeviceToHost));
+  uint64_t tot[2];
+  std::memcpy(tot, fix + 4, sizeof(tot));
+  out4[2] = tot[0] + fix[2]; out4[3] = tot[1] + fix[3];
   return VERS_OK;
 }
 
