@@ -23,7 +23,8 @@ def prescan_on():
 
 
 B = 40   # two full groups of 16 and one of 8 on the most probed list
-SHAPES = {"d96": (6000, 96, 12, 6), "d300": (6000, 300, 2, 2)}   # n, d, k, nprobe; d = 300: ld 320 (padded columns), lists of ~47 tiles
+SHAPES = {"d96": (6000, 96, 12, 6), "d300": (6000, 300, 2, 2),   # n, d, k, nprobe; d = 300: ld 320 (padded columns), lists of ~47 tiles
+          "d40": (600, 40, 12, 6)}   # ld 64: a tile is two steps, fewer than the load ring primes; lists of ~50 rows: most items are one tile
 TOP_KS = (1, 10, 48)
 
 

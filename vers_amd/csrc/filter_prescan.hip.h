@@ -13,30 +13,27 @@
 //       (v_mfma_f32_32x32x2_f32), all into ONE accumulator per row half.  RescoreArgs::shadow = 1 is therefore the audited error model as
 //       it stands (pre_bound, prescan.hip.h): nothing is added to it.  The one difference is outside the model: |x|^2 of a DISALLOWED row
 //       enters the k-step as 0 (its NaN would otherwise poison the allowed row 32 further through the 0 * NaN cross term).
-//       The query block sits in LDS as fp16 hi and lo parts of the scaled query, 16 slots per octet (QG 8: eight of them zero); the MFMA's
-//       columns 16 .. 31 repeat 0 .. 15 and are ignored, as in the prescan's narrow blocks.  Loads run kFpRing steps ahead in registers across
-//       tile ends, every one unconditional; |x|^2 of the lane's row and the merge group's shared threshold travel with the step.
+//       The query block (shadow_mma.hip.h's planes) has 16 slots per octet (QG 8: eight of them zero); the MFMA's columns 16 .. 31 repeat
+//       0 .. 15 and are ignored.  The load ring is shadow_mma.hip.h's, written out over the live tiles of a window.
 //       A row is a candidate when its bit in the tile's mask word is set and val's order bits do not exceed the query's threshold: the
 //       smallest known kp-th val of the merge group (bounds32: relaxed agent-scope load per tile, atomicMin when a list's kp-th improves; a
 //       stale value only prunes less).  Keys are (order bits of val, seq_base + row): the unfiltered walk's sequence numbers.
 //       SURVIVORS -> LISTS.  A wave keeps the kp smallest keys of each of its <= 16 queries in registers, one key per lane (filter_item2's
-//       lists), and writes them at the item's end: exact per item, no lock, no shared buffer, no spin.  The path from the accumulator layout
-//       (a lane = one query column x 32 rows) is two-stage.  Stage one is a compare per register against the lane's own threshold and ONE
-//       ballot: after the first tiles nothing passes and the tile costs ~100 VALU instructions.  Only when something passes (or is not
-//       finite) does the wave transpose the tile's vals through a private 4 KiB LDS slice to row-per-lane and run, per live query, the mask
-//       test, a ballot and wave_topk_update for the survivors (a rank sort when the list is still empty and many pass).  The prescan's
+//       lists), and writes them at the item's end: exact per item, no lock, no shared buffer, no spin.  The two-stage path from the
+//       accumulators to the lists is the list offer of shadow_mma.hip.h, through a private 4 KiB LDS slice.  The prescan's
 //       append-and-compact buffer was the alternative: it serves eight waves that share a list across a quad; here a list belongs to one wave
 //       and one short item, so its lock, its `done` counter and its overflow rounds would buy nothing, and per-item lists keep the slot
 //       format and the certificate's "cut rows lie at or above the list's last val" argument per slot.
 //       A non-finite val of an ALLOWED row sets the merge group's qflags word; a disallowed row's val is never looked at.
 //   (2) ivf_rescore_kernel<kRescoreWaves>, launched unchanged on slots of kp keys per (pair, segment) and pj_nq = segments per pair.
 //   (3) filter_fallback_kernel -- the queries the finish queued in fail_list, re-scanned over their probed lists' allowed rows with the
-//       reference's ordered chain (range_exact_kernel's arithmetic) and the chain path's keys: a block per queued query, a wave per live tile,
+//       reference's ordered chain (tile_row_chain, shared with range_exact_kernel) and the chain path's keys: a block per queued query, a wave per live tile,
 //       one list per wave, folded by wave 0.  Returns before its first store when nothing is queued.
 #pragma once
 #include "filter.hip.h"
 #include "ivf_src.hip.h"
 #include "prescan.hip.h"
+#include "shadow_mma.hip.h"
 
 #pragma clang fp contract(off)
 
@@ -44,9 +41,7 @@ namespace vers {
 
 // option "filter_prescan": 0 -- measured
 constexpr int64_t kFilterPrescanDefault = 0;
-constexpr int kFpCbStep = 2;  // column blocks of 16 per step of the prefetch ring: 4 loads, 4 KiB per wave
-constexpr int kFpRing = 4;    // steps in flight: 16 KiB per wave, across tile ends
-constexpr int kFpTrPitch = 17;  // floats per row of a wave's transpose slice (16 queries + 1: conflict-free column reads)
+constexpr int kFpTrPitch = 17;  // floats per row of a wave's transpose slice (shadow_list_offer<16>: 16 queries + 1)
 constexpr int kFpFbWaves = 4;
 // slots of vers_ivf_filter_prescan_stats (u64 each) and, behind them, the finish's u32 count of failed certificates
 constexpr int kFpCalls = 0, kFpFallback = 1, kFpStats = 2;
@@ -96,7 +91,20 @@ static __global__ void filter_pre_begin_kernel(const uint32_t* pj_list, const ui
 }
 
 // ---- (1) the scan ---------------------------------------------------------------------------------------------------------------------
-// Accumulator layout (prescan.hip.h): lane l holds query column n = l & 31 and rows 32 h + 8 (e >> 2) + 4 (l >> 5) + (e & 3) of the tile.
+// shadow_list_offer's lists of a wave: a register per query (filter_item2's), the rows the tile's mask word allows, the walk's sequence numbers
+template <int QG>
+struct FilterPreLists {
+  static constexpr int kUnroll = QG;
+  uint64_t (&list)[QG];
+  uint64_t mw;
+  uint32_t nrows, vseq;  // vseq: lane q holds query q's sequence number of the item's first row
+  int lane;
+  __device__ __forceinline__ bool row_ok(uint32_t row) const { return ((mw >> lane) & 1ull) && row < nrows; }
+  __device__ __forceinline__ uint32_t key_lo(int q, uint32_t row) const { return (uint32_t)__builtin_amdgcn_readlane((int)vseq, q) + row; }
+  __device__ __forceinline__ uint64_t load(int q) const { return list[q]; }
+  __device__ __forceinline__ void store(int q, uint64_t l) const { list[q] = l; }  // (q: a constant once unrolled)
+};
+
 template <int QG, int METRIC, class Src>
 __device__ __forceinline__ void filter_prescan_item(const Src& src, const FilterPreParams& p, uint32_t it, const ItemView<QG>& v, int lane, const f16x8_t* qh,
                                                     float* tr, FilterCounts& fc) {
@@ -112,7 +120,6 @@ __device__ __forceinline__ void filter_prescan_item(const Src& src, const Filter
   }
   const int qi = lane & 15, hf = lane >> 5;
   const bool qlive = qi < (int)v.nq;
-  const bool col = qlive && !(lane & 16);  // the lane's accumulators hold a live query's vals once (columns 16 .. 31 repeat 0 .. 15)
   // per-query constants, lane qi (and its three repeats) = query qi
   uint32_t vslot = 0, vseq = 0;
   uint64_t vout = 0;
@@ -124,89 +131,36 @@ __device__ __forceinline__ void filter_prescan_item(const Src& src, const Filter
   }
   const uint32_t slot0 = (uint32_t)__builtin_amdgcn_readlane((int)vslot, 0);  // (query 0 is live: the unconditional loads of dead lanes read its word)
   if (!qlive) vslot = slot0;
-  uint32_t thrb = qlive ? __hip_atomic_load(p.bounds32 + vslot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;  // order bits; stale = prunes less
-  uint32_t pubb = thrb;  // the smallest value this lane has seen in or sent to the shared word
+  const uint32_t thr0 = qlive ? __hip_atomic_load(p.bounds32 + vslot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;  // order bits; stale = prunes less
+  ShadowList sl{thr0, thr0, 0xFFFFu, 0u};
   const uint32_t kp = p.kp;
   uint64_t list[QG];
 #pragma unroll
   for (int q = 0; q < QG; ++q) list[q] = kKeyMax;
-  uint32_t empty = 0xFFFFu, badmask = 0u;  // wave-uniform: queries whose list holds nothing yet | queries with a non-finite val of an allowed row
 
   const __amdgpu_buffer_rsrc_t rsrc =
       __builtin_amdgcn_make_buffer_rsrc((void*)(p.rows_h + (uint64_t)srow0 * p.ld), 0, (int)(n_tiles * kWave * p.ld * 2u), 0x00020000);
   const uint32_t lane_off = (uint32_t)lane * 16u, tile_bytes = p.ld * 128u;
   const float* xn_item = p.xnorm + srow0;
-  const uint32_t nst = p.ld / (16u * kFpCbStep);  // steps per tile (ld is a multiple of 64)
-  const uint32_t n_cb = p.ld / 16u;
+  const uint32_t nst = p.ld / (16u * kShCbStep);  // steps per tile (ld is a multiple of 64)
   const f16x8_t* const qhi = qh + (size_t)hf * 16 + qi;
-  const f16x8_t* const qlo = qhi + (size_t)n_cb * 32;
-  u32x4 buf[kFpRing][2 * kFpCbStep];
-  float xn[kFpRing];
-  uint32_t gthr[kFpRing];
+  const f16x8_t* const qlo = qhi + (size_t)(p.ld / 16u) * 32;
+  // shadow_mma.hip.h's ring, written out over the live bits of a window, the MFMA step in the loop: as closures of a shared ring they
+  // cost this kernel scalar registers it does not have (said there)
+  u32x4 buf[kShRing][2 * kShCbStep];
+  float xn[kShRing];
+  uint32_t gthr[kShRing];  // the merge group's shared threshold as it came with each step
   f32x16_t acc[2];
 #pragma unroll
   for (int e = 0; e < 16; ++e) acc[0][e] = acc[1][e] = 0.0f;
   uint32_t loaded = 0;
 
-  // end of tile t (of the item): |x|^2 through the matrix core, the threshold, the two-stage path to the lists
+  // end of tile t (of the item): the list offer of shadow_mma.hip.h on the wave's register lists
   auto tile_done = [&](uint32_t t, float xnv, uint32_t g) __attribute__((always_inline)) {
     const uint64_t mw = readlane64(word, (int)(t & 63u));
     const float xs = ((mw >> lane) & 1ull) ? xnv : 0.0f;  // (a disallowed row's |x|^2 is not looked at either)
-    const float nrm = METRIC ? 0.0f : 1.0f;
-    acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(xs, hf == 0 ? nrm : 0.0f, acc[0], 0, 0, 0);
-    acc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(xs, hf == 1 ? nrm : 0.0f, acc[1], 0, 0, 0);
-    if (qlive && g < thrb) thrb = g;
-    if (g < pubb) pubb = g;
-    const float thrf = thrb == 0xFFFFFFFFu ? __builtin_inff() : __uint_as_float(order_bits_to_f32_bits(thrb));
-    bool any = false;
-#pragma unroll
-    for (int h = 0; h < 2; ++h)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) any |= (acc[h][e] <= thrf) || !(__builtin_fabsf(acc[h][e]) < __builtin_inff());
-    if (__ballot(any && col) != 0ull) {  // (wave-uniform) rare after the first tiles
-      __builtin_amdgcn_wave_barrier();  // the slice's readers of the previous tile are done
-      if (!(lane & 16)) {
-#pragma unroll
-        for (int h = 0; h < 2; ++h)
-#pragma unroll
-          for (int e = 0; e < 16; ++e) tr[(32 * h + 8 * (e >> 2) + 4 * hf + (e & 3)) * kFpTrPitch + qi] = acc[h][e];
-      }
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      const uint32_t row = t * kWave + (uint32_t)lane;
-      const bool allowed = ((mw >> lane) & 1ull) && row < v.nrows;
-#pragma unroll
-      for (int q = 0; q < QG; ++q) {
-        if (q < (int)v.nq) {  // wave-uniform
-          const float val = tr[lane * kFpTrPitch + q];
-          const bool fin = __builtin_fabsf(val) < __builtin_inff();
-          if (__ballot(allowed && !fin) != 0ull) badmask |= 1u << q;
-          const uint32_t tb = (uint32_t)__builtin_amdgcn_readlane((int)thrb, q);
-          const uint32_t vb = f32_to_order_bits(val);
-          const bool pass = allowed && fin && vb <= tb;
-          const uint64_t pm = __ballot(pass);
-          if (pm != 0ull) {
-            const uint64_t cand = pass ? (((uint64_t)vb << 32) | ((uint32_t)__builtin_amdgcn_readlane((int)vseq, q) + row)) : kKeyMax;
-            if (((empty >> q) & 1u) && __popcll(pm) > 8) {  // an empty list and many survivors: one sort instead of an ordered insert each
-              list[q] = cand;
-              wave_rank_sort64<true>(list[q], lane);
-            } else {
-              wave_topk_update(list[q], kp, cand, kKeyMax);
-            }
-            empty &= ~(1u << q);
-            const uint32_t nb = (uint32_t)(readlane64(list[q], (int)kp - 1) >> 32);  // 0xFFFFFFFF: the list is not full
-            if (qi == q && nb < thrb) thrb = nb;
-          }
-        }
-      }
-      // a list's kp-th val improved on what the merge group knows: tell its other items
-      if (lane < 16 && qlive && thrb < pubb) {
-        atomicMin(p.bounds32 + vslot, thrb);
-        pubb = thrb;
-      }
-    }
-#pragma unroll
-    for (int e = 0; e < 16; ++e) acc[0][e] = acc[1][e] = 0.0f;
+    shadow_tile_norm(acc, xs, METRIC ? 0.0f : 1.0f, lane, qlive, g, sl);
+    shadow_list_offer<16>(acc, t, lane, qlive, v.nq, kp, tr, p.bounds32 + vslot, sl, FilterPreLists<QG>{list, mw, v.nrows, vseq, lane});
   };
 
   for (uint32_t w0 = 0;; w0 += kWave) {
@@ -216,28 +170,28 @@ __device__ __forceinline__ void filter_prescan_item(const Src& src, const Filter
       const uint32_t n_steps = n_live * nst;
       uint64_t li = live, lc = live;  // live tiles not yet issued / not yet consumed, the current one included
       uint32_t ti = w0 + (uint32_t)__ffsll((unsigned long long)li) - 1u, ci = 0;  // (tile, step) the next issue fetches
-      auto issue_next = [&](u32x4 (&r)[2 * kFpCbStep], float& x, uint32_t& g) __attribute__((always_inline)) {
+      auto issue_next = [&](u32x4 (&r)[2 * kShCbStep], float& x, uint32_t& g) __attribute__((always_inline)) {
         x = xn_item[ti * kWave + (uint32_t)lane];
         // the shared threshold is consumed once per tile, with the step that completes it; on the others every lane reads ONE word (prescan_item_g)
         g = __hip_atomic_load(p.bounds32 + (ci + 1 >= nst ? vslot : slot0), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const uint32_t soff = ti * tile_bytes + ci * (kFpCbStep * 2048u);
+        const uint32_t soff = ti * tile_bytes + ci * (kShCbStep * 2048u);
 #pragma unroll
-        for (int i = 0; i < 2 * kFpCbStep; ++i) r[i] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, lane_off, soff + (uint32_t)i * 1024u, kPreAux);
+        for (int i = 0; i < 2 * kShCbStep; ++i) r[i] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, lane_off, soff + (uint32_t)i * 1024u, kPreAux);
         if (ci + 1 < nst) ++ci;
         else if (li & (li - 1)) { li &= li - 1; ci = 0; ti = w0 + (uint32_t)__ffsll((unsigned long long)li) - 1u; }  // else: stay on the last step (a harmless re-read)
       };
 #pragma unroll
-      for (int b = 0; b < kFpRing - 1; ++b) issue_next(buf[b], xn[b], gthr[b]);
+      for (int b = 0; b < kShRing - 1; ++b) issue_next(buf[b], xn[b], gthr[b]);
       uint32_t cc = 0;  // step being consumed
-      for (uint32_t s0 = 0; s0 < n_steps; s0 += kFpRing) {
+      for (uint32_t s0 = 0; s0 < n_steps; s0 += kShRing) {
 #pragma unroll
-        for (int b = 0; b < kFpRing; ++b) {
-          issue_next(buf[(b + kFpRing - 1) % kFpRing], xn[(b + kFpRing - 1) % kFpRing], gthr[(b + kFpRing - 1) % kFpRing]);
+        for (int b = 0; b < kShRing; ++b) {
+          issue_next(buf[(b + kShRing - 1) % kShRing], xn[(b + kShRing - 1) % kShRing], gthr[(b + kShRing - 1) % kShRing]);
           if (s0 + b < n_steps) {  // uniform
 #pragma unroll
-            for (int k = 0; k < kFpCbStep; ++k) {
-              const f16x8_t bh = qhi[(size_t)(cc * kFpCbStep + k) * 32];
-              const f16x8_t bl = qlo[(size_t)(cc * kFpCbStep + k) * 32];
+            for (int k = 0; k < kShCbStep; ++k) {
+              const f16x8_t bh = qhi[(size_t)(cc * kShCbStep + k) * 32];
+              const f16x8_t bl = qlo[(size_t)(cc * kShCbStep + k) * 32];
 #pragma unroll
               for (int h = 0; h < 2; ++h) {
                 const f16x8_t ar = __builtin_bit_cast(f16x8_t, buf[b][2 * k + h]);
@@ -268,7 +222,7 @@ __device__ __forceinline__ void filter_prescan_item(const Src& src, const Filter
 #pragma unroll
   for (int q = 0; q < QG; ++q)
     if (q < (int)v.nq && lane < (int)kp) reinterpret_cast<uint64_t*>(readlane64(vout, q))[lane] = list[q];  // ascending, kKeyMax padded
-  if (lane < 16 && qlive && ((badmask >> lane) & 1u)) p.qflags[vslot] = 1u;
+  if (lane < 16 && qlive && ((sl.bad >> lane) & 1u)) p.qflags[vslot] = 1u;
 }
 
 template <int QG, int METRIC, class Src>
@@ -299,18 +253,10 @@ __global__ __launch_bounds__(kWave * kWavesPerBlock) void filter_prescan_kernel(
     ItemView<QG> v;
     src.get(it, v);  // v.qb / v.nq are the same for the four items of the quad
     __syncthreads();  // the previous quad's readers are done with the LDS block
-    for (uint32_t i = threadIdx.x; i < n_cb * 32u; i += kWave * kWavesPerBlock) {
-      const uint32_t cb = i >> 5, oct = (i >> 4) & 1u, q = i & 15u;
-      f16x8_t hi, lo;
+    shadow_stage_queries<16, true>(qh, n_cb, [&](uint32_t c0, uint32_t q, float (&y)[8]) __attribute__((always_inline)) {
 #pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const float y = q < (uint32_t)QG ? scale * v.qb[(size_t)(cb * 16u + oct * 8u + (uint32_t)j) * QG + q] : 0.0f;
-        hi[j] = (_Float16)y;
-        lo[j] = (_Float16)(y - (float)hi[j]);
-      }
-      qh[i] = hi;
-      qh[(size_t)n_cb * 32u + i] = lo;
-    }
+      for (int j = 0; j < 8; ++j) y[j] = q < (uint32_t)QG ? scale * v.qb[(size_t)(c0 + (uint32_t)j) * QG + q] : 0.0f;
+    });
     __syncthreads();
     if (v.nrows == 0) continue;  // padding item (wave-uniform; barriers are outside)
     filter_prescan_item<QG, METRIC>(src, p, it, v, lane, qh, tr, fc);
@@ -350,24 +296,7 @@ __global__ __launch_bounds__(kWave * kFpFbWaves) void filter_fallback_kernel(Fil
         if (mw == 0ull) continue;
         const uint32_t row = t * kWave + (uint32_t)lane;
         const bool allowed = ((mw >> lane) & 1ull) && row < len;
-        // the reference's ordered chain over the f32 tile (range_exact_kernel's: 4-column groups 1 KiB apart, one 16-byte load each)
-        const f32x4* const xp = reinterpret_cast<const f32x4*>(a.rows + (uint64_t)((srow0 >> 6) + t) * 64ull * a.ld) + lane;
-        float acc = 0.0f;
-#pragma unroll 8
-        for (uint32_t c = 0; c < a.ld / 4; ++c) {
-          const f32x4 x4 = xp[(uint64_t)c * 64];
-          const f32x4 q4 = q4p[c];
-#pragma unroll
-          for (int u = 0; u < 4; ++u) {
-            if (METRIC == 0) {
-              const float d = __fsub_rn(x4[u], q4[u]);
-              acc = __fadd_rn(acc, __fmul_rn(d, d));
-            } else {
-              acc = __fadd_rn(acc, __fmul_rn(x4[u], q4[u]));
-            }
-          }
-        }
-        const float dist = METRIC == 0 ? acc : __fsub_rn(1.0f, acc);
+        const float dist = tile_row_chain<METRIC>(reinterpret_cast<const f32x4*>(a.rows + (uint64_t)((srow0 >> 6) + t) * 64ull * a.ld) + lane, q4p, a.ld);
         nan_seen |= allowed && (dist != dist);
         wave_topk_update(list, a.top_k, allowed ? make_key(dist, seq0 + row) : kKeyMax, kKeyMax);
       }

@@ -37,6 +37,7 @@
 #include "ivf_src.hip.h"
 #include "prescan.hip.h"
 #include "range.hip.h"
+#include "shadow_mma.hip.h"
 
 #pragma clang fp contract(off)
 
@@ -93,8 +94,6 @@ struct RangeExactParams {
 // option "range_prescan": 0 -- measured: the filter leaves hardly more than the hits, but the finish's lane-per-candidate
 // chains cost more than the chain passes they replace as soon as a query has ~100 results; count + fill won only at ~10 per query.
 constexpr int64_t kRangePrescanDefault = 0;
-constexpr int kRpCbStep = 2;  // column blocks of 16 per step of the prefetch ring: 4 loads, 4 KiB per wave
-constexpr int kRpRing = 4;    // steps in flight: 8 column blocks, 16 KiB per wave, across tile ends
 inline size_t range_prefilter_lds_bytes(uint32_t ld) { return (size_t)(ld / 16u) * 1024u + 16u; }  // query block (hi | lo columns) + hand-out word
 inline size_t range_exact_lds_bytes(uint32_t ld) { return (size_t)kWavesPerBlock * ((size_t)ld * sizeof(float) + kWave * (sizeof(uint32_t) + sizeof(uint64_t))); }
 inline uint32_t range_prefilter_grid(int n_cu, uint32_t ld, uint32_t items) {  // 2 blocks per CU (176 .. 186 registers a wave: 32 KiB of loads in flight per SIMD), 1 where two query blocks exceed LDS
@@ -149,11 +148,8 @@ static __global__ void range_pair_tiles_kernel(const uint32_t* pj_list, const ui
 }
 
 // ---- (1) the pre-filter -----------------------------------------------------------------------------------------------------------------
-// One work item: a wave walks the 64-row tiles of its row segment.  A step = kRpCbStep column blocks: per column block one ds_read_b128 of
-// the B operand and two 16-byte non-temporal loads of the shadow's pieces (cb, h = 0 / 1) -- already in the A operand's order -- and two
-// MFMAs into the two 16-register accumulators of the tile's row halves, so every LDS operand feeds both.  The loads run kRpRing steps ahead
-// in registers, across tile ends, every one unconditional (steps past the end re-read the last: scan_item says why); |x|^2 of the lane's
-// row travels with the step (no load outside the ring).
+// One work item: a wave walks the 64-row tiles of its row segment through the load ring of shadow_mma.hip.h.  Per column block one
+// ds_read_b128 of the B operand and two MFMAs into the two 16-register accumulators of the tile's row halves, so every LDS operand feeds both.
 // Accumulator layout (prescan.hip.h): lane l holds query column n = l & 31 and rows 32 h + 8 (e >> 2) + 4 (l >> 5) + (e & 3) of the tile.
 template <int QG, int METRIC, class Src>
 __device__ __forceinline__ void range_prefilter_item(const Src& src, const RangePreParams& p, uint32_t it, const ItemView<QG>& v, int lane, const f16x8_t* qh,
@@ -172,30 +168,16 @@ __device__ __forceinline__ void range_prefilter_item(const Src& src, const Range
   const uint32_t srow0 = src.storage_row(it);
   const __amdgpu_buffer_rsrc_t rsrc =
       __builtin_amdgcn_make_buffer_rsrc((void*)(p.rows_h + (uint64_t)srow0 * p.ld), 0, (int)(n_tiles * kWave * p.ld * 2u), 0x00020000);
-  const uint32_t lane_off = (uint32_t)lane * 16u, tile_bytes = p.ld * 128u;
-  const float* xn_item = p.xnorm + srow0;
-  const uint32_t nst = p.ld / (16u * kRpCbStep);  // steps per tile (ld is a multiple of 64)
-  const uint32_t n_steps = n_tiles * nst;
-  u32x4 buf[kRpRing][2 * kRpCbStep];
-  float xn[kRpRing];
-  uint32_t ti = 0, ci = 0;  // (tile, step) the next issue fetches
-  auto issue_next = [&](u32x4 (&r)[2 * kRpCbStep], float& x) {
-    x = xn_item[ti * kWave + (uint32_t)lane];
-    const uint32_t soff = ti * tile_bytes + ci * (kRpCbStep * 2048u);
-#pragma unroll
-    for (int i = 0; i < 2 * kRpCbStep; ++i) r[i] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, lane_off, soff + (uint32_t)i * 1024u, kPreAux);
-    if (ci + 1 < nst) ++ci;
-    else if (ti + 1 < n_tiles) { ci = 0; ++ti; }
-  };
-#pragma unroll
-  for (int b = 0; b < kRpRing - 1; ++b) issue_next(buf[b], xn[b]);
+  ShadowRing ring{rsrc, p.xnorm + srow0, p.ld * 128u, p.ld / (16u * kShCbStep), 0u, n_tiles, 1u};  // every tile of the item
+  auto extra = [](int, bool) __attribute__((always_inline)) {};  // (the radius does not move: no word travels with a step)
+  ring.prime(lane, extra);
   f32x16_t acc[2];
 #pragma unroll
   for (int e = 0; e < 16; ++e) acc[0][e] = acc[1][e] = 0.0f;
   uint32_t ccount = 0;  // lanes 0 .. 15: the query's candidates in the item so far
 
   // end of a tile: hi + lo (the lanes of column n and n + 16), + |x|^2, the comparison, the (query, tile) word
-  auto tile_done = [&](uint32_t t, float xnv) {
+  auto tile_done = [&](uint32_t t, float xnv, int) __attribute__((always_inline)) {
     uint32_t w[2] = {0u, 0u};  // candidate bits of the lane's rows of each half: bit = row within the half
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
@@ -224,25 +206,15 @@ __device__ __forceinline__ void range_prefilter_item(const Src& src, const Range
     }
   };
 
-  uint32_t tc = 0, cc = 0;  // (tile, step) being consumed
-  for (uint32_t s0 = 0; s0 < n_steps; s0 += kRpRing) {
+  auto mma = [&](uint32_t cc, const u32x4 (&r)[2 * kShCbStep]) __attribute__((always_inline)) {
 #pragma unroll
-    for (int b = 0; b < kRpRing; ++b) {
-      issue_next(buf[(b + kRpRing - 1) % kRpRing], xn[(b + kRpRing - 1) % kRpRing]);
-      if (s0 + b < n_steps) {  // uniform
-#pragma unroll
-        for (int k = 0; k < kRpCbStep; ++k) {
-          const f16x8_t bq = qh[(size_t)(cc * kRpCbStep + k) * kWave + lane];
-          acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8_t, buf[b][2 * k]), bq, acc[0], 0, 0, 0);
-          acc[1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8_t, buf[b][2 * k + 1]), bq, acc[1], 0, 0, 0);
-        }
-        if (++cc == nst) {
-          cc = 0;
-          tile_done(tc++, xn[b]);
-        }
-      }
+    for (int k = 0; k < kShCbStep; ++k) {
+      const f16x8_t bq = qh[(size_t)(cc * kShCbStep + k) * kWave + lane];
+      acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8_t, r[2 * k]), bq, acc[0], 0, 0, 0);
+      acc[1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8_t, r[2 * k + 1]), bq, acc[1], 0, 0, 0);
     }
-  }
+  };
+  ring.run(n_tiles * ring.nst, lane, extra, mma, tile_done);
   if (lane < 16 && qlive) p.cand[slot] = ccount;  // (one item per slot: a plain store)
   tested += (unsigned long long)v.nrows * v.nq;
   cands += wave_sum_u32(lane < 16 && qlive ? ccount : 0u);
@@ -277,14 +249,12 @@ __global__ __launch_bounds__(kWave * kWavesPerBlock) void range_prefilter_kernel
     __syncthreads();  // the previous quad's readers are done with the LDS block
     for (uint32_t i = threadIdx.x; i < n_cb * kWave; i += kWave * kWavesPerBlock) {
       const uint32_t cb = i >> 6, n = i & 31u, oct = (i >> 5) & 1u, q = n & 15u;
-      f16x8_t o;
+      float y[8];
 #pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const float y = q < (uint32_t)QG ? scale * v.qb[(size_t)(cb * 16u + oct * 8u + (uint32_t)j) * QG + q] : 0.0f;
-        const _Float16 hi = (_Float16)y;
-        o[j] = n < 16u ? hi : (_Float16)(y - (float)hi);
-      }
-      qh[i] = o;
+      for (int j = 0; j < 8; ++j) y[j] = q < (uint32_t)QG ? scale * v.qb[(size_t)(cb * 16u + oct * 8u + (uint32_t)j) * QG + q] : 0.0f;
+      f16x8_t hi, lo;
+      shadow_split8(y, hi, lo);
+      qh[i] = n < 16u ? hi : lo;
     }
     __syncthreads();
     if (v.nrows == 0) continue;  // padding item (wave-uniform; barriers are outside)
@@ -373,24 +343,7 @@ __global__ __launch_bounds__(kWave * kWavesPerBlock) void range_exact_kernel(Ran
           const uint32_t bit = nth_set_bit64(wds[wi], c - (wi ? pre[wi - 1u] : 0u));
           const uint32_t row = (t0 + wi) * kWave + bit;  // within the segment
           const uint32_t srow = srow0 + row;
-          // the reference's ordered chain over the f32 tile (ivf_rescore_kernel's: 4-column groups 1 KiB apart, one 16-byte load each)
-          const f32x4* const xp = reinterpret_cast<const f32x4*>(a.rows + (uint64_t)(srow >> 6) * 64ull * a.ld) + (srow & 63u);
-          float acc = 0.0f;
-#pragma unroll 8
-          for (uint32_t j = 0; j < a.ld / 4; ++j) {
-            const f32x4 x4 = xp[(uint64_t)j * 64];
-            const f32x4 q4 = q4p[j];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-              if (METRIC == 0) {
-                const float t = __fsub_rn(x4[u], q4[u]);
-                acc = __fadd_rn(acc, __fmul_rn(t, t));
-              } else {
-                acc = __fadd_rn(acc, __fmul_rn(x4[u], q4[u]));
-              }
-            }
-          }
-          const float dist = METRIC == 0 ? acc : __fsub_rn(1.0f, acc);
+          const float dist = tile_row_chain<METRIC>(reinterpret_cast<const f32x4*>(a.rows + (uint64_t)(srow >> 6) * 64ull * a.ld) + (srow & 63u), q4p, a.ld);
           const bool hit = have && dist <= rad;
           const uint64_t m = __ballot(hit);
           if constexpr (!FILL) {
